@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- differentiable cell-steps/s (forward + adjoint) of the time-fused HIP stepper.
 
-    python bench.py --gpus N --steps K --warmup W [--workload macro|micro]
+    python bench.py --gpus N --steps K --warmup W [--workload macro|micro] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input: a full differentiable rollout
 (forward sweep writing the Jacobian tape + reverse sweep reading it back) of BASELINE.json configs[1]
@@ -57,7 +57,12 @@ def parse():
                     "(roofline.traffic / issue_side then quote the committed passes under profiles/, fingerprint permitting)")
     ap.add_argument("--also-replicas", type=int, default=0, help="N > 1: replicas per rank of the config 5 sub-record (default 256); "
                     "giving it forces the sub-record even when the headline's shape is overridden (tests)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="behind the timed passes, write what the last one handed its "
+                    "caller (rank 0's shard: final state, gradients, loss) as DIR/<name>.npy, at most 64 MB in all (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(n):
@@ -195,6 +200,10 @@ class MacroWorkload:
         g_u0 = ops.macro_state_from_ru_bwd(self.r0, self.u0, g_y0, g_r0, self.um)
         return loss, g_r0, g_u0
 
+    def outputs(self, g_a, g_b):
+        """what the last pass handed its caller: the final state (r, y, u, ueq) and d loss / d (r0, u0)"""
+        return {"r_T": self.out[0], "y_T": self.out[1], "u_T": self.out[2], "ueq_T": self.out[3], "g_r0": g_a, "g_u0": g_b}
+
     def parity_check(self, g_a, g_b):
         """The last timed pass of THIS run against the oracle's run of the same lanes (cpu_baseline keeps its first pass): final
         (r, u) and d loss / d (r0, u0) of lanes 0 .. cores - 1, norm-relative per tensor."""
@@ -309,6 +318,10 @@ class MicroWorkload:
             e[3].record()
             self.ev.append(e)
         return loss, g_p0, g_v0
+
+    def outputs(self, g_a, g_b):
+        """the final (p, v) and d loss / d (p0, v0) of the last pass"""
+        return {"p_T": self.out[0], "v_T": self.out[1], "g_p0": g_a, "g_v0": g_b}
 
     def parity_check(self, g_a, g_b):
         """As MacroWorkload.parity_check: final (p, v) and d loss / d (p0, v0) of lanes 0 .. cores - 1."""
@@ -434,6 +447,10 @@ class ItscpMacroWorkload:
             e[3].record()
             self.ev.append(e)
         return loss.detach(), self.action.grad, self.action.grad
+
+    def outputs(self, g_a, g_b):
+        """every replica's reward and d loss / d action (loss = -sum reward) of the last pass"""
+        return {"reward": self.reward, "g_action": g_a}
 
     def parity_check(self, g_a, g_b):
         """Replica 0 of the last timed pass against the oracle's episode: reward and d reward / d action."""
@@ -572,6 +589,10 @@ class ItscpHybridWorkload:
     def dropped_replicas(self):
         d = getattr(self, "dropped", None)
         return 0 if d is None else int(d)
+
+    def outputs(self, g_a, g_b):
+        """every replica's reward, d loss / d action (loss = -sum reward; non-finite rows dropped to zero) and counts [R][4]"""
+        return {"reward": self.reward, "g_action": g_a, "counts": self.counts}
 
     def parity_check(self, g_a, g_b):
         """Replica 0 of the last timed pass against the oracle's episode of the same schedule and action: reward, number of
@@ -717,7 +738,7 @@ class StubWorkload:
     def __init__(self, dev, rank, R, _n, _t):
         self.L, self.N, self.T, self.rank = R, 4, 1, rank
         self.units = R * 4
-        self.action = (torch.arange(R * 3, dtype=torch.float32, device=dev).reshape(R, 3) + 100.0 * rank).requires_grad_(True)
+        self.action = torch.arange(R * 3, dtype=torch.float32, device=dev).reshape(R, 3) + 100.0 * rank
         self.err = torch.zeros(4, dtype=torch.int32, device=dev)
         self.ev = []
         self.passes = 0
@@ -729,13 +750,17 @@ class StubWorkload:
         self.passes += 1
         if os.environ.get("DHTS_STUB_FAIL_RANK") == str(self.rank) and self.passes == 2:
             os._exit(7)
-        self.action.grad = None
+        # d loss / d action written out: autograd's first backward counts the devices of every backend, which starts the HIP runtime
+        # (it opens the GPU) even in a rank that sees none -- and the stub's ranks are host-only
         loss = (self.action * self.action).sum()
-        loss.backward()
-        return loss.detach(), self.action.grad, self.action.grad
+        grad = 2.0 * self.action
+        return loss, grad, grad
 
     def cpu_baseline(self, seconds=0.0):
         return None
+
+    def outputs(self, g_a, g_b):
+        return {"g_action": g_a}
 
     def parity_check(self, g_a, g_b):
         return None
@@ -1021,6 +1046,29 @@ def collective_run(w, steps, warmup, shared_grad, dev, record):
     return elapsed, flat, parts, (g_a, g_b)
 
 
+DUMP_BUDGET_B = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` as <path>/<name>.npy, float32, or float64 where the path computed float64 (integer outputs
+    widened to float64), so that two builds can be compared output for output on the same seeded inputs.  Beyond
+    DUMP_BUDGET_B in all, each array keeps a fixed sample of its rows (numpy default_rng(0), in order): the same rows in every
+    run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = np.atleast_1d(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t))
+        host[name] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.dtype != np.float64 else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET_B:
+            a = a.reshape(-1) if a.shape[0] == 1 else a
+            keep = max(1, a.shape[0] * DUMP_BUDGET_B // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def replica_sweep(dev, sizes=(256, 512, 1024, 2048), passes=3):
     """Config 4's network at several replicas per GPU, ONE instance (2 048 replicas built once, prefixes timed): the saturated
     throughput of the hybrid path on one GPU and the one-GPU time of config 5's whole 2 048-replica problem (the strong-scaling
@@ -1111,6 +1159,9 @@ def main():
         _L.lib().dhts_set_option(_L.OPT_MACRO_FWD_ROTATE, chosen)
         rotate_rec = {"ms_per_pass_with": ms[1], "ms_per_pass_without": ms[0], "chosen": chosen}
     elapsed, flat, parts, (g_a, g_b) = collective_run(w, args.steps, args.warmup, shared_grad, dev, record=not stub)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on this workload (the parity check's extra pass would overwrite it); loss: all-reduced over ranks
+        dump_outputs(args.dump_outputs, dict(w.outputs(g_a, g_b), loss=flat[-1:]))
 
     # N > 1, the driver's default command: BASELINE config 5 behind the headline -- the itscp hybrid network, 256 replicas per rank
     # (2 048 over 8 GPUs), d reward / d (shared signal schedule) [45] || reward all-reduced once per pass.  Every rank runs it.

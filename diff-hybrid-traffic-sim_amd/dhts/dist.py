@@ -151,7 +151,9 @@ def barrier():
         if dist.get_backend() == "nccl":
             dist.barrier(device_ids=[torch.cuda.current_device()])
         else:
-            dist.barrier()
+            # an all-reduce of one host float is the same rendezvous: dist.barrier() first looks for an accelerator
+            # (torch._C._get_accelerator), which starts the HIP runtime -- and opens the GPU -- in every host-only rank
+            dist.all_reduce(torch.zeros(1))
 
 
 def shutdown():

@@ -159,6 +159,8 @@ def test_two_rank_gloo_replica_sharding(oracle, tmp_path):
 def _run_bench(args, extra_env=None, timeout=240):
     import time
     env = dict(os.environ, OMP_NUM_THREADS="1", DHTS_DIST_BACKEND="gloo")       # (by name: eight ranks never fit a test box's GPUs)
+    # host-only ranks on any machine: the stub needs no device, and on a GPU box eight ranks would each open the same GPU
+    env["HIP_VISIBLE_DEVICES"] = "-1"
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)                       # no launcher environment: bench.py starts its own ranks
     env.update(extra_env or {})
