@@ -635,6 +635,12 @@ class DeviceHybridTables:
             v.n_replica_tables = int(n_replicas)
         return v
 
+    def schedules(self):
+        """The uploaded inflow schedules read back to the host: float64 [R][T][L], one per replica of this batch (a `first(n)`
+        view gives its n), or [1][T][L] for tables shared by all replicas."""
+        s = self._keep[8].cpu().numpy().reshape(-1, self.T, self.n_lanes)
+        return s[:self.n_replica_tables] if self.n_replica_tables else s
+
     def set_draws(self, draws):
         """A fresh stream of admission draws for the next episode (micro source lanes; same length as the uploaded one)."""
         import numpy as np
