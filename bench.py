@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- differentiable cell-steps/s (forward + adjoint) of the time-fused HIP stepper.
 
-    python bench.py --gpus N --steps K --warmup W [--workload macro|micro] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload macro|micro] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input: a full differentiable rollout
 (forward sweep writing the Jacobian tape + reverse sweep reading it back) of BASELINE.json configs[1]
@@ -14,8 +14,12 @@ Every rank owns its own shard of independent lanes / replicas (weak scaling: the
 configuration above), there is no data-path collective, and the flat [d loss / d theta_shared || loss] buffer is
 all-reduced over RCCL once per pass.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set up, warm up, time the K steps, write --dump-outputs, print.  --full adds
+everything else: the counter passes of this run (N = 1), the sub-records under "also" (N = 1: configs 3 and 4, the stepwise network,
+the replica sweep, config 2 x 8 lanes; N > 1: config 5), cpu_baseline and parity_check against the oracle.
+
 roofline.achieved / frac are priced in the bytes the dominant kernel MOVES (its compact tape, checked against PMC passes:
-at N = 1 the run takes them itself before it touches the GPU -- live_counters -- and falls back to the ones under profiles/); the reference's algorithmic tape bytes (48 B per cell-step, 32 B per vehicle-step) divided by
+at N = 1 a --full run takes them itself before it touches the GPU -- live_counters -- otherwise the ones under profiles/ are quoted); the reference's algorithmic tape bytes (48 B per cell-step, 32 B per vehicle-step) divided by
 the same time are reported beside them as achieved_algorithmic / frac_algorithmic.
 """
 import argparse
@@ -50,12 +54,15 @@ def parse():
     ap.add_argument("--lanes", type=int, default=0, help="override lanes per GPU")
     ap.add_argument("--cells", type=int, default=0, help="override cells / vehicles per lane")
     ap.add_argument("--time-steps", type=int, default=0, help="override simulated time steps per rollout")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the sub-records of the default run (N = 1: configs 3 and 4, the stepwise "
-                    "network, the replica sweep, config 2 x 8 lanes; N > 1: config 5)")
-    ap.add_argument("--no-live-counters", action="store_true", help="N = 1: skip the rocprofv3 --pmc child passes taken before the timed region "
-                    "(roofline.traffic / issue_side then quote the committed passes under profiles/, fingerprint permitting)")
-    ap.add_argument("--also-replicas", type=int, default=0, help="N > 1: replicas per rank of the config 5 sub-record (default 256); "
+    ap.add_argument("--full", action="store_true", help="beside the headline, everything else the benchmark measures and checks: the "
+                    "counter passes of this run (N = 1), the sub-records (N = 1: configs 3 and 4, the stepwise network, the replica "
+                    "sweep, config 2 x 8 lanes; N > 1: config 5), the CPU baseline and the parity check against the oracle.  Without "
+                    "it a run sets up, warms up, times the steps, dumps (--dump-outputs) and prints the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the sub-records")
+    ap.add_argument("--no-live-counters", action="store_true", help="--full, N = 1: skip the rocprofv3 --pmc child passes taken before the "
+                    "timed region (roofline.traffic / issue_side then quote the committed passes under profiles/, fingerprint permitting)")
+    ap.add_argument("--also-replicas", type=int, default=0, help="--full, N > 1: replicas per rank of the config 5 sub-record (default 256); "
                     "giving it forces the sub-record even when the headline's shape is overridden (tests)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="behind the timed passes, write what the last one handed its "
                     "caller (rank 0's shard: final state, gradients, loss) as DIR/<name>.npy, at most 64 MB in all (dump_outputs)")
@@ -1107,9 +1114,9 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))        # before any GPU call: the children own the devices
-    if (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload != "stub" and not args.no_live_counters
+    if (args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload != "stub" and not args.no_live_counters
             and not (args.lanes or args.cells or args.time_steps) and not under_profiler() and torch.cuda.device_count() > 0):
-        # child processes; this one has not touched the GPU yet.  The default run takes them for its sub-records' workloads too
+        # child processes; this one has not touched the GPU yet.  The full run takes them for its sub-records' workloads too
         deadline = time.time() + 180.0
         for key in ((args.workload,) if args.no_also or args.workload != "macro" else ("macro", "micro", "itscp_hybrid", "itscp_stepwise")):
             if not live_counters(key, deadline):
@@ -1163,10 +1170,10 @@ def main():
         # before anything else runs on this workload (the parity check's extra pass would overwrite it); loss: all-reduced over ranks
         dump_outputs(args.dump_outputs, dict(w.outputs(g_a, g_b), loss=flat[-1:]))
 
-    # N > 1, the driver's default command: BASELINE config 5 behind the headline -- the itscp hybrid network, 256 replicas per rank
+    # N > 1 with --full: BASELINE config 5 behind the headline -- the itscp hybrid network, 256 replicas per rank
     # (2 048 over 8 GPUs), d reward / d (shared signal schedule) [45] || reward all-reduced once per pass.  Every rank runs it.
     second = None
-    if world > 1 and not args.no_also and ((args.workload == "macro" and (default_shape or args.also_replicas)) or stub):
+    if world > 1 and args.full and not args.no_also and ((args.workload == "macro" and (default_shape or args.also_replicas)) or stub):
         if not stub:
             kernels_head = kernel_records(w)           # (the events and the census need the tape: read them before it goes)
             census_head = w.tape_census() if rank == 0 else None
@@ -1254,7 +1261,7 @@ def main():
             out["collective"] = collective
         if second is not None:
             out["also"] = [second]
-        if world == 1:
+        if world == 1 and args.full:
             if args.workload == "macro" and default_shape and not args.no_also:
                 del w.tape            # 24 GB back to the allocator before the other workloads take theirs
                 torch.cuda.empty_cache()

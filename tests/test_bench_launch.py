@@ -107,11 +107,11 @@ def test_two_ranks_hybrid_replicas_shared_schedule(cuda):
 
 @pytest.mark.gpu
 def test_two_ranks_default_command_appends_config5(cuda):
-    """What `bench.py --gpus N` adds for N > 1: behind the config-2 loop every rank runs the itscp hybrid network (here 8 replicas
+    """What `bench.py --gpus N --full` adds for N > 1: behind the config-2 loop every rank runs the itscp hybrid network (here 8 replicas
     per rank instead of 256) with the all-reduce of [d reward / d action (45) || reward]; the line names the backend and every
     rank's device."""
     two = run_bench(["--gpus", "2", "--workload", "macro", "--lanes", "64", "--time-steps", "50", "--steps", "3", "--warmup", "1",
-                     "--no-cpu-baseline", "--also-replicas", "8"], env={"DHTS_DIST_BACKEND": "gloo"})
+                     "--no-cpu-baseline", "--also-replicas", "8", "--full"], env={"DHTS_DIST_BACKEND": "gloo"})
     assert two.returncode == 0, two.stderr[-3000:]
     b = last_json(two.stdout)
     col = b["collective"]

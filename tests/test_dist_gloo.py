@@ -174,7 +174,7 @@ def test_bench_launcher_eight_ranks_over_gloo():
     all-reduce of [gradient || loss], max-over-ranks timing, the gather of every rank's part and rank 0's ONE JSON line relayed
     by the parent -- the stub workload on CPU, collectives over gloo (the launcher and collective code of the 8-GPU run)."""
     import json
-    p, _ = _run_bench(["--workload", "stub", "--gpus", "8", "--steps", "3", "--warmup", "1"])
+    p, _ = _run_bench(["--workload", "stub", "--gpus", "8", "--steps", "3", "--warmup", "1", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout                        # one line, from rank 0
@@ -189,7 +189,7 @@ def test_bench_launcher_eight_ranks_over_gloo():
     # who took part: the backend by name and one identity per rank (on a GPU node: name, PCI bus id, uuid of eight distinct devices)
     col = o["collective"]
     assert col["backend"] == "gloo" and col["world"] == 8 and [d["rank"] for d in col["devices"]] == list(range(8))
-    # N > 1 appends the second workload (on GPUs: BASELINE config 5, 256 hybrid replicas per rank) with its own per-pass all-reduce
+    # N > 1 with --full appends the second workload (on GPUs: BASELINE config 5, 256 hybrid replicas per rank) with its own per-pass all-reduce
     # of [gradient || loss]: here the stub at another shape (3 x 3 per rank), timed and checked the same way
     assert len(o["also"]) == 1
     sec = o["also"][0]
@@ -198,6 +198,16 @@ def test_bench_launcher_eight_ranks_over_gloo():
     want2 = [float(sum((k + 100.0 * r) ** 2 for k in range(9))) for r in range(8)]
     assert chk2["rank_parts"] == want2 and chk2["buffer_floats"] == 4
     assert chk2["reduced"] == chk2["sum_of_rank_parts"] == sec["loss_last_pass"] and chk2["grad_max_abs_diff"] == 0.0
+
+
+def test_bench_plain_run_has_no_sub_record():
+    """Without --full the line carries the headline alone: the launcher, the timed passes and the all-reduce check, no `also`."""
+    import json
+    p, _ = _run_bench(["--workload", "stub", "--gpus", "2", "--steps", "2", "--warmup", "1"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    o = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert o["n_gpus"] == 2 and o["steps"] == 2 and len(o["allreduce_check"]["rank_parts"]) == 2
+    assert "also" not in o
 
 
 def test_more_ranks_than_gpus_is_refused_unless_gloo_is_named(monkeypatch):
