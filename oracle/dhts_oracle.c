@@ -223,6 +223,37 @@ void oracle_arz_flux_prime(const double q0[4], double u_max, float fp[4]) {
     flux_prime(&Q0, u_max, fp);
 }
 
+static inline float dot2(float a0, float b0, float a1, float b1);
+static void matmul22(const float a[4], const float b[4], float o[4]);
+
+/* Batch form of the three entry points above plus the float32 products and the CFL test, for sweeps of millions of
+ * interfaces: in [n][9] = rL yL uL ueqL rR yR uR ueqR u_max (the layout of dhts.ops.arz_interface_batch).  Out (row-major, n rows):
+ * case [n], q0 [n][4], speed [n][2], flux [n][2] = (r u, y u) of Q_0 (_arz.py:94-101), dL dR fp A B [n][4] float32 with
+ * A = fp @ dL, B = fp @ dR as np.matmul forms them (dmacro_lane.py:126-129), cfl_bad [n] = the assert of
+ * _macro_lane.py:141-146 failing for this interface. */
+void oracle_arz_batch(long n, const double *in, double dt, double dx, int *case_ind, double *q0, double *speed, double *flux,
+                      float *dL, float *dR, float *fp, float *A, float *B, int *cfl_bad) {
+    #pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; i++) {
+        const double *x = in + 9 * i;
+        fullq QL = {x[0], x[1], x[2], x[3]}, QR = {x[4], x[5], x[6], x[7]}, Q0;
+        const double um = x[8];
+        double s0, s1;
+        int ci;
+        riemann(&QL, &QR, um, &ci, &Q0, &s0, &s1);
+        case_ind[i] = ci;
+        q0[4 * i] = Q0.r; q0[4 * i + 1] = Q0.y; q0[4 * i + 2] = Q0.u; q0[4 * i + 3] = Q0.ueq;
+        speed[2 * i] = s0; speed[2 * i + 1] = s1;
+        flux[2 * i] = Q0.r * Q0.u; flux[2 * i + 1] = Q0.y * Q0.u;
+        dLdR(ci, &Q0, &QL, &QR, um, dL + 4 * i, dR + 4 * i);
+        flux_prime(&Q0, um, fp + 4 * i);
+        matmul22(fp + 4 * i, dL + 4 * i, A + 4 * i);
+        matmul22(fp + 4 * i, dR + 4 * i, B + 4 * i);
+        const double a0 = py_max(fabs(s0), 1e-5), a1 = py_max(fabs(s1), 1e-5);
+        cfl_bad[i] = !((dt < dx / a0) && (dt < dx / a1));
+    }
+}
+
 /* ------------------------------------------------------------------------------------------------
  * float32 glue: the same helpers evaluated on 0-dim float32 torch tensors (every op rounded to
  * float32, Python scalars cast to float32; torch.pow(x, 0.5) == sqrt on the reference's build).
@@ -553,6 +584,28 @@ void oracle_idm_jac(double a_max, double a_pref, double v, double v_target, doub
             dLd[3] = (float)(dt * a_max * (-2 * (s / pow(dp, 2))));
         else
             dLd[3] = (float)(dt * a_max * (-2 * (s / pow(dp, 2)) * (-v / (2 * sqrt(a_max * a_pref)))));
+    }
+}
+
+/* Batch form of one vehicle's step as a lane takes it (_micro_lane.py:151-183, dmicro_lane.py:97): in [n][9] = a_max a_pref v
+ * v_target dp dv min_space time_pref dt with the RAW gap and speed difference (the layout of dhts.ops.idm_batch; p = 0).
+ * A negative gap zeroes both deltas, the acceleration takes max(gap, 1e-5), the Jacobians the un-clamped deltas.
+ * Out: next_pv [n][2] = float32 (p + dt v), float32 (v + dt acc) (as doubles), acc_sstar [n][2], flags [n][2] = clipped_acc,
+ * clipped_spacing, collided [n], dEgo dLeading [n][4] float32. */
+void oracle_idm_batch(long n, const double *in, double *next_pv, double *acc_sstar, int *flags, int *collided, float *dE, float *dLd) {
+    #pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; i++) {
+        const double *x = in + 9 * i;
+        const double v = x[2], dt = x[8];
+        double dp = x[4], dv = x[5];
+        collided[i] = dp < 0;
+        if (dp < 0) { dp = 0; dv = 0; }
+        double s;
+        const double acc = oracle_idm_acc(x[0], x[1], v, x[3], py_max(dp, 1e-5), dv, x[6], x[7], dt, &s, flags + 2 * i);
+        next_pv[2 * i] = (float)(0.0 + dt * v);
+        next_pv[2 * i + 1] = (float)(v + dt * acc);
+        acc_sstar[2 * i] = acc; acc_sstar[2 * i + 1] = s;
+        oracle_idm_jac(x[0], x[1], v, x[3], x[4], x[5], x[6], x[7], s, dt, flags + 2 * i, dE + 4 * i, dLd + 4 * i);
     }
 }
 

@@ -44,6 +44,10 @@ void oracle_arz_dLdR(int case_ind, const double q0[4], const double L[4], const 
 /* flux Jacobian at Q_0, row-major 2x2 float32.  model/macro/darz.py:217-233 */
 void oracle_arz_flux_prime(const double q0[4], double u_max, float fp[4]);
 
+/* all of the above for n interfaces, in [n][9] = rL yL uL ueqL rR yR uR ueqR u_max; outputs row-major (see dhts_oracle.c) */
+void oracle_arz_batch(long n, const double *in, double dt, double dx, int *case_ind, double *q0, double *speed, double *flux,
+                      float *dL, float *dR, float *fp, float *A, float *B, int *cfl_bad);
+
 /* float32 glue (torch 0-dim tensor arithmetic in the reference): model/macro/_arz.py:82-92,121-138 */
 void oracle_arz_from_r_u(float r, float u, float u_max, float *y, float *u_eq);     /* FullQ.from_r_u / set_r_u */
 void oracle_arz_from_r_y(float r, float y, float u_max, float *u, float *u_eq);     /* FullQ.set_r_y         */
@@ -91,6 +95,10 @@ double oracle_idm_acc(double a_max, double a_pref, double v, double v_target, do
 void oracle_idm_jac(double a_max, double a_pref, double v, double v_target, double dp, double dv,
                     double min_space, double time_pref, double sstar, double dt, const int flags[2],
                     float dEgo[4], float dLeading[4]);
+
+/* one vehicle's step for n vehicles, in [n][9] = a_max a_pref v v_target dp dv min_space time_pref dt (raw deltas) */
+void oracle_idm_batch(long n, const double *in, double *next_pv, double *acc_sstar, int *flags, int *collided, float *dEgo,
+                      float *dLeading);
 
 /* one lane step (dMicroForwardLayer.forward, road/lane/dmicro_lane.py:230-269).
  * p, v [V] float32 (index i follows i+1, head = V-1); params [V][6] double =

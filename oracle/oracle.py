@@ -36,6 +36,10 @@ def lib():
         _lib.oracle_arz_riemann.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.oracle_arz_dLdR.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         _lib.oracle_arz_flux_prime.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        _lib.oracle_arz_batch.argtypes = [C.c_long, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 10
+        _lib.oracle_arz_batch.restype = None
+        _lib.oracle_idm_batch.argtypes = [C.c_long] + [C.c_void_p] * 7
+        _lib.oracle_idm_batch.restype = None
         _lib.oracle_arz_from_r_u.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.oracle_arz_from_r_y.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.oracle_macro_step.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_double] * 3 + [C.c_void_p] * 8
@@ -85,6 +89,32 @@ def arz_flux_prime(q0, u_max):
     fp = np.zeros((2, 2), np.float32)
     lib().oracle_arz_flux_prime(_p(_f64(q0)), float(u_max), _p(fp))
     return fp
+
+
+def arz_batch(inp, dt=0.01, dx=5.0):
+    """n interfaces at once, inp float64 [n][9] = rL yL uL ueqL rR yR uR ueqR u_max (dhts.ops.arz_interface_batch's layout).
+    Returns case [n], q0 [n][4], speed [n][2], flux [n][2] (double), dL dR fp A B [n][2][2] (float32), cfl_bad [n] (bool)."""
+    inp = _f64(inp).reshape(-1, 9)
+    n = inp.shape[0]
+    case, bad = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    q0, speed, flux = np.zeros((n, 4)), np.zeros((n, 2)), np.zeros((n, 2))
+    m = [np.zeros((n, 2, 2), np.float32) for _ in range(5)]
+    lib().oracle_arz_batch(n, _p(inp), float(dt), float(dx), _p(case), _p(q0), _p(speed), _p(flux), *[_p(a) for a in m], _p(bad))
+    return dict(case=case, q0=q0, speed=speed, flux=flux, dL=m[0], dR=m[1], fp=m[2], A=m[3], B=m[4], cfl_bad=bad.astype(bool))
+
+
+def idm_batch(inp):
+    """n vehicle steps at once, inp float64 [n][9] = a_max a_pref v v_target dp dv min_space time_pref dt with the raw deltas
+    (dhts.ops.idm_batch's layout).  Returns next_p, next_v (float32 values as double), acc, sstar, clipped_acc,
+    clipped_spacing, collided [n] and dEgo, dLeading [n][2][2] float32."""
+    inp = _f64(inp).reshape(-1, 9)
+    n = inp.shape[0]
+    nxt, acs = np.zeros((n, 2)), np.zeros((n, 2))
+    flags, col = np.zeros((n, 2), np.int32), np.zeros(n, np.int32)
+    dE, dLd = np.zeros((n, 2, 2), np.float32), np.zeros((n, 2, 2), np.float32)
+    lib().oracle_idm_batch(n, _p(inp), _p(nxt), _p(acs), _p(flags), _p(col), _p(dE), _p(dLd))
+    return dict(next_p=nxt[:, 0], next_v=nxt[:, 1], acc=acs[:, 0], sstar=acs[:, 1], clipped_acc=flags[:, 0].astype(bool),
+                clipped_spacing=flags[:, 1].astype(bool), collided=col.astype(bool), dEgo=dE, dLeading=dLd)
 
 
 def arz_from_r_u(r, u, u_max):
