@@ -297,8 +297,7 @@ class BatchedMacroNetwork:
             self.inter_ptr = up(np.concatenate([[0], np.cumsum([len(x) for x in slots])]))
             self.inter_idx = up(np.array([j for x in slots for j in x] or [0]))
             self._csr_sq = int(n_inter_sq)
-        self.desc = _lib.NetDesc(1, L, Cn, self.T, int(n_inter_sq), int(frames_per_phase), a.numel(), float(dt), um, float(static_speed),
-                                 float(vehicle_length))
+        _, self.desc = ops._net_desc(a.reshape(1, -1), self.dtab, n_inter_sq, frames_per_phase, dt, um, static_speed, vehicle_length)
         self.err = ops.new_error_record(dev)
         for g in self.groups:
             g["desc"] = ops.macro_desc(g["B"], g["n"], dt, g["dx"], um)

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import MacroDesc, MicroDesc, check
+from .tables import UploadedTables
 
 EPS = 1e-5  # model/macro/_arz.py:2
 
@@ -72,7 +73,7 @@ def raise_on_fault(err):
 def macro_desc(L, N, dt, dx, u_max):
     if not (1 <= N <= _lib.MACRO_MAX_CELLS):
         raise ValueError("cells per lane must be in 1..%d" % _lib.MACRO_MAX_CELLS)
-    return MacroDesc(int(L), int(N), float(dt), float(dx), float(u_max))
+    return MacroDesc(n_lanes=int(L), n_cells=int(N), dt=float(dt), dx=float(dx), u_max=float(u_max))
 
 
 def macro_tape_numel(desc, T):
@@ -449,31 +450,52 @@ def idm_jac_batch(inp):
 # ---------------------------------------------------------------------------------------------------------
 # macro road network with differentiable signals (itscp `macro` mode), replica batch
 # ---------------------------------------------------------------------------------------------------------
+def _net_desc(action, tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length):
+    """(action [R][A] as a contiguous float32 tensor, the dhts_net_desc of R replicas of `tables`).  `action` may be the bare shape
+    (R, A) instead -- a question about a batch size (net_hybrid_plan), not a launch: nothing is checked against the tables then."""
+    a = None if isinstance(action, tuple) else _f32c(action.detach(), "action")
+    R, A = action if a is None else a.shape
+    if a is not None and tables.n_replica_tables not in (0, R):
+        raise ValueError("per-replica tables must match the number of replicas")
+    return a, _lib.NetDesc(n_replicas=int(R), n_lanes=tables.n_lanes, n_cells=tables.n_cells, n_steps=tables.T, n_inter_sq=int(n_inter_sq),
+                           frames_per_phase=int(frames_per_phase), n_action=int(A), dt=float(dt), u_max=float(u_max),
+                           static_speed=float(static_speed), vehicle_length=float(vehicle_length))
+
+
+class _FaultRecord:
+    """Whose dhts_error a network rollout writes, and who reads it (net_macro_rollout / net_hybrid_rollout say it for the caller).
+    err = None: the record is ours -- a fresh one per direction, or `own`, one the front end keeps (StepwiseNetwork.err) -- and each
+    direction reads it back and raises, unless check_faults is off: reading synchronises, which a HIP-graph capture cannot have.
+    A caller's `err` is sticky across calls, is used by both directions and is read by the caller alone; a caller's `err_bwd` takes
+    the reverse sweep's faults instead, so that sweep raises nothing either."""
+
+    def __init__(self, device, check_faults=True, err=None, err_bwd=None, own=None):
+        self.checked = bool(check_faults) and err is None
+        self.fwd = err if err is not None else (own if own is not None else new_error_record(device))
+        self._bwd = err_bwd if err_bwd is not None else (err if err is not None else own)
+        self._bwd_checked = self.checked and err_bwd is None
+
+    def after_forward(self):
+        if self.checked:
+            raise_on_fault(self.fwd)
+
+    def for_reverse(self, device):
+        return self._bwd if self._bwd is not None else new_error_record(device)
+
+    def after_reverse(self, err):
+        if self._bwd_checked:
+            raise_on_fault(err)      # a NaN in the reverse sweep asserts like the reference (dmacro_lane.py:308)
+
+
 class DeviceNetTables:
     """dhts.network.MacroNetworkTables uploaded once; `tables` may be one MacroNetworkTables (shared by all replicas)
     or a list of them (one per replica: same topology, own schedules / per-step routes)."""
 
     def __init__(self, tables, device):
-        import numpy as np
-        many = isinstance(tables, (list, tuple))
-        first = tables[0] if many else tables
-        self.n_lanes, self.n_cells, self.T = first.n_lanes, first.n_cells, first.T
-        self.n_replica_tables = len(tables) if many else 0
-        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=device)    # noqa: E731
-        self.lane_ncell, self.lane_off = up(first.lane_ncell, torch.int32), up(first.lane_off, torch.int32)
-        self.sig_kind, self.inter = up(first.sig_kind, torch.int32), up(first.inter, torch.int32)
-        self.lane_dx = up(first.lane_dx, torch.float64)
-        stack = (lambda name: np.stack([getattr(t, name) for t in tables])) if many else (lambda name: getattr(first, name))
-        self.left_src, self.left_gate = up(stack("left_src"), torch.int32), up(stack("left_gate"), torch.int32)
-        self.right_src, self.schedule = up(stack("right_src"), torch.int32), up(stack("schedule"), torch.float64)
-        pad1 = lambda a: a if len(a) else np.zeros(1, dtype=np.int32)      # noqa: E731  (never pass a NULL pointer)
-        self.nxt_ptr, self.nxt_idx = up(first.nxt_ptr, torch.int32), up(pad1(first.nxt_idx), torch.int32)
-        self.prv_ptr, self.prv_idx = up(first.prv_ptr, torch.int32), up(pad1(first.prv_idx), torch.int32)
-        self.c = _lib.NetTables(self.lane_ncell.data_ptr(), self.lane_off.data_ptr(), self.sig_kind.data_ptr(),
-                                self.inter.data_ptr(), self.lane_dx.data_ptr(), self.left_src.data_ptr(),
-                                self.left_gate.data_ptr(), self.right_src.data_ptr(), self.schedule.data_ptr(),
-                                self.T * self.n_lanes if many else 0, self.nxt_ptr.data_ptr(), self.nxt_idx.data_ptr(),
-                                self.prv_ptr.data_ptr(), self.prv_idx.data_ptr(), first.n_edges)
+        up = UploadedTables(tables, device)
+        self.n_lanes, self.n_cells, self.T, self.n_replica_tables = up.n_lanes, up.n_cells, up.T, up.n_replica_tables
+        self.__dict__.update(up.d)         # the tensors by C field name (dhts.batched.update copies into left_src, ..., schedule)
+        self.c = up.net_tables()
 
 
 class NetMacroRollout(torch.autograd.Function):
@@ -483,12 +505,8 @@ class NetMacroRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length, check_faults=True,
                 err=None):
-        a = _f32c(action.detach(), "action")
-        R, A = a.shape
-        if dev_tables.n_replica_tables not in (0, R):
-            raise ValueError("per-replica tables must match the number of replicas")
-        d = _lib.NetDesc(R, dev_tables.n_lanes, dev_tables.n_cells, dev_tables.T, int(n_inter_sq), int(frames_per_phase), A,
-                         float(dt), float(u_max), float(static_speed), float(vehicle_length))
+        a, d = _net_desc(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length)
+        R = d.n_replicas
         lib = _lib.lib()
         hist_n, tape_n = lib.dhts_net_macro_hist_bytes(C.byref(d)) // 4, lib.dhts_net_macro_tape_bytes(C.byref(d)) // 4
         if hist_n == 0:
@@ -500,16 +518,12 @@ class NetMacroRollout(torch.autograd.Function):
         queue = torch.empty(R, dev_tables.T, dev_tables.n_lanes, dtype=torch.float32, device=dev)
         reward = torch.empty(R, dtype=torch.float32, device=dev)
         ws = torch.zeros(R * dev_tables.T * 2 * dev_tables.n_lanes, dtype=torch.float32, device=dev)
-        own_err = err is None              # a caller's record is sticky across calls and read by the caller (no sync here)
-        if own_err:
-            err = new_error_record(dev)
+        rec = _FaultRecord(dev, check_faults, err)
         check(lib.dhts_net_macro_rollout_fwd(C.byref(d), C.byref(dev_tables.c), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc),
-                                             _ptr(queue), _ptr(reward), _ptr(ws), _ptr(err), _stream()),
+                                             _ptr(queue), _ptr(reward), _ptr(ws), _ptr(rec.fwd), _stream()),
               "dhts_net_macro_rollout_fwd")
-        if check_faults and own_err:     # reading the record back synchronises: off inside HIP-graph capture
-            raise_on_fault(err)
-        ctx.d, ctx.tables, ctx.check_faults = d, dev_tables, bool(check_faults) and own_err
-        ctx.err = None if own_err else err
+        rec.after_forward()
+        ctx.d, ctx.tables, ctx.rec = d, dev_tables, rec
         ctx.save_for_backward(a, hist, tape, kc, queue, ws)
         ctx.mark_non_differentiable(queue)
         return reward, queue
@@ -519,13 +533,12 @@ class NetMacroRollout(torch.autograd.Function):
         a, hist, tape, kc, queue, ws = ctx.saved_tensors
         d = ctx.d
         g_action = torch.empty_like(a)
-        err = ctx.err if ctx.err is not None else new_error_record(a.device)
+        err = ctx.rec.for_reverse(a.device)
         g = g_reward.contiguous().float()          # a named local: the (possibly fresh) tensor must outlive the launch
         check(_lib.lib().dhts_net_macro_rollout_bwd(C.byref(d), C.byref(ctx.tables.c), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc),
                                                     _ptr(queue), _ptr(g), _ptr(g_action), _ptr(ws), _ptr(err),
                                                     _stream()), "dhts_net_macro_rollout_bwd")
-        if ctx.check_faults:
-            raise_on_fault(err)
+        ctx.rec.after_reverse(err)
         return g_action, None, None, None, None, None, None, None, None, None
 
 
@@ -541,21 +554,14 @@ def net_macro_rollout(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_ma
 def net_macro_eval(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed=0.2, vehicle_length=5.0, err=None):
     """An evaluation episode (ItscpEnv.step(action, False) of the reference: hard signal / boundary / is_static thresholds,
     trainer.py:94-142) of R replicas of a macro network: returns (reward [R], queue [R][T][L]); nothing differentiable."""
-    a = _f32c(action.detach(), "action")
-    R, A = a.shape
-    if dev_tables.n_replica_tables not in (0, R):
-        raise ValueError("per-replica tables must match the number of replicas")
-    d = _lib.NetDesc(R, dev_tables.n_lanes, dev_tables.n_cells, dev_tables.T, int(n_inter_sq), int(frames_per_phase), A,
-                     float(dt), float(u_max), float(static_speed), float(vehicle_length))
+    a, d = _net_desc(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length)
+    R = d.n_replicas
     queue = torch.empty(R, dev_tables.T, dev_tables.n_lanes, dtype=torch.float32, device=a.device)
     reward = torch.empty(R, dtype=torch.float32, device=a.device)
-    own_err = err is None
-    if own_err:
-        err = new_error_record(a.device)
-    check(_lib.lib().dhts_net_macro_rollout_eval(C.byref(d), C.byref(dev_tables.c), _ptr(a), _ptr(queue), _ptr(reward), _ptr(err),
+    rec = _FaultRecord(a.device, err=err)
+    check(_lib.lib().dhts_net_macro_rollout_eval(C.byref(d), C.byref(dev_tables.c), _ptr(a), _ptr(queue), _ptr(reward), _ptr(rec.fwd),
                                                  _stream()), "dhts_net_macro_rollout_eval")
-    if own_err:
-        raise_on_fault(err)
+    rec.after_forward()
     return reward, queue
 
 
@@ -568,61 +574,16 @@ class DeviceHybridTables:
     def __init__(self, tables, routes, device, records_per_step=0, lane_capacity=0, vehicle_params=None):
         """vehicle_params [n_routes][6] (rows as `routes`): the IDM attributes of the vehicle that takes each route row
         (dhts_hybrid_tables::veh_params); None = every vehicle a default_micro_vehicle(speed_limit)."""
-        import numpy as np
         if lane_capacity not in (0, 16, 32, 64, 128):
             raise ValueError("lane_capacity (vehicles a micro lane holds at once) must be 0 (= 16), 16, 32, 64 or 128")
-        self.lane_capacity = int(lane_capacity)
+        self.lane_capacity, self.records_per_step = int(lane_capacity), int(records_per_step)
         self.two_per_cu = 0                # dhts_hybrid_tables::two_per_cu: 0 = DHTS_OPT_HYB_PACK decides, 1 = packed, -1 = one replica per unit
-        many = isinstance(tables, (list, tuple))
-        t = tables[0] if many else tables
-        for i, x in enumerate(tables if many else [t]):
+        for x in tables if isinstance(tables, (list, tuple)) else [tables]:
             x.check_kernel_limits()
-            if (x.n_lanes, x.n_cells, x.T) != (t.n_lanes, t.n_cells, t.T) or not np.array_equal(np.asarray(x.lane_source), np.asarray(t.lane_source)):
-                raise ValueError("per-replica tables must share the topology of table 0 (lanes, cells, steps, source lanes): table %d differs" % i)
-            if np.asarray(x.lane_source).any() and getattr(x, "draws", None) is None:
-                raise ValueError("table %d has micro source lanes but no admission draws (HybridNetworkTables.set_micro_sources)" % i)
-        self.n_lanes, self.n_cells, self.T = t.n_lanes, t.n_cells, t.T
-        self.n_replica_tables = len(tables) if many else 0
-        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=device)    # noqa: E731
-        pad1 = lambda a: a if len(a) else np.zeros(1, dtype=np.int32)      # noqa: E731
-        stack = (lambda name: np.stack([getattr(x, name) for x in tables])) if many else (lambda name: getattr(t, name))
-        from .network import group_routes
-        routes = np.ascontiguousarray(routes, dtype=np.int32)
-        if routes.ndim != 2 or routes.shape[0] < 1 or routes.shape[1] > 32:
-            raise ValueError("routes must be [n_routes >= 1][stride <= 32]")
-        self._veh_params = None
-        if vehicle_params is not None:
-            routes, route_ptr, vp = group_routes(routes, t.n_lanes, vehicle_params)
-            self._veh_params = up(vp, torch.float64)
-        else:
-            routes, route_ptr = group_routes(routes, t.n_lanes)
-        self.n_routes, self.route_stride = int(routes.shape[0]), int(routes.shape[1])
-        self.records_per_step = int(records_per_step)
-        self.n_micro = int((np.asarray(t.lane_macro) == 0).sum())
-        self._keep = [up(t.lane_ncell, torch.int32), up(t.lane_off, torch.int32), up(t.sig_kind, torch.int32), up(t.inter, torch.int32),
-                      up(t.lane_dx, torch.float64), up(stack("left_src"), torch.int32), up(stack("left_gate"), torch.int32),
-                      up(stack("right_src"), torch.int32), up(stack("schedule"), torch.float64), up(t.nxt_ptr, torch.int32),
-                      up(pad1(t.nxt_idx), torch.int32), up(t.prv_ptr, torch.int32), up(pad1(t.prv_idx), torch.int32),
-                      up(t.lane_macro, torch.int32), up(t.lane_length, torch.float64), up(stack("conv_next"), torch.int32),
-                      up(routes, torch.int32), up(route_ptr, torch.int32)]
-        # micro source lanes (itscp `micro` mode): the lane flags and the host's admission draws (per replica when `tables` is a list)
-        self.has_sources = bool(np.asarray(t.lane_source).any())
-        self.micro_tensor_ladder = bool(getattr(t, "micro_tensor_ladder", False))
-        self.n_draws, self.draws_stride = 0, 0
-        if self.has_sources:
-            if many:
-                n = max(len(x.draws) for x in tables)
-                d = np.full((len(tables), n), 2.0)           # (a draw of 2.0 admits nobody)
-                for i, x in enumerate(tables):
-                    d[i, :len(x.draws)] = x.draws
-                self.n_draws, self.draws_stride = n, n
-            else:
-                d = np.asarray(t.draws, dtype=np.float64)
-                self.n_draws = len(d)
-            self._keep += [up(t.lane_source, torch.int32), up(d, torch.float64)]
-        k = [x.data_ptr() for x in self._keep]
-        self.net = _lib.NetTables(k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], self.T * self.n_lanes if many else 0,
-                                  k[9], k[10], k[11], k[12], t.n_edges)
+        up = self._up = UploadedTables(tables, device, routes, vehicle_params)
+        for name in ("n_lanes", "n_cells", "T", "n_replica_tables", "n_micro", "has_sources", "micro_tensor_ladder"):
+            setattr(self, name, getattr(up, name))
+        self.net = up.net_tables()         # (filled once: nothing here rebinds a tensor, see set_draws)
 
     def first(self, n_replicas):
         """The same uploaded tables as a batch of the first `n_replicas` replicas (no copy: the per-replica arrays are
@@ -638,26 +599,30 @@ class DeviceHybridTables:
     def schedules(self):
         """The uploaded inflow schedules read back to the host: float64 [R][T][L], one per replica of this batch (a `first(n)`
         view gives its n), or [1][T][L] for tables shared by all replicas."""
-        s = self._keep[8].cpu().numpy().reshape(-1, self.T, self.n_lanes)
+        s = self._up.d["schedule"].cpu().numpy().reshape(-1, self.T, self.n_lanes)
         return s[:self.n_replica_tables] if self.n_replica_tables else s
 
     def set_draws(self, draws):
-        """A fresh stream of admission draws for the next episode (micro source lanes; same length as the uploaded one)."""
-        import numpy as np
-        if not self.has_sources:
-            raise ValueError("the network has no micro source lanes")
-        d = torch.as_tensor(np.ascontiguousarray(draws, dtype=np.float64), device=self._keep[19].device)
-        if d.shape != self._keep[19].shape:
-            raise ValueError("draws must keep their shape %s" % (tuple(self._keep[19].shape),))
-        self._keep[19].copy_(d)
+        """A fresh stream of admission draws for the next episode (micro source lanes; same length as the uploaded one), copied
+        into the uploaded tensor (UploadedTables.replace says when that is sound)."""
+        self._up.set_draws(draws, in_place=True)
 
     def c(self, loss_steps=0):
-        k = [x.data_ptr() for x in self._keep]
-        src = (k[18], k[19]) if self.has_sources else (None, None)
-        return _lib.HybridTables(self.net, k[13], k[14], k[15], k[16], k[17], self.n_routes, self.route_stride, self.records_per_step,
-                                 int(loss_steps), self.n_micro, src[0], src[1], self.n_draws, self.draws_stride, self.lane_capacity,
-                                 1 if self.micro_tensor_ladder else 0, None if self._veh_params is None else self._veh_params.data_ptr(),
-                                 int(self.two_per_cu))
+        return self._up.hybrid_tables(self.net, records_per_step=self.records_per_step, loss_steps=int(loss_steps),
+                                      lane_capacity=self.lane_capacity, two_per_cu=int(self.two_per_cu))
+
+
+def _hybrid_buffers(d, tc, dev):
+    """What a fused hybrid rollout writes: (hist, tape, kc, queue [R][T][L], reward [R], counts [R][4], workspace)."""
+    lib, R, T = _lib.lib(), d.n_replicas, d.n_steps
+    ws_n = lib.dhts_net_hybrid_workspace_bytes(C.byref(d), C.byref(tc))
+    if ws_n == 0:
+        raise ValueError("unsupported hybrid network size")
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+    # (an all-micro network has no cells: the kernels' unconditional prefetches still want something to read)
+    return (f32(max(R * (T + 1) * 4 * d.n_cells, 64)), f32(max(lib.dhts_net_hybrid_tape_bytes(C.byref(d)) // 4, 64)),
+            f32(max(R * T * d.n_cells, 64)), f32(R, T, d.n_lanes), f32(R), torch.zeros(R, 4, dtype=torch.int32, device=dev),
+            torch.empty(ws_n, dtype=torch.uint8, device=dev))
 
 
 class NetHybridRollout(torch.autograd.Function):
@@ -668,58 +633,37 @@ class NetHybridRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length, loss_steps,
                 check_faults=True, err=None, err_bwd=None):
-        a = _f32c(action.detach(), "action")
-        R, A = a.shape
         t = dev_tables
-        if t.n_replica_tables not in (0, R):
-            raise ValueError("per-replica tables must match the number of replicas")
-        d = _lib.NetDesc(R, t.n_lanes, t.n_cells, t.T, int(n_inter_sq), int(frames_per_phase), A, float(dt), float(u_max),
-                         float(static_speed), float(vehicle_length))
+        a, d = _net_desc(action, t, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length)
+        R = d.n_replicas
         tc = t.c(loss_steps)
-        lib = _lib.lib()
-        ws_n = lib.dhts_net_hybrid_workspace_bytes(C.byref(d), C.byref(tc))
-        if ws_n == 0:
-            raise ValueError("unsupported hybrid network size")
-        dev = a.device
-        # (an all-micro network has no cells: the kernels' unconditional prefetches still want something to read)
-        hist = torch.empty(max(R * (t.T + 1) * 4 * t.n_cells, 64), dtype=torch.float32, device=dev)
-        tape = torch.empty(max(lib.dhts_net_hybrid_tape_bytes(C.byref(d)) // 4, 64), dtype=torch.float32, device=dev)
-        kc = torch.empty(max(R * t.T * t.n_cells, 64), dtype=torch.float32, device=dev)
-        queue = torch.empty(R, t.T, t.n_lanes, dtype=torch.float32, device=dev)
-        reward = torch.empty(R, dtype=torch.float32, device=dev)
-        counts = torch.zeros(R, 4, dtype=torch.int32, device=dev)
-        ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
-        own_err = err is None              # a caller's record is sticky across calls and read by the caller (no sync here)
-        if own_err:
-            err = new_error_record(dev)
-        check(lib.dhts_net_hybrid_rollout_fwd(C.byref(d), C.byref(tc), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc), _ptr(queue),
-                                              _ptr(reward), _ptr(counts), _ptr(ws), _ptr(err), _stream()),
-              "dhts_net_hybrid_rollout_fwd")
-        if check_faults and own_err:     # reading the record back synchronises: off inside HIP-graph capture
-            try:
-                raise_on_fault(err)
-            except CapacityError:
-                # two replicas per compute unit (more replicas than units) halve the record staging area: the same batch once more
-                # with one replica per unit before the caller hears of it (the reverse sweep follows the tables it is given)
-                plan = (C.c_int32 * 8)()
-                check(lib.dhts_net_hybrid_plan(C.byref(d), C.byref(tc), plan), "dhts_net_hybrid_plan")
-                if not plan[0]:
-                    raise
-                import copy
-                t = copy.copy(t)
-                t.two_per_cu = -1
-                tc = t.c(loss_steps)
-                err.zero_()
-                counts.zero_()
-                check(lib.dhts_net_hybrid_rollout_fwd(C.byref(d), C.byref(tc), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc), _ptr(queue),
-                                                      _ptr(reward), _ptr(counts), _ptr(ws), _ptr(err), _stream()),
-                      "dhts_net_hybrid_rollout_fwd")
-                raise_on_fault(err)
-        # the reverse sweep raises only on a record of its own: a caller-owned one (err, or err_bwd for the reverse sweep alone) is
-        # the caller's to read -- that is how a batch tolerates one member's NaN
-        ctx.d, ctx.tables, ctx.loss_steps = d, t, int(loss_steps)
-        ctx.check_faults = bool(check_faults) and own_err and err_bwd is None
-        ctx.err = err_bwd if err_bwd is not None else (None if own_err else err)
+        lib, dev = _lib.lib(), a.device
+        hist, tape, kc, queue, reward, counts, ws = _hybrid_buffers(d, tc, dev)
+        rec = _FaultRecord(dev, check_faults, err, err_bwd)
+
+        def launch(tc):
+            check(lib.dhts_net_hybrid_rollout_fwd(C.byref(d), C.byref(tc), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc), _ptr(queue),
+                                                  _ptr(reward), _ptr(counts), _ptr(ws), _ptr(rec.fwd), _stream()),
+                  "dhts_net_hybrid_rollout_fwd")
+            rec.after_forward()
+        try:
+            launch(tc)
+        except CapacityError:            # (raised only where the record is ours and check_faults is on)
+            # two replicas per compute unit (more replicas than units) halve the record staging area: the same batch once more
+            # with one replica per unit before the caller hears of it (the reverse sweep follows the tables it is given)
+            plan = (C.c_int32 * 8)()
+            check(lib.dhts_net_hybrid_plan(C.byref(d), C.byref(tc), plan), "dhts_net_hybrid_plan")
+            if not plan[0]:
+                raise
+            import copy
+            t = copy.copy(t)
+            t.two_per_cu = -1
+            rec.fwd.zero_()
+            counts.zero_()
+            launch(t.c(loss_steps))
+        # (a caller's record -- err, or err_bwd for the reverse sweep alone -- is the caller's to read: that is how a batch
+        # tolerates one member's NaN)
+        ctx.d, ctx.tables, ctx.loss_steps, ctx.rec = d, t, int(loss_steps), rec
         ctx.save_for_backward(a, hist, tape, kc, queue, ws)
         ctx.mark_non_differentiable(reward, queue, counts)
         if loss_steps and loss_steps > 0:
@@ -735,13 +679,12 @@ class NetHybridRollout(torch.autograd.Function):
         d = ctx.d
         tc = ctx.tables.c(ctx.loss_steps)
         g_action = torch.empty_like(a)
-        err = ctx.err if ctx.err is not None else new_error_record(a.device)
+        err = ctx.rec.for_reverse(a.device)
         g = g_cut.contiguous().float()             # a named local: the (possibly fresh) tensor must outlive the launch
         check(_lib.lib().dhts_net_hybrid_rollout_bwd(C.byref(d), C.byref(tc), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc), _ptr(queue),
                                                      _ptr(g), _ptr(g_action), _ptr(ws), _ptr(err), _stream()),
               "dhts_net_hybrid_rollout_bwd")
-        if ctx.check_faults:
-            raise_on_fault(err)     # a NaN in the reverse sweep asserts like the reference (dmacro_lane.py:308)
+        ctx.rec.after_reverse(err)
         return g_action, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -760,34 +703,23 @@ class NetHybridStateRollout(torch.autograd.Function):
         R, Cc = r0.shape
         if Cc != t.n_cells:
             raise ValueError("state must be [R][%d cells]" % t.n_cells)
-        if t.n_replica_tables not in (0, R):
-            raise ValueError("per-replica tables must match the number of replicas")
         dev = r0.device
         r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+        action = torch.full((R, 1), 0.5, dtype=torch.float32, device=dev)                # no signals: one dummy phase
+        action, d = _net_desc(action, t, 1, max(int(t.T), 1), dt, u_max, 0.2, vehicle_length)
         y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
         state0 = torch.stack([r0c, y0, u0c, q0], dim=1).contiguous()                       # [R][4][C]
         g0 = None if ghost0 is None else _f32c(ghost0.detach(), "ghost0")
         if g0 is not None and tuple(g0.shape) != (R, t.n_lanes, 4):
             raise ValueError("ghost0 must be [R][%d lanes][4]" % t.n_lanes)
-        action = torch.full((R, 1), 0.5, dtype=torch.float32, device=dev)                # no signals: one dummy phase
-        d = _lib.NetDesc(R, t.n_lanes, t.n_cells, t.T, 1, max(int(t.T), 1), 1, float(dt), float(u_max), 0.2, float(vehicle_length))
         tc = t.c(0)
         lib = _lib.lib()
-        ws_n = lib.dhts_net_hybrid_workspace_bytes(C.byref(d), C.byref(tc))
-        if ws_n == 0:
-            raise ValueError("unsupported hybrid network size")
-        hist = torch.empty(max(R * (t.T + 1) * 4 * t.n_cells, 64), dtype=torch.float32, device=dev)
-        tape = torch.empty(max(lib.dhts_net_hybrid_tape_bytes(C.byref(d)) // 4, 64), dtype=torch.float32, device=dev)
-        kc = torch.empty(max(R * t.T * t.n_cells, 64), dtype=torch.float32, device=dev)
-        queue = torch.empty(R, t.T, t.n_lanes, dtype=torch.float32, device=dev)
-        reward = torch.empty(R, dtype=torch.float32, device=dev)
-        counts = torch.zeros(R, 4, dtype=torch.int32, device=dev)
+        hist, tape, kc, queue, reward, counts, ws = _hybrid_buffers(d, tc, dev)
         veh = torch.zeros(R, 128, 4, dtype=torch.float32, device=dev)
         veh[:, :, 0] = -1.0
         events = torch.full((R, 256, 2), -1, dtype=torch.int32, device=dev)
-        ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
         err = new_error_record(dev)
-        io = _lib.HybridStateIO(1 if plain else 0, _ptr(state0), None if g0 is None else _ptr(g0), _ptr(veh), _ptr(events))
+        io = _lib.HybridStateIO(plain=1 if plain else 0, state0=_ptr(state0), ghost0=_ptr(g0), veh_out=_ptr(veh), events=_ptr(events))
         check(lib.dhts_net_hybrid_state_rollout_fwd(C.byref(d), C.byref(tc), C.byref(io), _ptr(action), _ptr(hist), _ptr(tape), _ptr(kc),
                                                     _ptr(queue), _ptr(reward), _ptr(counts), _ptr(ws), _ptr(err), _stream()),
               "dhts_net_hybrid_state_rollout_fwd")
@@ -843,8 +775,7 @@ def net_hybrid_plan(n_replicas, n_action, dev_tables, n_inter_sq=1, frames_per_p
     """What net_hybrid_rollout would launch for a batch of `n_replicas` under the current DHTS_OPT_HYB_PACK (dhts_net_hybrid_plan):
     {"packed": two replicas per compute unit, "block", "stage_h", "lds_fwd", "lds_bwd", "loc_lanes", "max_step_records", "cus"}."""
     t = dev_tables
-    d = _lib.NetDesc(int(n_replicas), t.n_lanes, t.n_cells, t.T, int(n_inter_sq), int(frames_per_phase), int(n_action), float(dt),
-                     float(u_max), 0.2, 5.0)
+    _, d = _net_desc((n_replicas, n_action), t, n_inter_sq, frames_per_phase, dt, u_max, 0.2, 5.0)
     tc = t.c(0)
     plan = (C.c_int32 * 8)()
     check(_lib.lib().dhts_net_hybrid_plan(C.byref(d), C.byref(tc), plan), "dhts_net_hybrid_plan")
@@ -857,24 +788,17 @@ def net_hybrid_plan(n_replicas, n_action, dev_tables, n_inter_sq=1, frames_per_p
 def net_hybrid_eval(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed=0.2, vehicle_length=5.0, err=None):
     """An evaluation episode (hard thresholds, see net_macro_eval) of R replicas of a hybrid network: returns
     (reward [R], queue [R][T][L], counts [R][4] = vehicles spawned, vehicles deposited, 0, 0)."""
-    a = _f32c(action.detach(), "action")
-    R, A = a.shape
     t = dev_tables
-    if t.n_replica_tables not in (0, R):
-        raise ValueError("per-replica tables must match the number of replicas")
-    d = _lib.NetDesc(R, t.n_lanes, t.n_cells, t.T, int(n_inter_sq), int(frames_per_phase), A, float(dt), float(u_max),
-                     float(static_speed), float(vehicle_length))
+    a, d = _net_desc(action, t, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length)
+    R = d.n_replicas
     tc = t.c(0)
     queue = torch.empty(R, t.T, t.n_lanes, dtype=torch.float32, device=a.device)
     reward = torch.empty(R, dtype=torch.float32, device=a.device)
     counts = torch.zeros(R, 4, dtype=torch.int32, device=a.device)
-    own_err = err is None
-    if own_err:
-        err = new_error_record(a.device)
+    rec = _FaultRecord(a.device, err=err)
     check(_lib.lib().dhts_net_hybrid_rollout_eval(C.byref(d), C.byref(tc), _ptr(a), _ptr(queue), _ptr(reward), _ptr(counts),
-                                                  _ptr(err), _stream()), "dhts_net_hybrid_rollout_eval")
-    if own_err:
-        raise_on_fault(err)
+                                                  _ptr(rec.fwd), _stream()), "dhts_net_hybrid_rollout_eval")
+    rec.after_forward()
     return reward, queue, counts
 
 

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .tables import UploadedTables
 
 
 def default_lane_capacity(tables, vehicle_length, ceiling=32):
@@ -70,6 +71,9 @@ def as_hybrid_tables(t):
     return h
 
 
+_NETSTEP_POINTERS = tuple(n for n, ty in _lib.NetstepTables._fields_ if ty is C.c_void_p)      # (`groups` is a typed HOST pointer)
+
+
 class StepwiseNetwork:
     """A network's tables on the device for dhts_netstep_rollout_fwd / _bwd.  `routes` [n][stride <= 32] int (-1 padded): the k-th
     vehicle spawned onto a micro lane takes that lane's k-th route (cyclically; waiting lists of micro source lanes in admission
@@ -80,17 +84,12 @@ class StepwiseNetwork:
         device functions with workgroup barriers instead of kernel boundaries; ~10 x fewer microseconds per step for the grids the
         reference builds).  `tables` may then be a LIST of tables of one topology (own schedules / per-step routes / draws each): one
         replica per entry, rollout() takes action [R][A] and returns [R]-shaped results."""
-        from .network import group_routes
         many = isinstance(tables, (list, tuple))
         tabs = [as_hybrid_tables(x) for x in tables] if many else [as_hybrid_tables(tables)]
         if many and not persistent:
             raise ValueError("StepwiseNetwork: a list of tables (replicas) needs persistent=True")
         t = tabs[0]
-        for i, x in enumerate(tabs):
-            if (x.n_lanes, x.n_cells, x.T) != (t.n_lanes, t.n_cells, t.T) or not np.array_equal(x.lane_macro, t.lane_macro) or \
-                    not np.array_equal(x.lane_ncell, t.lane_ncell) or not np.array_equal(np.asarray(x.lane_source), np.asarray(t.lane_source)):
-                raise ValueError("per-replica tables must share the topology of table 0: table %d differs" % i)
-        self.n_replicas = len(tabs) if many else 0            # 0: one network, un-batched shapes
+        self.n_replicas = self.n_replica_tables = len(tabs) if many else 0            # 0: one network, un-batched shapes
         self.tabs = tabs
         self.persistent = bool(persistent)
         self.t, self.device = t, device
@@ -101,8 +100,6 @@ class StepwiseNetwork:
         self.lane_capacity, self.max_events = int(lane_capacity), int(max_events)
         lane_macro = np.asarray(t.lane_macro, dtype=np.int32)
         ncell = np.asarray(t.lane_ncell, dtype=np.int64)
-        if np.asarray(t.lane_source).any() and any(getattr(x, "draws", None) is None for x in tabs):
-            raise ValueError("a network with micro source lanes needs its admission draws (HybridNetworkTables.set_micro_sources)")
         # ---- groups of ARZ lanes with equal (cells, cell length): contiguous blocks of the group-major cell / lane order ----
         keys = {}
         for l in range(L):
@@ -126,7 +123,8 @@ class StepwiseNetwork:
         self.cell_pos = np.concatenate([lane_off[l] + np.arange(ncell[l]) for l in range(L) if lane_macro[l]] or [np.zeros(0, np.int64)]).astype(np.int64)
         order = np.concatenate([own_off[l] + np.arange(ncell[l]) for l in range(L) if lane_macro[l]] or [np.zeros(0, np.int64)])
         assert np.array_equal(order, np.arange(t.n_cells)), "lane_off of the tables must be lane-major over the macro lanes"
-        self._garr = (_lib.NetstepGroup * max(1, len(self.groups)))(*[_lib.NetstepGroup(*g) for g in self.groups])
+        self._garr = (_lib.NetstepGroup * max(1, len(self.groups)))(
+            *[_lib.NetstepGroup(lane_pos0=p, n_lanes=n, n_cells=nc, cell0=c, dx=dx) for p, n, nc, c, dx in self.groups])
         # the persistent kernels' maps: interface item lane_off[l] + lane_gpos[l] + k (k = 0 .. n) -> lane; cell -> lane
         if_lane = np.zeros(max(1, t.n_cells + pos), dtype=np.int32)
         cell_lane = np.zeros(max(1, t.n_cells), dtype=np.int32)
@@ -152,46 +150,12 @@ class StepwiseNetwork:
                         raise ValueError("lane %d is gated by the signal of lane %d, which belongs to another intersection" % (l, g_))
         self._csr_sq = -1
         self._inter = np.asarray(t.inter, dtype=np.int64)
-        # ---- routes ----
-        routes = np.ascontiguousarray(routes, dtype=np.int32)
-        if routes.ndim != 2 or routes.shape[0] < 1 or routes.shape[1] > 32:
-            raise ValueError("routes must be [n_routes >= 1][stride <= 32]")
-        vp = None
-        if vehicle_params is not None:        # [n_routes][6], rows as `routes` (dhts_hybrid_tables::veh_params)
-            routes, route_ptr, vp = group_routes(routes, L, vehicle_params)
-        else:
-            routes, route_ptr = group_routes(routes, L)
-        self.n_routes, self.route_stride = int(routes.shape[0]), int(routes.shape[1])
-        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=device)      # noqa: E731
-        pad1 = lambda a: a if len(a) else np.zeros(1, dtype=np.int32)      # noqa: E731
-        i32, f64 = torch.int32, torch.float64
-        stack = (lambda name: np.stack([getattr(x, name) for x in tabs])) if many else (lambda name: getattr(t, name))
-        self.d = dict(
-            lane_ncell=up(t.lane_ncell, i32), lane_off=up(lane_off, i32), sig_kind=up(t.sig_kind, i32), inter=up(t.inter, i32),
-            lane_dx=up(t.lane_dx, f64), left_src=up(stack("left_src"), i32), left_gate=up(stack("left_gate"), i32),
-            right_src=up(stack("right_src"), i32), schedule=up(stack("schedule"), f64), nxt_ptr=up(t.nxt_ptr, i32),
-            nxt_idx=up(pad1(t.nxt_idx), i32), prv_ptr=up(t.prv_ptr, i32),
-            prv_idx=up(pad1(t.prv_idx), i32), lane_macro=up(lane_macro, i32), lane_len=up(t.lane_length, f64),
-            conv_next=up(stack("conv_next"), i32), routes=up(routes, i32), route_ptr=up(route_ptr, i32), lane_gpos=up(lane_gpos, i32),
-            if_lane=up(if_lane, i32), cell_lane=up(cell_lane, i32),
-            micro_lanes=up(pad1(np.asarray(micro, dtype=np.int32)), i32), lane_mslot=up(mslot, i32),
-            cap_lanes=up(pad1(np.asarray(caps, dtype=np.int32)), i32), lane_cslot=up(cslot, i32))
-        self.has_sources = bool(np.asarray(t.lane_source).any())
-        self.micro_tensor_ladder = bool(getattr(t, "micro_tensor_ladder", False))
-        self.n_draws, self.draws_stride = 0, 0
-        if self.has_sources:
-            if many:
-                n = max(len(x.draws) for x in tabs)
-                d = np.full((len(tabs), n), 2.0)               # (a draw of 2.0 admits nobody)
-                for i, x in enumerate(tabs):
-                    d[i, :len(x.draws)] = x.draws
-                self.n_draws, self.draws_stride = n, n
-            else:
-                d = np.asarray(t.draws, dtype=np.float64)
-                self.n_draws = len(d)
-            self.d["lane_source"], self.d["draws"] = up(t.lane_source, i32), up(d, f64)
-        if vp is not None:
-            self.d["veh_params"] = up(vp, f64)
+        # ---- the shared tables (cells group-major: lane_off), then this path's own ----
+        up = self._up = UploadedTables(tabs if many else t, device, routes, vehicle_params, overrides={"lane_off": lane_off})
+        self.d = up.d
+        for name, a in (("lane_gpos", lane_gpos), ("if_lane", if_lane), ("cell_lane", cell_lane), ("micro_lanes", micro or [0]),
+                        ("lane_mslot", mslot), ("cap_lanes", caps or [0]), ("lane_cslot", cslot)):
+            self.d[name] = up.upload(name, a)
         self.err = ops.new_error_record(device)
 
     # ---- per-episode data in place (same topology): new schedules / per-step routes / draws ----
@@ -206,23 +170,15 @@ class StepwiseNetwork:
         if not same:
             raise ValueError("StepwiseNetwork.update: the network's topology changed; build a new one")
         self.t = t
-        # NEW tensors, not copies into the old ones: a differentiable rollout that has not run its reverse sweep yet keeps
-        # references to the tables it was stepped with (several episodes summed before one backward(): Trainer.train_epoch with
-        # num_episode_per_epoch > 1)
-        for name, dt in (("left_src", torch.int32), ("left_gate", torch.int32), ("right_src", torch.int32), ("conv_next", torch.int32),
-                         ("schedule", torch.float64)):
-            self.d[name] = torch.as_tensor(np.ascontiguousarray(getattr(t, name)), dtype=dt, device=self.device)
+        for name in ("left_src", "left_gate", "right_src", "conv_next", "schedule"):
+            self._up.replace(name, getattr(t, name), in_place=False)
 
     def set_draws(self, draws):
-        if not self.has_sources:
-            raise ValueError("the network has no micro source lanes")
-        d = torch.as_tensor(np.ascontiguousarray(draws, dtype=np.float64))
-        if d.shape != self.d["draws"].shape:
-            raise ValueError("draws must keep their shape %s" % (tuple(self.d["draws"].shape),))
-        self.d["draws"] = d.to(self.device)            # (a new tensor: see update())
+        """As update(), for the admission draws: a new tensor (UploadedTables.replace says why not a copy into the old one)."""
+        self._up.set_draws(draws, in_place=False)
 
     def _c(self, n_inter_sq, loss_steps):
-        d = self.d
+        d, up = self.d, self._up
         sq = int(n_inter_sq)
         if self._csr_sq != sq:
             if self.n_lanes and int(self._inter.max()) >= sq:
@@ -231,21 +187,13 @@ class StepwiseNetwork:
             for l in range(self.n_lanes):
                 if self.t.lane_macro[l]:
                     slots[int(self._inter[l])] += [2 * l, 2 * l + 1]
-            up = lambda x: torch.as_tensor(np.ascontiguousarray(x), dtype=torch.int32, device=self.device)      # noqa: E731
-            d["inter_ptr"] = up(np.concatenate([[0], np.cumsum([len(x) for x in slots])]))
-            d["inter_idx"] = up(np.array([j for x in slots for j in x] or [0]))
+            d["inter_ptr"] = up.upload("inter_ptr", np.concatenate([[0], np.cumsum([len(x) for x in slots])]))
+            d["inter_idx"] = up.upload("inter_idx", np.array([j for x in slots for j in x] or [0]))
             self._csr_sq = sq
-        p = lambda k: d[k].data_ptr()      # noqa: E731
-        net = _lib.NetTables(p("lane_ncell"), p("lane_off"), p("sig_kind"), p("inter"), p("lane_dx"), p("left_src"), p("left_gate"),
-                             p("right_src"), p("schedule"), self.T * self.n_lanes if self.n_replicas else 0, p("nxt_ptr"), p("nxt_idx"),
-                             p("prv_ptr"), p("prv_idx"), self.t.n_edges)
-        src = (p("lane_source"), p("draws")) if self.has_sources else (None, None)
-        hyb = _lib.HybridTables(net, p("lane_macro"), p("lane_len"), p("conv_next"), p("routes"), p("route_ptr"), self.n_routes,
-                                self.route_stride, 0, int(loss_steps), self.n_micro, src[0], src[1], self.n_draws, self.draws_stride,
-                                self.lane_capacity, 1 if self.micro_tensor_ladder else 0, p("veh_params") if "veh_params" in d else None, 0)
-        return _lib.NetstepTables(hyb, p("lane_gpos"), self._garr, len(self.groups), p("micro_lanes"), p("lane_mslot"), p("cap_lanes"),
-                                  p("lane_cslot"), self.n_caps, p("inter_ptr"), p("inter_idx"), self.max_events, p("if_lane"), p("cell_lane"),
-                                  1 if self.persistent else 0, int(d["inter_idx"].numel()))
+        hyb = up.hybrid_tables(up.net_tables(), loss_steps=int(loss_steps), lane_capacity=self.lane_capacity)
+        return _lib.NetstepTables(hyb=hyb, groups=self._garr, n_groups=len(self.groups), n_caps=self.n_caps, max_events=self.max_events,
+                                  persistent=int(self.persistent), n_inter_slots=int(d["inter_idx"].numel()),
+                                  **{n: d[n].data_ptr() for n in _NETSTEP_POINTERS})
 
     def rollout(self, action, n_inter_sq, frames_per_phase, dt, u_max, static_speed=0.2, vehicle_length=5.0, differentiable=True,
                 loss_steps=0, check_faults=True):
@@ -265,13 +213,10 @@ class _NetstepRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, action, net, sq, F, dt, um, s0, vlen, differentiable, loss_steps, check_faults):
         R = net.n_replicas
-        a = ops._f32c(action.detach().reshape(R, -1) if R else action.detach().reshape(-1), "action")
-        if R and a.shape[0] != R:
-            raise ValueError("action must be [%d][A] for this network's %d replicas" % (R, R))
+        Rn = max(R, 1)
+        a, d = ops._net_desc(action.reshape(Rn, -1), net, sq, F, dt, um, s0, vlen)
         dev = a.device
         lib = _lib.lib()
-        Rn = max(R, 1)
-        d = _lib.NetDesc(Rn, net.n_lanes, net.n_cells, net.T, sq, F, a.numel() // Rn, dt, um, s0, vlen)
         tc = net._c(sq, loss_steps)
         ws_n = lib.dhts_netstep_workspace_bytes(C.byref(d), C.byref(tc))
         if ws_n == 0:
@@ -288,14 +233,14 @@ class _NetstepRollout(torch.autograd.Function):
         queue = torch.empty(Rn, net.T, net.n_lanes, dtype=torch.float32, device=dev)
         reward = torch.empty(Rn, 2, dtype=torch.float32, device=dev)
         counts = torch.zeros(Rn, 4, dtype=torch.int32, device=dev)
+        rec = ops._FaultRecord(dev, check_faults, own=net.err)      # the network's record, zeroed per episode, read in both directions
         net.err.zero_()
         _lib.check(lib.dhts_netstep_rollout_fwd(C.byref(d), C.byref(tc), 0 if differentiable else 1, ops._ptr(a), ops._ptr(hist), ops._ptr(queue),
-                                                ops._ptr(reward), ops._ptr(counts), ops._ptr(ws), ops._ptr(net.err), ops._stream()),
+                                                ops._ptr(reward), ops._ptr(counts), ops._ptr(ws), ops._ptr(rec.fwd), ops._stream()),
                    "dhts_netstep_rollout_fwd")
-        if check_faults:
-            ops.raise_on_fault(net.err)
+        rec.after_forward()
         net.last_hist = hist if R else hist[0]
-        ctx.net, ctx.d, ctx.tc, ctx.differentiable, ctx.check_faults = net, d, tc, differentiable, check_faults
+        ctx.d, ctx.tc, ctx.differentiable, ctx.rec = d, tc, differentiable, rec
         ctx.tables = list(net.d.values())             # (tc holds raw pointers: keep the tensors of THIS episode alive, see update())
         ctx.save_for_backward(a, hist, queue.reshape(Rn, net.T, net.n_lanes), ws)
         ctx.shape = action.shape
@@ -311,12 +256,11 @@ class _NetstepRollout(torch.autograd.Function):
         if not ctx.differentiable:
             raise RuntimeError("an evaluation episode (differentiable=False) keeps nothing for a reverse sweep")
         a, hist, queue, ws = ctx.saved_tensors
-        net = ctx.net
+        err = ctx.rec.for_reverse(a.device)
         g = g_cut.reshape(-1).contiguous().float()
         g_action = torch.empty_like(a)
         _lib.check(_lib.lib().dhts_netstep_rollout_bwd(C.byref(ctx.d), C.byref(ctx.tc), ops._ptr(a), ops._ptr(hist), ops._ptr(queue), ops._ptr(g),
-                                                       ops._ptr(g_action), ops._ptr(ws), ops._ptr(net.err), ops._stream()),
+                                                       ops._ptr(g_action), ops._ptr(ws), ops._ptr(err), ops._stream()),
                    "dhts_netstep_rollout_bwd")
-        if ctx.check_faults:
-            ops.raise_on_fault(net.err)
+        ctx.rec.after_reverse(err)
         return (g_action.reshape(ctx.shape),) + (None,) * 10

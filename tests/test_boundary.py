@@ -3,6 +3,8 @@ checks; the product never touches the oracle.  No GPU needed (no compute calls).
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -24,6 +26,78 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), "libdhts.so does not export %s" % n
     # and the binding table covers the header exactly
     assert sorted(_lib.SIGNATURES) == names
+
+
+# C struct of include/dhts.h -> its ctypes mirror in dhts/_lib.py (dhts_error has none: a fault record is an int32 [4] tensor)
+MIRRORS = {"dhts_macro_desc": "MacroDesc", "dhts_micro_desc": "MicroDesc", "dhts_net_desc": "NetDesc", "dhts_net_tables": "NetTables",
+           "dhts_hybrid_tables": "HybridTables", "dhts_hybrid_state_io": "HybridStateIO", "dhts_netstep_group": "NetstepGroup",
+           "dhts_netstep_tables": "NetstepTables"}
+
+
+def header_code():
+    txt = open(os.path.join(ROOT, "include", "dhts.h")).read()
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+def header_structs():
+    """{struct name: [field names in declaration order]} of every `typedef struct` of the header."""
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", header_code(), flags=re.S):
+        decls = [d for d in (x.strip() for x in body.split(";")) if d]
+        out[name] = [re.search(r"(\w+)\s*$", part).group(1) for d in decls for part in d.split(",")]
+    return out
+
+
+def header_prototypes():
+    """{function name: number of parameters} of every prototype of the header."""
+    out = {}
+    for name, params in re.findall(r"\b(dhts_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header_code()):
+        out[name] = 0 if params.strip() == "void" else len(params.split(","))
+    return out
+
+
+def test_structures_mirror_the_header_field_for_field():
+    """dhts.tables and dhts.ops fill the structs BY NAME, so the names and their order are what has to agree with the header."""
+    from dhts import _lib
+    structs = header_structs()
+    assert sorted(set(structs) - set(MIRRORS)) == ["dhts_error"]
+    mirrored = {n for n, v in vars(_lib).items() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    assert mirrored == set(MIRRORS.values())
+    for cname, pyname in MIRRORS.items():
+        assert [f[0] for f in getattr(_lib, pyname)._fields_] == structs[cname], "%s does not mirror %s" % (pyname, cname)
+
+
+def test_signatures_take_as_many_arguments_as_the_prototypes():
+    from dhts import _lib
+    protos = header_prototypes()
+    assert sorted(protos) == header_functions() == sorted(_lib.SIGNATURES)
+    for name, n in protos.items():
+        assert len(_lib.SIGNATURES[name][1]) == n, "%s: the header declares %d parameters" % (name, n)
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
+def test_structure_layout_is_the_c_compilers(tmp_path):
+    """sizeof of the mirrored structs and every field's offset and size, as the host C compiler lays the header out, against ctypes."""
+    from dhts import _lib
+    structs = header_structs()
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "dhts.h"', 'int main(void) {']
+    for cname in MIRRORS:
+        lines.append('    printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        lines += ['    printf("%s.%s %%zu+%%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (cname, f, cname, f, cname, f)
+                  for f in structs[cname]]
+    lines += ['    return 0;', '}']
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)],
+                       capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    theirs = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    ours = {}
+    for cname, pyname in MIRRORS.items():
+        st = getattr(_lib, pyname)
+        ours[cname] = str(C.sizeof(st))
+        ours.update({"%s.%s" % (cname, f): "%d+%d" % (getattr(st, f).offset, getattr(st, f).size) for f, _ in st._fields_})
+    assert ours == theirs
 
 
 def test_version_and_padding():
