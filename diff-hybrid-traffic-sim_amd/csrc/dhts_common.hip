@@ -3,8 +3,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dhts.h"
+#include "host_common.hpp"
 
-int dhts_opt_reward_chain = 0;      // DHTS_OPT_REWARD_CHAIN (dhts_set_option, macro_kernels.hip)
+int dhts_opt_reward_chain = 0;      // DHTS_OPT_REWARD_CHAIN
 
 namespace dhts {
 
@@ -68,13 +69,44 @@ int dhts_launch_reward_chain(int R, int T, int L, const float *queue, const int3
                              float *reward, int stride, void *stream) {
     if (R <= 0 || T <= 0 || L <= 0) return DHTS_OK;
     const int cut = (loss_steps > 0 && loss_steps < T) ? loss_steps : T;
-    dhts::reward_chain_kernel<<<R, 64, 0, (hipStream_t)stream>>>(T, L, queue, lane_macro, hard, dt, cut, reward, stride);
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
+    dhts::launch(dhts::reward_chain_kernel, R, 64, 0, stream, T, L, queue, lane_macro, hard, dt, cut, reward, stride);
+    return dhts::launch_status();
 }
+
+// every option, the values it takes and the variable it sets (host_common.hpp declares them; each lives with its family)
+namespace {
+struct Option { int id, lo, hi; const int *set; int *target; };      // lo .. hi, or (set != nullptr) one of set[0 .. 3]
+const int kBlockSet[4] = {0, 256, 512, 1024}, kGroupSet[4] = {0, 1, 2, 4};
+const Option kOptions[] = {
+    {DHTS_OPT_MACRO_FWD_WAVES, 0, 16, nullptr, &dhts_fwd_waves_override},
+    {DHTS_OPT_MACRO_FWD_VARIANT, 0, 2, nullptr, &dhts_fwd_variant},
+    {DHTS_OPT_MACRO_FWD_ROTATE, 0, 1, nullptr, &dhts_fwd_rotate},
+    {DHTS_OPT_MACRO_FWD_GROUP, 0, 4, kGroupSet, &dhts_fwd_group},
+    {DHTS_OPT_MICRO_FWD_WAVES, 0, 4, kGroupSet, &dhts_micro_fwd_waves_override},
+    {DHTS_OPT_NETSTEP_BLOCK, 0, 1024, kBlockSet, &dhts_netstep_block},
+    {DHTS_OPT_NETSTEP_LDS_KB, 0, 158, nullptr, &dhts_netstep_lds_kb},
+    {DHTS_OPT_HYB_PACK, 0, 2, nullptr, &dhts_hyb_pack},
+    {DHTS_OPT_REWARD_CHAIN, 0, 1, nullptr, &dhts_opt_reward_chain},
+};
+}  // namespace
 
 extern "C" {
 
 int dhts_version(void) { return DHTS_VERSION; }
+
+int dhts_set_option(int option, int value) {
+    for (const Option &o : kOptions) {
+        if (o.id != option) continue;
+        bool ok = value >= o.lo && value <= o.hi;
+        if (ok && o.set) ok = value == o.set[0] || value == o.set[1] || value == o.set[2] || value == o.set[3];
+        if (!ok) return DHTS_E_INVALID;
+        *o.target = value;
+        return DHTS_OK;
+    }
+    return DHTS_E_INVALID;
+}
+
+int dhts_padded(int n) { return dhts::padded64(n); }
 
 int dhts_device_count(void) {
     int n = 0;

@@ -481,7 +481,7 @@ __global__ void __launch_bounds__(kMaxBlock) net_hybrid_fwd_kernel(int R_, int L
     __syncthreads();
     n_macro = (int)scanw[0]; n_micro = (int)scanw[1]; n_caps = (int)scanw[2]; n_conv = (int)scanw[3];
     const int NIm = C + n_macro;                     // interfaces that exist
-    if (n_micro > kMaxMicro || n_caps > kMaxCaps || n_micro != tb.n_micro) { if (tid == 0) net_fault(err, DHTS_FAULT_CAPACITY, -1, 0, n_micro); return; }
+    if (n_micro > kMaxMicro || n_caps > kMaxCaps || n_micro != tb.n_micro) { if (tid == 0) raise_fault(err, DHTS_FAULT_CAPACITY, -1, 0, n_micro); return; }
     __syncthreads();
     (void)NI; (void)n_conv;          // (the hand-off walk visits candidates since round 4; convlist stays a set-up table)
     // ---- per-thread roles
@@ -933,11 +933,11 @@ __global__ void __launch_bounds__(kMaxBlock) net_hybrid_fwd_kernel(int R_, int L
             if (!kHard) { step_off[T + 1] = rec_n; *reinterpret_cast<int *>(wsr + ws.mode) = tb.loc_lanes | (tb.max_step_records << 8); }
             counts[4 * rep + 2] = rec_n;
         }
-        if (fl_fault) net_fault(err, DHTS_FAULT_CAPACITY, 0, 0, rec_n);
+        if (fl_fault) raise_fault(err, DHTS_FAULT_CAPACITY, 0, 0, rec_n);
     }
     if (in_mw) {
         if (is_mt) { counts[4 * rep + 0] = spawned; counts[4 * rep + 1] = deposits; counts[4 * rep + 3] = n_ev; }
-        if (rec.over || cap_fault) net_fault(err, DHTS_FAULT_CAPACITY, 0, 0, 0);
+        if (rec.over || cap_fault) raise_fault(err, DHTS_FAULT_CAPACITY, 0, 0, 0);
         if (kState && tb.veh_out) {
             // every vehicle ever spawned: gone (-1) unless a lane still lists it (one wavefront: its stores to a row stay in order)
             float *vo = tb.veh_out + (size_t)rep * 4 * V;
@@ -955,7 +955,7 @@ __global__ void __launch_bounds__(kMaxBlock) net_hybrid_fwd_kernel(int R_, int L
         for (int l = 0; l < L; ++l) rew = rew + ql[l];
         reward[rep] = rew;
     }
-    if (fault_step >= 0) net_fault(err, DHTS_FAULT_CFL, fault_step, i_lane, fault_index);
+    if (fault_step >= 0) raise_fault(err, DHTS_FAULT_CFL, fault_step, i_lane, fault_index);
 #undef LF
 #undef LI
 }
@@ -1247,8 +1247,8 @@ __global__ void __launch_bounds__(kMaxBlock) net_hybrid_bwd_kernel(int R_, int L
     }
     if (is_own && T > 0) ga += (double)gam[own_q];       // step 0's outboxes (buffer 0; the loop's last barrier is behind them)
     if (is_own && cur_phase >= 0) g_action[(size_t)rep * n_action + cur_phase * sq + own_q] = (float)ga;
-    if (bad_step >= 0) net_fault(err, DHTS_FAULT_NAN, bad_step, rep, tid);
-    if ((over && is_mt) || bad_key || (bad_mode && tid == 0)) net_fault(err, DHTS_FAULT_CAPACITY, 0, 0, bad_mode ? -3 : (bad_key ? -2 : 0));
+    if (bad_step >= 0) raise_fault(err, DHTS_FAULT_NAN, bad_step, rep, tid);
+    if ((over && is_mt) || bad_key || (bad_mode && tid == 0)) raise_fault(err, DHTS_FAULT_CAPACITY, 0, 0, bad_mode ? -3 : (bad_key ? -2 : 0));
 #undef LF
 }
 
@@ -1289,13 +1289,13 @@ static inline HybTables hyb_tables(const dhts_hybrid_tables *t) {
     h.g_stateT = nullptr; h.g_veh = nullptr; h.g_state0 = nullptr;
     return h;
 }
-int dhts_hyb_pack = 2;                           // DHTS_OPT_HYB_PACK (dhts_set_option, macro_kernels.hip): 0 never, 1 always, 2 = more replicas than CUs
+int dhts_hyb_pack = 2;                           // DHTS_OPT_HYB_PACK: 0 never, 1 always, 2 = more replicas than CUs
 constexpr size_t kHybPackBudget = 79 * 1024;     // two workgroups share a compute unit's 160 KB
 static inline int hyb_block(const dhts_net_desc *d) {
     int need = d->n_cells + d->n_lanes;
     if (need < 2 * d->n_lanes) need = 2 * d->n_lanes;
     if (need < d->n_action) need = d->n_action;
-    return ((need + 63) & ~63) + 64;               // + the micro wavefront
+    return padded64(need) + 64;                    // + the micro wavefront
 }
 
 static int hyb_cu_count() {
@@ -1317,8 +1317,11 @@ static int hyb_cu_count() {
 // most eight wavefronts, the lanes keep their default capacity of 16 vehicles (a caller climbing the capacity ladder gets
 // the full staging area back) and both plans fit.  Measured at BASELINE config 4's network, 512 / 1 024 replicas: forward 6.16 ->
 // 4.95 / 12.08 -> 9.74 ms, results bit-identical (tools/probes/exp_hyb_pack.py, profiles/r06_hyb_pack.log).
-struct HybPlan { bool packed; size_t fwd_budget; int stage_h, loc_lanes, max_rec; size_t lds_fwd, lds_bwd; int block; };
-static HybPlan hyb_plan(const dhts_net_desc *d, const dhts_hybrid_tables *t, bool state_io) {
+// may_pack = false: the forms that always take a compute unit for a replica (state io, evaluation episodes).
+// bound: the kernels' launch-bounds instantiation -- it sets the vector registers a thread may take (512 / 768 / 1024 threads: 256 /
+// 168 / 128 registers).
+struct HybPlan { bool packed; size_t fwd_budget; int stage_h, loc_lanes, max_rec; size_t lds_fwd, lds_bwd; int block, bound; };
+static HybPlan hyb_plan(const dhts_net_desc *d, const dhts_hybrid_tables *t, bool may_pack) {
     HybPlan p;
     const HybWs ws = hyb_ws(d->n_lanes, d->n_cells, d->n_steps, t->n_routes, t->records_per_step);
     const int NS = t->n_micro > kMaxCaps ? t->n_micro : kMaxCaps, lane_sh = hyb_lane_sh(t);
@@ -1327,7 +1330,7 @@ static HybPlan hyb_plan(const dhts_net_desc *d, const dhts_hybrid_tables *t, boo
     p.block = hyb_block(d);
     p.packed = false;
     const int mode = t->two_per_cu > 0 ? 1 : (t->two_per_cu < 0 ? 0 : dhts_hyb_pack);      // the tables' own word first, then the option
-    if (!state_io && p.block <= 512 && lane_sh == 4 && (mode == 1 || (mode == 2 && d->n_replicas > hyb_cu_count()))) {
+    if (may_pack && p.block <= 512 && lane_sh == 4 && (mode == 1 || (mode == 2 && d->n_replicas > hyb_cu_count()))) {
         const int h = hyb_stage_h(d->n_lanes, d->n_cells, d->n_inter_sq, ws.V, NS, d->n_action, lane_sh, kHybPackBudget);
         const int mr = NS * h < kMaxStepRecords ? NS * h : kMaxStepRecords;
         if (h >= 16 && hyb_lds_b(d->n_lanes, d->n_cells, d->n_inter_sq, ws.V, E, NS, mr).total + act <= kHybPackBudget) p.packed = true;
@@ -1338,8 +1341,12 @@ static HybPlan hyb_plan(const dhts_net_desc *d, const dhts_hybrid_tables *t, boo
     p.max_rec = p.packed ? (NS * p.stage_h < kMaxStepRecords ? NS * p.stage_h : kMaxStepRecords) : kMaxStepRecords;
     p.lds_fwd = hyb_lds(d->n_lanes, d->n_cells, d->n_inter_sq, ws.V, NS, p.stage_h, lane_sh).total + act;
     p.lds_bwd = hyb_lds_b(d->n_lanes, d->n_cells, d->n_inter_sq, ws.V, E, p.loc_lanes, p.max_rec).total + act;
+    p.bound = p.packed ? 1024 : (p.block <= 512 ? 512 : (p.block <= 768 ? 768 : 1024));
     return p;
 }
+// f(std::integral_constant<int, bound>) for the plan's launch-bounds instantiation
+template <class F>
+static bool hyb_pick_bound(const HybPlan &pl, F &&f) { return pick<512, 1024, 768>(pl.bound, f); }
 
 #ifdef DHTS_HYB_STAMPS
 extern "C" int dhts_debug_trace(int *out) {       // [2 kernels][640 steps][16 waves][5 barriers x (arrival, release)] of replica 0
@@ -1349,11 +1356,6 @@ extern "C" int dhts_debug_stamps(long long *out) {       // [2 kernels][8 replic
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(dhts::dhts_hyb_stamps), sizeof(long long) * 2 * 8 * 16 * 24) == hipSuccess ? 0 : -1;
 }
 #endif
-
-// dhts_common.hip: the reward as the reference's one float32 chain, lanes outermost (DHTS_OPT_REWARD_CHAIN)
-extern int dhts_opt_reward_chain;
-int dhts_launch_reward_chain(int R, int T, int L, const float *queue, const int32_t *lane_macro, int hard, double dt, int loss_steps,
-                             float *reward, int stride, void *stream);
 
 extern "C" {
 
@@ -1368,7 +1370,7 @@ size_t dhts_net_hybrid_workspace_bytes(const dhts_net_desc *d, const dhts_hybrid
 
 int dhts_net_hybrid_plan(const dhts_net_desc *d, const dhts_hybrid_tables *t, int32_t plan[8]) {
     if (!hyb_desc_ok(d) || !hyb_tables_ok(t) || !plan) return DHTS_E_INVALID;
-    const HybPlan p = hyb_plan(d, t, false);
+    const HybPlan p = hyb_plan(d, t, true);
     plan[0] = p.packed ? 1 : 0; plan[1] = p.block; plan[2] = p.stage_h; plan[3] = (int32_t)p.lds_fwd; plan[4] = (int32_t)p.lds_bwd;
     plan[5] = p.loc_lanes; plan[6] = p.max_rec; plan[7] = hyb_cu_count();
     return DHTS_OK;
@@ -1381,25 +1383,22 @@ static int hyb_fwd_launch(const dhts_net_desc *d, const dhts_hybrid_tables *t, c
         return DHTS_E_INVALID;
     HybTables ht = hyb_tables(t);
     if (io) { ht.plain = io->plain; ht.state0 = io->state0; ht.ghost0 = io->ghost0; ht.veh_out = io->veh_out; ht.events = io->events; }
-    const int B = hyb_block(d);
-    if (B > 1024) return DHTS_E_INVALID;
-    const HybPlan pl = hyb_plan(d, t, io != nullptr);
-    const bool pack = pl.packed;
+    const HybPlan pl = hyb_plan(d, t, io == nullptr);
+    if (pl.block > 1024) return DHTS_E_INVALID;
     ht.lds_budget = (int)pl.fwd_budget; ht.loc_lanes = pl.loc_lanes; ht.max_step_records = pl.max_rec;
     if (pl.stage_h < 8) return DHTS_E_INVALID;       // (a lane with one vehicle stages ~10 records in a step with a hand-off)
-    const size_t lds = pl.lds_fwd;
-    if (lds > 160 * 1024) return DHTS_E_INVALID;
-    // (the block-size bound sets the vector registers a thread may take: 256 / 168 / 128)
-    auto kern = io ? (B <= 512 ? net_hybrid_fwd_kernel<512, false, true> : (B <= 768 ? net_hybrid_fwd_kernel<768, false, true> : net_hybrid_fwd_kernel<1024, false, true>))
-                   : (pack ? net_hybrid_fwd_kernel<1024, false> : (B <= 512 ? net_hybrid_fwd_kernel<512, false> : (B <= 768 ? net_hybrid_fwd_kernel<768, false> : net_hybrid_fwd_kernel<1024, false>)));
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_LAUNCH;
-    kern<<<d->n_replicas, B, lds, (hipStream_t)stream>>>(
-        d->n_replicas, d->n_lanes, d->n_cells, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt, d->u_max,
-        d->static_speed, d->vehicle_length, ht, action, hist, reinterpret_cast<float4 *>(tape), kc, queue, reward,
-        counts, reinterpret_cast<char *>(workspace), t->records_per_step, err);
-    if (hipGetLastError() != hipSuccess) return DHTS_E_LAUNCH;
+    if (pl.lds_fwd > 160 * 1024) return DHTS_E_INVALID;
+    bool lds_ok = true;
+    pick<0, 1>(io != nullptr, [&](auto sio) {
+        hyb_pick_bound(pl, [&](auto mb) {
+            lds_ok = launch_lds(net_hybrid_fwd_kernel<decltype(mb)::value, false, decltype(sio)::value != 0>, d->n_replicas, pl.block, pl.lds_fwd,
+                                kLdsDefault, stream, d->n_replicas, d->n_lanes, d->n_cells, d->n_steps, d->n_inter_sq, d->frames_per_phase,
+                                d->n_action, d->dt, d->u_max, d->static_speed, d->vehicle_length, ht, action, hist,
+                                reinterpret_cast<float4 *>(tape), kc, queue, reward, counts, reinterpret_cast<char *>(workspace),
+                                t->records_per_step, err);
+        });
+    });
+    if (!lds_ok || launch_status() != DHTS_OK) return DHTS_E_LAUNCH;
     // (the state form's reward is a by-product nobody reads: plain networks have no loss)
     if (dhts_opt_reward_chain && !io) return dhts_launch_reward_chain(d->n_replicas, d->n_steps, d->n_lanes, queue, t->lane_macro, 0, d->dt, 0, reward, 1, stream);
     return DHTS_OK;
@@ -1419,23 +1418,18 @@ int dhts_net_hybrid_state_rollout_fwd(const dhts_net_desc *d, const dhts_hybrid_
 int dhts_net_hybrid_rollout_eval(const dhts_net_desc *d, const dhts_hybrid_tables *t, const float *action, float *queue,
                                  float *reward, int32_t *counts, dhts_error *err, void *stream) {
     if (!hyb_desc_ok(d) || !hyb_tables_ok(t) || !action || !queue || !reward || !counts) return DHTS_E_INVALID;
-    const int B = hyb_block(d);
-    if (B > 1024) return DHTS_E_INVALID;
-    const HybWs ws = hyb_ws(d->n_lanes, d->n_cells, d->n_steps, t->n_routes, t->records_per_step);
-    const int NS = t->n_micro > kMaxCaps ? t->n_micro : kMaxCaps;
-    const int stage_h = hyb_stage_h(d->n_lanes, d->n_cells, d->n_inter_sq, ws.V, NS, d->n_action, hyb_lane_sh(t));
-    if (stage_h < 8) return DHTS_E_INVALID;       // (a lane with one vehicle stages ~10 records in a step with a hand-off)
-    const size_t lds = hyb_lds(d->n_lanes, d->n_cells, d->n_inter_sq, ws.V, NS, stage_h, hyb_lane_sh(t)).total + up16(sizeof(float) * (size_t)d->n_action);
-    if (lds > 160 * 1024) return DHTS_E_INVALID;
-    auto kern = B <= 512 ? net_hybrid_fwd_kernel<512, true> : (B <= 768 ? net_hybrid_fwd_kernel<768, true> : net_hybrid_fwd_kernel<1024, true>);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_LAUNCH;
-    kern<<<d->n_replicas, B, lds, (hipStream_t)stream>>>(
-        d->n_replicas, d->n_lanes, d->n_cells, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt, d->u_max,
-        d->static_speed, d->vehicle_length, hyb_tables(t), action, nullptr, nullptr, nullptr, queue, reward, counts, nullptr,
-        t->records_per_step, err);
-    if (hipGetLastError() != hipSuccess) return DHTS_E_LAUNCH;
+    const HybPlan pl = hyb_plan(d, t, false);
+    if (pl.block > 1024) return DHTS_E_INVALID;
+    if (pl.stage_h < 8) return DHTS_E_INVALID;       // (a lane with one vehicle stages ~10 records in a step with a hand-off)
+    if (pl.lds_fwd > 160 * 1024) return DHTS_E_INVALID;
+    bool lds_ok = true;
+    hyb_pick_bound(pl, [&](auto mb) {
+        lds_ok = launch_lds(net_hybrid_fwd_kernel<decltype(mb)::value, true>, d->n_replicas, pl.block, pl.lds_fwd, kLdsDefault, stream,
+                            d->n_replicas, d->n_lanes, d->n_cells, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt,
+                            d->u_max, d->static_speed, d->vehicle_length, hyb_tables(t), action, nullptr, nullptr, nullptr, queue, reward,
+                            counts, nullptr, t->records_per_step, err);
+    });
+    if (!lds_ok || launch_status() != DHTS_OK) return DHTS_E_LAUNCH;
     if (dhts_opt_reward_chain) return dhts_launch_reward_chain(d->n_replicas, d->n_steps, d->n_lanes, queue, t->lane_macro, 1, d->dt, 0, reward, 1, stream);
     return DHTS_OK;
 }
@@ -1447,23 +1441,22 @@ static int hyb_bwd_launch(const dhts_net_desc *d, const dhts_hybrid_tables *t, i
         return DHTS_E_INVALID;
     HybTables ht = hyb_tables(t);
     ht.plain = plain; ht.g_stateT = g_stateT; ht.g_veh = g_veh; ht.g_state0 = g_state0;
-    const int B = hyb_block(d);
-    if (B > 1024) return DHTS_E_INVALID;
     const bool state_io = plain || g_stateT || g_veh || g_state0;
-    const HybPlan pl = hyb_plan(d, t, state_io);
+    const HybPlan pl = hyb_plan(d, t, !state_io);
+    if (pl.block > 1024) return DHTS_E_INVALID;
     ht.loc_lanes = pl.loc_lanes; ht.max_step_records = pl.max_rec;
-    const size_t lds = pl.lds_bwd;
-    if (lds > 160 * 1024) return DHTS_E_INVALID;
-    auto kern = state_io ? (B <= 512 ? net_hybrid_bwd_kernel<512, true> : (B <= 768 ? net_hybrid_bwd_kernel<768, true> : net_hybrid_bwd_kernel<1024, true>))
-                         : (pl.packed ? net_hybrid_bwd_kernel<1024> : (B <= 512 ? net_hybrid_bwd_kernel<512> : (B <= 768 ? net_hybrid_bwd_kernel<768> : net_hybrid_bwd_kernel<1024>)));
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_LAUNCH;
-    kern<<<d->n_replicas, B, lds, (hipStream_t)stream>>>(
-        d->n_replicas, d->n_lanes, d->n_cells, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt, d->u_max,
-        d->static_speed, d->vehicle_length, ht, action, hist, reinterpret_cast<const float4 *>(tape), kc, queue,
-        g_reward, g_action, reinterpret_cast<const char *>(workspace), t->records_per_step, err);
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
+    if (pl.lds_bwd > 160 * 1024) return DHTS_E_INVALID;
+    bool lds_ok = true;
+    pick<0, 1>(state_io, [&](auto sio) {
+        hyb_pick_bound(pl, [&](auto mb) {
+            lds_ok = launch_lds(net_hybrid_bwd_kernel<decltype(mb)::value, decltype(sio)::value != 0>, d->n_replicas, pl.block, pl.lds_bwd,
+                                kLdsDefault, stream, d->n_replicas, d->n_lanes, d->n_cells, d->n_steps, d->n_inter_sq, d->frames_per_phase,
+                                d->n_action, d->dt, d->u_max, d->static_speed, d->vehicle_length, ht, action, hist,
+                                reinterpret_cast<const float4 *>(tape), kc, queue, g_reward, g_action,
+                                reinterpret_cast<const char *>(workspace), t->records_per_step, err);
+        });
+    });
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 int dhts_net_hybrid_rollout_bwd(const dhts_net_desc *d, const dhts_hybrid_tables *t, const float *action, const float *hist,
                                 const float *tape, const float *kc, const float *queue, const float *g_reward,

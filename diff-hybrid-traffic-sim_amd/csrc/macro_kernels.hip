@@ -18,6 +18,7 @@
 
 #include "../../include/dhts.h"
 #include "arz_device.hpp"
+#include "host_common.hpp"
 
 namespace dhts {
 
@@ -41,15 +42,6 @@ __device__ __forceinline__ double bcast0(double x) {
     int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll));
     int hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ void raise_fault(dhts_error *err, int code, int step, int lane, int index) {
-    if (err == nullptr) return;
-    if (atomicCAS(&err->code, 0, code) == 0) {
-        err->step = step;
-        err->lane = lane;
-        err->index = index;
-    }
 }
 
 // ---- the rollout tape -----------------------------------------------------------------------------------------------
@@ -1215,35 +1207,15 @@ using namespace dhts;
 static inline bool macro_desc_ok(const dhts_macro_desc *d) {
     return d && d->n_lanes > 0 && d->n_cells > 0 && d->n_cells <= DHTS_MACRO_MAX_CELLS && d->dt > 0 && d->dx > 0 && d->u_max > 0;
 }
-static inline int launch_status() { return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH; }
-static inline int grid_1d(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
+// test / tuning hooks (dhts_set_option, dhts_common.hip): force the number of wavefronts per lane of the forward kernel (0 = heuristic);
+// select the rollout forward kernel (0 = two-phase kernels, 1 = the one-phase kernel the single-step operator uses, 2 = no pair kernel)
+int dhts_fwd_waves_override = 0;
+int dhts_fwd_variant = 0;
+int dhts_fwd_rotate = 1;        // DHTS_OPT_MACRO_FWD_ROTATE: priority rotation between the two halves of the pair kernel's grid
+int dhts_fwd_group = 0;         // DHTS_OPT_MACRO_FWD_GROUP: traffic lanes per workgroup in the two-phase forward kernel (0 = heuristic)
 
-// test / tuning hooks: force the number of wavefronts per lane of the forward kernel (0 = heuristic); select the rollout
-// forward kernel (0 = two-phase kernel, 1 = the one-phase kernel the single-step operator uses)
-static int dhts_fwd_waves_override = 0;
-static int dhts_fwd_variant = 0;
-static int dhts_fwd_rotate = 1;        // DHTS_OPT_MACRO_FWD_ROTATE: priority rotation between the two halves of the pair kernel's grid
-static int dhts_fwd_group = 0;         // DHTS_OPT_MACRO_FWD_GROUP: traffic lanes per workgroup in the two-phase forward kernel (0 = heuristic)
-static inline int padded64(int n) { return (n + 63) & ~63; }
-
-// Wavefronts per lane of the two-phase forward kernel: two 64-cell passes per wavefront whenever the lane fits 16 of them -- the
-// two passes of a thread are independent instruction streams, and at 1024 x 512 the four-wave workgroups of all lanes are
-// resident at once (4 per CU) instead of taking two rounds.  Measured (tools/sweep_fwd_waves.py, forward ms for 1 / 2 / 4 / 8 /
-// 16 waves per lane; literal pass counts 1, 2, run-time above):
-//   1024 x 512: 7.5 / 3.95 / 3.50 / 4.07 / -      4096 x 256: 9.3 / 7.50 / 7.93 / - / -      256 x 2048: 19.6 / 10.7 / 6.0 / 4.09 / 3.54
-static void macro_fwd2_plan(int N, int &W, int &p) {
-    W = dhts_fwd_waves_override > 0 ? dhts_fwd_waves_override : (N + 127) / 128;
-    if (W > 16) W = 16;
-    if (W < 1) W = 1;
-    p = (N + 64 * W - 1) / (64 * W);
-    W = (N + 64 * p - 1) / (64 * p);
-}
-static inline bool macro_fwd2_fits(const dhts_macro_desc *d) {
-    return d && sizeof(CellRec) * (size_t)(d->n_cells + 2) + 16 * (size_t)(d->n_cells + 1) + sizeof(int) * (size_t)(d->n_cells + 2) + 16 <=
-                    160 * 1024;
+static inline size_t fwd2_lds_bytes(int N) {
+    return sizeof(CellRec) * (size_t)(N + 2) + 16 * (size_t)(N + 1) + sizeof(int) * (size_t)(N + 2) + 16;
 }
 // The pair kernel (macro_fwd_pairs.inc) takes full lanes of 128 W cells without a state history; traffic lanes per workgroup as
 // for the lane-group kernel (four up to three wavefronts per lane, else two; one where the launch would leave CUs without a
@@ -1261,64 +1233,93 @@ static inline int macro_fwd3_group(const dhts_macro_desc *d, bool want_hist) {
     if ((size_t)G * fwd3_region_bytes(d->n_cells) > 160 * 1024) return 0;
     return G;
 }
-static inline int macro_bwd_fast_block(int N) { return N <= 64 ? 64 : (N <= 128 ? 128 : (N <= 256 ? 256 : (N <= 512 ? 512 : 1024))); }
-static inline bool macro_bwd_is_fast(int N, int T) { return N >= 2 && N <= 1024 && T > 0; }      // (T = 0: no tape to prefetch from)
-// the two-cells-per-thread sweep (1024 threads): lanes of 1026 .. 2048 cells without per-step cotangents (the step tag has 20 bits)
-static inline bool macro_bwd_is_fast2(int N, int T, bool want_hist) { return N > 1025 && N <= 2048 && T > 0 && T < (1 << 20) - 1 && !want_hist; }
 
-static int macro_fwd2_launch(const dhts_macro_desc *d, int T,
+// Which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for a shape, decided here once: the launches switch on these fields
+// and dhts_macro_rollout_plan copies them out.
+enum { kMacroFwdLane = 0, kMacroFwdOnePhase = 1, kMacroFwdPair = 2 };      // plan[0]
+enum { kMacroBwdGeneral = 0, kMacroBwdFast = 1, kMacroBwdFast2 = 2 };      // plan[4]
+struct MacroPlan {
+    bool hist, tape;      // what the caller asks for: the state history resp. per-step cotangents; the tape
+    int fwd;              // forward kernel
+    int W, p;             // two-phase kernels: wavefronts per lane, 64-cell passes per wavefront (0, 0: the one-phase kernel plans its own)
+    bool dense;           // two-phase kernels: every thread-pass owns a cell, no history (kFull)
+    int G;                // traffic lanes per workgroup (the pair kernel; 1 otherwise)
+    size_t lds_fwd;       // two-phase kernels
+    int bwd, bwd_block;   // reverse kernel and its threads per lane
+    bool bwd_full;        // fast: N = block (128 .. 512, no per-step cotangents); fast2: N = 2 x block
+    size_t lds_bwd;
+};
+static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, bool want_tape) {
+    MacroPlan pl = {};
+    const int N = d->n_cells;
+    pl.hist = want_hist; pl.tape = want_tape; pl.G = 1;
+    // lanes whose records do not fit the two-phase kernels' LDS take the one-phase kernel (same tape format)
+    if (dhts_fwd_variant == 1 || fwd2_lds_bytes(N) > 160 * 1024) {
+        pl.fwd = kMacroFwdOnePhase;
+    } else {
+        // Wavefronts per lane of the two-phase forward kernel: two 64-cell passes per wavefront whenever the lane fits 16 of them -- the
+        // two passes of a thread are independent instruction streams, and at 1024 x 512 the four-wave workgroups of all lanes are
+        // resident at once (4 per CU) instead of taking two rounds.  Measured (tools/sweep_fwd_waves.py, forward ms for 1 / 2 / 4 / 8 /
+        // 16 waves per lane; literal pass counts 1, 2, run-time above):
+        //   1024 x 512: 7.5 / 3.95 / 3.50 / 4.07 / -      4096 x 256: 9.3 / 7.50 / 7.93 / - / -      256 x 2048: 19.6 / 10.7 / 6.0 / 4.09 / 3.54
+        int W = dhts_fwd_waves_override > 0 ? dhts_fwd_waves_override : (N + 127) / 128;
+        if (W > 16) W = 16;
+        if (W < 1) W = 1;
+        pl.p = (N + 64 * W - 1) / (64 * W);
+        pl.W = (N + 64 * pl.p - 1) / (64 * pl.p);
+        pl.dense = (pl.p == 1 || pl.p == 2) && N == 64 * pl.p * pl.W && !want_hist;
+        const int G = macro_fwd3_group(d, want_hist);
+        pl.fwd = G > 0 ? kMacroFwdPair : kMacroFwdLane;
+        if (G > 0) pl.G = G;
+        pl.lds_fwd = G > 0 ? (size_t)G * fwd3_region_bytes(N) : fwd2_lds_bytes(N);
+    }
+    if (N >= 2 && N <= 1024 && T > 0) {       // (T = 0: no tape to prefetch from)
+        pl.bwd = kMacroBwdFast;
+        pl.bwd_block = N <= 64 ? 64 : (N <= 128 ? 128 : (N <= 256 ? 256 : (N <= 512 ? 512 : 1024)));
+        pl.bwd_full = !want_hist && N == pl.bwd_block && N >= 128 && N <= 512;
+        pl.lds_bwd = bwd_fast_lds_bytes(pl.bwd_block);
+    } else if (N > 1025 && N <= 2048 && T > 0 && T < (1 << 20) - 1 && !want_hist) {
+        // the two-cells-per-thread sweep (1024 threads): lanes of 1026 .. 2048 cells without per-step cotangents (the step tag has 20 bits)
+        pl.bwd = kMacroBwdFast2;
+        pl.bwd_block = 1024;
+        pl.bwd_full = N == 2048;
+        pl.lds_bwd = bwd_fast2_lds_bytes(1024);
+    } else {
+        pl.bwd = kMacroBwdGeneral;
+        pl.bwd_block = padded64(N) > 512 ? 512 : padded64(N);
+        pl.lds_bwd = sizeof(float) * (size_t)((6 * (N + 2) + 3) & ~3) + 2 * (size_t)(N + 1);
+    }
+    return pl;
+}
+
+// the two-phase kernels (the caller has checked its arguments)
+static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int T,
                              const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                              float *r_out, float *y_out, float *u_out, float *ueq_out,
                              float *tape, float *hist, dhts_error *err, void *stream) {
-    if (!macro_desc_ok(d) || T < 0 || !r || !y || !u || !ueq || !ghost || !r_out || !y_out || !u_out || !ueq_out)
-        return DHTS_E_INVALID;
     const int N = d->n_cells;
-    const size_t lds = sizeof(CellRec) * (size_t)(N + 2) + 16 * (size_t)(N + 1) + sizeof(int) * (size_t)(N + 2) + 16;
-    if (lds > 160 * 1024) return DHTS_E_INVALID;
-    if (lds > 64 * 1024 &&
-        (hipFuncSetAttribute((const void *)macro_rollout_fwd2_kernel<1, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-         hipFuncSetAttribute((const void *)macro_rollout_fwd2_kernel<2, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-         hipFuncSetAttribute((const void *)macro_rollout_fwd2_kernel<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-         hipFuncSetAttribute((const void *)macro_rollout_fwd2_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-         hipFuncSetAttribute((const void *)macro_rollout_fwd2_kernel<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess))
-        return DHTS_E_LAUNCH;
-    int W, p;
-    macro_fwd2_plan(N, W, p);
-#define DHTS_FWD2_ARGS d->n_lanes, N, T, p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, \
-                       reinterpret_cast<float4 *>(tape), hist, err
-    const int G3 = macro_fwd3_group(d, hist != nullptr);
-    if (G3 > 0) {
+    float4 *tp = reinterpret_cast<float4 *>(tape);
+    bool lds_ok = true;
+    if (pl.fwd == kMacroFwdLane) {
+        // <kP, kFull, kHist> as 10 kP + kFull (kHist = !kFull); kP = 0: the run-time pass count
+        pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
+            constexpr int kV = decltype(v)::value;
+            lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0>, d->n_lanes, 64 * pl.W, pl.lds_fwd, kLdsDefault,
+                                stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tp,
+                                hist, err);
+        });
+    } else {
         // the pair kernel: a thread owns two adjacent cells and their right interfaces (macro_fwd_pairs.inc)
-        const size_t ldsg = (size_t)G3 * fwd3_region_bytes(N);
-#define DHTS_FWD3_ARGS d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float4 *>(tape), err, dhts_fwd_rotate
-#define DHTS_FWDG_ARGS d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float4 *>(tape), err
-#define DHTS_FWD3(GG, TT)                                                                                                         \
-    {                                                                                                                             \
-        if (ldsg > 64 * 1024 && hipFuncSetAttribute((const void *)macro_rollout_fwd3_kernel<GG, TT>,                              \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg) != hipSuccess)         \
-            return DHTS_E_LAUNCH;                                                                                                 \
-        macro_rollout_fwd3_kernel<GG, TT><<<d->n_lanes / GG, 64 * GG * (N / 128), ldsg, (hipStream_t)stream>>>(DHTS_FWD3_ARGS);    \
+        pick<4, 2, 1>(pl.G, [&](auto g) {
+            pick<0, 1>(pl.tape, [&](auto tp_) {
+                constexpr int kG = decltype(g)::value;
+                lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0>, d->n_lanes / kG, 64 * kG * (N / 128), pl.lds_fwd,
+                                    kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out,
+                                    ueq_out, tp, err, dhts_fwd_rotate);
+            });
+        });
     }
-        if (G3 == 1 && tape) DHTS_FWD3(1, true)
-        else if (G3 == 1) DHTS_FWD3(1, false)
-        else if (G3 == 2 && tape) DHTS_FWD3(2, true)
-        else if (G3 == 2) DHTS_FWD3(2, false)
-        else if (tape) DHTS_FWD3(4, true)
-        else DHTS_FWD3(4, false)
-#undef DHTS_FWD3
-#undef DHTS_FWDG_ARGS
-    } else if (p == 1 && N == 64 * W && hist == nullptr)
-        macro_rollout_fwd2_kernel<1, true, false><<<d->n_lanes, 64 * W, lds, (hipStream_t)stream>>>(DHTS_FWD2_ARGS);
-    else if (p == 2 && N == 128 * W && hist == nullptr)
-        macro_rollout_fwd2_kernel<2, true, false><<<d->n_lanes, 64 * W, lds, (hipStream_t)stream>>>(DHTS_FWD2_ARGS);
-    else if (p == 1)
-        macro_rollout_fwd2_kernel<1, false, true><<<d->n_lanes, 64 * W, lds, (hipStream_t)stream>>>(DHTS_FWD2_ARGS);
-    else if (p == 2)
-        macro_rollout_fwd2_kernel<2, false, true><<<d->n_lanes, 64 * W, lds, (hipStream_t)stream>>>(DHTS_FWD2_ARGS);
-    else
-        macro_rollout_fwd2_kernel<0, false, true><<<d->n_lanes, 64 * W, lds, (hipStream_t)stream>>>(DHTS_FWD2_ARGS);
-#undef DHTS_FWD2_ARGS
-    return launch_status();
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
 template <bool kIface>
@@ -1330,9 +1331,6 @@ static int macro_fwd_launch(const dhts_macro_desc *d, int T,
         return DHTS_E_INVALID;
     const int N = d->n_cells;
     const size_t lds = sizeof(float) * 8 * (size_t)(N + 2);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)macro_rollout_fwd_kernel<kIface>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_LAUNCH;
     // Waves per lane: about 5 wavefronts on every SIMD of the chip (256 CUs x 4 SIMDs) when there are few lanes, 2 per lane
     // when there are many, at most 8, and never more than the lane has 63-cell chunks (p = passes per wave, chunk = 64 p - 1
     // cells).  Measured forward times in ms for waves per lane 1 / 2 / 3 / 5 / 8 (tools/sweep_fwd_waves.py, 1000 steps):
@@ -1346,9 +1344,9 @@ static int macro_fwd_launch(const dhts_macro_desc *d, int T,
     int p = 1;
     while ((N + (64 * p - 1) - 1) / (64 * p - 1) > W) ++p;
     W = (N + (64 * p - 1) - 1) / (64 * p - 1);
-    macro_rollout_fwd_kernel<kIface><<<d->n_lanes, 64 * W, lds, (hipStream_t)stream>>>(
-        d->n_lanes, N, T, p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out,
-        reinterpret_cast<float4 *>(tape), hist, err);
+    if (!launch_lds(macro_rollout_fwd_kernel<kIface>, d->n_lanes, 64 * W, lds, kLdsDefault, stream, d->n_lanes, N, T, p, d->dt, d->dx, d->u_max,
+                    r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float4 *>(tape), hist, err))
+        return DHTS_E_LAUNCH;
     return launch_status();
 }
 static int macro_blocks_bwd_launch(const dhts_macro_desc *d, int T, const float *tape,
@@ -1358,77 +1356,41 @@ static int macro_blocks_bwd_launch(const dhts_macro_desc *d, int T, const float 
     const size_t lds = sizeof(float) * 6 * (size_t)(d->n_cells + 2);
     int B = padded64(d->n_cells);
     if (B > 512) B = 512;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)macro_blocks_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (!launch_lds(macro_blocks_bwd_kernel, d->n_lanes, B, lds, kLdsDefault, stream, d->n_lanes, d->n_cells, T,
+                    reinterpret_cast<const float4 *>(tape), g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err))
         return DHTS_E_LAUNCH;
-    macro_blocks_bwd_kernel<<<d->n_lanes, B, lds, (hipStream_t)stream>>>(
-        d->n_lanes, d->n_cells, T, reinterpret_cast<const float4 *>(tape), g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err);
     return launch_status();
 }
 static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float *tape,
                                     const float *g_r, const float *g_y, const float *g_hist,
                                     float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
     if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out) return DHTS_E_INVALID;
-    const int N = d->n_cells;
-    int B = padded64(N);
-    if (B > 512) B = 512;
-    if (macro_bwd_is_fast(N, T)) {
-        const int kB = macro_bwd_fast_block(N);
-        const size_t lds = bwd_fast_lds_bytes(kB);
-        if (kB == 1024 &&
-            (hipFuncSetAttribute((const void *)macro_rollout_bwd_fast_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds) != hipSuccess ||
-             hipFuncSetAttribute((const void *)macro_rollout_bwd_fast_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds) != hipSuccess))
-            return DHTS_E_LAUNCH;
-        const float4 *tp = reinterpret_cast<const float4 *>(tape);
-        const double cc = d->dt / d->dx;
-        hipStream_t st = (hipStream_t)stream;
-#define DHTS_BWD_FAST(KB)                                                                                                        \
-    if (g_hist)                                                                                                                  \
-        macro_rollout_bwd_fast_kernel<KB, true><<<d->n_lanes, KB, lds, st>>>(d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, \
-                                                                             g_y_out, g_ghost, err);                            \
-    else if (N == KB && KB >= 128 && KB <= 512)                                                                                  \
-        macro_rollout_bwd_fast_kernel<KB, false, true><<<d->n_lanes, KB, lds, st>>>(d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist,   \
-                                                                                    g_r_out, g_y_out, g_ghost, err);            \
-    else                                                                                                                         \
-        macro_rollout_bwd_fast_kernel<KB, false><<<d->n_lanes, KB, lds, st>>>(d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, \
-                                                                              g_y_out, g_ghost, err);
-        if (kB == 64) { DHTS_BWD_FAST(64) }
-        else if (kB == 128) { DHTS_BWD_FAST(128) }
-        else if (kB == 256) { DHTS_BWD_FAST(256) }
-        else if (kB == 512) { DHTS_BWD_FAST(512) }
-        else { DHTS_BWD_FAST(1024) }
-#undef DHTS_BWD_FAST
-        return launch_status();
+    const MacroPlan pl = macro_plan(d, T, g_hist != nullptr, tape != nullptr);
+    const int N = d->n_cells, B = pl.bwd_block;
+    const float4 *tp = reinterpret_cast<const float4 *>(tape);
+    const double cc = d->dt / d->dx;
+    if (pl.lds_bwd > 160 * 1024) return DHTS_E_INVALID;
+    bool lds_ok = true;
+    if (pl.bwd == kMacroBwdFast) {
+        // <kB, kHist, kFull> as 10 kB + (0 plain, 1 kHist, 2 kFull).  The list holds every instantiation the library has always had, in
+        // the order that keeps them where they have always been in the code object (last entry first).
+        pick<10242, 5120, 5122, 5121, 2560, 2562, 2561, 1280, 1282, 1281, 640, 642, 641, 10241, 10240>(
+            10 * B + (pl.hist ? 1 : (pl.bwd_full ? 2 : 0)), [&](auto v) {
+                constexpr int kV = decltype(v)::value;
+                lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, kV % 10 == 1, kV % 10 == 2>, d->n_lanes, B, pl.lds_bwd, kLdsDefault,
+                                    stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err);
+            });
+    } else if (pl.bwd == kMacroBwdFast2) {
+        pick<0, 1>(pl.bwd_full, [&](auto full) {
+            lds_ok = launch_lds(macro_rollout_bwd_fast2_kernel<1024, decltype(full)::value != 0>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream,
+                                d->n_lanes, N, T, cc, tp, g_r, g_y, g_r_out, g_y_out, g_ghost, err);
+        });
+    } else {
+        lds_ok = launch_lds(macro_rollout_bwd_kernel, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist,
+                            g_r_out, g_y_out, g_ghost, err);
     }
-    if (macro_bwd_is_fast2(N, T, g_hist != nullptr)) {
-        const size_t lds2 = bwd_fast2_lds_bytes(1024);
-        const float4 *tp = reinterpret_cast<const float4 *>(tape);
-        if (N == 2048) {
-            if (hipFuncSetAttribute((const void *)macro_rollout_bwd_fast2_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-                return DHTS_E_LAUNCH;
-            macro_rollout_bwd_fast2_kernel<1024, true><<<d->n_lanes, 1024, lds2, (hipStream_t)stream>>>(d->n_lanes, N, T, d->dt / d->dx, tp, g_r, g_y, g_r_out,
-                                                                                                     g_y_out, g_ghost, err);
-        } else {
-            if (hipFuncSetAttribute((const void *)macro_rollout_bwd_fast2_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-                return DHTS_E_LAUNCH;
-            macro_rollout_bwd_fast2_kernel<1024, false><<<d->n_lanes, 1024, lds2, (hipStream_t)stream>>>(d->n_lanes, N, T, d->dt / d->dx, tp, g_r, g_y, g_r_out,
-                                                                                                      g_y_out, g_ghost, err);
-        }
-        return launch_status();
-    }
-    const size_t lds = sizeof(float) * (size_t)((6 * (N + 2) + 3) & ~3) + 2 * (size_t)(N + 1);
-    if (lds > 160 * 1024) return DHTS_E_INVALID;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)macro_rollout_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_LAUNCH;
-    macro_rollout_bwd_kernel<<<d->n_lanes, B, lds, (hipStream_t)stream>>>(
-        d->n_lanes, N, T, d->dt / d->dx, reinterpret_cast<const float4 *>(tape), g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err);
-    return launch_status();
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
-
-extern int dhts_micro_fwd_waves_override;     // micro_kernels.hip
 
 #ifdef DHTS_FWD3_STAMPS
 extern "C" int dhts_debug_fwd_clock(long long *out) {         // [2 kernels][16 workgroups][2]
@@ -1439,53 +1401,7 @@ extern "C" int dhts_debug_fwd3_stamps(long long *out) {       // [16 workgroups]
 }
 #endif
 
-extern int dhts_netstep_lds_kb, dhts_netstep_block;      // netstep_hybrid.hip
-extern int dhts_hyb_pack;                                // hybrid_kernels.hip
-extern int dhts_opt_reward_chain;                        // dhts_common.hip
-
 extern "C" {
-
-int dhts_set_option(int option, int value) {
-    if (option == DHTS_OPT_MACRO_FWD_WAVES && value >= 0 && value <= 16) {
-        dhts_fwd_waves_override = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_MACRO_FWD_VARIANT && value >= 0 && value <= 2) {
-        dhts_fwd_variant = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_MACRO_FWD_ROTATE && (value == 0 || value == 1)) {
-        dhts_fwd_rotate = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_NETSTEP_BLOCK && (value == 0 || value == 256 || value == 512 || value == 1024)) {
-        dhts_netstep_block = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_NETSTEP_LDS_KB && (value == 0 || (value >= 1 && value <= 158))) {
-        dhts_netstep_lds_kb = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_REWARD_CHAIN && (value == 0 || value == 1)) {
-        dhts_opt_reward_chain = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_HYB_PACK && value >= 0 && value <= 2) {
-        dhts_hyb_pack = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_MACRO_FWD_GROUP && (value == 0 || value == 1 || value == 2 || value == 4)) {
-        dhts_fwd_group = value;
-        return DHTS_OK;
-    }
-    if (option == DHTS_OPT_MICRO_FWD_WAVES && (value == 0 || value == 1 || value == 2 || value == 4)) {
-        dhts_micro_fwd_waves_override = value;
-        return DHTS_OK;
-    }
-    return DHTS_E_INVALID;
-}
-
-int dhts_padded(int n) { return (n + 63) & ~63; }
 
 size_t dhts_macro_tape_bytes(const dhts_macro_desc *d, int T) {
     if (!macro_desc_ok(d) || T < 0) return 0;
@@ -1493,7 +1409,7 @@ size_t dhts_macro_tape_bytes(const dhts_macro_desc *d, int T) {
 }
 size_t dhts_macro_step_tape_bytes(const dhts_macro_desc *d) {
     if (!macro_desc_ok(d)) return 0;
-    return (size_t)d->n_lanes * 3 * dhts_padded(d->n_cells) * sizeof(float4);
+    return (size_t)d->n_lanes * 3 * padded64(d->n_cells) * sizeof(float4);
 }
 
 int dhts_arz_interface_batch(int64_t n, int variant, const double *in, double dt, double dx, int32_t *case_ind, double *q0,
@@ -1502,7 +1418,7 @@ int dhts_arz_interface_batch(int64_t n, int variant, const double *in, double dt
     if (n < 0 || (variant != 0 && variant != 1) || !in || !case_ind || !q0 || !flux || !dL || !dR || !fp || !A || !B || !cfl_bad)
         return DHTS_E_INVALID;
     if (n == 0) return DHTS_OK;
-    arz_interface_batch_kernel<<<grid_1d(n), 256, 0, (hipStream_t)stream>>>(n, variant, in, dt, dx, case_ind, q0, flux, dL, dR, fp,
+    launch(arz_interface_batch_kernel, grid_1d(n), 256, 0, stream, n, variant, in, dt, dx, case_ind, q0, flux, dL, dR, fp,
                                                                           A, B, cfl_bad, speed);
     return launch_status();
 }
@@ -1510,21 +1426,21 @@ int dhts_arz_interface_batch(int64_t n, int variant, const double *in, double dt
 int dhts_macro_state_from_ru(int64_t n, double u_max, const float *r, const float *u, float *y, float *ueq, void *stream) {
     if (n < 0 || !r || !u || !y || !ueq) return DHTS_E_INVALID;
     if (n == 0) return DHTS_OK;
-    macro_state_from_ru_kernel<<<grid_1d(n), 256, 0, (hipStream_t)stream>>>(n, (float)u_max, r, u, y, ueq);
+    launch(macro_state_from_ru_kernel, grid_1d(n), 256, 0, stream, n, (float)u_max, r, u, y, ueq);
     return launch_status();
 }
 int dhts_macro_state_from_ru_bwd(int64_t n, double u_max, const float *r, const float *u, const float *g_y,
                                  float *g_r, float *g_u, void *stream) {
     if (n < 0 || !r || !u || !g_y || !g_r || !g_u) return DHTS_E_INVALID;
     if (n == 0) return DHTS_OK;
-    macro_state_from_ru_bwd_kernel<<<grid_1d(n), 256, 0, (hipStream_t)stream>>>(n, (float)u_max, r, u, g_y, g_r, g_u);
+    launch(macro_state_from_ru_bwd_kernel, grid_1d(n), 256, 0, stream, n, (float)u_max, r, u, g_y, g_r, g_u);
     return launch_status();
 }
 int dhts_macro_u_tap_bwd(int64_t n, double u_max, const float *r, const float *y, const float *g_u,
                          float *g_r, float *g_y, void *stream) {
     if (n < 0 || !r || !y || !g_u || !g_r || !g_y) return DHTS_E_INVALID;
     if (n == 0) return DHTS_OK;
-    macro_u_tap_bwd_kernel<<<grid_1d(n), 256, 0, (hipStream_t)stream>>>(n, (float)u_max, r, y, g_u, g_r, g_y);
+    launch(macro_u_tap_bwd_kernel, grid_1d(n), 256, 0, stream, n, (float)u_max, r, y, g_u, g_r, g_y);
     return launch_status();
 }
 
@@ -1533,43 +1449,31 @@ int dhts_macro_rollout_fwd(const dhts_macro_desc *d, int T,
                            const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                            float *r_out, float *y_out, float *u_out, float *ueq_out,
                            float *tape, float *hist, dhts_error *err, void *stream) {
-    // lanes whose records do not fit the two-phase kernel's LDS take the one-phase kernel (same tape format)
-    if (dhts_fwd_variant == 1 || !macro_fwd2_fits(d))
+    if (!macro_desc_ok(d) || T < 0 || !r || !y || !u || !ueq || !ghost || !r_out || !y_out || !u_out || !ueq_out) return DHTS_E_INVALID;
+    const MacroPlan pl = macro_plan(d, T, hist != nullptr, tape != nullptr);
+    if (pl.fwd == kMacroFwdOnePhase)
         return macro_fwd_launch<true>(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, hist, err, stream);
-    return macro_fwd2_launch(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, hist, err, stream);
+    return macro_fwd2_launch(pl, d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, hist, err, stream);
 }
 int dhts_macro_rollout_bwd(const dhts_macro_desc *d, int T, const float *tape,
                            const float *g_r, const float *g_y, const float *g_hist,
                            float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
     return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, stream);
 }
-// which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for this shape: the very functions the launches call
+// which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for this shape: the plan the launches read
 int dhts_macro_rollout_plan(const dhts_macro_desc *d, int T, int want_hist, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
-    for (int k = 0; k < 8; ++k) plan[k] = 0;
-    const int N = d->n_cells;
-    if (dhts_fwd_variant == 1 || !macro_fwd2_fits(d)) {
-        plan[0] = 1;
-    } else {
-        int W, p;
-        macro_fwd2_plan(N, W, p);
-        plan[0] = macro_fwd3_group(d, want_hist != 0) > 0 ? 2 : 0;
-        plan[1] = W;
-        plan[2] = p;
-        plan[3] = ((p == 1 || p == 2) && N == 64 * p * W && !want_hist) ? 1 : 0;
-    }
-    plan[4] = macro_bwd_is_fast(N, T) ? 1 : (macro_bwd_is_fast2(N, T, want_hist != 0) ? 2 : 0);
-    plan[5] = plan[4] == 1 ? macro_bwd_fast_block(N) : (plan[4] == 2 ? 1024 : (padded64(N) > 512 ? 512 : padded64(N)));
-    plan[6] = want_hist ? 1 : 0;
-    plan[7] = plan[0] == 2 ? macro_fwd3_group(d, want_hist != 0) : 1;
+    const MacroPlan pl = macro_plan(d, T, want_hist != 0, true);
+    plan[0] = pl.fwd; plan[1] = pl.W; plan[2] = pl.p; plan[3] = pl.dense ? 1 : 0;
+    plan[4] = pl.bwd; plan[5] = pl.bwd_block; plan[6] = pl.hist ? 1 : 0; plan[7] = pl.G;
     return DHTS_OK;
 }
 int dhts_macro_tape_expand(const dhts_macro_desc *d, int T, const float *tape, float *dqs, void *stream) {
     if (!macro_desc_ok(d) || T < 0 || (T > 0 && (!tape || !dqs))) return DHTS_E_INVALID;
     if (T == 0) return DHTS_OK;
     const size_t lds = 2 * (size_t)(d->n_cells + 1);
-    macro_tape_expand_kernel<<<(unsigned)((size_t)T * d->n_lanes), 256, lds, (hipStream_t)stream>>>(
-        d->n_cells, d->dt / d->dx, reinterpret_cast<const float4 *>(tape), reinterpret_cast<float4 *>(dqs));
+    launch(macro_tape_expand_kernel, (unsigned)((size_t)T * d->n_lanes), 256, lds, stream, d->n_cells, d->dt / d->dx,
+           reinterpret_cast<const float4 *>(tape), reinterpret_cast<float4 *>(dqs));
     return launch_status();
 }
 // the single-step operator keeps the reference's per-cell blocks dqs[a][3][2][2] (48 B per cell)

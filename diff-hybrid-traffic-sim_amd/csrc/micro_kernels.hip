@@ -16,18 +16,10 @@
 
 #include "../../include/dhts.h"
 #include "arz_device.hpp"   // dot2
+#include "host_common.hpp"
 #include "idm_device.hpp"
 
 namespace dhts {
-
-__device__ __forceinline__ void raise_fault_m(dhts_error *err, int code, int step, int lane, int index) {
-    if (err == nullptr) return;
-    if (atomicCAS(&err->code, 0, code) == 0) {
-        err->step = step;
-        err->lane = lane;
-        err->index = index;
-    }
-}
 
 // compact rollout tape entry: (dEgo[1][0], dEgo[1][1], dLeading[1][1]).  The first rows of both blocks are constants
 // ([1, dt] and [0, 0]) and dLeading[1][0] = -dEgo[1][0] bit for bit: dt * (2 a s^2 / gap^3) against dt * (-2 a s^2 / gap^3),
@@ -132,7 +124,7 @@ __global__ __launch_bounds__(64 * kW) void micro_rollout_fwd_kernel(
     // slots >= count pass through: a step writes only live slots, and with kW > 1 and an odd T the final buffer is the one the
     // initial load never filled
     for (int k = t; k < V; k += kStride) { p_out[base + k] = k < n ? Fp[k] : p_in[base + k]; v_out[base + k] = k < n ? Fv[k] : v_in[base + k]; }
-    if (fault_step >= 0) raise_fault_m(err, DHTS_FAULT_COLLISION, fault_step, lane, fault_index);
+    if (fault_step >= 0) raise_fault(err, DHTS_FAULT_COLLISION, fault_step, lane, fault_index);
 }
 
 // known-answer entry: n independent vehicles.  in [9][n] double = a_max a_pref v v_target dp dv min_space time_pref dt
@@ -322,7 +314,7 @@ __global__ void micro_rollout_bwd_kernel(
     __syncthreads();
     if (bad_step >= 0) atomicMax(&s_bad, (bad_step << 10) | (1023 - bad_index));      // capacity <= 1024 vehicles
     __syncthreads();
-    if (t == 0 && s_bad >= 0) raise_fault_m(err, DHTS_FAULT_NAN, s_bad >> 10, lane, 1023 - (s_bad & 1023));
+    if (t == 0 && s_bad >= 0) raise_fault(err, DHTS_FAULT_NAN, s_bad >> 10, lane, 1023 - (s_bad & 1023));
 }
 
 // The single-step operator in the float32 TENSOR ladder (idm_step_f32): what the reference's plain MicroLane computes when its vehicle
@@ -374,7 +366,7 @@ __global__ void micro_step_tensor_fwd_kernel(int L, int V, double dt, const floa
             tp[Vp + i] = make_float4(o.dLd[0], o.dLd[1], o.dLd[2], o.dLd[3]);
         }
     }
-    if (fault_index >= 0) raise_fault_m(err, DHTS_FAULT_COLLISION, 0, lane, fault_index);
+    if (fault_index >= 0) raise_fault(err, DHTS_FAULT_COLLISION, 0, lane, fault_index);
 }
 
 }  // namespace dhts
@@ -384,51 +376,28 @@ using namespace dhts;
 static inline bool micro_desc_ok(const dhts_micro_desc *d) {
     return d && d->n_lanes > 0 && d->capacity > 0 && d->capacity <= DHTS_MICRO_MAX_VEHICLES && d->dt > 0;
 }
-static inline int launch_status_m() { return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH; }
-
 int dhts_micro_fwd_waves_override = 0;      // DHTS_OPT_MICRO_FWD_WAVES: 0 = heuristic, 1 / 2 / 4 wavefronts per lane
 
-template <int K, int kW, bool kCompact>
-static void launch_micro_fwd(const dhts_micro_desc *d, int T, const float *p, const float *v, const int32_t *count,
-                             const double *params, const double *head, float *p_out, float *v_out, float *tape,
-                             float *hist, dhts_error *err, hipStream_t s) {
-    const size_t lds = sizeof(float) * (kW > 1 ? 4 : 2) * (size_t)(d->capacity + 1);
-    if (count == nullptr && d->capacity == 64 * kW * K)
-        micro_rollout_fwd_kernel<K, kW, kCompact, true><<<d->n_lanes, 64 * kW, lds, s>>>(d->n_lanes, d->capacity, T, d->dt, p, v, count,
-                                                                                 params, head, p_out, v_out, tape, hist, err);
-    else
-        micro_rollout_fwd_kernel<K, kW, kCompact, false><<<d->n_lanes, 64 * kW, lds, s>>>(d->n_lanes, d->capacity, T, d->dt, p, v, count,
-                                                                                  params, head, p_out, v_out, tape, hist, err);
-}
-
-// wavefronts per lane of the forward kernel (1, 2 or 4)
-static int micro_fwd_waves(const dhts_micro_desc *d) {
+// Which instantiations the rollout launches for a shape: read by the launches below and by dhts_micro_rollout_plan.
+struct MicroPlan {
+    int W, K;                // forward: wavefronts per lane (1, 2 or 4) and the literal passes per thread (1, 2, 4, 8 or 16)
+    bool full;               // forward: every slot of every lane holds a vehicle (kFull)
+    int bwd_block;           // reverse: threads per lane
+    bool bwd_per_thread;     // reverse: the one-vehicle-per-thread sweep (the kernel's own test: the lane fits the block and there is a tape)
+};
+static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
+    MicroPlan pl;
+    // wavefronts per lane: one wave keeps the whole lane free of barriers; with few lanes per SIMD more waves per lane buy
+    // the latency hiding back (256 CUs x 4 SIMDs x 8 waves)
     int W = dhts_micro_fwd_waves_override;
     if (W == 0) W = (d->capacity > 64 && (long long)d->n_lanes * 2 <= 8192) ? 2 : 1;
-    if (W >= 4 && d->capacity > 128) return 4;
-    if (W >= 2 && d->capacity > 64) return 2;
-    return 1;
-}
-static int micro_fwd_passes(const dhts_micro_desc *d, int W) {       // the literal K dispatch_micro_fwd instantiates
-    const int K = (d->capacity + 64 * W - 1) / (64 * W);
-    return K <= 1 ? 1 : (K <= 2 ? 2 : (K <= 4 ? 4 : (K <= 8 ? 8 : 16)));
-}
-static int micro_bwd_block(const dhts_micro_desc *d) {
-    int B = (d->capacity + 63) & ~63;
-    return B > 256 ? 256 : B;
-}
-
-// passes per thread for kW wavefronts per lane
-template <int kW, bool kCompact>
-static void dispatch_micro_fwd(const dhts_micro_desc *d, int T, const float *p, const float *v, const int32_t *count,
-                               const double *params, const double *head, float *p_out, float *v_out, float *tape,
-                               float *hist, dhts_error *err, hipStream_t s) {
-    const int K = (d->capacity + 64 * kW - 1) / (64 * kW);
-    if (K <= 1) launch_micro_fwd<1, kW, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
-    else if (K <= 2) launch_micro_fwd<2, kW, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
-    else if (K <= 4) launch_micro_fwd<4, kW, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
-    else if (K <= 8) launch_micro_fwd<8, kW, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
-    else launch_micro_fwd<16, kW, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
+    pl.W = (W >= 4 && d->capacity > 128) ? 4 : ((W >= 2 && d->capacity > 64) ? 2 : 1);
+    const int K = (d->capacity + 64 * pl.W - 1) / (64 * pl.W);
+    pl.K = K <= 1 ? 1 : (K <= 2 ? 2 : (K <= 4 ? 4 : (K <= 8 ? 8 : 16)));
+    pl.full = !has_count && d->capacity == 64 * pl.W * pl.K;
+    pl.bwd_block = padded64(d->capacity) > 256 ? 256 : padded64(d->capacity);
+    pl.bwd_per_thread = d->capacity <= pl.bwd_block && T > 0;
+    return pl;
 }
 
 template <bool kCompact>
@@ -436,14 +405,17 @@ static int micro_fwd_launch(const dhts_micro_desc *d, int T,
                             const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                             float *p_out, float *v_out, float *tape, float *hist, dhts_error *err, void *stream) {
     if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || !head || !p_out || !v_out) return DHTS_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    // wavefronts per lane: one wave keeps the whole lane free of barriers; with few lanes per SIMD more waves per lane buy
-    // the latency hiding back (256 CUs x 4 SIMDs x 8 waves)
-    const int W = micro_fwd_waves(d);
-    if (W == 4) dispatch_micro_fwd<4, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
-    else if (W == 2) dispatch_micro_fwd<2, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
-    else dispatch_micro_fwd<1, kCompact>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, s);
-    return launch_status_m();
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const size_t lds = sizeof(float) * (pl.W > 1 ? 4 : 2) * (size_t)(d->capacity + 1);
+    pick<1, 2, 4>(pl.W, [&](auto w) {
+        pick<16, 8, 4, 2, 1>(pl.K, [&](auto k) {
+            pick<0, 1>(pl.full, [&](auto full) {
+                launch(micro_rollout_fwd_kernel<decltype(k)::value, decltype(w)::value, kCompact, decltype(full)::value != 0>, d->n_lanes,
+                       64 * pl.W, lds, stream, d->n_lanes, d->capacity, T, d->dt, p, v, count, params, head, p_out, v_out, tape, hist, err);
+            });
+        });
+    });
+    return launch_status();
 }
 template <bool kCompact>
 static int micro_bwd_launch(const dhts_micro_desc *d, int T, const float *tape, const int32_t *count,
@@ -451,11 +423,18 @@ static int micro_bwd_launch(const dhts_micro_desc *d, int T, const float *tape, 
                             float *g_p_out, float *g_v_out, double *g_head, int fold, dhts_error *err, void *stream) {
     if (!micro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_p || !g_v || !g_p_out || !g_v_out) return DHTS_E_INVALID;
     const size_t lds = sizeof(float) * 4 * (size_t)(d->capacity + 2);
-    const int B = micro_bwd_block(d);
-    micro_rollout_bwd_kernel<kCompact><<<d->n_lanes, B, lds, (hipStream_t)stream>>>(
-        d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out,
-        g_head, fold, err);
-    return launch_status_m();
+    launch(micro_rollout_bwd_kernel<kCompact>, d->n_lanes, micro_plan(d, T, count != nullptr).bwd_block, lds, stream,
+           d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, fold, err);
+    return launch_status();
+}
+template <bool kHeadOnly>
+static int micro_step_tensor_launch(const dhts_micro_desc *d, const float *p, const float *v, const int32_t *count, const double *params,
+                                    const double *head, float *p_out, float *v_out, float *tape, dhts_error *err, void *stream) {
+    if (!micro_desc_ok(d) || !p || !v || !params || !head || !p_out || !v_out) return DHTS_E_INVALID;
+    const int B = d->capacity <= 64 ? 64 : (d->capacity <= 128 ? 128 : 256);
+    launch(micro_step_tensor_fwd_kernel<kHeadOnly>, d->n_lanes, B, 0, stream, d->n_lanes, d->capacity, d->dt, p, v, count, params, head,
+           p_out, v_out, tape, err);
+    return launch_status();
 }
 
 extern "C" {
@@ -464,25 +443,23 @@ int dhts_idm_batch(int64_t n, int variant, const double *in, double *next_pv, fl
                    double *acc_sstar, int32_t *clips, void *stream) {
     if (n < 0 || (variant != 0 && variant != 1) || !in || !next_pv || !dEgo || !dLeading || !collided || !acc_sstar || !clips) return DHTS_E_INVALID;
     if (n == 0) return DHTS_OK;
-    int64_t g = (n + 255) / 256;
-    idm_batch_kernel<<<(int)(g > 2048 ? 2048 : g), 256, 0, (hipStream_t)stream>>>(n, variant, in, next_pv, dEgo, dLeading, collided, acc_sstar, clips);
-    return launch_status_m();
+    launch(idm_batch_kernel, grid_1d(n), 256, 0, stream, n, variant, in, next_pv, dEgo, dLeading, collided, acc_sstar, clips);
+    return launch_status();
 }
 
 int dhts_idm_jac_batch(int64_t n, const double *in, float *dEgo, float *dLeading, void *stream) {
     if (n <= 0 || !in || !dEgo || !dLeading) return DHTS_E_INVALID;
-    const int64_t blocks = (n + 255) / 256;
-    idm_jac_batch_kernel<<<(int)(blocks > 4096 ? 4096 : blocks), 256, 0, (hipStream_t)stream>>>(n, in, dEgo, dLeading);
-    return launch_status_m();
+    launch(idm_jac_batch_kernel, grid_1d(n, 4096), 256, 0, stream, n, in, dEgo, dLeading);
+    return launch_status();
 }
 
 size_t dhts_micro_tape_bytes(const dhts_micro_desc *d, int T) {
     if (!micro_desc_ok(d) || T < 0) return 0;
-    return (size_t)T * d->n_lanes * ((d->capacity + 63) & ~63) * sizeof(MicroTape3);
+    return (size_t)T * d->n_lanes * padded64(d->capacity) * sizeof(MicroTape3);
 }
 size_t dhts_micro_step_tape_bytes(const dhts_micro_desc *d) {
     if (!micro_desc_ok(d)) return 0;
-    return (size_t)d->n_lanes * 2 * ((d->capacity + 63) & ~63) * sizeof(float4);
+    return (size_t)d->n_lanes * 2 * padded64(d->capacity) * sizeof(float4);
 }
 
 int dhts_micro_rollout_fwd(const dhts_micro_desc *d, int T,
@@ -495,16 +472,16 @@ int dhts_micro_rollout_bwd(const dhts_micro_desc *d, int T, const float *tape, c
                                       float *g_p_out, float *g_v_out, double *g_head, dhts_error *err, void *stream) {
     return micro_bwd_launch<true>(d, T, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, 1, err, stream);
 }
-// which kernel instantiations dhts_micro_rollout_fwd / _bwd launch for this shape: the very functions the launches call
+// which kernel instantiations dhts_micro_rollout_fwd / _bwd launch for this shape: the plan the launches read
 int dhts_micro_rollout_plan(const dhts_micro_desc *d, int T, int has_count, int32_t plan[8]) {
     if (!micro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
+    const MicroPlan pl = micro_plan(d, T, has_count != 0);
     for (int k = 0; k < 8; ++k) plan[k] = 0;
-    const int W = micro_fwd_waves(d), K = micro_fwd_passes(d, W), B = micro_bwd_block(d);
-    plan[0] = W;
-    plan[1] = K;
-    plan[2] = (!has_count && d->capacity == 64 * W * K) ? 1 : 0;
-    plan[3] = (d->capacity <= B && T > 0) ? 1 : 0;
-    plan[4] = B;
+    plan[0] = pl.W;
+    plan[1] = pl.K;
+    plan[2] = pl.full ? 1 : 0;
+    plan[3] = pl.bwd_per_thread ? 1 : 0;
+    plan[4] = pl.bwd_block;
     return DHTS_OK;
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)
@@ -516,20 +493,12 @@ int dhts_micro_step_fwd(const dhts_micro_desc *d,
 int dhts_micro_step_fwd_tensor(const dhts_micro_desc *d,
                                const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                                float *p_out, float *v_out, float *tape, dhts_error *err, void *stream) {
-    if (!micro_desc_ok(d) || !p || !v || !params || !head || !p_out || !v_out) return DHTS_E_INVALID;
-    const int B = d->capacity <= 64 ? 64 : (d->capacity <= 128 ? 128 : 256);
-    micro_step_tensor_fwd_kernel<false><<<d->n_lanes, B, 0, (hipStream_t)stream>>>(d->n_lanes, d->capacity, d->dt, p, v, count, params, head,
-                                                                                 p_out, v_out, tape, err);
-    return launch_status_m();
+    return micro_step_tensor_launch<false>(d, p, v, count, params, head, p_out, v_out, tape, err, stream);
 }
 int dhts_micro_step_fwd_tensor_head(const dhts_micro_desc *d,
                                     const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                                     float *p_out, float *v_out, float *tape, dhts_error *err, void *stream) {
-    if (!micro_desc_ok(d) || !p || !v || !params || !head || !p_out || !v_out) return DHTS_E_INVALID;
-    const int B = d->capacity <= 64 ? 64 : (d->capacity <= 128 ? 128 : 256);
-    micro_step_tensor_fwd_kernel<true><<<d->n_lanes, B, 0, (hipStream_t)stream>>>(d->n_lanes, d->capacity, d->dt, p, v, count, params, head,
-                                                                                p_out, v_out, tape, err);
-    return launch_status_m();
+    return micro_step_tensor_launch<true>(d, p, v, count, params, head, p_out, v_out, tape, err, stream);
 }
 int dhts_micro_step_bwd(const dhts_micro_desc *d, const float *tape, const int32_t *count,
                         const float *g_p, const float *g_v,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dhts.h"
+#include "host_common.hpp"   // raise_fault
 
 namespace dhts {
 
@@ -102,11 +103,6 @@ struct NetTables {
     const int32_t *nxt_ptr, *nxt_idx, *prv_ptr, *prv_idx;       // static adjacency, CSR, ascending ids
     int n_edges;
 };
-
-__device__ __forceinline__ void net_fault(dhts_error *err, int code, int step, int lane, int index) {
-    if (err == nullptr) return;
-    if (atomicCAS(&err->code, 0, code) == 0) { err->step = step; err->lane = lane; err->index = index; }
-}
 
 // phase signals of intersection k at step t: west-east and north-south switches and their inputs (_env.py:885-962).
 // `phase_raw` = t / F and `frame` = t % F are passed in so that rollouts can count them instead of dividing every step.

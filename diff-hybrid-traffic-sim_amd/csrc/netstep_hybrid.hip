@@ -451,12 +451,12 @@ template <class A> __device__ __forceinline__ void ns_micro_fwd(const A &a, int 
             int admitted = 0;
             if (has) {
                 const int idx = used0 + carry + rank;
-                if (idx >= a.n_draws) net_fault(a.err, DHTS_FAULT_CAPACITY, t, l, -1);
+                if (idx >= a.n_draws) raise_fault(a.err, DHTS_FAULT_CAPACITY, t, l, -1);
                 else {
                     const double draw = ns_glob(a.draws)[idx];
                     const int r_lo = ns_glob(a.route_ptr)[l], r_n = ns_glob(a.route_ptr)[l + 1] - r_lo;
                     if (draw < ns_row(a, t).schedule[l] && rused[l] < r_n) {
-                        if (n >= cap) net_fault(a.err, DHTS_FAULT_CAPACITY, t, l, n);
+                        if (n >= cap) raise_fault(a.err, DHTS_FAULT_CAPACITY, t, l, n);
                         else {
                             const size_t b = (size_t)m * cap;
                             ns_shift_in(P0, V0, A_, vroute, vcur, b, n);
@@ -621,7 +621,7 @@ template <class A> __device__ __forceinline__ void ns_micro_fwd(const A &a, int 
             pv.a_max = q[0]; pv.a_pref = q[1]; pv.v_target = q[2]; pv.min_space = q[3]; pv.time_pref = q[4]; pv.length = prm.length;
             one_step(pv);
         } else one_step(prm);
-        if (o.collided) net_fault(a.err, DHTS_FAULT_COLLISION, t, a.micro_lanes[m], i);
+        if (o.collided) raise_fault(a.err, DHTS_FAULT_COLLISION, t, a.micro_lanes[m], i);
         P1[idx] = o.np; V1[idx] = o.nv;
         if (tape) tape[idx] = make_float4(o.dE[2], o.dE[3], o.dLd[2], o.dLd[3]);
     }
@@ -640,7 +640,7 @@ __global__ void __launch_bounds__(kNsBlock) ns_boundary_fwd_kernel(NsArgs a, int
 template <class A> __device__ __forceinline__ void ns_push_event(const A &a, NsCounters *cnt, int t, const NsEvent &e) {
     if (a.hard) return;
     const int k = cnt->n_events;
-    if (k >= a.max_events) { net_fault(a.err, DHTS_FAULT_CAPACITY, t, e.lane, -2); return; }
+    if (k >= a.max_events) { raise_fault(a.err, DHTS_FAULT_CAPACITY, t, e.lane, -2); return; }
     ns_ptr<NsEvent>(a, a.lo.ev)[k] = e;
     cnt->n_events = k + 1;
 }
@@ -722,7 +722,7 @@ template <class A> __device__ __forceinline__ void ns_convert(const A &a, int t,
                             const float space = n ? P1[b] - 0.5f * vlen : (float)a.lane_len[m];
                             if (level >= vlen && space >= vlen * 1.0f) {
                                 const int r_lo = ns_glob(a.route_ptr)[m], r_n = ns_glob(a.route_ptr)[m + 1] - r_lo;
-                                if (r_n <= 0 || n >= cap) net_fault(a.err, DHTS_FAULT_CAPACITY, t, m, n);
+                                if (r_n <= 0 || n >= cap) raise_fault(a.err, DHTS_FAULT_CAPACITY, t, m, n);
                                 else {
                                     const int rrow = r_lo + rused[m] % r_n;
                                     rused[m] += 1;
@@ -757,7 +757,7 @@ template <class A> __device__ __forceinline__ void ns_convert(const A &a, int t,
                                     if (hp >= Lf) {
                                         const int m2 = a.lane_mslot[nid];
                                         const int n2 = lane_n[m2];
-                                        if (n2 >= cap) net_fault(a.err, DHTS_FAULT_CAPACITY, t, nid, n2);
+                                        if (n2 >= cap) raise_fault(a.err, DHTS_FAULT_CAPACITY, t, nid, n2);
                                         else {
                                             const int vr_ = vroute[hs];
                                             lane_n[ms] = n - 1;
@@ -1462,7 +1462,7 @@ template <class A> __device__ __forceinline__ void ns_cell_bwd_item(const A &a, 
     const auto gg = ns_gghost(a) + (size_t)a.lane_gpos[l] * 4;
     if (k == 0) { gg[0] = (double)dot2(d0.x, gr, d0.z, gy); gg[1] = (double)dot2(d0.y, gr, d0.w, gy); }
     if (k == n - 1) { gg[2] = (double)dot2(d2.x, gr, d2.z, gy); gg[3] = (double)dot2(d2.y, gr, d2.w, gy); }
-    if (!(isfinite(pr) && isfinite(py))) net_fault(a.err, DHTS_FAULT_NAN, t, l, k);
+    if (!(isfinite(pr) && isfinite(py))) raise_fault(a.err, DHTS_FAULT_NAN, t, l, k);
 }
 
 // The static tables of a network (per lane, per cell, adjacency) staged in LDS for a persistent kernel: every item of every phase
@@ -1644,7 +1644,7 @@ __global__ void __launch_bounds__(kNsBlock) ns_persist_fwd_kernel(NsArgs a0, con
         printf("   head gaps: lane part %lld | scans %lld (rest in 'head gaps');  loss: lane prefixes %lld | samples (thread 0) %lld | wait %lld | lane sums = 'loss'\n",
                ns_sub_[16] / T, ns_sub_[17] / T, ns_sub_[6] / T, ns_sub_[7] / T, ns_sub_[15] / T);
 #endif
-    if (fault_step >= 0) net_fault(a.err, DHTS_FAULT_CFL, fault_step, fault_lane, fault_index);
+    if (fault_step >= 0) raise_fault(a.err, DHTS_FAULT_CFL, fault_step, fault_lane, fault_index);
     if constexpr (MS) {                  // what the reverse sweep starts from
         auto lane_n = ns_ptr<int>(a, a.lo.lane_n);
         for (int m = tid; m < a0.Lm; m += B) lane_n[m] = a.m_lane_n[m];
@@ -1859,7 +1859,7 @@ static NsArgs ns_args(const dhts_net_desc *d, const dhts_netstep_tables *t, int 
 // What a workgroup's 160 KB hold beside the phases' scratch: the static tables + the per-step table rows + ghosts resp. slots / ghost
 // cotangents (TB: small, the head of every item's look-up chain), then the state rows and -- reverse sweep -- the cotangent planes (ST)
 int dhts_netstep_block = 0;            // DHTS_OPT_NETSTEP_BLOCK: threads per workgroup of the persistent kernels (0 = heuristic)
-int dhts_netstep_lds_kb = 0;           // DHTS_OPT_NETSTEP_LDS_KB (dhts_set_option, macro_kernels.hip): 0 = all a workgroup may take
+int dhts_netstep_lds_kb = 0;           // DHTS_OPT_NETSTEP_LDS_KB: 0 = all a workgroup may take
 static NsPlan ns_plan(const NsArgs &a, size_t scratch, bool bwd) {
     NsPlan pl = {(int)scratch, 0, 0, 0, 0, 0, 0, 0};
     const size_t budget = (size_t)(dhts_netstep_lds_kb > 0 ? dhts_netstep_lds_kb : 158) * 1024;      // (the kernels' static LDS -- argument block, scan scratch -- stays below 2 KB)
@@ -1883,28 +1883,22 @@ static int ns_persist_block(const NsArgs &a) {
     return kNsBlock;
 }
 
-template <int TA, int SS, bool MS>
-static int ns_launch_persist_fwd(const NsArgs &a, const float *action, const NsPlan &pl, size_t lds, int n_replicas, hipStream_t st) {
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute((const void *)ns_persist_fwd_kernel<TA, SS, MS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_INVALID;
-    ns_persist_fwd_kernel<TA, SS, MS><<<n_replicas, ns_persist_block(a), lds, st>>>(a, action, pl);
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
-}
-template <int TA, int SS, bool MS>
-static int ns_launch_persist_bwd(const NsArgs &a, const float *action, const float *g_reward, float *g_action, const NsPlan &pl, size_t lds,
-                                 int n_replicas, hipStream_t st) {
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute((const void *)ns_persist_bwd_kernel<TA, SS, MS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_INVALID;
-    ns_persist_bwd_kernel<TA, SS, MS><<<n_replicas, ns_persist_block(a), lds, st>>>(a, action, g_reward, g_action, pl);
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
-}
+// these kernels ask for their dynamic LDS from 48 KB on (the other families from 64 KB on, host_common.hpp)
+constexpr size_t kNsLdsDefault = 48 * 1024;
 
-// dhts_common.hip: the reward as the reference's one float32 chain, lanes outermost (DHTS_OPT_REWARD_CHAIN)
-extern int dhts_opt_reward_chain;
-int dhts_launch_reward_chain(int R, int T, int L, const float *queue, const int32_t *lane_macro, int hard, double dt, int loss_steps,
-                             float *reward, int stride, void *stream);
+// The persistent kernels' instantiation <TA, SS, MS> for a plan, as the one number 100 TA + 10 SS + MS.  TA: 3 = tables, rows and
+// ghosts in LDS, 1 = none; SS: 2 = state rows (and, reverse, cotangent planes) in LDS, 1 = the planes alone (reverse only), 0 = none;
+// MS: the micro lanes' state in LDS.
+static int ns_variant(const NsPlan &pl) {
+    return (pl.tables ? 300 : 100) + (pl.st ? 20 : (pl.gl ? 10 : 0)) + ((pl.tables && pl.ms) ? 1 : 0);
+}
+// f(std::integral_constant<int, variant>): every instantiation a direction has (a forward plan has no planes: no SS = 1)
+template <bool kBwd, class F>
+static bool ns_pick_variant(const NsPlan &pl, F &&f) {
+    if constexpr (kBwd) return pick<100, 110, 120, 300, 310, 320, 301, 311, 321>(ns_variant(pl), f);
+    else return pick<100, 120, 300, 320, 301, 321>(ns_variant(pl), f);
+}
+static inline size_t ns_plan_lds(const NsPlan &pl) { return (size_t)pl.scratch + pl.tables + pl.st + pl.gl + pl.rows + pl.misc + pl.ms + pl.routes; }
 
 extern "C" {
 
@@ -1926,12 +1920,15 @@ int dhts_netstep_rollout_fwd(const dhts_net_desc *d, const dhts_netstep_tables *
         if (sizeof(float) * 2 * (size_t)L > lds) lds = sizeof(float) * 2 * (size_t)L;
         if (ns_convert_scratch(L, C, plane) > lds) lds = ns_convert_scratch(L, C, plane);
         const NsPlan pl = ns_plan(a, ns_al16(lds), false);
-        lds = (size_t)pl.scratch + pl.tables + pl.st + pl.gl + pl.rows + pl.misc + pl.ms + pl.routes;
+        lds = ns_plan_lds(pl);
         if (lds > 160 * 1024) return DHTS_E_INVALID;
-        int rc;
-        if (pl.tables && pl.ms) rc = pl.st ? ns_launch_persist_fwd<3, 2, true>(a, action, pl, lds, d->n_replicas, st) : ns_launch_persist_fwd<3, 0, true>(a, action, pl, lds, d->n_replicas, st);
-        else if (pl.tables) rc = pl.st ? ns_launch_persist_fwd<3, 2, false>(a, action, pl, lds, d->n_replicas, st) : ns_launch_persist_fwd<3, 0, false>(a, action, pl, lds, d->n_replicas, st);
-        else rc = pl.st ? ns_launch_persist_fwd<1, 2, false>(a, action, pl, lds, d->n_replicas, st) : ns_launch_persist_fwd<1, 0, false>(a, action, pl, lds, d->n_replicas, st);
+        int rc = DHTS_E_INVALID;
+        ns_pick_variant<false>(pl, [&](auto v) {
+            constexpr int kV = decltype(v)::value;
+            if (launch_lds(ns_persist_fwd_kernel<kV / 100, kV / 10 % 10, kV % 10 != 0>, d->n_replicas, ns_persist_block(a), lds, kNsLdsDefault,
+                           stream, a, action, pl))
+                rc = launch_status();
+        });
         if (rc == DHTS_OK && dhts_opt_reward_chain)
             rc = dhts_launch_reward_chain(d->n_replicas, T, L, queue, t->hyb.lane_macro, hard, d->dt, a.loss_steps, reward, 2, stream);
         return rc;
@@ -1939,16 +1936,14 @@ int dhts_netstep_rollout_fwd(const dhts_net_desc *d, const dhts_netstep_tables *
     // running state of the episode
     if (hipMemsetAsync(ws + a.lo.P, 0, a.lo.counters + sizeof(NsCounters) - a.lo.P, st) != hipSuccess) return DHTS_E_LAUNCH;
     const int nmax = C > L ? C : L;
-    ns_init_fwd_kernel<<<(nmax + 255) / 256, 256, 0, st>>>(a);
+    launch(ns_init_fwd_kernel, (nmax + 255) / 256, 256, 0, stream, a);
     const size_t lds_b = sizeof(float) * 2 * (size_t)(Lm > 0 ? Lm : 1), lds_c = ns_convert_scratch(L, C, plane);
-    if (lds_b > 48 * 1024 || lds_c > 160 * 1024 ||
-        (lds_c > 48 * 1024 && hipFuncSetAttribute((const void *)ns_convert_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess))
-        return DHTS_E_INVALID;
+    if (lds_b > kNsLdsDefault || lds_c > 160 * 1024 || !allow_lds(ns_convert_fwd_kernel, lds_c, kNsLdsDefault)) return DHTS_E_INVALID;
     const int ghost_blocks = (ns_ghost_items(L) + kNsBlock - 1) / kNsBlock;
     float *ghost = reinterpret_cast<float *>(ws + a.lo.ghost);
     float *tape0 = reinterpret_cast<float *>(ws + a.lo.tape);
     for (int step = 0; step < T; ++step) {
-        ns_boundary_fwd_kernel<<<1 + ghost_blocks, kNsBlock, lds_b, st>>>(a, step, action);
+        launch(ns_boundary_fwd_kernel, 1 + ghost_blocks, kNsBlock, lds_b, stream, a, step, action);
         const float *cur = hist + (size_t)step * 4 * C;
         float *nxt = hist + (size_t)(step + 1) * 4 * C;
         size_t tape_off = 0;
@@ -1962,10 +1957,10 @@ int dhts_netstep_rollout_fwd(const dhts_net_desc *d, const dhts_netstep_tables *
             if (rc != DHTS_OK) return rc;
             tape_off += dhts_macro_step_tape_bytes(&md) / sizeof(float);
         }
-        ns_convert_fwd_kernel<<<1, kNsBlock, lds_c, st>>>(a, step);
+        launch(ns_convert_fwd_kernel, 1, kNsBlock, lds_c, stream, a, step);
     }
-    ns_reward_kernel<<<1, kNsBlock, sizeof(float) * 2 * (size_t)L, st>>>(a);
-    if (hipGetLastError() != hipSuccess) return DHTS_E_LAUNCH;
+    launch(ns_reward_kernel, 1, kNsBlock, sizeof(float) * 2 * (size_t)L, stream, a);
+    if (launch_status() != DHTS_OK) return DHTS_E_LAUNCH;
     if (dhts_opt_reward_chain) return dhts_launch_reward_chain(1, T, L, queue, t->hyb.lane_macro, hard, d->dt, a.loss_steps, reward, 2, stream);
     return DHTS_OK;
 }
@@ -1980,29 +1975,29 @@ int dhts_netstep_rollout_bwd(const dhts_net_desc *d, const dhts_netstep_tables *
     char *ws = a.ws;
     if (t->persistent) {
         const NsPlan pl = ns_plan(a, ns_al16(ns_micro_bwd_scratch(L, C, Lm, (size_t)Lm * a.cap)), true);
-        const size_t lds = (size_t)pl.scratch + pl.tables + pl.st + pl.gl + pl.rows + pl.misc + pl.ms + pl.routes;
+        const size_t lds = ns_plan_lds(pl);
         if (lds > 160 * 1024) return DHTS_E_INVALID;
-#define NS_BWD(TA_, SS_, MS_) ns_launch_persist_bwd<TA_, SS_, MS_>(a, action, g_reward, g_action, pl, lds, d->n_replicas, st)
-        const int ss = pl.st ? 2 : (pl.gl ? 1 : 0);
-        if (pl.tables && pl.ms) return ss == 2 ? NS_BWD(3, 2, true) : (ss == 1 ? NS_BWD(3, 1, true) : NS_BWD(3, 0, true));
-        if (pl.tables) return ss == 2 ? NS_BWD(3, 2, false) : (ss == 1 ? NS_BWD(3, 1, false) : NS_BWD(3, 0, false));
-        return ss == 2 ? NS_BWD(1, 2, false) : (ss == 1 ? NS_BWD(1, 1, false) : NS_BWD(1, 0, false));
-#undef NS_BWD
+        int rc = DHTS_E_INVALID;
+        ns_pick_variant<true>(pl, [&](auto v) {
+            constexpr int kV = decltype(v)::value;
+            if (launch_lds(ns_persist_bwd_kernel<kV / 100, kV / 10 % 10, kV % 10 != 0>, d->n_replicas, ns_persist_block(a), lds, kNsLdsDefault,
+                           stream, a, action, g_reward, g_action, pl))
+                rc = launch_status();
+        });
+        return rc;
     }
     // cotangents start at zero; the lanes hold what the forward left (lane_n)
     if (hipMemsetAsync(ws + a.lo.G, 0, a.lo.n_bwd - a.lo.G, st) != hipSuccess) return DHTS_E_LAUNCH;
     if (Lm > 0 && hipMemcpyAsync(ws + a.lo.n_bwd, ws + a.lo.lane_n, sizeof(int) * (size_t)Lm, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return DHTS_E_LAUNCH;
     const size_t lds_m = ns_micro_bwd_scratch(L, C, Lm, (size_t)Lm * a.cap);
-    if (lds_m > 160 * 1024 ||
-        hipFuncSetAttribute((const void *)ns_micro_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m) != hipSuccess)
-        return DHTS_E_INVALID;
+    if (lds_m > 160 * 1024 || !set_max_lds((const void *)ns_micro_bwd_kernel, lds_m)) return DHTS_E_INVALID;      // (asked whatever the size)
     float *G = reinterpret_cast<float *>(ws + a.lo.G);
     double *g_ghost = reinterpret_cast<double *>(ws + a.lo.g_ghost);
     const float *tape0 = reinterpret_cast<const float *>(ws + a.lo.tape);
     const int lane_blocks = (L + 255) / 256, act_blocks = (a.sq + 3) / 4;
     for (int step = T - 1; step >= 0; --step) {
-        ns_micro_bwd_kernel<<<1, kNsBlock, lds_m, st>>>(a, step, action, g_reward);
+        launch(ns_micro_bwd_kernel, 1, kNsBlock, lds_m, stream, a, step, action, g_reward);
         float *Gn = G + (size_t)((step + 1) & 1) * 3 * C, *Gp = G + (size_t)(step & 1) * 3 * C;
         if (C > 0 && hipMemsetAsync(Gp + 2 * (size_t)C, 0, sizeof(float) * (size_t)C, st) != hipSuccess) return DHTS_E_LAUNCH;
         size_t tape_off = 0;
@@ -2016,12 +2011,12 @@ int dhts_netstep_rollout_bwd(const dhts_net_desc *d, const dhts_netstep_tables *
             tape_off += dhts_macro_step_tape_bytes(&md) / sizeof(float);
         }
         if (C > 0) {
-            ns_ghosts_bwd_kernel<<<(ns_ghost_items(L) + 255) / 256, 256, 0, st>>>(a, step, action);
-            ns_ghosts_gather_kernel<<<lane_blocks + act_blocks, 256, 0, st>>>(a, step, lane_blocks);
+            launch(ns_ghosts_bwd_kernel, (ns_ghost_items(L) + 255) / 256, 256, 0, stream, a, step, action);
+            launch(ns_ghosts_gather_kernel, lane_blocks + act_blocks, 256, 0, stream, a, step, lane_blocks);
         }
     }
-    ns_finish_bwd_kernel<<<(a.n_action + 255) / 256, 256, 0, st>>>(a, g_action);
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
+    launch(ns_finish_bwd_kernel, (a.n_action + 255) / 256, 256, 0, stream, a, g_action);
+    return launch_status();
 }
 
 }  // extern "C"

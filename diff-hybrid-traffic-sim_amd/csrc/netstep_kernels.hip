@@ -200,8 +200,8 @@ int dhts_net_ghosts_fwd(const dhts_net_desc *d, const dhts_net_tables *t, int st
                         const float *u, const float *own_in, float *own_out, float *ghost, void *stream) {
     if (!netstep_ok(d, t, step) || !action || !r || !u || !own_in || !own_out || !ghost) return DHTS_E_INVALID;
     const int n = 2 * d->n_lanes;
-    net_ghosts_fwd_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(netstep_args(d, t, step), hard, action, r, u, own_in, own_out, ghost);
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
+    launch(net_ghosts_fwd_kernel, (n + 255) / 256, 256, 0, stream, netstep_args(d, t, step), hard, action, r, u, own_in, own_out, ghost);
+    return launch_status();
 }
 
 int dhts_net_ghosts_bwd(const dhts_net_desc *d, const dhts_net_tables *t, const int32_t *inter_ptr, const int32_t *inter_idx, int step,
@@ -213,11 +213,11 @@ int dhts_net_ghosts_bwd(const dhts_net_desc *d, const dhts_net_tables *t, const 
         return DHTS_E_INVALID;
     const NetStepArgs a = netstep_args(d, t, step);
     const int n = 2 * d->n_lanes;
-    net_ghosts_bwd_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(a, action, r, y, u, own_in, g_ghost, g_own_in, g_own_out, scratch);
+    launch(net_ghosts_bwd_kernel, (n + 255) / 256, 256, 0, stream, a, action, r, y, u, own_in, g_ghost, g_own_in, g_own_out, scratch);
     const int m = d->n_lanes > d->n_inter_sq ? d->n_lanes : d->n_inter_sq;
-    net_ghosts_gather_kernel<<<(m + 255) / 256, 256, 0, (hipStream_t)stream>>>(a, t->nxt_ptr, t->nxt_idx, t->prv_ptr, t->prv_idx, inter_ptr,
-                                                                              inter_idx, scratch, g_r, g_y, g_action);
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
+    launch(net_ghosts_gather_kernel, (m + 255) / 256, 256, 0, stream, a, t->nxt_ptr, t->nxt_idx, t->prv_ptr, t->prv_idx, inter_ptr, inter_idx,
+           scratch, g_r, g_y, g_action);
+    return launch_status();
 }
 
 }  // extern "C"

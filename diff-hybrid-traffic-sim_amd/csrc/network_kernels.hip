@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_fwd_kernel(int R, int L, 
         for (int l = 0; l < L; ++l) rew = rew + ql[l];
         reward[rep] = rew;
     }
-    if (fault_step >= 0) net_fault(err, DHTS_FAULT_CFL, fault_step, i_lane, fault_index);
+    if (fault_step >= 0) raise_fault(err, DHTS_FAULT_CFL, fault_step, i_lane, fault_index);
 }
 
 // reverse: two barriers per step, global reads (history rows, loss constants, tape, queue terms, tables) fetched one step
@@ -552,7 +552,7 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_bwd_kernel(int R, int L, 
         // inbox entries and the reduction scratch are rewritten two barriers later
     }
     if (tid < sq && cur_phase >= 0) g_action[(size_t)rep * n_action + cur_phase * sq + tid] = (float)ga;
-    if (bad_step >= 0) net_fault(err, DHTS_FAULT_NAN, bad_step, rep, tid);
+    if (bad_step >= 0) raise_fault(err, DHTS_FAULT_NAN, bad_step, rep, tid);
 }
 
 }  // namespace dhts
@@ -568,11 +568,11 @@ static inline bool net_desc_ok(const dhts_net_desc *d) {
 static inline int net_block(const dhts_net_desc *d) {
     int need = d->n_cells + d->n_lanes;
     if (need < d->n_action) need = d->n_action;
-    return (need + 63) & ~63;
+    return padded64(need);
 }
 // forward kernels: wavefronts of their own for the loss where they fit the workgroup
 static inline int net_fwd_block(const dhts_net_desc *d, bool &loss_waves) {
-    const int Bp = net_block(d), B = Bp + ((d->n_cells + 63) & ~63);
+    const int Bp = net_block(d), B = Bp + padded64(d->n_cells);
     loss_waves = B <= 1024;
     return loss_waves ? B : Bp;
 }
@@ -590,18 +590,13 @@ static inline bool net_tables_ok(const dhts_net_tables *t) {
            t->n_edges >= 0;
 }
 
-// dhts_common.hip: the reward as the reference's one float32 chain, lanes outermost (DHTS_OPT_REWARD_CHAIN)
-extern int dhts_opt_reward_chain;
-int dhts_launch_reward_chain(int R, int T, int L, const float *queue, const int32_t *lane_macro, int hard, double dt, int loss_steps,
-                             float *reward, int stride, void *stream);
-
 extern "C" {
 
 size_t dhts_net_macro_hist_bytes(const dhts_net_desc *d) {
     return net_desc_ok(d) ? sizeof(float) * (size_t)d->n_replicas * (d->n_steps + 1) * 4 * d->n_cells : 0;
 }
 size_t dhts_net_macro_tape_bytes(const dhts_net_desc *d) {
-    return net_desc_ok(d) ? sizeof(float4) * (size_t)d->n_replicas * d->n_steps * 3 * ((d->n_cells + 63) & ~63) : 0;
+    return net_desc_ok(d) ? sizeof(float4) * (size_t)d->n_replicas * d->n_steps * 3 * padded64(d->n_cells) : 0;
 }
 
 int dhts_net_macro_rollout_fwd(const dhts_net_desc *d, const dhts_net_tables *t, const float *action, float *hist, float *tape,
@@ -612,23 +607,18 @@ int dhts_net_macro_rollout_fwd(const dhts_net_desc *d, const dhts_net_tables *t,
     const int B = net_fwd_block(d, lw), L = d->n_lanes, C = d->n_cells;
     const size_t lds = net_fwd_lds_base(L, C) + net_staged_bytes(L, d->n_inter_sq, d->n_action);
     if (lds > 160 * 1024) return DHTS_E_INVALID;
-#define DHTS_NET_FWD_ARGS d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt, d->u_max, d->static_speed, \
-        d->vehicle_length, net_tables(t), action, hist, reinterpret_cast<float4 *>(tape), kc, queue, reward, workspace, err
-#define DHTS_NET_FWD_LAUNCH(LW, MB)                                                                                                   \
-    {                                                                                                                                 \
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)net_macro_fwd_kernel<false, LW, MB>,                                 \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)              \
-            return DHTS_E_LAUNCH;                                                                                                     \
-        net_macro_fwd_kernel<false, LW, MB><<<d->n_replicas, B, lds, (hipStream_t)stream>>>(DHTS_NET_FWD_ARGS);                       \
-    }
-    if (lw) {
-        if (B <= 512) DHTS_NET_FWD_LAUNCH(true, 512) else if (B <= 640) DHTS_NET_FWD_LAUNCH(true, 640) else DHTS_NET_FWD_LAUNCH(true, 1024)
-    } else {
-        if (B <= 512) DHTS_NET_FWD_LAUNCH(false, 512) else if (B <= 640) DHTS_NET_FWD_LAUNCH(false, 640) else DHTS_NET_FWD_LAUNCH(false, 1024)
-    }
-#undef DHTS_NET_FWD_LAUNCH
-#undef DHTS_NET_FWD_ARGS
-    if (hipGetLastError() != hipSuccess) return DHTS_E_LAUNCH;
+    bool lds_ok = true;
+    // (the block-size bound sets the vector registers a thread may take)
+    pick<0, 1>(lw, [&](auto w) {
+        pick<1024, 640, 512>(B <= 512 ? 512 : (B <= 640 ? 640 : 1024), [&](auto mb) {
+            const auto kern = net_macro_fwd_kernel<false, decltype(w)::value != 0, decltype(mb)::value>;
+            if ((lds_ok = allow_lds(kern, lds)))
+                launch(kern, d->n_replicas, B, lds, stream, d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action,
+                       d->dt, d->u_max, d->static_speed, d->vehicle_length, net_tables(t), action, hist, reinterpret_cast<float4 *>(tape), kc,
+                       queue, reward, workspace, err);
+        });
+    });
+    if (!lds_ok || launch_status() != DHTS_OK) return DHTS_E_LAUNCH;
     if (dhts_opt_reward_chain) return dhts_launch_reward_chain(d->n_replicas, d->n_steps, L, queue, nullptr, 0, d->dt, 0, reward, 1, stream);
     return DHTS_OK;
 }
@@ -639,13 +629,11 @@ int dhts_net_macro_rollout_eval(const dhts_net_desc *d, const dhts_net_tables *t
     const int B = net_block(d), L = d->n_lanes, C = d->n_cells;
     const size_t lds = net_fwd_lds_base(L, C) + net_staged_bytes(L, d->n_inter_sq, d->n_action);
     if (lds > 160 * 1024) return DHTS_E_INVALID;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)net_macro_fwd_kernel<true, false, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DHTS_E_LAUNCH;
-    net_macro_fwd_kernel<true, false, 1024><<<d->n_replicas, B, lds, (hipStream_t)stream>>>(
-        d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt, d->u_max, d->static_speed,
-        d->vehicle_length, net_tables(t), action, nullptr, nullptr, nullptr, queue, reward, nullptr, err);
-    if (hipGetLastError() != hipSuccess) return DHTS_E_LAUNCH;
+    const auto kern = net_macro_fwd_kernel<true, false, 1024>;
+    if (!allow_lds(kern, lds)) return DHTS_E_LAUNCH;
+    launch(kern, d->n_replicas, B, lds, stream, d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt,
+           d->u_max, d->static_speed, d->vehicle_length, net_tables(t), action, nullptr, nullptr, nullptr, queue, reward, nullptr, err);
+    if (launch_status() != DHTS_OK) return DHTS_E_LAUNCH;
     if (dhts_opt_reward_chain) return dhts_launch_reward_chain(d->n_replicas, d->n_steps, L, queue, nullptr, 1, d->dt, 0, reward, 1, stream);
     return DHTS_OK;
 }
@@ -659,19 +647,15 @@ int dhts_net_macro_rollout_bwd(const dhts_net_desc *d, const dhts_net_tables *t,
     const int E = t->n_edges > 0 ? t->n_edges : 1;
     const size_t lds = net_bwd_lds_base(L, C, E, d->n_inter_sq) + net_staged_bytes(L, d->n_inter_sq, d->n_action);
     if (lds > 160 * 1024) return DHTS_E_INVALID;
-#define DHTS_NET_BWD_LAUNCH(MB)                                                                                                       \
-    {                                                                                                                                 \
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)net_macro_bwd_kernel<MB>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                   (int)lds) != hipSuccess)                                                          \
-            return DHTS_E_LAUNCH;                                                                                                     \
-        net_macro_bwd_kernel<MB><<<d->n_replicas, B, lds, (hipStream_t)stream>>>(                                                     \
-            d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action, d->dt, d->u_max, d->static_speed,       \
-            d->vehicle_length, net_tables(t), action, hist, reinterpret_cast<const float4 *>(tape), kc, queue, g_reward, g_action,    \
-            workspace, err);                                                                                                          \
-    }
-    if (B <= 512) DHTS_NET_BWD_LAUNCH(512) else DHTS_NET_BWD_LAUNCH(1024)
-#undef DHTS_NET_BWD_LAUNCH
-    return hipGetLastError() == hipSuccess ? DHTS_OK : DHTS_E_LAUNCH;
+    bool lds_ok = true;
+    pick<1024, 512>(B <= 512 ? 512 : 1024, [&](auto mb) {
+        const auto kern = net_macro_bwd_kernel<decltype(mb)::value>;
+        if ((lds_ok = allow_lds(kern, lds)))
+            launch(kern, d->n_replicas, B, lds, stream, d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action,
+                   d->dt, d->u_max, d->static_speed, d->vehicle_length, net_tables(t), action, hist, reinterpret_cast<const float4 *>(tape),
+                   kc, queue, g_reward, g_action, workspace, err);
+    });
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
 }  // extern "C"

@@ -1095,3 +1095,32 @@ def test_micro_step_under_a_tensor_head_gap_vs_oracle(cuda, oracle, V):
         head_differs += int(nv_h[l, -1].item() != nv_a[l, -1].item())
     print("heads whose new speed differs from the double step's: %d of %d" % (head_differs, L))
     assert head_differs > 0
+
+
+# =================================================================================================================
+# dhts_set_option: the values every option takes
+# =================================================================================================================
+@pytest.mark.parametrize("name,accepted,refused,default", [
+    ("OPT_MACRO_FWD_WAVES", (0, 1, 16), (-1, 17), 0),
+    ("OPT_MICRO_FWD_WAVES", (0, 1, 2, 4), (-1, 3, 5, 8), 0),
+    ("OPT_MACRO_FWD_VARIANT", (0, 1, 2), (-1, 3), 0),
+    ("OPT_MACRO_FWD_GROUP", (0, 1, 2, 4), (-1, 3, 5, 8), 0),
+    ("OPT_MACRO_FWD_ROTATE", (0, 1), (-1, 2), 1),
+    ("OPT_NETSTEP_LDS_KB", (0, 1, 158), (-1, 159), 0),
+    ("OPT_NETSTEP_BLOCK", (0, 256, 512, 1024), (-1, 1, 128, 255, 257, 768, 1025, 2048), 0),
+    ("OPT_HYB_PACK", (0, 1, 2), (-1, 3), 2),
+    ("OPT_REWARD_CHAIN", (0, 1), (-1, 2), 0),
+])
+def test_set_option_accepts_exactly_its_documented_values(name, accepted, refused, default):
+    """include/dhts.h: every option's values just inside its accepted set are taken (DHTS_OK) and those just outside refused
+    (DHTS_E_INVALID) without touching the setting; an unknown option is refused."""
+    from dhts import _lib
+    lib = _lib.lib()
+    try:
+        for v in accepted:
+            assert lib.dhts_set_option(getattr(_lib, name), v) == _lib.OK, (name, v)
+        for v in refused:
+            assert lib.dhts_set_option(getattr(_lib, name), v) == _lib.E_INVALID, (name, v)
+    finally:
+        assert lib.dhts_set_option(getattr(_lib, name), default) == _lib.OK
+    assert lib.dhts_set_option(0, 0) == _lib.E_INVALID and lib.dhts_set_option(10, 0) == _lib.E_INVALID
