@@ -275,4 +275,53 @@ __device__ __forceinline__ void idm_step(double p, double v, double dp_raw, doub
     o.dLd[3] = clipped_a ? 0.f : (float)l3;
 }
 
+// ---- partials with respect to the driver parameters -----------------------------------------------------------
+// d acc / d (accel_max, accel_pref, target_speed, min_space, time_pref, gap) of IDM.compute_acceleration (_idm.py:30-49) as the
+// forward executed it -- what autograd of the plain MicroLane (_micro_lane.py:166-183) gives when a vehicle's attributes are tensors:
+//   c = v dv / (2 sqrt(a b))   s = max(s0 + v T + c, 0)   F = 1 - (v / v0)^4 - (s / gap)^2   Q = -2 a s / gap^2
+//   d/da = F - Q c / (2 a)   d/db = -Q c / (2 b)   d/dv0 = 4 a (v / v0)^4 / v0   d/ds0 = Q   d/dT = Q v   d/dgap = 2 a s^2 / gap^3
+// Under the spacing clip s = 0 and every Q term vanishes; under the acceleration clip acc = -v / dt holds no parameter.
+// The per-vehicle constants are IEEE operations done once; a step has ONE division (the gap's reciprocal, IEEE: this runs in the reverse
+// sweep, which waits for its tape and has the instructions to spare).
+struct IdmParamDerived {
+    double a_max, min_space, time_pref;
+    double inv_2sab, inv_vt, inv_2a, inv_2b;
+};
+__device__ __forceinline__ IdmParamDerived idm_param_derive(const IdmParams &m) {
+    IdmParamDerived d;
+    d.a_max = m.a_max; d.min_space = m.min_space; d.time_pref = m.time_pref;
+    d.inv_2sab = 1.0 / (2 * sqrt(m.a_max * m.a_pref));
+    d.inv_vt = 1.0 / m.v_target;
+    d.inv_2a = 1.0 / (2 * m.a_max);
+    d.inv_2b = 1.0 / (2 * m.a_pref);
+    return d;
+}
+struct IdmParamJac {
+    double d[6];        // d acc / d (a_max, a_pref, v_target, min_space, time_pref, gap); all 0 under the acceleration clip
+    bool clipped_acc, clipped_spacing;
+};
+// v: ego speed; gap, dv: the operands compute_acceleration received (the gap AFTER the collision rule and the clamp to
+// POSITION_DELTA_EPS, _micro_lane.py:151-166)
+__device__ __forceinline__ void idm_param_jac(double v, double gap, double dv, const IdmParamDerived &m, double dt, IdmParamJac &o) {
+    const double c = (v * dv) * m.inv_2sab;
+    const double s_raw = m.min_space + v * m.time_pref + c;
+    o.clipped_spacing = (s_raw < 0.0);
+    const double s = o.clipped_spacing ? 0. : s_raw;
+    const double rg = 1.0 / gap;
+    const double vr = v * m.inv_vt;
+    const double vr2 = vr * vr;
+    const double vr4 = vr2 * vr2;
+    const double sr = s * rg;
+    const double F = 1.0 - vr4 - sr * sr;
+    o.clipped_acc = (m.a_max * F < -v / dt);
+    const double Q = -2.0 * m.a_max * sr * rg;
+    const double Qc = o.clipped_spacing ? 0. : Q * c;
+    o.d[0] = F - Qc * m.inv_2a;
+    o.d[1] = -Qc * m.inv_2b;
+    o.d[2] = 4.0 * m.a_max * vr4 * m.inv_vt;
+    o.d[3] = Q;
+    o.d[4] = Q * v;
+    o.d[5] = -Q * sr;
+}
+
 }  // namespace dhts

@@ -26,18 +26,33 @@ namespace dhts {
 // both 0 under the acceleration clip (didm.py:38-103) -- 12 bytes per vehicle-step instead of the 32 of dqs[V][2][2][2]
 struct __attribute__((packed, aligned(4))) MicroTape3 { float e2, e3, l3; };
 
+// The parameter tape (dhts_micro_param_tape_bytes; opaque to callers): a 64-byte header that names the shape it was written for, the
+// lanes' head gaps [L][2] double (the reverse sweep is not handed them) rounded up to whole 64 bytes, then [step][lane][Vp] float2 =
+// the (p, v) a vehicle entered the step with: 8 B per vehicle-step.
+struct ParamTapeHeader { int32_t magic, L, V, T; int32_t pad[12]; };
+constexpr int32_t kParamTapeMagic = 0x50544431;
+__host__ __device__ inline ParamTapeHeader param_tape_header(int L, int V, int T) {
+    ParamTapeHeader h = {};
+    h.magic = kParamTapeMagic; h.L = L; h.V = V; h.T = T;
+    return h;
+}
+__host__ __device__ inline size_t param_tape_steps_offset(int L) { return sizeof(ParamTapeHeader) + (((size_t)L * 16 + 63) & ~(size_t)63); }
+
 // grid = L workgroups of 64 * kW threads; dynamic LDS = 2 * (V + 1) floats (kW = 1) or twice that (kW > 1: the state
 // ping-pongs between two buffers so that one workgroup barrier per step separates a step's reads from the next step's).
 // kW wavefronts per lane: thread `tid` of pass j owns slot (64 kW) j + tid.
 // kFull: every slot of every lane holds a vehicle (no counts, V = 64 kW K): no validity masks, no index clamps, and only the
 // last pass can hold the head vehicle.
-template <int K, int kW, bool kCompact, bool kFull>
+// kParams: the rollout will be differentiated with respect to the driver parameters too: beside the tape, every step writes the
+// operands of its IDM evaluation that the reverse sweep cannot rebuild -- the vehicle's pre-step (p, v) -- into the parameter tape
+// (layout: ParamTapeHeader below).  Same arithmetic, same tape, same outputs as without it.
+template <int K, int kW, bool kCompact, bool kFull, bool kParams = false>
 __global__ __launch_bounds__(64 * kW) void micro_rollout_fwd_kernel(
     int L, int V, int T, double dt,
     const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ tape, float *__restrict__ hist,
-    dhts_error *err) {
+    dhts_error *err, char *__restrict__ ptape = nullptr) {
     extern __shared__ float lds[];
     const int lane = blockIdx.x;
     const int t = threadIdx.x;
@@ -72,6 +87,15 @@ __global__ __launch_bounds__(64 * kW) void micro_rollout_fwd_kernel(
     __syncthreads();
     const double head_dp = head[(size_t)lane * 2], head_dv = head[(size_t)lane * 2 + 1];
     int fault_step = -1, fault_index = 0;
+    float2 *pt0 = nullptr;
+    if constexpr (kParams) {
+        if (t == 0) {
+            if (lane == 0) *reinterpret_cast<ParamTapeHeader *>(ptape) = param_tape_header(L, V, T);
+            double *ph = reinterpret_cast<double *>(ptape + sizeof(ParamTapeHeader)) + (size_t)lane * 2;
+            ph[0] = head_dp; ph[1] = head_dv;
+        }
+        pt0 = reinterpret_cast<float2 *>(ptape + param_tape_steps_offset(L)) + (size_t)lane * Vp;
+    }
 
     for (int step = 0; step < T; ++step) {
         float4 *tp = (tape && !kCompact) ? reinterpret_cast<float4 *>(tape) + ((size_t)step * L + lane) * 2 * Vp : nullptr;
@@ -115,6 +139,7 @@ __global__ __launch_bounds__(64 * kW) void micro_rollout_fwd_kernel(
                     tp[Vp + i] = make_float4(o.dLd[0], o.dLd[1], o.dLd[2], o.dLd[3]);
                 }
                 if (hp) { hp[i] = o.np; hp[V + i] = o.nv; }
+                if constexpr (kParams) pt0[(size_t)step * L * Vp + i] = make_float2(rp[j], rv[j]);
             }
         }
         if constexpr (kW > 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS-only: tape stores stay in flight
@@ -177,12 +202,39 @@ __global__ void idm_jac_batch_kernel(int64_t n, const double *__restrict__ in, f
     }
 }
 
-// grid = L workgroups of blockDim.x threads; dynamic LDS = 4 * (V + 2) floats
-template <bool kCompact>
+// known-answer entry of the parameter partials ALONE (idm_param_jac, the function the reverse sweep calls): n independent operand
+// sets, in [9][n] double as idm_batch_kernel's with the RAW gap; the collision rule and the clamp are the lane's (a gap the forward
+// replaced by a constant has no partial).  dacc [6][n] = d acc / d (a_max, a_pref, v_target, min_space, time_pref, gap)
+__global__ void idm_param_jac_batch_kernel(int64_t n, const double *__restrict__ in, double *__restrict__ dacc, int32_t *__restrict__ clips) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        IdmParams m;
+        m.a_max = in[i]; m.a_pref = in[n + i]; m.v_target = in[3 * n + i]; m.min_space = in[6 * n + i];
+        m.time_pref = in[7 * n + i]; m.length = 0.;
+        const double v = in[2 * n + i], dt = in[8 * n + i];
+        double gap = in[4 * n + i], dv = in[5 * n + i];
+        const bool live_gap = gap >= 1e-5;
+        if (gap < 0) { gap = 0; dv = 0; }
+        gap = (1e-5 > gap) ? 1e-5 : gap;
+        IdmParamJac pj;
+        idm_param_jac(v, gap, dv, idm_param_derive(m), dt, pj);
+        for (int q = 0; q < 6; ++q) dacc[q * n + i] = (pj.clipped_acc || (q == 5 && !live_gap)) ? 0. : pj.d[q];
+        clips[i] = pj.clipped_acc ? 1 : 0; clips[n + i] = pj.clipped_spacing ? 1 : 0;
+    }
+}
+
+// grid = L workgroups of blockDim.x threads; dynamic LDS = 4 * (V + 2) floats (kParams: 6 * (V + 2))
+// kParams: the sweep also sums, per vehicle, gv dt d acc / d theta over the steps (gv = the cotangent of the vehicle's speed AFTER the
+// step, g_hist term included): the partials are recomputed in double from the parameter tape's pre-step (p, v), the leader's (through
+// LDS) and the vehicle's parameters in registers; the acceleration clip is the forward's own decision, read off the tape entry (all
+// three zero).  Six double sums per thread, added in step order -- no atomics.  One vehicle per thread only: the launch sizes the
+// block to the lane (up to 1024 threads), a smaller block is reported as DHTS_FAULT_CAPACITY and g_params is NaN.
+// The state recurrence is the same instructions on the same values: g_p_out, g_v_out, g_head are those of the sweep without it.
+template <bool kCompact, bool kParams = false>
 __global__ void micro_rollout_bwd_kernel(
     int L, int V, int T, double dt, const float *__restrict__ tape, const int32_t *__restrict__ count,
     const float *__restrict__ g_p_in, const float *__restrict__ g_v_in, const float *__restrict__ g_hist,
-    float *__restrict__ g_p_out, float *__restrict__ g_v_out, double *__restrict__ g_head, int fold, dhts_error *err) {
+    float *__restrict__ g_p_out, float *__restrict__ g_v_out, double *__restrict__ g_head, int fold, dhts_error *err,
+    const char *__restrict__ ptape = nullptr, const double *__restrict__ params = nullptr, double *__restrict__ g_params = nullptr) {
     extern __shared__ float lds[];
     const int lane = blockIdx.x;
     const int t = threadIdx.x;
@@ -201,6 +253,27 @@ __global__ void micro_rollout_bwd_kernel(
     double gh_p = 0., gh_v = 0.;       // held by the thread that owns the head vehicle
     int bad_step = -1, bad_index = 0;  // first non-finite cotangent this thread meets (the latest step: the sweep runs backwards)
     int step_hi = T - 1;
+    // kParams: this thread's vehicle, its sums, and whether the parameter tape is the one a forward of this shape wrote
+    float *Xp = lds + 4 * P, *Xv = lds + 5 * P;        // pre-step state of the step being replayed (kParams only)
+    IdmParamDerived pm = {};
+    double half_len = 0., head_dp = 0., head_dv = 0.;
+    double sum[6] = {0., 0., 0., 0., 0., 0.};           // a_max, a_pref, v_target, min_space, time_pref, gap
+    bool pt_ok = false;
+    if constexpr (kParams) {
+        const ParamTapeHeader h = *reinterpret_cast<const ParamTapeHeader *>(ptape);
+        pt_ok = h.magic == kParamTapeMagic && h.L == L && h.V == V && h.T == T && V <= B;
+        if (pt_ok && t < n) {
+            const size_t plane = (size_t)L * V;
+            IdmParams raw;
+            raw.a_max = params[0 * plane + base + t]; raw.a_pref = params[1 * plane + base + t];
+            raw.v_target = params[2 * plane + base + t]; raw.min_space = params[3 * plane + base + t];
+            raw.time_pref = params[4 * plane + base + t]; raw.length = params[5 * plane + base + t];
+            pm = idm_param_derive(raw);
+            half_len = (params[5 * plane + base + (t + 1 < n ? t + 1 : t)] + raw.length) * 0.5;
+            const double *ph = reinterpret_cast<const double *>(ptape + sizeof(ParamTapeHeader)) + (size_t)lane * 2;
+            head_dp = ph[0]; head_dv = ph[1];
+        }
+    }
     if constexpr (kCompact) {
         if (V <= B && T > 0) {         // (T = 0: no tape to prefetch from -- the tape pointer may be NULL)
             // One vehicle per thread (the rollouts' common shape): the tape entry of the NEXT step to replay is loaded while
@@ -221,11 +294,20 @@ __global__ void micro_rollout_bwd_kernel(
                 hp1 = a[0]; hv1 = a[V]; hp2 = b[0]; hv2 = b[V];
             }
             const float dtf = (float)dt;
+            // (a tape of another shape is never read: the loads stay on its header)
+            const float2 *pt0 = reinterpret_cast<const float2 *>(ptape + ((kParams && pt_ok) ? param_tape_steps_offset(L) : 0)) +
+                                ((kParams && pt_ok) ? (size_t)lane * Vp + (k < V ? k : 0) : 0);
+            const size_t pstride = (kParams && pt_ok) ? step_stride : 0;
+            float2 px = make_float2(0.f, 0.f), px2 = px;
+            if constexpr (kParams) { px = pt0[(size_t)(T - 1) * pstride]; px2 = pt0[(size_t)(T > 1 ? T - 2 : 0) * pstride]; }
             for (int step = T - 1; step >= 0; --step) {
                 const MicroTape3 c = nx;
                 const float chp = hp1, chv = hv1;
                 nx = nx2; hp1 = hp2; hv1 = hv2;
                 nx2 = tc0[(size_t)(step > 1 ? step - 2 : 0) * step_stride];       // two steps ahead
+                const float2 cx = px;
+                float gv_step = 0.f;
+                if constexpr (kParams) { px = px2; px2 = pt0[(size_t)(step > 1 ? step - 2 : 0) * pstride]; }
                 if (gh0) { const float *a = gh0 + (size_t)(step > 1 ? step - 2 : 0) * h_stride; hp2 = a[0]; hv2 = a[V]; }
                 if (vk) {
                     float gp = Gp[k], gv = Gv[k];
@@ -234,8 +316,29 @@ __global__ void micro_rollout_bwd_kernel(
                     Gv[k] = dot2(dtf, gp, c.e3, gv);
                     C1p[k + 1] = dot2(0.f, gp, -c.e2, gv);     // grad_ps[1:] += dqs[:, 1]^T g
                     C1v[k + 1] = dot2(0.f, gp, c.l3, gv);
+                    if constexpr (kParams) { Xp[k] = cx.x; Xv[k] = cx.y; gv_step = gv; }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if constexpr (kParams) {
+                    if (vk && pt_ok) {
+                        // compute_state_delta and the collision / clamp rules of the forward, _micro_lane.py:149-166, 201-212
+                        const bool is_head = k == n - 1;
+                        const double pv = cx.y;
+                        double gap = is_head ? head_dp : fabs((double)Xp[k + 1] - (double)cx.x) - half_len;
+                        double dv = is_head ? head_dv : pv - (double)Xv[k + 1];
+                        const bool live_gap = !is_head && gap >= 1e-5;       // else a constant: nothing flows to the lengths
+                        if (gap < 0) { gap = 0; dv = 0; }
+                        gap = (1e-5 > gap) ? 1e-5 : gap;
+                        if (!(c.e2 == 0.f && c.e3 == 0.f && c.l3 == 0.f)) {  // (the forward's acceleration clip zeroes all three)
+                            IdmParamJac pj;
+                            idm_param_jac(pv, gap, dv, pm, dt, pj);
+                            const double w = (double)gv_step * dt;
+#pragma unroll
+                            for (int q = 0; q < 5; ++q) sum[q] += w * pj.d[q];
+                            if (live_gap) sum[5] += w * pj.d[5];
+                        }
+                    }
+                }
                 if (vk) {
                     float np_ = Gp[k], nv_ = Gv[k];
                     if (k > 0) { np_ += C1p[k]; nv_ += C1v[k]; }
@@ -303,6 +406,22 @@ __global__ void micro_rollout_bwd_kernel(
     for (int k = t; k < V; k += B) {
         g_p_out[base + k] = (k < n) ? Gp[k] : 0.f;
         g_v_out[base + k] = (k < n) ? Gv[k] : 0.f;
+    }
+    if constexpr (kParams) {
+        // length enters a gap as -(len_leader + len) / 2 (_micro_lane.py:211): a vehicle's own gap sum and its follower's
+        double *A = reinterpret_cast<double *>(C1p);            // (C1p, C1v: 2 P floats = P doubles; the sweeps are done with them)
+        __syncthreads();
+        if (t < V) A[t] = (t < n) ? sum[5] : 0.;
+        __syncthreads();
+        if (t < V) {
+            const size_t plane = (size_t)L * V;
+            const bool live = t < n;
+            const double nan = __builtin_nan("");
+#pragma unroll
+            for (int q = 0; q < 5; ++q) g_params[q * plane + base + t] = !pt_ok ? nan : (live ? sum[q] : 0.);
+            g_params[5 * plane + base + t] = !pt_ok ? nan : (live ? -0.5 * (A[t] + (t > 0 ? A[t - 1] : 0.)) : 0.);
+        }
+        if (!pt_ok && t == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);      // not this shape's parameter tape (or block < lane)
     }
     if (g_head) {
         if (n == 0) { if (t == 0) { g_head[(size_t)lane * 2] = 0.; g_head[(size_t)lane * 2 + 1] = 0.; } }
@@ -384,6 +503,9 @@ struct MicroPlan {
     bool full;               // forward: every slot of every lane holds a vehicle (kFull)
     int bwd_block;           // reverse: threads per lane
     bool bwd_per_thread;     // reverse: the one-vehicle-per-thread sweep (the kernel's own test: the lane fits the block and there is a tape)
+    // the rollout that is differentiated w.r.t. the driver parameters too (dhts_micro_rollout_fwd_params / _bwd_params)
+    int ptape_bytes;         // parameter tape, bytes per vehicle-step: 8 = the pre-step (p, v), partials recomputed in the reverse sweep
+    int pbwd_block;          // its reverse sweep: threads per lane -- the whole lane, one vehicle per thread holds its six double sums
 };
 static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     MicroPlan pl;
@@ -397,21 +519,24 @@ static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     pl.full = !has_count && d->capacity == 64 * pl.W * pl.K;
     pl.bwd_block = padded64(d->capacity) > 256 ? 256 : padded64(d->capacity);
     pl.bwd_per_thread = d->capacity <= pl.bwd_block && T > 0;
+    pl.ptape_bytes = (int)sizeof(float2);
+    pl.pbwd_block = padded64(d->capacity);
     return pl;
 }
 
-template <bool kCompact>
+template <bool kCompact, bool kParams = false>
 static int micro_fwd_launch(const dhts_micro_desc *d, int T,
                             const float *p, const float *v, const int32_t *count, const double *params, const double *head,
-                            float *p_out, float *v_out, float *tape, float *hist, dhts_error *err, void *stream) {
+                            float *p_out, float *v_out, float *tape, float *hist, dhts_error *err, void *stream, char *ptape = nullptr) {
     if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || !head || !p_out || !v_out) return DHTS_E_INVALID;
+    if (kParams && (!ptape || (T > 0 && !tape))) return DHTS_E_INVALID;      // (the reverse sweep reads the acceleration clip off the tape)
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
     const size_t lds = sizeof(float) * (pl.W > 1 ? 4 : 2) * (size_t)(d->capacity + 1);
     pick<1, 2, 4>(pl.W, [&](auto w) {
         pick<16, 8, 4, 2, 1>(pl.K, [&](auto k) {
             pick<0, 1>(pl.full, [&](auto full) {
-                launch(micro_rollout_fwd_kernel<decltype(k)::value, decltype(w)::value, kCompact, decltype(full)::value != 0>, d->n_lanes,
-                       64 * pl.W, lds, stream, d->n_lanes, d->capacity, T, d->dt, p, v, count, params, head, p_out, v_out, tape, hist, err);
+                launch(micro_rollout_fwd_kernel<decltype(k)::value, decltype(w)::value, kCompact, decltype(full)::value != 0, kParams>, d->n_lanes,
+                       64 * pl.W, lds, stream, d->n_lanes, d->capacity, T, d->dt, p, v, count, params, head, p_out, v_out, tape, hist, err, ptape);
             });
         });
     });
@@ -424,7 +549,18 @@ static int micro_bwd_launch(const dhts_micro_desc *d, int T, const float *tape, 
     if (!micro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_p || !g_v || !g_p_out || !g_v_out) return DHTS_E_INVALID;
     const size_t lds = sizeof(float) * 4 * (size_t)(d->capacity + 2);
     launch(micro_rollout_bwd_kernel<kCompact>, d->n_lanes, micro_plan(d, T, count != nullptr).bwd_block, lds, stream,
-           d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, fold, err);
+           d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, fold, err,
+           (const char *)nullptr, (const double *)nullptr, (double *)nullptr);
+    return launch_status();
+}
+static int micro_bwd_params_launch(const dhts_micro_desc *d, int T, const float *tape, const char *ptape, const int32_t *count,
+                                   const double *params, const float *g_p, const float *g_v, const float *g_hist,
+                                   float *g_p_out, float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream) {
+    if (!micro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !ptape || !params || !g_params || !g_p || !g_v || !g_p_out || !g_v_out)
+        return DHTS_E_INVALID;
+    const size_t lds = sizeof(float) * 6 * (size_t)(d->capacity + 2);
+    launch(micro_rollout_bwd_kernel<true, true>, d->n_lanes, micro_plan(d, T, count != nullptr).pbwd_block, lds, stream,
+           d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, 1, err, ptape, params, g_params);
     return launch_status();
 }
 template <bool kHeadOnly>
@@ -472,6 +608,26 @@ int dhts_micro_rollout_bwd(const dhts_micro_desc *d, int T, const float *tape, c
                                       float *g_p_out, float *g_v_out, double *g_head, dhts_error *err, void *stream) {
     return micro_bwd_launch<true>(d, T, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, 1, err, stream);
 }
+size_t dhts_micro_param_tape_bytes(const dhts_micro_desc *d, int T) {
+    if (!micro_desc_ok(d) || T < 0) return 0;
+    return param_tape_steps_offset(d->n_lanes) + (size_t)T * d->n_lanes * padded64(d->capacity) * micro_plan(d, T, false).ptape_bytes;
+}
+int dhts_micro_rollout_fwd_params(const dhts_micro_desc *d, int T,
+                                  const float *p, const float *v, const int32_t *count, const double *params, const double *head,
+                                  float *p_out, float *v_out, float *tape, void *ptape, float *hist, dhts_error *err, void *stream) {
+    return micro_fwd_launch<true, true>(d, T, p, v, count, params, head, p_out, v_out, tape, hist, err, stream, (char *)ptape);
+}
+int dhts_micro_rollout_bwd_params(const dhts_micro_desc *d, int T, const float *tape, const void *ptape, const int32_t *count,
+                                  const double *params, const float *g_p, const float *g_v, const float *g_hist,
+                                  float *g_p_out, float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream) {
+    return micro_bwd_params_launch(d, T, tape, (const char *)ptape, count, params, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, g_params,
+                                   err, stream);
+}
+int dhts_idm_param_jac_batch(int64_t n, const double *in, double *dacc, int32_t *clips, void *stream) {
+    if (n <= 0 || !in || !dacc || !clips) return DHTS_E_INVALID;
+    launch(idm_param_jac_batch_kernel, grid_1d(n, 4096), 256, 0, stream, n, in, dacc, clips);
+    return launch_status();
+}
 // which kernel instantiations dhts_micro_rollout_fwd / _bwd launch for this shape: the plan the launches read
 int dhts_micro_rollout_plan(const dhts_micro_desc *d, int T, int has_count, int32_t plan[8]) {
     if (!micro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
@@ -482,6 +638,8 @@ int dhts_micro_rollout_plan(const dhts_micro_desc *d, int T, int has_count, int3
     plan[2] = pl.full ? 1 : 0;
     plan[3] = pl.bwd_per_thread ? 1 : 0;
     plan[4] = pl.bwd_block;
+    plan[5] = pl.ptape_bytes;
+    plan[6] = pl.pbwd_block;
     return DHTS_OK;
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)

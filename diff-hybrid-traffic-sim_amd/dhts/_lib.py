@@ -115,6 +115,10 @@ SIGNATURES = {
     "dhts_micro_step_tape_bytes": (C.c_size_t, [C.POINTER(MicroDesc)]),
     "dhts_micro_rollout_fwd": (C.c_int, [C.POINTER(MicroDesc), C.c_int] + [_P] * 11),
     "dhts_micro_rollout_bwd": (C.c_int, [C.POINTER(MicroDesc), C.c_int] + [_P] * 10),
+    "dhts_micro_param_tape_bytes": (C.c_size_t, [C.POINTER(MicroDesc), C.c_int]),
+    "dhts_micro_rollout_fwd_params": (C.c_int, [C.POINTER(MicroDesc), C.c_int] + [_P] * 12),
+    "dhts_micro_rollout_bwd_params": (C.c_int, [C.POINTER(MicroDesc), C.c_int] + [_P] * 13),
+    "dhts_idm_param_jac_batch": (C.c_int, [C.c_int64] + [_P] * 4),
     "dhts_micro_rollout_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
     "dhts_micro_step_fwd": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),

@@ -255,6 +255,12 @@ def micro_tape_numel(desc, T):
     return _lib.lib().dhts_micro_tape_bytes(C.byref(desc), int(T)) // 4
 
 
+def micro_param_tape_numel(desc, T):
+    """float32 elements of the parameter tape of a rollout that is differentiated w.r.t. the driver parameters (opaque: a header, the
+    head gaps and 8 bytes per vehicle-step, include/dhts.h)."""
+    return _lib.lib().dhts_micro_param_tape_bytes(C.byref(desc), int(T)) // 4
+
+
 def micro_step_tape_numel(desc):
     """float32 elements of the single-step operator's tape (the reference's dqs)."""
     return _lib.lib().dhts_micro_step_tape_bytes(C.byref(desc)) // 4
@@ -273,8 +279,9 @@ def micro_step_fwd(desc, p, v, params, head, count=None, tape=None, err=None, te
     return out
 
 
-def micro_rollout_fwd(desc, T, p, v, params, head, count=None, tape=None, hist=None, err=None, out=None):
-    """p, v [L][V] float32; params [6][L][V] float64; head [L][2] float64; count [L] int32 or None."""
+def micro_rollout_fwd(desc, T, p, v, params, head, count=None, tape=None, hist=None, err=None, out=None, ptape=None):
+    """p, v [L][V] float32; params [6][L][V] float64; head [L][2] float64; count [L] int32 or None.
+    ptape (float32 [micro_param_tape_numel]): also fill the parameter tape (dhts_micro_rollout_fwd_params; needs `tape`)."""
     L, V = desc.n_lanes, desc.capacity
     p, v = _f32c(p, "p"), _f32c(v, "v")
     if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
@@ -288,18 +295,41 @@ def micro_rollout_fwd(desc, T, p, v, params, head, count=None, tape=None, hist=N
     params, head = params.contiguous(), head.contiguous()
     if out is None:
         out = (torch.empty_like(p), torch.empty_like(v))
+    if ptape is not None:
+        if ptape.dtype != torch.float32 or ptape.numel() != micro_param_tape_numel(desc, T):
+            raise ValueError("ptape must be float32 [micro_param_tape_numel(desc, T)]")
+        check(_lib.lib().dhts_micro_rollout_fwd_params(C.byref(desc), int(T), _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
+                                                       _ptr(out[0]), _ptr(out[1]), _ptr(tape), _ptr(ptape), _ptr(hist), _ptr(err),
+                                                       _stream()), "dhts_micro_rollout_fwd_params")
+        return out
     check(_lib.lib().dhts_micro_rollout_fwd(C.byref(desc), int(T), _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
                                             _ptr(out[0]), _ptr(out[1]), _ptr(tape), _ptr(hist), _ptr(err), _stream()),
           "dhts_micro_rollout_fwd")
     return out
 
 
-def micro_rollout_bwd(desc, T, tape, g_p, g_v, count=None, g_hist=None, err=None, out=None, g_head=None):
+def micro_rollout_bwd(desc, T, tape, g_p, g_v, count=None, g_hist=None, err=None, out=None, g_head=None,
+                      ptape=None, params=None, g_params=None):
+    """Reverse sweep -> (g_p0, g_v0, g_head).  With ptape, params (the forward's) and g_params (float64 [6][L][V], filled here) the
+    sweep also sums the gradient w.r.t. the driver parameters (dhts_micro_rollout_bwd_params); the three go together."""
     g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
     if out is None:
         out = (torch.empty_like(g_p), torch.empty_like(g_v))
     if g_head is None:
         g_head = torch.zeros(desc.n_lanes, 2, dtype=torch.float64, device=g_p.device)
+    if ptape is not None or params is not None or g_params is not None:
+        L, V = desc.n_lanes, desc.capacity
+        if ptape is None or params is None or g_params is None:
+            raise ValueError("ptape, params and g_params go together")
+        if ptape.dtype != torch.float32 or ptape.numel() != micro_param_tape_numel(desc, T):
+            raise ValueError("ptape must be float32 [micro_param_tape_numel(desc, T)]")
+        for name, t in (("params", params), ("g_params", g_params)):
+            if t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
+        check(_lib.lib().dhts_micro_rollout_bwd_params(C.byref(desc), int(T), _ptr(tape), _ptr(ptape), _ptr(count), _ptr(params),
+                                                       _ptr(g_p), _ptr(g_v), _ptr(g_hist), _ptr(out[0]), _ptr(out[1]), _ptr(g_head),
+                                                       _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_params")
+        return out[0], out[1], g_head
     check(_lib.lib().dhts_micro_rollout_bwd(C.byref(desc), int(T), _ptr(tape), _ptr(count), _ptr(g_p), _ptr(g_v),
                                             _ptr(g_hist), _ptr(out[0]), _ptr(out[1]), _ptr(g_head), _ptr(err), _stream()),
           "dhts_micro_rollout_bwd")
@@ -312,6 +342,14 @@ def micro_rollout_plan(desc, T, has_count=False):
     check(_lib.lib().dhts_micro_rollout_plan(C.byref(desc), int(T), int(bool(has_count)), C.byref(plan)), "dhts_micro_rollout_plan")
     keys = ("fwd_waves", "fwd_passes", "fwd_full_lane", "bwd_one_vehicle_per_thread", "bwd_block")
     return dict(zip(keys, list(plan)[:5]))
+
+
+def micro_param_plan(desc, T, has_count=False):
+    """The same plan's entries for the rollout that is differentiated w.r.t. the driver parameters: bytes per vehicle-step of its
+    parameter tape (8 = the pre-step state; the reverse sweep recomputes the partials) and the block size of its reverse sweep."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_micro_rollout_plan(C.byref(desc), int(T), int(bool(has_count)), C.byref(plan)), "dhts_micro_rollout_plan")
+    return dict(param_tape_bytes=plan[5], param_bwd_block=plan[6])
 
 
 def micro_step_bwd(desc, tape, g_p, g_v, count=None):
@@ -332,6 +370,9 @@ class MicroRollout(torch.autograd.Function):
     (micro.py:36-118): vehicles ordered tail -> head, head gap = lane defaults (1000, 0).
     The head gap is differentiable: `head` [L][2] float64 receives the cotangent of
     (head_position_delta, head_speed_delta).
+    So are the driver parameters: when `params` [6][L][V] float64 requires grad, the forward also fills the parameter tape and the
+    reverse sweep returns d loss / d params (what autograd of the reference's plain MicroLane gives for tensor attributes,
+    _micro_lane.py:131-214 over _idm.py:30-49); outputs and the other gradients are bit for bit those of a call without it.
     """
 
     @staticmethod
@@ -339,11 +380,19 @@ class MicroRollout(torch.autograd.Function):
         L, V = p0.shape
         desc = micro_desc(L, V, dt)
         p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
-        need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad
+        want_params = params.requires_grad
+        need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or want_params
         tape = torch.empty(micro_tape_numel(desc, T), dtype=torch.float32, device=p0.device) if need_grad else None
         hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=p0.device) if want_hist else None
         err = new_error_record(p0.device)
-        pT, vT = micro_rollout_fwd(desc, T, p0c, v0c, params, head.detach(), count=count, tape=tape, hist=hist, err=err)
+        # parameter gradient: its tape and its result buffer are made here (nothing is allocated inside backward)
+        ctx.ptape = ctx.params = ctx.g_params = None
+        if want_params:
+            ctx.params = params.detach().contiguous()
+            ctx.ptape = torch.empty(micro_param_tape_numel(desc, T), dtype=torch.float32, device=p0.device)
+            ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=p0.device)
+        pT, vT = micro_rollout_fwd(desc, T, p0c, v0c, params.detach(), head.detach(), count=count, tape=tape, hist=hist, err=err,
+                                   ptape=ctx.ptape)
         if check_faults:                 # a collision is printed like the reference does, and tolerated
             raise_on_fault(err)
         ctx.desc, ctx.T, ctx.tape, ctx.count, ctx.want_hist, ctx.check_faults = desc, T, tape, count, want_hist, check_faults
@@ -363,13 +412,14 @@ class MicroRollout(torch.autograd.Function):
         gh = g_hist.contiguous() if (ctx.want_hist and g_hist is not None) else None
         err = ctx.err_bwd
         err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
-        g_p0, g_v0, g_head = micro_rollout_bwd(desc, T, ctx.tape, g_p, g_v, count=ctx.count, g_hist=gh, err=err)
+        g_p0, g_v0, g_head = micro_rollout_bwd(desc, T, ctx.tape, g_p, g_v, count=ctx.count, g_hist=gh, err=err,
+                                               ptape=ctx.ptape, params=ctx.params, g_params=ctx.g_params)
         # The record only feeds a warning (the reference's micro backward returns NaNs silently, dmicro_lane.py:271-298): it is not
         # read back here -- that would be a host synchronisation per reverse sweep -- unless the gradient that is being returned
         # anyway is non-finite, which the caller's next use of it would synchronise on as well.
         if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
             MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
-        return g_p0, g_v0, None, g_head, None, None, None, None, None
+        return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None
 
 
 def micro_bwd_fault(warn=True):
@@ -445,6 +495,20 @@ def idm_jac_batch(inp):
     dLd = torch.empty(4, n, dtype=torch.float32, device=dev)
     check(_lib.lib().dhts_idm_jac_batch(n, _ptr(soa), _ptr(dE), _ptr(dLd), _stream()), "dhts_idm_jac_batch")
     return dE.t().reshape(n, 2, 2), dLd.t().reshape(n, 2, 2)
+
+
+def idm_param_jac_batch(inp):
+    """inp: float64 [n][9] as idm_batch (a_max a_pref v v_target dp dv min_space time_pref dt, dp raw; CUDA) -> d acc / d (a_max, a_pref,
+    v_target, min_space, time_pref, dp) [n][6] float64 of IDM.compute_acceleration as the lane's step executes it (reference
+    _idm.py:30-49 under _micro_lane.py:151-166), clipped_acc, clipped_spacing [n] bool: the function the parameter reverse sweep calls."""
+    if inp.dtype != torch.float64 or not inp.is_cuda or inp.dim() != 2 or inp.shape[1] != 9:
+        raise TypeError("inp must be a float64 CUDA tensor of shape [n][9]")
+    n, dev = inp.shape[0], inp.device
+    soa = inp.t().contiguous()
+    dacc = torch.empty(6, n, dtype=torch.float64, device=dev)
+    clips = torch.empty(2, n, dtype=torch.int32, device=dev)
+    check(_lib.lib().dhts_idm_param_jac_batch(n, _ptr(soa), _ptr(dacc), _ptr(clips), _stream()), "dhts_idm_param_jac_batch")
+    return dacc.t().contiguous(), clips[0].bool(), clips[1].bool()
 
 
 # ---------------------------------------------------------------------------------------------------------

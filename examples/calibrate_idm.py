@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Calibration of IDM drivers from observed trajectories: the inverse problem the parameter gradient of the fused micro rollout serves.
+
+L lanes of V vehicles (example/inverse/micro.py's initial states: 4 len spacing + U[0, 2 len) jitter, v ~ lerp(0.3, 0.7) u_max), all
+driven by ONE shared driver theta = (accel_max, accel_pref, target_speed, min_space, time_pref); the observed trajectories are a rollout
+of the ground-truth driver (MicroVehicle.default_micro_vehicle).  params = theta[:, None, None].expand(...) puts the same five numbers
+(and the fixed vehicle length) on every vehicle, so autograd sums the per-vehicle gradients of dhts.micro_rollout back onto theta;
+loss = mean squared distance to the observed (p, v) at every step; Adam on theta, kept inside a box around the initial guess.
+Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt, like the other examples.
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "diff-hybrid-traffic-sim_amd"))
+
+import torch as th  # noqa: E402
+
+import dhts  # noqa: E402
+from road.vehicle.micro_vehicle import MicroVehicle  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser("IDM calibration from trajectories (gradient descent on the driver parameters, MI355X)")
+    ap.add_argument("--n_trial", type=int, default=1)
+    ap.add_argument("--n_lane", type=int, default=64)
+    ap.add_argument("--n_vehicle", type=int, default=32)
+    ap.add_argument("--n_step", type=int, default=200)
+    ap.add_argument("--vehicle_length", type=float, default=5.0)
+    ap.add_argument("--speed_limit", type=float, default=30.0)
+    ap.add_argument("--delta_time", type=float, default=0.01)
+    ap.add_argument("--n_episode", type=int, default=100)
+    ap.add_argument("--lr", type=float, default=2e-2)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--run_name", default=None)
+    args = ap.parse_args()
+
+    dev = th.device("cuda", 0)
+    th.manual_seed(args.seed)
+    L, V, T, um, ln, dt = args.n_lane, args.n_vehicle, args.n_step, args.speed_limit, args.vehicle_length, args.delta_time
+    run = args.run_name or "idm_{}".format(time.strftime("%Y%m%d_%H%M%S"))
+    log_dir = os.path.join("result", "calibrate", run, "gd")
+    os.makedirs(log_dir, exist_ok=True)
+
+    truth = th.tensor(MicroVehicle.default_micro_vehicle(um).params(), dtype=th.float64, device=dev)
+    length = truth[5:6]
+    head = th.tensor([[1000.0, 0.0]], dtype=th.float64, device=dev).expand(L, 2).contiguous()
+
+    def rollout(theta):
+        params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+        return dhts.micro_rollout(p0, v0, params, head, T, dt, want_hist=True)[2]
+
+    for trial in range(args.n_trial):
+        p0 = (th.arange(V, device=dev) * 4.0 * ln)[None, :] + th.rand(L, V, device=dev) * 2.0 * ln
+        v0 = th.lerp(th.tensor(0.3 * um, device=dev), th.tensor(0.7 * um, device=dev), th.rand(L, V, device=dev))
+        with th.no_grad():
+            observed = rollout(truth[:5])
+        guess = truth[:5] * (1.0 + 0.2 * (2.0 * th.rand(5, dtype=th.float64, device=dev) - 1.0))
+        lo, hi = 0.5 * guess, 1.5 * guess
+        theta = guess.clone().requires_grad_(True)
+        opt = th.optim.Adam([theta], lr=args.lr)
+        lines = []
+        t0 = time.time()
+        for ep in range(args.n_episode):
+            loss = ((rollout(theta) - observed) ** 2).mean()
+            opt.zero_grad()
+            loss.backward()
+            err = ((theta.detach() - truth[:5]) / truth[:5]).abs().max()
+            opt.step()
+            with th.no_grad():
+                theta.copy_(th.max(th.min(theta, hi), lo))
+            lines.append("{} {}\n".format(err.item(), loss.item()))
+        th.cuda.synchronize()
+        wall = time.time() - t0
+        with open(os.path.join(log_dir, "trial_{}.txt".format(trial)), "w") as f:
+            f.writelines(lines)
+        first, last = lines[0].split(), lines[-1].split()
+        print("Trial # {}: loss {:.6g} -> {:.6g}, worst relative parameter error {:.3f} -> {:.3f} in {} episodes, {:.2f} s".format(
+            trial, float(first[1]), float(last[1]), float(first[0]), float(last[0]), args.n_episode, wall))
+
+
+if __name__ == "__main__":
+    main()

@@ -286,10 +286,49 @@ int dhts_micro_rollout_bwd(const dhts_micro_desc *d, int T, const float *tape, c
                            const float *g_p, const float *g_v, const float *g_hist,
                            float *g_p_out, float *g_v_out, double *g_head, dhts_error *err, void *stream);
 
-/* Which kernel instantiations the two calls above launch (see dhts_macro_rollout_plan):
+/*
+ * The same rollout, differentiated with respect to the DRIVER PARAMETERS as well: what autograd of the reference's plain MicroLane
+ * (road/lane/_micro_lane.py:131-214 over IDM.compute_acceleration, model/micro/_idm.py:30-49) gives when the attributes of its
+ * MicroVehicles are tensors -- the derivative of every step as the forward executed it, summed over the steps.  With gv = the cotangent
+ * of a vehicle's speed after a step (g_hist term included) a step adds gv dt d acc / d theta to the vehicle's own parameters:
+ *     c = v dv / (2 sqrt(a b))     s = max(s0 + v T + c, 0)     F = 1 - (v / v0)^4 - (s / gap)^2     Q = -2 a s / gap^2
+ *     d/da = F - Q c / (2 a)    d/db = -Q c / (2 b)    d/dv0 = 4 a (v / v0)^4 / v0    d/ds0 = Q    d/dT = Q v
+ * (spacing clip: the Q terms vanish; acceleration clip: nothing), and, through gap = |p_lead - p| - (len_lead + len) / 2 (:211),
+ * -0.5 gv dt (2 a s^2 / gap^3) to the vehicle's own length and to its leader's -- not for the head vehicle (its gap is
+ * head_position_delta) nor where the forward replaced the gap by a constant (collision :151-160, POSITION_DELTA_EPS :166).
+ *
+ * dhts_micro_rollout_fwd_params computes, and writes to p_out / v_out / tape / hist, exactly what dhts_micro_rollout_fwd does, and
+ * fills the PARAMETER TAPE ptape beside it (tape and ptape are both required).  ptape is opaque; dhts_micro_param_tape_bytes sizes it:
+ *     64 B header (names the shape it was written for) | head gaps [L][2] double, rounded up to whole 64 B |
+ *     [step][lane][Vp] x 8 B = the float32 (p, v) the vehicle entered the step with        (Vp = capacity rounded up to 64)
+ * i.e. 8 bytes per vehicle-step beside the tape's 12: the reverse sweep recomputes the partials in double from that state, the
+ * leader's and params; the acceleration clip is the forward's own decision, read off the tape entry.
+ * dhts_micro_rollout_bwd_params is dhts_micro_rollout_bwd (same g_p_out, g_v_out, g_head, bit for bit) and returns
+ *     g_params [6][L][V] DOUBLE, laid out like params (slots at or beyond a lane's count: 0)
+ * summed per vehicle in double, in step order, without atomics (bitwise repeatable).  params must be the forward's.  A ptape that
+ * was written for another shape is not read: DHTS_FAULT_CAPACITY (index -3) and g_params = NaN.
+ */
+size_t dhts_micro_param_tape_bytes(const dhts_micro_desc *d, int T);
+int dhts_micro_rollout_fwd_params(const dhts_micro_desc *d, int T,
+                                  const float *p, const float *v, const int32_t *count, const double *params, const double *head,
+                                  float *p_out, float *v_out, float *tape, void *ptape, float *hist, dhts_error *err, void *stream);
+int dhts_micro_rollout_bwd_params(const dhts_micro_desc *d, int T, const float *tape, const void *ptape, const int32_t *count,
+                                  const double *params, const float *g_p, const float *g_v, const float *g_hist,
+                                  float *g_p_out, float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream);
+/* The parameter partials alone, n independent operand sets (the function the reverse sweep above calls):
+ *   in    [9][n] DOUBLE (SoA) as dhts_idm_batch: a_max a_pref v v_target position_delta speed_delta min_space time_pref delta_time,
+ *         position_delta RAW: the collision rule and the clamp to 1e-5 (_micro_lane.py:151-166) are applied here
+ *   out   dacc [6][n] DOUBLE = d acc / d (a_max, a_pref, v_target, min_space, time_pref, position_delta), the last one 0 where the
+ *         gap was replaced by a constant, all 0 under the acceleration clip; clips [2][n] int32 = (clipped_acceleration,
+ *         clipped_optimal_spacing) as this step derived them */
+int dhts_idm_param_jac_batch(int64_t n, const double *in, double *dacc, int32_t *clips, void *stream);
+
+/* Which kernel instantiations the calls above launch (see dhts_macro_rollout_plan):
  *   plan[0] forward wavefronts per lane (1, 2, 4)     plan[1] passes per thread (the literal K: 1, 2, 4, 8, 16)
  *   plan[2] 1 = the full-lane instantiation (count == NULL and capacity = 64 x wavefronts x passes)
- *   plan[3] reverse sweep: 1 = the prefetched one-vehicle-per-thread path, 0 = the strided loop     plan[4] its block size */
+ *   plan[3] reverse sweep: 1 = the prefetched one-vehicle-per-thread path, 0 = the strided loop     plan[4] its block size
+ *   plan[5] the parameter tape's bytes per vehicle-step (8 = pre-step state, partials recomputed by the reverse sweep)
+ *   plan[6] block size of dhts_micro_rollout_bwd_params (the whole lane: always one vehicle per thread) */
 int dhts_micro_rollout_plan(const dhts_micro_desc *d, int T, int has_count, int32_t plan[8]);
 
 int dhts_micro_step_fwd(const dhts_micro_desc *d,

@@ -18,6 +18,7 @@ Golden sets:
   G4     macro_rollout_*.npz T-step rollouts through RoadNetwork.forward with loss and gradients
   G5     idm_kat.npz         IDM.compute_acceleration + dIDM.compute_dEgo/dLeading
   G6     micro_rollout_*.npz dMicroLane rollouts with loss and gradients
+  G6p    micro_params_*.npz  the same lanes through the plain MicroLane with float64 attribute tensors: d loss / d driver parameters
   G7     hybrid_hybrid3.npz  macro -> micro -> macro network with spawn / hand-off events, loss and gradients
   G8     itscp_*.npz         itscp environment (needs tools/ref_stubs for highway_env / gym / pygame): lane table,
                              schedules, per-step macro routes, action -> reward, d reward / d action, per-step queues
@@ -550,6 +551,87 @@ def gen_micro_rollouts(which):
 
 
 # ----------------------------------------------------------------------------------------------
+# G6p: the same lanes through the PLAIN MicroLane with float64 0-dim attribute tensors: autograd fills the attributes' .grad
+# ----------------------------------------------------------------------------------------------
+
+def micro_params_run(V, T, dt, sl, seed, params, tap, spacing, jitter, vlo, vhi, store32):
+    """One differentiated rollout of the plain MicroLane.  store32: after every step the state goes through the lane's own
+    get_state_vector / set_state_vector (a differentiable copy into float32 vectors, _micro_lane.py:227-255) -- the float32 store per
+    step of dMicroLane and of the fused rollout; without it the float64 attribute tensors promote the state to float64 from the first
+    step on, which is ANOTHER rollout at the 1e-5 level after a few hundred steps of dense traffic."""
+    from road.lane._micro_lane import MicroLane
+    th.manual_seed(seed)
+    rng = np.random.default_rng(seed)
+    vlen = 5.0
+    p0 = th.arange(0, V) * spacing * vlen + th.rand(V) * jitter * vlen       # as micro_rollout above: same seeds, same lanes
+    v0 = th.lerp(th.tensor([vlo * sl]), th.tensor([vhi * sl]), th.rand(V))
+    p0 = p0.to(th.float32).requires_grad_(True)
+    v0 = v0.to(th.float32).requires_grad_(True)
+    lane = MicroLane(0, 1e10, sl)
+    names = ("accel_max", "accel_pref", "target_speed", "min_space", "time_pref", "length")
+    par = np.zeros((V, 6), dtype=np.float64)
+    attrs = []
+    for i in range(V):
+        mv = MicroVehicle.default_micro_vehicle(sl)
+        if params == "random":
+            mv.accel_max = float(sl * rng.uniform(0.8, 1.5))
+            mv.accel_pref = float(sl * rng.uniform(0.6, 1.5))
+            mv.target_speed = float(sl * rng.uniform(0.8, 1.2))
+            mv.min_space = float(vlen * rng.uniform(0.1, 1.0))
+            mv.time_pref = float(rng.uniform(0.1, 1.5))
+        par[i] = [float(getattr(mv, k)) for k in names]
+        row = [th.tensor(par[i, j], dtype=th.float64, requires_grad=True) for j in range(6)]
+        for k, t in zip(names, row):
+            setattr(mv, k, t)
+        attrs.append(row)
+        lane.add_head_vehicle(mv)            # slot i follows slot i + 1
+    lane.set_state_vector(p0, v0)
+    head = (lane.head_position_delta, lane.head_speed_delta)
+    loss = 0
+    for t in range(T):
+        lane.forward(dt)
+        lane.update_state()
+        p, v = lane.get_state_vector()
+        if store32:
+            lane.set_state_vector(p, v)
+        if tap == "every_sum":
+            loss = loss + p.sum() + v.sum()
+    pT, vT = lane.get_state_vector()
+    if tap == "final_sq":
+        loss = 1e-4 * (pT ** 2).sum() + (vT ** 2).sum()
+    loss.backward()
+    g_par = np.array([[float(t.grad) if t.grad is not None else 0.0 for t in row] for row in attrs], dtype=np.float64)
+    return dict(p0=p0.detach().numpy(), v0=v0.detach().numpy(), params=par, head=np.array(head, dtype=np.float64),
+                loss=np.float64(float(loss.detach())), pT=pT.detach().numpy(), vT=vT.detach().numpy(),
+                g_p0=p0.grad.numpy(), g_v0=v0.grad.numpy(), g_params=g_par)
+
+
+def micro_params(name, V, T, dt, sl, seed, params="default", tap="final_sq", spacing=4.0, jitter=2.0, vlo=0.3, vhi=0.7):
+    """Two runs of the same lane: the float32-stored one is the golden (loss, pT, vT, g_p0, g_v0, g_params); the run whose state stays
+    float64 is kept beside it under *_f64state."""
+    a = micro_params_run(V, T, dt, sl, seed, params, tap, spacing, jitter, vlo, vhi, True)
+    b = micro_params_run(V, T, dt, sl, seed, params, tap, spacing, jitter, vlo, vhi, False)
+    assert np.array_equal(a["p0"], b["p0"]) and np.array_equal(a["params"], b["params"])
+    print("G6p %-10s V=%d T=%d loss=%.6f (float64 state %.6f) |g_params| per plane %s" % (
+        name, V, T, float(a["loss"]), float(b["loss"]), np.linalg.norm(a["g_params"], axis=0)))
+    np.savez_compressed(
+        os.path.join(OUT, "micro_params_%s.npz" % name), T=np.int64(T), dt=np.float64(dt), tap=np.array(tap), **a,
+        **{k + "_f64state": b[k] for k in ("loss", "pT", "vT", "g_p0", "g_v0", "g_params")},
+        meta=meta(seed=seed, V=V, T=T, dt=dt, speed_limit=sl, params=params, tap=tap, head=[float(x) for x in a["head"]],
+                  columns="accel_max accel_pref target_speed min_space time_pref length",
+                  note="state through get_state_vector / set_state_vector (float32) after every step; *_f64state: state left float64"))
+
+
+def gen_micro_params(which):
+    if "inv10" in which:
+        micro_params("inv10", 10, 200, 0.01, 30.0, seed=1, params="default", tap="final_sq")
+    if "rand24" in which:
+        micro_params("rand24", 24, 150, 1.0 / 30.0, 20.0, seed=4, params="random", tap="every_sum")
+    if "dense16" in which:
+        micro_params("dense16", 16, 400, 0.01, 30.0, seed=9, params="default", tap="final_sq")
+
+
+# ----------------------------------------------------------------------------------------------
 # G7: 3-lane hybrid network macro(0) -> micro(1) -> macro(2)  (example/inverse/hybrid.py:37-82)
 # ----------------------------------------------------------------------------------------------
 
@@ -914,6 +996,8 @@ def main():
         gen_idm_kat_smallgap()
     if "G6" in only:
         gen_micro_rollouts(set(args.g6.split(",")))
+    if "G6p" in only:
+        gen_micro_params(set(args.g6.split(",")))
     if "G7" in only:
         gen_hybrid()
         # other sizes, horizons, speed limits and initial states of the same three-lane network (round 6)
