@@ -8,9 +8,14 @@ straight connector to the opposite leaving lane and (right-most lane only) a rig
 Neighbouring intersections are joined leaving -> approaching.  Lane geometry is only used for lane LENGTHS; it is
 reproduced with the same floating-point construction so that ceil(length / cell_length) gives the same cell counts.
 """
+import copy
+import itertools
+import warnings
+
 import numpy as np
 import torch as th
 
+from dhts import _lib, episode, ops
 from dmath.operation import sigmoid
 from example.common.rms import RunningMean
 from example.control.itscp._env_config import default_config
@@ -83,14 +88,6 @@ class Box:
         self.dtype = np.dtype(dtype)
 
 
-def _vehicle_attributes(v, sim):
-    """(accel_max, accel_pref, target_speed, min_space, time_pref, length) of a MicroVehicle; None = default_micro_vehicle(speed_limit)."""
-    if v is None:
-        from road.vehicle.micro_vehicle import MicroVehicle
-        v = MicroVehicle.default_micro_vehicle(sim.speed_limit)
-    return [float(v.accel_max), float(v.accel_pref), float(v.target_speed), float(v.min_space), float(v.time_pref), float(v.length)]
-
-
 class ItscpEnv:
 
     def __init__(self, schedule_callback=itscp_random_schedule):
@@ -107,6 +104,14 @@ class ItscpEnv:
         self.render_eval = False
         self.route_provider = None          # optional callable(lane_id) -> MicroRoute replacing create_random_route
         self.time = self.steps = 0
+        # given by the caller instead of drawn: `hybrid` spawn routes [n][<= 32], their vehicles' attributes [n][6], `micro` admission draws
+        self.fused_routes = self.fused_vehicle_params = self.fused_draws = None
+        self.device_path = episode.EpisodeState()       # which device path the episodes take, and its uploaded tables
+
+    fused_counts = property(lambda self: self.device_path.counts)
+    fused_overflowed = property(lambda self: self.device_path.overflowed)
+    last_path = property(lambda self: self.device_path.last_path)
+    _fused_done = property(lambda self: self.device_path.done)      # (the flag's name before dhts/episode.py: tests and tools read it)
 
     def action_size(self):
         length = self.config["policy_length"] * self.config["duration"]
@@ -126,18 +131,17 @@ class ItscpEnv:
         self.reward_queue_c = -1.0
         self.macro_route_schedule = [self.simulator.create_random_macro_route() for _ in range(self.num_timestep)]
         self._make_micro_route()
-        self._fused_cache = None            # tables of the fused kernels depend on the schedules / routes drawn above
-        self._fused_done = False
+        self.device_path.new_episode(reset=True)        # (the uploaded tables depend on the schedules / routes drawn above)
         return self.observe()
 
     def rewind(self):
         """Episode state back to what reset() left, keeping the drawn schedules, routes and the uploaded kernel tables.
         Valid after fused episodes only (they never touch the lane objects); the reference deep-copies the environment
         per episode instead (trainer.py:172)."""
-        if self.steps and not getattr(self, "_fused_done", False):
+        if self.steps and not self.device_path.done:
             raise RuntimeError("rewind() after a lane-by-lane episode: the lane objects moved, call reset()")
         self.time = self.steps = 0
-        self._fused_done = False
+        self.device_path.new_episode()
         self.queue_length.clear()
         self.flux.clear()
         self.is_static_rms = RunningMean(100_000)
@@ -152,28 +156,26 @@ class ItscpEnv:
         twin.queue_length, twin.flux = {}, {}
         twin.config = dict(self.config)
         twin.is_static_rms = RunningMean(100_000)
+        twin.device_path = copy.copy(self.device_path)         # (own fields, the same uploaded tables)
         twin._lanes_shared = True
         return twin
 
     def _own_lanes(self):
         if getattr(self, "_lanes_shared", False):
-            import copy
             memo = {}
             self.simulator = copy.deepcopy(self.simulator, memo)
             self.lane = copy.deepcopy(self.lane, memo)
             self._lanes_shared = False
 
     def __deepcopy__(self, memo):
-        """Episode copy for the lane-by-lane path: everything is copied except the uploaded tables of the fused kernels,
-        which are immutable and shared."""
-        import copy
+        """Episode copy for the lane-by-lane path: everything is copied except the uploaded tables of the device paths
+        (EpisodeState.__deepcopy__)."""
         twin = object.__new__(type(self))
         memo[id(self)] = twin
         # what an episode only reads is shared, not copied: the drawn inflow schedules (lanes x steps numpy scalars -- 86 000 objects
-        # at config 4, 0.4 s per copy) and the per-step macro routes, beside the uploaded tables
-        shared = ("_fused_cache", "_batched_net", "schedule", "macro_route_schedule")
+        # at config 4, 0.4 s per copy) and the per-step macro routes
         for k, v in self.__dict__.items():
-            twin.__dict__[k] = v if k in shared else copy.deepcopy(v, memo)
+            twin.__dict__[k] = v if k in ("schedule", "macro_route_schedule") else copy.deepcopy(v, memo)
         return twin
 
     def _make_micro_route(self):
@@ -276,12 +278,12 @@ class ItscpEnv:
         self.steps += 1
         self.queue_length.clear()
         self.flux.clear()
-        if getattr(self, "_fused_done", False):
+        if self.device_path.done:
             raise NotImplementedError("the fused episode leaves the lane objects at their reset state: call reset() first, "
                                       "or set config['fused'] = False to step lane by lane")
         reward = self._step_fused(action, differentiable)
         if reward is None:
-            self.last_path = "lane-by-lane"
+            self.device_path.last_path = "lane-by-lane"
             self._own_lanes()                       # (an episode_copy() twin: the lane-by-lane path moves the lane objects)
             self._simulate(action, differentiable)
             reward = self._reward(action)
@@ -289,267 +291,78 @@ class ItscpEnv:
         info = {"img": []}
         return obs, reward, self.steps >= self.config["duration"], info
 
-    # ---- fused episode: the whole differentiable rollout in two kernel launches (dhts_net_*_rollout_fwd / _bwd) -----------
+    # ---- device episode: the whole differentiable rollout in two kernel launches (dhts_net_*_rollout_fwd / _bwd) ---------
     def _step_fused(self, action, differentiable=True):
-        """First step after reset() in `macro` / `hybrid` mode with config["fused"] (default on): reward (differentiable
-        w.r.t. `action`) and the per-step queue terms from the fused network kernels instead of one operator call per
+        """First step after reset() in `macro` / `hybrid` / `micro` mode with config["fused"] (default on): reward (differentiable
+        w.r.t. `action`) and the per-step queue terms from the device paths (dhts/episode.py) instead of one operator call per
         lane and step.  differentiable=False (an evaluation episode, Trainer.evaluate): the same episode with the reference's
         hard thresholds (dhts_net_*_rollout_eval), one launch, nothing kept for a reverse sweep.  Same numbers as the operator path in `macro` mode; in `hybrid` mode vehicle routes are pre-drawn
         per spawn lane (`fused_routes`, or 8 per lane from create_random_route) instead of being drawn at spawn time.
         Returns None when the network or the call is outside what the kernels cover (the operator path runs then)."""
-        if not self.config.get("fused", True) or self.config["mode"] not in ("macro", "hybrid", "micro") or self.steps != 1 or self.time != 0:
+        if (not self.config.get("fused", True) or self.config["mode"] not in ("macro", "hybrid", "micro") or self.steps != 1 or self.time != 0
+                or not (isinstance(action, th.Tensor) and action.is_cuda)
+                or any(sl.is_micro() and sl.num_vehicle() for sl in self.simulator.lane.values())):
             return None
-        if not (isinstance(action, th.Tensor) and action.is_cuda):
-            return None
-        from dhts import _lib, ops
-        sim = self.simulator
-        if any(sl.is_micro() and sl.num_vehicle() for sl in sim.lane.values()):
-            return None
-        cache = getattr(self, "_fused_cache", None)
-        lane_cap = getattr(self, "_fused_lane_capacity", 0)     # vehicles a micro lane holds (0 = the kernels' default 16)
-        if cache is None:
-            cache = self._fused_cache = self._build_fused_cache(action.device, lane_cap)
-        kind, tab = cache
-        if kind == "none":
-            return None
-        args = (self.num_intersection ** 2, self.config["signal_length"] * self.config["simulation_frequency"],
-                1.0 / self.config["simulation_frequency"], self.simulator.speed_limit, self.config["static_speed"],
-                self.simulator.vehicle_length)
-        a = action.reshape(1, -1)
-        draws = None
-        if self.config["mode"] == "micro" and kind in ("micro", "stepwise"):
-            draws = getattr(self, "fused_draws", None)
-            pending = self.__dict__.pop("_fused_pending_draws", None)
-            if pending is not None:
-                draws = pending
-            elif draws is None:
-                draws = np.random.random(self._fused_n_draws)
-            else:
-                draws = np.concatenate([np.asarray(draws, dtype=np.float64), np.full(self._fused_n_draws, 2.0)])[:self._fused_n_draws]
-            tab.set_draws(draws)
-        try:
-            if kind == "batched":
-                if self.config.get("batched_graph", True) and not getattr(self, "_batched_graph_failed", False):
-                    try:                                    # the whole episode as one HIP graph (captured at the first call)
-                        reward, queue = tab.graphed_rollout(a[0], *args, differentiable=differentiable)
-                    except RuntimeError as e:
-                        if isinstance(e, ops.CapacityError) or "capture" not in str(e).lower():
-                            raise
-                        import warnings
-                        warnings.warn("ItscpEnv: HIP-graph capture of the batched episode failed (%s); running it eagerly" % e)
-                        self._batched_graph_failed = True
-                        reward, queue = tab.rollout(a[0], *args, differentiable=differentiable)
-                else:
-                    reward, queue = tab.rollout(a[0], *args, differentiable=differentiable)
-                reward, queue = reward.reshape(1), queue.unsqueeze(0)
-            elif kind == "stepwise":
-                # a network beyond one workgroup (or an episode beyond the fused kernels' vehicle capacities): step by step on the
-                # device, all lanes at once (dhts/stepwise.py)
-                cut, _, queue, counts = tab.rollout(a[0], *args, differentiable=differentiable)
-                reward, queue = cut.reshape(1), queue.unsqueeze(0)
-                self.fused_counts = counts.tolist()
-            elif kind == "macro":
-                reward, queue = ops.net_macro_rollout(a, tab, *args) if differentiable else ops.net_macro_eval(a, tab, *args)
-            elif differentiable:
-                reward, _, queue, counts = ops.net_hybrid_rollout(a, tab, *args)
-                self.fused_counts = counts[0].tolist()
-            else:
-                reward, queue, counts = ops.net_hybrid_eval(a, tab, *args)
-                self.fused_counts = counts[0].tolist()
-        except _lib.DhtsError as e:
-            # Two library errors have another way to run, both DHTS_E_INVALID sizing refusals: the persistent form of a network whose
-            # scratch does not fit a workgroup's LDS (-> the stepwise form), and a fused hybrid launch whose LDS plan does not fit at
-            # the lane capacity the ladder asked for (-> the next rung, below).  Anything else -- a failed launch, a bad argument, any
-            # error of the macro paths -- is a bug or a broken device and goes to the caller.
-            if e.status != _lib.E_INVALID or kind not in ("hybrid", "micro", "stepwise"):
-                raise
-            if kind == "stepwise":
-                if not getattr(tab, "persistent", False):
+        st = self.device_path
+        draws = None            # the admission draws of THIS episode (`micro` mode): every rung of the ladder sees the same ones
+        while True:
+            runner = st.runner or self._build_runner(action.device)
+            if runner.plan.path == "none":
+                return None
+            if (n := runner.n_draws) and draws is None:
+                draws = np.random.random(n) if self.fused_draws is None else np.concatenate([np.asarray(self.fused_draws, dtype=np.float64), np.full(n, 2.0)])[:n]
+            if draws is not None:
+                runner.set_draws(draws[None])
+            try:
+                reward, queue, counts = runner.rollout(action.reshape(1, -1), differentiable)
+                break
+            except (_lib.DhtsError, ops.CapacityError) as e:
+                # more than this launch was sized for, or a sizing that does not fit a workgroup's LDS; the attempt touched nothing on the host
+                rung = episode.next_rung(runner.plan, e, runner.event_bound, int(self.config.get("fused_max_lane_capacity", 1024)))
+                if rung is None:
                     raise
-                self._stepwise_no_persistent = True
-                self._stepwise_cache = None
-                self._fused_cache = None
-                if draws is not None:
-                    self._fused_pending_draws = draws
-                return self._step_fused(action, differentiable)
-            return self._climb_capacity_ladder(action, differentiable, kind, lane_cap, draws, e)
-        except ops.CapacityError as e:
-            if kind == "stepwise" and e.index == -2:
-                # the hand-off event list (dhts_netstep_tables::max_events), not a lane: more lanes' worth of vehicles would not help.
-                # The hard bound: every micro lane's head leaves (with up to three deposit cells) and every capacitor spawns, every step
-                bound = self.num_timestep * (4 * tab.n_micro + 2 * tab.n_caps) + 64
-                have = tab.max_events if tab.max_events > 0 else 0
-                if have < bound:
-                    self._stepwise_max_events = bound
-                    self._stepwise_cache = None
-                    self._fused_cache = None
-                    if draws is not None:
-                        self._fused_pending_draws = draws
-                    return self._step_fused(action, differentiable)
-            return self._climb_capacity_ladder(action, differentiable, kind, lane_cap, draws, e)
-        self.last_path = {"macro": "fused", "hybrid": "fused", "micro": "fused"}.get(kind, kind)
+                if rung == episode.LANE_BY_LANE:
+                    return self._fall_back_lane_by_lane(draws, e)
+                st.rung, st.runner = rung, None
+        st.counts = st.counts if counts is None else counts[0].tolist()
+        st.last_path = "fused" if runner.plan.path in ("macro", "hybrid", "micro") else runner.plan.path
         q = np.ascontiguousarray(queue[0].detach().cpu().numpy().T)      # [L][T]
         for i, lid in enumerate(self.lane.keys()):
             self.queue_length[lid] = q[i].tolist()              # (Python floats like the lane-by-lane path's, converted in C)
             self.flux.setdefault(lid, [])
         self.time = self.num_timestep
-        self._fused_done = True
+        st.done = True
         return (-self.reward_queue_c) * reward[0]
 
-    def _climb_capacity_ladder(self, action, differentiable, kind, lane_cap, draws, e):
-        """The same episode on the next rung (more vehicle slots per micro lane, then the stepwise path), or lane by lane (None)."""
-        # The episode needs more than this launch was sized for (vehicles per micro lane, vehicles per episode, records), or the
-        # sizing does not fit one workgroup's LDS (DhtsError).  Nothing on the host was touched by the attempt; the ladder is
-        #   fused kernels at 16 vehicles per lane -> fused at 128 -> stepwise device path at 32 -> 128 -> 1024 -> lane by lane
-        #   (a network that starts on the stepwise path starts at the capacity its geometry asks for, dhts.stepwise.default_lane_capacity),
-        # every rung the SAME episode: same drawn routes (kept in _fused_routes_drawn), same admission draws.
-        ladder = [("fused", 16), ("fused", 128), ("stepwise", 32), ("stepwise", 128), ("stepwise", 1024)]
-        here = ("stepwise" if kind == "stepwise" else "fused",
-                lane_cap if lane_cap else (16 if kind != "stepwise" else getattr(self, "_stepwise_lane_capacity", 32)))
-        nxt = None
-        if kind in ("micro", "hybrid", "stepwise"):
-            for rung in ladder:
-                if (rung[0] == "stepwise", rung[1]) > (here[0] == "stepwise", here[1]) and rung[1] <= int(self.config.get("fused_max_lane_capacity", 1024)):
-                    nxt = rung
-                    break
-        if nxt is not None:
-            self._fused_lane_capacity = nxt[1]
-            self._fused_prefer_stepwise = nxt[0] == "stepwise"
-            self._fused_cache = None
-            if draws is not None:
-                self._fused_pending_draws = draws          # the retry is the same episode: the same admission draws
-            return self._step_fused(action, differentiable)
-        # The reference has no such limits (_micro_lane.py:53-113): this episode runs lane by lane instead (minutes, not
-        # milliseconds).  In `micro` mode the admission draws the kernels were given are replayed, so that the episode is the one
-        # that was asked for.
-        if not getattr(self, "_fused_overflow_warned", False):
-            self._fused_overflow_warned = True
-            import warnings
+    def _build_runner(self, device):
+        """Plan the episode from where the ladder stands and upload its tables; any ValueError on the way = lane by lane."""
+        st = self.device_path
+        try:
+            routes = self.fused_routes if self.fused_routes is not None else st.routes_drawn
+            inputs = episode.episode_inputs(self, routes, self.fused_vehicle_params)
+            if routes is None and self.config["mode"] == "hybrid":
+                st.routes_drawn = inputs.routes                         # (a capacity retry is the same episode: the same routes)
+            config = dict(self.config, stepwise_lane_capacity=0)        # (a key of ReplicaBatch: the environment ignores it)
+            plan = episode.plan_episode(inputs.tables, self.config["mode"], config, self.simulator.vehicle_length, st.rung)
+            st.runner = episode.Runner(plan, inputs, device, st.kept, self.config.get("batched_graph", True))
+        except ValueError:
+            st.runner = episode.Runner(episode.LANE_BY_LANE)
+        if st.runner.key is not None:
+            st.kept = st.runner                                         # (a stepwise / batched network survives reset())
+        return st.runner
+
+    def _fall_back_lane_by_lane(self, draws, e):
+        # The reference has no capacity limits (_micro_lane.py:53-113): past the last rung the episode runs lane by lane (minutes, not
+        # milliseconds).  In `micro` mode the admission draws the kernels were given are replayed: the episode that was asked for.
+        st = self.device_path
+        if not st.overflow_warned:
             warnings.warn("ItscpEnv: the device paths' capacity was exceeded (%s); this episode runs lane by lane" % e)
         self._own_lanes()                       # (an episode_copy() twin: from here on the lane objects are written to)
-        if draws is not None:
-            it = iter(np.asarray(draws, dtype=np.float64).tolist())
-
-            def replay():
-                v = next(it, None)
-                return float(np.random.random()) if v is None else v
-            self.simulator.random_draw = replay
-        self.fused_overflowed = True
+        if draws is not None:       # (and np.random once they run out)
+            self.simulator.random_draw = itertools.chain(np.asarray(draws, dtype=np.float64).tolist(),
+                                                         iter(lambda: float(np.random.random()), None)).__next__
+        st.overflowed = st.overflow_warned = True
         return None
-
-    def _build_fused_cache(self, device, lane_cap):
-        """(kind, device tables) of this episode: "macro" / "hybrid" / "micro" = the fused kernels (one workgroup per network),
-        "batched" / "stepwise" = the step-by-step device paths for networks beyond that (dhts/batched.py, dhts/stepwise.py),
-        ("none", None) = lane by lane."""
-        from dhts import ops
-        from dhts.network import HybridNetworkTables, MacroNetworkTables
-        sim = self.simulator
-        mode = self.config["mode"]
-        T = self.num_timestep
-        try:
-            n_cells = sum(getattr(sl, "num_cell", 0) for sl in sim.lane.values() if sl.is_macro())
-            if mode == "macro" and n_cells + len(sim.lane) <= 1024:
-                return ("macro", ops.DeviceNetTables(MacroNetworkTables.from_env(self), device))
-            if mode == "macro":
-                # more cells + lanes than one workgroup holds one item per thread of (e.g. --n_intersection=3 --n_lane=3: 360 lanes,
-                # ~1 700 cells): step by step on the device (dhts/stepwise.py, persistent form: 6.9 ms per 120-step differentiable
-                # episode of that network against 11.4 ms for the replayed HIP graph of round 4's batched-lane path, dhts/batched.py,
-                # which config "macro_path" = "batched" still selects)
-                tabs = MacroNetworkTables.from_env(self)
-                if self.config.get("macro_path", "stepwise") == "stepwise":
-                    return ("stepwise", self._stepwise_net(tabs, np.asarray([[-1, -1]], dtype=np.int32), device, 32))
-                from dhts.batched import BatchedMacroNetwork
-                net = getattr(self, "_batched_net", None)           # survives reset(): same topology, new schedules / routes
-                try:
-                    if net is None:
-                        raise ValueError
-                    net.update(tabs)                                # in place: an episode captured as a HIP graph stays valid
-                except ValueError:
-                    net = self._batched_net = BatchedMacroNetwork(tabs, device)
-                return ("batched", net)
-            tab, routes, veh_params = self._fused_episode_inputs()
-            fits = True
-            try:
-                tab.check_kernel_limits()
-            except ValueError:
-                fits = False
-            if fits and not getattr(self, "_fused_prefer_stepwise", False) and lane_cap in (0, 16, 32, 64, 128):
-                return (mode, ops.DeviceHybridTables(tab, routes, device, lane_capacity=lane_cap, vehicle_params=veh_params))
-            # beyond one workgroup (cells + lanes > 960, > 64 IDM lanes, > 16 spawning lanes) or beyond the fused kernels' vehicle
-            # capacities: step by step on the device (dhts/stepwise.py)
-            if not lane_cap:
-                from dhts.stepwise import default_lane_capacity
-                lane_cap = self._stepwise_lane_capacity = default_lane_capacity(tab, self.simulator.vehicle_length)
-            return ("stepwise", self._stepwise_net(tab, routes, device, lane_cap, veh_params))
-        except ValueError:
-            return ("none", None)
-
-    def _fused_episode_inputs(self):
-        """(tables, route rows, per-row vehicle attributes or None) of a `hybrid` / `micro` mode episode as the network kernels take
-        them -- host arrays; tools/probes/fuzz_env.py hands the same three to the CPU checker."""
-        from dhts.network import HybridNetworkTables
-        sim = self.simulator
-        mode = self.config["mode"]
-        T = self.num_timestep
-        tab = HybridNetworkTables.from_env(self)
-        veh_params = getattr(self, "fused_vehicle_params", None)     # [routes][6] beside `fused_routes` (hybrid mode), or None
-        if mode == "micro":
-            # every lane an IDM lane; source lanes admit their waiting vehicles against np.random draws
-            # (_simulator.py:153-174): the waiting routes in admission order (the list is popped from its end) are
-            # the route rows, the draws of the episode are drawn up front (fused_draws replays a recorded stream)
-            rows, vrows = [], []
-            for l in range(tab.n_lanes):
-                waiting = sim.lane_waiting_micro_vehicle.get(l, [])
-                for k, r in enumerate(reversed(sim.lane_waiting_micro_route.get(l, []))):
-                    r = list(r.route)[:32]
-                    rows.append(r + [-1] * (32 - len(r)))
-                    v = waiting[len(waiting) - 1 - k] if k < len(waiting) else None
-                    vrows.append(_vehicle_attributes(v, sim))
-            routes = np.asarray(rows if rows else [[-1, -1]], dtype=np.int32)
-            # the waiting vehicles' own IDM attributes ride beside their routes (dhts_hybrid_tables::veh_params) unless every one of
-            # them is the default vehicle the reference's reset() builds (_env.py:205-219)
-            if any(v != _vehicle_attributes(None, sim) for v in vrows):
-                veh_params = np.asarray(vrows, dtype=np.float64)
-            self._fused_n_draws = T * max(1, int(tab.lane_source.sum()))
-            tab.set_micro_sources(np.full(self._fused_n_draws, 2.0))
-        else:
-            routes = getattr(self, "fused_routes", None)
-            if routes is None:
-                routes = getattr(self, "_fused_routes_drawn", None)      # (a capacity retry is the same episode: the same routes)
-            if routes is None:
-                routes = []
-                for l in range(tab.n_lanes):
-                    if tab.lane_macro[l] == 0 and any(tab.lane_macro[a] for a in tab.prev_lanes[l]):
-                        for _ in range(8):
-                            r = list(sim.create_random_route(l).route)[:32]
-                            routes.append(r + [-1] * (32 - len(r)))
-                if not routes:
-                    routes = [[-1, -1]]
-                self._fused_routes_drawn = routes
-            routes = np.asarray(routes, dtype=np.int32)
-        return tab, routes, veh_params
-
-    def _stepwise_net(self, tab, routes, device, lane_cap, veh_params=None):
-        from dhts.stepwise import StepwiseNetwork
-        net = getattr(self, "_stepwise_cache", None)            # survives reset(): same topology -> new per-episode tables only
-        max_events = int(getattr(self, "_stepwise_max_events", 0))
-        vkey = None if veh_params is None else np.asarray(veh_params, dtype=np.float64).tobytes()
-        if net is not None and net[1] == (lane_cap, routes.shape, routes.tobytes(), vkey) and net[0].max_events == max_events:
-            try:
-                net[0].update(tab)
-                if tab.lane_source.any():
-                    net[0].t.draws = tab.draws
-                return net[0]
-            except ValueError:
-                pass
-        # persistent form (one kernel per direction) where it pays (up to 1 024 lanes / 4 096 cells: dhts.stepwise.persistent_form_pays)
-        # unless config["stepwise_persistent"] says otherwise; a network whose scratch does not fit one workgroup's LDS comes back as
-        # DhtsError at the first launch and is rebuilt in the stepwise form (a handful of launches per step)
-        from dhts.stepwise import persistent_form_pays
-        persistent = bool(self.config.get("stepwise_persistent", persistent_form_pays(tab))) and not getattr(self, "_stepwise_no_persistent", False)
-        sw = StepwiseNetwork(tab, routes, device, lane_capacity=lane_cap, persistent=persistent, max_events=max_events, vehicle_params=veh_params)
-        self._stepwise_cache = (sw, (lane_cap, routes.shape, routes.tobytes(), vkey))
-        return sw
 
     def _simulate(self, action, differentiable):
         self.time = 0

@@ -53,20 +53,14 @@ def main():
     env.reset()
     if args.n_replica > 1:
         return batch(args, env, dev)
-    cache = None
     rng = np.random.default_rng(args.seed)
     action = th.tensor(rng.uniform(0.3, 0.7, env.action_size()).astype(np.float32), device=dev, requires_grad=True)
     opt = th.optim.Adam([action], lr=args.lr)
     t0 = time.time()
     for ep in range(args.n_episode):
-        # a fresh episode of the same problem: keep the drawn schedules / routes (and the uploaded tables), rewind the env
-        env.steps = 0
-        env.time = 0
-        env._fused_done = False
-        env._fused_cache = cache if cache is not None else env._fused_cache
+        env.rewind()        # a fresh episode of the same problem: the drawn schedules / routes and the uploaded tables are kept
         opt.zero_grad()
         _, reward, _, _ = env.step(action, True)
-        cache = env._fused_cache
         (-reward).backward()
         opt.step()
         with th.no_grad():
@@ -77,18 +71,13 @@ def main():
 
 def batch(args, env, dev):
     """Many restarts in one launch: the network tables are shared, every replica owns an action vector."""
-    from dhts import ops
+    from dhts import episode, ops
     from dhts.network import HybridNetworkTables
-    tab = HybridNetworkTables.from_env(env)
-    routes = []
-    for l in range(tab.n_lanes):
-        if tab.lane_macro[l] == 0 and any(tab.lane_macro[a] for a in tab.prev_lanes[l]):
-            for _ in range(8):
-                r = list(env.simulator.create_random_route(l).route)[:32]
-                routes.append(r + [-1] * (32 - len(r)))
-    dev_tab = ops.DeviceHybridTables(tab, np.asarray(routes if routes else [[-1, -1]], dtype=np.int32), dev)
-    sim_args = (env.num_intersection ** 2, env.config["signal_length"] * env.config["simulation_frequency"],
-                1.0 / env.config["simulation_frequency"], args.speed_limit)
+    inputs = episode.episode_inputs(env)
+    # (`macro` mode runs through the same kernels here: the network as hybrid tables whose lanes are all ARZ lanes)
+    tab = inputs.tables if args.mode == "hybrid" else HybridNetworkTables.from_env(env)
+    dev_tab = ops.DeviceHybridTables(tab, inputs.routes, dev)
+    sim_args = inputs.args[:4]          # (static speed and vehicle length: the operators' defaults)
     gen = th.Generator(device="cpu").manual_seed(args.seed)
     action = (0.1 + 0.8 * th.rand(args.n_replica, env.action_size(), generator=gen)).to(dev).requires_grad_(True)
     opt = th.optim.Adam([action], lr=args.lr, capturable=args.graph)

@@ -79,7 +79,7 @@ def test_env_step_runs_a_network_beyond_one_workgroup_batched(cuda, oracle):
     reward.backward()
     torch.cuda.synchronize()
     t_diff = time.time() - t0
-    assert env._fused_cache[0] == "batched" and env._fused_done
+    assert env.device_path.runner.plan.path == "batched" and env.device_path.done
     sq, F = env.num_intersection ** 2, env.config["signal_length"] * env.config["simulation_frequency"]
     o = oracle.net_macro(tab, act, sq, F, 1.0 / env.config["simulation_frequency"], env.simulator.speed_limit,
                          env.config["static_speed"], env.simulator.vehicle_length)
@@ -102,10 +102,10 @@ def test_env_step_runs_a_network_beyond_one_workgroup_batched(cuda, oracle):
           % (tab.n_cells, tab.T, t_diff, t_eval))
     # a second pair of episodes after reset(): new schedules and routes go into the device tables in place, the captured graphs
     # are replayed; the numbers are again the oracle's for the new tables
-    net = env._batched_net
+    net = env.device_path.kept.tab
     env.config["random_seed"] = 6              # (another inflow schedule and other per-step routes)
     env.reset()
-    assert env._batched_net is net
+    assert env.device_path.kept.tab is net
     tab2 = MacroNetworkTables.from_env(env)
     action2 = torch.tensor(act, device=cuda, requires_grad=True)
     torch.cuda.synchronize()
@@ -114,7 +114,7 @@ def test_env_step_runs_a_network_beyond_one_workgroup_batched(cuda, oracle):
     reward2.backward()
     torch.cuda.synchronize()
     t_replay = time.time() - t0
-    assert env._fused_cache[1] is net and not getattr(env, "_batched_graph_failed", False) and len(net._graphs) == 2
+    assert env.device_path.runner.tab is net and not env.device_path.runner.graph_failed and len(net._graphs) == 2
     o2 = oracle.net_macro(tab2, act, sq, F, 1.0 / env.config["simulation_frequency"], env.simulator.speed_limit,
                           env.config["static_speed"], env.simulator.vehicle_length)
     assert abs(float(reward2.detach()) - o2["reward"]) <= 1e-5 * abs(o2["reward"])

@@ -290,8 +290,8 @@ def test_env_step_falls_back_when_a_fused_capacity_is_exceeded(cuda):
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         obs, reward, done, info = env.step(action, True)
-    assert getattr(env, "_fused_cache", ("none",))[0] == "micro"                        # the fused path was set up and tried
-    assert getattr(env, "fused_overflowed", False) and not getattr(env, "_fused_done", False)
+    assert env.device_path.runner.plan.path == "micro"                                 # the fused path was set up and tried
+    assert env.fused_overflowed and not env.device_path.done
     assert any("capacity" in str(x.message) for x in w)
     keys = list(env.lane.keys())
     assert all(len(env.queue_length[k]) == T for k in keys)                             # the whole episode ran, lane by lane
@@ -306,7 +306,7 @@ def test_env_step_falls_back_when_a_fused_capacity_is_exceeded(cuda):
     with warnings.catch_warnings(record=True) as w2:
         warnings.simplefilter("always")
         _, reward2, _, _ = env2.step(action2, True)
-    assert env2._fused_done and env2._fused_lane_capacity == 128 and not getattr(env2, "fused_overflowed", False)
+    assert env2.device_path.done and env2.device_path.rung.lane_capacity == 128 and not env2.fused_overflowed
     assert not any("capacity" in str(x.message) for x in w2)
     reward2.backward()
     q1 = np.array([[float(x) for x in env.queue_length[k]] for k in keys])
@@ -363,7 +363,7 @@ def test_env_steps_waiting_vehicles_with_their_own_attributes(cuda, golden_dir, 
             v.accel_max, v.accel_pref, v.target_speed, v.min_space, v.time_pref, v.length = p
     env.fused_draws = g["rand_draws"]
     if path == "stepwise":
-        env._fused_prefer_stepwise, env._fused_lane_capacity = True, 32
+        env.device_path.pin("stepwise", lane_capacity=32)
     action = torch.tensor(g["action"], device=cuda, requires_grad=True)
     _, reward, _, _ = env.step(action, True)
     reward.backward()

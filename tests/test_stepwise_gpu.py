@@ -212,7 +212,7 @@ def test_env_step_takes_the_stepwise_path_beyond_the_fused_limits(cuda, golden_d
     reward.backward()
     grad = action.grad.cpu().numpy()
     t1 = time.perf_counter()
-    assert env._fused_cache[0] == "stepwise" and env._fused_done and env.last_path == "stepwise" and env._fused_cache[1].persistent
+    assert env.device_path.runner.plan.path == "stepwise" and env.device_path.done and env.last_path == "stepwise" and env.device_path.runner.tab.persistent
     queue = np.array([env.queue_length[k] for k in keys])
     tol_q = TOL_STATE
     assert state_report("env.step %s: queues vs reference" % name, queue, g["queue"]) <= tol_q
@@ -360,17 +360,16 @@ def test_env_capacity_ladder_starts_at_the_geometric_capacity(cuda, golden_dir):
     action = torch.tensor(g["action"], device=cuda, requires_grad=True)
     obs, reward, done, info = env.step(action, True)
     t, _ = itscp_hybrid_tables(g)
-    assert env.last_path == "stepwise" and env._fused_cache[1].lane_capacity == default_lane_capacity(t, m["vehicle_length"]) == 8
+    assert env.last_path == "stepwise" and env.device_path.runner.tab.lane_capacity == default_lane_capacity(t, m["vehicle_length"]) == 8
     r0 = float(reward.detach())
     assert abs(r0 - float(g["reward"])) <= 1e-5 * abs(float(g["reward"]))
     env2 = build_env(g, m, replay_routes=True)
     env2.fused_routes = g["spawn_routes"]
-    env2._fused_lane_capacity = 1
-    env2._fused_prefer_stepwise = True
+    env2.device_path.pin("stepwise", lane_capacity=1)
     a2 = torch.tensor(g["action"], device=cuda, requires_grad=True)
     _, reward2, _, _ = env2.step(a2, True)
     reward2.backward()
-    assert env2.last_path == "stepwise" and env2._fused_cache[1].lane_capacity == 32
+    assert env2.last_path == "stepwise" and env2.device_path.runner.tab.lane_capacity == 32
     assert float(reward2.detach()) == r0
     assert np.abs(a2.grad.cpu().numpy() - g["g_action"]).max() <= TOL_GRAD * np.abs(g["g_action"]).max()
 
@@ -491,7 +490,7 @@ def test_network_wider_than_the_workgroup(cuda, oracle):
     a_env = torch.tensor(act, device=cuda, requires_grad=True)
     _, r_env, _, _ = env.step(a_env, True)
     r_env.backward()
-    assert env.last_path == "stepwise" and not env._fused_cache[1].persistent
+    assert env.last_path == "stepwise" and not env.device_path.runner.tab.persistent
     assert np.isfinite(float(r_env.detach())) and np.isfinite(a_env.grad.cpu().numpy()).all() and float(a_env.grad.abs().max()) > 0
 
 
@@ -509,17 +508,17 @@ def test_env_ladder_survives_a_fused_launch_that_does_not_fit(cuda, golden_dir, 
     def episode():
         env = build_env(g, m, replay_routes=True)
         env.fused_routes = g["spawn_routes"]
-        env._fused_lane_capacity = 128
+        env.device_path.pin("fused", lane_capacity=128)
         action = torch.tensor(g["action"], device=cuda, requires_grad=True)
         _, reward, _, _ = env.step(action, True)
         reward.backward()
-        assert env._fused_done
+        assert env.device_path.done
         assert abs(float(reward.detach()) - float(g["reward"])) <= 1e-5 * abs(float(g["reward"]))
         assert np.abs(action.grad.cpu().numpy() - g["g_action"]).max() <= TOL_GRAD * np.abs(g["g_action"]).max()
         assert env.fused_counts[0] == m["n_vehicle_spawned"]
         return env
     env = episode()
-    assert env.last_path == "fused" and env._fused_cache[1].lane_capacity == 128
+    assert env.last_path == "fused" and env.device_path.runner.tab.lane_capacity == 128
     real = ops.net_hybrid_rollout
 
     def refuse(a, tab, *args, **kw):
@@ -530,7 +529,7 @@ def test_env_ladder_survives_a_fused_launch_that_does_not_fit(cuda, golden_dir, 
         return real(a, tab, *args, **kw)
     monkeypatch.setattr(ops, "net_hybrid_rollout", refuse)
     env = episode()
-    assert env.last_path == "stepwise" and env._fused_cache[1].lane_capacity == 32
+    assert env.last_path == "stepwise" and env.device_path.runner.tab.lane_capacity == 32
 
 
 def test_env_does_not_swallow_library_errors(cuda, golden_dir, monkeypatch):
@@ -574,12 +573,13 @@ def test_event_list_overflow_is_told_apart_from_a_full_lane(cuda, golden_dir):
     # the environment: forced onto the stepwise path with a list of four events -> one retry with the hard bound, same numbers
     env = build_env(g, m, replay_routes=True)
     env.fused_routes = g["spawn_routes"]
-    env._fused_prefer_stepwise, env._fused_lane_capacity, env._stepwise_max_events = True, 32, 4
+    env.device_path.pin("stepwise", lane_capacity=32, max_events=4)
     action = torch.tensor(g["action"], device=cuda, requires_grad=True)
     _, reward, _, _ = env.step(action, True)
     reward.backward()
-    assert env.last_path == "stepwise" and env._fused_cache[1].lane_capacity == 32          # the lane capacity did not climb
-    assert env._fused_cache[1].max_events == m["T"] * (4 * env._fused_cache[1].n_micro + 2 * env._fused_cache[1].n_caps) + 64
+    assert env.last_path == "stepwise" and env.device_path.runner.tab.lane_capacity == 32          # the lane capacity did not climb
+    net = env.device_path.runner.tab
+    assert net.max_events == m["T"] * (4 * net.n_micro + 2 * net.n_caps) + 64
     assert abs(float(reward.detach()) - float(g["reward"])) <= 1e-5 * abs(float(g["reward"]))
     assert np.abs(action.grad.cpu().numpy() - g["g_action"]).max() <= TOL_GRAD * np.abs(g["g_action"]).max()
 

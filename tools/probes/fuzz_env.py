@@ -13,7 +13,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "diff-hybrid-traffic-sim_amd"), os.path.join(ROOT, "tests")]
-from dhts import _lib      # noqa: E402
+from dhts import _lib, episode      # noqa: E402
 from dhts.network import MacroNetworkTables, group_routes      # noqa: E402
 from example.control.itscp import problem as problems      # noqa: E402
 from example.control.itscp._env import ItscpEnv      # noqa: E402
@@ -47,8 +47,7 @@ for trial in range(n_env):
     env.config.update(cfg)
     env.reset()
     act = rng.uniform(0.1, 0.9, env.action_size()).astype(np.float32)
-    args = (env.num_intersection ** 2, env.config["signal_length"] * env.config["simulation_frequency"],
-            1.0 / env.config["simulation_frequency"], env.simulator.speed_limit, env.config["static_speed"], env.simulator.vehicle_length)
+    args = episode.sim_args(env)
     # the checker's run, on the environment's own host tables
     # a quarter of the hybrid / micro environments: every vehicle with attributes of its own (micro_vehicle.py:75-121's ranges; hybrid: drawn
     # for 0.7 x the speed limit, so that a deposited vehicle stays inside the ARZ cells' CFL bound) -- dhts_hybrid_tables::veh_params
@@ -64,11 +63,11 @@ for trial in range(n_env):
     if mode == "macro":
         tab = MacroNetworkTables.from_env(env)
     else:
-        tab, routes, vp = env._fused_episode_inputs()
+        tab, routes, vp, n_draws, _ = episode.episode_inputs(env)
         if own and mode == "hybrid":
             vp = env.fused_vehicle_params = np.array([attributes(0.7 * env.simulator.speed_limit) for _ in range(len(routes))])
         if mode == "micro":
-            draws = rng.random(env._fused_n_draws)
+            draws = rng.random(n_draws)
             env.fused_draws = draws
             tab.set_micro_sources(draws)
         else:
@@ -105,7 +104,7 @@ for trial in range(n_env):
     # the product's run
     a = torch.tensor(act, device=cuda, requires_grad=not hard)
     obs, reward, done, info = env.step(a, not hard)
-    path = getattr(env, "last_path", "lane by lane") if getattr(env, "_fused_done", False) else "lane by lane"
+    path = env.last_path if env.device_path.done else "lane by lane"
     paths[path] = paths.get(path, 0) + 1
     if not hard:
         reward.backward()
@@ -137,7 +136,7 @@ for trial in range(n_env):
                 ok = False
     if not ok:
         bad += 1
-        note += "  <-- MISMATCH (counts %s / %s)" % (getattr(env, "fused_counts", None), ref.get("n_spawned"))
+        note += "  <-- MISMATCH (counts %s / %s)" % (env.fused_counts, ref.get("n_spawned"))
     elif eg > 1e-4:
         # conditioning: how far does the CHECKER's own gradient move when one action changes by one float32 ulp?  (an episode on a knife edge
         # of the float32 arithmetic amplifies rounding differences between any two implementations; only a distance beyond that is a finding)
