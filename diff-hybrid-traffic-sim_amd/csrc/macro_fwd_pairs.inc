@@ -165,7 +165,15 @@ __device__ __forceinline__ void pair_phase1(float ra, float ya, float rb, float 
 // grid = L / kG workgroups of kG traffic lanes; block = 64 kG W threads (W = N / 128 wavefronts per lane); dynamic LDS = kG regions.
 // kFairShift: steps per turn (2^kFairShift) of the priority rotation between the two halves of the grid (above).
 constexpr int kFairShift = 3;
-template <int kG, bool kTape>
+// kSched: `ghost` is a boundary schedule [T][L][2][4] (dhts_macro_rollout_fwd_sched).  Only phase 2 reads the boundary records, so the
+// threads m < 2 that wrote them rewrite them in phase 1 of every step n >= 1 -- between the barrier behind phase 2 of step n - 1 and the
+// one in front of phase 2 of step n: no further barrier -- from a row that has been in registers since step n - 1, and then load row n + 1:
+// the load has a whole step to arrive and never stands between a wavefront and its barrier.  The row waits as ONE register: thread t < 8
+// of the lane's LAST wavefront holds element t and the row's address is a scalar (a float4 and a pointer per thread spilled the kernel);
+// v_readlane hands the eight values to the two writers.  The last wavefront, because vector memory operations retire in order: the wait
+// for the row also waits for all but a few of the wavefront's tape stores issued behind the load, and the last wavefront's youngest ones
+// are its phase-1 entries, a whole phase 2 old -- the first wavefront has just stored the step's exceptions.
+template <int kG, bool kTape, bool kSched = false>
 __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
     int L, int N, int T, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
@@ -253,9 +261,32 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
     long long st_last_ = __builtin_amdgcn_s_memtime(), st_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const long long clk0_ = __builtin_amdgcn_s_memtime(), rt0_ = __builtin_amdgcn_s_memrealtime();
 #endif
+    float sched_v = 0.f;
+    const float *sched_row = nullptr;                // (wave-uniform) the lane's row of the next step
+    const bool sched_wave = kSched && __builtin_amdgcn_readfirstlane(wl) == Wl - 1;
+    if constexpr (kSched) {
+        sched_row = ghost + ((size_t)L + (size_t)__builtin_amdgcn_readfirstlane(lane)) * 8;
+        if (sched_wave && t < 8 && T > 1) sched_v = sched_row[t];
+    }
     auto body = [&](auto upd_c, auto solve_c, const int n) {
         constexpr bool upd = decltype(upd_c)::value;       // finish step n - 1
         constexpr bool solve = decltype(solve_c)::value;   // start step n
+        if constexpr (kSched && upd && solve) {
+            if (sched_wave) {
+                float e[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) e[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sched_v), k));
+                if (t < 2) {
+                    const float4 st = t ? make_float4(e[4], e[5], e[6], e[7]) : make_float4(e[0], e[1], e[2], e[3]);
+                    CellPre cg;
+                    arz_cell_pre((double)st.x, um, cg);
+                    CellRec *gr = region_cr(sub) + (t ? H : H + 1);
+                    gr->st = st; gr->sh = make_double2(cg.s, cg.h); gr->q0 = make_double2(cg.q0, 0.);
+                }
+                sched_row += (size_t)L * 8;
+                if (t < 8 && n + 1 < T) sched_v = sched_row[t];
+            }
+        }
         char *row0 = reinterpret_cast<char *>((kTape && solve) ? tp_pair : nullptr);
         if (kTape) tp_pair += tp_stride;
         int *cnt = CNT + (n & 1);

@@ -80,7 +80,10 @@ __device__ __forceinline__ float4 tape_trivial_A(const TapeFp &s) { return make_
 // Wave w owns the cells [w C, min(N, (w + 1) C)) with C = 64 p - 1, i.e. at most 64 p interfaces = p passes, so no
 // wave ever needs a pass for a single left-over interface; the state is ping-pong buffered in LDS and the only
 // synchronisation is one workgroup barrier per time step.
-template <bool kIface>
+// kSched: `ghost` is a boundary schedule [T][L][2][4] (dhts_macro_rollout_fwd_sched): row 0 is loaded like a constant ghost; the row of
+// step + 1 goes into the OTHER buffer's boundary slots at the end of step `step`, out of registers that were loaded one step earlier
+// (threads 0 .. 7, one float each), so no step waits for the load it issues.
+template <bool kIface, bool kSched = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(5, 5))) void macro_rollout_fwd_kernel(
     int L, int N, int T, int p, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
@@ -122,9 +125,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     kc.set_um(um); kc.set_grid(dt, dx);
     int fault_step = -1, fault_index = 0;
     // an upstream ghost in double (ghost_source_pack, arz_device.hpp: the itscp source lanes of the stepwise network paths)
-    const bool src_ghost = ghost_is_source(ghost[(size_t)lane * 8]);
+    const bool src_ghost = !kSched && ghost_is_source(ghost[(size_t)lane * 8]);     // (a schedule holds float32 cells only)
     double src_r = 0., src_y = 0., src_u = 0., src_q = 0.;
     if (src_ghost) ghost_source_unpack(ghost[(size_t)lane * 8 + 2], ghost[(size_t)lane * 8 + 3], um, src_r, src_y, src_u, src_q);
+    float sched_v = 0.f;                             // element (side, k) = (tid >> 2, tid & 3) of the next step's row
+    const float *sched_p = nullptr;
+    if constexpr (kSched) {
+        sched_p = ghost + ((size_t)L + lane) * 8 + (tid & 7);
+        if (tid < 8 && T > 1) sched_v = *sched_p;
+    }
 
     for (int step = 0; step < T; ++step) {
         const float *cur = lds + (step & 1) * 4 * P;
@@ -194,6 +203,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
                     }
                     if (hp) { hp[i] = nr; hp[N + i] = ny; hp[2 * N + i] = nu; }
                 }
+            }
+        }
+        if constexpr (kSched) {
+            if (tid < 8 && step + 1 < T) {
+                nxt[(tid & 3) * P + ((tid >> 2) ? N + 1 : 0)] = sched_v;
+                sched_p += (size_t)L * 8;
+                if (step + 2 < T) sched_v = *sched_p;
             }
         }
         __syncthreads();
@@ -306,7 +322,10 @@ __device__ __forceinline__ void cell_glue_pre(float r, float y, float umf, const
 // to interleave; kFull: every thread-pass owns a cell (N = kP blockDim.x): no validity masks; kHist: the state history may
 // be asked for.  The step body is instantiated with literal (finish the previous step, start this one) flags: first step,
 // steps in between, last.
-template <int kP, bool kFull, bool kHist>
+// kSched: `ghost` is a boundary schedule [T][L][2][4]: threads 0 and 1 rewrite the two boundary records in phase 1 of every step n >= 1 (after
+// the barrier behind phase 2 of step n - 1, the last reader of the old ones; thread 0, the only phase-1 reader, writes before it reads) from
+// a row that has been in registers since step n - 1, then load the row of step n + 1.
+template <int kP, bool kFull, bool kHist, bool kSched = false>
 __global__ __launch_bounds__(1024) void macro_rollout_fwd2_kernel(
     int L, int N, int T, int p_arg, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
@@ -364,9 +383,26 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd2_kernel(
     constexpr bool kKeep = kP > 0;
     double rd_own[kP > 0 ? kP : 1], yd_own[kP > 0 ? kP : 1];
 
+    float4 sched_st = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 *sched_p = nullptr;
+    if constexpr (kSched) {
+        sched_p = reinterpret_cast<const float4 *>(ghost) + ((size_t)L + lane) * 2 + (tid & 1);
+        if (tid < 2 && T > 1) sched_st = *sched_p;
+    }
+
     auto body = [&](auto upd_c, auto solve_c, const int n) {
         constexpr bool upd = decltype(upd_c)::value;       // finish step n - 1
         constexpr bool solve = decltype(solve_c)::value;   // start step n
+        if constexpr (kSched && upd && solve) {
+            if (tid < 2) {
+                CellPre cg;
+                arz_cell_pre((double)sched_st.x, um, cg);
+                CellRec *gr = CR + (tid ? N + 1 : 0);
+                gr->st = sched_st; gr->sh = make_double2(cg.s, cg.h); gr->q0 = make_double2(cg.q0, 0.);
+                sched_p += (size_t)L * 2;
+                if (n + 1 < T) sched_st = *sched_p;
+            }
+        }
         float4 *tp = solve ? tp_run : nullptr;
         TapeFp *tS = reinterpret_cast<TapeFp *>(tp);
         unsigned *tH = tape_hdr(tp, geo);
@@ -612,7 +648,9 @@ __host__ __device__ inline size_t bwd_fast_lds_bytes(int kB) {
 // kHist: per-step cotangents g_hist [T][L][2][N] (a loss on the state history) are added to the cell's cotangent in front of
 // every step; they ride in the register sets of the trivial products, three steps ahead.
 // kFull: N = kB, every thread holds a cell (BASELINE config 2: 512 cells): no validity masks around the step's pieces.
-template <int kB, bool kHist, bool kFull = false>
+// kSched: `g_ghost` is [T][L][2][2] (dhts_macro_rollout_bwd_sched): the two threads that sum the boundary cotangents store each step's
+// addend instead, one 16-byte store per side and step.
+template <int kB, bool kHist, bool kFull = false, bool kSched = false>
 __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void macro_rollout_bwd_fast_kernel(     // <= 128 VGPRs
     int L, int N, int T, double cc, const float4 *__restrict__ tape,
     const float *__restrict__ g_r_in, const float *__restrict__ g_y_in, const float *__restrict__ g_hist,
@@ -642,6 +680,8 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     if (vk) g = v2f{g_r_in[base + k], g_y_in[base + k]};
 
     double gh_r = 0., gh_y = 0.;         // ghost cotangent sums: thread 0 the left ghost's, thread N - 1 the right one's
+    // kSched: the row of the step, stepped down in front of every interval; slot 0 the left boundary's, slot 1 the right one's
+    double2 *gs_run = kSched ? reinterpret_cast<double2 *>(g_ghost) + ((size_t)T * L + lane) * 2 : nullptr;
     int n_fin = 0;                       // checks of the cell's cotangent that found it finite: a non-finite one stays so (every later value is a
                                          // sum of products with it), so the count says where the first one appeared -- T + 1 checks, newest step first
     // byte offsets inside a row (32-bit, on top of the row's uniform base address)
@@ -726,6 +766,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // for three intervals (2 workgroups x 3 steps x 9 KB per CU: what 6 TB/s at ~2 us of latency need).
 #define DHTS_STEP(CL, s_, Q, R, sl_, sr_, gh_, ea_, eb_, ix_, ec_, cq_)                  \
     {                                                                                    \
+        if (kSched) gs_run -= 2 * (size_t)L;                                             \
         if (vk) {                                                                        \
             g = (c1v + C2[(R) * P + k + 1]) + C0[(R) * P + k + 1];                       \
             if (kHist) g += gh_cur;                /* the cotangent of the state after step s, if the loss looks at it */ \
@@ -736,8 +777,13 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             C0[(Q) * P + k] = c0;                                                        \
             C2[(Q) * P + k + 2] = c2v;                                                   \
             if (edge_wave) {                      /* a scalar branch: two wavefronts of the workgroup take it */ \
+                if (kSched) {                                                            \
+                    if (k == 0) gs_run[0] = make_double2((double)c0.x, (double)c0.y);    \
+                    if (k == N - 1) gs_run[1] = make_double2((double)c2v.x, (double)c2v.y); \
+                } else {                                                                 \
                 if (k == 0) { gh_r += (double)c0.x; gh_y += (double)c0.y; }              \
                 if (k == N - 1) { gh_r += (double)c2v.x; gh_y += (double)c2v.y; }        \
+                }                                                                        \
             }                                                                            \
             if (!(CL) || (s_) >= 1) DHTS_BLOCKS((s_) - 1, R, sl_, sr_)                   \
             if (kHist) gh_cur = gh_;               /* of step s - 1: the set is refilled below */ \
@@ -823,7 +869,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #undef DHTS_SCATTER
 #undef DHTS_STEP
     if (vk) { g_r_out[base + k] = g.x; g_y_out[base + k] = g.y; }
-    if (g_ghost) {
+    if (!kSched && g_ghost) {
         if (t == 0) { g_ghost[(size_t)lane * 4 + 0] = gh_r; g_ghost[(size_t)lane * 4 + 1] = gh_y; }
         if (t == N - 1) { g_ghost[(size_t)lane * 4 + 2] = gh_r; g_ghost[(size_t)lane * 4 + 3] = gh_y; }
     }
@@ -843,7 +889,7 @@ __host__ __device__ inline size_t bwd_fast2_lds_bytes(int kB) {
     const size_t P = 2 * (size_t)kB + 2;
     return 2 * 2 * 8 * P + 2 * 4 * P + 2 * 2 * 16 * (size_t)kB;
 }
-template <int kB, bool kFull>          // kFull: N = 2 kB, both cells of every thread exist (one basic block per interval)
+template <int kB, bool kFull, bool kSched = false>          // kFull: N = 2 kB, both cells of every thread exist (one basic block per interval); kSched: as above
 __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void macro_rollout_bwd_fast2_kernel(     // <= 128 VGPRs
     int L, int N, int T, double cc, const float4 *__restrict__ tape,
     const float *__restrict__ g_r_in, const float *__restrict__ g_y_in,
@@ -872,6 +918,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
     double gh_r = 0., gh_y = 0.;         // ghost cotangent sums: the thread of cell 0 the left ghost's, the thread of cell N - 1 the
                                          // right one's (never the same thread: the launcher keeps N = kB + 1 away from this kernel)
+    double2 *gs_run = kSched ? reinterpret_cast<double2 *>(g_ghost) + ((size_t)T * L + lane) * 2 : nullptr;      // (as in the one-cell kernel)
     int bad_step = -1;                   // (first non-finite cotangent: step << 1 | which of the two cells)
     unsigned zv;
     asm volatile("v_mov_b32 %0, 0" : "=v"(zv));     // keeps the count loads on the vector memory path (vmcnt, not lgkmcnt)
@@ -960,8 +1007,13 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         C2[(Q) * P + (k_) + 2] = c2v;                                                    \
         if (__builtin_amdgcn_ballot_w64(((k_) == 0) | ((k_) == N - 1))) {                \
             asm volatile("" ::: "memory");          /* a real branch: two wavefronts of the workgroup take it */ \
+            if (kSched) {                                                                \
+                if ((k_) == 0) gs_run[0] = make_double2((double)c0.x, (double)c0.y);     \
+                if ((k_) == N - 1) gs_run[1] = make_double2((double)c2v.x, (double)c2v.y); \
+            } else {                                                                     \
             if ((k_) == 0) { gh_r += (double)c0.x; gh_y += (double)c0.y; }               \
             if ((k_) == N - 1) { gh_r += (double)c2v.x; gh_y += (double)c2v.y; }         \
+            }                                                                            \
         }                                                                                \
     }
     // One barrier interval, step s (LDS copy Q, its neighbours' copy R = 1 - Q): the two cells' chain parts, then the blocks of
@@ -970,6 +1022,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // products of step s - 3.
 #define DHTS_STEP(s_, Q, R, S_, ea_, eb_, ix_, cq_)                                      \
     {                                                                                    \
+        if (kSched) gs_run -= 2 * (size_t)L;                                             \
         if (va) DHTS_CELL(s_, Q, R, ka, a)                                               \
         if (vb) DHTS_CELL(s_, Q, R, kb, b)                                               \
         if ((s_) >= 1) {                                                                 \
@@ -1037,7 +1090,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #undef DHTS_STEP
     if (va) { g_r_out[base + ka] = ga.x; g_y_out[base + ka] = ga.y; }
     if (vb) { g_r_out[base + kb] = gb.x; g_y_out[base + kb] = gb.y; }
-    if (g_ghost) {
+    if (!kSched && g_ghost) {
         if (ka == 0) { g_ghost[(size_t)lane * 4 + 0] = gh_r; g_ghost[(size_t)lane * 4 + 1] = gh_y; }
         if (ka == N - 1 || kb == N - 1) { g_ghost[(size_t)lane * 4 + 2] = gh_r; g_ghost[(size_t)lane * 4 + 3] = gh_y; }
     }
@@ -1046,6 +1099,8 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
 // Reverse sweep over the rollout tape, any lane length (lanes above 1024 cells, single cells), per-step cotangents (g_hist) or not.
 // grid = L workgroups of `blockDim.x` threads (multiple of 64).  Dynamic LDS: 6 planes of (N + 2) floats | u16 SLOT[N + 1].
+// kSched: `g_ghost` is [T][L][2][2]: every step's boundary addend is stored instead of summed.
+template <bool kSched = false>
 __global__ __launch_bounds__(512) void macro_rollout_bwd_kernel(
     int L, int N, int T, double cc, const float4 *__restrict__ tape,
     const float *__restrict__ g_r_in, const float *__restrict__ g_y_in, const float *__restrict__ g_hist,
@@ -1091,8 +1146,14 @@ __global__ __launch_bounds__(512) void macro_rollout_bwd_kernel(
                 C0r[k] = c0r; C0y[k] = c0y;
                 C2r[k + 2] = c2r; C2y[k + 2] = c2y;
                 Gr[k + 1] = c1r; Gy[k + 1] = c1y;
-                if (k == 0) { ghl_r += (double)c0r; ghl_y += (double)c0y; }
-                if (k == N - 1) { ghr_r += (double)c2r; ghr_y += (double)c2y; }
+                if constexpr (kSched) {
+                    double2 *gs = reinterpret_cast<double2 *>(g_ghost) + ((size_t)step * L + lane) * 2;
+                    if (k == 0) gs[0] = make_double2((double)c0r, (double)c0y);
+                    if (k == N - 1) gs[1] = make_double2((double)c2r, (double)c2y);
+                } else {
+                    if (k == 0) { ghl_r += (double)c0r; ghl_y += (double)c0y; }
+                    if (k == N - 1) { ghr_r += (double)c2r; ghr_y += (double)c2y; }
+                }
             }
             __syncthreads();
             for (int k = t; k < N; k += B) {
@@ -1107,7 +1168,7 @@ __global__ __launch_bounds__(512) void macro_rollout_bwd_kernel(
         }
     }
     for (int k = t; k < N; k += B) { g_r_out[base + k] = Gr[k + 1]; g_y_out[base + k] = Gy[k + 1]; }
-    if (g_ghost) {
+    if (!kSched && g_ghost) {
         if (t == 0) { g_ghost[(size_t)lane * 4 + 0] = ghl_r; g_ghost[(size_t)lane * 4 + 1] = ghl_y; }
         if (t == (N - 1) % B) { g_ghost[(size_t)lane * 4 + 2] = ghr_r; g_ghost[(size_t)lane * 4 + 3] = ghr_y; }
     }
@@ -1292,15 +1353,32 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
     return pl;
 }
 
-// the two-phase kernels (the caller has checked its arguments)
+// the two-phase kernels (the caller has checked its arguments); sched: `ghost` is a boundary schedule [T][L][2][4] (the kSched
+// instantiations, picked by the same plan fields; they stand behind the constant-boundary ones in the code object)
 static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int T,
                              const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                              float *r_out, float *y_out, float *u_out, float *ueq_out,
-                             float *tape, float *hist, dhts_error *err, void *stream) {
+                             float *tape, float *hist, dhts_error *err, void *stream, bool sched = false) {
     const int N = d->n_cells;
     float4 *tp = reinterpret_cast<float4 *>(tape);
     bool lds_ok = true;
-    if (pl.fwd == kMacroFwdLane) {
+    if (sched && pl.fwd == kMacroFwdLane) {
+        pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
+            constexpr int kV = decltype(v)::value;
+            lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0, true>, d->n_lanes, 64 * pl.W, pl.lds_fwd,
+                                kLdsDefault, stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out,
+                                ueq_out, tp, hist, err);
+        });
+    } else if (sched) {
+        pick<4, 2, 1>(pl.G, [&](auto g) {
+            pick<0, 1>(pl.tape, [&](auto tp_) {
+                constexpr int kG = decltype(g)::value;
+                lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0, true>, d->n_lanes / kG, 64 * kG * (N / 128),
+                                    pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out,
+                                    u_out, ueq_out, tp, err, dhts_fwd_rotate);
+            });
+        });
+    } else if (pl.fwd == kMacroFwdLane) {
         // <kP, kFull, kHist> as 10 kP + kFull (kHist = !kFull); kP = 0: the run-time pass count
         pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
             constexpr int kV = decltype(v)::value;
@@ -1322,7 +1400,7 @@ static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int 
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
-template <bool kIface>
+template <bool kIface, bool kSched = false>
 static int macro_fwd_launch(const dhts_macro_desc *d, int T,
                             const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                             float *r_out, float *y_out, float *u_out, float *ueq_out,
@@ -1344,7 +1422,7 @@ static int macro_fwd_launch(const dhts_macro_desc *d, int T,
     int p = 1;
     while ((N + (64 * p - 1) - 1) / (64 * p - 1) > W) ++p;
     W = (N + (64 * p - 1) - 1) / (64 * p - 1);
-    if (!launch_lds(macro_rollout_fwd_kernel<kIface>, d->n_lanes, 64 * W, lds, kLdsDefault, stream, d->n_lanes, N, T, p, d->dt, d->dx, d->u_max,
+    if (!launch_lds(macro_rollout_fwd_kernel<kIface, kSched>, d->n_lanes, 64 * W, lds, kLdsDefault, stream, d->n_lanes, N, T, p, d->dt, d->dx, d->u_max,
                     r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float4 *>(tape), hist, err))
         return DHTS_E_LAUNCH;
     return launch_status();
@@ -1361,17 +1439,35 @@ static int macro_blocks_bwd_launch(const dhts_macro_desc *d, int T, const float 
         return DHTS_E_LAUNCH;
     return launch_status();
 }
+// sched: g_ghost is the per-step boundary cotangent [T][L][2][2] (the kSched instantiations, behind the others in the code object)
 static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float *tape,
                                     const float *g_r, const float *g_y, const float *g_hist,
-                                    float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
-    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out) return DHTS_E_INVALID;
+                                    float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream, bool sched = false) {
+    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out || (sched && !g_ghost)) return DHTS_E_INVALID;
     const MacroPlan pl = macro_plan(d, T, g_hist != nullptr, tape != nullptr);
     const int N = d->n_cells, B = pl.bwd_block;
     const float4 *tp = reinterpret_cast<const float4 *>(tape);
     const double cc = d->dt / d->dx;
     if (pl.lds_bwd > 160 * 1024) return DHTS_E_INVALID;
     bool lds_ok = true;
-    if (pl.bwd == kMacroBwdFast) {
+    if (sched) {
+        if (pl.bwd == kMacroBwdFast) {
+            pick<10242, 5120, 5122, 5121, 2560, 2562, 2561, 1280, 1282, 1281, 640, 642, 641, 10241, 10240>(
+                10 * B + (pl.hist ? 1 : (pl.bwd_full ? 2 : 0)), [&](auto v) {
+                    constexpr int kV = decltype(v)::value;
+                    lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, kV % 10 == 1, kV % 10 == 2, true>, d->n_lanes, B, pl.lds_bwd,
+                                        kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err);
+                });
+        } else if (pl.bwd == kMacroBwdFast2) {
+            pick<0, 1>(pl.bwd_full, [&](auto full) {
+                lds_ok = launch_lds(macro_rollout_bwd_fast2_kernel<1024, decltype(full)::value != 0, true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault,
+                                    stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_r_out, g_y_out, g_ghost, err);
+            });
+        } else {
+            lds_ok = launch_lds(macro_rollout_bwd_kernel<true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y,
+                                g_hist, g_r_out, g_y_out, g_ghost, err);
+        }
+    } else if (pl.bwd == kMacroBwdFast) {
         // <kB, kHist, kFull> as 10 kB + (0 plain, 1 kHist, 2 kFull).  The list holds every instantiation the library has always had, in
         // the order that keeps them where they have always been in the code object (last entry first).
         pick<10242, 5120, 5122, 5121, 2560, 2562, 2561, 1280, 1282, 1281, 640, 642, 641, 10241, 10240>(
@@ -1386,7 +1482,7 @@ static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float
                                 d->n_lanes, N, T, cc, tp, g_r, g_y, g_r_out, g_y_out, g_ghost, err);
         });
     } else {
-        lds_ok = launch_lds(macro_rollout_bwd_kernel, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist,
+        lds_ok = launch_lds(macro_rollout_bwd_kernel<false>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist,
                             g_r_out, g_y_out, g_ghost, err);
     }
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
@@ -1460,7 +1556,33 @@ int dhts_macro_rollout_bwd(const dhts_macro_desc *d, int T, const float *tape,
                            float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
     return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, stream);
 }
-// which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for this shape: the plan the launches read
+// the same rollout with a boundary schedule: the same plan, the kSched instantiation of the kernel it names
+int dhts_macro_rollout_fwd_sched(const dhts_macro_desc *d, int T,
+                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost_sched,
+                                 float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                 float *tape, float *hist, dhts_error *err, void *stream) {
+    if (!macro_desc_ok(d) || T < 0 || !r || !y || !u || !ueq || !ghost_sched || !r_out || !y_out || !u_out || !ueq_out) return DHTS_E_INVALID;
+    if (T == 0) {       // no row to read: the state comes back as it went in (what the constant-boundary rollout does with T = 0)
+        const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
+        const float *src[4] = {r, y, u, ueq};
+        float *dst[4] = {r_out, y_out, u_out, ueq_out};
+        for (int k = 0; k < 4; ++k)
+            if (dst[k] != src[k] && hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+                return DHTS_E_LAUNCH;
+        return DHTS_OK;
+    }
+    const MacroPlan pl = macro_plan(d, T, hist != nullptr, tape != nullptr);
+    if (pl.fwd == kMacroFwdOnePhase)
+        return macro_fwd_launch<true, true>(d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out, tape, hist, err, stream);
+    return macro_fwd2_launch(pl, d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out, tape, hist, err, stream, true);
+}
+int dhts_macro_rollout_bwd_sched(const dhts_macro_desc *d, int T, const float *tape,
+                                 const float *g_r, const float *g_y, const float *g_hist,
+                                 float *g_r_out, float *g_y_out, double *g_ghost_sched, dhts_error *err, void *stream) {
+    if (!g_ghost_sched) return DHTS_E_INVALID;
+    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost_sched, err, stream, true);
+}
+// which kernel instantiations dhts_macro_rollout_fwd / _bwd (and their _sched forms) launch for this shape: the plan the launches read
 int dhts_macro_rollout_plan(const dhts_macro_desc *d, int T, int want_hist, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
     const MacroPlan pl = macro_plan(d, T, want_hist != 0, true);

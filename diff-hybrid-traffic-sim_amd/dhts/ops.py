@@ -157,6 +157,37 @@ def macro_rollout_bwd(desc, T, tape, g_r, g_y, g_hist=None, err=None, out=None, 
     return out[0], out[1], g_ghost
 
 
+def macro_rollout_fwd_sched(desc, T, r, y, u, ueq, ghost_sched, tape=None, hist=None, err=None, out=None):
+    """macro_rollout_fwd with a boundary schedule: ghost_sched [T][L][2][4], row t read by step t."""
+    L, N = desc.n_lanes, desc.n_cells
+    for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
+        if tuple(t.shape) != (L, N):
+            raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
+    if tuple(ghost_sched.shape) != (int(T), L, 2, 4):
+        raise ValueError("ghost_sched must have shape (%d, %d, 2, 4)" % (int(T), L))
+    r, y, u, ueq, ghost_sched = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost_sched, "ghost_sched")))
+    if int(T) == 0:             # an empty tensor has no address; the entry point wants one and reads no row
+        ghost_sched = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
+    if out is None:
+        out = tuple(torch.empty_like(r) for _ in range(4))
+    check(_lib.lib().dhts_macro_rollout_fwd_sched(C.byref(desc), int(T), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost_sched),
+                                                  _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                                                  _ptr(tape), _ptr(hist), _ptr(err), _stream()), "dhts_macro_rollout_fwd_sched")
+    return out
+
+
+def macro_rollout_bwd_sched(desc, T, tape, g_r, g_y, g_hist=None, err=None, out=None):
+    """returns (g_r0, g_y0, g_ghost_sched [T][L][2][2] float64): row t = the cotangent that reaches the boundary cells of step t."""
+    g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
+    if out is None:
+        out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    g_sched = torch.empty(max(int(T), 1), desc.n_lanes, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
+    check(_lib.lib().dhts_macro_rollout_bwd_sched(C.byref(desc), int(T), _ptr(tape), _ptr(g_r), _ptr(g_y), _ptr(g_hist),
+                                                  _ptr(out[0]), _ptr(out[1]), _ptr(g_sched), _ptr(err), _stream()),
+          "dhts_macro_rollout_bwd_sched")
+    return out[0], out[1], g_sched[:int(T)]
+
+
 def macro_rollout_plan(desc, T, want_hist=False):
     """Which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for this shape (include/dhts.h)."""
     plan = (C.c_int32 * 8)()
@@ -178,6 +209,7 @@ class MacroRollout(torch.autograd.Function):
     """T fused differentiable steps of L independent straight ARZ lanes.
 
     (r0, u0 [L][N], ghost_r, ghost_u [L][2]) -> (rT, yT, uT [L][N]) (+ hist [T][L][3][N] when asked).
+    ghost_r, ghost_u [T][L][2] instead: a boundary schedule, row t set in front of step t; their gradients come back per step.
     What example/inverse/macro.py does with one dMacroLane in a RoadNetwork (macro.py:34-68,
     _inverse.py:91-99), for L lanes at once: state set by set_state_vector_u, ghosts by
     set_leftmost_cell / set_rightmost_cell, T x RoadNetwork.forward, state read by get_state_vector.
@@ -186,19 +218,27 @@ class MacroRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True):
         L, N = r0.shape
+        sched = ghost_r.dim() == 3
+        if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
+            raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
+        want = (int(T), L, 2) if sched else (L, 2)
+        if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
+            raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
         desc = macro_desc(L, N, dt, dx, u_max)
         r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
         gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
         y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
-        gy, gq = macro_state_from_ru(gr, gu, u_max)
-        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4]
+        gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
+        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4], or [T][L][2][4]
         need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
         tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
         hist = torch.empty(T, L, 3, N, dtype=torch.float32, device=r0.device) if want_hist else None
         err = new_error_record(r0.device)
-        rT, yT, uT, qT = macro_rollout_fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=hist, err=err)
+        fwd = macro_rollout_fwd_sched if sched else macro_rollout_fwd
+        rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=hist, err=err)
         if check_faults:
             raise_on_fault(err)
+        ctx.sched = sched
         ctx.desc, ctx.T, ctx.u_max, ctx.tape, ctx.want_hist, ctx.check_faults = desc, T, u_max, tape, want_hist, check_faults
         ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, hist)
         ctx.mark_non_differentiable(qT)
@@ -224,11 +264,12 @@ class MacroRollout(torch.autograd.Function):
             macro_u_tap_bwd(hr, hy, g_hist[:, :, 2].contiguous(), ghr, ghy, um)
             gh = torch.stack([ghr, ghy], dim=2).contiguous()                   # [T][L][2][N]
         err = new_error_record(dev)
-        g_r0, g_y0, g_ghost = macro_rollout_bwd(desc, T, ctx.tape, g_r, g_y, g_hist=gh, err=err)
+        bwd = macro_rollout_bwd_sched if ctx.sched else macro_rollout_bwd
+        g_r0, g_y0, g_ghost = bwd(desc, T, ctx.tape, g_r, g_y, g_hist=gh, err=err)      # [L][2][2], or [T][L][2][2] per step
         if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
             raise_on_fault(err)
         g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
-        # ghost (r, y) cotangent sums -> ghost (r, u) leaves, in double (the sum is ill-conditioned)
+        # ghost (r, y) cotangents (sums over the steps, or per step) -> ghost (r, u) leaves, in double (the sum is ill-conditioned)
         rr, uu, qq = gr.double(), gu.double(), gq.double()
         dueq = torch.where(rr < 0, torch.zeros_like(rr), -um * 0.5 / torch.sqrt(rr.clamp_min(0) + EPS))
         g_gr = (g_ghost[..., 0] + g_ghost[..., 1] * ((uu - qq) - rr * dueq)).float()

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Inflow estimation on a macroscopic lane: which upstream density profile produced these downstream detector readings?
+
+A lane starts in a known uniform free-flow state.  The truth is a smooth density pulse in the upstream boundary cell (a platoon
+arriving), the cell at its equilibrium speed; the downstream boundary cell stays at the initial state.  A few detectors downstream
+record the density after every step.  From those readings alone the [T] upstream density profile is recovered with Adam: the loss is
+on the state HISTORY (want_hist=True) and its gradient reaches every step's boundary cell through the per-step boundary cotangent of
+the fused rollout (dhts.macro_rollout with ghost_r, ghost_u of shape [T][L][2]).  Every trial solves n_lane independent problems at
+once.  What a detector at cell c can see of the profile ends c cells' travel time before the end of the horizon: the tail of the
+profile stays at its first guess.
+
+Same output conventions as inverse_macro.py: one log line "{profile_error} {loss}" per episode in
+result/inflow/<run>/gd/trial_<k>.txt and one summary line per trial.  PyTorch does the optimiser step; every simulated step (forward
+and adjoint) runs in the HIP kernels.
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "diff-hybrid-traffic-sim_amd"))
+
+import torch as th  # noqa: E402
+
+import dhts  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser("Upstream inflow profile from downstream detectors (gradient descent, MI355X)")
+    ap.add_argument("--n_trial", type=int, default=1)
+    ap.add_argument("--n_cell", type=int, default=64)
+    ap.add_argument("--n_timestep", type=int, default=300)
+    ap.add_argument("--cell_length", type=float, default=5.0)
+    ap.add_argument("--speed_limit", type=float, default=30.0)
+    ap.add_argument("--delta_time", type=float, default=0.01)
+    ap.add_argument("--n_episode", type=int, default=100)
+    ap.add_argument("--n_lane", type=int, default=1)
+    ap.add_argument("--n_detector", type=int, default=4)
+    ap.add_argument("--lr", type=float, default=2e-2)
+    ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--run_name", default=None)
+    args = ap.parse_args()
+
+    dev = th.device("cuda", 0)
+    if args.seed is not None:
+        th.manual_seed(args.seed)
+    L, N, T, um = args.n_lane, args.n_cell, args.n_timestep, args.speed_limit
+    dt, dx = args.delta_time, args.cell_length
+    run = args.run_name or "inflow_{}".format(time.strftime("%Y%m%d_%H%M%S"))
+    log_dir = os.path.join("result", "inflow", run, "gd")
+    os.makedirs(log_dir, exist_ok=True)
+    # detectors in the first eighth of the lane: at free-flow speed the pulse covers about a cell per 30 steps (dx = 5, dt = 0.01)
+    det = th.unique(th.linspace(0, max(N // 8, 1), args.n_detector, device=dev).long().clamp(0, N - 1))
+    r_base = 0.2
+
+    def u_eq(r):
+        return um * (1.0 - th.sqrt(r + 1e-5))
+
+    def schedule(up_r):
+        """[T][L] upstream densities -> boundary (r, u) [T][L][2]: upstream at its equilibrium speed, downstream the base state."""
+        down = th.full_like(up_r, r_base)
+        return th.stack([up_r, down], dim=-1), th.stack([u_eq(up_r), u_eq(down)], dim=-1)
+
+    for trial in range(args.n_trial):
+        r0 = th.full((L, N), r_base, device=dev)
+        u0 = u_eq(r0)
+        tt = th.arange(T, device=dev, dtype=th.float32)[:, None]
+        peak = 0.35 + 0.25 * th.rand(1, L, device=dev)                 # pulse height, centre and width differ per lane
+        mid = (0.25 + 0.15 * th.rand(1, L, device=dev)) * T
+        wid = (0.08 + 0.06 * th.rand(1, L, device=dev)) * T
+        up_true = r_base + peak * th.exp(-((tt - mid) / wid) ** 2)     # [T][L]
+        with th.no_grad():
+            out = dhts.macro_rollout(r0, u0, *schedule(up_true), T, dt, dx, um, want_hist=True)
+            obs = out[4][:, :, 0][:, :, det].clone()                   # [T][L][detectors]: the density readings
+        up_est = th.full((T, L), r_base, device=dev, requires_grad=True)
+        opt = th.optim.Adam([up_est], lr=args.lr)
+        lines = []
+        t0 = time.time()
+        for ep in range(args.n_episode):
+            gr, gu = schedule(up_est)
+            hist = dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, want_hist=True)[4]
+            loss = ((hist[:, :, 0][:, :, det] - obs) ** 2).sum()
+            err = ((up_est.detach() - up_true) ** 2).sum()
+            opt.zero_grad(set_to_none=False)
+            loss.backward()
+            opt.step()
+            with th.no_grad():
+                up_est.clamp_(0.0, 1.0)
+            lines.append("{} {}\n".format(err.item(), loss.item()))
+        th.cuda.synchronize()
+        dt_wall = time.time() - t0
+        with open(os.path.join(log_dir, "trial_{}.txt".format(trial)), "w") as f:
+            f.writelines(lines)
+        first, last = lines[0].split(), lines[-1].split()
+        print("Trial # {}: loss {:.6f} -> {:.6f}, profile error {:.6f} -> {:.6f} in {} episodes, {:.2f} s "
+              "({:.3e} differentiable cell-steps/s)".format(trial, float(first[1]), float(last[1]), float(first[0]), float(last[0]),
+                                                            args.n_episode, dt_wall, L * N * T * args.n_episode / dt_wall))
+
+
+if __name__ == "__main__":
+    main()

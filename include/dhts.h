@@ -199,8 +199,31 @@ int dhts_macro_rollout_bwd(const dhts_macro_desc *d, int T, const float *tape,
                            const float *g_r, const float *g_y, const float *g_hist,
                            float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream);
 
-/* Which kernel instantiations the two calls above launch for this shape and the current options (answered by the functions
- * the launches themselves call; tests pin the benchmarked instantiations with it):
+/*
+ * The same rollout with TIME-VARYING boundary cells (set_leftmost_cell / set_rightmost_cell with fresh tensors in front of every
+ * RoadNetwork.forward) and the cotangent of every step's boundary cells.  Everything else -- state planes, tape format and
+ * dhts_macro_tape_bytes, hist / g_hist, the fault record (a CFL fault carries step, lane and interface), the plan below -- is that of the
+ * two calls above, and with ghost_sched[t] = ghost for every t the states, hist, the tape and g_r_out / g_y_out are theirs bit for bit.
+ *   ghost_sched   [T][L][2][4] float32 = per step and lane (left, right) x (r, y, u, ueq): step t (the step that turns the state after t
+ *                 steps into the state after t + 1) reads row t and no other.  float32 cells only: the double "source" encoding of
+ *                 dhts_macro_step_fwd is not decoded here (a NaN density is taken as a NaN density).
+ *   g_ghost_sched [T][L][2][2] DOUBLE = per step and lane (left, right) x (r, y): row t is the cotangent that reaches the boundary cells
+ *                 of step t, i.e. exactly the addend dhts_macro_rollout_bwd adds into g_ghost at that step (a float32 value, widened);
+ *                 the rows added up newest step first give g_ghost bit for bit.  Every row is written (plain stores, no atomics: two
+ *                 runs give the same bits); g_hist as above.
+ * T = 0 is accepted (no row is read or written).  NULL ghost_sched / g_ghost_sched or a bad descriptor: DHTS_E_INVALID, nothing is
+ * dereferenced.
+ */
+int dhts_macro_rollout_fwd_sched(const dhts_macro_desc *d, int T,
+                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost_sched,
+                                 float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                 float *tape, float *hist, dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_sched(const dhts_macro_desc *d, int T, const float *tape,
+                                 const float *g_r, const float *g_y, const float *g_hist,
+                                 float *g_r_out, float *g_y_out, double *g_ghost_sched, dhts_error *err, void *stream);
+
+/* Which kernel instantiations the calls above launch for this shape and the current options -- the _sched forms take the same ones,
+ * compiled for a schedule -- (answered by the functions the launches themselves call; tests pin the benchmarked instantiations with it):
  *   plan[0] forward kernel: 0 = two-phase lane kernel, 1 = one-phase, 2 = two-phase pair kernel
  *   plan[1] wavefronts per lane     plan[2] 64-cell passes per wavefront (pair kernel: two adjacent cells per thread)
  *   plan[3] 1 = the full-lane, history-free instantiation (n_cells = 64 x passes x wavefronts and hist == NULL)

@@ -16,6 +16,7 @@ Golden sets:
   G1/G2  riemann_kat.npz     ARZ.riemann_solve + dARZ.compute_dLdR + dARZ.flux_prime per interface
   G3     macro_step.npz      one dMacroLane step: next state, Jacobian tape dqs, backward of cotangents
   G4     macro_rollout_*.npz T-step rollouts through RoadNetwork.forward with loss and gradients
+  G4s    macro_sched_*.npz   the same with fresh boundary cells in front of every step and their per-step gradients
   G5     idm_kat.npz         IDM.compute_acceleration + dIDM.compute_dEgo/dLeading
   G6     micro_rollout_*.npz dMicroLane rollouts with loss and gradients
   G6p    micro_params_*.npz  the same lanes through the plain MicroLane with float64 attribute tensors: d loss / d driver parameters
@@ -397,6 +398,79 @@ def gen_macro_rollouts(which):
     if "c2slice" in which:   # ONE lane of BASELINE config 2 at its full shape: 512 cells x 1000 steps (round 3: pins the
         # very kernel instantiations bench.py times -- four wavefronts x two passes, no history -- against the reference)
         macro_rollout("c2slice", 512, 1000, 5.0, 0.01, 30.0, seed=2027, init="bench", tap="final_sq", record_steps=0)
+
+
+# ----------------------------------------------------------------------------------------------
+# G4s: macro rollouts with time-varying boundary cells
+# ----------------------------------------------------------------------------------------------
+
+def macro_sched(name, N, T, dx, dt, um, seed, init="uniform", tap="final_sq", boundary="random", record_steps=0):
+    """G4's one-dMacroLane RoadNetwork with set_leftmost_cell(gr[t, 0], gu[t, 0]) / set_rightmost_cell(gr[t, 1], gu[t, 1]) in front of
+    every RoadNetwork.forward(dt, True); gr, gu [T][2] are leaves, their .grad the per-step boundary gradient.
+    boundary: "random" = independent values per step in the init's range; "pulse" = a smooth upstream density pulse, the downstream cell
+    constant."""
+    th.manual_seed(seed)
+    if init == "uniform":
+        r0, u0 = th.rand(N), th.rand(N) * um
+        gr, gu = th.rand(T, 2), th.rand(T, 2) * um
+    elif init == "bench":
+        r0, u0 = 0.05 + 0.9 * th.rand(N), th.rand(N) * um
+        gr, gu = 0.05 + 0.9 * th.rand(T, 2), th.rand(T, 2) * um
+    elif init == "sanity":
+        r0 = th.rand(N)
+        u0 = th.lerp(th.tensor([0.4 * um]), th.tensor([0.7 * um]), th.rand(N))
+        gr = th.rand(T, 2)
+        gu = th.lerp(th.tensor([0.4 * um]), th.tensor([0.7 * um]), th.rand(T, 2))
+    if boundary == "pulse":
+        tt = th.arange(T, dtype=th.float32)
+        gr = th.stack([0.2 + 0.6 * th.exp(-((tt - 0.4 * T) / (0.15 * T)) ** 2), th.full((T,), float(gr[0, 1]))], dim=1)
+        gu = th.stack([um * (1.0 - th.sqrt(gr[:, 0])), th.full((T,), float(gu[0, 1]))], dim=1)      # upstream cell at its equilibrium speed
+    r0 = r0.to(th.float32).requires_grad_(True)
+    u0 = u0.to(th.float32).requires_grad_(True)
+    gr = gr.to(th.float32).contiguous().requires_grad_(True)
+    gu = gu.to(th.float32).contiguous().requires_grad_(True)
+
+    lane = dMacroLane(0, N * dx, um, dx)
+    lane.set_state_vector_u(r0, u0)
+    net = RoadNetwork(um)
+    net.add_lane(lane)
+
+    steps_r, steps_y, steps_u = [], [], []
+    loss = 0
+    for t in range(T):
+        lane.set_leftmost_cell(gr[t, 0], gu[t, 0])
+        lane.set_rightmost_cell(gr[t, 1], gu[t, 1])
+        net.forward(dt, True)
+        if tap == "every_sum":
+            r, y, u = lane.get_state_vector()
+            loss = loss + r.sum() + y.sum() + u.sum()
+        if t < record_steps:
+            r, y, u = lane.get_state_vector()
+            steps_r.append(r.detach().numpy().copy())
+            steps_y.append(y.detach().numpy().copy())
+            steps_u.append(u.detach().numpy().copy())
+    rT, yT, uT = lane.get_state_vector()
+    if tap == "final_sq":
+        loss = (rT ** 2).sum() + (uT ** 2).sum()
+    loss.backward()
+    print("G4s %-10s N=%d T=%d loss=%.6f" % (name, N, T, float(loss)))
+    np.savez_compressed(
+        os.path.join(OUT, "macro_sched_%s.npz" % name),
+        r0=r0.detach().numpy(), u0=u0.detach().numpy(), ghost_r=gr.detach().numpy(), ghost_u=gu.detach().numpy(),
+        rT=rT.detach().numpy(), yT=yT.detach().numpy(), uT=uT.detach().numpy(),
+        loss=np.float64(float(loss)),
+        g_r0=r0.grad.numpy(), g_u0=u0.grad.numpy(), g_ghost_r=gr.grad.numpy(), g_ghost_u=gu.grad.numpy(),
+        steps_r=np.array(steps_r, dtype=np.float32), steps_y=np.array(steps_y, dtype=np.float32),
+        steps_u=np.array(steps_u, dtype=np.float32),
+        meta=meta(seed=seed, N=N, T=T, dx=dx, dt=dt, u_max=um, init=init, tap=tap, boundary=boundary))
+
+
+def gen_macro_scheds():
+    # (seeds: the first tried for each case; none had to be dropped for a knife edge of the reference's arithmetic -- the chained oracle
+    # of tests/macro_sched_ref.py is inside TOL_STATE / TOL_GRAD on all three)
+    macro_sched("small", 24, 40, 5.0, 0.01, 30.0, seed=3, init="uniform", tap="final_sq", boundary="random", record_steps=4)
+    macro_sched("pulse64", 64, 120, 5.0, 0.01, 30.0, seed=2026, init="bench", tap="final_sq", boundary="pulse", record_steps=4)
+    macro_sched("sanity", 100, 10, 100.0, 0.03, 30.0, seed=0, init="sanity", tap="every_sum", boundary="random", record_steps=4)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -988,6 +1062,8 @@ def main():
         gen_riemann_kat_stale()
     if "G3" in only:
         gen_macro_step()
+    if "G4s" in only:
+        gen_macro_scheds()
     if "G4" in only:
         gen_macro_rollouts(set(args.g4.split(",")))
     if "G5" in only:
