@@ -173,13 +173,20 @@ constexpr int kFairShift = 3;
 // v_readlane hands the eight values to the two writers.  The last wavefront, because vector memory operations retire in order: the wait
 // for the row also waits for all but a few of the wavefront's tape stores issued behind the load, and the last wavefront's youngest ones
 // are its phase-1 entries, a whole phase 2 old -- the first wavefront has just stored the step's exceptions.
-template <int kG, bool kTape, bool kSched = false>
+// kTaps: detector taps (macro_kernels.hip, "detector taps").  The threads are dealt as in phase 2 -- thread g works for lane g % kG of the
+// group -- but from the far end: it takes detector slot 64 Wl - 1 - g / kG (+ 64 Wl for a further one, D > N / 2 only) and reads that
+// cell's record in phase 2 of step n: the state after step n - 1, which phase 1 has just written and nobody writes again before the
+// barrier behind phase 2.  ONE vector register (det_own) and one scalar flag (tap_wave) live across the step loop; everything else is
+// formed again from the thread index where it is used (behind an empty asm, so that the compiler does not hoist it out of the step loop
+// into registers the kernel does not have: hoisted, the config-2 instantiation spilled 4 registers; like this it has none).
+template <int kG, bool kTape, bool kSched = false, bool kTaps = false>
 __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
     int L, int N, int T, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
     const float *__restrict__ q_in, const float *__restrict__ ghost,
     float *__restrict__ r_out, float *__restrict__ y_out, float *__restrict__ u_out, float *__restrict__ q_out,
-    float4 *__restrict__ tape, dhts_error *err, int rotate) {
+    float4 *__restrict__ tape, dhts_error *err, int rotate,
+    const int32_t *__restrict__ det, int n_det, float *__restrict__ taps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int t = tid & 63;
@@ -268,6 +275,25 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
         sched_row = ghost + ((size_t)L + (size_t)__builtin_amdgcn_readfirstlane(lane)) * 8;
         if (sched_wave && t < 8 && T > 1) sched_v = sched_row[t];
     }
+    int det_own = -1;
+    bool tap_wave = false;
+    if constexpr (kTaps) {
+        const int j0 = (Wl << 6) - 1 - tid / kG;
+        tap_wave = __builtin_amdgcn_readfirstlane((Wl << 6) - 1 - (tid | 63) / kG) < n_det;      // the wavefront's lowest slot
+        if (j0 < n_det) det_own = det[j0];
+    }
+    auto tap = [&](const int s) {                       // the state after step s, out of the lanes' records
+        if (tap_wave) {
+            int tl = threadIdx.x;
+            asm volatile("" : "+v"(tl));
+            const int sl = tl & (kG - 1);
+            const CellRec *cr = region_cr(sl);
+            const int Hh = H;
+            float *row = taps + ((size_t)s * L + (size_t)(kG * blockIdx.x + sl)) * 3 * n_det;
+            taps_write(det, n_det, det_own, (Wl << 6) - 1 - tl / kG, Wl << 6, N, row,
+                       [=](unsigned dc) { return cr[(dc & 1u) ? Hh + 1 + ((dc + 1u) >> 1) : (dc >> 1)].st; });
+        }
+    };
     auto body = [&](auto upd_c, auto solve_c, const int n) {
         constexpr bool upd = decltype(upd_c)::value;       // finish step n - 1
         constexpr bool solve = decltype(solve_c)::value;   // start step n
@@ -322,6 +348,12 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
             *reinterpret_cast<float2 *>(y_out + base + 2 * m) = make_float2(ya, yb);
             *reinterpret_cast<float2 *>(u_out + base + 2 * m) = make_float2(ua, ub);
             *reinterpret_cast<float2 *>(q_out + base + 2 * m) = make_float2(qa, qb);
+            if constexpr (kTaps && upd) {               // the final step writes no records: the state once more, for the taps
+                CRa->st = make_float4(ra, ya, ua, qa);
+                CRb->st = make_float4(rb, yb, ub, qb);
+                lds_only_barrier();
+                tap(n - 1);
+            }
             return;
         }
         const bool easy1 = po.easy1, easy2 = po.triv2 & !last_t;
@@ -369,6 +401,7 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
             }
         }
         __builtin_amdgcn_s_setprio(0);
+        if constexpr (kTaps && upd) tap(n - 1);
         if (tid < kG) region_cnt(tid)[(n + 1) & 1] = n_forced;
 #ifdef DHTS_FWD3_STAMPS
         const bool held_ = __builtin_amdgcn_ballot_w64(held) != 0;

@@ -76,6 +76,29 @@ static_assert(sizeof(TapeFp) == 12, "TapeFp layout");
 // than three planes, 4.32 against 4.41 and 4.44 ms)
 __device__ __forceinline__ float4 tape_trivial_A(const TapeFp &s) { return make_float4(s.f0, 1.f, s.f2, s.f3); }
 
+// ---- detector taps (dhts_macro_rollout_fwd_taps) -------------------------------------------------------------------
+// kTaps in the forward kernels: `taps` [T][L][3][n_det] receives (r, y, u) of the cells det[0 .. n_det) after every step -- what
+// hist[t][l][:][det[j]] would hold -- without a history.  MAPPING: the cell's owner does not store its own cell (it would carry a slot
+// index per owned cell through the whole step loop: two registers in the pair kernel, which has six to spare under its 128); the reading
+// threads do -- thread j' of the tap wavefronts takes detector j', keeps det[j'] in ONE register for the whole rollout and, behind the
+// barrier that already orders the step's cell records (LDS) for phase 2, reads the record of that cell and stores its three floats.
+// The tap wavefronts are the LAST ones of a lane (the first ones hold the head of the phase-2 queue); a wavefront whose first detector
+// slot is >= n_det pays one scalar branch per step.  The final step writes no records (nothing solves after it): the taps forms store
+// the float32 state once more and take one extra barrier, once per rollout, so that every row comes out of the same code.
+// INDEX CONTRACT: det[] is not validated on the host (no sync).  An entry is compared against [0, N) as an unsigned value before any
+// address is formed from it; an entry outside matches no cell and its column is not written.  j itself is a loop counter < n_det.
+template <class RecAt>
+__device__ __forceinline__ void taps_write(const int32_t *__restrict__ det, int n_det, int det_own, int j0, int stride, int N,
+                                           float *__restrict__ row, RecAt rec_at) {
+    for (int j = j0; j < n_det; j += stride) {
+        const unsigned dc = (unsigned)(j == j0 ? det_own : det[j]);      // (detectors beyond one per thread: re-read, D > threads only)
+        if (dc < (unsigned)N) {
+            const float4 st = rec_at(dc);
+            row[j] = st.x; row[n_det + j] = st.y; row[2 * n_det + j] = st.z;
+        }
+    }
+}
+
 // grid = L workgroups (one traffic lane each) of W = blockDim.x / 64 wavefronts; dynamic LDS = 2 * 4 * (N + 2) floats.
 // Wave w owns the cells [w C, min(N, (w + 1) C)) with C = 64 p - 1, i.e. at most 64 p interfaces = p passes, so no
 // wave ever needs a pass for a single left-over interface; the state is ping-pong buffered in LDS and the only
@@ -83,19 +106,23 @@ __device__ __forceinline__ float4 tape_trivial_A(const TapeFp &s) { return make_
 // kSched: `ghost` is a boundary schedule [T][L][2][4] (dhts_macro_rollout_fwd_sched): row 0 is loaded like a constant ghost; the row of
 // step + 1 goes into the OTHER buffer's boundary slots at the end of step `step`, out of registers that were loaded one step earlier
 // (threads 0 .. 7, one float each), so no step waits for the load it issues.
-template <bool kIface, bool kSched = false>
+// kTaps: see above; the state after step `step` is the plane set the step wrote, which the next step only reads.
+template <bool kIface, bool kSched = false, bool kTaps = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(5, 5))) void macro_rollout_fwd_kernel(
     int L, int N, int T, int p, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
     const float *__restrict__ q_in, const float *__restrict__ ghost,
     float *__restrict__ r_out, float *__restrict__ y_out, float *__restrict__ u_out, float *__restrict__ q_out,
-    float4 *__restrict__ tape, float *__restrict__ hist, dhts_error *err) {
+    float4 *__restrict__ tape, float *__restrict__ hist, dhts_error *err,
+    const int32_t *__restrict__ det, int n_det, float *__restrict__ taps) {
     extern __shared__ float lds[];
     const int lane = blockIdx.x;
     const int tid = threadIdx.x;
     const int t = tid & 63;
     const int wv = tid >> 6;
     const int P = N + 2;
+    int det_own = -1;
+    if constexpr (kTaps) { if (tid < n_det) det_own = det[tid]; }
     const size_t base = (size_t)lane * N;
 
     // buffer b, plane k (r, y, u, u_eq) at lds + (b * 4 + k) * P; index c + 1 holds cell c, 0 and N + 1 the ghosts
@@ -213,6 +240,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
             }
         }
         __syncthreads();
+        if constexpr (kTaps) {
+            if (__builtin_amdgcn_readfirstlane(wv << 6) < n_det) {
+                const float *nx = nxt;
+                taps_write(det, n_det, det_own, tid, (int)blockDim.x, N, taps + ((size_t)step * L + lane) * 3 * n_det, [=](unsigned dc) {
+                    return make_float4(nx[dc + 1], nx[P + dc + 1], nx[2 * P + dc + 1], 0.f);
+                });
+            }
+        }
     }
     const float *fin = lds + (T & 1) * 4 * P;
     for (int k = tid; k < N; k += blockDim.x) {
@@ -325,13 +360,15 @@ __device__ __forceinline__ void cell_glue_pre(float r, float y, float umf, const
 // kSched: `ghost` is a boundary schedule [T][L][2][4]: threads 0 and 1 rewrite the two boundary records in phase 1 of every step n >= 1 (after
 // the barrier behind phase 2 of step n - 1, the last reader of the old ones; thread 0, the only phase-1 reader, writes before it reads) from
 // a row that has been in registers since step n - 1, then load the row of step n + 1.
-template <int kP, bool kFull, bool kHist, bool kSched = false>
+// kTaps: detector taps (above), read in phase 2 of step n (state after step n - 1) from the records phase 1 has just written.
+template <int kP, bool kFull, bool kHist, bool kSched = false, bool kTaps = false>
 __global__ __launch_bounds__(1024) void macro_rollout_fwd2_kernel(
     int L, int N, int T, int p_arg, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
     const float *__restrict__ q_in, const float *__restrict__ ghost,
     float *__restrict__ r_out, float *__restrict__ y_out, float *__restrict__ u_out, float *__restrict__ q_out,
-    float4 *__restrict__ tape, float *__restrict__ hist, dhts_error *err) {
+    float4 *__restrict__ tape, float *__restrict__ hist, dhts_error *err,
+    const int32_t *__restrict__ det, int n_det, float *__restrict__ taps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = blockIdx.x;
     const int tid = threadIdx.x;
@@ -389,6 +426,21 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd2_kernel(
         sched_p = reinterpret_cast<const float4 *>(ghost) + ((size_t)L + lane) * 2 + (tid & 1);
         if (tid < 2 && T > 1) sched_st = *sched_p;
     }
+    // kTaps: thread (blockDim - 1 - tid) takes detector slot tap_j (+ blockDim per further one); tap_wave: this wavefront holds any
+    const int tap_j = (int)blockDim.x - 1 - tid;
+    int det_own = -1;
+    bool tap_wave = false;
+    if constexpr (kTaps) {
+        tap_wave = __builtin_amdgcn_readfirstlane((Wc - 1 - wv) << 6) < n_det;
+        if (tap_j < n_det) det_own = det[tap_j];
+    }
+    auto tap = [&](const int s) {                       // the state after step s, out of the records
+        if (tap_wave) {
+            const CellRec *cr = CR;
+            taps_write(det, n_det, det_own, tap_j, (int)blockDim.x, N, taps + ((size_t)s * L + lane) * 3 * n_det,
+                       [=](unsigned dc) { return cr[dc + 1].st; });
+        }
+    };
 
     auto body = [&](auto upd_c, auto solve_c, const int n) {
         constexpr bool upd = decltype(upd_c)::value;       // finish step n - 1
@@ -430,6 +482,7 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd2_kernel(
                 CellPre cp;
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
                 if (vc && solve) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
+                else if (kTaps && vc) own->st = st;          // the final step's state, for the taps below
                 if (vc && hp) { hp[i] = st.x; hp[N + i] = st.y; hp[2 * N + i] = st.z; }
             }
             if (!solve) {
@@ -459,7 +512,10 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd2_kernel(
             if (nt) Q[atomicAdd(cnt, 1)] = i;
             if (tp && vc) tS[ic] = TapeFp{fp[0], fp[2], fp[3]};
         }
-        if (!solve) return;
+        if (!solve) {
+            if constexpr (kTaps && upd) { lds_only_barrier(); tap(n - 1); }
+            return;
+        }
         lds_only_barrier();
         // ---- phase 2: the queued interfaces ----
         int k0 = tid - (rot << 6);
@@ -490,6 +546,7 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd2_kernel(
             if (f.cfl_bad && fault_step < 0) { fault_step = n; fault_index = (int)i; }
         }
         __builtin_amdgcn_s_setprio(0);
+        if constexpr (kTaps && upd) tap(n - 1);
         if (tid == 0) CNT[(n + 1) & 1] = 1;
         if (++rot == Wc) rot = 0;
         lds_only_barrier();
@@ -650,11 +707,19 @@ __host__ __device__ inline size_t bwd_fast_lds_bytes(int kB) {
 // kFull: N = kB, every thread holds a cell (BASELINE config 2: 512 cells): no validity masks around the step's pieces.
 // kSched: `g_ghost` is [T][L][2][2] (dhts_macro_rollout_bwd_sched): the two threads that sum the boundary cotangents store each step's
 // addend instead, one 16-byte store per side and step.
-template <int kB, bool kHist, bool kFull = false, bool kSched = false>
+// kTaps: `g_hist` is g_taps [T][L][2][n_det] (dhts_macro_rollout_bwd_taps), the cotangent of (r, y) of the cells det[j] after every step.
+// It rides where the history's cotangent rides (same register sets, three steps ahead, the same g += gh_cur), but only a thread whose cell
+// is a detector loads it -- from column dslot, its cell's place in det[] -- and everyone else holds zero: the sums are those of a dense
+// g_hist that is zero elsewhere.  dslot comes out of an LDS map filled once (borrowed from C0 before the planes are zeroed): entry j of
+// det[] is compared against [0, N) before it indexes the map, so an entry outside matches no cell, and dslot is -1 or a j < n_det.
+template <int kB, bool kHist, bool kFull = false, bool kSched = false, bool kTaps = false>
 __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void macro_rollout_bwd_fast_kernel(     // <= 128 VGPRs
     int L, int N, int T, double cc, const float4 *__restrict__ tape,
     const float *__restrict__ g_r_in, const float *__restrict__ g_y_in, const float *__restrict__ g_hist,
-    float *__restrict__ g_r_out, float *__restrict__ g_y_out, double *__restrict__ g_ghost, dhts_error *err) {
+    float *__restrict__ g_r_out, float *__restrict__ g_y_out, double *__restrict__ g_ghost, dhts_error *err,
+    const int32_t *__restrict__ det, int n_det) {
+    static_assert(!(kHist && kTaps), "per-step cotangents come densely or at detectors, not both");
+    constexpr bool kCot = kHist || kTaps;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = blockIdx.x;
     const int t = threadIdx.x;
@@ -675,6 +740,19 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // the wavefronts that hold cell 0 / cell N - 1 sum the ghosts' cotangents (a scalar: the test costs the others one s_cbranch)
     const int edge_wave = __builtin_amdgcn_readfirstlane(((t >> 6) == 0 || (t >> 6) == ((N - 1) >> 6)) ? 1 : 0);
 
+    int dslot = -1;                      // kTaps: the column of this thread's cell in g_taps, -1 = not a detector
+    if constexpr (kTaps) {
+        int *MAP = reinterpret_cast<int *>(C0);          // [P] ints of the 4 P the two copies of C0 hold
+        for (int i = t; i < P; i += B) MAP[i] = -1;
+        __syncthreads();
+        for (int j = t; j < n_det; j += B) {
+            const unsigned dc = (unsigned)det[j];
+            if (dc < (unsigned)N) MAP[dc] = j;
+        }
+        __syncthreads();
+        if (vk) dslot = MAP[k];
+        __syncthreads();
+    }
     for (int i = t; i < 2 * P; i += B) { C0[i] = zero2; C2[i] = zero2; STAMP[i] = 0u; }
     v2f g = zero2;
     if (vk) g = v2f{g_r_in[base + k], g_y_in[base + k]};
@@ -697,9 +775,9 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // (no multiplications in the loop).
     // per-step cotangents: row of step - 4 as well (the set refilled in the interval of `step` serves step - 4's blocks AND the
     // cotangent added in front of step - 4)
-    const size_t hstride = (size_t)L * 2 * N;
-    const float *hb = kHist ? g_hist + (size_t)lane * 2 * N + kl : nullptr;
-    const float *pH = kHist ? hb + (size_t)(T > 5 ? T - 5 : 0) * hstride : nullptr;
+    const size_t hstride = (size_t)L * 2 * (kTaps ? n_det : N);
+    const float *hb = kHist ? g_hist + (size_t)lane * 2 * N + kl : (kTaps ? g_hist + (size_t)lane * 2 * n_det : nullptr);
+    const float *pH = kCot ? hb + (size_t)(T > 5 ? T - 5 : 0) * hstride : nullptr;
     const char *pS = tb + (size_t)(T > 5 ? T - 5 : 0) * stride;      // row of step - 4 in the interval of `step`
     const char *pE = tb + (size_t)(T > 6 ? T - 6 : 0) * stride;      // row of step - 5
     const char *pC = tb + (size_t)(T > 9 ? T - 9 : 0) * stride;      // row of step - 8
@@ -716,6 +794,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         sl_ = tape_fp_bits(__builtin_amdgcn_raw_buffer_load_b96(rs_, off_sl, 0, 0));     \
         sr_ = tape_fp_bits(__builtin_amdgcn_raw_buffer_load_b96(rs_, off_sr, 0, 0));     \
         if (kHist) gh_ = v2f{(hp_)[0], (hp_)[N]};                                        \
+        if (kTaps) { if (dslot >= 0) gh_ = v2f{(hp_)[dslot], (hp_)[n_det + dslot]}; }    \
     }
 #define DHTS_LOAD_E(rb_, c_, ea_, eb_, ix_)                                              \
     if (t < (c_)) {                                                                      \
@@ -769,7 +848,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         if (kSched) gs_run -= 2 * (size_t)L;                                             \
         if (vk) {                                                                        \
             g = (c1v + C2[(R) * P + k + 1]) + C0[(R) * P + k + 1];                       \
-            if (kHist) g += gh_cur;                /* the cotangent of the state after step s, if the loss looks at it */ \
+            if (kCot) g += gh_cur;                 /* the cotangent of the state after step s, if the loss looks at it */ \
             n_fin += (isfinite(g.x) && isfinite(g.y)) ? 1 : 0;                           \
             const v2f c0 = pk_dot(d0lo, d0hi, g), c2v = pk_dot(d2lo, d2hi, g);           \
             c1v = pk_dot(d1lo, d1hi, g);                                                 \
@@ -786,14 +865,14 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 }                                                                        \
             }                                                                            \
             if (!(CL) || (s_) >= 1) DHTS_BLOCKS((s_) - 1, R, sl_, sr_)                   \
-            if (kHist) gh_cur = gh_;               /* of step s - 1: the set is refilled below */ \
+            if (kCot) gh_cur = gh_;                /* of step s - 1: the set is refilled below */ \
         }                                                                                \
         if (!(CL) || (s_) >= 2) DHTS_SCATTER((s_) - 2, Q, ec_, ea_, eb_, ix_);           \
         ec_ = cq_;                                                                       \
         DHTS_LOAD_E(pE, ec_, ea_, eb_, ix_);                                             \
         DHTS_LOAD_CNT(pC, cq_);                                                          \
         DHTS_LOAD_S(pS, pH, sl_, sr_, gh_);                                              \
-        if (kHist) pH -= (!(CL) || (s_) > 4) ? hstride : 0;                              \
+        if (kCot) pH -= (!(CL) || (s_) > 4) ? hstride : 0;                               \
         pS -= (!(CL) || (s_) > 4) ? stride : 0;                                          \
         pE -= (!(CL) || (s_) > 5) ? stride : 0;                                          \
         pC -= (!(CL) || (s_) > 8) ? stride : 0;                                          \
@@ -831,7 +910,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     DHTS_LOAD_CNT(DHTS_ROW(T - 8), cqB);
     lds_only_barrier();
     if (vk) DHTS_BLOCKS(T - 1, 0, slA, srA)
-    if (kHist) gh_cur = ghA;                             // of step T - 1
+    if (kCot) gh_cur = ghA;                              // of step T - 1
     DHTS_LOAD_S(DHTS_ROW(T - 4), DHTS_HROW(T - 4), slA, srA, ghA);
     lds_only_barrier();                                  // (the first interval scatters step T - 3 into the copy these blocks were read from)
 #undef DHTS_HROW
@@ -1100,11 +1179,15 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 // Reverse sweep over the rollout tape, any lane length (lanes above 1024 cells, single cells), per-step cotangents (g_hist) or not.
 // grid = L workgroups of `blockDim.x` threads (multiple of 64).  Dynamic LDS: 6 planes of (N + 2) floats | u16 SLOT[N + 1].
 // kSched: `g_ghost` is [T][L][2][2]: every step's boundary addend is stored instead of summed.
-template <bool kSched = false>
+// kTaps: `g_hist` is g_taps [T][L][2][n_det]: in front of every step thread j adds column j to the cotangent of cell det[j] in LDS (an entry
+// outside [0, N) is skipped before it forms an address), beside the slot clearing, two barriers ahead of the loop that reads the cells:
+// the same float32 sum as gr += gh[k] with a dense g_hist.  What lanes of 1026 .. 2048 cells take with detectors, as with a history.
+template <bool kSched = false, bool kTaps = false>
 __global__ __launch_bounds__(512) void macro_rollout_bwd_kernel(
     int L, int N, int T, double cc, const float4 *__restrict__ tape,
     const float *__restrict__ g_r_in, const float *__restrict__ g_y_in, const float *__restrict__ g_hist,
-    float *__restrict__ g_r_out, float *__restrict__ g_y_out, double *__restrict__ g_ghost, dhts_error *err) {
+    float *__restrict__ g_r_out, float *__restrict__ g_y_out, double *__restrict__ g_ghost, dhts_error *err,
+    const int32_t *__restrict__ det, int n_det) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = blockIdx.x;
     const int t = threadIdx.x;
@@ -1128,7 +1211,14 @@ __global__ __launch_bounds__(512) void macro_rollout_bwd_kernel(
         unsigned short *SLOT = reinterpret_cast<unsigned short *>(xbase);
         for (int step = T - 1; step >= 0; --step) {
             const float4 *row = tape + ((size_t)step * L + lane) * geo.row_f4;
-            const float *gh = g_hist ? g_hist + ((size_t)step * L + lane) * 2 * N : nullptr;
+            const float *gh = (!kTaps && g_hist) ? g_hist + ((size_t)step * L + lane) * 2 * N : nullptr;
+            if constexpr (kTaps) {
+                const float *gt = g_hist + ((size_t)step * L + lane) * 2 * n_det;
+                for (int j = t; j < n_det; j += B) {
+                    const unsigned dc = (unsigned)det[j];
+                    if (dc < (unsigned)N) { Gr[dc + 1] += gt[j]; Gy[dc + 1] += gt[n_det + j]; }
+                }
+            }
             tape_clear_slots(N, SLOT, t, B);
             __syncthreads();
             tape_fill_slots(row, geo, N, SLOT, t, B);
@@ -1307,10 +1397,12 @@ struct MacroPlan {
     int G;                // traffic lanes per workgroup (the pair kernel; 1 otherwise)
     size_t lds_fwd;       // two-phase kernels
     int bwd, bwd_block;   // reverse kernel and its threads per lane
-    bool bwd_full;        // fast: N = block (128 .. 512, no per-step cotangents); fast2: N = 2 x block
+    bool bwd_full;        // fast: N = block (128 .. 512, no dense per-step cotangents); fast2: N = 2 x block
     size_t lds_bwd;
 };
-static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, bool want_tape) {
+// taps: the detector form (dhts_macro_rollout_fwd_taps / _bwd_taps): the plan of the same shape WITHOUT a history, except that lanes of
+// 1026 .. 2048 cells take the general reverse sweep (the two-cells-per-thread kernel carries no per-step cotangents), as with a history
+static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, bool want_tape, bool taps = false) {
     MacroPlan pl = {};
     const int N = d->n_cells;
     pl.hist = want_hist; pl.tape = want_tape; pl.G = 1;
@@ -1339,7 +1431,7 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
         pl.bwd_block = N <= 64 ? 64 : (N <= 128 ? 128 : (N <= 256 ? 256 : (N <= 512 ? 512 : 1024)));
         pl.bwd_full = !want_hist && N == pl.bwd_block && N >= 128 && N <= 512;
         pl.lds_bwd = bwd_fast_lds_bytes(pl.bwd_block);
-    } else if (N > 1025 && N <= 2048 && T > 0 && T < (1 << 20) - 1 && !want_hist) {
+    } else if (N > 1025 && N <= 2048 && T > 0 && T < (1 << 20) - 1 && !want_hist && !taps) {
         // the two-cells-per-thread sweep (1024 threads): lanes of 1026 .. 2048 cells without per-step cotangents (the step tag has 20 bits)
         pl.bwd = kMacroBwdFast2;
         pl.bwd_block = 1024;
@@ -1355,19 +1447,41 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
 
 // the two-phase kernels (the caller has checked its arguments); sched: `ghost` is a boundary schedule [T][L][2][4] (the kSched
 // instantiations, picked by the same plan fields; they stand behind the constant-boundary ones in the code object)
+// det != NULL: the detector form (the kTaps instantiations, behind all others; `hist` is NULL then)
 static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int T,
                              const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                              float *r_out, float *y_out, float *u_out, float *ueq_out,
-                             float *tape, float *hist, dhts_error *err, void *stream, bool sched = false) {
+                             float *tape, float *hist, dhts_error *err, void *stream, bool sched = false,
+                             const int32_t *det = nullptr, int n_det = 0, float *taps = nullptr) {
     const int N = d->n_cells;
     float4 *tp = reinterpret_cast<float4 *>(tape);
     bool lds_ok = true;
-    if (sched && pl.fwd == kMacroFwdLane) {
+    if (det && pl.fwd == kMacroFwdLane) {
+        pick<0, 1>(sched, [&](auto sc) {
+            pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
+                constexpr int kV = decltype(v)::value;
+                lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0, decltype(sc)::value != 0, true>, d->n_lanes,
+                                    64 * pl.W, pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost,
+                                    r_out, y_out, u_out, ueq_out, tp, hist, err, det, n_det, taps);
+            });
+        });
+    } else if (det) {
+        pick<0, 1>(sched, [&](auto sc) {
+            pick<4, 2, 1>(pl.G, [&](auto g) {
+                pick<0, 1>(pl.tape, [&](auto tp_) {
+                    constexpr int kG = decltype(g)::value;
+                    lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0, decltype(sc)::value != 0, true>, d->n_lanes / kG,
+                                        64 * kG * (N / 128), pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq,
+                                        ghost, r_out, y_out, u_out, ueq_out, tp, err, dhts_fwd_rotate, det, n_det, taps);
+                });
+            });
+        });
+    } else if (sched && pl.fwd == kMacroFwdLane) {
         pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
             constexpr int kV = decltype(v)::value;
             lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0, true>, d->n_lanes, 64 * pl.W, pl.lds_fwd,
                                 kLdsDefault, stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out,
-                                ueq_out, tp, hist, err);
+                                ueq_out, tp, hist, err, det, n_det, taps);
         });
     } else if (sched) {
         pick<4, 2, 1>(pl.G, [&](auto g) {
@@ -1375,7 +1489,7 @@ static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int 
                 constexpr int kG = decltype(g)::value;
                 lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0, true>, d->n_lanes / kG, 64 * kG * (N / 128),
                                     pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out,
-                                    u_out, ueq_out, tp, err, dhts_fwd_rotate);
+                                    u_out, ueq_out, tp, err, dhts_fwd_rotate, det, n_det, taps);
             });
         });
     } else if (pl.fwd == kMacroFwdLane) {
@@ -1384,7 +1498,7 @@ static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int 
             constexpr int kV = decltype(v)::value;
             lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0>, d->n_lanes, 64 * pl.W, pl.lds_fwd, kLdsDefault,
                                 stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tp,
-                                hist, err);
+                                hist, err, det, n_det, taps);
         });
     } else {
         // the pair kernel: a thread owns two adjacent cells and their right interfaces (macro_fwd_pairs.inc)
@@ -1393,18 +1507,19 @@ static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int 
                 constexpr int kG = decltype(g)::value;
                 lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0>, d->n_lanes / kG, 64 * kG * (N / 128), pl.lds_fwd,
                                     kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out,
-                                    ueq_out, tp, err, dhts_fwd_rotate);
+                                    ueq_out, tp, err, dhts_fwd_rotate, det, n_det, taps);
             });
         });
     }
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
-template <bool kIface, bool kSched = false>
+template <bool kIface, bool kSched = false, bool kTaps = false>
 static int macro_fwd_launch(const dhts_macro_desc *d, int T,
                             const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                             float *r_out, float *y_out, float *u_out, float *ueq_out,
-                            float *tape, float *hist, dhts_error *err, void *stream) {
+                            float *tape, float *hist, dhts_error *err, void *stream,
+                            const int32_t *det = nullptr, int n_det = 0, float *taps = nullptr) {
     if (!macro_desc_ok(d) || T < 0 || !r || !y || !u || !ueq || !ghost || !r_out || !y_out || !u_out || !ueq_out)
         return DHTS_E_INVALID;
     const int N = d->n_cells;
@@ -1422,8 +1537,8 @@ static int macro_fwd_launch(const dhts_macro_desc *d, int T,
     int p = 1;
     while ((N + (64 * p - 1) - 1) / (64 * p - 1) > W) ++p;
     W = (N + (64 * p - 1) - 1) / (64 * p - 1);
-    if (!launch_lds(macro_rollout_fwd_kernel<kIface, kSched>, d->n_lanes, 64 * W, lds, kLdsDefault, stream, d->n_lanes, N, T, p, d->dt, d->dx, d->u_max,
-                    r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float4 *>(tape), hist, err))
+    if (!launch_lds(macro_rollout_fwd_kernel<kIface, kSched, kTaps>, d->n_lanes, 64 * W, lds, kLdsDefault, stream, d->n_lanes, N, T, p, d->dt, d->dx,
+                    d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float4 *>(tape), hist, err, det, n_det, taps))
         return DHTS_E_LAUNCH;
     return launch_status();
 }
@@ -1440,23 +1555,40 @@ static int macro_blocks_bwd_launch(const dhts_macro_desc *d, int T, const float 
     return launch_status();
 }
 // sched: g_ghost is the per-step boundary cotangent [T][L][2][2] (the kSched instantiations, behind the others in the code object)
+// det != NULL: the detector form: g_hist is g_taps [T][L][2][n_det] (the kTaps instantiations, behind all others)
 static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float *tape,
                                     const float *g_r, const float *g_y, const float *g_hist,
-                                    float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream, bool sched = false) {
+                                    float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream, bool sched = false,
+                                    const int32_t *det = nullptr, int n_det = 0) {
     if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out || (sched && !g_ghost)) return DHTS_E_INVALID;
-    const MacroPlan pl = macro_plan(d, T, g_hist != nullptr, tape != nullptr);
+    const MacroPlan pl = macro_plan(d, T, g_hist != nullptr && !det, tape != nullptr, det != nullptr);
     const int N = d->n_cells, B = pl.bwd_block;
     const float4 *tp = reinterpret_cast<const float4 *>(tape);
     const double cc = d->dt / d->dx;
     if (pl.lds_bwd > 160 * 1024) return DHTS_E_INVALID;
     bool lds_ok = true;
-    if (sched) {
+    if (det) {
+        pick<0, 1>(sched, [&](auto sc) {
+            constexpr bool kS = decltype(sc)::value != 0;
+            if (pl.bwd == kMacroBwdFast) {
+                // <kB, kFull> as 10 kB + 2 kFull
+                pick<5120, 5122, 2560, 2562, 1280, 1282, 640, 10240>(10 * B + (pl.bwd_full ? 2 : 0), [&](auto v) {
+                    constexpr int kV = decltype(v)::value;
+                    lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, false, kV % 10 == 2, kS, true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault,
+                                        stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
+                });
+            } else {
+                lds_ok = launch_lds(macro_rollout_bwd_kernel<kS, true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r,
+                                    g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
+            }
+        });
+    } else if (sched) {
         if (pl.bwd == kMacroBwdFast) {
             pick<10242, 5120, 5122, 5121, 2560, 2562, 2561, 1280, 1282, 1281, 640, 642, 641, 10241, 10240>(
                 10 * B + (pl.hist ? 1 : (pl.bwd_full ? 2 : 0)), [&](auto v) {
                     constexpr int kV = decltype(v)::value;
                     lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, kV % 10 == 1, kV % 10 == 2, true>, d->n_lanes, B, pl.lds_bwd,
-                                        kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err);
+                                        kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
                 });
         } else if (pl.bwd == kMacroBwdFast2) {
             pick<0, 1>(pl.bwd_full, [&](auto full) {
@@ -1465,7 +1597,7 @@ static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float
             });
         } else {
             lds_ok = launch_lds(macro_rollout_bwd_kernel<true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y,
-                                g_hist, g_r_out, g_y_out, g_ghost, err);
+                                g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
         }
     } else if (pl.bwd == kMacroBwdFast) {
         // <kB, kHist, kFull> as 10 kB + (0 plain, 1 kHist, 2 kFull).  The list holds every instantiation the library has always had, in
@@ -1474,7 +1606,7 @@ static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float
             10 * B + (pl.hist ? 1 : (pl.bwd_full ? 2 : 0)), [&](auto v) {
                 constexpr int kV = decltype(v)::value;
                 lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, kV % 10 == 1, kV % 10 == 2>, d->n_lanes, B, pl.lds_bwd, kLdsDefault,
-                                    stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err);
+                                    stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
             });
     } else if (pl.bwd == kMacroBwdFast2) {
         pick<0, 1>(pl.bwd_full, [&](auto full) {
@@ -1483,7 +1615,7 @@ static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float
         });
     } else {
         lds_ok = launch_lds(macro_rollout_bwd_kernel<false>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist,
-                            g_r_out, g_y_out, g_ghost, err);
+                            g_r_out, g_y_out, g_ghost, err, det, n_det);
     }
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
@@ -1581,6 +1713,48 @@ int dhts_macro_rollout_bwd_sched(const dhts_macro_desc *d, int T, const float *t
                                  float *g_r_out, float *g_y_out, double *g_ghost_sched, dhts_error *err, void *stream) {
     if (!g_ghost_sched) return DHTS_E_INVALID;
     return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost_sched, err, stream, true);
+}
+// the rollout with detector taps instead of a history (constant boundary cells or a schedule): the plan of the same shape without a
+// history, the kTaps instantiation of the kernel it names
+static inline bool macro_taps_ok(const dhts_macro_desc *d, const int32_t *det, int n_det) {
+    return macro_desc_ok(d) && det && n_det >= 1 && n_det <= d->n_cells;
+}
+int dhts_macro_rollout_fwd_taps(const dhts_macro_desc *d, int T,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                float *r_out, float *y_out, float *u_out, float *ueq_out, float *tape,
+                                const int32_t *det, int n_det, float *taps, dhts_error *err, void *stream) {
+    if (!macro_taps_ok(d, det, n_det) || !taps || T < 0 || !r || !y || !u || !ueq || !ghost || !r_out || !y_out || !u_out || !ueq_out)
+        return DHTS_E_INVALID;
+    if (T == 0) {       // no step, no row of taps, of the tape or of a schedule: the state comes back as it went in
+        const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
+        const float *src[4] = {r, y, u, ueq};
+        float *dst[4] = {r_out, y_out, u_out, ueq_out};
+        for (int k = 0; k < 4; ++k)
+            if (dst[k] != src[k] && hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+                return DHTS_E_LAUNCH;
+        return DHTS_OK;
+    }
+    const MacroPlan pl = macro_plan(d, T, false, tape != nullptr, true);
+    if (pl.fwd == kMacroFwdOnePhase) {
+        if (ghost_is_sched)
+            return macro_fwd_launch<true, true, true>(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, nullptr, err, stream, det, n_det, taps);
+        return macro_fwd_launch<true, false, true>(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, nullptr, err, stream, det, n_det, taps);
+    }
+    return macro_fwd2_launch(pl, d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, nullptr, err, stream, ghost_is_sched != 0, det,
+                             n_det, taps);
+}
+int dhts_macro_rollout_bwd_taps(const dhts_macro_desc *d, int T, const float *tape, const float *g_r, const float *g_y,
+                                const int32_t *det, int n_det, const float *g_taps,
+                                float *g_r_out, float *g_y_out, double *g_ghost, int ghost_is_sched, dhts_error *err, void *stream) {
+    if (!macro_taps_ok(d, det, n_det) || !g_taps) return DHTS_E_INVALID;
+    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_taps, g_r_out, g_y_out, g_ghost, err, stream, ghost_is_sched != 0, det, n_det);
+}
+int dhts_macro_taps_plan(const dhts_macro_desc *d, int T, int n_det, int32_t plan[8]) {
+    if (!macro_desc_ok(d) || T < 0 || !plan || n_det < 1 || n_det > d->n_cells) return DHTS_E_INVALID;
+    const MacroPlan pl = macro_plan(d, T, false, true, true);
+    plan[0] = pl.fwd; plan[1] = pl.W; plan[2] = pl.p; plan[3] = pl.dense ? 1 : 0;
+    plan[4] = pl.bwd; plan[5] = pl.bwd_block; plan[6] = 0; plan[7] = pl.G;
+    return DHTS_OK;
 }
 // which kernel instantiations dhts_macro_rollout_fwd / _bwd (and their _sched forms) launch for this shape: the plan the launches read
 int dhts_macro_rollout_plan(const dhts_macro_desc *d, int T, int want_hist, int32_t plan[8]) {

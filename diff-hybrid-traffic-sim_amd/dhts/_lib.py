@@ -92,6 +92,9 @@ SIGNATURES = {
     "dhts_macro_rollout_fwd_sched": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 13),
     "dhts_macro_rollout_bwd_sched": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 9),
     "dhts_macro_rollout_plan": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
+    "dhts_macro_rollout_fwd_taps": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 6 + [C.c_int] + [_P] * 3),
+    "dhts_macro_rollout_bwd_taps": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 4 + [C.c_int] + [_P] * 4 + [C.c_int] + [_P] * 2),
+    "dhts_macro_taps_plan": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
     "dhts_macro_tape_expand": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 3),
     "dhts_macro_step_fwd": (C.c_int, [C.POINTER(MacroDesc)] + [_P] * 12),
     "dhts_macro_step_bwd": (C.c_int, [C.POINTER(MacroDesc)] + [_P] * 8),

@@ -197,12 +197,88 @@ def macro_rollout_plan(desc, T, want_hist=False):
     return dict(zip(keys, list(plan)))
 
 
+def _det_i32(det, N):
+    if not isinstance(det, torch.Tensor) or det.dtype != torch.int32 or not det.is_cuda or det.dim() != 1:
+        raise ValueError("det must be a one-dimensional int32 CUDA tensor")
+    if not 1 <= det.numel() <= N:
+        raise ValueError("det must hold 1..%d cell indices (got %d)" % (N, det.numel()))
+    return det.contiguous()
+
+
+def macro_rollout_fwd_taps(desc, T, r, y, u, ueq, ghost, det, tape=None, err=None, out=None, taps=None):
+    """macro_rollout_fwd / _sched with detector taps instead of a history.  ghost [L][2][4], or a schedule [T][L][2][4]; det int32 CUDA
+    [D]: cell indices, strictly ascending, in [0, N) (not looked at here: include/dhts.h, index contract).  Returns
+    ((r, y, u, ueq) after T steps, taps [T][L][3][D] = (r, y, u) of cell det[j] after every step)."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
+        if tuple(t.shape) != (L, N):
+            raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
+    sched = ghost.dim() == 4
+    if tuple(ghost.shape) != ((T, L, 2, 4) if sched else (L, 2, 4)):
+        raise ValueError("ghost must have shape (%d, 2, 4) or (%d, %d, 2, 4)" % (L, T, L))
+    det = _det_i32(det, N)
+    D = det.numel()
+    r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, "ghost")))
+    if sched and T == 0:        # an empty tensor has no address; the entry point wants one and reads no row
+        ghost = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
+    if taps is None:
+        taps = torch.empty(max(T, 1), L, 3, D, dtype=torch.float32, device=r.device)[:T]
+    elif tuple(taps.shape) != (T, L, 3, D) or taps.dtype != torch.float32 or not taps.is_cuda or not taps.is_contiguous():
+        raise ValueError("taps must be a contiguous float32 CUDA tensor of shape (%d, %d, 3, %d)" % (T, L, D))
+    if out is None:
+        out = tuple(torch.empty_like(r) for _ in range(4))
+    check(_lib.lib().dhts_macro_rollout_fwd_taps(C.byref(desc), T, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(tape),
+                                                 _ptr(det), D, C.c_void_p(taps.data_ptr() or det.data_ptr()),      # (T = 0: no address, no row)
+                                                 _ptr(err), _stream()),
+          "dhts_macro_rollout_fwd_taps")
+    return out, taps
+
+
+def macro_rollout_bwd_taps(desc, T, tape, g_r, g_y, det, g_taps, sched=False, err=None, out=None):
+    """macro_rollout_bwd / _sched with g_taps [T][L][2][D], the cotangent of (r, y) of the cells det[j] after every step.  Returns
+    (g_r0, g_y0, g_ghost): [L][2][2] float64, or the per-step [T][L][2][2] when sched."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    det = _det_i32(det, N)
+    D = det.numel()
+    if tuple(g_taps.shape) != (T, L, 2, D):
+        raise ValueError("g_taps must have shape (%d, %d, 2, %d)" % (T, L, D))
+    g_r, g_y, g_taps = _f32c(g_r, "g_r"), _f32c(g_y, "g_y"), _f32c(g_taps, "g_taps")
+    if tuple(g_r.shape) != (L, N) or tuple(g_y.shape) != (L, N):
+        raise ValueError("g_r and g_y must have shape (%d, %d)" % (L, N))
+    if out is None:
+        out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    if sched:
+        g_ghost = torch.empty(max(T, 1), L, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
+    else:
+        g_ghost = torch.zeros(L, 2, 2, dtype=torch.float64, device=g_r.device)
+    check(_lib.lib().dhts_macro_rollout_bwd_taps(C.byref(desc), T, _ptr(tape), _ptr(g_r), _ptr(g_y), _ptr(det), D,
+                                                 C.c_void_p(g_taps.data_ptr() or det.data_ptr()), _ptr(out[0]), _ptr(out[1]),
+                                                 _ptr(g_ghost), int(bool(sched)), _ptr(err), _stream()), "dhts_macro_rollout_bwd_taps")
+    return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
+
+
+def macro_taps_plan(desc, T, n_det):
+    """Which kernel instantiations dhts_macro_rollout_fwd_taps / _bwd_taps launch for this shape: the fields of macro_rollout_plan."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_macro_taps_plan(C.byref(desc), int(T), int(n_det), C.byref(plan)), "dhts_macro_taps_plan")
+    keys = ("fwd_kernel", "fwd_waves", "fwd_passes", "fwd_full_lane", "bwd_pipelined", "bwd_block", "hist", "fwd_lanes_per_group")
+    return dict(zip(keys, list(plan)))
+
+
 def macro_tape_expand(desc, T, tape):
     """The reference's blocks dqs (dmacro_lane.py:56) of all T steps from a rollout tape: float32 [T][L][3][Np][4]."""
     Np = _lib.lib().dhts_padded(desc.n_cells)
     dqs = torch.empty(int(T), desc.n_lanes, 3, Np, 4, dtype=torch.float32, device=tape.device)
     check(_lib.lib().dhts_macro_tape_expand(C.byref(desc), int(T), _ptr(tape), _ptr(dqs), _stream()), "dhts_macro_tape_expand")
     return dqs
+
+
+def _ghost_ry_to_ru(g_ghost, gr, gu, gq, um):
+    """ghost (r, y) cotangents (sums over the steps, or per step) -> ghost (r, u) leaves, in double (the sum is ill-conditioned)."""
+    rr, uu, qq = gr.double(), gu.double(), gq.double()
+    dueq = torch.where(rr < 0, torch.zeros_like(rr), -um * 0.5 / torch.sqrt(rr.clamp_min(0) + EPS))
+    return (g_ghost[..., 0] + g_ghost[..., 1] * ((uu - qq) - rr * dueq)).float(), (g_ghost[..., 1] * rr).float()
 
 
 class MacroRollout(torch.autograd.Function):
@@ -257,7 +333,7 @@ class MacroRollout(torch.autograd.Function):
         if g_uT is not None:
             macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
         gh = None
-        if ctx.want_hist and g_hist is not None:
+        if ctx.want_hist and g_hist is not None and g_hist.numel():      # (T = 0: no row, and an empty tensor has no address)
             # per-step taps: (r, y) cotangents directly, u cotangent through the float32 glue of that step's state
             hr, hy = hist[:, :, 0].contiguous(), hist[:, :, 1].contiguous()
             ghr, ghy = g_hist[:, :, 0].contiguous().clone(), g_hist[:, :, 1].contiguous().clone()
@@ -269,17 +345,109 @@ class MacroRollout(torch.autograd.Function):
         if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
             raise_on_fault(err)
         g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
-        # ghost (r, y) cotangents (sums over the steps, or per step) -> ghost (r, u) leaves, in double (the sum is ill-conditioned)
-        rr, uu, qq = gr.double(), gu.double(), gq.double()
-        dueq = torch.where(rr < 0, torch.zeros_like(rr), -um * 0.5 / torch.sqrt(rr.clamp_min(0) + EPS))
-        g_gr = (g_ghost[..., 0] + g_ghost[..., 1] * ((uu - qq) - rr * dueq)).float()
-        g_gu = (g_ghost[..., 1] * rr).float()
+        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um)
         return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None
 
 
-def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True):
-    return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist,
-                              check_faults)
+class MacroRolloutTaps(torch.autograd.Function):
+    """MacroRollout with detector readings instead of a history: (...) -> (rT, yT, uT, qT, readings [T][L][3][D]), readings[t][l][:][j] =
+    (r, y, u) of cell det[j] after step t -- get_state_vector read at chosen cells after every RoadNetwork.forward, as the inverse
+    examples do.  Nothing of size [T][L][N] is written, saved or read back."""
+
+    @staticmethod
+    def forward(ctx, r0, u0, ghost_r, ghost_u, det, T, dt, dx, u_max, check_faults=True):
+        L, N = r0.shape
+        sched = ghost_r.dim() == 3
+        if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
+            raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
+        want = (int(T), L, 2) if sched else (L, 2)
+        if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
+            raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
+        desc = macro_desc(L, N, dt, dx, u_max)
+        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+        gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
+        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
+        gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
+        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4], or [T][L][2][4]
+        need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
+        tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
+        err = new_error_record(r0.device)
+        (rT, yT, uT, qT), readings = macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
+        if check_faults:
+            raise_on_fault(err)
+        ctx.sched = sched
+        ctx.desc, ctx.T, ctx.u_max, ctx.tape, ctx.check_faults = desc, T, u_max, tape, check_faults
+        ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, readings, det)
+        ctx.mark_non_differentiable(qT)
+        return rT, yT, uT, qT, readings
+
+    @staticmethod
+    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_read):
+        r0, u0, gr, gu, gq, rT, yT, readings, det = ctx.saved_tensors
+        desc, T, um = ctx.desc, ctx.T, ctx.u_max
+        L, N = desc.n_lanes, desc.n_cells
+        dev = r0.device
+        g_r = g_rT.contiguous().clone() if g_rT is not None else torch.zeros(L, N, device=dev)
+        g_y = g_yT.contiguous().clone() if g_yT is not None else torch.zeros(L, N, device=dev)
+        if g_uT is not None:
+            macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
+        err = new_error_record(dev)
+        if g_read is not None and g_read.numel():
+            # (r, y) cotangents directly, the u cotangent through the float32 glue of the readings' own (r, y): T L D elements
+            tr, ty = readings[:, :, 0].contiguous(), readings[:, :, 1].contiguous()
+            gtr, gty = g_read[:, :, 0].contiguous().clone(), g_read[:, :, 1].contiguous().clone()
+            macro_u_tap_bwd(tr, ty, g_read[:, :, 2].contiguous(), gtr, gty, um)
+            gt = torch.stack([gtr, gty], dim=2).contiguous()                   # [T][L][2][D]
+            g_r0, g_y0, g_ghost = macro_rollout_bwd_taps(desc, T, ctx.tape, g_r, g_y, det, gt, sched=ctx.sched, err=err)
+        else:                            # no readings to look at (T = 0): the plain sweep over the same tape
+            bwd = macro_rollout_bwd_sched if ctx.sched else macro_rollout_bwd
+            g_r0, g_y0, g_ghost = bwd(desc, T, ctx.tape, g_r, g_y, err=err)
+        if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
+            raise_on_fault(err)
+        g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
+        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um)
+        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None
+
+
+def _detector_indices(detectors, N, device):
+    """dhts.macro_rollout's `detectors` -> int32 CUDA [D].  A sequence of ints or a CPU integer tensor is validated (ValueError) before
+    anything touches a device; a CUDA int32 tensor is used as it is."""
+    if isinstance(detectors, torch.Tensor) and detectors.is_cuda:
+        if detectors.dtype != torch.int32 or detectors.dim() != 1 or not 1 <= detectors.numel() <= N:
+            raise ValueError("a CUDA `detectors` must be a one-dimensional int32 tensor of 1..%d entries" % N)
+        return detectors.contiguous()
+    if isinstance(detectors, torch.Tensor):
+        if detectors.dim() != 1 or detectors.dtype.is_floating_point or detectors.dtype.is_complex or detectors.dtype == torch.bool:
+            raise ValueError("`detectors` must be a one-dimensional integer tensor")
+        cells = detectors.tolist()
+    else:
+        cells = list(detectors)
+        if any(isinstance(c, bool) or int(c) != c for c in cells):
+            raise ValueError("`detectors` must hold integers")
+        cells = [int(c) for c in cells]
+    if not cells:
+        raise ValueError("`detectors` is empty")
+    if cells[0] < 0 or cells[-1] >= N or any(a >= b for a, b in zip(cells, cells[1:])) or any(not 0 <= c < N for c in cells):
+        raise ValueError("`detectors` must be strictly ascending cell indices in [0, %d) (got %s)" % (N, cells))
+    return torch.tensor(cells, dtype=torch.int32, device=device)
+
+
+def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None):
+    """T fused differentiable steps of L straight ARZ lanes (MacroRollout): returns (rT, yT, uT, qT), with want_hist also hist [T][L][3][N].
+
+    detectors: cell indices at which the state is read after every step -- a sequence of ints or a CPU integer tensor (non-empty, strictly
+    ascending, in [0, N): checked, ValueError otherwise, then uploaded), or a CUDA int32 tensor, which is used as it is so that a graph
+    capture sees no upload and no synchronisation and which is therefore NOT validated: the kernels skip an index outside [0, N) (its
+    column of the readings stays unwritten) and never form an address from one.  Returns (rT, yT, uT, qT, readings) then, readings
+    [T][L][3][D] = (r, y, u) of cell detectors[j] after every step, differentiable in all three; no [T][L][N] history is written or
+    read.  Not together with want_hist (ValueError): a caller who wants every cell has the history."""
+    if detectors is None:
+        return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist,
+                                  check_faults)
+    if want_hist:
+        raise ValueError("want_hist and detectors exclude each other: the history holds every cell")
+    det = _detector_indices(detectors, int(r0.shape[-1]), r0.device)
+    return MacroRolloutTaps.apply(r0, u0, ghost_r, ghost_u, det, int(T), float(dt), float(dx), float(u_max), check_faults)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -4,8 +4,10 @@
 A lane starts in a known uniform free-flow state.  The truth is a smooth density pulse in the upstream boundary cell (a platoon
 arriving), the cell at its equilibrium speed; the downstream boundary cell stays at the initial state.  A few detectors downstream
 record the density after every step.  From those readings alone the [T] upstream density profile is recovered with Adam: the loss is
-on the state HISTORY (want_hist=True) and its gradient reaches every step's boundary cell through the per-step boundary cotangent of
-the fused rollout (dhts.macro_rollout with ghost_r, ghost_u of shape [T][L][2]).  Every trial solves n_lane independent problems at
+on the detector READINGS (dhts.macro_rollout with detectors=...: the state at those cells after every step, nothing of size
+[T][L][N]) and its gradient reaches every step's boundary cell through the per-step boundary cotangent of the fused rollout
+(ghost_r, ghost_u of shape [T][L][2]).  --readings history takes the readings out of the full state history (want_hist=True)
+instead: the same numbers, log line for log line, at the cost of the history.  Every trial solves n_lane independent problems at
 once.  What a detector at cell c can see of the profile ends c cells' travel time before the end of the horizon: the tail of the
 profile stays at its first guess.
 
@@ -39,6 +41,8 @@ def main():
     ap.add_argument("--n_detector", type=int, default=4)
     ap.add_argument("--lr", type=float, default=2e-2)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--readings", choices=("detectors", "history"), default="detectors",
+                    help="read the detectors through dhts.macro_rollout(detectors=...) or out of the full state history")
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
 
@@ -52,7 +56,14 @@ def main():
     os.makedirs(log_dir, exist_ok=True)
     # detectors in the first eighth of the lane: at free-flow speed the pulse covers about a cell per 30 steps (dx = 5, dt = 0.01)
     det = th.unique(th.linspace(0, max(N // 8, 1), args.n_detector, device=dev).long().clamp(0, N - 1))
+    det32 = det.to(th.int32)                                           # on the device already: used as it is, no upload per episode
     r_base = 0.2
+
+    def densities(gr, gu):
+        """[T][L][detectors]: the density at the detectors after every step."""
+        if args.readings == "detectors":
+            return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, detectors=det32)[4][:, :, 0].contiguous()
+        return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, want_hist=True)[4][:, :, 0][:, :, det]
 
     def u_eq(r):
         return um * (1.0 - th.sqrt(r + 1e-5))
@@ -71,16 +82,14 @@ def main():
         wid = (0.08 + 0.06 * th.rand(1, L, device=dev)) * T
         up_true = r_base + peak * th.exp(-((tt - mid) / wid) ** 2)     # [T][L]
         with th.no_grad():
-            out = dhts.macro_rollout(r0, u0, *schedule(up_true), T, dt, dx, um, want_hist=True)
-            obs = out[4][:, :, 0][:, :, det].clone()                   # [T][L][detectors]: the density readings
+            obs = densities(*schedule(up_true)).clone()                # the density readings
         up_est = th.full((T, L), r_base, device=dev, requires_grad=True)
         opt = th.optim.Adam([up_est], lr=args.lr)
         lines = []
         t0 = time.time()
         for ep in range(args.n_episode):
             gr, gu = schedule(up_est)
-            hist = dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, want_hist=True)[4]
-            loss = ((hist[:, :, 0][:, :, det] - obs) ** 2).sum()
+            loss = ((densities(gr, gu) - obs) ** 2).sum()
             err = ((up_est.detach() - up_true) ** 2).sum()
             opt.zero_grad(set_to_none=False)
             loss.backward()

@@ -232,6 +232,38 @@ int dhts_macro_rollout_bwd_sched(const dhts_macro_desc *d, int T, const float *t
  *   plan[7] traffic lanes per workgroup (the pair kernel: DHTS_OPT_MACRO_FWD_GROUP; 1 otherwise) */
 int dhts_macro_rollout_plan(const dhts_macro_desc *d, int T, int want_hist, int32_t plan[8]);
 
+/*
+ * The same rollout with DETECTOR TAPS: the state at a few chosen cells after every step, and its cotangent, without a history.
+ * Replaces get_state_vector read at chosen cells after every RoadNetwork.forward, as the inverse examples do with loop-detector
+ * readings (example/inverse/macro.py:34-68, _inverse.py:91-99), where hist / g_hist would move [T][L][N] planes for a handful of cells.
+ *   det    [n_det] int32, DEVICE memory, shared by all lanes: cell indices, strictly ascending, in [0, n_cells); 1 <= n_det <= n_cells.
+ *   taps   [T][L][3][n_det] float32 = (r, y, u) of cell det[j] after every step: exactly what hist[t][l][:][det[j]] would hold.  Plain
+ *          stores, no atomics; every element is written when T > 0 and the indices are valid; two runs give the same bits.
+ *   g_taps [T][L][2][n_det] float32 = cotangent of those (r, y); added to the cell's cotangent where and when g_hist is added, so that
+ *          g_r_out / g_y_out / g_ghost equal those of a g_hist that is zero outside the detector columns.
+ *   ghost / g_ghost: [L][2][4] / [L][2][2] DOUBLE (g_ghost may be NULL) when ghost_is_sched == 0 -- the semantics of
+ *          dhts_macro_rollout_fwd / _bwd --, the schedules [T][L][2][4] / [T][L][2][2] of the _sched pair when it is 1 (g_ghost required).
+ * There is no hist in this form (a caller who wants every cell has it in the calls above).  Tape format, dhts_macro_tape_bytes and the
+ * fault record are those of the calls above; T = 0 is accepted (no row is read or written, the state comes back as it went in).
+ * INDEX CONTRACT: the entry points cannot look at the contents of det without a synchronisation and do not; the kernels are safe by
+ * construction instead.  Every entry is compared against [0, n_cells) before any address, global or LDS, is formed from it; an entry
+ * outside matches no cell: its column of taps is not written and its column of g_taps is not read.  Entries that repeat or are out
+ * of order touch no memory outside the buffers either, but which of two equal entries a reverse sweep reads is then unspecified.
+ * NULL det / taps / g_taps, n_det outside 1 .. n_cells or a bad descriptor: DHTS_E_INVALID, nothing is dereferenced.
+ * dhts_macro_taps_plan has the fields of dhts_macro_rollout_plan (plan[6] = 0) and IS the plan of the same shape without a history --
+ * full lanes of 128 W cells stay on the pair kernel with the same lanes per workgroup, N = block keeps the full reverse instantiation --
+ * with one exception: lanes of 1026 .. 2048 cells take the general reverse sweep (plan[4] = 0), as they do with a history; the
+ * two-cells-per-thread kernel carries no per-step cotangents.
+ */
+int dhts_macro_rollout_fwd_taps(const dhts_macro_desc *d, int T,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                float *r_out, float *y_out, float *u_out, float *ueq_out, float *tape,
+                                const int32_t *det, int n_det, float *taps, dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_taps(const dhts_macro_desc *d, int T, const float *tape, const float *g_r, const float *g_y,
+                                const int32_t *det, int n_det, const float *g_taps,
+                                float *g_r_out, float *g_y_out, double *g_ghost, int ghost_is_sched, dhts_error *err, void *stream);
+int dhts_macro_taps_plan(const dhts_macro_desc *d, int T, int n_det, int32_t plan[8]);
+
 /* One step = the drop-in for a batch of dMacroForwardLayer.forward / .backward calls (T = 1 of the above;
  * tape is one step's worth).
  * A ghost cell of Python floats: the reference's Riemann solve reads a boundary cell that holds plain floats in double
