@@ -57,9 +57,9 @@ inline bool launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, size_t unask
 
 // Run-time value -> template argument: calls f(std::integral_constant<int, V>{}) for the V of the list that equals v (false: none
 // does).  A family's plan names the instantiation in ints; the launch picks it with this and writes its argument list once.
-// A list is also the set of instantiations the library holds, and its order (last entry first, inner picks before the next outer entry)
-// the order in which they stand in the code object: reordering one changes the library's device-code fingerprint (bench.py
-// library_code_sha16, profiles/issue_counters.json) though no kernel changes -- keep the lists as they are unless that is meant.
+// A list is also the set of instantiations the library holds: name what a plan can name and nothing else; a combination a kernel
+// rules out is left out with `if constexpr` in f.  Editing a list changes the library's device-code fingerprint (bench.py
+// library_code_sha16, profiles/issue_counters.json) even where no kernel changes, so the counter record is re-taken afterwards.
 template <int... Vs, class F>
 inline bool pick(int v, F &&f) {
     return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);

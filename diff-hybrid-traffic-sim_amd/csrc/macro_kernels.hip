@@ -1445,81 +1445,35 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
     return pl;
 }
 
-// the two-phase kernels (the caller has checked its arguments); sched: `ghost` is a boundary schedule [T][L][2][4] (the kSched
-// instantiations, picked by the same plan fields; they stand behind the constant-boundary ones in the code object)
-// det != NULL: the detector form (the kTaps instantiations, behind all others; `hist` is NULL then)
-static int macro_fwd2_launch(const MacroPlan &pl, const dhts_macro_desc *d, int T,
-                             const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
-                             float *r_out, float *y_out, float *u_out, float *ueq_out,
-                             float *tape, float *hist, dhts_error *err, void *stream, bool sched = false,
-                             const int32_t *det = nullptr, int n_det = 0, float *taps = nullptr) {
-    const int N = d->n_cells;
-    float4 *tp = reinterpret_cast<float4 *>(tape);
-    bool lds_ok = true;
-    if (det && pl.fwd == kMacroFwdLane) {
-        pick<0, 1>(sched, [&](auto sc) {
-            pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
-                constexpr int kV = decltype(v)::value;
-                lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0, decltype(sc)::value != 0, true>, d->n_lanes,
-                                    64 * pl.W, pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost,
-                                    r_out, y_out, u_out, ueq_out, tp, hist, err, det, n_det, taps);
-            });
-        });
-    } else if (det) {
-        pick<0, 1>(sched, [&](auto sc) {
-            pick<4, 2, 1>(pl.G, [&](auto g) {
-                pick<0, 1>(pl.tape, [&](auto tp_) {
-                    constexpr int kG = decltype(g)::value;
-                    lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0, decltype(sc)::value != 0, true>, d->n_lanes / kG,
-                                        64 * kG * (N / 128), pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq,
-                                        ghost, r_out, y_out, u_out, ueq_out, tp, err, dhts_fwd_rotate, det, n_det, taps);
-                });
-            });
-        });
-    } else if (sched && pl.fwd == kMacroFwdLane) {
-        pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
-            constexpr int kV = decltype(v)::value;
-            lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0, true>, d->n_lanes, 64 * pl.W, pl.lds_fwd,
-                                kLdsDefault, stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out,
-                                ueq_out, tp, hist, err, det, n_det, taps);
-        });
-    } else if (sched) {
-        pick<4, 2, 1>(pl.G, [&](auto g) {
-            pick<0, 1>(pl.tape, [&](auto tp_) {
-                constexpr int kG = decltype(g)::value;
-                lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0, true>, d->n_lanes / kG, 64 * kG * (N / 128),
-                                    pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out,
-                                    u_out, ueq_out, tp, err, dhts_fwd_rotate, det, n_det, taps);
-            });
-        });
-    } else if (pl.fwd == kMacroFwdLane) {
-        // <kP, kFull, kHist> as 10 kP + kFull (kHist = !kFull); kP = 0: the run-time pass count
-        pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
-            constexpr int kV = decltype(v)::value;
-            lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0>, d->n_lanes, 64 * pl.W, pl.lds_fwd, kLdsDefault,
-                                stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tp,
-                                hist, err, det, n_det, taps);
-        });
-    } else {
-        // the pair kernel: a thread owns two adjacent cells and their right interfaces (macro_fwd_pairs.inc)
-        pick<4, 2, 1>(pl.G, [&](auto g) {
-            pick<0, 1>(pl.tape, [&](auto tp_) {
-                constexpr int kG = decltype(g)::value;
-                lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0>, d->n_lanes / kG, 64 * kG * (N / 128), pl.lds_fwd,
-                                    kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out,
-                                    ueq_out, tp, err, dhts_fwd_rotate, det, n_det, taps);
-            });
-        });
-    }
-    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+// The form of a rollout call: what it takes besides the state, the boundary cells and the tape.  The six rollout entry points fill one
+// and hand it to macro_rollout_fwd_launch resp. macro_rollout_bwd_launch; kSched and kTaps of the kernels are picked from it like every
+// other template argument, so a further form is one more field here and one more pick there.
+struct MacroForm {
+    bool sched;           // the boundary cells are a schedule [T][L][2][4]; g_ghost is per step [T][L][2][2]
+    const int32_t *det;   // detector cells [n_det], NULL: none
+    int n_det;
+    float *hist, *taps;   // forward: the state history [T][L][3][N] (not with detectors) resp. the readings [T][L][3][n_det]
+    const float *g_cot;   // reverse: the per-step cotangents, g_hist [T][L][2][N] or with detectors g_taps [T][L][2][n_det]; NULL: none
+};
+
+// T == 0 of the _sched and _taps entry points: no step and no row of a schedule, of the tape or of the readings to address, so the state
+// comes back as it went in (what the constant-boundary rollout's kernel does with T = 0)
+static int macro_state_copy(const dhts_macro_desc *d, const float *r, const float *y, const float *u, const float *ueq,
+                            float *r_out, float *y_out, float *u_out, float *ueq_out, void *stream) {
+    const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
+    const float *src[4] = {r, y, u, ueq};
+    float *dst[4] = {r_out, y_out, u_out, ueq_out};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k] != src[k] && hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+            return DHTS_E_LAUNCH;
+    return DHTS_OK;
 }
 
-template <bool kIface, bool kSched = false, bool kTaps = false>
-static int macro_fwd_launch(const dhts_macro_desc *d, int T,
+// The one-phase kernel.  kIface = false is the single-step operator's form (dqs-layout tape), which has neither a schedule nor taps.
+static int macro_fwd_launch(bool iface, const dhts_macro_desc *d, int T,
                             const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                             float *r_out, float *y_out, float *u_out, float *ueq_out,
-                            float *tape, float *hist, dhts_error *err, void *stream,
-                            const int32_t *det = nullptr, int n_det = 0, float *taps = nullptr) {
+                            float *tape, const MacroForm &f, dhts_error *err, void *stream) {
     if (!macro_desc_ok(d) || T < 0 || !r || !y || !u || !ueq || !ghost || !r_out || !y_out || !u_out || !ueq_out)
         return DHTS_E_INVALID;
     const int N = d->n_cells;
@@ -1537,11 +1491,59 @@ static int macro_fwd_launch(const dhts_macro_desc *d, int T,
     int p = 1;
     while ((N + (64 * p - 1) - 1) / (64 * p - 1) > W) ++p;
     W = (N + (64 * p - 1) - 1) / (64 * p - 1);
-    if (!launch_lds(macro_rollout_fwd_kernel<kIface, kSched, kTaps>, d->n_lanes, 64 * W, lds, kLdsDefault, stream, d->n_lanes, N, T, p, d->dt, d->dx,
-                    d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float4 *>(tape), hist, err, det, n_det, taps))
-        return DHTS_E_LAUNCH;
-    return launch_status();
+    bool lds_ok = true;
+    pick<1, 0>(iface, [&](auto fc) {
+        pick<0, 1>(f.sched, [&](auto sc) {
+            pick<0, 1>(f.det != nullptr, [&](auto tp) {
+                constexpr bool kIface = decltype(fc)::value != 0, kS = decltype(sc)::value != 0, kT = decltype(tp)::value != 0;
+                if constexpr (kIface || (!kS && !kT))
+                    lds_ok = launch_lds(macro_rollout_fwd_kernel<kIface, kS, kT>, d->n_lanes, 64 * W, lds, kLdsDefault, stream, d->n_lanes, N, T, p,
+                                        d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out,
+                                        reinterpret_cast<float4 *>(tape), f.hist, err, f.det, f.n_det, f.taps);
+            });
+        });
+    });
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
+
+// The forward rollout of every form: the plan names the kernel and its shape arguments, the form its kSched and kTaps.
+static int macro_rollout_fwd_launch(const dhts_macro_desc *d, int T,
+                                    const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
+                                    float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                    float *tape, const MacroForm &f, dhts_error *err, void *stream) {
+    const MacroPlan pl = macro_plan(d, T, f.hist != nullptr, tape != nullptr, f.det != nullptr);
+    if (pl.fwd == kMacroFwdOnePhase) return macro_fwd_launch(true, d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, f, err, stream);
+    const int N = d->n_cells;
+    float4 *tp = reinterpret_cast<float4 *>(tape);
+    bool lds_ok = true;
+    pick<0, 1>(f.sched, [&](auto sc) {
+        pick<0, 1>(f.det != nullptr, [&](auto tap) {
+            constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
+            if (pl.fwd == kMacroFwdLane) {
+                // <kP, kFull, kHist> as 10 kP + kFull (kHist = !kFull, with detectors too: `hist` is NULL then); kP = 0: the run-time
+                // pass count
+                pick<0, 20, 10, 21, 11>(10 * (pl.p <= 2 ? pl.p : 0) + (pl.dense ? 1 : 0), [&](auto v) {
+                    constexpr int kV = decltype(v)::value;
+                    lds_ok = launch_lds(macro_rollout_fwd2_kernel<kV / 10, kV % 10 != 0, kV % 10 == 0, kS, kT>, d->n_lanes, 64 * pl.W, pl.lds_fwd,
+                                        kLdsDefault, stream, d->n_lanes, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out,
+                                        ueq_out, tp, f.hist, err, f.det, f.n_det, f.taps);
+                });
+            } else {
+                // the pair kernel: a thread owns two adjacent cells and their right interfaces (macro_fwd_pairs.inc)
+                pick<4, 2, 1>(pl.G, [&](auto g) {
+                    pick<0, 1>(pl.tape, [&](auto tp_) {
+                        constexpr int kG = decltype(g)::value;
+                        lds_ok = launch_lds(macro_rollout_fwd3_kernel<kG, decltype(tp_)::value != 0, kS, kT>, d->n_lanes / kG, 64 * kG * (N / 128),
+                                            pl.lds_fwd, kLdsDefault, stream, d->n_lanes, N, T, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out,
+                                            y_out, u_out, ueq_out, tp, err, dhts_fwd_rotate, f.det, f.n_det, f.taps);
+                    });
+                });
+            }
+        });
+    });
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+
 static int macro_blocks_bwd_launch(const dhts_macro_desc *d, int T, const float *tape,
                                   const float *g_r, const float *g_y, const float *g_hist,
                                   float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
@@ -1554,69 +1556,44 @@ static int macro_blocks_bwd_launch(const dhts_macro_desc *d, int T, const float 
         return DHTS_E_LAUNCH;
     return launch_status();
 }
-// sched: g_ghost is the per-step boundary cotangent [T][L][2][2] (the kSched instantiations, behind the others in the code object)
-// det != NULL: the detector form: g_hist is g_taps [T][L][2][n_det] (the kTaps instantiations, behind all others)
-static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float *tape,
-                                    const float *g_r, const float *g_y, const float *g_hist,
-                                    float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream, bool sched = false,
-                                    const int32_t *det = nullptr, int n_det = 0) {
-    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out || (sched && !g_ghost)) return DHTS_E_INVALID;
-    const MacroPlan pl = macro_plan(d, T, g_hist != nullptr && !det, tape != nullptr, det != nullptr);
+
+// The reverse sweep of every form, as above.
+static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float *tape, const float *g_r, const float *g_y,
+                                    float *g_r_out, float *g_y_out, double *g_ghost, const MacroForm &f, dhts_error *err, void *stream) {
+    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out || (f.sched && !g_ghost)) return DHTS_E_INVALID;
+    const MacroPlan pl = macro_plan(d, T, f.g_cot != nullptr && !f.det, tape != nullptr, f.det != nullptr);
     const int N = d->n_cells, B = pl.bwd_block;
     const float4 *tp = reinterpret_cast<const float4 *>(tape);
     const double cc = d->dt / d->dx;
     if (pl.lds_bwd > 160 * 1024) return DHTS_E_INVALID;
     bool lds_ok = true;
-    if (det) {
-        pick<0, 1>(sched, [&](auto sc) {
-            constexpr bool kS = decltype(sc)::value != 0;
+    pick<0, 1>(f.sched, [&](auto sc) {
+        pick<0, 1>(f.det != nullptr, [&](auto tap) {
+            constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
             if (pl.bwd == kMacroBwdFast) {
-                // <kB, kFull> as 10 kB + 2 kFull
-                pick<5120, 5122, 2560, 2562, 1280, 1282, 640, 10240>(10 * B + (pl.bwd_full ? 2 : 0), [&](auto v) {
-                    constexpr int kV = decltype(v)::value;
-                    lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, false, kV % 10 == 2, kS, true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault,
-                                        stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
-                });
+                // <kB, kHist, kFull> as 10 kB + (0 plain, 1 kHist, 2 kFull): every combination a plan can name (kFull: 128 <= N = kB <= 512).
+                // Detectors exclude the dense per-step cotangents (the plan of the taps form has no history).
+                pick<5120, 5122, 5121, 2560, 2562, 2561, 1280, 1282, 1281, 640, 641, 10241, 10240>(
+                    10 * B + (pl.hist ? 1 : (pl.bwd_full ? 2 : 0)), [&](auto v) {
+                        constexpr int kV = decltype(v)::value;
+                        if constexpr (!(kT && kV % 10 == 1))
+                            lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, kV % 10 == 1, kV % 10 == 2, kS, kT>, d->n_lanes, B, pl.lds_bwd,
+                                                kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, f.g_cot, g_r_out, g_y_out, g_ghost, err,
+                                                f.det, f.n_det);
+                    });
+            } else if (pl.bwd == kMacroBwdFast2) {
+                // two cells per thread: no per-step cotangents, so no detector form (the plan sends that to the general sweep)
+                if constexpr (!kT)
+                    pick<0, 1>(pl.bwd_full, [&](auto full) {
+                        lds_ok = launch_lds(macro_rollout_bwd_fast2_kernel<1024, decltype(full)::value != 0, kS>, d->n_lanes, B, pl.lds_bwd,
+                                            kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_r_out, g_y_out, g_ghost, err);
+                    });
             } else {
-                lds_ok = launch_lds(macro_rollout_bwd_kernel<kS, true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r,
-                                    g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
+                lds_ok = launch_lds(macro_rollout_bwd_kernel<kS, kT>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r,
+                                    g_y, f.g_cot, g_r_out, g_y_out, g_ghost, err, f.det, f.n_det);
             }
         });
-    } else if (sched) {
-        if (pl.bwd == kMacroBwdFast) {
-            pick<10242, 5120, 5122, 5121, 2560, 2562, 2561, 1280, 1282, 1281, 640, 642, 641, 10241, 10240>(
-                10 * B + (pl.hist ? 1 : (pl.bwd_full ? 2 : 0)), [&](auto v) {
-                    constexpr int kV = decltype(v)::value;
-                    lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, kV % 10 == 1, kV % 10 == 2, true>, d->n_lanes, B, pl.lds_bwd,
-                                        kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
-                });
-        } else if (pl.bwd == kMacroBwdFast2) {
-            pick<0, 1>(pl.bwd_full, [&](auto full) {
-                lds_ok = launch_lds(macro_rollout_bwd_fast2_kernel<1024, decltype(full)::value != 0, true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault,
-                                    stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_r_out, g_y_out, g_ghost, err);
-            });
-        } else {
-            lds_ok = launch_lds(macro_rollout_bwd_kernel<true>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y,
-                                g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
-        }
-    } else if (pl.bwd == kMacroBwdFast) {
-        // <kB, kHist, kFull> as 10 kB + (0 plain, 1 kHist, 2 kFull).  The list holds every instantiation the library has always had, in
-        // the order that keeps them where they have always been in the code object (last entry first).
-        pick<10242, 5120, 5122, 5121, 2560, 2562, 2561, 1280, 1282, 1281, 640, 642, 641, 10241, 10240>(
-            10 * B + (pl.hist ? 1 : (pl.bwd_full ? 2 : 0)), [&](auto v) {
-                constexpr int kV = decltype(v)::value;
-                lds_ok = launch_lds(macro_rollout_bwd_fast_kernel<kV / 10, kV % 10 == 1, kV % 10 == 2>, d->n_lanes, B, pl.lds_bwd, kLdsDefault,
-                                    stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, det, n_det);
-            });
-    } else if (pl.bwd == kMacroBwdFast2) {
-        pick<0, 1>(pl.bwd_full, [&](auto full) {
-            lds_ok = launch_lds(macro_rollout_bwd_fast2_kernel<1024, decltype(full)::value != 0>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream,
-                                d->n_lanes, N, T, cc, tp, g_r, g_y, g_r_out, g_y_out, g_ghost, err);
-        });
-    } else {
-        lds_ok = launch_lds(macro_rollout_bwd_kernel<false>, d->n_lanes, B, pl.lds_bwd, kLdsDefault, stream, d->n_lanes, N, T, cc, tp, g_r, g_y, g_hist,
-                            g_r_out, g_y_out, g_ghost, err, det, n_det);
-    }
+    });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
@@ -1673,46 +1650,45 @@ int dhts_macro_u_tap_bwd(int64_t n, double u_max, const float *r, const float *y
 }
 
 // rollouts keep the compact tape described above (three floats per trivial interface + the exceptions' products)
+static inline bool macro_fwd_args_ok(const dhts_macro_desc *d, int T, const float *r, const float *y, const float *u, const float *ueq,
+                                     const float *ghost, const float *r_out, const float *y_out, const float *u_out, const float *ueq_out) {
+    return macro_desc_ok(d) && T >= 0 && r && y && u && ueq && ghost && r_out && y_out && u_out && ueq_out;
+}
 int dhts_macro_rollout_fwd(const dhts_macro_desc *d, int T,
                            const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                            float *r_out, float *y_out, float *u_out, float *ueq_out,
                            float *tape, float *hist, dhts_error *err, void *stream) {
-    if (!macro_desc_ok(d) || T < 0 || !r || !y || !u || !ueq || !ghost || !r_out || !y_out || !u_out || !ueq_out) return DHTS_E_INVALID;
-    const MacroPlan pl = macro_plan(d, T, hist != nullptr, tape != nullptr);
-    if (pl.fwd == kMacroFwdOnePhase)
-        return macro_fwd_launch<true>(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, hist, err, stream);
-    return macro_fwd2_launch(pl, d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, hist, err, stream);
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out)) return DHTS_E_INVALID;
+    MacroForm f = {};
+    f.hist = hist;
+    return macro_rollout_fwd_launch(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, f, err, stream);
 }
 int dhts_macro_rollout_bwd(const dhts_macro_desc *d, int T, const float *tape,
                            const float *g_r, const float *g_y, const float *g_hist,
                            float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
-    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost, err, stream);
+    MacroForm f = {};
+    f.g_cot = g_hist;
+    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
 }
 // the same rollout with a boundary schedule: the same plan, the kSched instantiation of the kernel it names
 int dhts_macro_rollout_fwd_sched(const dhts_macro_desc *d, int T,
                                  const float *r, const float *y, const float *u, const float *ueq, const float *ghost_sched,
                                  float *r_out, float *y_out, float *u_out, float *ueq_out,
                                  float *tape, float *hist, dhts_error *err, void *stream) {
-    if (!macro_desc_ok(d) || T < 0 || !r || !y || !u || !ueq || !ghost_sched || !r_out || !y_out || !u_out || !ueq_out) return DHTS_E_INVALID;
-    if (T == 0) {       // no row to read: the state comes back as it went in (what the constant-boundary rollout does with T = 0)
-        const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
-        const float *src[4] = {r, y, u, ueq};
-        float *dst[4] = {r_out, y_out, u_out, ueq_out};
-        for (int k = 0; k < 4; ++k)
-            if (dst[k] != src[k] && hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-                return DHTS_E_LAUNCH;
-        return DHTS_OK;
-    }
-    const MacroPlan pl = macro_plan(d, T, hist != nullptr, tape != nullptr);
-    if (pl.fwd == kMacroFwdOnePhase)
-        return macro_fwd_launch<true, true>(d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out, tape, hist, err, stream);
-    return macro_fwd2_launch(pl, d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out, tape, hist, err, stream, true);
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out)) return DHTS_E_INVALID;
+    if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
+    MacroForm f = {};
+    f.sched = true;
+    f.hist = hist;
+    return macro_rollout_fwd_launch(d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out, tape, f, err, stream);
 }
 int dhts_macro_rollout_bwd_sched(const dhts_macro_desc *d, int T, const float *tape,
                                  const float *g_r, const float *g_y, const float *g_hist,
                                  float *g_r_out, float *g_y_out, double *g_ghost_sched, dhts_error *err, void *stream) {
-    if (!g_ghost_sched) return DHTS_E_INVALID;
-    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_hist, g_r_out, g_y_out, g_ghost_sched, err, stream, true);
+    MacroForm f = {};
+    f.sched = true;
+    f.g_cot = g_hist;
+    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_r_out, g_y_out, g_ghost_sched, f, err, stream);
 }
 // the rollout with detector taps instead of a history (constant boundary cells or a schedule): the plan of the same shape without a
 // history, the kTaps instantiation of the kernel it names
@@ -1723,46 +1699,36 @@ int dhts_macro_rollout_fwd_taps(const dhts_macro_desc *d, int T,
                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
                                 float *r_out, float *y_out, float *u_out, float *ueq_out, float *tape,
                                 const int32_t *det, int n_det, float *taps, dhts_error *err, void *stream) {
-    if (!macro_taps_ok(d, det, n_det) || !taps || T < 0 || !r || !y || !u || !ueq || !ghost || !r_out || !y_out || !u_out || !ueq_out)
+    if (!macro_taps_ok(d, det, n_det) || !taps || !macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out))
         return DHTS_E_INVALID;
-    if (T == 0) {       // no step, no row of taps, of the tape or of a schedule: the state comes back as it went in
-        const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
-        const float *src[4] = {r, y, u, ueq};
-        float *dst[4] = {r_out, y_out, u_out, ueq_out};
-        for (int k = 0; k < 4; ++k)
-            if (dst[k] != src[k] && hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-                return DHTS_E_LAUNCH;
-        return DHTS_OK;
-    }
-    const MacroPlan pl = macro_plan(d, T, false, tape != nullptr, true);
-    if (pl.fwd == kMacroFwdOnePhase) {
-        if (ghost_is_sched)
-            return macro_fwd_launch<true, true, true>(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, nullptr, err, stream, det, n_det, taps);
-        return macro_fwd_launch<true, false, true>(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, nullptr, err, stream, det, n_det, taps);
-    }
-    return macro_fwd2_launch(pl, d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, nullptr, err, stream, ghost_is_sched != 0, det,
-                             n_det, taps);
+    if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
+    MacroForm f = {};
+    f.sched = ghost_is_sched != 0;
+    f.det = det; f.n_det = n_det; f.taps = taps;
+    return macro_rollout_fwd_launch(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, f, err, stream);
 }
 int dhts_macro_rollout_bwd_taps(const dhts_macro_desc *d, int T, const float *tape, const float *g_r, const float *g_y,
                                 const int32_t *det, int n_det, const float *g_taps,
                                 float *g_r_out, float *g_y_out, double *g_ghost, int ghost_is_sched, dhts_error *err, void *stream) {
     if (!macro_taps_ok(d, det, n_det) || !g_taps) return DHTS_E_INVALID;
-    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_taps, g_r_out, g_y_out, g_ghost, err, stream, ghost_is_sched != 0, det, n_det);
+    MacroForm f = {};
+    f.sched = ghost_is_sched != 0;
+    f.det = det; f.n_det = n_det; f.g_cot = g_taps;
+    return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
 }
-int dhts_macro_taps_plan(const dhts_macro_desc *d, int T, int n_det, int32_t plan[8]) {
-    if (!macro_desc_ok(d) || T < 0 || !plan || n_det < 1 || n_det > d->n_cells) return DHTS_E_INVALID;
-    const MacroPlan pl = macro_plan(d, T, false, true, true);
-    plan[0] = pl.fwd; plan[1] = pl.W; plan[2] = pl.p; plan[3] = pl.dense ? 1 : 0;
-    plan[4] = pl.bwd; plan[5] = pl.bwd_block; plan[6] = 0; plan[7] = pl.G;
-    return DHTS_OK;
-}
-// which kernel instantiations dhts_macro_rollout_fwd / _bwd (and their _sched forms) launch for this shape: the plan the launches read
-int dhts_macro_rollout_plan(const dhts_macro_desc *d, int T, int want_hist, int32_t plan[8]) {
-    if (!macro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
-    const MacroPlan pl = macro_plan(d, T, want_hist != 0, true);
+// which kernel instantiations the rollout entry points launch for a shape: the plan the launches read, as include/dhts.h lays it out
+static int macro_plan_out(const MacroPlan &pl, int32_t plan[8]) {
     plan[0] = pl.fwd; plan[1] = pl.W; plan[2] = pl.p; plan[3] = pl.dense ? 1 : 0;
     plan[4] = pl.bwd; plan[5] = pl.bwd_block; plan[6] = pl.hist ? 1 : 0; plan[7] = pl.G;
     return DHTS_OK;
+}
+int dhts_macro_taps_plan(const dhts_macro_desc *d, int T, int n_det, int32_t plan[8]) {
+    if (!macro_desc_ok(d) || T < 0 || !plan || n_det < 1 || n_det > d->n_cells) return DHTS_E_INVALID;
+    return macro_plan_out(macro_plan(d, T, false, true, true), plan);       // (no history: plan[6] = 0)
+}
+int dhts_macro_rollout_plan(const dhts_macro_desc *d, int T, int want_hist, int32_t plan[8]) {       // (the _sched forms too)
+    if (!macro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
+    return macro_plan_out(macro_plan(d, T, want_hist != 0, true), plan);
 }
 int dhts_macro_tape_expand(const dhts_macro_desc *d, int T, const float *tape, float *dqs, void *stream) {
     if (!macro_desc_ok(d) || T < 0 || (T > 0 && (!tape || !dqs))) return DHTS_E_INVALID;
@@ -1777,7 +1743,7 @@ int dhts_macro_step_fwd(const dhts_macro_desc *d,
                         const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
                         float *r_out, float *y_out, float *u_out, float *ueq_out,
                         float *tape, dhts_error *err, void *stream) {
-    return macro_fwd_launch<false>(d, 1, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, nullptr, err, stream);
+    return macro_fwd_launch(false, d, 1, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, MacroForm{}, err, stream);
 }
 int dhts_macro_step_bwd(const dhts_macro_desc *d, const float *tape, const float *g_r, const float *g_y,
                         float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {

@@ -127,76 +127,6 @@ def macro_u_tap_bwd(r, y, g_u, g_r, g_y, u_max):
                                           _stream()), "dhts_macro_u_tap_bwd")
 
 
-def macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, tape=None, hist=None, err=None, out=None):
-    """state planes [L][N]; ghost [L][2][4]; returns (r, y, u, ueq) after T steps."""
-    L, N = desc.n_lanes, desc.n_cells
-    for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
-        if tuple(t.shape) != (L, N):
-            raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
-    if tuple(ghost.shape) != (L, 2, 4):
-        raise ValueError("ghost must have shape (%d, 2, 4)" % L)
-    r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, "ghost")))
-    if out is None:
-        out = tuple(torch.empty_like(r) for _ in range(4))
-    check(_lib.lib().dhts_macro_rollout_fwd(C.byref(desc), int(T), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost),
-                                            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
-                                            _ptr(tape), _ptr(hist), _ptr(err), _stream()), "dhts_macro_rollout_fwd")
-    return out
-
-
-def macro_rollout_bwd(desc, T, tape, g_r, g_y, g_hist=None, err=None, out=None, g_ghost=None):
-    """returns (g_r0, g_y0, g_ghost[L][2][2] float64)."""
-    g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
-    if out is None:
-        out = (torch.empty_like(g_r), torch.empty_like(g_y))
-    if g_ghost is None:
-        g_ghost = torch.zeros(desc.n_lanes, 2, 2, dtype=torch.float64, device=g_r.device)
-    check(_lib.lib().dhts_macro_rollout_bwd(C.byref(desc), int(T), _ptr(tape), _ptr(g_r), _ptr(g_y), _ptr(g_hist),
-                                            _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err), _stream()),
-          "dhts_macro_rollout_bwd")
-    return out[0], out[1], g_ghost
-
-
-def macro_rollout_fwd_sched(desc, T, r, y, u, ueq, ghost_sched, tape=None, hist=None, err=None, out=None):
-    """macro_rollout_fwd with a boundary schedule: ghost_sched [T][L][2][4], row t read by step t."""
-    L, N = desc.n_lanes, desc.n_cells
-    for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
-        if tuple(t.shape) != (L, N):
-            raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
-    if tuple(ghost_sched.shape) != (int(T), L, 2, 4):
-        raise ValueError("ghost_sched must have shape (%d, %d, 2, 4)" % (int(T), L))
-    r, y, u, ueq, ghost_sched = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost_sched, "ghost_sched")))
-    if int(T) == 0:             # an empty tensor has no address; the entry point wants one and reads no row
-        ghost_sched = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
-    if out is None:
-        out = tuple(torch.empty_like(r) for _ in range(4))
-    check(_lib.lib().dhts_macro_rollout_fwd_sched(C.byref(desc), int(T), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost_sched),
-                                                  _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
-                                                  _ptr(tape), _ptr(hist), _ptr(err), _stream()), "dhts_macro_rollout_fwd_sched")
-    return out
-
-
-def macro_rollout_bwd_sched(desc, T, tape, g_r, g_y, g_hist=None, err=None, out=None):
-    """returns (g_r0, g_y0, g_ghost_sched [T][L][2][2] float64): row t = the cotangent that reaches the boundary cells of step t."""
-    g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
-    if out is None:
-        out = (torch.empty_like(g_r), torch.empty_like(g_y))
-    g_sched = torch.empty(max(int(T), 1), desc.n_lanes, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
-    check(_lib.lib().dhts_macro_rollout_bwd_sched(C.byref(desc), int(T), _ptr(tape), _ptr(g_r), _ptr(g_y), _ptr(g_hist),
-                                                  _ptr(out[0]), _ptr(out[1]), _ptr(g_sched), _ptr(err), _stream()),
-          "dhts_macro_rollout_bwd_sched")
-    return out[0], out[1], g_sched[:int(T)]
-
-
-def macro_rollout_plan(desc, T, want_hist=False):
-    """Which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for this shape (include/dhts.h)."""
-    plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_macro_rollout_plan(C.byref(desc), int(T), int(bool(want_hist)), C.byref(plan)), "dhts_macro_rollout_plan")
-    # fwd_kernel: 0 = two-phase lane kernel, 1 = one-phase, 2 = two-phase pair kernel
-    keys = ("fwd_kernel", "fwd_waves", "fwd_passes", "fwd_full_lane", "bwd_pipelined", "bwd_block", "hist", "fwd_lanes_per_group")
-    return dict(zip(keys, list(plan)))
-
-
 def _det_i32(det, N):
     if not isinstance(det, torch.Tensor) or det.dtype != torch.int32 or not det.is_cuda or det.dim() != 1:
         raise ValueError("det must be a one-dimensional int32 CUDA tensor")
@@ -205,65 +135,126 @@ def _det_i32(det, N):
     return det.contiguous()
 
 
-def macro_rollout_fwd_taps(desc, T, r, y, u, ueq, ghost, det, tape=None, err=None, out=None, taps=None):
-    """macro_rollout_fwd / _sched with detector taps instead of a history.  ghost [L][2][4], or a schedule [T][L][2][4]; det int32 CUDA
-    [D]: cell indices, strictly ascending, in [0, N) (not looked at here: include/dhts.h, index contract).  Returns
-    ((r, y, u, ueq) after T steps, taps [T][L][3][D] = (r, y, u) of cell det[j] after every step)."""
+def _macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, ghost_name, sched, tape, err, out, hist=None, det=None, taps=None):
+    """The forward rollout of every form (include/dhts.h): ghost [L][2][4], or with `sched` a schedule [T][L][2][4]; with `det` the
+    detector form, which writes `taps` instead of `hist`.  Returns (out, taps)."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
     for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
         if tuple(t.shape) != (L, N):
             raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
-    sched = ghost.dim() == 4
-    if tuple(ghost.shape) != ((T, L, 2, 4) if sched else (L, 2, 4)):
-        raise ValueError("ghost must have shape (%d, 2, 4) or (%d, %d, 2, 4)" % (L, T, L))
-    det = _det_i32(det, N)
-    D = det.numel()
-    r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, "ghost")))
+    want = (T, L, 2, 4) if sched else (L, 2, 4)
+    if tuple(ghost.shape) != want:
+        raise ValueError("%s must have shape %s" % (ghost_name, want))
+    if det is not None:
+        det = _det_i32(det, N)
+    r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, ghost_name)))
     if sched and T == 0:        # an empty tensor has no address; the entry point wants one and reads no row
         ghost = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
-    if taps is None:
-        taps = torch.empty(max(T, 1), L, 3, D, dtype=torch.float32, device=r.device)[:T]
-    elif tuple(taps.shape) != (T, L, 3, D) or taps.dtype != torch.float32 or not taps.is_cuda or not taps.is_contiguous():
-        raise ValueError("taps must be a contiguous float32 CUDA tensor of shape (%d, %d, 3, %d)" % (T, L, D))
+    if det is not None:
+        D = det.numel()
+        if taps is None:
+            taps = torch.empty(max(T, 1), L, 3, D, dtype=torch.float32, device=r.device)[:T]
+        elif tuple(taps.shape) != (T, L, 3, D) or taps.dtype != torch.float32 or not taps.is_cuda or not taps.is_contiguous():
+            raise ValueError("taps must be a contiguous float32 CUDA tensor of shape (%d, %d, 3, %d)" % (T, L, D))
     if out is None:
         out = tuple(torch.empty_like(r) for _ in range(4))
-    check(_lib.lib().dhts_macro_rollout_fwd_taps(C.byref(desc), T, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(tape),
-                                                 _ptr(det), D, C.c_void_p(taps.data_ptr() or det.data_ptr()),      # (T = 0: no address, no row)
-                                                 _ptr(err), _stream()),
-          "dhts_macro_rollout_fwd_taps")
+    state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost))
+    outs = tuple(_ptr(o) for o in out)
+    if det is not None:
+        check(_lib.lib().dhts_macro_rollout_fwd_taps(C.byref(desc), T, *state, int(sched), *outs, _ptr(tape), _ptr(det), D,
+                                                     C.c_void_p(taps.data_ptr() or det.data_ptr()),      # (T = 0: no address, no row)
+                                                     _ptr(err), _stream()), "dhts_macro_rollout_fwd_taps")
+    else:
+        entry = "dhts_macro_rollout_fwd_sched" if sched else "dhts_macro_rollout_fwd"
+        check(getattr(_lib.lib(), entry)(C.byref(desc), T, *state, *outs, _ptr(tape), _ptr(hist), _ptr(err), _stream()), entry)
     return out, taps
+
+
+def _macro_rollout_bwd(desc, T, tape, g_r, g_y, sched, err, out, g_hist=None, det=None, g_taps=None, g_ghost=None):
+    """The reverse sweep of every form: per-step cotangents g_hist [T][L][2][N], or with `det` g_taps [T][L][2][D].  Returns
+    (g_r0, g_y0, g_ghost): float64 [L][2][2] summed over the steps, or with `sched` per step [T][L][2][2]."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    if det is not None:
+        det = _det_i32(det, N)
+        D = det.numel()
+        if tuple(g_taps.shape) != (T, L, 2, D):
+            raise ValueError("g_taps must have shape (%d, %d, 2, %d)" % (T, L, D))
+    g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
+    if det is not None:
+        g_taps = _f32c(g_taps, "g_taps")
+        if tuple(g_r.shape) != (L, N) or tuple(g_y.shape) != (L, N):
+            raise ValueError("g_r and g_y must have shape (%d, %d)" % (L, N))
+    if out is None:
+        out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    if g_ghost is None and sched:
+        g_ghost = torch.empty(max(T, 1), L, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
+    elif g_ghost is None:
+        g_ghost = torch.zeros(L, 2, 2, dtype=torch.float64, device=g_r.device)
+    grads = (_ptr(tape), _ptr(g_r), _ptr(g_y))
+    if det is not None:
+        check(_lib.lib().dhts_macro_rollout_bwd_taps(C.byref(desc), T, *grads, _ptr(det), D,
+                                                     C.c_void_p(g_taps.data_ptr() or det.data_ptr()), _ptr(out[0]), _ptr(out[1]),
+                                                     _ptr(g_ghost), int(bool(sched)), _ptr(err), _stream()), "dhts_macro_rollout_bwd_taps")
+    else:
+        entry = "dhts_macro_rollout_bwd_sched" if sched else "dhts_macro_rollout_bwd"
+        check(getattr(_lib.lib(), entry)(C.byref(desc), T, *grads, _ptr(g_hist), _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err),
+                                         _stream()), entry)
+    return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
+
+
+def macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, tape=None, hist=None, err=None, out=None):
+    """state planes [L][N]; ghost [L][2][4]; returns (r, y, u, ueq) after T steps."""
+    return _macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, "ghost", False, tape, err, out, hist=hist)[0]
+
+
+def macro_rollout_bwd(desc, T, tape, g_r, g_y, g_hist=None, err=None, out=None, g_ghost=None):
+    """returns (g_r0, g_y0, g_ghost[L][2][2] float64)."""
+    return _macro_rollout_bwd(desc, T, tape, g_r, g_y, False, err, out, g_hist=g_hist, g_ghost=g_ghost)
+
+
+def macro_rollout_fwd_sched(desc, T, r, y, u, ueq, ghost_sched, tape=None, hist=None, err=None, out=None):
+    """macro_rollout_fwd with a boundary schedule: ghost_sched [T][L][2][4], row t read by step t."""
+    return _macro_rollout_fwd(desc, T, r, y, u, ueq, ghost_sched, "ghost_sched", True, tape, err, out, hist=hist)[0]
+
+
+def macro_rollout_bwd_sched(desc, T, tape, g_r, g_y, g_hist=None, err=None, out=None):
+    """returns (g_r0, g_y0, g_ghost_sched [T][L][2][2] float64): row t = the cotangent that reaches the boundary cells of step t."""
+    return _macro_rollout_bwd(desc, T, tape, g_r, g_y, True, err, out, g_hist=g_hist)
+
+
+def macro_rollout_fwd_taps(desc, T, r, y, u, ueq, ghost, det, tape=None, err=None, out=None, taps=None):
+    """macro_rollout_fwd / _sched with detector taps instead of a history.  ghost [L][2][4], or a schedule [T][L][2][4]; det int32 CUDA
+    [D]: cell indices, strictly ascending, in [0, N) (not looked at here: include/dhts.h, index contract).  Returns
+    ((r, y, u, ueq) after T steps, taps [T][L][3][D] = (r, y, u) of cell det[j] after every step)."""
+    if det is None:
+        raise ValueError("det must be a one-dimensional int32 CUDA tensor")
+    return _macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, "ghost", ghost.dim() == 4, tape, err, out, det=det, taps=taps)
 
 
 def macro_rollout_bwd_taps(desc, T, tape, g_r, g_y, det, g_taps, sched=False, err=None, out=None):
     """macro_rollout_bwd / _sched with g_taps [T][L][2][D], the cotangent of (r, y) of the cells det[j] after every step.  Returns
     (g_r0, g_y0, g_ghost): [L][2][2] float64, or the per-step [T][L][2][2] when sched."""
-    L, N, T = desc.n_lanes, desc.n_cells, int(T)
-    det = _det_i32(det, N)
-    D = det.numel()
-    if tuple(g_taps.shape) != (T, L, 2, D):
-        raise ValueError("g_taps must have shape (%d, %d, 2, %d)" % (T, L, D))
-    g_r, g_y, g_taps = _f32c(g_r, "g_r"), _f32c(g_y, "g_y"), _f32c(g_taps, "g_taps")
-    if tuple(g_r.shape) != (L, N) or tuple(g_y.shape) != (L, N):
-        raise ValueError("g_r and g_y must have shape (%d, %d)" % (L, N))
-    if out is None:
-        out = (torch.empty_like(g_r), torch.empty_like(g_y))
-    if sched:
-        g_ghost = torch.empty(max(T, 1), L, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
-    else:
-        g_ghost = torch.zeros(L, 2, 2, dtype=torch.float64, device=g_r.device)
-    check(_lib.lib().dhts_macro_rollout_bwd_taps(C.byref(desc), T, _ptr(tape), _ptr(g_r), _ptr(g_y), _ptr(det), D,
-                                                 C.c_void_p(g_taps.data_ptr() or det.data_ptr()), _ptr(out[0]), _ptr(out[1]),
-                                                 _ptr(g_ghost), int(bool(sched)), _ptr(err), _stream()), "dhts_macro_rollout_bwd_taps")
-    return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
+    if det is None:
+        raise ValueError("det must be a one-dimensional int32 CUDA tensor")
+    return _macro_rollout_bwd(desc, T, tape, g_r, g_y, sched, err, out, det=det, g_taps=g_taps)
+
+
+_MACRO_PLAN_KEYS = ("fwd_kernel", "fwd_waves", "fwd_passes", "fwd_full_lane", "bwd_pipelined", "bwd_block", "hist", "fwd_lanes_per_group")
+
+
+def macro_rollout_plan(desc, T, want_hist=False):
+    """Which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for this shape (include/dhts.h).
+    fwd_kernel: 0 = two-phase lane kernel, 1 = one-phase, 2 = two-phase pair kernel."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_macro_rollout_plan(C.byref(desc), int(T), int(bool(want_hist)), C.byref(plan)), "dhts_macro_rollout_plan")
+    return dict(zip(_MACRO_PLAN_KEYS, list(plan)))
 
 
 def macro_taps_plan(desc, T, n_det):
     """Which kernel instantiations dhts_macro_rollout_fwd_taps / _bwd_taps launch for this shape: the fields of macro_rollout_plan."""
     plan = (C.c_int32 * 8)()
     check(_lib.lib().dhts_macro_taps_plan(C.byref(desc), int(T), int(n_det), C.byref(plan)), "dhts_macro_taps_plan")
-    keys = ("fwd_kernel", "fwd_waves", "fwd_passes", "fwd_full_lane", "bwd_pipelined", "bwd_block", "hist", "fwd_lanes_per_group")
-    return dict(zip(keys, list(plan)))
+    return dict(zip(_MACRO_PLAN_KEYS, list(plan)))
 
 
 def macro_tape_expand(desc, T, tape):
@@ -281,81 +272,29 @@ def _ghost_ry_to_ru(g_ghost, gr, gu, gq, um):
     return (g_ghost[..., 0] + g_ghost[..., 1] * ((uu - qq) - rr * dueq)).float(), (g_ghost[..., 1] * rr).float()
 
 
+def _per_step_cotangent(steps, g_steps, um):
+    """The cotangent of per-step states [T][L][3][X] (r, y, u; X = N: the history, X = D: detector readings) as the reverse sweep
+    takes it, [T][L][2][X]: (r, y) directly, u through the float32 glue of the saved (r, y) of that step."""
+    sr, sy = steps[:, :, 0].contiguous(), steps[:, :, 1].contiguous()
+    g_sr, g_sy = g_steps[:, :, 0].contiguous().clone(), g_steps[:, :, 1].contiguous().clone()
+    macro_u_tap_bwd(sr, sy, g_steps[:, :, 2].contiguous(), g_sr, g_sy, um)
+    return torch.stack([g_sr, g_sy], dim=2).contiguous()
+
+
 class MacroRollout(torch.autograd.Function):
     """T fused differentiable steps of L independent straight ARZ lanes.
 
-    (r0, u0 [L][N], ghost_r, ghost_u [L][2]) -> (rT, yT, uT [L][N]) (+ hist [T][L][3][N] when asked).
+    (r0, u0 [L][N], ghost_r, ghost_u [L][2]) -> (rT, yT, uT, qT [L][N]) (+ hist [T][L][3][N] when asked).
     ghost_r, ghost_u [T][L][2] instead: a boundary schedule, row t set in front of step t; their gradients come back per step.
+    det (int32 CUDA [D], the last argument): detector readings [T][L][3][D] as the fifth output instead of a history,
+    readings[t][l][:][j] = (r, y, u) of cell det[j] after step t; nothing of size [T][L][N] is written, saved or read back then.
     What example/inverse/macro.py does with one dMacroLane in a RoadNetwork (macro.py:34-68,
     _inverse.py:91-99), for L lanes at once: state set by set_state_vector_u, ghosts by
-    set_leftmost_cell / set_rightmost_cell, T x RoadNetwork.forward, state read by get_state_vector.
+    set_leftmost_cell / set_rightmost_cell, T x RoadNetwork.forward, state read by get_state_vector (at chosen cells: the readings).
     """
 
     @staticmethod
-    def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True):
-        L, N = r0.shape
-        sched = ghost_r.dim() == 3
-        if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
-            raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
-        want = (int(T), L, 2) if sched else (L, 2)
-        if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
-            raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
-        desc = macro_desc(L, N, dt, dx, u_max)
-        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
-        gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
-        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
-        gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
-        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4], or [T][L][2][4]
-        need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
-        tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
-        hist = torch.empty(T, L, 3, N, dtype=torch.float32, device=r0.device) if want_hist else None
-        err = new_error_record(r0.device)
-        fwd = macro_rollout_fwd_sched if sched else macro_rollout_fwd
-        rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=hist, err=err)
-        if check_faults:
-            raise_on_fault(err)
-        ctx.sched = sched
-        ctx.desc, ctx.T, ctx.u_max, ctx.tape, ctx.want_hist, ctx.check_faults = desc, T, u_max, tape, want_hist, check_faults
-        ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, hist)
-        ctx.mark_non_differentiable(qT)
-        if want_hist:
-            return rT, yT, uT, qT, hist
-        return rT, yT, uT, qT
-
-    @staticmethod
-    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_hist=None):
-        r0, u0, gr, gu, gq, rT, yT, hist = ctx.saved_tensors
-        desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        L, N = desc.n_lanes, desc.n_cells
-        dev = r0.device
-        g_r = g_rT.contiguous().clone() if g_rT is not None else torch.zeros(L, N, device=dev)
-        g_y = g_yT.contiguous().clone() if g_yT is not None else torch.zeros(L, N, device=dev)
-        if g_uT is not None:
-            macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
-        gh = None
-        if ctx.want_hist and g_hist is not None and g_hist.numel():      # (T = 0: no row, and an empty tensor has no address)
-            # per-step taps: (r, y) cotangents directly, u cotangent through the float32 glue of that step's state
-            hr, hy = hist[:, :, 0].contiguous(), hist[:, :, 1].contiguous()
-            ghr, ghy = g_hist[:, :, 0].contiguous().clone(), g_hist[:, :, 1].contiguous().clone()
-            macro_u_tap_bwd(hr, hy, g_hist[:, :, 2].contiguous(), ghr, ghy, um)
-            gh = torch.stack([ghr, ghy], dim=2).contiguous()                   # [T][L][2][N]
-        err = new_error_record(dev)
-        bwd = macro_rollout_bwd_sched if ctx.sched else macro_rollout_bwd
-        g_r0, g_y0, g_ghost = bwd(desc, T, ctx.tape, g_r, g_y, g_hist=gh, err=err)      # [L][2][2], or [T][L][2][2] per step
-        if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
-            raise_on_fault(err)
-        g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
-        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um)
-        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None
-
-
-class MacroRolloutTaps(torch.autograd.Function):
-    """MacroRollout with detector readings instead of a history: (...) -> (rT, yT, uT, qT, readings [T][L][3][D]), readings[t][l][:][j] =
-    (r, y, u) of cell det[j] after step t -- get_state_vector read at chosen cells after every RoadNetwork.forward, as the inverse
-    examples do.  Nothing of size [T][L][N] is written, saved or read back."""
-
-    @staticmethod
-    def forward(ctx, r0, u0, ghost_r, ghost_u, det, T, dt, dx, u_max, check_faults=True):
+    def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, det=None):
         L, N = r0.shape
         sched = ghost_r.dim() == 3
         if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
@@ -372,18 +311,25 @@ class MacroRolloutTaps(torch.autograd.Function):
         need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
         tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
         err = new_error_record(r0.device)
-        (rT, yT, uT, qT), readings = macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
+        if det is not None:
+            (rT, yT, uT, qT), steps = macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
+        else:
+            steps = torch.empty(T, L, 3, N, dtype=torch.float32, device=r0.device) if want_hist else None
+            fwd = macro_rollout_fwd_sched if sched else macro_rollout_fwd
+            rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=steps, err=err)
         if check_faults:
             raise_on_fault(err)
         ctx.sched = sched
         ctx.desc, ctx.T, ctx.u_max, ctx.tape, ctx.check_faults = desc, T, u_max, tape, check_faults
-        ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, readings, det)
+        ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, steps, det)
         ctx.mark_non_differentiable(qT)
-        return rT, yT, uT, qT, readings
+        if steps is not None:
+            return rT, yT, uT, qT, steps
+        return rT, yT, uT, qT
 
     @staticmethod
-    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_read):
-        r0, u0, gr, gu, gq, rT, yT, readings, det = ctx.saved_tensors
+    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_steps=None):
+        r0, u0, gr, gu, gq, rT, yT, steps, det = ctx.saved_tensors
         desc, T, um = ctx.desc, ctx.T, ctx.u_max
         L, N = desc.n_lanes, desc.n_cells
         dev = r0.device
@@ -391,22 +337,20 @@ class MacroRolloutTaps(torch.autograd.Function):
         g_y = g_yT.contiguous().clone() if g_yT is not None else torch.zeros(L, N, device=dev)
         if g_uT is not None:
             macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
+        gs = None
+        if steps is not None and g_steps is not None and g_steps.numel():      # (T = 0: no row, and an empty tensor has no address)
+            gs = _per_step_cotangent(steps, g_steps, um)                         # [T][L][2][N], with detectors [T][L][2][D]
         err = new_error_record(dev)
-        if g_read is not None and g_read.numel():
-            # (r, y) cotangents directly, the u cotangent through the float32 glue of the readings' own (r, y): T L D elements
-            tr, ty = readings[:, :, 0].contiguous(), readings[:, :, 1].contiguous()
-            gtr, gty = g_read[:, :, 0].contiguous().clone(), g_read[:, :, 1].contiguous().clone()
-            macro_u_tap_bwd(tr, ty, g_read[:, :, 2].contiguous(), gtr, gty, um)
-            gt = torch.stack([gtr, gty], dim=2).contiguous()                   # [T][L][2][D]
-            g_r0, g_y0, g_ghost = macro_rollout_bwd_taps(desc, T, ctx.tape, g_r, g_y, det, gt, sched=ctx.sched, err=err)
-        else:                            # no readings to look at (T = 0): the plain sweep over the same tape
+        if gs is not None and det is not None:
+            g_r0, g_y0, g_ghost = macro_rollout_bwd_taps(desc, T, ctx.tape, g_r, g_y, det, gs, sched=ctx.sched, err=err)
+        else:                            # (no readings to look at: the plain sweep over the same tape)
             bwd = macro_rollout_bwd_sched if ctx.sched else macro_rollout_bwd
-            g_r0, g_y0, g_ghost = bwd(desc, T, ctx.tape, g_r, g_y, err=err)
+            g_r0, g_y0, g_ghost = bwd(desc, T, ctx.tape, g_r, g_y, g_hist=gs, err=err)      # [L][2][2], or [T][L][2][2] per step
         if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
             raise_on_fault(err)
         g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
         g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um)
-        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None
+        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None, None
 
 
 def _detector_indices(detectors, N, device):
@@ -441,13 +385,12 @@ def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, c
     column of the readings stays unwritten) and never form an address from one.  Returns (rT, yT, uT, qT, readings) then, readings
     [T][L][3][D] = (r, y, u) of cell detectors[j] after every step, differentiable in all three; no [T][L][N] history is written or
     read.  Not together with want_hist (ValueError): a caller who wants every cell has the history."""
-    if detectors is None:
-        return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist,
-                                  check_faults)
-    if want_hist:
-        raise ValueError("want_hist and detectors exclude each other: the history holds every cell")
-    det = _detector_indices(detectors, int(r0.shape[-1]), r0.device)
-    return MacroRolloutTaps.apply(r0, u0, ghost_r, ghost_u, det, int(T), float(dt), float(dx), float(u_max), check_faults)
+    det = None
+    if detectors is not None:
+        if want_hist:
+            raise ValueError("want_hist and detectors exclude each other: the history holds every cell")
+        det = _detector_indices(detectors, int(r0.shape[-1]), r0.device)
+    return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist, check_faults, det)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -10,30 +10,13 @@ import numpy as np
 import pytest
 
 import macro_sched_ref as R
-from util import TOL_GRAD, TOL_STATE, grad_report, meta_of, state_report
+from util import TOL_GRAD, TOL_STATE, grad_report, meta_of, options, state_report
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT, DX, UM = 0.01, 5.0, 30.0
 LANE, ONE_PHASE, PAIR = 0, 1, 2          # plan: fwd_kernel
 GENERAL, FAST, FAST2 = 0, 1, 2           # plan: bwd_pipelined
-
-
-class options:
-    """dhts_set_option for the length of a with-block (the forward kernel's test hooks), back to the defaults afterwards."""
-
-    def __init__(self, variant=0, group=0):
-        self.v = {"OPT_MACRO_FWD_VARIANT": variant, "OPT_MACRO_FWD_GROUP": group}
-
-    def __enter__(self):
-        from dhts import _lib
-        for k, v in self.v.items():
-            assert _lib.lib().dhts_set_option(getattr(_lib, k), v) == 0
-
-    def __exit__(self, *exc):
-        from dhts import _lib
-        for k in self.v:
-            _lib.lib().dhts_set_option(getattr(_lib, k), 0)
 
 
 # id: (L, N, T, want_hist, variant, group, forward kernel, lanes per workgroup, reverse kernel, its block)
@@ -63,6 +46,13 @@ CASES = {
     "lane1000": (1, 1000, 3, False, 0, 0, LANE, 1, FAST, 1024),
     "lane1026": (1, 1026, 3, False, 0, 0, LANE, 1, FAST2, 1024),
     "lane2048": (1, 2048, 4, False, 0, 0, LANE, 1, FAST2, 1024),
+    # the run-time pass count (three passes on 11 wavefronts); the dense two-pass lane kernel with the pair kernel turned off; the
+    # reverse sweep's 512- and 1024-thread blocks with per-step cotangents
+    "lane2100": (1, 2100, 3, False, 0, 0, LANE, 1, GENERAL, 512),
+    "lane2100_hist": (1, 2100, 3, True, 0, 0, LANE, 1, GENERAL, 512),
+    "lane128_nopair": (2, 128, 5, False, 2, 0, LANE, 1, FAST, 128),
+    "lane300_hist": (2, 300, 4, True, 0, 0, LANE, 1, FAST, 512),
+    "lane1000_hist": (1, 1000, 3, True, 0, 0, LANE, 1, FAST, 1024),
     # one-phase kernel: forced, and where the plan picks it itself (the lane's records do not fit the two-phase kernels' LDS)
     "onephase65": (2, 65, 5, False, 1, 0, ONE_PHASE, 1, FAST, 128),
     "onephase65_hist": (2, 65, 4, True, 1, 0, ONE_PHASE, 1, FAST, 128),

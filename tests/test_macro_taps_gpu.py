@@ -11,30 +11,13 @@ import numpy as np
 import pytest
 
 import macro_sched_ref as R
-from util import TOL_GRAD, TOL_STATE, grad_report, state_report
+from util import TOL_GRAD, TOL_STATE, grad_report, options, state_report
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT, DX, UM = 0.01, 5.0, 30.0
 LANE, ONE_PHASE, PAIR = 0, 1, 2          # plan: fwd_kernel
 GENERAL, FAST, FAST2 = 0, 1, 2           # plan: bwd_pipelined
-
-
-class options:
-    """dhts_set_option for the length of a with-block (the forward kernel's test hooks), back to the defaults afterwards."""
-
-    def __init__(self, variant=0, group=0):
-        self.v = {"OPT_MACRO_FWD_VARIANT": variant, "OPT_MACRO_FWD_GROUP": group}
-
-    def __enter__(self):
-        from dhts import _lib
-        for k, v in self.v.items():
-            assert _lib.lib().dhts_set_option(getattr(_lib, k), v) == 0
-
-    def __exit__(self, *exc):
-        from dhts import _lib
-        for k in self.v:
-            _lib.lib().dhts_set_option(getattr(_lib, k), 0)
 
 
 # id: (L, N, T, variant, group, detectors, forward kernel, lanes per workgroup, reverse kernel of the taps plan, its block)
@@ -60,6 +43,11 @@ CASES = {
     # 1026 .. 2048 cells: the taps plan takes the general reverse sweep (include/dhts.h), as the history does
     "lane1026": (1, 1026, 3, 0, 0, [0, 63, 64, 1023, 1024, 1025], LANE, 1, GENERAL, 512),
     "lane2048": (1, 2048, 4, 0, 0, [0, 127, 128, 1024, 2047], LANE, 1, GENERAL, 512),
+    # the run-time pass count (three passes on 11 wavefronts); the dense two-pass lane kernel with the pair kernel turned off; the
+    # reverse sweep's 512-thread block on a lane shorter than it
+    "lane2100": (1, 2100, 3, 0, 0, [0, 63, 64, 1023, 1024, 2099], LANE, 1, GENERAL, 512),
+    "lane128_nopair": (2, 128, 5, 2, 0, [0, 63, 64, 127], LANE, 1, FAST, 128),
+    "lane300": (2, 300, 4, 0, 0, [0, 149, 150, 299], LANE, 1, FAST, 512),
     # one-phase kernel: forced, and where the plan picks it itself
     "onephase65": (2, 65, 5, 1, 0, list(range(65)), ONE_PHASE, 1, FAST, 128),
     "onephase2500": (1, 2500, 3, 0, 0, [0, 63, 64, 2499], ONE_PHASE, 1, GENERAL, 512),

@@ -51,6 +51,23 @@ def meta_of(npz):
     return json.loads(str(npz["meta"]))
 
 
+class options:
+    """dhts_set_option for the length of a with-block (the forward kernel's test hooks), back to the defaults afterwards."""
+
+    def __init__(self, variant=0, group=0):
+        self.v = {"OPT_MACRO_FWD_VARIANT": variant, "OPT_MACRO_FWD_GROUP": group}
+
+    def __enter__(self):
+        from dhts import _lib
+        for k, v in self.v.items():
+            assert _lib.lib().dhts_set_option(getattr(_lib, k), v) == 0
+
+    def __exit__(self, *exc):
+        from dhts import _lib
+        for k in self.v:
+            _lib.lib().dhts_set_option(getattr(_lib, k), 0)
+
+
 # tolerances of BASELINE.json north_star: state <= 1e-5 relative, gradients <= 1e-4 (norm-relative)
 TOL_STATE = 1e-5
 TOL_GRAD = 1e-4

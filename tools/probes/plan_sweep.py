@@ -63,6 +63,10 @@ def sweep(hybrid):
             d = _lib.MacroDesc(L, N, 0.01, 5.0, 30.0)
             rc = lib.dhts_macro_rollout_plan(C.byref(d), T, hist, C.byref(plan))
             out["macro v%d w%d g%d N%d L%d T%d h%d" % (variant, waves, group, N, L, T, hist)] = [rc] + list(plan)
+        for N, L, T, n_det in itertools.product(MACRO_CELLS, MACRO_LANES, MACRO_T, (1, None)):        # (None: a detector in every cell)
+            d = _lib.MacroDesc(L, N, 0.01, 5.0, 30.0)
+            rc = lib.dhts_macro_taps_plan(C.byref(d), T, n_det or N, C.byref(plan))
+            out["taps v%d w%d g%d N%d L%d T%d d%d" % (variant, waves, group, N, L, T, n_det or N)] = [rc] + list(plan)
     for name in ("OPT_MACRO_FWD_VARIANT", "OPT_MACRO_FWD_WAVES", "OPT_MACRO_FWD_GROUP"):
         assert opt(name, 0) == 0
     for waves in (0, 1, 2, 4):
