@@ -87,6 +87,7 @@ const Option kOptions[] = {
     {DHTS_OPT_NETSTEP_LDS_KB, 0, 158, nullptr, &dhts_netstep_lds_kb},
     {DHTS_OPT_HYB_PACK, 0, 2, nullptr, &dhts_hyb_pack},
     {DHTS_OPT_REWARD_CHAIN, 0, 1, nullptr, &dhts_opt_reward_chain},
+    {DHTS_OPT_MACRO_JVP_VARIANT, 0, 1, nullptr, &dhts_jvp_variant},
 };
 }  // namespace
 

@@ -72,6 +72,7 @@ extern int dhts_fwd_waves_override;          // macro_kernels.hip, DHTS_OPT_MACR
 extern int dhts_fwd_variant;                 // macro_kernels.hip, DHTS_OPT_MACRO_FWD_VARIANT
 extern int dhts_fwd_rotate;                  // macro_kernels.hip, DHTS_OPT_MACRO_FWD_ROTATE
 extern int dhts_fwd_group;                   // macro_kernels.hip, DHTS_OPT_MACRO_FWD_GROUP
+extern int dhts_jvp_variant;                 // macro_kernels.hip, DHTS_OPT_MACRO_JVP_VARIANT
 extern int dhts_micro_fwd_waves_override;    // micro_kernels.hip, DHTS_OPT_MICRO_FWD_WAVES
 extern int dhts_netstep_block;               // netstep_hybrid.hip, DHTS_OPT_NETSTEP_BLOCK
 extern int dhts_netstep_lds_kb;              // netstep_hybrid.hip, DHTS_OPT_NETSTEP_LDS_KB

@@ -1350,6 +1350,9 @@ __global__ void macro_u_tap_bwd_kernel(int64_t n, float um, const float *__restr
     }
 }
 
+// ---- forward-mode tangent sweep over the rollout tape (dhts_macro_rollout_jvp) and its glue ----------------------
+#include "macro_jvp.inc"
+
 }  // namespace dhts
 
 // ---- C ABI -----------------------------------------------------------------------------------------------
@@ -1364,6 +1367,7 @@ int dhts_fwd_waves_override = 0;
 int dhts_fwd_variant = 0;
 int dhts_fwd_rotate = 1;        // DHTS_OPT_MACRO_FWD_ROTATE: priority rotation between the two halves of the pair kernel's grid
 int dhts_fwd_group = 0;         // DHTS_OPT_MACRO_FWD_GROUP: traffic lanes per workgroup in the two-phase forward kernel (0 = heuristic)
+int dhts_jvp_variant = 0;       // DHTS_OPT_MACRO_JVP_VARIANT: 1 = the general tangent sweep for every shape
 
 static inline size_t fwd2_lds_bytes(int N) {
     return sizeof(CellRec) * (size_t)(N + 2) + 16 * (size_t)(N + 1) + sizeof(int) * (size_t)(N + 2) + 16;
@@ -1597,6 +1601,75 @@ static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
+// The tangent sweep (macro_jvp.inc): which kernel a shape takes, how many directions ride in one launch and how many launches n_dir
+// directions need.  Launches of 4, then 2, then 1 directions; a remainder of 3 runs as ONE launch of 4 with a slot masked (the tape is
+// read once instead of twice); lanes too long for the general kernel's LDS at 4 directions (two plane sets per direction) take fewer.
+static inline int jvp_width(int rem, int kmax) {          // the instantiation that carries the next launch: 3 directions ride in 4 slots
+    if (rem >= 3 && kmax >= 4) return 4;
+    int k = kmax < 2 ? kmax : 2;
+    while (k > rem) k >>= 1;
+    return k;
+}
+struct JvpPlan {
+    bool fast;
+    int block;            // threads per lane
+    int kmax;             // directions a launch may carry: 4, 2 or 1 (0: not even one fits)
+    int widest, launches; // of n_dir directions: the slots of the widest launch, the number of launches
+};
+static JvpPlan macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir) {
+    JvpPlan pl = {};
+    const int N = d->n_cells;
+    pl.fast = dhts_jvp_variant == 0 && N >= 2 && N <= 1024 && T > 0;       // (T = 0: no tape to prefetch from, and nothing is launched)
+    pl.kmax = 4;
+    if (pl.fast) {
+        pl.block = N <= 64 ? 64 : (N <= 128 ? 128 : (N <= 256 ? 256 : (N <= 512 ? 512 : 1024)));
+    } else {
+        pl.block = padded64(N) > 512 ? 512 : padded64(N);
+        while (pl.kmax > 0 && jvp_general_lds_bytes(N, pl.kmax) > 160 * 1024) pl.kmax >>= 1;
+    }
+    for (int rem = n_dir; rem > 0 && pl.kmax > 0;) {
+        int k = jvp_width(rem, pl.kmax);
+        if (!pl.launches) pl.widest = k;
+        rem -= k < rem ? k : rem;
+        ++pl.launches;
+    }
+    if (T == 0) pl.launches = 0;          // nothing to sweep: the entry point copies the tangents
+    return pl;
+}
+
+static int macro_rollout_jvp_launch(const dhts_macro_desc *d, int T, const float *tape, int n_dir, const float *t_r, const float *t_y,
+                                    const float *t_ghost, int ghost_is_sched, float *t_r_out, float *t_y_out,
+                                    const int32_t *det, int n_det, float *t_taps, dhts_error *err, void *stream) {
+    const JvpPlan pl = macro_jvp_plan(d, T, n_dir);
+    if (pl.kmax < 1) return DHTS_E_INVALID;
+    const int L = d->n_lanes, N = d->n_cells, B = pl.block;
+    const float4 *tp = reinterpret_cast<const float4 *>(tape);
+    const double cc = d->dt / d->dx;
+    const int ghost_mode = !t_ghost ? 0 : (ghost_is_sched ? 2 : 1);
+    const size_t dir_state = (size_t)L * N, dir_ghost = (ghost_mode == 2 ? (size_t)T : 1) * L * 4, dir_taps = (size_t)T * L * 2 * n_det;
+    bool lds_ok = true;
+    for (int k0 = 0; k0 < n_dir && lds_ok;) {
+        const int kk = jvp_width(n_dir - k0, pl.kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+        const float *a_r = t_r + k0 * dir_state, *a_y = t_y + k0 * dir_state, *a_g = t_ghost ? t_ghost + k0 * dir_ghost : nullptr;
+        float *o_r = t_r_out + k0 * dir_state, *o_y = t_y_out + k0 * dir_state, *o_t = det ? t_taps + k0 * dir_taps : nullptr;
+        pick<4, 2, 1>(kk, [&](auto kv) {
+            constexpr int kK = decltype(kv)::value;
+            if (pl.fast) {
+                pick<64, 128, 256, 512, 1024>(B, [&](auto bv) {
+                    constexpr int kB = decltype(bv)::value;
+                    lds_ok = launch_lds(macro_rollout_jvp_fast_kernel<kB, kK>, L, B, jvp_fast_lds_bytes(kB, kK), kLdsDefault, stream, L, N, T, cc,
+                                        tp, a_r, a_y, a_g, ghost_mode, n_act, o_r, o_y, det, n_det, o_t, err);
+                });
+            } else {
+                lds_ok = launch_lds(macro_rollout_jvp_kernel<kK>, L, B, jvp_general_lds_bytes(N, kK), kLdsDefault, stream, L, N, T, cc, tp, a_r,
+                                    a_y, a_g, ghost_mode, n_act, o_r, o_y, det, n_det, o_t, err);
+            }
+        });
+        k0 += n_act;
+    }
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+
 #ifdef DHTS_FWD3_STAMPS
 extern "C" int dhts_debug_fwd_clock(long long *out) {         // [2 kernels][16 workgroups][2]
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(dhts::dhts_fwd_clock), sizeof(long long) * 2 * 16 * 2) == hipSuccess ? 0 : -1;
@@ -1748,6 +1821,45 @@ int dhts_macro_step_fwd(const dhts_macro_desc *d,
 int dhts_macro_step_bwd(const dhts_macro_desc *d, const float *tape, const float *g_r, const float *g_y,
                         float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
     return macro_blocks_bwd_launch(d, 1, tape, g_r, g_y, nullptr, g_r_out, g_y_out, g_ghost, err, stream);
+}
+
+// ---- the tangent sweep ----------------------------------------------------------------------------------------------------------
+int dhts_macro_rollout_jvp(const dhts_macro_desc *d, int T, const float *tape, int n_dir, const float *t_r, const float *t_y,
+                           const float *t_ghost, int ghost_is_sched, float *t_r_out, float *t_y_out,
+                           const int32_t *det, int n_det, float *t_taps, dhts_error *err, void *stream) {
+    if (!macro_desc_ok(d) || T < 0 || n_dir < 1 || (T > 0 && !tape) || !t_r || !t_y || !t_r_out || !t_y_out) return DHTS_E_INVALID;
+    if ((det != nullptr) != (t_taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells))) return DHTS_E_INVALID;
+    if (ghost_is_sched && !t_ghost) return DHTS_E_INVALID;       // a schedule that is not there (zero boundary tangents: NULL with 0)
+    if (T == 0) {                                                // no step: the tangents come back as they went in, no row is read or written
+        const size_t bytes = sizeof(float) * (size_t)n_dir * d->n_lanes * d->n_cells;
+        if (t_r_out != t_r && hipMemcpyAsync(t_r_out, t_r, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        if (t_y_out != t_y && hipMemcpyAsync(t_y_out, t_y, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        return DHTS_OK;
+    }
+    return macro_rollout_jvp_launch(d, T, tape, n_dir, t_r, t_y, t_ghost, ghost_is_sched, t_r_out, t_y_out, det, det ? n_det : 0, t_taps, err,
+                                    stream);
+}
+int dhts_macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]) {
+    if (!macro_desc_ok(d) || T < 0 || n_dir < 1 || !plan || n_det < 0 || n_det > d->n_cells) return DHTS_E_INVALID;
+    const JvpPlan pl = macro_jvp_plan(d, T, n_dir);
+    if (pl.kmax < 1) return DHTS_E_INVALID;
+    plan[0] = pl.fast ? 1 : 0; plan[1] = pl.block; plan[2] = pl.widest; plan[3] = pl.launches;
+    plan[4] = plan[5] = plan[6] = plan[7] = 0;
+    return DHTS_OK;
+}
+int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,
+                                 void *stream) {
+    if (n < 0 || !r || !u || !t_r || !t_u || !t_y) return DHTS_E_INVALID;
+    if (n == 0) return DHTS_OK;
+    launch(macro_state_from_ru_jvp_kernel, grid_1d(n), 256, 0, stream, n, (float)u_max, r, u, t_r, t_u, t_y);
+    return launch_status();
+}
+int dhts_macro_u_tap_jvp(int64_t n, double u_max, const float *r, const float *y, const float *t_r, const float *t_y, float *t_u,
+                         void *stream) {
+    if (n < 0 || !r || !y || !t_r || !t_y || !t_u) return DHTS_E_INVALID;
+    if (n == 0) return DHTS_OK;
+    launch(macro_u_tap_jvp_kernel, grid_1d(n), 256, 0, stream, n, (float)u_max, r, y, t_r, t_y, t_u);
+    return launch_status();
 }
 
 }  // extern "C"

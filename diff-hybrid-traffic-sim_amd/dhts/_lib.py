@@ -23,6 +23,7 @@ OPT_NETSTEP_LDS_KB = 6
 OPT_NETSTEP_BLOCK = 7
 OPT_HYB_PACK = 8
 OPT_REWARD_CHAIN = 9
+OPT_MACRO_JVP_VARIANT = 11
 MACRO_MAX_CELLS = 4000
 MICRO_MAX_VEHICLES = 1024
 
@@ -95,6 +96,10 @@ SIGNATURES = {
     "dhts_macro_rollout_fwd_taps": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 6 + [C.c_int] + [_P] * 3),
     "dhts_macro_rollout_bwd_taps": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 4 + [C.c_int] + [_P] * 4 + [C.c_int] + [_P] * 2),
     "dhts_macro_taps_plan": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
+    "dhts_macro_rollout_jvp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, _P, C.c_int] + [_P] * 3 + [C.c_int] + [_P] * 3 + [C.c_int] + [_P] * 3),
+    "dhts_macro_jvp_plan": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
+    "dhts_macro_state_from_ru_jvp": (C.c_int, [C.c_int64, C.c_double] + [_P] * 6),
+    "dhts_macro_u_tap_jvp": (C.c_int, [C.c_int64, C.c_double] + [_P] * 6),
     "dhts_macro_tape_expand": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 3),
     "dhts_macro_step_fwd": (C.c_int, [C.POINTER(MacroDesc)] + [_P] * 12),
     "dhts_macro_step_bwd": (C.c_int, [C.POINTER(MacroDesc)] + [_P] * 8),

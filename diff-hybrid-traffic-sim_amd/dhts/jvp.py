@@ -1,0 +1,97 @@
+"""Forward-mode differentiation of the fused ARZ rollout: dhts.macro_rollout_jvp, K Jacobian-vector products in one pass over the
+rollout tape (dhts_macro_rollout_jvp, include/dhts.h).  The raw operators are in dhts.ops; MacroRollout (reverse mode) is untouched."""
+import torch
+
+from . import ops
+
+
+def _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u):
+    """Shape checks of dhts.macro_rollout_jvp's tangents (ValueError, before anything touches a device).  Returns K."""
+    given = [(n, t) for n, t in (("t_r0", t_r0), ("t_u0", t_u0), ("t_ghost_r", t_ghost_r), ("t_ghost_u", t_ghost_u)) if t is not None]
+    if not given:
+        raise ValueError("macro_rollout_jvp needs at least one of t_r0, t_u0, t_ghost_r, t_ghost_u")
+    if r0.dim() != 2:
+        raise ValueError("r0 must be [L][N]")
+    L, N = r0.shape
+    for n, t in given:
+        if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] < 1:
+            raise ValueError("%s must be a tensor with a leading direction axis K >= 1" % n)
+    K = int(given[0][1].shape[0])
+    want_g = (K, int(T), L, 2) if ghost_r.dim() == 3 else (K, L, 2)
+    for n, t in given:
+        want = (K, L, N) if n in ("t_r0", "t_u0") else want_g
+        if tuple(t.shape) != want:
+            raise ValueError("%s must have shape %s (got %s): all tangents share K = %d, boundary tangents follow the form of ghost_r"
+                             % (n, want, tuple(t.shape), K))
+    return K
+
+
+def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, t_u0=None, t_ghost_r=None, t_ghost_u=None,
+                      detectors=None, check_faults=True):
+    """dhts.macro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
+
+    Returns ((rT, yT, uT, qT[, readings]), (t_rT, t_yT, t_uT[, t_readings])).  The primal outputs are those of
+    dhts.macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, detectors=detectors) bit for bit.  The tangents carry a leading
+    direction axis K: t_r0, t_u0 [K][L][N]; t_ghost_r, t_ghost_u [K][L][2], or [K][T][L][2] when ghost_r, ghost_u are a schedule
+    [T][L][2].  At least one is given, all share K, a missing one is zero; anything else is a ValueError before anything touches a device.
+    Direction i of the outputs is J applied to direction i of the inputs: t_rT, t_yT, t_uT [K][L][N] and, with detectors, t_readings
+    [K][T][L][3][D], the tangent of (r, y, u) of cell detectors[j] after every step.  Nothing returned here is differentiable (no
+    autograd graph is recorded; the inputs are read as constants): for gradients use dhts.macro_rollout."""
+    if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
+        raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
+    T = int(T)
+    K = _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u)
+    L, N = r0.shape
+    sched = ghost_r.dim() == 3
+    want = (T, L, 2) if sched else (L, 2)
+    if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want or tuple(u0.shape) != (L, N):
+        raise ValueError("u0 must have the shape of r0, ghost_r and ghost_u shape %s" % (want,))
+    det = None if detectors is None else ops._detector_indices(detectors, N, r0.device)
+    desc = ops.macro_desc(L, N, dt, dx, u_max)
+    with torch.no_grad():
+        # the forward rollout with a tape, as MacroRollout.forward runs it
+        r0c, u0c = ops._f32c(r0.detach(), "r0"), ops._f32c(u0.detach(), "u0")
+        gr, gu = ops._f32c(ghost_r.detach(), "ghost_r"), ops._f32c(ghost_u.detach(), "ghost_u")
+        y0, q0 = ops.macro_state_from_ru(r0c, u0c, u_max)
+        gy, gq = ops.macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
+        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()
+        tape = torch.empty(ops.macro_tape_numel(desc, T), dtype=torch.float32, device=r0c.device)
+        err = ops.new_error_record(r0c.device)
+        readings = None
+        if det is not None:
+            (rT, yT, uT, qT), readings = ops.macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
+        else:
+            fwd = ops.macro_rollout_fwd_sched if sched else ops.macro_rollout_fwd
+            rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, err=err)
+        if check_faults:
+            ops.raise_on_fault(err)
+        # the leaves' tangents -> tangents of (r, y)
+        dev = r0c.device
+
+        def tan(t, shape):
+            return torch.zeros(shape, dtype=torch.float32, device=dev) if t is None else ops._f32c(t.detach(), "tangent")
+
+        tr0, tu0 = tan(t_r0, (K, L, N)), tan(t_u0, (K, L, N))
+        ty0 = ops.macro_state_from_ru_jvp(r0c.expand(K, L, N), u0c.expand(K, L, N), tr0, tu0, u_max)
+        t_ghost = None
+        if (t_ghost_r is not None or t_ghost_u is not None) and gr.numel():
+            tgr, tgu = tan(t_ghost_r, (K,) + want), tan(t_ghost_u, (K,) + want)
+            tgy = ops.macro_state_from_ru_jvp(gr.expand((K,) + want), gu.expand((K,) + want), tgr, tgu, u_max)
+            t_ghost = torch.stack([tgr, tgy], dim=-1).contiguous()          # [K][L][2][2], or [K][T][L][2][2]
+        err = ops.new_error_record(dev)
+        t_rT, t_yT, t_taps = ops.macro_rollout_jvp(desc, T, tape if T > 0 else None, tr0, ty0, t_ghost=t_ghost, det=det, err=err)
+        if check_faults:
+            ops.raise_on_fault(err)
+        t_uT = ops.macro_u_tap_jvp(rT.expand(K, L, N), yT.expand(K, L, N), t_rT, t_yT, u_max)
+        primal = (rT, yT, uT, qT)
+        if det is None:
+            return primal, (t_rT, t_yT, t_uT)
+        D = det.numel()
+        if T > 0:
+            sr, sy = readings[:, :, 0].expand(K, T, L, D), readings[:, :, 1].expand(K, T, L, D)
+            tsr, tsy = t_taps[:, :, :, 0].contiguous(), t_taps[:, :, :, 1].contiguous()
+            tsu = ops.macro_u_tap_jvp(sr, sy, tsr, tsy, u_max)
+            t_readings = torch.stack([tsr, tsy, tsu], dim=3).contiguous()
+        else:
+            t_readings = torch.zeros(K, 0, L, 3, D, dtype=torch.float32, device=dev)
+        return primal + (readings,), (t_rT, t_yT, t_uT, t_readings)

@@ -393,6 +393,79 @@ def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, c
     return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist, check_faults, det)
 
 
+# ---- forward mode: Jacobian-vector products over the rollout tape ---------------------------------------------------------------------
+def macro_state_from_ru_jvp(r, u, t_r, t_u, u_max):
+    """t_y = (dy/dr) t_r + (dy/du) t_u of y = r (u - u_eq(r)), elementwise; all four of one shape."""
+    r, u, t_r, t_u = (_f32c(t, n) for t, n in ((r, "r"), (u, "u"), (t_r, "t_r"), (t_u, "t_u")))
+    if not (r.shape == u.shape == t_r.shape == t_u.shape):
+        raise ValueError("r, u, t_r and t_u must have one shape")
+    t_y = torch.empty_like(r)
+    check(_lib.lib().dhts_macro_state_from_ru_jvp(r.numel(), float(u_max), _ptr(r), _ptr(u), _ptr(t_r), _ptr(t_u), _ptr(t_y), _stream()),
+          "dhts_macro_state_from_ru_jvp")
+    return t_y
+
+
+def macro_u_tap_jvp(r, y, t_r, t_y, u_max):
+    """t_u = (du/dr) t_r + (du/dy) t_y of the speed tap u = y / max(r, eps) + u_eq(max(r, eps)), elementwise; all four of one shape."""
+    r, y, t_r, t_y = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (t_r, "t_r"), (t_y, "t_y")))
+    if not (r.shape == y.shape == t_r.shape == t_y.shape):
+        raise ValueError("r, y, t_r and t_y must have one shape")
+    t_u = torch.empty_like(r)
+    check(_lib.lib().dhts_macro_u_tap_jvp(r.numel(), float(u_max), _ptr(r), _ptr(y), _ptr(t_r), _ptr(t_y), _ptr(t_u), _stream()),
+          "dhts_macro_u_tap_jvp")
+    return t_u
+
+
+def macro_rollout_jvp(desc, T, tape, t_r, t_y, t_ghost=None, det=None, err=None, out=None, t_taps=None):
+    """The tangent sweep over a rollout tape (include/dhts.h): t_r, t_y [K][L][N]; t_ghost None (zero), [K][L][2][2] (the same tangent in
+    front of every step) or a schedule [K][T][L][2][2], (left, right) x (r, y); det int32 CUDA [D] or None.  Returns (t_rT, t_yT, t_taps):
+    t_taps [K][T][L][2][D] = the tangent of (r, y) of cell det[j] after every step, None without det."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    if t_r.dim() != 3 or tuple(t_r.shape[1:]) != (L, N) or t_r.shape[0] < 1 or t_y.shape != t_r.shape:
+        raise ValueError("t_r and t_y must have shape (K, %d, %d) with K >= 1" % (L, N))
+    K = int(t_r.shape[0])
+    t_r, t_y = _f32c(t_r, "t_r"), _f32c(t_y, "t_y")
+    sched = False
+    if t_ghost is not None:
+        sched = t_ghost.dim() == 5
+        want = (K, T, L, 2, 2) if sched else (K, L, 2, 2)
+        if tuple(t_ghost.shape) != want:
+            raise ValueError("t_ghost must have shape (%d, %d, 2, 2) or (%d, %d, %d, 2, 2)" % (K, L, K, T, L))
+        t_ghost = _f32c(t_ghost, "t_ghost")
+        if not t_ghost.numel():          # (a schedule of no steps: no row, and an empty tensor has no address)
+            t_ghost, sched = None, False
+    D = 0
+    if det is not None:
+        det = _det_i32(det, N)
+        D = det.numel()
+        if t_taps is None:
+            t_taps = torch.empty(K, T, L, 2, D, dtype=torch.float32, device=t_r.device)
+        elif tuple(t_taps.shape) != (K, T, L, 2, D) or t_taps.dtype != torch.float32 or not t_taps.is_cuda or not t_taps.is_contiguous():
+            raise ValueError("t_taps must be a contiguous float32 CUDA tensor of shape (%d, %d, %d, 2, %d)" % (K, T, L, D))
+    elif t_taps is not None:
+        raise ValueError("t_taps without det")
+    if T > 0 and tape is None:
+        raise ValueError("a sweep of T > 0 steps needs the rollout's tape")
+    if out is None:
+        out = (torch.empty_like(t_r), torch.empty_like(t_y))
+    taps_ptr = None if det is None else C.c_void_p(t_taps.data_ptr() or det.data_ptr())      # (T = 0: no address, no row)
+    check(_lib.lib().dhts_macro_rollout_jvp(C.byref(desc), T, _ptr(tape), K, _ptr(t_r), _ptr(t_y), _ptr(t_ghost), int(sched),
+                                            _ptr(out[0]), _ptr(out[1]), _ptr(det), D, taps_ptr, _ptr(err), _stream()),
+          "dhts_macro_rollout_jvp")
+    return out[0], out[1], t_taps
+
+
+_MACRO_JVP_PLAN_KEYS = ("kernel", "block", "dirs_per_launch", "launches")
+
+
+def macro_jvp_plan(desc, T, n_dir, n_det=0):
+    """What dhts_macro_rollout_jvp launches for this shape: kernel 0 = general, 1 = fast; its block; the directions of the widest launch;
+    the number of launches (0 for T = 0)."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_macro_jvp_plan(C.byref(desc), int(T), int(n_dir), int(n_det), C.byref(plan)), "dhts_macro_jvp_plan")
+    return dict(zip(_MACRO_JVP_PLAN_KEYS, list(plan)))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # micro
 # ---------------------------------------------------------------------------------------------------------

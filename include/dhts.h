@@ -116,6 +116,10 @@ int dhts_device_count(void);
  * float32 rounding, 6e-6 relative at config 4).  An evaluation episode follows the reference's mixed chain (a Python float
  * until the first cell lane's tensor term joins it).  0 (default).  The queue terms and the gradient are the same either way. */
 #define DHTS_OPT_REWARD_CHAIN 9
+/* DHTS_OPT_MACRO_JVP_VARIANT: kernel behind dhts_macro_rollout_jvp: 0 = heuristic (one cell per thread with the tangents in registers
+ * for lanes of 2 .. 1024 cells, the general kernel otherwise), 1 = the general kernel for every shape (tests hold the fast kernel to it).
+ * Same results bit for bit.  (Option 10 is not assigned: dhts_set_option(10, ...) is DHTS_E_INVALID, as for every unknown option.) */
+#define DHTS_OPT_MACRO_JVP_VARIANT 11
 int dhts_set_option(int option, int value);
 /* cells / vehicle slots rounded up to the tape's padded width (multiple of 64) */
 int dhts_padded(int n);
@@ -263,6 +267,41 @@ int dhts_macro_rollout_bwd_taps(const dhts_macro_desc *d, int T, const float *ta
                                 const int32_t *det, int n_det, const float *g_taps,
                                 float *g_r_out, float *g_y_out, double *g_ghost, int ghost_is_sched, dhts_error *err, void *stream);
 int dhts_macro_taps_plan(const dhts_macro_desc *d, int T, int n_det, int32_t plan[8]);
+
+/*
+ * Forward-mode tangent sweep (Jacobian-vector products) over a rollout tape: n_dir = K directions in one call, oldest step first.
+ * The sweep applies the cell blocks the reverse sweep applies transposed (dqs[a][0 .. 2], rebuilt from the tape with the same float32
+ * operations; dhts_macro_tape_expand writes them out), row-major 2 x 2 in (r, y):
+ *     t'_k = (dqs[k][1] t_k + dqs[k][0] t_{k-1}) + dqs[k][2] t_{k+1},   every 2-term product a float32 multiply + fused multiply-add,
+ * with t_{-1} / t_{n_cells} the tangent of the left / right boundary cell of that step.  The tape of a step is read once for up to four
+ * directions (launches of 4, then 2, then 1 directions, a remainder of 3 as one launch of 4 with a slot masked: dhts_macro_jvp_plan).  The result of a direction does not depend on K, on its
+ * place among the directions or on the kernel that ran it, bit for bit.
+ *   t_r, t_y            [K][lane][cell] float32: tangent of the initial (r, y); t_r_out, t_y_out: of the final one (may alias t_r, t_y)
+ *   t_ghost             tangent of the boundary cells, (left, right) x (r, y) float32: NULL = zero; [K][lane][2][2] = the same in front
+ *                       of every step (ghost_is_sched = 0); [K][T][lane][2][2] = row t read by step t and no other (ghost_is_sched != 0).
+ *                       ghost_is_sched != 0 with a NULL t_ghost is DHTS_E_INVALID (zero tangents are NULL with ghost_is_sched = 0).
+ *   det, n_det, t_taps  det NULL (then t_taps NULL too): no readings.  Else t_taps [K][T][lane][2][n_det] receives the tangent of (r, y)
+ *                       of the cells det[j] AFTER every step, where dhts_macro_rollout_fwd_taps writes taps.  The index contract is the
+ *                       taps form's: an entry outside [0, n_cells) is compared away before any address is formed; its column is not written.
+ *   err                 the first step after which a thread finds a non-finite tangent raises DHTS_FAULT_NAN (step, lane, cell).
+ * T = 0 is accepted: the tangents come back as they went in, no row of anything is read or written.  A bad descriptor, n_dir < 1, a
+ * NULL tape with T > 0, NULL t_r / t_y / t_r_out / t_y_out, det without t_taps or the reverse, n_det outside 1 .. n_cells with det:
+ * DHTS_E_INVALID, nothing is dereferenced.
+ * dhts_macro_jvp_plan: plan[0] 0 = general kernel, 1 = fast (2 <= n_cells <= 1024, T > 0)     plan[1] block size
+ *   plan[2] direction slots of the widest launch (4, 2, 1; lanes too long for the general kernel's LDS at 4 directions take fewer)
+ *   plan[3] number of launches (0 for T = 0)     plan[4 .. 7] 0.  n_det: 0 = no readings, else 1 .. n_cells.
+ */
+int dhts_macro_rollout_jvp(const dhts_macro_desc *d, int T, const float *tape, int n_dir,
+                           const float *t_r, const float *t_y, const float *t_ghost, int ghost_is_sched,
+                           float *t_r_out, float *t_y_out, const int32_t *det, int n_det, float *t_taps,
+                           dhts_error *err, void *stream);
+int dhts_macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]);
+/* tangent of y = r (u - u_eq(r)): t_y = (dy/dr) t_r + (dy/du) t_u, the partials dhts_macro_state_from_ru_bwd applies, in float32 */
+int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u,
+                                 float *t_y, void *stream);
+/* tangent of the speed tap: t_u = (du/dr) t_r + (du/dy) t_y, the partials of dhts_macro_u_tap_bwd (below eps the density is a constant) */
+int dhts_macro_u_tap_jvp(int64_t n, double u_max, const float *r, const float *y, const float *t_r, const float *t_y,
+                         float *t_u, void *stream);
 
 /* One step = the drop-in for a batch of dMacroForwardLayer.forward / .backward calls (T = 1 of the above;
  * tape is one step's worth).
