@@ -411,6 +411,9 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_bwd_kernel(int R, int L, 
     const bool is_sg = tid >= sg_base && tid < sg_base + sq;
     const int sg_q = tid - sg_base;
     float g_r = 0.f, g_y = 0.f;          // cotangent of this thread's cell at time t+1
+    // cotangent of the stored downstream ghost (side-1 ghost thread): the forward keeps every step's blended ghost and a sink lane reads
+    // it back as the next step's green value, so a SIGNALLED sink lane's earlier signals act through it (none exists in an itscp grid)
+    float gown_r = 0.f, gown_u = 0.f;
     double ga = 0.;                      // thread q < sq: d reward / d action[cur_phase * sq + q], flushed when the phase changes
     int cur_phase = -1;
     int bad_step = -1;          // first non-finite cotangent this thread meets (reverse order: the latest step)
@@ -494,13 +497,14 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_bwd_kernel(int R, int L, 
                 const float s2 = soft_switch(sg - 0.5f, kSigK);
                 const float fr = s2 * grn_r + (1.0f - s2) * 1.0f, fu = s2 * grn_u + (1.0f - s2) * 0.0f;
                 const int lastc = g_off + g_n - 1;
-                float g_fr = c2[lastc], g_fu = 0.f;
+                float g_fr = c2[lastc] + gown_r, g_fu = gown_u;      // the blended ghost is also the stored one
                 glue_y_bwd(fr, fu, um, c2[C + lastc], g_fr, g_fu);
                 if (src >= 0) {
                     add_r = g_fr * s2;
                     glue_u_bwd(Hc[first], Hc[C + first], um, g_fu * s2, add_r, add_y);
                     tgt = (float)first;
-                }
+                    gown_r = 0.f; gown_u = 0.f;
+                } else { gown_r = g_fr * s2; gown_u = g_fu * s2; }
                 if (g_kind != 0) {
                     const float g_s2 = g_fr * (grn_r - 1.0f) + g_fu * grn_u;
                     const float g_sig = g_s2 * soft_switch_grad(sg - 0.5f, kSigK);
@@ -576,6 +580,18 @@ static inline int net_fwd_block(const dhts_net_desc *d, bool &loss_waves) {
     loss_waves = B <= 1024;
     return loss_waves ? B : Bp;
 }
+// What the fused pair launches for a network: the forward's block with or without wavefronts of their own for the loss and the
+// launch-bounds instantiation each kernel takes (it sets the vector registers a thread may take).  The launches below and
+// dhts_net_macro_plan read this one struct.
+struct NetMacroPlan { int fwd_block; bool loss_waves; int fwd_bound, bwd_block, bwd_bound; };
+static inline NetMacroPlan net_macro_plan(const dhts_net_desc *d) {
+    NetMacroPlan p;
+    p.fwd_block = net_fwd_block(d, p.loss_waves);
+    p.fwd_bound = p.fwd_block <= 512 ? 512 : (p.fwd_block <= 640 ? 640 : 1024);
+    p.bwd_block = net_block(d);
+    p.bwd_bound = p.bwd_block <= 512 ? 512 : 1024;
+    return p;
+}
 static inline NetTables net_tables(const dhts_net_tables *t) {
     NetTables n;
     n.lane_ncell = t->lane_ncell; n.lane_off = t->lane_off; n.sig_kind = t->sig_kind; n.inter = t->inter; n.lane_dx = t->lane_dx;
@@ -599,18 +615,27 @@ size_t dhts_net_macro_tape_bytes(const dhts_net_desc *d) {
     return net_desc_ok(d) ? sizeof(float4) * (size_t)d->n_replicas * d->n_steps * 3 * padded64(d->n_cells) : 0;
 }
 
+int dhts_net_macro_plan(const dhts_net_desc *d, int32_t plan[8]) {
+    if (!net_desc_ok(d) || !plan) return DHTS_E_INVALID;
+    const NetMacroPlan p = net_macro_plan(d);
+    plan[0] = p.fwd_block; plan[1] = p.loss_waves ? 1 : 0; plan[2] = p.fwd_bound; plan[3] = p.bwd_block; plan[4] = p.bwd_bound;
+    plan[5] = plan[6] = plan[7] = 0;
+    return DHTS_OK;
+}
+
 int dhts_net_macro_rollout_fwd(const dhts_net_desc *d, const dhts_net_tables *t, const float *action, float *hist, float *tape,
                                float *kc, float *queue, float *reward, float *workspace, dhts_error *err, void *stream) {
     if (!net_desc_ok(d) || !net_tables_ok(t) || !action || !hist || !tape || !kc || !queue || !reward || !workspace)
         return DHTS_E_INVALID;
-    bool lw;
-    const int B = net_fwd_block(d, lw), L = d->n_lanes, C = d->n_cells;
+    const NetMacroPlan pl = net_macro_plan(d);
+    const bool lw = pl.loss_waves;
+    const int B = pl.fwd_block, L = d->n_lanes, C = d->n_cells;
     const size_t lds = net_fwd_lds_base(L, C) + net_staged_bytes(L, d->n_inter_sq, d->n_action);
     if (lds > 160 * 1024) return DHTS_E_INVALID;
     bool lds_ok = true;
     // (the block-size bound sets the vector registers a thread may take)
     pick<0, 1>(lw, [&](auto w) {
-        pick<1024, 640, 512>(B <= 512 ? 512 : (B <= 640 ? 640 : 1024), [&](auto mb) {
+        pick<1024, 640, 512>(pl.fwd_bound, [&](auto mb) {
             const auto kern = net_macro_fwd_kernel<false, decltype(w)::value != 0, decltype(mb)::value>;
             if ((lds_ok = allow_lds(kern, lds)))
                 launch(kern, d->n_replicas, B, lds, stream, d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action,
@@ -643,12 +668,13 @@ int dhts_net_macro_rollout_bwd(const dhts_net_desc *d, const dhts_net_tables *t,
                                const float *workspace, dhts_error *err, void *stream) {
     if (!net_desc_ok(d) || !net_tables_ok(t) || !action || !hist || !tape || !kc || !queue || !g_action || !workspace)
         return DHTS_E_INVALID;
-    const int B = net_block(d), L = d->n_lanes, C = d->n_cells;
+    const NetMacroPlan pl = net_macro_plan(d);
+    const int B = pl.bwd_block, L = d->n_lanes, C = d->n_cells;
     const int E = t->n_edges > 0 ? t->n_edges : 1;
     const size_t lds = net_bwd_lds_base(L, C, E, d->n_inter_sq) + net_staged_bytes(L, d->n_inter_sq, d->n_action);
     if (lds > 160 * 1024) return DHTS_E_INVALID;
     bool lds_ok = true;
-    pick<1024, 512>(B <= 512 ? 512 : 1024, [&](auto mb) {
+    pick<1024, 512>(pl.bwd_bound, [&](auto mb) {
         const auto kern = net_macro_bwd_kernel<decltype(mb)::value>;
         if ((lds_ok = allow_lds(kern, lds)))
             launch(kern, d->n_replicas, B, lds, stream, d->n_replicas, L, C, d->n_steps, d->n_inter_sq, d->frames_per_phase, d->n_action,

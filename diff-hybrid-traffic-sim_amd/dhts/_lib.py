@@ -105,6 +105,7 @@ SIGNATURES = {
     "dhts_macro_step_bwd": (C.c_int, [C.POINTER(MacroDesc)] + [_P] * 8),
     "dhts_net_macro_hist_bytes": (C.c_size_t, [C.POINTER(NetDesc)]),
     "dhts_net_macro_tape_bytes": (C.c_size_t, [C.POINTER(NetDesc)]),
+    "dhts_net_macro_plan": (C.c_int, [C.POINTER(NetDesc), C.POINTER(C.c_int32 * 8)]),
     "dhts_net_macro_rollout_fwd": (C.c_int, [C.POINTER(NetDesc), C.POINTER(NetTables)] + [_P] * 9),
     "dhts_net_macro_rollout_eval": (C.c_int, [C.POINTER(NetDesc), C.POINTER(NetTables)] + [_P] * 5),
     "dhts_net_macro_rollout_bwd": (C.c_int, [C.POINTER(NetDesc), C.POINTER(NetTables)] + [_P] * 10),

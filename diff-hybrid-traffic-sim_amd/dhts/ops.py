@@ -854,6 +854,21 @@ def net_macro_eval(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, 
     return reward, queue
 
 
+_NET_MACRO_PLAN_KEYS = ("fwd_block", "loss_waves", "fwd_bound", "bwd_block", "bwd_bound")
+
+
+def net_macro_plan(n_action, dev_tables, n_inter_sq=1, frames_per_phase=1, dt=1.0 / 30.0, u_max=30.0):
+    """What net_macro_rollout launches for this network (dhts_net_macro_plan): the forward kernel's block, whether it runs the loss on
+    wavefronts of its own, its launch bound; the reverse sweep's block (net_macro_eval's too) and launch bound.  `dev_tables`: anything
+    with n_lanes, n_cells, T and n_replica_tables (DeviceNetTables) -- nothing is launched."""
+    _, d = _net_desc((1, n_action), dev_tables, n_inter_sq, frames_per_phase, dt, u_max, 0.2, 5.0)
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_net_macro_plan(C.byref(d), C.byref(plan)), "dhts_net_macro_plan")
+    out = dict(zip(_NET_MACRO_PLAN_KEYS, [int(x) for x in plan]))
+    out["loss_waves"] = bool(out["loss_waves"])
+    return out
+
+
 class DeviceHybridTables:
     """dhts.network.HybridNetworkTables plus the pre-drawn vehicle routes [n_routes][stride] (int, -1 padded; the k-th
     vehicle spawned onto a lane takes the k-th route starting there, cyclically), uploaded once.  `tables` may be one

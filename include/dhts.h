@@ -481,6 +481,11 @@ typedef struct dhts_net_tables {
 } dhts_net_tables;
 size_t dhts_net_macro_hist_bytes(const dhts_net_desc *d);   /* state history [R][T+1][4][C] float32 */
 size_t dhts_net_macro_tape_bytes(const dhts_net_desc *d);   /* Jacobian tape [R][T][3][Cp][4] float32 */
+/* What the fused pair below launches for this network (the evaluation kernel takes the reverse sweep's block, bound 1024):
+ * plan[0] forward block size     plan[1] 1 = the forward runs the loss on wavefronts of its own (pad64(max(C + L, n_action)) + pad64(C)
+ * threads fit 1024), 0 = behind the physics role     plan[2] forward launch bound (512, 640 or 1024 threads)
+ * plan[3] reverse block size = pad64(max(C + L, n_action))     plan[4] reverse launch bound (512 or 1024)     plan[5..7] 0 */
+int dhts_net_macro_plan(const dhts_net_desc *d, int32_t plan[8]);
 /* action [R][n_action]; out: hist, tape, kc [R][T][C] (loss sigmoid constants), queue [R][T][L] (loss terms q^2 dt),
  * reward [R] float32 = - sum of the queue terms; workspace [R][T][2 L] float32 (kept for the reverse sweep) */
 int dhts_net_macro_rollout_fwd(const dhts_net_desc *d, const dhts_net_tables *t, const float *action, float *hist, float *tape,

@@ -1021,6 +1021,10 @@ void oracle_net_macro_bwd(const oracle_net_desc *d, const int *lane_ncell, const
     float *own_r = (float *)malloc(sizeof(float) * 2 * (size_t)L * (size_t)(T + 1));   /* stored sink ghosts per step */
     net_signal *sg = (net_signal *)malloc(sizeof(net_signal) * (size_t)d->n_inter_sq);
     double *ga = (double *)calloc((size_t)d->n_action, sizeof(double));
+    /* cotangent of every lane's stored downstream ghost (r, u): set_rightmost_cell keeps the blended tensors (_simulator.py:134-137,
+     * _macro_lane.py:160-162) and a sink lane reads them back as next step's green value (road_network.py:312-319), so a signalled
+     * sink lane's earlier signals act through the stored ghost */
+    float *g_own = (float *)calloc((size_t)2 * L, sizeof(float));
     /* replay the stored downstream ghosts of sink lanes (they only depend on themselves) */
     for (int l = 0; l < L; l++) { own_r[2 * l] = 0.f; own_r[2 * l + 1] = um; }
     for (int t = 0; t < T; t++) {
@@ -1091,12 +1095,15 @@ void oracle_net_macro_bwd(const oracle_net_desc *d, const int *lane_ncell, const
                 const float sig = lane_signal(sg, sig_kind[l], inter[l]);
                 const float s2 = soft_switch(sig - 0.5f, 32.f);
                 const float fr = s2 * grn_r + (1.0f - s2) * 1.0f, fu = s2 * grn_u + (1.0f - s2) * 0.0f;
-                float g_fr = gr_[n + 1], g_fu = 0.f;
+                float g_fr = gr_[n + 1] + g_own[2 * l], g_fu = g_own[2 * l + 1];     /* the blended ghost is also stored */
                 glue_y_bwd(fr, fu, um, gy_[n + 1], &g_fr, &g_fu);
                 if (rs >= 0) {
                     const int first = lane_off[rs];
                     gp[first] += g_fr * s2;
                     glue_u_bwd(cur[first], cur[C + first], um, g_fu * s2, &gp[first], &gp[C + first]);
+                    g_own[2 * l] = 0.f; g_own[2 * l + 1] = 0.f;
+                } else {
+                    g_own[2 * l] = g_fr * s2; g_own[2 * l + 1] = g_fu * s2;
                 }
                 if (sig_kind[l] != 0) {
                     const float g_s2 = g_fr * (grn_r - 1.0f) + g_fu * grn_u;
@@ -1110,7 +1117,7 @@ void oracle_net_macro_bwd(const oracle_net_desc *d, const int *lane_ncell, const
         float *tmp = g; g = gp; gp = tmp;
     }
     for (int k = 0; k < d->n_action; k++) g_action[k] = (float)ga[k];
-    free(g); free(gp); free(buf); free(own_r); free(sg); free(ga);
+    free(g); free(gp); free(buf); free(own_r); free(sg); free(ga); free(g_own);
 }
 
 #include "dhts_oracle_hybrid.inc"
