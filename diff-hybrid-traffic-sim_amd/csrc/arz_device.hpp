@@ -109,6 +109,16 @@ __device__ __forceinline__ void glue_y_bwd(float r, float u, float um, float g_y
 // float32 2-term dot the way NumPy's matmul accumulates it
 __device__ __forceinline__ float dot2(float a0, float b0, float a1, float b1) { return __fmaf_rn(a1, b1, a0 * b0); }
 
+// the blocks of a cell (row-major 2x2, d0 / d1 / d2 w.r.t. its left neighbour / itself / its right neighbour) from the products (A, B) of its
+// left and right interfaces, exactly as the reference forms them (dmacro_lane.py:126-129); cf = dt / dx, ncf = -cf
+__device__ __forceinline__ void cell_blocks(const float4 &aL, const float4 &bL, const float4 &aR, const float4 &bR, float cf, float ncf,
+                                            float4 &d0, float4 &d1, float4 &d2) {
+    d0.x = ncf * (-aL.x); d0.y = ncf * (-aL.y); d0.z = ncf * (-aL.z); d0.w = ncf * (-aL.w);
+    d2.x = ncf * bR.x; d2.y = ncf * bR.y; d2.z = ncf * bR.z; d2.w = ncf * bR.w;
+    d1.x = 1.f - cf * (aR.x - bL.x); d1.y = 0.f - cf * (aR.y - bL.y);
+    d1.z = 0.f - cf * (aR.z - bL.z); d1.w = 1.f - cf * (aR.w - bL.w);
+}
+
 struct Iface {
     double Fr, Fy;   // flux of Q_0: (r*u, y*u)                                  (_arz.py:94-101)
     float A[4];      // fp(Q_0) @ dQ_0/dQ_L   row-major 2x2, float32             (dmacro_lane.py:126-129)

@@ -24,10 +24,7 @@
             float we, ns, a, pr; int ai;
             phase_signal_at(act, n_action, sq, F, rev_ph, rev_fr, sg_q, we, ns, a, pr, ai);
             sg[6 * sg_q] = we; sg[6 * sg_q + 1] = ns;
-            // d sigmoid(k x) / d x = s (1 - s) k with the sigmoid values just computed (0 outside the clamp, like the operator)
-            const float zs = (a - pr) * kSigK;
-            const bool sat = zs < -16.f || zs > 16.f;
-            sg[6 * sg_q + 2] = sat ? 0.f : we * (1.f - we) * kSigK; sg[6 * sg_q + 3] = sat ? 0.f : -(ns * (1.f - ns) * kSigK);
+            signal_slopes(we, ns, a, pr, false, sg[6 * sg_q + 2], sg[6 * sg_q + 3]);
         }
         int seg_lo[kPhases], seg_n[kPhases];            // this lane's record segments of the step (micro wave)
 #pragma unroll
@@ -140,7 +137,7 @@
             }
         }
         // ghost threads: the forward blend of this step's ghost (everything that needs no cotangent), while only the micro
-        // wave has work; the cotangent part follows two phases later
+        // wave has work; the cotangent part follows two phases later (ghost_up_bwd / ghost_down_bwd of net_device.hpp, cut in two here)
         float gh_gr = 0.f, gh_gu = 0.f, gh_s = 1.f, gh_fr = 0.f, gh_fu = 0.f, gh_ds = 0.f, gh_ds2 = 0.f; int gh_cell = -1, gh_kd = 0;
         if (!kMw && is_ghost && g_macro) {
             if (g_side == 0) {
@@ -151,7 +148,7 @@
                     if (plain) gh_s = 1.f;               // (the neighbour's edge cell as it is: 1 * g + 0 * red below is exact)
                     else if (gate == -1) gh_s = 0.f;
                     else if (gate >= 0) { gh_kd = linfo[gate] & 3; it = linfo[gate] >> 2; if (gh_kd != 0) gh_s = sg[6 * it + (gh_kd - 1)]; }
-                    gh_fr = gh_gr * gh_s + 0.f * (1.0f - gh_s); gh_fu = gh_gu * gh_s + um * (1.0f - gh_s);
+                    ghost_up_blend(gh_gr, gh_gu, gh_s, um, gh_fr, gh_fu);
                     if (gh_kd != 0) gh_ds = sg[6 * it + 2 + (gh_kd - 1)];
                     if (gh_kd != 0 && it != g_inter) bad_key = true;
                 }
@@ -161,7 +158,7 @@
                 gh_gu = src < 0 ? w_own_u : Hc[2 * C + gh_cell];
                 const float sgl = g_kind != 0 ? sg[6 * g_inter + (g_kind - 1)] : 1.f;
                 gh_s = plain ? 1.f : soft_switch(sgl - 0.5f, kSigK);
-                gh_fr = gh_s * gh_gr + (1.0f - gh_s) * 1.0f; gh_fu = gh_s * gh_gu + (1.0f - gh_s) * 0.0f;
+                ghost_down_blend(gh_gr, gh_gu, gh_s, gh_fr, gh_fu);
                 if (g_kind != 0) { gh_ds = soft_switch_grad(sgl - 0.5f, kSigK); gh_ds2 = sg[6 * g_inter + 2 + (g_kind - 1)]; }
             }
         }
@@ -172,12 +169,8 @@
             const int c = tid;
             float gr = gL[c], gy = gL[C + c];
             glue_u_bwd(Hn[c], Hn[C + c], um, gL[2 * C + c], gr, gy);
-            // the cell's blocks from the interface products, exactly as the reference forms them (dmacro_lane.py:126-129)
             float4 d0, d1, d2;
-            d0.x = c_ncf * (-aL.x); d0.y = c_ncf * (-aL.y); d0.z = c_ncf * (-aL.z); d0.w = c_ncf * (-aL.w);
-            d2.x = c_ncf * bR.x; d2.y = c_ncf * bR.y; d2.z = c_ncf * bR.z; d2.w = c_ncf * bR.w;
-            d1.x = 1.f - c_cf * (aR.x - bL.x); d1.y = 0.f - c_cf * (aR.y - bL.y);
-            d1.z = 0.f - c_cf * (aR.z - bL.z); d1.w = 1.f - c_cf * (aR.w - bL.w);
+            cell_blocks(aL, bL, aR, bR, c_cf, c_ncf, d0, d1, d2);
             c0[c] = dot2(d0.x, gr, d0.z, gy); c0[C + c] = dot2(d0.y, gr, d0.w, gy);
             c2[c] = dot2(d2.x, gr, d2.z, gy); c2[C + c] = dot2(d2.y, gr, d2.w, gy);
             v_r = dot2(d1.x, gr, d1.z, gy); v_y = dot2(d1.y, gr, d1.w, gy);
@@ -208,7 +201,7 @@
                     glue_y_bwd(gh_fr, gh_fu, um, c0[C + g_off], g_fr, g_fu);
                     add_r = g_fr * gh_s; add_u = g_fu * gh_s;
                     tgt = (float)gh_cell;
-                    if (gh_kd != 0) a_val = (g_fr * gh_gr + g_fu * (gh_gu - um)) * gh_ds;
+                    if (gh_kd != 0) a_val = ghost_up_switch_bwd(g_fr, g_fu, gh_gr, gh_gu, um) * gh_ds;
                 }
             } else {
                 const int lastc = g_off + g_n - 1;
@@ -217,8 +210,7 @@
                 if (src >= 0) { add_r = g_fr * gh_s; add_u = g_fu * gh_s; tgt = (float)gh_cell; gown_r = 0.f; gown_u = 0.f; }
                 else { gown_r = g_fr * gh_s; gown_u = g_fu * gh_s; }
                 if (g_kind != 0) {
-                    const float g_s2 = g_fr * (gh_gr - 1.0f) + g_fu * gh_gu;
-                    a_val = g_s2 * gh_ds * gh_ds2;
+                    a_val = ghost_down_switch_bwd(g_fr, g_fu, gh_gr, gh_gu) * gh_ds * gh_ds2;
                 }
             }
             if (tgt >= 0.f) {

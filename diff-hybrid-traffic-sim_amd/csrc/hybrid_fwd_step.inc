@@ -31,8 +31,7 @@
                         float s = 1.f;
                         if (gate == -1) s = 0.f;
                         else if (gate >= 0) { const int kd = linfo[gate] & 3; if (kd != 0) s = sig[2 * (linfo[gate] >> 2) + (kd - 1)]; }
-                        fr = gr * s + 0.f * (1.0f - s);
-                        fu = gu * s + um * (1.0f - s);
+                        ghost_up_blend(gr, gu, s, um, fr, fu);
                     }
                     glue_from_r_u(fr, fu, um, fy, fq);
                 }
@@ -45,8 +44,7 @@
                 } else {
                     const float sg = g_kind != 0 ? sig[2 * g_inter + (g_kind - 1)] : 1.f;
                     const float s2 = kHard ? (sg > 0.5f ? 1.f : 0.f) : soft_switch(sg - 0.5f, kSigK);
-                    fr = s2 * gr + (1.0f - s2) * 1.0f;
-                    fu = s2 * gu + (1.0f - s2) * 0.0f;
+                    ghost_down_blend(gr, gu, s2, fr, fu);
                 }
                 glue_from_r_u(fr, fu, um, fy, fq);
                 own_r = fr; own_u = fu;

@@ -581,14 +581,6 @@ struct BwdPlanes {
 __device__ __forceinline__ BwdPlanes bwd_planes(float *lds, int P) {
     return BwdPlanes{lds, lds + P, lds + 2 * P, lds + 3 * P, lds + 4 * P, lds + 5 * P};
 }
-// the cell blocks from the interface products exactly as the forward forms them (dmacro_lane.py:126-129)
-__device__ __forceinline__ void cell_blocks(const float4 &aL, const float4 &bL, const float4 &aR, const float4 &bR, float cf, float ncf,
-                                            float4 &d0, float4 &d1, float4 &d2) {
-    d0.x = ncf * (-aL.x); d0.y = ncf * (-aL.y); d0.z = ncf * (-aL.z); d0.w = ncf * (-aL.w);
-    d2.x = ncf * bR.x; d2.y = ncf * bR.y; d2.z = ncf * bR.z; d2.w = ncf * bR.w;
-    d1.x = 1.f - cf * (aR.x - bL.x); d1.y = 0.f - cf * (aR.y - bL.y);
-    d1.z = 0.f - cf * (aR.z - bL.z); d1.w = 1.f - cf * (aR.w - bL.w);
-}
 
 // Reverse sweep over the single-step operator's blocked tape [lane][3][Np][4] (T = 1 from the C ABI; any T works).
 // grid = L workgroups of `blockDim.x` threads (multiple of 64); dynamic LDS = 6 * (N + 2) floats.

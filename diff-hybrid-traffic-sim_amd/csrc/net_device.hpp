@@ -1,8 +1,9 @@
-// net_device.hpp -- device helpers shared by the road-network kernels (network_kernels.hip, hybrid_kernels.hip).
+// net_device.hpp -- device helpers shared by the road-network kernels (network_kernels.hip, hybrid_kernels.hip, netstep_kernels.hip, netstep_hybrid.hip, the *_step.inc).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/dhts.h"
+#include "arz_device.hpp"    // glue_y_bwd
 #include "host_common.hpp"   // raise_fault
 
 namespace dhts {
@@ -47,6 +48,43 @@ __device__ __forceinline__ float soft_switch_grad(float value, float constant) {
     if (z < -16.f || z > 16.f) return 0.f;
     const float s = 1.f / (1.f + expf(-z));
     return s * (1.f - s) * constant;
+}
+
+// ---- the ghost exchange of a road network and its adjoint (_simulator.py:42-137, road_network.py:79-111): ONE definition for the fused
+// macro and hybrid kernels and the stepwise, persistent and batched ones.  float32, operation for operation what the reference's tensors
+// do: the 0.f * and * 0.0f terms carry NaN and infinity.  (The tests' own restatements of this math stay apart on purpose: they judge it.)
+// upstream ghost: the source lane's last cell (gr, gu) where the gate's switch s is green, an empty road (0, um) where it is red
+__device__ __forceinline__ void ghost_up_blend(float gr, float gu, float s, float um, float &fr, float &fu) {
+    fr = gr * s + 0.f * (1.0f - s); fu = gu * s + um * (1.0f - s);
+}
+// downstream ghost: the next lane's first cell (or the lane's stored ghost) where the lane's own switch s2 is green, a jam (1, 0) where red
+__device__ __forceinline__ void ghost_down_blend(float gr, float gu, float s2, float &fr, float &fu) {
+    fr = s2 * gr + (1.0f - s2) * 1.0f; fu = s2 * gu + (1.0f - s2) * 0.0f;
+}
+// Adjoints: from the step's cotangent (gg_r, gg_y) of the ghost's (r, y) to the cotangent (g_fr, g_fu) of the blended (r, u).  The caller
+// multiplies it by the switch for the source cell or the stored ghost and, under its guard, takes the switch's cotangent from the one-liners.
+// A downstream ghost is also the ghost the lane stores: gg_r comes summed with the stored ghost's cotangent of r, gg_u is that of u.
+// (References: a caller's LDS operand is read where it is used, after the blend -- the fused reverse kernel keeps its instructions.)
+__device__ __forceinline__ void ghost_up_bwd(float grn_r, float grn_u, float s, float um, const float &gg_r, const float &gg_y, float &g_fr, float &g_fu) {
+    float fr, fu; ghost_up_blend(grn_r, grn_u, s, um, fr, fu);
+    g_fr = gg_r; g_fu = 0.f; glue_y_bwd(fr, fu, um, gg_y, g_fr, g_fu);
+}
+__device__ __forceinline__ void ghost_down_bwd(float grn_r, float grn_u, float s2, float um, const float &gg_r, const float &gg_u, const float &gg_y,
+                                               float &g_fr, float &g_fu) {
+    float fr, fu; ghost_down_blend(grn_r, grn_u, s2, fr, fu);
+    g_fr = gg_r; g_fu = gg_u; glue_y_bwd(fr, fu, um, gg_y, g_fr, g_fu);
+}
+__device__ __forceinline__ float ghost_up_switch_bwd(float g_fr, float g_fu, float grn_r, float grn_u, float um) { return g_fr * grn_r + g_fu * (grn_u - um); }
+__device__ __forceinline__ float ghost_down_switch_bwd(float g_fr, float g_fu, float grn_r, float grn_u) { return g_fr * (grn_r - 1.0f) + g_fu * grn_u; }
+// Slope of a phase signal (phase_signal_at below) w.r.t. the action entry a at progress pr, of_we: the west-east signal's, else the north-south
+// one's: d sigmoid(k x) / d x = s (1 - s) k with the sigmoid values just computed, 0 outside the clamp (like the operator) and for hard signals
+__device__ __forceinline__ float signal_slope(float we, float ns, float a, float pr, bool hard, bool of_we) {
+    const float zs = (a - pr) * kSigK;
+    const bool sat = hard || zs < -16.f || zs > 16.f;
+    return sat ? 0.f : (of_we ? we * (1.f - we) * kSigK : -(ns * (1.f - ns) * kSigK));
+}
+__device__ __forceinline__ void signal_slopes(float we, float ns, float a, float pr, bool hard, float &dwe, float &dns) {   // both, for a table
+    dwe = signal_slope(we, ns, a, pr, hard, true); dns = signal_slope(we, ns, a, pr, hard, false);
 }
 
 // Workgroup barrier that only drains LDS traffic.  __syncthreads() also waits for every outstanding global load / store

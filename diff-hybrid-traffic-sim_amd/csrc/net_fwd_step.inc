@@ -27,8 +27,7 @@
                         const int kd = linfo[gate] & 3;
                         if (kd != 0) s = sig[4 * (linfo[gate] >> 2) + (kd - 1)];
                     }
-                    fr = gr * s + 0.f * (1.0f - s);
-                    fu = gu * s + um * (1.0f - s);
+                    ghost_up_blend(gr, gu, s, um, fr, fu);
                     glue_from_r_u(fr, fu, um, fy, fq);
                 }
             } else {
@@ -37,8 +36,7 @@
                 else if (!kHard) { own_w[(size_t)t * 2 * L + 2 * g_lane] = gr; own_w[(size_t)t * 2 * L + 2 * g_lane + 1] = gu; }
                 const float sg = g_kind != 0 ? sig[4 * g_inter + (g_kind - 1)] : 1.f;
                 const float s2 = kHard ? (sg > 0.5f ? 1.f : 0.f) : soft_switch(sg - 0.5f, kSigK);
-                fr = s2 * gr + (1.0f - s2) * 1.0f;
-                fu = s2 * gu + (1.0f - s2) * 0.0f;
+                ghost_down_blend(gr, gu, s2, fr, fu);
                 glue_from_r_u(fr, fu, um, fy, fq);
                 own_r = fr; own_u = fu;
             }
@@ -89,7 +87,7 @@
                 float *hn = hist_r + (size_t)(t + 1) * 4 * C;
                 hn[c] = nr; hn[C + c] = ny; hn[2 * C + c] = nu; hn[3 * C + c] = nq;
                 const float *aL = AB + (size_t)iL * 8, *aR = AB + (size_t)iR * 8;
-                float4 d0, d1, d2;
+                float4 d0, d1, d2;                      // cell_blocks (arz_device.hpp) restated on the floats of the AB slots
                 d0.x = ncf * (-aL[0]); d0.y = ncf * (-aL[1]); d0.z = ncf * (-aL[2]); d0.w = ncf * (-aL[3]);
                 d2.x = ncf * aR[4]; d2.y = ncf * aR[5]; d2.z = ncf * aR[6]; d2.w = ncf * aR[7];
                 d1.x = 1.f - cf * (aR[0] - aL[4]); d1.y = 0.f - cf * (aR[1] - aL[5]);

@@ -302,10 +302,9 @@ template <class A> __device__ __forceinline__ void ns_signal_fill(const A &a, co
         float we, ns, av, pr; int ai;
         const bool hard = a.hard != 0;
         phase_signal_at(action, a.n_action, a.sq, a.F, t / a.F, t % a.F, q, we, ns, av, pr, ai, hard, a.tensor_ladder != 0);
-        const float z = (av - pr) * kSigK;
-        const bool sat = hard || z < -16.f || z > 16.f;
         const auto s4 = a.sg + ((size_t)(t & 1) * a.sq + q) * 4;
-        s4[0] = we; s4[1] = ns; s4[2] = sat ? 0.f : we * (1.f - we) * kSigK; s4[3] = sat ? 0.f : -(ns * (1.f - ns) * kSigK);
+        s4[0] = we; s4[1] = ns;
+        signal_slopes(we, ns, av, pr, hard, s4[2], s4[3]);
         if (q == 0) a.sgi[t & 1] = ai;
     }
 }
@@ -321,11 +320,7 @@ template <class A> __device__ __forceinline__ float ns_lane_signal(const A &a, c
     } else {
         float we, ns, av, pr; int ai;
         phase_signal_at(action, a.n_action, a.sq, a.F, t / a.F, t % a.F, a.inter[lid], we, ns, av, pr, ai, hard, a.tensor_ladder != 0);
-        if (ds_da) {
-            const float z = (av - pr) * kSigK;
-            const bool sat = hard || z < -16.f || z > 16.f;
-            *ds_da = sat ? 0.f : (kd == 1 ? we * (1.f - we) * kSigK : -(ns * (1.f - ns) * kSigK));
-        }
+        if (ds_da) *ds_da = signal_slope(we, ns, av, pr, hard, kd == 1);
         if (a_index) *a_index = ai;
         return kd == 1 ? we : ns;
     }
@@ -390,8 +385,7 @@ template <class A> __device__ __forceinline__ void ns_ghost_fwd_item(const A &a,
                 float gr = 0.f, gu = um;       // ls == -3: the lane's own stored upstream ghost (its single upstream lane is micro)
                 if (ls >= 0) { const int last = a.lane_off[ls] + a.lane_ncell[ls] - 1; gr = cur[last]; gu = cur[2 * C + last]; }
                 const float s = lg == -1 ? 0.f : (lg == -2 ? 1.f : ns_lane_signal(a, action, t, lg, hard, nullptr, nullptr));
-                fr = gr * s + 0.f * (1.0f - s);
-                fu = gu * s + um * (1.0f - s);
+                ghost_up_blend(gr, gu, s, um, fr, fu);
                 glue_from_r_u(fr, fu, um, fy, fq);
             }
         } else {
@@ -400,8 +394,7 @@ template <class A> __device__ __forceinline__ void ns_ghost_fwd_item(const A &a,
             if (rs >= 0) { const int first = a.lane_off[rs]; gr = cur[first]; gu = cur[2 * C + first]; }
             const float sg = ns_lane_signal(a, action, t, lane, hard, nullptr, nullptr);
             const float s2 = hard ? (sg > 0.5f ? 1.f : 0.f) : soft_switch(sg - 0.5f, kSigK);
-            fr = s2 * gr + (1.0f - s2) * 1.0f;
-            fu = s2 * gu + (1.0f - s2) * 0.0f;
+            ghost_down_blend(gr, gu, s2, fr, fu);
             glue_from_r_u(fr, fu, um, fy, fq);
             own_out[2 * lane] = fr; own_out[2 * lane + 1] = fu;
             if constexpr (A::kTB) { const auto o = a.ow + (size_t)((t + 1) & 1) * 2 * L; o[2 * lane] = fr; o[2 * lane + 1] = fu; }
@@ -1272,11 +1265,10 @@ template <class A> __device__ __forceinline__ void ns_ghost_bwd_item(const A &a,
                 float s = 1.f, ds = 0.f; int ai = -1;
                 if (lg == -1) s = 0.f;
                 else if (lg >= 0) s = ns_lane_signal(a, action, t, lg, false, &ds, &ai);
-                const float fr = grn_r * s + 0.f * (1.0f - s), fu = grn_u * s + um * (1.0f - s);
-                float g_fr = gg_r, g_fu = 0.f;
-                glue_y_bwd(fr, fu, um, gg_y, g_fr, g_fu);
+                float g_fr, g_fu;
+                ghost_up_bwd(grn_r, grn_u, s, um, gg_r, gg_y, g_fr, g_fu);
                 add_r = g_fr * s; add_u = g_fu * s;
-                if (ai >= 0) { a_val = (g_fr * grn_r + g_fu * (grn_u - um)) * ds; a_key = ai; }
+                if (ai >= 0) { a_val = ghost_up_switch_bwd(g_fr, g_fu, grn_r, grn_u, um) * ds; a_key = ai; }
             }
         } else {
             const int rs = rw.right_src[lane];
@@ -1288,15 +1280,11 @@ template <class A> __device__ __forceinline__ void ns_ghost_bwd_item(const A &a,
             float ds = 0.f; int ai = -1;
             const float sg = ns_lane_signal(a, action, t, lane, false, &ds, &ai);
             const float s2 = soft_switch(sg - 0.5f, kSigK);
-            const float fr = s2 * grn_r + (1.0f - s2) * 1.0f, fu = s2 * grn_u + (1.0f - s2) * 0.0f;
-            float g_fr = gg_r + g_own[2 * lane], g_fu = g_own[2 * lane + 1];       // the blended ghost is also the stored one
-            glue_y_bwd(fr, fu, um, gg_y, g_fr, g_fu);
+            float g_fr, g_fu;                            // (the blended ghost is also the stored one: its cotangent joins the step's)
+            ghost_down_bwd(grn_r, grn_u, s2, um, gg_r + g_own[2 * lane], g_own[2 * lane + 1], gg_y, g_fr, g_fu);
             if (rs >= 0) { add_r = g_fr * s2; add_u = g_fu * s2; g_own[2 * lane] = 0.f; g_own[2 * lane + 1] = 0.f; }
             else { g_own[2 * lane] = g_fr * s2; g_own[2 * lane + 1] = g_fu * s2; }
-            if (ai >= 0) {
-                const float g_s2 = g_fr * (grn_r - 1.0f) + g_fu * grn_u;
-                a_val = g_s2 * soft_switch_grad(sg - 0.5f, kSigK) * ds; a_key = ai;
-            }
+            if (ai >= 0) { a_val = ghost_down_switch_bwd(g_fr, g_fu, grn_r, grn_u) * soft_switch_grad(sg - 0.5f, kSigK) * ds; a_key = ai; }
         }
     }
     sl[0] = add_r; sl[1] = add_u; sl[2] = a_val; sl[3] = (float)a_key;

@@ -6,7 +6,8 @@
 // step as ONE batch per (cells, cell length) group through dhts_macro_step_fwd -- the straight-lane operator, whose ghosts
 // are inputs -- and the adjoint kernels route the operator's ghost cotangents back to the neighbours' edge cells, the
 // stored ghosts of sink lanes and the action.  Same float32 arithmetic, in the same order, as the ghost phases of
-// net_macro_fwd_kernel / net_macro_bwd_kernel (net_fwd_step.inc, network_kernels.hip); the host side is dhts/batched.py.
+// net_macro_fwd_kernel / net_macro_bwd_kernel (net_fwd_step.inc, network_kernels.hip), hybrid_fwd_step.inc, hybrid_bwd_step.inc and
+// netstep_hybrid.hip: all call the blends, their adjoints and the signal slopes of net_device.hpp; the host side is dhts/batched.py.
 // Thread j = 2 lane + side owns ghost (lane, side).  Nothing here is a hot loop: a step of a 360-lane network is 720 threads.
 #include <hip/hip_runtime.h>
 
@@ -30,10 +31,7 @@ __device__ __forceinline__ void ghost_signal(const NetStepArgs &a, const float *
     float we, ns, av, pr;
     phase_signal_at(action, a.n_action, a.sq, a.F, a.phase_raw, a.frame, it, we, ns, av, pr, a_index, hard);
     s = kd == 1 ? we : ns;
-    const float zs = (av - pr) * kSigK;
-    const bool sat = hard || zs < -16.f || zs > 16.f;
-    // d sigmoid(k x) / d x = s (1 - s) k with the sigmoid values just computed (0 outside the clamp, like the operator)
-    ds_da = sat ? 0.f : (kd == 1 ? we * (1.f - we) * kSigK : -(ns * (1.f - ns) * kSigK));
+    ds_da = signal_slope(we, ns, av, pr, hard, kd == 1);
 }
 
 // ghost [L][2][4] = (left, right) x (r, y, u, u_eq); own_in / own_out [L][2] = the lanes' stored downstream ghosts (r, u)
@@ -58,8 +56,7 @@ __global__ void net_ghosts_fwd_kernel(NetStepArgs a, int hard, const float *__re
                 const int kd = a.kind[gate];
                 if (kd != 0) { float ds; int ai; ghost_signal(a, action, a.inter[gate], kd, hard != 0, s, ds, ai); }
             }
-            fr = gr * s + 0.f * (1.0f - s);
-            fu = gu * s + um * (1.0f - s);
+            ghost_up_blend(gr, gu, s, um, fr, fu);
             glue_from_r_u(fr, fu, um, fy, fq);
         }
     } else {
@@ -70,8 +67,7 @@ __global__ void net_ghosts_fwd_kernel(NetStepArgs a, int hard, const float *__re
         float sg = 1.f;
         if (kd != 0) { float ds; int ai; ghost_signal(a, action, a.inter[lane], kd, hard != 0, sg, ds, ai); }
         const float s2 = hard ? (sg > 0.5f ? 1.f : 0.f) : soft_switch(sg - 0.5f, kSigK);
-        fr = s2 * gr + (1.0f - s2) * 1.0f;
-        fu = s2 * gu + (1.0f - s2) * 0.0f;
+        ghost_down_blend(gr, gu, s2, fr, fu);
         glue_from_r_u(fr, fu, um, fy, fq);
         own_out[2 * lane] = fr; own_out[2 * lane + 1] = fu;
     }
@@ -103,12 +99,11 @@ __global__ void net_ghosts_bwd_kernel(NetStepArgs a, const float *__restrict__ a
                 kd = a.kind[gate];
                 if (kd != 0) ghost_signal(a, action, a.inter[gate], kd, false, s, ds, ai);
             }
-            const float fr = grn_r * s + 0.f * (1.0f - s), fu = grn_u * s + um * (1.0f - s);
-            float g_fr = gg_r, g_fu = 0.f;
-            glue_y_bwd(fr, fu, um, gg_y, g_fr, g_fu);
+            float g_fr, g_fu;
+            ghost_up_bwd(grn_r, grn_u, s, um, gg_r, gg_y, g_fr, g_fu);
             add_r = g_fr * s;
             glue_u_bwd(r[last], y[last], um, g_fu * s, add_r, add_y);
-            if (kd != 0) { a_val = (g_fr * grn_r + g_fu * (grn_u - um)) * ds; a_key = ai; }
+            if (kd != 0) { a_val = ghost_up_switch_bwd(g_fr, g_fu, grn_r, grn_u, um) * ds; a_key = ai; }
         }
     } else {
         const int src = a.right_src[lane];
@@ -119,9 +114,8 @@ __global__ void net_ghosts_bwd_kernel(NetStepArgs a, const float *__restrict__ a
         float sg = 1.f, ds = 0.f; int ai = -1;
         if (kd != 0) ghost_signal(a, action, a.inter[lane], kd, false, sg, ds, ai);
         const float s2 = soft_switch(sg - 0.5f, kSigK);
-        const float fr = s2 * grn_r + (1.0f - s2) * 1.0f, fu = s2 * grn_u + (1.0f - s2) * 0.0f;
-        float g_fr = gg_r + g_own_in[2 * lane], g_fu = g_own_in[2 * lane + 1];      // the blended ghost is also the stored one
-        glue_y_bwd(fr, fu, um, gg_y, g_fr, g_fu);
+        float g_fr, g_fu;                                // (the blended ghost is also the stored one: its cotangent joins the step's)
+        ghost_down_bwd(grn_r, grn_u, s2, um, gg_r + g_own_in[2 * lane], g_own_in[2 * lane + 1], gg_y, g_fr, g_fu);
         float go_r = 0.f, go_u = 0.f;
         if (src >= 0) {
             add_r = g_fr * s2;
@@ -130,10 +124,7 @@ __global__ void net_ghosts_bwd_kernel(NetStepArgs a, const float *__restrict__ a
             go_r = g_fr * s2; go_u = g_fu * s2;
         }
         g_own_out[2 * lane] = go_r; g_own_out[2 * lane + 1] = go_u;
-        if (kd != 0) {
-            const float g_s2 = g_fr * (grn_r - 1.0f) + g_fu * grn_u;
-            a_val = g_s2 * soft_switch_grad(sg - 0.5f, kSigK) * ds; a_key = ai;
-        }
+        if (kd != 0) { a_val = ghost_down_switch_bwd(g_fr, g_fu, grn_r, grn_u) * soft_switch_grad(sg - 0.5f, kSigK) * ds; a_key = ai; }
     }
     float *sl = slot + (size_t)j * 4;
     sl[0] = add_r; sl[1] = add_y; sl[2] = a_val; sl[3] = (float)a_key;

@@ -433,10 +433,7 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_bwd_kernel(int R, int L, 
             float we, ns, a, pr; int ai;
             phase_signal_at(act, n_action, sq, F, rev_ph, rev_fr, sg_q, we, ns, a, pr, ai);
             sig[4 * sg_q] = we; sig[4 * sg_q + 1] = ns;
-            // d sigmoid(k x) / d x = s (1 - s) k with the sigmoid values just computed (0 outside the clamp, like the operator)
-            const float zs = (a - pr) * kSigK;
-            const bool sat = zs < -16.f || zs > 16.f;
-            sig[4 * sg_q + 2] = sat ? 0.f : we * (1.f - we) * kSigK; sig[4 * sg_q + 3] = sat ? 0.f : -(ns * (1.f - ns) * kSigK);
+            signal_slopes(we, ns, a, pr, false, sig[4 * sg_q + 2], sig[4 * sg_q + 3]);
         }
         if (t > 0) fetch(t - 1);
         // ---- phase B (no barrier in front: row t + 1 is in LDS since the previous iteration and every cell evaluates its own
@@ -478,16 +475,12 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_bwd_kernel(int R, int L, 
                         kd = linfo[gate] & 3; it = linfo[gate] >> 2;
                         if (kd != 0) s = sig[4 * it + (kd - 1)];
                     }
-                    const float fr = grn_r * s + 0.f * (1.0f - s), fu = grn_u * s + um * (1.0f - s);
-                    float g_fr = c0[g_off], g_fu = 0.f;
-                    glue_y_bwd(fr, fu, um, c0[C + g_off], g_fr, g_fu);
+                    float g_fr, g_fu;
+                    ghost_up_bwd(grn_r, grn_u, s, um, c0[g_off], c0[C + g_off], g_fr, g_fu);
                     add_r = g_fr * s;
                     glue_u_bwd(Hc[last], Hc[C + last], um, g_fu * s, add_r, add_y);
                     tgt = (float)last;
-                    if (kd != 0) {
-                        const float g_s = g_fr * grn_r + g_fu * (grn_u - um);
-                        a_val = g_s * sig[4 * it + 2 + (kd - 1)]; a_key = it;
-                    }
+                    if (kd != 0) { a_val = ghost_up_switch_bwd(g_fr, g_fu, grn_r, grn_u, um) * sig[4 * it + 2 + (kd - 1)]; a_key = it; }
                 }
             } else {
                 const int first = src < 0 ? 0 : (lfl[src] & 0xffff);
@@ -495,10 +488,9 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_bwd_kernel(int R, int L, 
                 const float grn_u = src < 0 ? w_own_u : Hc[2 * C + first];
                 const float sg = g_kind != 0 ? sig[4 * g_inter + (g_kind - 1)] : 1.f;
                 const float s2 = soft_switch(sg - 0.5f, kSigK);
-                const float fr = s2 * grn_r + (1.0f - s2) * 1.0f, fu = s2 * grn_u + (1.0f - s2) * 0.0f;
                 const int lastc = g_off + g_n - 1;
-                float g_fr = c2[lastc] + gown_r, g_fu = gown_u;      // the blended ghost is also the stored one
-                glue_y_bwd(fr, fu, um, c2[C + lastc], g_fr, g_fu);
+                float g_fr, g_fu;                        // (the blended ghost is also the stored one: its cotangent joins the step's)
+                ghost_down_bwd(grn_r, grn_u, s2, um, c2[lastc] + gown_r, gown_u, c2[C + lastc], g_fr, g_fu);
                 if (src >= 0) {
                     add_r = g_fr * s2;
                     glue_u_bwd(Hc[first], Hc[C + first], um, g_fu * s2, add_r, add_y);
@@ -506,8 +498,7 @@ __global__ void __launch_bounds__(kMaxBlock) net_macro_bwd_kernel(int R, int L, 
                     gown_r = 0.f; gown_u = 0.f;
                 } else { gown_r = g_fr * s2; gown_u = g_fu * s2; }
                 if (g_kind != 0) {
-                    const float g_s2 = g_fr * (grn_r - 1.0f) + g_fu * grn_u;
-                    const float g_sig = g_s2 * soft_switch_grad(sg - 0.5f, kSigK);
+                    const float g_sig = ghost_down_switch_bwd(g_fr, g_fu, grn_r, grn_u) * soft_switch_grad(sg - 0.5f, kSigK);
                     a_val = g_sig * sig[4 * g_inter + 2 + (g_kind - 1)]; a_key = g_inter;
                 }
             }
