@@ -65,6 +65,16 @@ inline bool pick(int v, F &&f) {
     return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
+// The tangent sweeps (dhts_macro_rollout_jvp, dhts_micro_rollout_jvp) run n directions as launches of 4, then 2, then 1: the width of
+// the instantiation that carries the next launch, `rem` directions left, at most `kmax` (4, 2 or 1) per launch.  A remainder of 3
+// rides in ONE launch of 4 with a slot masked (the tape is read once instead of twice).
+inline int jvp_width(int rem, int kmax) {
+    if (rem >= 3 && kmax >= 4) return 4;
+    int k = kmax < 2 ? kmax : 2;
+    while (k > rem) k >>= 1;
+    return k;
+}
+
 }  // namespace dhts
 
 // ---- option variables: each lives in its family's file; dhts_set_option (dhts_common.hip) holds the accepted values ----

@@ -1595,13 +1595,7 @@ static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float
 
 // The tangent sweep (macro_jvp.inc): which kernel a shape takes, how many directions ride in one launch and how many launches n_dir
 // directions need.  Launches of 4, then 2, then 1 directions; a remainder of 3 runs as ONE launch of 4 with a slot masked (the tape is
-// read once instead of twice); lanes too long for the general kernel's LDS at 4 directions (two plane sets per direction) take fewer.
-static inline int jvp_width(int rem, int kmax) {          // the instantiation that carries the next launch: 3 directions ride in 4 slots
-    if (rem >= 3 && kmax >= 4) return 4;
-    int k = kmax < 2 ? kmax : 2;
-    while (k > rem) k >>= 1;
-    return k;
-}
+// read once instead of twice: jvp_width, host_common.hpp); lanes too long for the general kernel's LDS at 4 directions (two plane sets per direction) take fewer.
 struct JvpPlan {
     bool fast;
     int block;            // threads per lane

@@ -10,6 +10,7 @@
 // Reverse (micro_rollout_bwd_kernel): one workgroup per lane, cotangent in LDS, newest step first:
 //   g'[i] = dEgo[i]^T g[i] + dLeading[i-1]^T g[i-1]; the virtual-leader slot's cotangent returns to the head
 //   vehicle and to the head gap (dmicro_lane.py:130-153, 271-298).
+// Tangent (micro_rollout_jvp_kernel, micro_jvp.inc): the same blocks untransposed, oldest step first, K directions per pass over the tape.
 //
 // Reference: road/lane/_micro_lane.py:131-214, road/lane/dmicro_lane.py:87-127 and :271-298.
 #include <hip/hip_runtime.h>
@@ -488,6 +489,9 @@ __global__ void micro_step_tensor_fwd_kernel(int L, int V, double dt, const floa
     if (fault_index >= 0) raise_fault(err, DHTS_FAULT_COLLISION, 0, lane, fault_index);
 }
 
+// ---- forward-mode tangent sweep over the rollout tape (dhts_micro_rollout_jvp) ----------------------------------
+#include "micro_jvp.inc"
+
 }  // namespace dhts
 
 using namespace dhts;
@@ -506,6 +510,9 @@ struct MicroPlan {
     // the rollout that is differentiated w.r.t. the driver parameters too (dhts_micro_rollout_fwd_params / _bwd_params)
     int ptape_bytes;         // parameter tape, bytes per vehicle-step: 8 = the pre-step (p, v), partials recomputed in the reverse sweep
     int pbwd_block;          // its reverse sweep: threads per lane -- the whole lane, one vehicle per thread holds its six double sums
+    // the tangent sweep (dhts_micro_rollout_jvp, micro_jvp.inc)
+    int jvp_block;           // threads per lane: the whole lane, one vehicle per thread holds its tangents
+    int jvp_kmax;            // directions a launch may carry: 4, with t_params too (6 double tangents each: 128 VGPRs, no scratch)
 };
 static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     MicroPlan pl;
@@ -521,6 +528,8 @@ static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     pl.bwd_per_thread = d->capacity <= pl.bwd_block && T > 0;
     pl.ptape_bytes = (int)sizeof(float2);
     pl.pbwd_block = padded64(d->capacity);
+    pl.jvp_block = padded64(d->capacity);
+    pl.jvp_kmax = 4;
     return pl;
 }
 
@@ -562,6 +571,42 @@ static int micro_bwd_params_launch(const dhts_micro_desc *d, int T, const float 
     launch(micro_rollout_bwd_kernel<true, true>, d->n_lanes, micro_plan(d, T, count != nullptr).pbwd_block, lds, stream,
            d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, 1, err, ptape, params, g_params);
     return launch_status();
+}
+// n_dir directions as launches of 4, then 2, then 1 (jvp_width: a remainder of 3 rides in ONE launch of 4 with a slot masked)
+struct MicroJvpGroups { int widest, launches; };
+static MicroJvpGroups micro_jvp_groups(const MicroPlan &pl, int n_dir) {
+    MicroJvpGroups g = {0, 0};
+    for (int rem = n_dir; rem > 0;) {
+        const int k = jvp_width(rem, pl.jvp_kmax);
+        if (!g.launches) g.widest = k;
+        rem -= k < rem ? k : rem;
+        ++g.launches;
+    }
+    return g;
+}
+static int micro_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const float *tape, const char *ptape, const int32_t *count,
+                            const double *params, const float *t_p, const float *t_v, const double *t_head, const double *t_params,
+                            float *t_p_out, float *t_v_out, float *t_hist, dhts_error *err, void *stream) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int L = d->n_lanes, V = d->capacity;
+    const size_t dir_state = (size_t)L * V, dir_hist = (size_t)T * L * 2 * V;
+    bool lds_ok = true;
+    for (int k0 = 0; k0 < n_dir && lds_ok;) {
+        const int kk = jvp_width(n_dir - k0, pl.jvp_kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+        const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
+        float *o_h = t_hist ? t_hist + k0 * dir_hist : nullptr;
+        pick<4, 2, 1>(kk, [&](auto kv) {
+            constexpr int kK = decltype(kv)::value;
+            pick<0, 1>(t_params != nullptr, [&](auto pv) {
+                constexpr bool kParams = decltype(pv)::value != 0;
+                lds_ok = launch_lds(micro_rollout_jvp_kernel<kK, kParams>, L, pl.jvp_block, micro_jvp_lds_bytes(V, kK, kParams), kLdsDefault,
+                                    stream, L, V, T, d->dt, tape, ptape, count, params, t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q,
+                                    n_act, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, o_h, err);
+            });
+        });
+        k0 += n_act;
+    }
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 template <bool kHeadOnly>
 static int micro_step_tensor_launch(const dhts_micro_desc *d, const float *p, const float *v, const int32_t *count, const double *params,
@@ -640,6 +685,26 @@ int dhts_micro_rollout_plan(const dhts_micro_desc *d, int T, int has_count, int3
     plan[4] = pl.bwd_block;
     plan[5] = pl.ptape_bytes;
     plan[6] = pl.pbwd_block;
+    return DHTS_OK;
+}
+// ---- the tangent sweep ----------------------------------------------------------------------------------------------------------
+int dhts_micro_rollout_jvp(const dhts_micro_desc *d, int T, int n_dir, const float *tape, const void *ptape, const int32_t *count,
+                           const double *params, const float *t_p, const float *t_v, const double *t_head, const double *t_params,
+                           float *t_p_out, float *t_v_out, float *t_hist, dhts_error *err, void *stream) {
+    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || (T > 0 && !tape) || !t_p || !t_v || !t_p_out || !t_v_out) return DHTS_E_INVALID;
+    if ((ptape != nullptr) != (params != nullptr) || (ptape != nullptr) != (t_params != nullptr)) return DHTS_E_INVALID;     // the three go together
+    return micro_jvp_launch(d, T, n_dir, tape, (const char *)ptape, count, params, t_p, t_v, t_head, t_params, t_p_out, t_v_out, t_hist, err,
+                            stream);
+}
+int dhts_micro_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]) {
+    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !plan) return DHTS_E_INVALID;
+    const MicroPlan pl = micro_plan(d, T, false);
+    const MicroJvpGroups g = micro_jvp_groups(pl, n_dir);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.jvp_block;
+    plan[1] = g.widest;
+    plan[2] = g.launches;
+    plan[3] = (int32_t)micro_jvp_lds_bytes(d->capacity, g.widest, want_params != 0);
     return DHTS_OK;
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)

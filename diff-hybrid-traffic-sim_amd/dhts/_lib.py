@@ -131,6 +131,8 @@ SIGNATURES = {
     "dhts_micro_rollout_bwd_params": (C.c_int, [C.POINTER(MicroDesc), C.c_int] + [_P] * 13),
     "dhts_idm_param_jac_batch": (C.c_int, [C.c_int64] + [_P] * 4),
     "dhts_micro_rollout_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
+    "dhts_micro_rollout_jvp": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 13),
+    "dhts_micro_jvp_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
     "dhts_micro_step_fwd": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor_head": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),

@@ -1,5 +1,6 @@
-"""Forward-mode differentiation of the fused ARZ rollout: dhts.macro_rollout_jvp, K Jacobian-vector products in one pass over the
-rollout tape (dhts_macro_rollout_jvp, include/dhts.h).  The raw operators are in dhts.ops; MacroRollout (reverse mode) is untouched."""
+"""Forward-mode differentiation of the fused rollouts: dhts.macro_rollout_jvp (ARZ) and dhts.micro_rollout_jvp (IDM), K Jacobian-vector
+products in one pass over the rollout tape (dhts_macro_rollout_jvp, dhts_micro_rollout_jvp, include/dhts.h).  The raw operators are in
+dhts.ops; MacroRollout and MicroRollout (reverse mode) are untouched."""
 import torch
 
 from . import ops
@@ -95,3 +96,74 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
         else:
             t_readings = torch.zeros(K, 0, L, 3, D, dtype=torch.float32, device=dev)
         return primal + (readings,), (t_rT, t_yT, t_uT, t_readings)
+
+
+def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head):
+    """Shape checks of dhts.micro_rollout_jvp's tangents (ValueError, before anything touches a device).  Returns K."""
+    given = [(n, t) for n, t in (("t_p0", t_p0), ("t_v0", t_v0), ("t_params", t_params), ("t_head", t_head)) if t is not None]
+    if not given:
+        raise ValueError("micro_rollout_jvp needs at least one of t_p0, t_v0, t_params, t_head")
+    if p0.dim() != 2:
+        raise ValueError("p0 must be [L][V]")
+    L, V = p0.shape
+    for n, t in given:
+        if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] < 1:
+            raise ValueError("%s must be a tensor with a leading direction axis K >= 1" % n)
+    K = int(given[0][1].shape[0])
+    want = dict(t_p0=(K, L, V), t_v0=(K, L, V), t_params=(K, 6, L, V), t_head=(K, L, 2))
+    for n, t in given:
+        if tuple(t.shape) != want[n]:
+            raise ValueError("%s must have shape %s (got %s): all tangents share K = %d" % (n, want[n], tuple(t.shape), K))
+    return K
+
+
+def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_params=None, t_head=None, count=None, want_hist=False,
+                      check_faults=True):
+    """dhts.micro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
+
+    Returns ((pT, vT[, hist]), (t_pT, t_vT[, t_hist])).  The primal outputs are those of dhts.micro_rollout(p0, v0, params, head, T, dt,
+    count=count, want_hist=want_hist) bit for bit.  The tangents carry a leading direction axis K: t_p0, t_v0 [K][L][V]; t_params
+    [K][6][L][V]; t_head [K][L][2].  At least one is given, all share K, a missing one is zero; anything else is a ValueError before
+    anything touches a device.  Direction i of the outputs is J applied to direction i of the inputs: t_pT, t_vT [K][L][V] float32 and,
+    with want_hist, t_hist [K][T][L][2][V]; slots at or beyond a lane's count are exactly 0.  The forward fills the parameter tape only
+    when t_params is given.  Nothing returned here is differentiable (no autograd graph is recorded; the inputs are read as constants):
+    for gradients use dhts.micro_rollout."""
+    T = int(T)
+    K = _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head)
+    L, V = p0.shape
+    if tuple(v0.shape) != (L, V) or tuple(params.shape) != (6, L, V) or tuple(head.shape) != (L, 2):
+        raise ValueError("v0 must have the shape of p0, params shape (6, %d, %d), head shape (%d, 2)" % (L, V, L))
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    desc = ops.micro_desc(L, V, dt)
+    with torch.no_grad():
+        # the forward rollout with a tape, as MicroRollout.forward runs it
+        p0c, v0c = ops._f32c(p0.detach(), "p0"), ops._f32c(v0.detach(), "v0")
+        dev = p0c.device
+        par = params.detach().contiguous()
+        tape = torch.empty(ops.micro_tape_numel(desc, T), dtype=torch.float32, device=dev)
+        ptape = torch.empty(ops.micro_param_tape_numel(desc, T), dtype=torch.float32, device=dev) if t_params is not None else None
+        hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=dev) if want_hist else None
+        err = ops.new_error_record(dev)
+        pT, vT = ops.micro_rollout_fwd(desc, T, p0c, v0c, par, head.detach(), count=count, tape=tape, hist=hist, err=err, ptape=ptape)
+        if check_faults:                 # a collision is printed like the reference does, and tolerated
+            ops.raise_on_fault(err)
+
+        def tan(t, shape, dtype):
+            if t is None:
+                return torch.zeros(shape, dtype=dtype, device=dev)
+            return t.detach().to(device=dev, dtype=dtype).contiguous()
+
+        tp, tv = tan(t_p0, (K, L, V), torch.float32), tan(t_v0, (K, L, V), torch.float32)
+        th = None if t_head is None else tan(t_head, (K, L, 2), torch.float64)
+        tq = None if t_params is None else tan(t_params, (K, 6, L, V), torch.float64)
+        err = ops.new_error_record(dev)
+        t_pT, t_vT, t_hist = ops.micro_rollout_jvp(desc, T, tape if T > 0 else None, tp, tv, count=count, t_head=th, ptape=ptape,
+                                                   params=par if tq is not None else None, t_params=tq, want_hist=want_hist, err=err)
+        if check_faults:
+            ops.raise_on_fault(err)
+    if want_hist:
+        return (pT, vT, hist), (t_pT, t_vT, t_hist)
+    return (pT, vT), (t_pT, t_vT)

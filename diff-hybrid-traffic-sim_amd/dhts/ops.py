@@ -577,6 +577,60 @@ def micro_param_plan(desc, T, has_count=False):
     return dict(param_tape_bytes=plan[5], param_bwd_block=plan[6])
 
 
+# ---- forward mode: Jacobian-vector products over the rollout tape ---------------------------------------------------------------------
+def micro_rollout_jvp(desc, T, tape, t_p, t_v, count=None, t_head=None, ptape=None, params=None, t_params=None, want_hist=False,
+                      err=None, out=None, t_hist=None):
+    """The tangent sweep over a rollout tape (include/dhts.h): t_p, t_v float32 [K][L][V]; t_head float64 [K][L][2] or None (zero);
+    ptape, params (the forward's) and t_params float64 [K][6][L][V] go together or are all None; count int32 [L] or None.
+    Returns (t_pT, t_vT, t_hist): t_hist [K][T][L][2][V] = the tangent of hist after every step, None unless want_hist (or t_hist, a
+    buffer to fill, is given)."""
+    L, V, T = desc.n_lanes, desc.capacity, int(T)
+    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
+        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
+    K = int(t_p.shape[0])
+    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    if t_head is not None and (t_head.dtype != torch.float64 or tuple(t_head.shape) != (K, L, 2) or not t_head.is_contiguous()):
+        raise ValueError("t_head must be a contiguous float64 [%d][%d][2]" % (K, L))
+    if ptape is not None or params is not None or t_params is not None:
+        if ptape is None or params is None or t_params is None:
+            raise ValueError("ptape, params and t_params go together")
+        if ptape.dtype != torch.float32 or ptape.numel() != micro_param_tape_numel(desc, T):
+            raise ValueError("ptape must be float32 [micro_param_tape_numel(desc, T)]")
+        if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V) or not params.is_contiguous():
+            raise ValueError("params must be a contiguous float64 [6][L][V]")
+        if t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous():
+            raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
+    if T > 0 and tape is None:
+        raise ValueError("a sweep of T > 0 steps needs the rollout's tape")
+    if tape is not None and (tape.dtype != torch.float32 or tape.numel() != micro_tape_numel(desc, T)):
+        raise ValueError("tape must be float32 [micro_tape_numel(desc, T)]")
+    if t_hist is not None:
+        if tuple(t_hist.shape) != (K, T, L, 2, V) or t_hist.dtype != torch.float32 or not t_hist.is_cuda or not t_hist.is_contiguous():
+            raise ValueError("t_hist must be a contiguous float32 CUDA tensor of shape (%d, %d, %d, 2, %d)" % (K, T, L, V))
+    elif want_hist:
+        t_hist = torch.empty(K, T, L, 2, V, dtype=torch.float32, device=t_p.device)
+    if out is None:
+        out = (torch.empty_like(t_p), torch.empty_like(t_v))
+    hist_ptr = None if t_hist is None or not t_hist.numel() else _ptr(t_hist)      # (T = 0: no row, and an empty tensor has no address)
+    check(_lib.lib().dhts_micro_rollout_jvp(C.byref(desc), T, K, _ptr(tape) if T > 0 else None, _ptr(ptape), _ptr(count), _ptr(params),
+                                            _ptr(t_p), _ptr(t_v), _ptr(t_head), _ptr(t_params), _ptr(out[0]), _ptr(out[1]), hist_ptr,
+                                            _ptr(err), _stream()), "dhts_micro_rollout_jvp")
+    return out[0], out[1], t_hist
+
+
+_MICRO_JVP_PLAN_KEYS = ("block", "dirs_per_launch", "launches", "lds_bytes")
+
+
+def micro_jvp_plan(desc, T, n_dir, want_params=False):
+    """What dhts_micro_rollout_jvp launches for this shape: its block (one vehicle per thread), the direction slots of the widest launch,
+    the number of launches and the widest launch's dynamic LDS bytes."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_micro_jvp_plan(C.byref(desc), int(T), int(n_dir), int(bool(want_params)), C.byref(plan)), "dhts_micro_jvp_plan")
+    return dict(zip(_MICRO_JVP_PLAN_KEYS, list(plan)))
+
+
 def micro_step_bwd(desc, tape, g_p, g_v, count=None):
     """dMicroForwardLayer.backward for a batch of lanes: returns (g_p[L][V], g_v[L][V], g_virtual[L][2] float64),
     g_virtual = raw cotangent of the virtual leader slot (not folded into the head vehicle)."""

@@ -6,7 +6,12 @@ driven by ONE shared driver theta = (accel_max, accel_pref, target_speed, min_sp
 of the ground-truth driver (MicroVehicle.default_micro_vehicle).  params = theta[:, None, None].expand(...) puts the same five numbers
 (and the fixed vehicle length) on every vehicle, so autograd sums the per-vehicle gradients of dhts.micro_rollout back onto theta;
 loss = mean squared distance to the observed (p, v) at every step; Adam on theta, kept inside a box around the initial guess.
-Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt, like the other examples.
+--method lm fits the same five numbers with Levenberg-Marquardt instead: the residuals are the T x L x 2 x V trajectory differences, and
+their Jacobian has five columns, so ONE dhts.micro_rollout_jvp call with K = 5 directions (unit direction i of theta expanded over
+every vehicle, want_hist=True) returns the trajectories AND the whole Jacobian in one pass over the rollout tape; the 5 x 5 normal
+equations are formed and solved on the device, a step is kept where it lowers the loss (one more rollout, no tape) and the damping
+follows.  Same box, same log.
+Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt (lm: .../lm/trial_k.txt), like the other examples.
 """
 import argparse
 import os
@@ -33,6 +38,8 @@ def main():
     ap.add_argument("--delta_time", type=float, default=0.01)
     ap.add_argument("--n_episode", type=int, default=100)
     ap.add_argument("--lr", type=float, default=2e-2)
+    ap.add_argument("--method", choices=("adam", "lm"), default="adam")
+    ap.add_argument("--damping", type=float, default=1e-2, help="Levenberg-Marquardt: the first damping factor")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
@@ -41,7 +48,7 @@ def main():
     th.manual_seed(args.seed)
     L, V, T, um, ln, dt = args.n_lane, args.n_vehicle, args.n_step, args.speed_limit, args.vehicle_length, args.delta_time
     run = args.run_name or "idm_{}".format(time.strftime("%Y%m%d_%H%M%S"))
-    log_dir = os.path.join("result", "calibrate", run, "gd")
+    log_dir = os.path.join("result", "calibrate", run, "gd" if args.method == "adam" else args.method)
     os.makedirs(log_dir, exist_ok=True)
 
     truth = th.tensor(MicroVehicle.default_micro_vehicle(um).params(), dtype=th.float64, device=dev)
@@ -59,19 +66,41 @@ def main():
             observed = rollout(truth[:5])
         guess = truth[:5] * (1.0 + 0.2 * (2.0 * th.rand(5, dtype=th.float64, device=dev) - 1.0))
         lo, hi = 0.5 * guess, 1.5 * guess
-        theta = guess.clone().requires_grad_(True)
-        opt = th.optim.Adam([theta], lr=args.lr)
         lines = []
         t0 = time.time()
-        for ep in range(args.n_episode):
-            loss = ((rollout(theta) - observed) ** 2).mean()
-            opt.zero_grad()
-            loss.backward()
-            err = ((theta.detach() - truth[:5]) / truth[:5]).abs().max()
-            opt.step()
-            with th.no_grad():
-                theta.copy_(th.max(th.min(theta, hi), lo))
-            lines.append("{} {}\n".format(err.item(), loss.item()))
+        if args.method == "lm":
+            theta, lam = guess.clone(), args.damping
+            unit = th.zeros(5, 6, L, V, dtype=th.float64, device=dev)      # direction i: d params / d theta_i, the same on every vehicle
+            for i in range(5):
+                unit[i, i] = 1.0
+            for ep in range(args.n_episode):
+                params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+                (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, head, T, dt, t_params=unit, want_hist=True)
+                res = (hist - observed).reshape(-1).double()
+                jac = t_hist.reshape(5, -1).double()                        # [5][T L 2 V]: column i of the Jacobian
+                loss = (res ** 2).mean()
+                err = ((theta - truth[:5]) / truth[:5]).abs().max()
+                lines.append("{} {}\n".format(err.item(), loss.item()))
+                jtj, jtr = jac @ jac.T, jac @ res
+                step = -th.linalg.solve(jtj + th.diag(lam * th.diagonal(jtj).clamp_min(1e-30)), jtr)
+                trial_theta = th.max(th.min(theta + step, hi), lo)
+                new_loss = ((rollout(trial_theta) - observed) ** 2).mean()
+                if new_loss.item() < loss.item():
+                    theta, lam = trial_theta, max(lam / 3.0, 1e-9)
+                else:
+                    lam = min(lam * 3.0, 1e9)
+        else:
+            theta = guess.clone().requires_grad_(True)
+            opt = th.optim.Adam([theta], lr=args.lr)
+            for ep in range(args.n_episode):
+                loss = ((rollout(theta) - observed) ** 2).mean()
+                opt.zero_grad()
+                loss.backward()
+                err = ((theta.detach() - truth[:5]) / truth[:5]).abs().max()
+                opt.step()
+                with th.no_grad():
+                    theta.copy_(th.max(th.min(theta, hi), lo))
+                lines.append("{} {}\n".format(err.item(), loss.item()))
         th.cuda.synchronize()
         wall = time.time() - t0
         with open(os.path.join(log_dir, "trial_{}.txt".format(trial)), "w") as f:

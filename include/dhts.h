@@ -425,6 +425,40 @@ int dhts_idm_param_jac_batch(int64_t n, const double *in, double *dacc, int32_t 
  *   plan[6] block size of dhts_micro_rollout_bwd_params (the whole lane: always one vehicle per thread) */
 int dhts_micro_rollout_plan(const dhts_micro_desc *d, int T, int has_count, int32_t plan[8]);
 
+/*
+ * Forward-mode tangent sweep (Jacobian-vector products) over a rollout's tape: n_dir = K directions in one call, oldest step first --
+ * what forward-mode autograd of the reference's plain MicroLane rollout gives (road/lane/_micro_lane.py:131-214 over
+ * IDM.compute_acceleration, model/micro/_idm.py:30-49), as dhts_micro_rollout_bwd / _bwd_params are its reverse mode.  The sweep
+ * applies the blocks the reverse sweep applies transposed, dEgo = [[1, dt], [e2, e3]] and dLeading = [[0, 0], [-e2, l3]] of the tape
+ * entry (e2, e3, l3), every 2-term product a float32 multiply + fused multiply-add; (t_pl, t_vl) = the leader's tangents before the step:
+ *     t_p' = 1 t_p + dt t_v          t_v' = ((e2 t_p + e3 t_v) + (-e2 t_pl + l3 t_vl)) + x
+ * The head vehicle (slot count - 1) follows the virtual leader (p + head_dp, v - head_dv), the reverse sweep's sign convention:
+ *     t_pl = (float)((double)t_p + t_head[0])        t_vl = (float)((double)t_v - t_head[1])
+ * x = +0.f without t_params.  With t_params (then ptape = the parameter tape of dhts_micro_rollout_fwd_params and params = the forward's
+ * are required too; the three go together) x = (float)(dt c), c summed in double with fused multiply-adds in this order:
+ *     c = sum_{q = 0 .. 4} (d acc / d theta_q) t_theta_q  [+ (d acc / d gap) (-(t_len_leader + t_len) / 2)  where the gap is live]
+ * the partials those of dhts_micro_rollout_bwd_params (dhts_idm_param_jac_batch), recomputed from ptape's pre-step state; under the
+ * acceleration clip (tape entry all zero) x = +0.f.  A direction's result does not depend on K or on its place among the directions, bit
+ * for bit; t_params = 0 gives the bits of the call without it.
+ *   tape                the rollout's tape (dhts_micro_tape_bytes); NULL is accepted for T = 0
+ *   t_p, t_v            [K][lane][V] float32: tangent of the initial (p, v)      t_p_out, t_v_out: of the final one
+ *   t_head              [K][lane][2] DOUBLE: tangent of (head_position_delta, head_speed_delta), or NULL (zero)
+ *   t_params            [K][6][lane][V] DOUBLE, laid out like params per direction, or NULL
+ *   t_hist              [K][T][lane][2][V] float32 or NULL: the tangent of what hist holds after every step
+ * Slots at or beyond a lane's count return exactly 0 (in t_hist too), as the reverse sweep does: the two sweeps are adjoint.
+ * K directions run as launches of 4, 2 or 1 (a remainder of 3 as one launch of 4 with a slot masked); with t_params a launch carries at
+ * most the number dhts_micro_jvp_plan reports.  err: the lane's earliest non-finite tangent raises DHTS_FAULT_NAN (step, lane, vehicle);
+ * a ptape that was written for another shape is not read beyond its header: DHTS_FAULT_CAPACITY (index -3), tangents = NaN.
+ * A bad descriptor, T < 0, n_dir < 1, a NULL tape with T > 0, NULL t_p / t_v / t_p_out / t_v_out, or ptape / params / t_params not all
+ * three or none: DHTS_E_INVALID, nothing is dereferenced.
+ * dhts_micro_jvp_plan: plan[0] block size (the lane rounded up to 64: one vehicle per thread)
+ *   plan[1] direction slots of the widest launch     plan[2] number of launches     plan[3] its dynamic LDS bytes     plan[4 .. 7] 0
+ */
+int dhts_micro_rollout_jvp(const dhts_micro_desc *d, int T, int n_dir, const float *tape, const void *ptape, const int32_t *count,
+                           const double *params, const float *t_p, const float *t_v, const double *t_head, const double *t_params,
+                           float *t_p_out, float *t_v_out, float *t_hist, dhts_error *err, void *stream);
+int dhts_micro_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
