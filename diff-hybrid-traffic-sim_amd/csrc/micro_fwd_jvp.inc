@@ -1,0 +1,215 @@
+// micro_fwd_jvp.inc -- the IDM rollout and kK tangent directions of it in ONE kernel, no tape; included by micro_kernels.hip inside
+// namespace dhts, after micro_jvp.inc.
+//
+// Forward mode walks the steps in the forward's own order, so the blocks of a vehicle-step (e2, e3, l3) are in the forward's registers
+// at the moment the tangent sweep wants them, and so is the pre-step (p, v) the parameter partials are recomputed from: neither the
+// 12 B tape entry nor the 8 B parameter-tape entry of micro_rollout_fwd_kernel + micro_rollout_jvp_kernel is written or read, and
+// nothing of size [T] exists unless the caller asks for hist / t_hist.
+//
+// Arithmetic: the two kernels' own.  A step forms (dp, dv) by the forward kernel's expressions from the float32 state, calls idm_step,
+// and hands MicroTape3{dE[2], dE[3], dLd[3]} to jvp_vehicle (micro_jvp.inc) per direction; kParams calls idm_param_jac once per
+// vehicle-step and sums x as micro_rollout_jvp_kernel does (double fused multiply-adds over q = 0 .. 4, then the gap term, then
+// (float)(dt cs); +0.f where there is no parameter term).  Nothing is restated but the forward's two lines for (dp, dv): the primal
+// outputs are dhts_micro_rollout_fwd's bits and the tangents dhts_micro_rollout_jvp's (tests/test_micro_fwd_jvp_gpu.py).
+//
+// Layout of a launch: as micro_rollout_jvp_kernel's -- directions [0, n_act) of the pointers it is handed, a slot d >= n_act carries
+// zeros and touches no memory.  Every launch of a call recomputes the primal and writes the same p_out, v_out; the host hands hist and
+// the forward's fault record to the first launch only.
+//   p_in, v_in, p_out, v_out   [L][V] float32      params [6][L][V] double      head [L][2] double
+//   t_p_in, t_v_in, t_p_out, t_v_out   [kK][L][V] float32      t_head [kK][L][2] double or NULL      t_params [kK][6][L][V] double
+//   hist [T][L][2][V] float32 or NULL (live slots only, as the forward)      t_hist [kK][T][L][2][V] float32 or NULL
+
+__host__ __device__ inline size_t micro_fwd_jvp_lds_bytes(int V, int kK) {
+    return sizeof(float2) * (size_t)(2 + 2 * kK) * (size_t)(V + 1) + 2 * sizeof(double) * (size_t)kK;
+}
+
+// grid = L workgroups (one traffic lane each) of blockDim.x >= V threads (V rounded up to 64): one vehicle per thread, its float32
+// (p, v), its kK tangent pairs and its derived parameters in registers for all T steps.  After a step a thread leaves its new (p, v) in
+// S [copy][slot] and its new tangents in TN [copy][direction][slot] for its follower -- the head vehicle's thread also leaves the
+// tangents of its virtual leader in the slot behind its own (virtual_leader), so every vehicle reads its leader the same way --; the
+// copies alternate with the step parity, so a step takes ONE barrier, and that one waits for LDS only: hist / t_hist stores stay in
+// flight across it.  The head-gap tangents wait in LDS (TH), as in micro_rollout_jvp_kernel.
+// Dynamic LDS: float2 S[2][V + 1] | float2 TN[2][kK][V + 1] | double TH[kK][2]
+// err: DHTS_FAULT_COLLISION where idm_step reported one (what the forward kernel reports).  err_jvp: DHTS_FAULT_NAN with the EARLIEST
+// (step, vehicle) of the workgroup (what the tangent kernel reports, by the same LDS minimum).  A block smaller than the lane:
+// DHTS_FAULT_CAPACITY (index -3) on both records, every output NaN.
+template <int kK, bool kParams>
+__global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
+    int L, int V, int T, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
+    const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ t_p_in,
+    const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
+    float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
+    float *__restrict__ hist, float *__restrict__ t_hist, dhts_error *err, dhts_error *err_jvp) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = blockIdx.x;
+    const int k = threadIdx.x;
+    const int B = blockDim.x;
+    const int P = V + 1;
+    float2 *S = reinterpret_cast<float2 *>(lds);         // [copy][P]
+    float2 *TN = S + 2 * P;                              // [copy][kK][P]
+    double *TH = reinterpret_cast<double *>(TN + 2 * kK * P);      // [kK][2]
+    const size_t base = (size_t)lane * V;
+    const size_t plane = (size_t)L * V;                  // one direction of a state tangent, one plane of params
+    const int nc = count ? count[lane] : V;
+    const int n = nc < 0 ? 0 : (nc > V ? V : nc);       // (no slot outside the lane is ever addressed)
+    const bool vk = k < n;
+    const bool is_head = k == n - 1;
+    const int kc = k < V ? k : 0;
+    const float dtf = (float)dt;
+    const double inv_dt = 1.0 / dt;
+    const size_t h_dir = (size_t)T * L * 2 * V;          // one direction of t_hist
+
+    if (V > B) {
+        const float nanf_ = __builtin_nanf("");
+        for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
+        if (hist)
+            for (int s = 0; s < T; ++s)
+                for (int i = k; i < 2 * V; i += B) hist[((size_t)s * L + lane) * 2 * V + i] = nanf_;
+        for (int d = 0; d < n_act; ++d) {
+            for (int i = k; i < V; i += B) { t_p_out[d * plane + base + i] = nanf_; t_v_out[d * plane + base + i] = nanf_; }
+            if (t_hist)
+                for (int s = 0; s < T; ++s)
+                    for (int i = k; i < 2 * V; i += B) t_hist[d * h_dir + ((size_t)s * L + lane) * 2 * V + i] = nanf_;
+        }
+        if (k == 0) { raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3); raise_fault(err_jvp, DHTS_FAULT_CAPACITY, 0, lane, -3); }
+        return;
+    }
+
+    // this thread's vehicle: its state, its tangents, its parameters and their tangents
+    float p = p_in[base + kc], v = v_in[base + kc];      // (a slot at or beyond count keeps them: the outputs pass it through)
+    float tp[kK], tv[kK];
+#pragma unroll
+    for (int d = 0; d < kK; ++d) {
+        const bool act = vk && d < n_act;
+        tp[d] = act ? t_p_in[d * plane + base + k] : 0.f;
+        tv[d] = act ? t_v_in[d * plane + base + k] : 0.f;
+    }
+    IdmDerived prm = {};
+    IdmParamDerived pm = {};
+    double half_len = 0.;
+    double tth[kParams ? kK : 1][6];                     // t_theta_0 .. 4, then -(t_len_leader + t_len) / 2
+    if constexpr (kParams) {
+#pragma unroll
+        for (int d = 0; d < kK; ++d)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) tth[d][q] = 0.;
+    }
+    if (vk) {
+        IdmParams raw;
+        raw.a_max = params[0 * plane + base + k]; raw.a_pref = params[1 * plane + base + k];
+        raw.v_target = params[2 * plane + base + k]; raw.min_space = params[3 * plane + base + k];
+        raw.time_pref = params[4 * plane + base + k]; raw.length = params[5 * plane + base + k];
+        prm = idm_derive(raw);
+        idm_set_dt(prm, dt);
+        const int kl = k + 1 < n ? k + 1 : k;
+        half_len = (params[5 * plane + base + kl] + raw.length) * 0.5;
+        if constexpr (kParams) {
+            pm = idm_param_derive(raw);
+#pragma unroll
+            for (int d = 0; d < kK; ++d) {
+                if (d < n_act) {
+                    const double *tq = t_params + (size_t)d * 6 * plane + base;
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) tth[d][q] = tq[q * plane + k];
+                    tth[d][5] = -(tq[5 * plane + kl] + tq[5 * plane + k]) * 0.5;
+                }
+            }
+        }
+    }
+    const double head_dp = head[(size_t)lane * 2], head_dv = head[(size_t)lane * 2 + 1];
+
+    for (int i = k; i < (2 + 2 * kK) * P; i += B) S[i] = make_float2(0.f, 0.f);
+    if (k < 2 * kK) TH[k] = ((k >> 1) < n_act && t_head) ? t_head[((size_t)(k >> 1) * L + lane) * 2 + (k & 1)] : 0.;
+    __syncthreads();
+
+    int fault_step = -1, bad_step = -1;
+    if (T > 0) {
+        if (vk) {
+            S[k] = make_float2(p, v);
+#pragma unroll
+            for (int d = 0; d < kK; ++d) {
+                TN[d * P + k] = make_float2(tp[d], tv[d]);
+                if (is_head) TN[d * P + k + 1] = virtual_leader(tp[d], tv[d], TH[2 * d], TH[2 * d + 1]);
+            }
+        }
+        __syncthreads();
+        for (int step = 0; step < T; ++step) {
+            const int q = step & 1;
+            if (vk) {
+                const float2 ls = S[q * P + k + 1];      // the leader's state before this step
+                const double pd = p, vd = v;
+                // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
+                const double dp = is_head ? head_dp : fabs((double)ls.x - pd) - half_len;
+                const double dv = is_head ? head_dv : vd - (double)ls.y;
+                IdmStep o;
+                idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
+                if (o.collided && fault_step < 0) fault_step = step;
+                MicroTape3 c;
+                c.e2 = o.dE[2]; c.e3 = o.dE[3]; c.l3 = o.dLd[3];
+                // kParams: the partials of this vehicle-step, once for all directions (the collision / clamp rules of the forward,
+                // _micro_lane.py:149-166, 201-212, as micro_rollout_jvp_kernel rebuilds them from the parameter tape)
+                IdmParamJac pj = {};
+                bool has_x = false, live_gap = false;
+                if constexpr (kParams) {
+                    double gap = dp, dvx = dv;
+                    live_gap = !is_head && gap >= 1e-5;      // else a constant: nothing flows to the lengths
+                    if (gap < 0) { gap = 0; dvx = 0; }
+                    gap = (1e-5 > gap) ? 1e-5 : gap;
+                    has_x = !(c.e2 == 0.f && c.e3 == 0.f && c.l3 == 0.f);      // (the forward's acceleration clip zeroes all three)
+                    if (has_x) idm_param_jac(vd, gap, dvx, pm, dt, pj);
+                }
+                bool fin = true;
+#pragma unroll
+                for (int d = 0; d < kK; ++d) {
+                    const float2 tl = TN[(q * kK + d) * P + k + 1];      // the leader's tangents before this step
+                    float x = 0.f;
+                    if constexpr (kParams) {
+                        if (has_x) {
+                            double cs = pj.d[0] * tth[d][0];
+#pragma unroll
+                            for (int qq = 1; qq < 5; ++qq) cs = __builtin_fma(pj.d[qq], tth[d][qq], cs);
+                            if (live_gap) cs = __builtin_fma(pj.d[5], tth[d][5], cs);
+                            x = (float)(dt * cs);
+                        }
+                    }
+                    float np_, nv_;
+                    jvp_vehicle(c, dtf, tp[d], tv[d], tl.x, tl.y, x, np_, nv_);
+                    tp[d] = np_; tv[d] = nv_;
+                    TN[((q ^ 1) * kK + d) * P + k] = make_float2(np_, nv_);
+                    if (is_head) TN[((q ^ 1) * kK + d) * P + k + 1] = virtual_leader(np_, nv_, TH[2 * d], TH[2 * d + 1]);
+                    fin = fin && isfinite(np_) && isfinite(nv_);
+                }
+                if (bad_step < 0 && !fin) bad_step = step;
+                p = o.np; v = o.nv;
+                S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
+                if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
+            }
+            if (t_hist && k < V) {                       // slots at or beyond count: 0 (their tangents never left it)
+                float *hp = t_hist + ((size_t)step * L + lane) * 2 * V + k;
+#pragma unroll
+                for (int d = 0; d < kK; ++d)
+                    if (d < n_act) { hp[d * h_dir] = tp[d]; hp[d * h_dir + V] = tv[d]; }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS-only: hist and t_hist stores stay in flight
+        }
+    }
+    if (k < V) {
+        p_out[base + k] = p; v_out[base + k] = v;
+#pragma unroll
+        for (int d = 0; d < kK; ++d)
+            if (d < n_act) { t_p_out[d * plane + base + k] = tp[d]; t_v_out[d * plane + base + k] = tv[d]; }
+    }
+    if (fault_step >= 0) raise_fault(err, DHTS_FAULT_COLLISION, fault_step, lane, k);
+    // the lane's EARLIEST non-finite tangent, as micro_rollout_jvp_kernel records it: the minimum of (step, vehicle) through one LDS word
+    if (err_jvp != nullptr) {
+        unsigned *word = reinterpret_cast<unsigned *>(lds);
+        __syncthreads();
+        if (k == 0) *word = 0xffffffffu;
+        __syncthreads();
+        static_assert(DHTS_MICRO_MAX_VEHICLES <= 1024, "the vehicle takes 10 bits of the key");
+        if (bad_step >= 0) atomicMin(word, ((unsigned)(bad_step < (1 << 21) - 1 ? bad_step : (1 << 21) - 1) << 10) | (unsigned)k);
+        __syncthreads();
+        const unsigned first = *word;
+        if (k == 0 && first != 0xffffffffu) raise_fault(err_jvp, DHTS_FAULT_NAN, (int)(first >> 10), lane, (int)(first & 1023u));
+    }
+}

@@ -11,6 +11,7 @@
 //   g'[i] = dEgo[i]^T g[i] + dLeading[i-1]^T g[i-1]; the virtual-leader slot's cotangent returns to the head
 //   vehicle and to the head gap (dmicro_lane.py:130-153, 271-298).
 // Tangent (micro_rollout_jvp_kernel, micro_jvp.inc): the same blocks untransposed, oldest step first, K directions per pass over the tape.
+// Fused (micro_rollout_fwd_jvp_kernel, micro_fwd_jvp.inc): the forward and K tangent directions stepped together, no tape at all.
 //
 // Reference: road/lane/_micro_lane.py:131-214, road/lane/dmicro_lane.py:87-127 and :271-298.
 #include <hip/hip_runtime.h>
@@ -491,6 +492,8 @@ __global__ void micro_step_tensor_fwd_kernel(int L, int V, double dt, const floa
 
 // ---- forward-mode tangent sweep over the rollout tape (dhts_micro_rollout_jvp) ----------------------------------
 #include "micro_jvp.inc"
+// ---- the rollout and its tangents in one kernel, no tape (dhts_micro_rollout_fwd_jvp) ----------------------------
+#include "micro_fwd_jvp.inc"
 
 }  // namespace dhts
 
@@ -513,6 +516,9 @@ struct MicroPlan {
     // the tangent sweep (dhts_micro_rollout_jvp, micro_jvp.inc)
     int jvp_block;           // threads per lane: the whole lane, one vehicle per thread holds its tangents
     int jvp_kmax;            // directions a launch may carry: 4, with t_params too (6 double tangents each: 128 VGPRs, no scratch)
+    // the tape-free fused forward + tangent kernel (dhts_micro_rollout_fwd_jvp, micro_fwd_jvp.inc)
+    int fwd_jvp_block;       // threads per lane: the whole lane, one vehicle per thread holds its state and its tangents
+    int fwd_jvp_kmax[2];     // directions a launch may carry, [0] state-only, [1] with t_params
 };
 static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     MicroPlan pl;
@@ -530,6 +536,9 @@ static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     pl.pbwd_block = padded64(d->capacity);
     pl.jvp_block = padded64(d->capacity);
     pl.jvp_kmax = 4;
+    pl.fwd_jvp_block = padded64(d->capacity);
+    pl.fwd_jvp_kmax[0] = 4;
+    pl.fwd_jvp_kmax[1] = 4;
     return pl;
 }
 
@@ -574,10 +583,10 @@ static int micro_bwd_params_launch(const dhts_micro_desc *d, int T, const float 
 }
 // n_dir directions as launches of 4, then 2, then 1 (jvp_width: a remainder of 3 rides in ONE launch of 4 with a slot masked)
 struct MicroJvpGroups { int widest, launches; };
-static MicroJvpGroups micro_jvp_groups(const MicroPlan &pl, int n_dir) {
+static MicroJvpGroups micro_jvp_groups(int kmax, int n_dir) {
     MicroJvpGroups g = {0, 0};
     for (int rem = n_dir; rem > 0;) {
-        const int k = jvp_width(rem, pl.jvp_kmax);
+        const int k = jvp_width(rem, kmax);
         if (!g.launches) g.widest = k;
         rem -= k < rem ? k : rem;
         ++g.launches;
@@ -602,6 +611,34 @@ static int micro_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const fl
                 lds_ok = launch_lds(micro_rollout_jvp_kernel<kK, kParams>, L, pl.jvp_block, micro_jvp_lds_bytes(V, kK, kParams), kLdsDefault,
                                     stream, L, V, T, d->dt, tape, ptape, count, params, t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q,
                                     n_act, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, o_h, err);
+            });
+        });
+        k0 += n_act;
+    }
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+// the same grouping under the fused kernel's own cap; every launch recomputes the primal (same bits), the first one alone is handed
+// hist and the forward's fault record
+static int micro_fwd_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                                const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out, float *hist,
+                                float *t_hist, dhts_error *err, dhts_error *err_jvp, void *stream) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int L = d->n_lanes, V = d->capacity, kmax = pl.fwd_jvp_kmax[t_params ? 1 : 0];
+    const size_t dir_state = (size_t)L * V, dir_hist = (size_t)T * L * 2 * V;
+    bool lds_ok = true;
+    for (int k0 = 0; k0 < n_dir && lds_ok;) {
+        const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+        const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
+        float *o_h = t_hist ? t_hist + k0 * dir_hist : nullptr;
+        pick<4, 2, 1>(kk, [&](auto kv) {
+            constexpr int kK = decltype(kv)::value;
+            pick<0, 1>(t_params != nullptr, [&](auto pv) {
+                constexpr bool kParams = decltype(pv)::value != 0;
+                lds_ok = launch_lds(micro_rollout_fwd_jvp_kernel<kK, kParams>, L, pl.fwd_jvp_block, micro_fwd_jvp_lds_bytes(V, kK), kLdsDefault,
+                                    stream, L, V, T, d->dt, p, v, count, params, head, t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q,
+                                    n_act, p_out, v_out, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, k0 == 0 ? hist : nullptr, o_h,
+                                    k0 == 0 ? err : nullptr, err_jvp);
             });
         });
         k0 += n_act;
@@ -699,12 +736,33 @@ int dhts_micro_rollout_jvp(const dhts_micro_desc *d, int T, int n_dir, const flo
 int dhts_micro_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]) {
     if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !plan) return DHTS_E_INVALID;
     const MicroPlan pl = micro_plan(d, T, false);
-    const MicroJvpGroups g = micro_jvp_groups(pl, n_dir);
+    const MicroJvpGroups g = micro_jvp_groups(pl.jvp_kmax, n_dir);
     for (int k = 0; k < 8; ++k) plan[k] = 0;
     plan[0] = pl.jvp_block;
     plan[1] = g.widest;
     plan[2] = g.launches;
     plan[3] = (int32_t)micro_jvp_lds_bytes(d->capacity, g.widest, want_params != 0);
+    return DHTS_OK;
+}
+// ---- the rollout and its tangents in one kernel, no tape ------------------------------------------------------------------------
+int dhts_micro_rollout_fwd_jvp(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                               const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                               const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out, float *hist,
+                               float *t_hist, dhts_error *err, dhts_error *err_jvp, void *stream) {
+    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !p || !v || !params || !head || !t_p || !t_v || !p_out || !v_out || !t_p_out || !t_v_out)
+        return DHTS_E_INVALID;
+    return micro_fwd_jvp_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out, hist,
+                                t_hist, err, err_jvp, stream);
+}
+int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]) {
+    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !plan) return DHTS_E_INVALID;
+    const MicroPlan pl = micro_plan(d, T, false);
+    const MicroJvpGroups g = micro_jvp_groups(pl.fwd_jvp_kmax[want_params != 0 ? 1 : 0], n_dir);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.fwd_jvp_block;
+    plan[1] = g.widest;
+    plan[2] = g.launches;
+    plan[3] = (int32_t)micro_fwd_jvp_lds_bytes(d->capacity, g.widest);
     return DHTS_OK;
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)

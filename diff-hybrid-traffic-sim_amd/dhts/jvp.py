@@ -118,7 +118,7 @@ def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head):
 
 
 def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_params=None, t_head=None, count=None, want_hist=False,
-                      check_faults=True):
+                      check_faults=True, fused=False):
     """dhts.micro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((pT, vT[, hist]), (t_pT, t_vT[, t_hist])).  The primal outputs are those of dhts.micro_rollout(p0, v0, params, head, T, dt,
@@ -126,8 +126,10 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
     [K][6][L][V]; t_head [K][L][2].  At least one is given, all share K, a missing one is zero; anything else is a ValueError before
     anything touches a device.  Direction i of the outputs is J applied to direction i of the inputs: t_pT, t_vT [K][L][V] float32 and,
     with want_hist, t_hist [K][T][L][2][V]; slots at or beyond a lane's count are exactly 0.  The forward fills the parameter tape only
-    when t_params is given.  Nothing returned here is differentiable (no autograd graph is recorded; the inputs are read as constants):
-    for gradients use dhts.micro_rollout."""
+    when t_params is given.  fused=True: the rollout and its tangents are stepped together by one kernel (dhts_micro_rollout_fwd_jvp)
+    and neither the tape nor the parameter tape is allocated -- same return values, bit for bit, and the same two fault checks in the
+    same order (the forward's, then the tangent sweep's).  Nothing returned here is differentiable (no autograd graph is recorded; the
+    inputs are read as constants): for gradients use dhts.micro_rollout."""
     T = int(T)
     K = _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head)
     L, V = p0.shape
@@ -139,17 +141,9 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
         raise ValueError("T must be >= 0")
     desc = ops.micro_desc(L, V, dt)
     with torch.no_grad():
-        # the forward rollout with a tape, as MicroRollout.forward runs it
         p0c, v0c = ops._f32c(p0.detach(), "p0"), ops._f32c(v0.detach(), "v0")
         dev = p0c.device
         par = params.detach().contiguous()
-        tape = torch.empty(ops.micro_tape_numel(desc, T), dtype=torch.float32, device=dev)
-        ptape = torch.empty(ops.micro_param_tape_numel(desc, T), dtype=torch.float32, device=dev) if t_params is not None else None
-        hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=dev) if want_hist else None
-        err = ops.new_error_record(dev)
-        pT, vT = ops.micro_rollout_fwd(desc, T, p0c, v0c, par, head.detach(), count=count, tape=tape, hist=hist, err=err, ptape=ptape)
-        if check_faults:                 # a collision is printed like the reference does, and tolerated
-            ops.raise_on_fault(err)
 
         def tan(t, shape, dtype):
             if t is None:
@@ -159,6 +153,25 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
         tp, tv = tan(t_p0, (K, L, V), torch.float32), tan(t_v0, (K, L, V), torch.float32)
         th = None if t_head is None else tan(t_head, (K, L, 2), torch.float64)
         tq = None if t_params is None else tan(t_params, (K, 6, L, V), torch.float64)
+        if fused:                            # one kernel, no tape
+            err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
+            (pT, vT, hist), (t_pT, t_vT, t_hist) = ops.micro_rollout_fwd_jvp(desc, T, p0c, v0c, par, head.detach(), tp, tv, count=count,
+                                                                             t_head=th, t_params=tq, want_hist=want_hist, err=err,
+                                                                             err_jvp=err_jvp)
+            if check_faults:                 # the forward's record first (a collision is printed and tolerated), then the tangents'
+                ops.raise_on_fault(err)
+                ops.raise_on_fault(err_jvp)
+            if want_hist:
+                return (pT, vT, hist), (t_pT, t_vT, t_hist)
+            return (pT, vT), (t_pT, t_vT)
+        # the forward rollout with a tape, as MicroRollout.forward runs it
+        tape = torch.empty(ops.micro_tape_numel(desc, T), dtype=torch.float32, device=dev)
+        ptape = torch.empty(ops.micro_param_tape_numel(desc, T), dtype=torch.float32, device=dev) if t_params is not None else None
+        hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=dev) if want_hist else None
+        err = ops.new_error_record(dev)
+        pT, vT = ops.micro_rollout_fwd(desc, T, p0c, v0c, par, head.detach(), count=count, tape=tape, hist=hist, err=err, ptape=ptape)
+        if check_faults:                 # a collision is printed like the reference does, and tolerated
+            ops.raise_on_fault(err)
         err = ops.new_error_record(dev)
         t_pT, t_vT, t_hist = ops.micro_rollout_jvp(desc, T, tape if T > 0 else None, tp, tv, count=count, t_head=th, ptape=ptape,
                                                    params=par if tq is not None else None, t_params=tq, want_hist=want_hist, err=err)

@@ -631,6 +631,69 @@ def micro_jvp_plan(desc, T, n_dir, want_params=False):
     return dict(zip(_MICRO_JVP_PLAN_KEYS, list(plan)))
 
 
+def micro_rollout_fwd_jvp(desc, T, p, v, params, head, t_p, t_v, count=None, t_head=None, t_params=None, want_hist=False, err=None,
+                          err_jvp=None, out=None):
+    """The rollout and K tangent directions of it in one kernel, no tape (dhts_micro_rollout_fwd_jvp, include/dhts.h): what
+    micro_rollout_fwd followed by micro_rollout_jvp returns, bit for bit.  p, v, params, head, count as micro_rollout_fwd; t_p, t_v
+    float32 [K][L][V]; t_head float64 [K][L][2] or None (zero); t_params float64 [K][6][L][V] or None (no parameter term).
+    err: the forward's fault record (collisions), err_jvp: the tangent sweep's (the earliest non-finite tangent); each may be None.
+    out: (p_out, v_out, t_p_out, t_v_out[, hist, t_hist]) buffers to fill; hist [T][L][2][V] and t_hist [K][T][L][2][V] are allocated
+    with want_hist unless handed in.  Returns ((pT, vT, hist), (t_pT, t_vT, t_hist)), the histories None unless asked for."""
+    L, V, T = desc.n_lanes, desc.capacity, int(T)
+    p, v = _f32c(p, "p"), _f32c(v, "v")
+    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
+        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
+    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
+        raise ValueError("params must be float64 [6][L][V]")
+    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
+        raise ValueError("head must be float64 [L][2]")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
+        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
+    K = int(t_p.shape[0])
+    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
+    if t_head is not None and (t_head.dtype != torch.float64 or tuple(t_head.shape) != (K, L, 2) or not t_head.is_contiguous()):
+        raise ValueError("t_head must be a contiguous float64 [%d][%d][2]" % (K, L))
+    if t_params is not None and (t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous()):
+        raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
+    params, head = params.contiguous(), head.contiguous()
+    out = tuple(out) if out is not None else ()
+    if len(out) not in (0, 4, 6):
+        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, hist, t_hist])")
+    hist, t_hist = (out[4], out[5]) if len(out) == 6 else (None, None)
+    for name, t, shape in (("hist", hist, (T, L, 2, V)), ("t_hist", t_hist, (K, T, L, 2, V))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, shape))
+    if want_hist and hist is None:
+        hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=p.device)
+    if want_hist and t_hist is None:
+        t_hist = torch.empty(K, T, L, 2, V, dtype=torch.float32, device=p.device)
+    if out:
+        state = out[:4]
+        for name, t, like in zip(("p_out", "v_out", "t_p_out", "t_v_out"), state, (p, v, t_p, t_v)):
+            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
+    else:
+        state = (torch.empty_like(p), torch.empty_like(v), torch.empty_like(t_p), torch.empty_like(t_v))
+    hptr = [None if h is None or not h.numel() else _ptr(h) for h in (hist, t_hist)]      # (T = 0: an empty tensor has no address)
+    check(_lib.lib().dhts_micro_rollout_fwd_jvp(C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head), _ptr(t_p),
+                                                _ptr(t_v), _ptr(t_head), _ptr(t_params), _ptr(state[0]), _ptr(state[1]), _ptr(state[2]),
+                                                _ptr(state[3]), hptr[0], hptr[1], _ptr(err), _ptr(err_jvp), _stream()),
+          "dhts_micro_rollout_fwd_jvp")
+    return (state[0], state[1], hist), (state[2], state[3], t_hist)
+
+
+def micro_fwd_jvp_plan(desc, T, n_dir, want_params=False):
+    """What dhts_micro_rollout_fwd_jvp launches for this shape: the keys of micro_jvp_plan."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_micro_fwd_jvp_plan(C.byref(desc), int(T), int(n_dir), int(bool(want_params)), C.byref(plan)),
+          "dhts_micro_fwd_jvp_plan")
+    return dict(zip(_MICRO_JVP_PLAN_KEYS, list(plan)))
+
+
 def micro_step_bwd(desc, tape, g_p, g_v, count=None):
     """dMicroForwardLayer.backward for a batch of lanes: returns (g_p[L][V], g_v[L][V], g_virtual[L][2] float64),
     g_virtual = raw cotangent of the virtual leader slot (not folded into the head vehicle)."""

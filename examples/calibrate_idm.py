@@ -10,7 +10,8 @@ loss = mean squared distance to the observed (p, v) at every step; Adam on theta
 their Jacobian has five columns, so ONE dhts.micro_rollout_jvp call with K = 5 directions (unit direction i of theta expanded over
 every vehicle, want_hist=True) returns the trajectories AND the whole Jacobian in one pass over the rollout tape; the 5 x 5 normal
 equations are formed and solved on the device, a step is kept where it lowers the loss (one more rollout, no tape) and the damping
-follows.  Same box, same log.
+follows.  Same box, same log.  --fused steps the rollout and the five tangents in one kernel (fused=True): no tape, no parameter tape,
+the same numbers bit for bit.
 Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt (lm: .../lm/trial_k.txt), like the other examples.
 """
 import argparse
@@ -40,9 +41,12 @@ def main():
     ap.add_argument("--lr", type=float, default=2e-2)
     ap.add_argument("--method", choices=("adam", "lm"), default="adam")
     ap.add_argument("--damping", type=float, default=1e-2, help="Levenberg-Marquardt: the first damping factor")
+    ap.add_argument("--fused", action="store_true", help="Levenberg-Marquardt: rollout and tangents in one tape-free kernel")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
+    if args.fused and args.method != "lm":
+        ap.error("--fused belongs to --method lm")
 
     dev = th.device("cuda", 0)
     th.manual_seed(args.seed)
@@ -75,7 +79,8 @@ def main():
                 unit[i, i] = 1.0
             for ep in range(args.n_episode):
                 params = th.cat([theta, length])[:, None, None].expand(6, L, V)
-                (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, head, T, dt, t_params=unit, want_hist=True)
+                (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, head, T, dt, t_params=unit, want_hist=True,
+                                                                      fused=args.fused)
                 res = (hist - observed).reshape(-1).double()
                 jac = t_hist.reshape(5, -1).double()                        # [5][T L 2 V]: column i of the Jacobian
                 loss = (res ** 2).mean()

@@ -459,6 +459,34 @@ int dhts_micro_rollout_jvp(const dhts_micro_desc *d, int T, int n_dir, const flo
                            float *t_p_out, float *t_v_out, float *t_hist, dhts_error *err, void *stream);
 int dhts_micro_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]);
 
+/*
+ * The rollout AND n_dir = K tangent directions of it in one kernel, without a tape: what dhts_micro_rollout_fwd (or _fwd_params, with
+ * t_params) followed by dhts_micro_rollout_jvp returns, bit for bit, from one entry point -- forward-mode autograd of the reference's
+ * plain MicroLane rollout (road/lane/_micro_lane.py:131-214 over IDM.compute_acceleration, model/micro/_idm.py:30-49; the blocks are
+ * those of road/lane/dmicro_lane.py:87-127).  Forward mode walks the steps in the forward's order, so a step's blocks (e2, e3, l3) and
+ * the pre-step (p, v) the parameter partials are recomputed from are used out of the forward's registers: neither the tape
+ * (dhts_micro_tape_bytes) nor the parameter tape (dhts_micro_param_tape_bytes) exists, and no memory grows with T unless hist / t_hist
+ * are asked for.  The arithmetic is the two calls' own (the same device functions), in the same order.
+ *   p, v, count, params, head, p_out, v_out, hist     as dhts_micro_rollout_fwd (slots at or beyond count pass through; hist or NULL)
+ *   t_p, t_v, t_head, t_params, t_p_out, t_v_out, t_hist     as dhts_micro_rollout_jvp (slots at or beyond count exactly 0)
+ * A non-NULL t_params selects the instantiation that carries the parameter term.  K directions run as launches of 4, 2 or 1 (a
+ * remainder of 3 as one launch of 4 with a slot masked), at most the number dhts_micro_fwd_jvp_plan reports per launch; every launch
+ * recomputes the primal and writes the same bits to p_out, v_out, the first one alone writes hist.  T = 0 launches too (it copies the
+ * state and the live tangents and zeroes the rest).
+ * Two fault records, each nullable, because the two checks of the pair do not collapse into one first-wins word:
+ *   err       what the forward reports: DHTS_FAULT_COLLISION (step, lane, vehicle) -- printed and tolerated by the reference
+ *   err_jvp   what the tangent sweep reports: DHTS_FAULT_NAN with the lane's EARLIEST (step, vehicle) of a non-finite tangent
+ * A bad descriptor, T < 0, n_dir < 1, or a NULL p / v / params / head / t_p / t_v / p_out / v_out / t_p_out / t_v_out: DHTS_E_INVALID,
+ * nothing is dereferenced.
+ * dhts_micro_fwd_jvp_plan: plan[0] block size (the lane rounded up to 64: one vehicle per thread)
+ *   plan[1] direction slots of the widest launch     plan[2] number of launches     plan[3] its dynamic LDS bytes     plan[4 .. 7] 0
+ */
+int dhts_micro_rollout_fwd_jvp(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                               const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                               const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out, float *hist,
+                               float *t_hist, dhts_error *err, dhts_error *err_jvp, void *stream);
+int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
