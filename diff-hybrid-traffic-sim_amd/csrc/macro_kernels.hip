@@ -1345,6 +1345,9 @@ __global__ void macro_u_tap_bwd_kernel(int64_t n, float um, const float *__restr
 // ---- forward-mode tangent sweep over the rollout tape (dhts_macro_rollout_jvp) and its glue ----------------------
 #include "macro_jvp.inc"
 
+// ---- the rollout and its tangents in one kernel, no tape (dhts_macro_rollout_fwd_jvp) ----------------------------
+#include "macro_fwd_jvp.inc"
+
 }  // namespace dhts
 
 // ---- C ABI -----------------------------------------------------------------------------------------------
@@ -1656,6 +1659,72 @@ static int macro_rollout_jvp_launch(const dhts_macro_desc *d, int T, const float
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
+// The tape-free fused forward + tangent kernel (macro_fwd_jvp.inc): the lane kernel's mapping (W wavefronts of p passes, computed as
+// macro_plan computes them for the two-phase lane kernel; DHTS_OPT_MACRO_FWD_VARIANT and _GROUP do not apply: there is one kernel) and the
+// widest launch whose dynamic LDS -- the lane kernel's records, the interface products, two tangent copies per direction -- fits 160 KB:
+// 4 directions up to 997 cells, 2 up to 1239, 1 up to 1410, none above (kmax = 0: the taped pair covers those lanes).
+struct FwdJvpPlan {
+    int W, p;             // wavefronts per lane, 64-cell passes per wavefront
+    int kmax;             // directions a launch may carry: 4, 2, 1 or 0
+    int widest, launches; // of n_dir directions: the slots of the widest launch, the number of launches
+    size_t lds;           // dynamic LDS of the widest launch
+};
+static FwdJvpPlan macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir) {
+    FwdJvpPlan pl = {};
+    const int N = d->n_cells;
+    int W = dhts_fwd_waves_override > 0 ? dhts_fwd_waves_override : (N + 127) / 128;
+    if (W > 12) W = 12;                   // (the kernel's launch bound; no lane that fits has more without DHTS_OPT_MACRO_FWD_WAVES)
+    if (W < 1) W = 1;
+    pl.p = (N + 64 * W - 1) / (64 * W);
+    pl.W = (N + 64 * pl.p - 1) / (64 * pl.p);
+    pl.kmax = 4;
+    while (pl.kmax > 0 && fwd_jvp_lds_bytes(N, pl.kmax) > 160 * 1024) pl.kmax >>= 1;
+    for (int rem = n_dir; rem > 0 && pl.kmax > 0;) {
+        const int k = jvp_width(rem, pl.kmax);
+        if (!pl.launches) pl.widest = k;
+        rem -= k < rem ? k : rem;
+        ++pl.launches;
+    }
+    if (T == 0) pl.launches = 0;          // no step: the entry point copies the state and the tangents
+    pl.lds = pl.widest > 0 ? fwd_jvp_lds_bytes(N, pl.widest) : 0;
+    return pl;
+}
+
+static int macro_fwd_jvp_launch(const dhts_macro_desc *d, int T, int n_dir, const float *r, const float *y, const float *u, const float *ueq,
+                                const float *ghost, int ghost_is_sched, const float *t_r, const float *t_y, const float *t_ghost,
+                                float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                                const int32_t *det, int n_det, float *taps, float *t_taps, dhts_error *err, dhts_error *err_jvp, void *stream) {
+    const FwdJvpPlan pl = macro_fwd_jvp_plan(d, T, n_dir);
+    if (pl.kmax < 1) return DHTS_E_INVALID;
+    const int L = d->n_lanes, N = d->n_cells;
+    const int ghost_mode = !t_ghost ? 0 : (ghost_is_sched ? 2 : 1);
+    const size_t dir_state = (size_t)L * N, dir_ghost = (ghost_mode == 2 ? (size_t)T : 1) * L * 4, dir_taps = (size_t)T * L * 2 * n_det;
+    bool lds_ok = true;
+    for (int k0 = 0; k0 < n_dir && lds_ok;) {
+        const int kk = jvp_width(n_dir - k0, pl.kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+        const float *a_r = t_r + k0 * dir_state, *a_y = t_y + k0 * dir_state, *a_g = t_ghost ? t_ghost + k0 * dir_ghost : nullptr;
+        float *o_r = t_r_out + k0 * dir_state, *o_y = t_y_out + k0 * dir_state, *o_t = det ? t_taps + k0 * dir_taps : nullptr;
+        // every launch recomputes the primal and writes the same bits; the first one alone is handed the readings and the forward's record
+        float *o_taps = k0 == 0 ? taps : nullptr;
+        dhts_error *o_err = k0 == 0 ? err : nullptr;
+        pick<4, 2, 1>(kk, [&](auto kv) {
+            pick<0, 1, 2>(pl.p <= 2 ? pl.p : 0, [&](auto pv) {
+                pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
+                    pick<0, 1>(det != nullptr, [&](auto tap) {
+                        constexpr int kK = decltype(kv)::value, kP = decltype(pv)::value;
+                        constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
+                        lds_ok = launch_lds(macro_rollout_fwd_jvp_kernel<kK, kP, kS, kT>, L, 64 * pl.W, fwd_jvp_lds_bytes(N, kK), kLdsDefault,
+                                            stream, L, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, a_r, a_y, a_g, ghost_mode, n_act,
+                                            r_out, y_out, u_out, ueq_out, o_r, o_y, det, n_det, o_taps, o_t, o_err, err_jvp);
+                    });
+                });
+            });
+        });
+        k0 += n_act;
+    }
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+
 #ifdef DHTS_FWD3_STAMPS
 extern "C" int dhts_debug_fwd_clock(long long *out) {         // [2 kernels][16 workgroups][2]
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(dhts::dhts_fwd_clock), sizeof(long long) * 2 * 16 * 2) == hipSuccess ? 0 : -1;
@@ -1831,6 +1900,34 @@ int dhts_macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, i
     if (pl.kmax < 1) return DHTS_E_INVALID;
     plan[0] = pl.fast ? 1 : 0; plan[1] = pl.block; plan[2] = pl.widest; plan[3] = pl.launches;
     plan[4] = plan[5] = plan[6] = plan[7] = 0;
+    return DHTS_OK;
+}
+// ---- the rollout and its tangents in one kernel, no tape ------------------------------------------------------------------------
+int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
+                               const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                               const float *t_r, const float *t_y, const float *t_ghost,
+                               float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                               const int32_t *det, int n_det, float *taps, float *t_taps,
+                               dhts_error *err, dhts_error *err_jvp, void *stream) {
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || n_dir < 1 || !t_r || !t_y || !t_r_out || !t_y_out)
+        return DHTS_E_INVALID;
+    if ((det != nullptr) != (taps != nullptr) || (det != nullptr) != (t_taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells)))
+        return DHTS_E_INVALID;
+    if (macro_fwd_jvp_plan(d, T, n_dir).kmax < 1) return DHTS_E_INVALID;       // the lane does not fit: the taped pair covers it
+    if (T == 0) {                                                // no step: state and tangents come back as they went in, no row is addressed
+        const size_t bytes = sizeof(float) * (size_t)n_dir * d->n_lanes * d->n_cells;
+        if (t_r_out != t_r && hipMemcpyAsync(t_r_out, t_r, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        if (t_y_out != t_y && hipMemcpyAsync(t_y_out, t_y, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
+    }
+    return macro_fwd_jvp_launch(d, T, n_dir, r, y, u, ueq, ghost, ghost_is_sched, t_r, t_y, t_ghost, r_out, y_out, u_out, ueq_out, t_r_out,
+                                t_y_out, det, det ? n_det : 0, taps, t_taps, err, err_jvp, stream);
+}
+int dhts_macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]) {
+    if (!macro_desc_ok(d) || T < 0 || n_dir < 1 || !plan || n_det < 0 || n_det > d->n_cells) return DHTS_E_INVALID;
+    const FwdJvpPlan pl = macro_fwd_jvp_plan(d, T, n_dir);
+    plan[0] = pl.W; plan[1] = pl.p; plan[2] = pl.widest; plan[3] = pl.launches; plan[4] = (int32_t)pl.lds;
+    plan[5] = plan[6] = plan[7] = 0;
     return DHTS_OK;
 }
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,

@@ -1,6 +1,7 @@
 """Forward-mode differentiation of the fused rollouts: dhts.macro_rollout_jvp (ARZ) and dhts.micro_rollout_jvp (IDM), K Jacobian-vector
-products in one pass over the rollout tape (dhts_macro_rollout_jvp, dhts_micro_rollout_jvp, include/dhts.h).  The raw operators are in
-dhts.ops; MacroRollout and MicroRollout (reverse mode) are untouched."""
+products in one pass over the rollout tape (dhts_macro_rollout_jvp, dhts_micro_rollout_jvp, include/dhts.h) or, with fused=True, in
+one kernel that steps the rollout and its tangents together and has no tape (dhts_macro_rollout_fwd_jvp, dhts_micro_rollout_fwd_jvp).
+The raw operators are in dhts.ops; MacroRollout and MicroRollout (reverse mode) are untouched."""
 import torch
 
 from . import ops
@@ -28,7 +29,7 @@ def _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u):
 
 
 def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, t_u0=None, t_ghost_r=None, t_ghost_u=None,
-                      detectors=None, check_faults=True):
+                      detectors=None, check_faults=True, fused=False):
     """dhts.macro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((rT, yT, uT, qT[, readings]), (t_rT, t_yT, t_uT[, t_readings])).  The primal outputs are those of
@@ -37,7 +38,17 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
     [T][L][2].  At least one is given, all share K, a missing one is zero; anything else is a ValueError before anything touches a device.
     Direction i of the outputs is J applied to direction i of the inputs: t_rT, t_yT, t_uT [K][L][N] and, with detectors, t_readings
     [K][T][L][3][D], the tangent of (r, y, u) of cell detectors[j] after every step.  Nothing returned here is differentiable (no
-    autograd graph is recorded; the inputs are read as constants): for gradients use dhts.macro_rollout."""
+    autograd graph is recorded; the inputs are read as constants): for gradients use dhts.macro_rollout.
+
+    fused=True: the rollout and its tangents are stepped together by one kernel (dhts_macro_rollout_fwd_jvp) and no tape is allocated
+    (17.3 B per cell-step: 9 GB at 1024 x 512 x 1000) -- same return values, bit for bit, and the same two fault checks in the same
+    order (the forward's, then the tangent sweep's); nothing it allocates grows with T but the readings.  It runs up to four directions
+    per launch and recomputes the primal in every launch, on the two-phase lane kernel's mapping with a larger LDS footprint, so it is
+    NOT always the faster path.  Measured on one MI355X: at 1024 lanes x 512 cells x 1000 steps it is slower than
+    fused=False for every K (1.04x, 1.08x at K = 1, 2; 1.8x at K = 3, 4; 2.4x at K = 8); at 4096 x 64 x 1000 with four detectors it
+    takes 0.74, 0.79 of the taped time at K = 1, 2 and 1.16 .. 1.61 from K = 3 on (0.89 at K = 3, 4 at 3328 lanes, which
+    a launch of four holds on the chip at once).  Choose it when the tape is what limits T, or for few directions on short lanes.
+    Lanes of more than 1410 cells do not fit it (ValueError before anything is launched; fused=False covers them)."""
     if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
         raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
     T = int(T)
@@ -49,23 +60,27 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
         raise ValueError("u0 must have the shape of r0, ghost_r and ghost_u shape %s" % (want,))
     det = None if detectors is None else ops._detector_indices(detectors, N, r0.device)
     desc = ops.macro_desc(L, N, dt, dx, u_max)
+    if fused and ops.macro_fwd_jvp_plan(desc, T, K)["dirs_per_launch"] < 1:
+        raise ValueError("macro_rollout_jvp(fused=True): a lane of %d cells does not fit the fused forward + tangent kernel (its records, "
+                         "the interface products and the tangent copies exceed the LDS of a workgroup); fused=False covers it" % N)
     with torch.no_grad():
-        # the forward rollout with a tape, as MacroRollout.forward runs it
         r0c, u0c = ops._f32c(r0.detach(), "r0"), ops._f32c(u0.detach(), "u0")
         gr, gu = ops._f32c(ghost_r.detach(), "ghost_r"), ops._f32c(ghost_u.detach(), "ghost_u")
         y0, q0 = ops.macro_state_from_ru(r0c, u0c, u_max)
         gy, gq = ops.macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
         ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()
-        tape = torch.empty(ops.macro_tape_numel(desc, T), dtype=torch.float32, device=r0c.device)
-        err = ops.new_error_record(r0c.device)
         readings = None
-        if det is not None:
-            (rT, yT, uT, qT), readings = ops.macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
-        else:
-            fwd = ops.macro_rollout_fwd_sched if sched else ops.macro_rollout_fwd
-            rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, err=err)
-        if check_faults:
-            ops.raise_on_fault(err)
+        if not fused:
+            # the forward rollout with a tape, as MacroRollout.forward runs it
+            tape = torch.empty(ops.macro_tape_numel(desc, T), dtype=torch.float32, device=r0c.device)
+            err = ops.new_error_record(r0c.device)
+            if det is not None:
+                (rT, yT, uT, qT), readings = ops.macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
+            else:
+                fwd = ops.macro_rollout_fwd_sched if sched else ops.macro_rollout_fwd
+                rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, err=err)
+            if check_faults:
+                ops.raise_on_fault(err)
         # the leaves' tangents -> tangents of (r, y)
         dev = r0c.device
 
@@ -79,10 +94,18 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
             tgr, tgu = tan(t_ghost_r, (K,) + want), tan(t_ghost_u, (K,) + want)
             tgy = ops.macro_state_from_ru_jvp(gr.expand((K,) + want), gu.expand((K,) + want), tgr, tgu, u_max)
             t_ghost = torch.stack([tgr, tgy], dim=-1).contiguous()          # [K][L][2][2], or [K][T][L][2][2]
-        err = ops.new_error_record(dev)
-        t_rT, t_yT, t_taps = ops.macro_rollout_jvp(desc, T, tape if T > 0 else None, tr0, ty0, t_ghost=t_ghost, det=det, err=err)
-        if check_faults:
-            ops.raise_on_fault(err)
+        if fused:                            # one kernel, no tape
+            err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
+            (rT, yT, uT, qT, readings), (t_rT, t_yT, t_taps) = ops.macro_rollout_fwd_jvp(desc, T, r0c, y0, u0c, q0, ghost, tr0, ty0,
+                                                                                         t_ghost=t_ghost, det=det, err=err, err_jvp=err_jvp)
+            if check_faults:                 # the pair's order: the forward's record first, then the tangents'
+                ops.raise_on_fault(err)
+                ops.raise_on_fault(err_jvp)
+        else:
+            err = ops.new_error_record(dev)
+            t_rT, t_yT, t_taps = ops.macro_rollout_jvp(desc, T, tape if T > 0 else None, tr0, ty0, t_ghost=t_ghost, det=det, err=err)
+            if check_faults:
+                ops.raise_on_fault(err)
         t_uT = ops.macro_u_tap_jvp(rT.expand(K, L, N), yT.expand(K, L, N), t_rT, t_yT, u_max)
         primal = (rT, yT, uT, qT)
         if det is None:

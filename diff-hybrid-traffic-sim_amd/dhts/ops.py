@@ -466,6 +466,83 @@ def macro_jvp_plan(desc, T, n_dir, n_det=0):
     return dict(zip(_MACRO_JVP_PLAN_KEYS, list(plan)))
 
 
+_MACRO_FWD_JVP_PLAN_KEYS = ("waves", "passes", "dirs_per_launch", "launches", "lds_bytes")
+
+
+def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, det=None, err=None, err_jvp=None, out=None, taps=None,
+                          t_taps=None):
+    """The rollout and K tangent directions of it in one kernel, no tape (dhts_macro_rollout_fwd_jvp, include/dhts.h): what
+    macro_rollout_fwd / _fwd_sched / _fwd_taps followed by macro_rollout_jvp returns, bit for bit.  r, y, u, ueq [L][N]; ghost [L][2][4]
+    or a schedule [T][L][2][4]; t_r, t_y [K][L][N]; t_ghost None (zero), [K][L][2][2], or [K][T][L][2][2] beside a schedule; det int32
+    CUDA [D] or None.  err: the forward's fault record (CFL), err_jvp: the tangent sweep's (the earliest non-finite tangent); each may be
+    None.  out: (r_out, y_out, u_out, ueq_out, t_r_out, t_y_out) buffers to fill; taps [T][L][3][D] and t_taps [K][T][L][2][D] are
+    allocated with det unless handed in.  A lane the plan cannot take is a ValueError before anything is launched.
+    Returns ((rT, yT, uT, qT, taps), (t_rT, t_yT, t_taps)), the readings None without det."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
+        if tuple(t.shape) != (L, N):
+            raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
+    sched = ghost.dim() == 4
+    want = (T, L, 2, 4) if sched else (L, 2, 4)
+    if tuple(ghost.shape) != want:
+        raise ValueError("ghost must have shape (%d, 2, 4) or (%d, %d, 2, 4)" % (L, T, L))
+    if t_r.dim() != 3 or tuple(t_r.shape[1:]) != (L, N) or t_r.shape[0] < 1 or t_y.shape != t_r.shape:
+        raise ValueError("t_r and t_y must have shape (K, %d, %d) with K >= 1" % (L, N))
+    K = int(t_r.shape[0])
+    if macro_fwd_jvp_plan(desc, T, K)["dirs_per_launch"] < 1:
+        raise ValueError("a lane of %d cells does not fit the fused forward + tangent kernel (its records, the interface products and "
+                         "the tangent copies exceed the LDS of a workgroup); fused=False, the taped pair, covers it" % N)
+    r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, "ghost")))
+    t_r, t_y = _f32c(t_r, "t_r"), _f32c(t_y, "t_y")
+    if sched and T == 0:        # an empty tensor has no address; the entry point wants one and reads no row
+        ghost = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
+    if t_ghost is not None:
+        want = (K, T, L, 2, 2) if sched else (K, L, 2, 2)
+        if tuple(t_ghost.shape) != want:
+            raise ValueError("t_ghost must have shape %s: it follows the form of ghost" % (want,))
+        t_ghost = _f32c(t_ghost, "t_ghost")
+        if not t_ghost.numel():          # (a schedule of no steps: no row, and an empty tensor has no address)
+            t_ghost = None
+    D = 0
+    if det is not None:
+        det = _det_i32(det, N)
+        D = det.numel()
+        for name, t, shape in (("taps", taps, (T, L, 3, D)), ("t_taps", t_taps, (K, T, L, 2, D))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, shape))
+        if taps is None:
+            taps = torch.empty(T, L, 3, D, dtype=torch.float32, device=r.device)
+        if t_taps is None:
+            t_taps = torch.empty(K, T, L, 2, D, dtype=torch.float32, device=r.device)
+    elif taps is not None or t_taps is not None:
+        raise ValueError("taps / t_taps without det")
+    if out is None:
+        out = tuple(torch.empty_like(r) for _ in range(4)) + (torch.empty_like(t_r), torch.empty_like(t_y))
+    else:
+        out = tuple(out)
+        if len(out) != 6:
+            raise ValueError("out must be (r_out, y_out, u_out, ueq_out, t_r_out, t_y_out)")
+        for name, t, like in zip(("r_out", "y_out", "u_out", "ueq_out", "t_r_out", "t_y_out"), out, (r, y, u, ueq, t_r, t_y)):
+            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
+    tptr = [None if h is None else C.c_void_p(h.data_ptr() or det.data_ptr()) for h in (taps, t_taps)]      # (T = 0: no address, no row)
+    check(_lib.lib().dhts_macro_rollout_fwd_jvp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
+                                                _ptr(t_r), _ptr(t_y), _ptr(t_ghost), *(_ptr(o) for o in out), _ptr(det), D, tptr[0],
+                                                tptr[1], _ptr(err), _ptr(err_jvp), _stream()), "dhts_macro_rollout_fwd_jvp")
+    return (out[0], out[1], out[2], out[3], taps), (out[4], out[5], t_taps)
+
+
+def macro_fwd_jvp_plan(desc, T, n_dir, n_det=0):
+    """What dhts_macro_rollout_fwd_jvp launches for this shape: the lane kernel's wavefronts per lane and passes per wavefront, the
+    direction slots of the widest launch (0: the lane does not fit), the number of launches (0 for T = 0 or when nothing fits) and the
+    widest launch's dynamic LDS bytes.  Needs no device."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_macro_fwd_jvp_plan(C.byref(desc), int(T), int(n_dir), int(n_det), C.byref(plan)), "dhts_macro_fwd_jvp_plan")
+    return dict(zip(_MACRO_FWD_JVP_PLAN_KEYS, list(plan)))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # micro
 # ---------------------------------------------------------------------------------------------------------

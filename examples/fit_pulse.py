@@ -7,7 +7,9 @@ that record the density after every step) with THREE unknowns per lane instead o
 T x D residuals.  --method lm (default) solves it with Levenberg-Marquardt: one dhts.macro_rollout_jvp call with K = 3 directions -- the
 pulse's own Jacobian w.r.t. (height, centre, width), formed in torch, as three tangent schedules of the boundary cell -- returns the
 readings AND their [T * D] x 3 Jacobian in one pass over the rollout tape; the 3 x 3 normal equations are solved per lane in torch, a
-step is kept where it lowers the lane's loss (one more rollout, no tape) and the damping follows.  --method adam fits the same three
+step is kept where it lowers the lane's loss (one more rollout, no tape) and the damping follows; with --fused that call steps the
+rollout and its tangents in one kernel and allocates no tape at all (dhts.macro_rollout_jvp(fused=True): the same trial file, bit for
+bit, and a horizon that memory no longer limits).  --method adam fits the same three
 numbers with Adam through dhts.macro_rollout and its reverse sweep, for comparison.  Every trial solves n_lane independent problems.
 
 Same output conventions as the other examples: one log line "{parameter_error} {loss}" per episode in
@@ -41,6 +43,8 @@ def main():
     ap.add_argument("--method", choices=("lm", "adam"), default="lm")
     ap.add_argument("--lr", type=float, default=2e-2, help="Adam's step, in units of (density, T steps, T steps)")
     ap.add_argument("--damping", type=float, default=1e-2, help="Levenberg-Marquardt: the first damping factor")
+    ap.add_argument("--fused", action="store_true",
+                    help="--method lm: step the rollout and its three tangents in one kernel, without a tape (same results, bit for bit)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
@@ -94,7 +98,7 @@ def main():
         t_gr, t_gu = th.stack([d_up, zero], dim=-1), th.stack([d_up * d_ueq, zero], dim=-1)      # [3][T][L][2]
         gr, gu = schedule(up)
         primal, tang = dhts.macro_rollout_jvp(r0, u0, gr, gu, T, dt, dx, um, t_ghost_r=t_gr.contiguous(), t_ghost_u=t_gu.contiguous(),
-                                              detectors=det32)
+                                              detectors=det32, fused=args.fused)
         return primal[4][:, :, 0], tang[3][:, :, :, 0].permute(2, 1, 3, 0).reshape(L, T * D, 3)
 
     for trial in range(args.n_trial):

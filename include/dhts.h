@@ -296,6 +296,46 @@ int dhts_macro_rollout_jvp(const dhts_macro_desc *d, int T, const float *tape, i
                            float *t_r_out, float *t_y_out, const int32_t *det, int n_det, float *t_taps,
                            dhts_error *err, void *stream);
 int dhts_macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]);
+
+/*
+ * The rollout AND n_dir = K tangent directions of it in one kernel, without a tape: what dhts_macro_rollout_fwd (or _fwd_sched, or
+ * _fwd_taps) followed by dhts_macro_rollout_jvp returns, bit for bit, from one entry point -- forward-mode differentiation of the
+ * reference's lane rollout (road/lane/_macro_lane.py:83-146; the blocks are those of road/lane/dmacro_lane.py:96-132, applied
+ * untransposed where :277-309 applies their transposes).  Forward mode walks the steps in the forward's order, so the interface products
+ * of a step are used out of on-chip memory where the forward would store its tape entry: the tape (dhts_macro_tape_bytes) does not
+ * exist, and no memory grows with T but the readings the caller asks for.  The arithmetic is the two calls' own (the same device
+ * functions), in the same order; a direction's result does not depend on K, on its slot or on fused versus taped.
+ *   r, y, u, ueq, ghost, ghost_is_sched, r_out .. ueq_out     as dhts_macro_rollout_fwd_taps: ghost [lane][2][4], or the schedule
+ *                       [T][lane][2][4] with ghost_is_sched != 0.  The outputs must not alias the inputs (every launch reads them again).
+ *   t_r, t_y, t_ghost, t_r_out, t_y_out     as dhts_macro_rollout_jvp, t_ghost following ghost_is_sched: NULL = zero,
+ *                       [K][lane][2][2], or [K][T][lane][2][2] beside a schedule
+ *   det, n_det, taps, t_taps     all three pointers or none: taps [T][lane][3][n_det] as dhts_macro_rollout_fwd_taps writes it, t_taps
+ *                       [K][T][lane][2][n_det] as dhts_macro_rollout_jvp does.  The index contract is theirs: every det[j] is compared
+ *                       against [0, n_cells) as an unsigned value before any address is formed from it; an entry outside writes nothing.
+ * There is no state history (the taped operator has none either).  The kernel is the two-phase lane kernel's mapping (one workgroup per
+ * lane; DHTS_OPT_MACRO_FWD_VARIANT and _GROUP do not apply), whose results the pair kernel equals bit for bit.  K directions run as
+ * launches of 4, 2 or 1 (a remainder of 3 as one launch of 4 with a slot masked), at most the number dhts_macro_fwd_jvp_plan reports
+ * per launch: 4 for lanes of up to 997 cells, 2 up to 1239, 1 up to 1410; a longer lane does not fit (its records, the interface
+ * products and two tangent copies per direction exceed 160 KB of LDS) and keeps the taped pair.  Every launch recomputes the primal and
+ * writes the same bits to r_out .. ueq_out; the first one alone writes taps and err.  T = 0: state and tangents come back as they went
+ * in, no row of anything is addressed.
+ * Two fault records, each nullable, kept apart as the pair keeps them:
+ *   err       what the forward reports: DHTS_FAULT_CFL (step, lane, interface)
+ *   err_jvp   what the tangent sweep reports: DHTS_FAULT_NAN with the lane's EARLIEST (step, cell) of a non-finite tangent
+ * A bad descriptor, T < 0, n_dir < 1, a NULL r / y / u / ueq / ghost / t_r / t_y / r_out / y_out / u_out / ueq_out / t_r_out / t_y_out,
+ * det without both taps and t_taps or the reverse, n_det outside 1 .. n_cells with det, or a lane that does not fit: DHTS_E_INVALID,
+ * nothing is dereferenced.
+ * dhts_macro_fwd_jvp_plan: plan[0] wavefronts per lane     plan[1] 64-cell passes per wavefront
+ *   plan[2] direction slots of the widest launch (4, 2, 1; 0: the lane does not fit)     plan[3] number of launches (0 for T = 0 or
+ *   when nothing fits)     plan[4] dynamic LDS bytes of the widest launch     plan[5 .. 7] 0.  n_det: 0 = no readings, else 1 .. n_cells.
+ */
+int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
+                               const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                               const float *t_r, const float *t_y, const float *t_ghost,
+                               float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                               const int32_t *det, int n_det, float *taps, float *t_taps,
+                               dhts_error *err, dhts_error *err_jvp, void *stream);
+int dhts_macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]);
 /* tangent of y = r (u - u_eq(r)): t_y = (dy/dr) t_r + (dy/du) t_u, the partials dhts_macro_state_from_ru_bwd applies, in float32 */
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u,
                                  float *t_y, void *stream);
