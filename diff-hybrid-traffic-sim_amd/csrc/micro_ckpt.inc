@@ -1,0 +1,314 @@
+// micro_ckpt.inc -- reverse mode of the IDM rollout without a tape in memory: the forward keeps the state every S steps, the reverse
+// sweep rebuilds S steps of tape in LDS from a checkpoint, sweeps them out of LDS and moves to the checkpoint before; included by
+// micro_kernels.hip inside namespace dhts, after micro_fwd_jvp.inc.
+//
+// What grows with T is the checkpoint buffer alone, float2 [C][L][Vp] (C = ceil(T / S), Vp = V rounded up to 64; row c = the (p, v)
+// every slot of the lane enters step c S with): 8 B per vehicle per S steps against the 12 B (20 B with the parameter tape) per
+// vehicle-step of micro_rollout_fwd_kernel + micro_rollout_bwd_kernel.
+//
+// Arithmetic: the taped pair's own.  A step forms (dp, dv) by the forward kernel's two expressions from the float32 state and calls
+// idm_step, as micro_rollout_fwd_jvp_kernel does, so pT, vT, hist and the rebuilt entries (e2, e3, l3) are the forward's bits (the build
+// has -ffp-contract=off and idm_step is the one place the step is written); the sweep is micro_rollout_bwd_kernel's
+// one-vehicle-per-thread branch expression for expression -- dot2 with (1, dt, e2, e3) / (0, 0, -e2, l3), the g_hist add, the head's
+// fold in double, the clip test e2 == e3 == l3 == 0, idm_param_jac and the sum[q] += w pj.d[q] order, the length fold, the NaN record.
+//   p_in, v_in, p_out, v_out [L][V] float32      params [6][L][V] double      head [L][2] double      hist [T][L][2][V] float32 or NULL
+//   g_p_in, g_v_in, g_p_out, g_v_out [L][V] float32      g_hist [T][L][2][V] float32 or NULL      g_head [L][2] double
+//   g_params [6][L][V] double (kParams)
+
+// (The dynamic LDS array of the two kernels has a name of its own, lds_ck: block-scope extern declarations of one name are one entity, and
+// an aligned(16) redeclaration of `lds` after micro_rollout_bwd_kernel pads that kernel's static LDS word from 4 to 16 bytes.)
+
+// dynamic LDS of the two kernels: the plan (micro_plan) and the kernels' own carving read these
+__host__ __device__ inline size_t micro_ckpt_fwd_lds_bytes(int V) { return sizeof(float2) * 2 * (size_t)(V + 1); }
+// reverse, fixed part: the replay's state hand-over S[2][V + 1] and the four cotangent arrays of V + 2 floats
+__host__ __device__ inline size_t micro_ckpt_bwd_fixed_bytes(int V) { return sizeof(float2) * 2 * (size_t)(V + 1) + sizeof(float) * 4 * (size_t)(V + 2); }
+// ... and per step of the segment ring: the entry (e2, e3, l3) per vehicle, with kParams also the pre-step (p, v) over V + 1 slots
+__host__ __device__ inline size_t micro_ckpt_bwd_step_bytes(int V, bool params) {
+    return sizeof(MicroTape3) * (size_t)V + (params ? sizeof(float2) * (size_t)(V + 1) : 0);
+}
+__host__ __device__ inline size_t micro_ckpt_bwd_lds_bytes(int V, int S, bool params) {
+    return micro_ckpt_bwd_fixed_bytes(V) + (size_t)S * micro_ckpt_bwd_step_bytes(V, params);
+}
+
+// grid = L workgroups (one traffic lane each) of blockDim.x >= V threads (V rounded up to 64): micro_rollout_fwd_jvp_kernel's mapping
+// without tangents -- one vehicle per thread, its float32 (p, v) and derived parameters in registers for all T steps, the new state left
+// in S [copy][slot] for the follower, copies alternating with the step parity: ONE barrier per step, and that one waits for LDS only
+// (checkpoint and hist stores stay in flight across it).  Dynamic LDS: float2 S[2][V + 1].
+// Before step c Sg every slot of the lane (live or not) stores its (p, v) to row c of ckpt.
+// err: DHTS_FAULT_COLLISION where idm_step reported one, as the forward kernel reports it.  A block smaller than the lane:
+// DHTS_FAULT_CAPACITY (index -3), outputs NaN (the launch sizes the block from the same plan: it does not happen).
+__global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
+    int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
+    const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
+    float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, float *__restrict__ hist, dhts_error *err) {
+    extern __shared__ __attribute__((aligned(16))) float lds_ck[];
+    const int lane = blockIdx.x;
+    const int k = threadIdx.x;
+    const int B = blockDim.x;
+    const int P = V + 1;
+    float2 *S = reinterpret_cast<float2 *>(lds_ck);         // [copy][P]
+    const size_t base = (size_t)lane * V;
+    const size_t plane = (size_t)L * V;
+    const int Vp = (V + 63) & ~63;
+    const int nc = count ? count[lane] : V;
+    const int n = nc < 0 ? 0 : (nc > V ? V : nc);       // (no slot outside the lane is ever addressed)
+    const bool vk = k < n;
+    const bool is_head = k == n - 1;
+    const int kc = k < V ? k : 0;
+    const double inv_dt = 1.0 / dt;
+
+    if (V > B) {
+        const float nanf_ = __builtin_nanf("");
+        for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
+        if (k == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);
+        return;
+    }
+
+    float p = p_in[base + kc], v = v_in[base + kc];      // (a slot at or beyond count keeps them: the outputs pass it through)
+    IdmDerived prm = {};
+    double half_len = 0.;
+    if (vk) {
+        IdmParams raw;
+        raw.a_max = params[0 * plane + base + k]; raw.a_pref = params[1 * plane + base + k];
+        raw.v_target = params[2 * plane + base + k]; raw.min_space = params[3 * plane + base + k];
+        raw.time_pref = params[4 * plane + base + k]; raw.length = params[5 * plane + base + k];
+        prm = idm_derive(raw);
+        idm_set_dt(prm, dt);
+        const int kl = k + 1 < n ? k + 1 : k;
+        half_len = (params[5 * plane + base + kl] + raw.length) * 0.5;
+    }
+    const double head_dp = head[(size_t)lane * 2], head_dv = head[(size_t)lane * 2 + 1];
+
+    for (int i = k; i < 2 * P; i += B) S[i] = make_float2(0.f, 0.f);
+    __syncthreads();
+
+    int fault_step = -1;
+    if (T > 0) {
+        if (vk) S[k] = make_float2(p, v);
+        __syncthreads();
+        float2 *ck = ckpt + (size_t)lane * Vp + k;       // this slot of row 0; a row is L Vp entries
+        int next_ck = 0;
+        for (int step = 0; step < T; ++step) {
+            const int q = step & 1;
+            if (step == next_ck) {
+                if (k < V) *ck = make_float2(p, v);
+                ck += (size_t)L * Vp;
+                next_ck += Sg;
+            }
+            if (vk) {
+                const float2 ls = S[q * P + k + 1];      // the leader's state before this step
+                const double pd = p, vd = v;
+                // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
+                const double dp = is_head ? head_dp : fabs((double)ls.x - pd) - half_len;
+                const double dv = is_head ? head_dv : vd - (double)ls.y;
+                IdmStep o;
+                idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
+                if (o.collided && fault_step < 0) fault_step = step;
+                p = o.np; v = o.nv;
+                S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
+                if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS-only: checkpoint and hist stores stay in flight
+        }
+    }
+    if (k < V) { p_out[base + k] = p; v_out[base + k] = v; }
+    if (fault_step >= 0) raise_fault(err, DHTS_FAULT_COLLISION, fault_step, lane, k);
+}
+
+// grid = L workgroups of blockDim.x >= V threads, one vehicle per thread.  Dynamic LDS (micro_ckpt_bwd_lds_bytes):
+//   float2 S[2][V + 1]             the replay's state hand-over, as in the forward
+//   float2 X[Sg][V + 1]            kParams: the (p, v) a vehicle entered step r of the segment with (slot V is never written nor used)
+//   float  Gp, Gv, C1p, C1v [V + 2]    the cotangents, as in micro_rollout_bwd_kernel (C1[i + 1] = dLeading[i]^T g[i])
+//   float  R[Sg][3][V]             the segment's tape: e2, e3, l3 of step r, one plane each
+// Segments c = C - 1 .. 0: load row c of ckpt (prefetched while the segment after it was swept), replay steps [c Sg, min(T, (c + 1) Sg))
+// into R (and X), one LDS-only barrier per step, then sweep them newest first.  A thread reads back only its own entries of R and X;
+// the leader's X[r][k + 1] is another thread's, and the barrier that ends the replay's last step is what it waits for.  The replay
+// raises no collision: the forward did.  g_hist rows travel two steps ahead in registers, as in micro_rollout_bwd_kernel.
+// err: DHTS_FAULT_NAN at the latest step, lowest vehicle, where a non-finite cotangent appeared.
+template <bool kParams>
+__global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
+    int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
+    const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
+    const float *__restrict__ g_v_in, const float *__restrict__ g_hist, float *__restrict__ g_p_out, float *__restrict__ g_v_out,
+    double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err) {
+    extern __shared__ __attribute__((aligned(16))) float lds_ck[];
+    const int lane = blockIdx.x;
+    const int k = threadIdx.x;
+    const int B = blockDim.x;
+    const int P1 = V + 1, P = V + 2;
+    float2 *S = reinterpret_cast<float2 *>(lds_ck);
+    float2 *X = S + 2 * P1;
+    float *Gp = reinterpret_cast<float *>(X + (kParams ? (size_t)Sg * P1 : 0));
+    float *Gv = Gp + P, *C1p = Gp + 2 * P, *C1v = Gp + 3 * P;
+    float *R = Gp + 4 * P;
+    const size_t base = (size_t)lane * V;
+    const size_t plane = (size_t)L * V;
+    const int Vp = (V + 63) & ~63;
+    const int nc = count ? count[lane] : V;
+    const int n = nc < 0 ? 0 : (nc > V ? V : nc);
+    const bool vk = k < n;
+    const bool is_head = k == n - 1;
+    const int kc = k < V ? k : 0;
+    const double inv_dt = 1.0 / dt;
+    const float dtf = (float)dt;
+
+    if (V > B) {
+        const float nanf_ = __builtin_nanf("");
+        for (int i = k; i < V; i += B) { g_p_out[base + i] = nanf_; g_v_out[base + i] = nanf_; }
+        if (k == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);
+        return;
+    }
+
+    for (int i = k; i < P; i += B) { Gp[i] = 0.f; Gv[i] = 0.f; C1p[i] = 0.f; C1v[i] = 0.f; }
+    for (int i = k; i < 2 * P1; i += B) S[i] = make_float2(0.f, 0.f);
+    __syncthreads();
+    if (vk) { Gp[k] = g_p_in[base + k]; Gv[k] = g_v_in[base + k]; }
+
+    // this thread's vehicle: the forward's derived parameters for the replay, the reverse sweep's for the partials
+    IdmDerived prm = {};
+    IdmParamDerived pm = {};
+    double half_len = 0.;
+    double sum[6] = {0., 0., 0., 0., 0., 0.};           // a_max, a_pref, v_target, min_space, time_pref, gap
+    if (vk) {
+        IdmParams raw;
+        raw.a_max = params[0 * plane + base + k]; raw.a_pref = params[1 * plane + base + k];
+        raw.v_target = params[2 * plane + base + k]; raw.min_space = params[3 * plane + base + k];
+        raw.time_pref = params[4 * plane + base + k]; raw.length = params[5 * plane + base + k];
+        prm = idm_derive(raw);
+        idm_set_dt(prm, dt);
+        if constexpr (kParams) pm = idm_param_derive(raw);
+        half_len = (params[5 * plane + base + (k + 1 < n ? k + 1 : k)] + raw.length) * 0.5;
+    }
+    const double head_dp = head[(size_t)lane * 2], head_dv = head[(size_t)lane * 2 + 1];
+    __syncthreads();
+
+    double gh_p = 0., gh_v = 0.;       // held by the thread that owns the head vehicle
+    int bad_step = -1;                 // first non-finite cotangent this thread meets (the latest step: the sweep runs backwards)
+    const int C = T > 0 ? (T + Sg - 1) / Sg : 0;
+    if (C > 0) {
+        const size_t row = (size_t)L * Vp;
+        const float2 *ck0 = ckpt + (size_t)lane * Vp + kc;
+        float2 ck = ck0[(size_t)(C - 1) * row];
+        const float *gh0 = g_hist ? g_hist + (size_t)lane * 2 * V + kc : nullptr;
+        const size_t h_stride = (size_t)L * 2 * V;
+        float hp1 = 0.f, hv1 = 0.f, hp2 = 0.f, hv2 = 0.f;
+        if (gh0) {
+            const float *a = gh0 + (size_t)(T - 1) * h_stride, *b = gh0 + (size_t)(T > 1 ? T - 2 : 0) * h_stride;
+            hp1 = a[0]; hv1 = a[V]; hp2 = b[0]; hv2 = b[V];
+        }
+        for (int c = C - 1; c >= 0; --c) {
+            const int s0 = c * Sg, s1 = (T - s0 < Sg) ? T : s0 + Sg;
+            float p = ck.x, v = ck.y;
+            ck = ck0[(size_t)(c > 0 ? c - 1 : 0) * row];         // the checkpoint before: in flight across the whole segment
+            // ---- replay steps [s0, s1) into the ring ----
+            if (vk) S[k] = make_float2(p, v);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            for (int r = 0; r < s1 - s0; ++r) {
+                const int q = r & 1;
+                if (vk) {
+                    const float2 ls = S[q * P1 + k + 1];
+                    const double pd = p, vd = v;
+                    // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
+                    const double dp = is_head ? head_dp : fabs((double)ls.x - pd) - half_len;
+                    const double dv = is_head ? head_dv : vd - (double)ls.y;
+                    IdmStep o;
+                    idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
+                    float *e = R + (size_t)r * 3 * V + k;
+                    e[0] = o.dE[2]; e[V] = o.dE[3]; e[2 * V] = o.dLd[3];
+                    if constexpr (kParams) X[(size_t)r * P1 + k] = make_float2(p, v);
+                    p = o.np; v = o.nv;
+                    S[(q ^ 1) * P1 + k] = make_float2(p, v);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            }
+            // ---- sweep them newest first, out of the ring ----
+            for (int step = s1 - 1; step >= s0; --step) {
+                const int r = step - s0;
+                const float chp = hp1, chv = hv1;
+                hp1 = hp2; hv1 = hv2;
+                if (gh0) { const float *a = gh0 + (size_t)(step > 1 ? step - 2 : 0) * h_stride; hp2 = a[0]; hv2 = a[V]; }
+                MicroTape3 e = {0.f, 0.f, 0.f};
+                float2 cx = make_float2(0.f, 0.f);
+                float gv_step = 0.f;
+                if (vk) {
+                    const float *er = R + (size_t)r * 3 * V + k;
+                    e.e2 = er[0]; e.e3 = er[V]; e.l3 = er[2 * V];
+                    float gp = Gp[k], gv = Gv[k];
+                    if (gh0) { gp += chp; gv += chv; }
+                    Gp[k] = dot2(1.f, gp, e.e2, gv);           // grad_ps[:-1] = dqs[:, 0]^T g
+                    Gv[k] = dot2(dtf, gp, e.e3, gv);
+                    C1p[k + 1] = dot2(0.f, gp, -e.e2, gv);     // grad_ps[1:] += dqs[:, 1]^T g
+                    C1v[k + 1] = dot2(0.f, gp, e.l3, gv);
+                    if constexpr (kParams) { cx = X[(size_t)r * P1 + k]; gv_step = gv; }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if constexpr (kParams) {
+                    if (vk) {
+                        // compute_state_delta and the collision / clamp rules of the forward, _micro_lane.py:149-166, 201-212
+                        const float2 xl = X[(size_t)r * P1 + k + 1];
+                        const double pv = cx.y;
+                        double gap = is_head ? head_dp : fabs((double)xl.x - (double)cx.x) - half_len;
+                        double dv = is_head ? head_dv : pv - (double)xl.y;
+                        const bool live_gap = !is_head && gap >= 1e-5;       // else a constant: nothing flows to the lengths
+                        if (gap < 0) { gap = 0; dv = 0; }
+                        gap = (1e-5 > gap) ? 1e-5 : gap;
+                        if (!(e.e2 == 0.f && e.e3 == 0.f && e.l3 == 0.f)) {  // (the forward's acceleration clip zeroes all three)
+                            IdmParamJac pj;
+                            idm_param_jac(pv, gap, dv, pm, dt, pj);
+                            const double w = (double)gv_step * dt;
+#pragma unroll
+                            for (int q = 0; q < 5; ++q) sum[q] += w * pj.d[q];
+                            if (live_gap) sum[5] += w * pj.d[5];
+                        }
+                    }
+                }
+                if (vk) {
+                    float np_ = Gp[k], nv_ = Gv[k];
+                    if (k > 0) { np_ += C1p[k]; nv_ += C1v[k]; }
+                    if (is_head) {
+                        // virtual leader = (p_head + head_dp, v_head - head_dv): its cotangent C1[n] returns to the head
+                        const float vp = C1p[n], vv = C1v[n];
+                        gh_p += (double)vp;
+                        gh_v -= (double)vv;
+                        np_ += vp; nv_ += vv;
+                    }
+                    Gp[k] = np_; Gv[k] = nv_;
+                    if (bad_step < 0 && !(isfinite(np_) && isfinite(nv_))) bad_step = step;
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            }
+        }
+    }
+    __syncthreads();
+    if (k < V) {
+        g_p_out[base + k] = vk ? Gp[k] : 0.f;
+        g_v_out[base + k] = vk ? Gv[k] : 0.f;
+    }
+    if constexpr (kParams) {
+        // length enters a gap as -(len_leader + len) / 2 (_micro_lane.py:211): a vehicle's own gap sum and its follower's
+        double *A = reinterpret_cast<double *>(C1p);            // (C1p, C1v: 2 P floats = P doubles; the sweeps are done with them)
+        __syncthreads();
+        if (k < V) A[k] = vk ? sum[5] : 0.;
+        __syncthreads();
+        if (k < V) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) g_params[q * plane + base + k] = vk ? sum[q] : 0.;
+            g_params[5 * plane + base + k] = vk ? -0.5 * (A[k] + (k > 0 ? A[k - 1] : 0.)) : 0.;
+        }
+    }
+    if (g_head) {
+        if (n == 0) { if (k == 0) { g_head[(size_t)lane * 2] = 0.; g_head[(size_t)lane * 2 + 1] = 0.; } }
+        else if (is_head) { g_head[(size_t)lane * 2] = gh_p; g_head[(size_t)lane * 2 + 1] = gh_v; }
+    }
+    // the lane's report: the latest step at which a non-finite cotangent appeared (the first the sweep met), lowest vehicle -- the
+    // maximum of (step, 1023 - vehicle) through one LDS word, off the data path
+    int *word = reinterpret_cast<int *>(lds_ck);
+    __syncthreads();
+    if (k == 0) *word = -1;
+    __syncthreads();
+    static_assert(DHTS_MICRO_MAX_VEHICLES <= 1024, "the vehicle takes 10 bits of the key");
+    if (bad_step >= 0) atomicMax(word, (bad_step << 10) | (1023 - k));
+    __syncthreads();
+    const int last = *word;
+    if (k == 0 && last >= 0) raise_fault(err, DHTS_FAULT_NAN, last >> 10, lane, 1023 - (last & 1023));
+}

@@ -12,6 +12,8 @@
 //   vehicle and to the head gap (dmicro_lane.py:130-153, 271-298).
 // Tangent (micro_rollout_jvp_kernel, micro_jvp.inc): the same blocks untransposed, oldest step first, K directions per pass over the tape.
 // Fused (micro_rollout_fwd_jvp_kernel, micro_fwd_jvp.inc): the forward and K tangent directions stepped together, no tape at all.
+// Checkpointed (micro_rollout_ckpt_fwd_kernel / _bwd_kernel, micro_ckpt.inc): reverse mode with the state kept every S steps and the tape
+//   of one segment at a time rebuilt in LDS.
 //
 // Reference: road/lane/_micro_lane.py:131-214, road/lane/dmicro_lane.py:87-127 and :271-298.
 #include <hip/hip_runtime.h>
@@ -494,6 +496,8 @@ __global__ void micro_step_tensor_fwd_kernel(int L, int V, double dt, const floa
 #include "micro_jvp.inc"
 // ---- the rollout and its tangents in one kernel, no tape (dhts_micro_rollout_fwd_jvp) ----------------------------
 #include "micro_fwd_jvp.inc"
+// ---- reverse mode from checkpoints, the segment tape in LDS (dhts_micro_rollout_fwd_ckpt / _bwd_ckpt) -------------
+#include "micro_ckpt.inc"
 
 }  // namespace dhts
 
@@ -519,7 +523,21 @@ struct MicroPlan {
     // the tape-free fused forward + tangent kernel (dhts_micro_rollout_fwd_jvp, micro_fwd_jvp.inc)
     int fwd_jvp_block;       // threads per lane: the whole lane, one vehicle per thread holds its state and its tangents
     int fwd_jvp_kmax[2];     // directions a launch may carry, [0] state-only, [1] with t_params
+    // the checkpointed pair (dhts_micro_rollout_fwd_ckpt / _bwd_ckpt, micro_ckpt.inc)
+    int ckpt_block;          // threads per lane of both kernels: the whole lane, one vehicle per thread
+    int ckpt_max_segment[2]; // steps the reverse kernel's ring can hold within kCkptLdsBudget, [0] state-only, [1] with g_params
+    int ckpt_segment;        // the segment length a caller gets who names none (one value for both reverse kernels: the forward
+                             // that writes the checkpoints does not know which of them will read them)
 };
+constexpr size_t kCkptLdsBudget = 160 * 1024;      // LDS of a CU: what one workgroup may take
+// The default segment: the longest, up to kCkptSegmentCap, whose reverse workgroup (sized with the parameter ring) still leaves
+// kCkptWavesPerCu wavefronts resident on a CU by LDS -- a longer segment divides the checkpoint bytes further, but the sweep is a
+// chain of LDS-only barriers that only other resident workgroups hide (DESIGN.md section 4e has the sweep both were set from).
+constexpr int kCkptSegmentCap = 16;
+constexpr int kCkptWavesPerCu = 16;
+static int micro_ckpt_max_segment(int V, bool params) {
+    return (int)((kCkptLdsBudget - micro_ckpt_bwd_fixed_bytes(V)) / micro_ckpt_bwd_step_bytes(V, params));
+}
 static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     MicroPlan pl;
     // wavefronts per lane: one wave keeps the whole lane free of barriers; with few lanes per SIMD more waves per lane buy
@@ -539,8 +557,24 @@ static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     pl.fwd_jvp_block = padded64(d->capacity);
     pl.fwd_jvp_kmax[0] = 4;
     pl.fwd_jvp_kmax[1] = 4;
+    pl.ckpt_block = padded64(d->capacity);
+    pl.ckpt_max_segment[0] = micro_ckpt_max_segment(d->capacity, false);
+    pl.ckpt_max_segment[1] = micro_ckpt_max_segment(d->capacity, true);
+    const int waves = pl.ckpt_block / 64;
+    const int groups = (kCkptWavesPerCu + waves - 1) / waves;                    // workgroups per CU that make kCkptWavesPerCu
+    const long long room = (long long)(kCkptLdsBudget / groups) - (long long)micro_ckpt_bwd_fixed_bytes(d->capacity);
+    int S = room > 0 ? (int)(room / (long long)micro_ckpt_bwd_step_bytes(d->capacity, true)) : 0;
+    S = S > kCkptSegmentCap ? kCkptSegmentCap : S;
+    S = S > pl.ckpt_max_segment[1] ? pl.ckpt_max_segment[1] : S;
+    pl.ckpt_segment = S < 1 ? 1 : S;
     return pl;
 }
+// the segment a call runs with: the caller's, or the plan's for 0; -1 where the reverse kernel's ring cannot hold it
+static int micro_ckpt_segment(const MicroPlan &pl, int segment, bool params) {
+    if (segment < 0 || segment > pl.ckpt_max_segment[params ? 1 : 0]) return -1;
+    return segment == 0 ? pl.ckpt_segment : segment;
+}
+static int micro_ckpt_count(int T, int S) { return T > 0 ? (T + S - 1) / S : 0; }
 
 template <bool kCompact, bool kParams = false>
 static int micro_fwd_launch(const dhts_micro_desc *d, int T,
@@ -644,6 +678,32 @@ static int micro_fwd_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, cons
         k0 += n_act;
     }
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+// the checkpointed pair: both read block and segment off the plan; the reverse kernel asks for its LDS above 64 KB
+static int micro_ckpt_fwd_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                 const double *params, const double *head, float *p_out, float *v_out, void *ckpt, float *hist,
+                                 dhts_error *err, void *stream) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int S = micro_ckpt_segment(pl, segment, false);        // (a forward is valid for every segment some reverse kernel can take)
+    if (S < 0) return DHTS_E_INVALID;
+    const bool ok = launch_lds(micro_rollout_ckpt_fwd_kernel, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity), kLdsDefault,
+                               stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out, (float2 *)ckpt, hist, err);
+    return ok ? launch_status() : DHTS_E_LAUNCH;
+}
+static int micro_ckpt_bwd_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count, const double *params,
+                                 const double *head, const float *g_p, const float *g_v, const float *g_hist, float *g_p_out,
+                                 float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int S = micro_ckpt_segment(pl, segment, g_params != nullptr);
+    if (S < 0) return DHTS_E_INVALID;
+    bool ok = true;
+    pick<0, 1>(g_params != nullptr, [&](auto pv) {
+        constexpr bool kParams = decltype(pv)::value != 0;
+        ok = launch_lds(micro_rollout_ckpt_bwd_kernel<kParams>, d->n_lanes, pl.ckpt_block, micro_ckpt_bwd_lds_bytes(d->capacity, S, kParams),
+                        kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, (const float2 *)ckpt, count, params, head, g_p, g_v, g_hist,
+                        g_p_out, g_v_out, g_head, g_params, err);
+    });
+    return ok ? launch_status() : DHTS_E_LAUNCH;
 }
 template <bool kHeadOnly>
 static int micro_step_tensor_launch(const dhts_micro_desc *d, const float *p, const float *v, const int32_t *count, const double *params,
@@ -764,6 +824,41 @@ int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want
     plan[2] = g.launches;
     plan[3] = (int32_t)micro_fwd_jvp_lds_bytes(d->capacity, g.widest);
     return DHTS_OK;
+}
+// ---- reverse mode from checkpoints, the segment tape in LDS ----------------------------------------------------------------------
+int dhts_micro_ckpt_plan(const dhts_micro_desc *d, int T, int want_params, int segment, int32_t plan[8]) {
+    if (!micro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
+    const MicroPlan pl = micro_plan(d, T, false);
+    const int S = micro_ckpt_segment(pl, segment, want_params != 0);
+    if (S < 0) return DHTS_E_INVALID;
+    const size_t bwd_lds = micro_ckpt_bwd_lds_bytes(d->capacity, S, want_params != 0);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.ckpt_block;
+    plan[1] = S;
+    plan[2] = pl.ckpt_max_segment[want_params != 0 ? 1 : 0];
+    plan[3] = micro_ckpt_count(T, S);
+    plan[4] = (int32_t)micro_ckpt_fwd_lds_bytes(d->capacity);
+    plan[5] = (int32_t)bwd_lds;
+    plan[6] = (int32_t)(kCkptLdsBudget / bwd_lds);
+    return DHTS_OK;
+}
+size_t dhts_micro_ckpt_bytes(const dhts_micro_desc *d, int T, int segment) {
+    if (!micro_desc_ok(d) || T < 0) return 0;
+    const int S = micro_ckpt_segment(micro_plan(d, T, false), segment, false);
+    if (S < 0) return 0;
+    return (size_t)micro_ckpt_count(T, S) * d->n_lanes * padded64(d->capacity) * sizeof(float2);
+}
+int dhts_micro_rollout_fwd_ckpt(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                const double *params, const double *head, float *p_out, float *v_out, void *ckpt, float *hist,
+                                dhts_error *err, void *stream) {
+    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || !head || !p_out || !v_out || (T > 0 && !ckpt)) return DHTS_E_INVALID;
+    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt, hist, err, stream);
+}
+int dhts_micro_rollout_bwd_ckpt(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count, const double *params,
+                                const double *head, const float *g_p, const float *g_v, const float *g_hist, float *g_p_out,
+                                float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream) {
+    if (!micro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !params || !head || !g_p || !g_v || !g_p_out || !g_v_out) return DHTS_E_INVALID;
+    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, g_params, err, stream);
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)
 int dhts_micro_step_fwd(const dhts_micro_desc *d,

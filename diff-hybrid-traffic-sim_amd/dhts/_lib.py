@@ -137,6 +137,10 @@ SIGNATURES = {
     "dhts_micro_jvp_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
     "dhts_micro_rollout_fwd_jvp": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 18),
     "dhts_micro_fwd_jvp_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
+    "dhts_micro_ckpt_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
+    "dhts_micro_ckpt_bytes": (C.c_size_t, [C.POINTER(MicroDesc), C.c_int, C.c_int]),
+    "dhts_micro_rollout_fwd_ckpt": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 11),
+    "dhts_micro_rollout_bwd_ckpt": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 13),
     "dhts_micro_step_fwd": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor_head": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),

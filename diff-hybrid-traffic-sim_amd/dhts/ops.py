@@ -9,6 +9,7 @@ Mirrors the reference operators
 batched over lanes and fused over time steps.
 """
 import ctypes as C
+import operator
 import warnings
 
 import torch
@@ -771,6 +772,96 @@ def micro_fwd_jvp_plan(desc, T, n_dir, want_params=False):
     return dict(zip(_MICRO_JVP_PLAN_KEYS, list(plan)))
 
 
+# ---- reverse mode from checkpoints: the tape of one segment at a time, in LDS ------------------------------------------------------------
+_MICRO_CKPT_PLAN_KEYS = ("block", "segment", "max_segment", "checkpoints", "fwd_lds_bytes", "bwd_lds_bytes", "bwd_groups_per_cu")
+
+
+def micro_ckpt_plan(desc, T, want_params=False, segment=0):
+    """What dhts_micro_rollout_fwd_ckpt / _bwd_ckpt launch for this shape (include/dhts.h): the block, the segment length used (the plan's
+    own for segment = 0), the longest one the reverse kernel's LDS holds (shorter with want_params), the number of checkpoints
+    ceil(T / segment), the dynamic LDS bytes of the two kernels and the reverse workgroups a CU holds by LDS.  ValueError: a segment
+    outside 0 .. max_segment."""
+    plan = (C.c_int32 * 8)()
+    if not 0 <= int(segment) <= 0x7fffffff:
+        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
+    status = _lib.lib().dhts_micro_ckpt_plan(C.byref(desc), int(T), int(bool(want_params)), int(segment), C.byref(plan))
+    if status == _lib.E_INVALID and int(T) >= 0:
+        raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment for %d vehicle slots%s" %
+                         (desc.capacity, " with the parameter gradient" if want_params else ""))
+    check(status, "dhts_micro_ckpt_plan")
+    return dict(zip(_MICRO_CKPT_PLAN_KEYS, list(plan)))
+
+
+def micro_ckpt_numel(desc, T, segment=0):
+    """float32 elements of the checkpoint buffer (opaque: the float32 (p, v) of every slot every `segment` steps, include/dhts.h)."""
+    return _lib.lib().dhts_micro_ckpt_bytes(C.byref(desc), int(T), int(segment)) // 4
+
+
+def micro_rollout_fwd_ckpt(desc, T, p, v, params, head, ckpt, count=None, segment=0, hist=None, err=None, out=None):
+    """micro_rollout_fwd that fills the checkpoint buffer `ckpt` (float32 [micro_ckpt_numel(desc, T, segment)]) instead of a tape
+    (dhts_micro_rollout_fwd_ckpt): the same (pT, vT) and hist, bit for bit."""
+    L, V = desc.n_lanes, desc.capacity
+    micro_ckpt_plan(desc, T, False, segment)
+    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
+        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
+    p, v = _f32c(p, "p"), _f32c(v, "v")
+    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
+        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
+    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
+        raise ValueError("params must be float64 [6][L][V]")
+    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
+        raise ValueError("head must be float64 [L][2]")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    params, head = params.contiguous(), head.contiguous()
+    if out is None:
+        out = (torch.empty_like(p), torch.empty_like(v))
+    check(_lib.lib().dhts_micro_rollout_fwd_ckpt(C.byref(desc), int(T), int(segment), _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(ckpt) if ckpt.numel() else None,
+                                                 _ptr(hist) if hist is not None and hist.numel() else None, _ptr(err), _stream()),
+          "dhts_micro_rollout_fwd_ckpt")
+    return out
+
+
+def micro_rollout_bwd_ckpt(desc, T, ckpt, params, head, g_p, g_v, count=None, segment=0, g_hist=None, err=None, out=None, g_head=None,
+                           g_params=None):
+    """Reverse sweep from the checkpoints of micro_rollout_fwd_ckpt -> (g_p0, g_v0, g_head): micro_rollout_bwd's bits.  params, head,
+    count, segment: the forward's.  g_params (float64 [6][L][V], filled here): also the gradient w.r.t. the driver parameters."""
+    L, V = desc.n_lanes, desc.capacity
+    micro_ckpt_plan(desc, T, g_params is not None, segment)
+    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
+        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
+    for name, t in (("params", params), ("g_params", g_params)):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
+    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2) or not head.is_contiguous():
+        raise ValueError("head must be a contiguous float64 [L][2]")
+    g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
+    if out is None:
+        out = (torch.empty_like(g_p), torch.empty_like(g_v))
+    if g_head is None:
+        g_head = torch.zeros(L, 2, dtype=torch.float64, device=g_p.device)
+    check(_lib.lib().dhts_micro_rollout_bwd_ckpt(C.byref(desc), int(T), int(segment), _ptr(ckpt) if ckpt.numel() else None, _ptr(count),
+                                                 _ptr(params), _ptr(head), _ptr(g_p), _ptr(g_v), _ptr(g_hist), _ptr(out[0]), _ptr(out[1]),
+                                                 _ptr(g_head), _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt")
+    return out[0], out[1], g_head
+
+
+def _checkpoint_segment(checkpoint, desc, T, want_params):
+    """The `checkpoint` argument of micro_rollout -> None (the taped path) or the segment length to run with; ValueError otherwise."""
+    if checkpoint is None or checkpoint is False:
+        return None
+    if checkpoint is True:
+        return micro_ckpt_plan(desc, T, want_params)["segment"]
+    try:
+        segment = operator.index(checkpoint)
+    except TypeError:
+        segment = 0
+    if segment < 1:
+        raise ValueError("checkpoint must be None, False, True or a positive int (the segment length), not %r" % (checkpoint,))
+    return micro_ckpt_plan(desc, T, want_params, segment)["segment"]
+
+
 def micro_step_bwd(desc, tape, g_p, g_v, count=None):
     """dMicroForwardLayer.backward for a batch of lanes: returns (g_p[L][V], g_v[L][V], g_virtual[L][2] float64),
     g_virtual = raw cotangent of the virtual leader slot (not folded into the head vehicle)."""
@@ -792,15 +883,22 @@ class MicroRollout(torch.autograd.Function):
     So are the driver parameters: when `params` [6][L][V] float64 requires grad, the forward also fills the parameter tape and the
     reverse sweep returns d loss / d params (what autograd of the reference's plain MicroLane gives for tensor attributes,
     _micro_lane.py:131-214 over _idm.py:30-49); outputs and the other gradients are bit for bit those of a call without it.
+    checkpoint (None / False: the taped path; True: the plan's segment length; a positive int: that one): keep the state every so many
+    steps instead of the tapes, and let the reverse sweep rebuild one segment of tape at a time in LDS (micro_ckpt_plan) -- the same
+    outputs and gradients bit for bit, and the only buffer that grows with T is 8 B per vehicle per segment.
     """
 
     @staticmethod
-    def forward(ctx, p0, v0, params, head, count, T, dt, want_hist=False, check_faults=True):
+    def forward(ctx, p0, v0, params, head, count, T, dt, want_hist=False, check_faults=True, checkpoint=None):
         L, V = p0.shape
         desc = micro_desc(L, V, dt)
-        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
         want_params = params.requires_grad
+        segment = _checkpoint_segment(checkpoint, desc, T, want_params)       # (ValueError before anything touches a device)
+        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
         need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or want_params
+        if segment is not None and need_grad:
+            return MicroRollout._forward_ckpt(ctx, p0c, v0c, params, head, count, desc, T, want_hist, check_faults, segment, want_params)
+        ctx.segment = None
         tape = torch.empty(micro_tape_numel(desc, T), dtype=torch.float32, device=p0.device) if need_grad else None
         hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=p0.device) if want_hist else None
         err = new_error_record(p0.device)
@@ -822,23 +920,45 @@ class MicroRollout(torch.autograd.Function):
         return pT, vT
 
     @staticmethod
+    def _forward_ckpt(ctx, p0c, v0c, params, head, count, desc, T, want_hist, check_faults, segment, want_params):
+        """The forward of a checkpointed call: everything the pair needs is made here -- the checkpoint buffer, hist, g_params and the two
+        fault records; neither tape exists."""
+        L, V, dev = desc.n_lanes, desc.capacity, p0c.device
+        ctx.tape = ctx.ptape = None
+        ctx.params, ctx.head = params.detach().contiguous(), head.detach().contiguous()
+        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
+        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev)
+        hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=dev) if want_hist else None
+        err = new_error_record(dev)
+        pT, vT = micro_rollout_fwd_ckpt(desc, T, p0c, v0c, ctx.params, ctx.head, ctx.ckpt, count=count, segment=segment, hist=hist, err=err)
+        if check_faults:
+            raise_on_fault(err)
+        ctx.desc, ctx.T, ctx.count, ctx.want_hist, ctx.check_faults, ctx.segment = desc, T, count, want_hist, check_faults, segment
+        ctx.err_bwd = new_error_record(dev)
+        return (pT, vT, hist) if want_hist else (pT, vT)
+
+    @staticmethod
     def backward(ctx, g_pT, g_vT, g_hist=None):
         desc, T = ctx.desc, ctx.T
-        dev = ctx.tape.device
+        dev = ctx.err_bwd.device
         L, V = desc.n_lanes, desc.capacity
         g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
         g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
         gh = g_hist.contiguous() if (ctx.want_hist and g_hist is not None) else None
         err = ctx.err_bwd
         err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
-        g_p0, g_v0, g_head = micro_rollout_bwd(desc, T, ctx.tape, g_p, g_v, count=ctx.count, g_hist=gh, err=err,
-                                               ptape=ctx.ptape, params=ctx.params, g_params=ctx.g_params)
+        if ctx.segment is not None:
+            g_p0, g_v0, g_head = micro_rollout_bwd_ckpt(desc, T, ctx.ckpt, ctx.params, ctx.head, g_p, g_v, count=ctx.count,
+                                                        segment=ctx.segment, g_hist=gh, err=err, g_params=ctx.g_params)
+        else:
+            g_p0, g_v0, g_head = micro_rollout_bwd(desc, T, ctx.tape, g_p, g_v, count=ctx.count, g_hist=gh, err=err,
+                                                   ptape=ctx.ptape, params=ctx.params, g_params=ctx.g_params)
         # The record only feeds a warning (the reference's micro backward returns NaNs silently, dmicro_lane.py:271-298): it is not
         # read back here -- that would be a host synchronisation per reverse sweep -- unless the gradient that is being returned
         # anyway is non-finite, which the caller's next use of it would synchronise on as well.
         if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
             MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
-        return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None
+        return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None, None
 
 
 def micro_bwd_fault(warn=True):
@@ -855,8 +975,9 @@ def micro_bwd_fault(warn=True):
     return step, lane, index
 
 
-def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True):
-    return MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), want_hist, bool(check_faults))
+def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None):
+    """MicroRollout.  checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape)."""
+    return MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), want_hist, bool(check_faults), checkpoint)
 
 
 # ---------------------------------------------------------------------------------------------------------

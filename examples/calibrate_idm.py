@@ -11,7 +11,8 @@ their Jacobian has five columns, so ONE dhts.micro_rollout_jvp call with K = 5 d
 every vehicle, want_hist=True) returns the trajectories AND the whole Jacobian in one pass over the rollout tape; the 5 x 5 normal
 equations are formed and solved on the device, a step is kept where it lowers the loss (one more rollout, no tape) and the damping
 follows.  Same box, same log.  --fused steps the rollout and the five tangents in one kernel (fused=True): no tape, no parameter tape,
-the same numbers bit for bit.
+the same numbers bit for bit.  --checkpoint [S] (Adam) runs the reverse mode from checkpoints (dhts.micro_rollout(checkpoint=...)): the
+state every S steps (the library's own S when none is given) instead of 20 B of tapes per vehicle-step, the same log bit for bit.
 Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt (lm: .../lm/trial_k.txt), like the other examples.
 """
 import argparse
@@ -42,11 +43,15 @@ def main():
     ap.add_argument("--method", choices=("adam", "lm"), default="adam")
     ap.add_argument("--damping", type=float, default=1e-2, help="Levenberg-Marquardt: the first damping factor")
     ap.add_argument("--fused", action="store_true", help="Levenberg-Marquardt: rollout and tangents in one tape-free kernel")
+    ap.add_argument("--checkpoint", type=int, nargs="?", const=True, default=None, metavar="S",
+                    help="Adam: reverse mode from checkpoints every S steps (no S: the library's choice) instead of the tapes")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
     if args.fused and args.method != "lm":
         ap.error("--fused belongs to --method lm")
+    if args.checkpoint is not None and args.method != "adam":
+        ap.error("--checkpoint belongs to --method adam")
 
     dev = th.device("cuda", 0)
     th.manual_seed(args.seed)
@@ -61,7 +66,7 @@ def main():
 
     def rollout(theta):
         params = th.cat([theta, length])[:, None, None].expand(6, L, V)
-        return dhts.micro_rollout(p0, v0, params, head, T, dt, want_hist=True)[2]
+        return dhts.micro_rollout(p0, v0, params, head, T, dt, want_hist=True, checkpoint=args.checkpoint)[2]
 
     for trial in range(args.n_trial):
         p0 = (th.arange(V, device=dev) * 4.0 * ln)[None, :] + th.rand(L, V, device=dev) * 2.0 * ln

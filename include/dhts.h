@@ -527,6 +527,41 @@ int dhts_micro_rollout_fwd_jvp(const dhts_micro_desc *d, int T, int n_dir, const
                                float *t_hist, dhts_error *err, dhts_error *err_jvp, void *stream);
 int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]);
 
+/*
+ * The rollout's REVERSE mode without a tape in memory: what dhts_micro_rollout_fwd + dhts_micro_rollout_bwd (or _fwd_params +
+ * _bwd_params, with g_params) return, bit for bit, from checkpoints.  Replaces the same T x L calls of dMicroForwardLayer.forward
+ * (dmicro_lane.py:230-269 = MicroLane.forward _micro_lane.py:131-214 + dMicroLane._backward :87-127) and of
+ * dMicroForwardLayer.backward (dmicro_lane.py:271-298, with the virtual-leader slot of dMicroLane.vectorize_input :130-153); the
+ * parameter gradient is that of road/lane/_micro_lane.py:131-214 over IDM.compute_acceleration, model/micro/_idm.py:30-49.
+ * The forward keeps the float32 state every S steps (S = the segment); the reverse sweep takes the segments last to first: it steps a
+ * segment again from its checkpoint -- the same device function on the same float32 operands, so the entries (e2, e3, l3) and the
+ * pre-step (p, v) are the tapes' bits --, holds them in LDS, and sweeps them newest first.  Neither the tape (dhts_micro_tape_bytes)
+ * nor the parameter tape (dhts_micro_param_tape_bytes) exists; what grows with T is
+ *     ckpt    dhts_micro_ckpt_bytes = C x L x Vp x 8 B, C = ceil(T / S) (0 for T = 0), Vp = capacity rounded up to 64; opaque
+ * i.e. 8 B per vehicle per S steps instead of 12 B (20 B with the parameter tape) per vehicle-step.
+ *   segment   0 = the plan's choice, else 1 .. the max_segment dhts_micro_ckpt_plan reports (the reverse kernel's LDS holds a segment:
+ *             fewer steps with g_params); the forward, the reverse sweep and dhts_micro_ckpt_bytes must be given the same value
+ *   dhts_micro_rollout_fwd_ckpt   p, v, count, params, head, p_out, v_out, hist, err as dhts_micro_rollout_fwd (same bits, hist at live
+ *                                 slots; DHTS_FAULT_COLLISION likewise); ckpt is filled (NULL is accepted for T = 0)
+ *   dhts_micro_rollout_bwd_ckpt   count, params, head: the forward's; g_p, g_v, g_hist, g_p_out, g_v_out, g_head, err as
+ *                                 dhts_micro_rollout_bwd; g_params [6][L][V] DOUBLE as dhts_micro_rollout_bwd_params, or NULL: state only
+ * The replay raises no collision again.  err of the reverse sweep: DHTS_FAULT_NAN at the latest step, lowest vehicle, as the taped sweep.
+ * A bad descriptor, T < 0, a segment outside 0 .. max_segment, or a NULL p / v / params / head / p_out / v_out / g_p / g_v / g_p_out /
+ * g_v_out (ckpt with T > 0): DHTS_E_INVALID, nothing is dereferenced (dhts_micro_ckpt_bytes: 0).
+ * dhts_micro_ckpt_plan (want_params: the reverse sweep will be handed g_params):
+ *   plan[0] block size of both kernels (the lane rounded up to 64: one vehicle per thread)     plan[1] the segment S used
+ *   plan[2] max_segment     plan[3] C     plan[4] dynamic LDS bytes of the forward     plan[5] of the reverse kernel
+ *   plan[6] reverse workgroups a CU holds by LDS (160 KB / plan[5])     plan[7] 0
+ */
+int dhts_micro_ckpt_plan(const dhts_micro_desc *d, int T, int want_params, int segment, int32_t plan[8]);
+size_t dhts_micro_ckpt_bytes(const dhts_micro_desc *d, int T, int segment);
+int dhts_micro_rollout_fwd_ckpt(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                const double *params, const double *head, float *p_out, float *v_out, void *ckpt, float *hist,
+                                dhts_error *err, void *stream);
+int dhts_micro_rollout_bwd_ckpt(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count, const double *params,
+                                const double *head, const float *g_p, const float *g_v, const float *g_hist, float *g_p_out,
+                                float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
