@@ -1348,6 +1348,9 @@ __global__ void macro_u_tap_bwd_kernel(int64_t n, float um, const float *__restr
 // ---- the rollout and its tangents in one kernel, no tape (dhts_macro_rollout_fwd_jvp) ----------------------------
 #include "macro_fwd_jvp.inc"
 
+// ---- reverse mode from checkpoints, the segment's interface products in LDS (dhts_macro_rollout_fwd_ckpt / _bwd_ckpt) ----
+#include "macro_ckpt.inc"
+
 }  // namespace dhts
 
 // ---- C ABI -----------------------------------------------------------------------------------------------
@@ -1725,6 +1728,88 @@ static int macro_fwd_jvp_launch(const dhts_macro_desc *d, int T, int n_dir, cons
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
+// The checkpointed pair (macro_ckpt.inc): the lane kernel's mapping for both kernels (W wavefronts of p passes as macro_plan computes them
+// for the two-phase lane kernel, at most 12 wavefronts; DHTS_OPT_MACRO_FWD_WAVES, _VARIANT and _GROUP do not apply: there is one kernel
+// pair, and every lane it takes has p = 1 or 2), the longest segment whose reverse LDS -- parked pointers, records, planes, one ring entry per step -- fits
+// kMacroCkptLdsBudget (0: not even one step fits, 1320 cells and above; the taped pair covers those lanes) and the segment a caller gets
+// who names none.  A pure function of the lane length: the two launches, dhts_macro_ckpt_plan and dhts_macro_ckpt_bytes read it.
+// The default segment is 4e's rule with this kernel's numbers: the longest, up to kMacroCkptSegmentCap, whose reverse workgroup still
+// leaves the residency the sweep needs to hide its barrier chain (replay and sweep are barrier chains: what hides them is another
+// workgroup).  That residency is kMacroCkptWavesPerCu = 12 wavefronts on a CU -- three per SIMD, all the reverse kernel's registers
+// admit --, or, for lanes whose LDS does not reach it even with a one-step ring, the workgroups per CU a one-step ring has.  Measured
+// (DESIGN 4f): the fastest pair at 1024 x 512 (S = 2 of 1 .. 7) and at 4096 x 64 (S = 3 of 1 .. 75) is the one this picks.
+constexpr size_t kMacroCkptLdsBudget = 160 * 1024;      // LDS of a CU: what one workgroup may take
+constexpr int kMacroCkptSegmentCap = 16;
+constexpr int kMacroCkptWavesPerCu = 12;
+struct MacroCkptPlan {
+    int W, p;             // wavefronts per lane, 64-cell passes per wavefront
+    int segment;          // the plan's own segment length
+    int max_segment;      // the longest one the reverse kernel's LDS holds; 0: the lane does not fit
+    size_t lds_fwd;
+};
+static MacroCkptPlan macro_ckpt_plan(const dhts_macro_desc *d) {
+    MacroCkptPlan pl = {};
+    const int N = d->n_cells;
+    int W = (N + 127) / 128;
+    if (W > 12) W = 12;
+    pl.p = (N + 64 * W - 1) / (64 * W);
+    pl.W = (N + 64 * pl.p - 1) / (64 * pl.p);
+    pl.lds_fwd = macro_ckpt_fwd_lds_bytes(N);
+    const size_t fixed = macro_ckpt_bwd_fixed_bytes(N), step = macro_ckpt_bwd_step_bytes(N);
+    pl.max_segment = fixed + step <= kMacroCkptLdsBudget && pl.p <= 2 ? (int)((kMacroCkptLdsBudget - fixed) / step) : 0;
+    const int by_regs = (kMacroCkptWavesPerCu + pl.W - 1) / pl.W;               // workgroups per CU that make kMacroCkptWavesPerCu
+    const int at_one = (int)(kMacroCkptLdsBudget / (fixed + step));             // ... that a one-step ring leaves
+    const int groups = at_one < 1 ? 1 : (by_regs < at_one ? by_regs : at_one);
+    const long long room = (long long)(kMacroCkptLdsBudget / groups) - (long long)fixed;
+    int S = room > 0 ? (int)(room / (long long)step) : 0;
+    S = S > kMacroCkptSegmentCap ? kMacroCkptSegmentCap : S;
+    S = S < 1 ? 1 : S;
+    pl.segment = S > pl.max_segment ? pl.max_segment : S;
+    return pl;
+}
+// the segment a call runs with: `segment` itself, the plan's for 0; -1: outside 0 .. max_segment, or the lane does not fit
+static int macro_ckpt_segment(const MacroCkptPlan &pl, int segment) {
+    if (pl.max_segment < 1 || segment < 0 || segment > pl.max_segment) return -1;
+    return segment == 0 ? pl.segment : segment;
+}
+static int macro_ckpt_count(int T, int S) { return T > 0 ? (T + S - 1) / S : 0; }
+
+static int macro_ckpt_fwd_launch(const dhts_macro_desc *d, int T, int S, const MacroCkptPlan &pl,
+                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                 float *r_out, float *y_out, float *u_out, float *ueq_out, const int32_t *det, int n_det, float *taps,
+                                 void *ckpt, dhts_error *err, void *stream) {
+    const int L = d->n_lanes, N = d->n_cells;
+    bool lds_ok = true;
+    pick<1, 2>(pl.p, [&](auto pv) {
+        pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
+            pick<0, 1>(det != nullptr, [&](auto tap) {
+                constexpr int kP = decltype(pv)::value;
+                constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
+                lds_ok = launch_lds(macro_rollout_ckpt_fwd_kernel<kP, kS, kT>, L, 64 * pl.W, pl.lds_fwd, kLdsDefault, stream, L, N, T, S, d->dt,
+                                    d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float2 *>(ckpt), err,
+                                    det, n_det, taps);
+            });
+        });
+    });
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+static int macro_ckpt_bwd_launch(const dhts_macro_desc *d, int T, int S, const MacroCkptPlan &pl, const void *ckpt,
+                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                 const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                 float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
+    const int L = d->n_lanes, N = d->n_cells;
+    bool lds_ok = true;
+    pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
+        pick<0, 1>(det != nullptr, [&](auto tap) {
+            constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
+            lds_ok = launch_lds(macro_rollout_ckpt_bwd_kernel<kS, kT>, L, 64 * pl.W, macro_ckpt_bwd_lds_bytes(N, S), kLdsDefault, stream, L, N, T, S,
+                                pl.p, d->dt, d->dx, d->u_max, reinterpret_cast<const float2 *>(ckpt), r, y, u, ueq, ghost, g_r, g_y, g_taps,
+                                g_r_out, g_y_out, g_ghost, err, det, n_det);
+        });
+    });
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+
 #ifdef DHTS_FWD3_STAMPS
 extern "C" int dhts_debug_fwd_clock(long long *out) {         // [2 kernels][16 workgroups][2]
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(dhts::dhts_fwd_clock), sizeof(long long) * 2 * 16 * 2) == hipSuccess ? 0 : -1;
@@ -1929,6 +2014,64 @@ int dhts_macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_de
     plan[0] = pl.W; plan[1] = pl.p; plan[2] = pl.widest; plan[3] = pl.launches; plan[4] = (int32_t)pl.lds;
     plan[5] = plan[6] = plan[7] = 0;
     return DHTS_OK;
+}
+// ---- reverse mode from checkpoints, the segment's interface products in LDS ------------------------------------------------------
+int dhts_macro_ckpt_plan(const dhts_macro_desc *d, int T, int n_det, int segment, int32_t plan[8]) {
+    if (!macro_desc_ok(d) || T < 0 || !plan || n_det < 0 || n_det > d->n_cells || segment < 0) return DHTS_E_INVALID;
+    const MacroCkptPlan pl = macro_ckpt_plan(d);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.W; plan[1] = pl.p; plan[3] = pl.max_segment; plan[5] = (int32_t)pl.lds_fwd;
+    if (pl.max_segment < 1) return segment == 0 ? DHTS_OK : DHTS_E_INVALID;       // the lane does not fit: max_segment = 0 says so
+    const int S = macro_ckpt_segment(pl, segment);
+    if (S < 0) return DHTS_E_INVALID;
+    const size_t bwd_lds = macro_ckpt_bwd_lds_bytes(d->n_cells, S);
+    plan[2] = S;
+    plan[4] = macro_ckpt_count(T, S);
+    plan[6] = (int32_t)bwd_lds;
+    plan[7] = (int32_t)(kMacroCkptLdsBudget / bwd_lds);
+    return DHTS_OK;
+}
+size_t dhts_macro_ckpt_bytes(const dhts_macro_desc *d, int T, int segment) {
+    if (!macro_desc_ok(d) || T < 0) return 0;
+    const int S = macro_ckpt_segment(macro_ckpt_plan(d), segment);
+    if (S < 0) return 0;
+    return (size_t)macro_ckpt_count(T, S) * d->n_lanes * macro_ckpt_row_bytes(d->n_cells);
+}
+int dhts_macro_rollout_fwd_ckpt(const dhts_macro_desc *d, int T, int segment,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream) {
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || (T > 0 && !ckpt)) return DHTS_E_INVALID;
+    if ((det != nullptr) != (taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells))) return DHTS_E_INVALID;
+    const MacroCkptPlan pl = macro_ckpt_plan(d);
+    const int S = macro_ckpt_segment(pl, segment);
+    if (S < 0) return DHTS_E_INVALID;
+    if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
+    return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, ghost_is_sched, r_out, y_out, u_out, ueq_out, det, det ? n_det : 0, taps, ckpt,
+                                 err, stream);
+}
+int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
+    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !r || !y || !u || !ueq || !ghost || !g_r || !g_y || !g_r_out || !g_y_out ||
+        (ghost_is_sched && !g_ghost))
+        return DHTS_E_INVALID;
+    if ((det != nullptr) != (g_taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells))) return DHTS_E_INVALID;
+    const MacroCkptPlan pl = macro_ckpt_plan(d);
+    const int S = macro_ckpt_segment(pl, segment);
+    if (S < 0) return DHTS_E_INVALID;
+    if (T == 0) {        // no step: the cotangents come back as they went in, the boundary sums are zero, no row is addressed
+        const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
+        if (g_r_out != g_r && hipMemcpyAsync(g_r_out, g_r, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        if (g_y_out != g_y && hipMemcpyAsync(g_y_out, g_y, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        if (!ghost_is_sched && g_ghost &&
+            hipMemsetAsync(g_ghost, 0, sizeof(double) * 4 * (size_t)d->n_lanes, (hipStream_t)stream) != hipSuccess)
+            return DHTS_E_LAUNCH;
+        return DHTS_OK;
+    }
+    return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, det, det ? n_det : 0, g_taps, g_r_out, g_y_out,
+                                 g_ghost, err, stream);
 }
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,
                                  void *stream) {

@@ -266,20 +266,43 @@ def macro_tape_expand(desc, T, tape):
     return dqs
 
 
-def _ghost_ry_to_ru(g_ghost, gr, gu, gq, um):
-    """ghost (r, y) cotangents (sums over the steps, or per step) -> ghost (r, u) leaves, in double (the sum is ill-conditioned)."""
+def _ghost_ry_to_ru(g_ghost, gr, gu, gq, um, rows=None):
+    """ghost (r, y) cotangents (sums over the steps, or per step) -> ghost (r, u) leaves, in double (the sum is ill-conditioned).
+    rows (per step only): so many steps at a time into results allocated once -- the same bits, elementwise as it is, and the double
+    copies and temporaries are of that many rows instead of T (the checkpointed backward, whose point is what it allocates)."""
+    if rows is not None and g_ghost.dim() == 4 and g_ghost.shape[0] > rows:
+        g_gr, g_gu = torch.empty_like(gr), torch.empty_like(gu)
+        for t in range(0, g_ghost.shape[0], rows):
+            g_gr[t:t + rows], g_gu[t:t + rows] = _ghost_ry_to_ru(g_ghost[t:t + rows], gr[t:t + rows], gu[t:t + rows], gq[t:t + rows], um)
+        return g_gr, g_gu
     rr, uu, qq = gr.double(), gu.double(), gq.double()
     dueq = torch.where(rr < 0, torch.zeros_like(rr), -um * 0.5 / torch.sqrt(rr.clamp_min(0) + EPS))
     return (g_ghost[..., 0] + g_ghost[..., 1] * ((uu - qq) - rr * dueq)).float(), (g_ghost[..., 1] * rr).float()
 
 
-def _per_step_cotangent(steps, g_steps, um):
+def _per_step_cotangent(steps, g_steps, um, rows=None):
     """The cotangent of per-step states [T][L][3][X] (r, y, u; X = N: the history, X = D: detector readings) as the reverse sweep
-    takes it, [T][L][2][X]: (r, y) directly, u through the float32 glue of the saved (r, y) of that step."""
+    takes it, [T][L][2][X]: (r, y) directly, u through the float32 glue of the saved (r, y) of that step.
+    rows: so many steps at a time into a result allocated once (the same bits; the five contiguous planes the glue kernel works on are
+    of that many rows instead of T: the checkpointed backward)."""
+    if rows is not None and steps.shape[0] > rows:
+        gs = torch.empty(steps.shape[0], steps.shape[1], 2, steps.shape[3], dtype=torch.float32, device=steps.device)
+        for t in range(0, steps.shape[0], rows):
+            gs[t:t + rows] = _per_step_cotangent(steps[t:t + rows], g_steps[t:t + rows], um)
+        return gs
     sr, sy = steps[:, :, 0].contiguous(), steps[:, :, 1].contiguous()
     g_sr, g_sy = g_steps[:, :, 0].contiguous().clone(), g_steps[:, :, 1].contiguous().clone()
     macro_u_tap_bwd(sr, sy, g_steps[:, :, 2].contiguous(), g_sr, g_sy, um)
     return torch.stack([g_sr, g_sy], dim=2).contiguous()
+
+
+_GLUE_PASSES, _GLUE_ELEMS = 16, 8192
+
+
+def _glue_rows(T, row_elems):
+    """Steps per pass of the checkpointed backward's glue: at most _GLUE_PASSES passes (their launches stay a small part of a sweep's
+    time), and no pass below _GLUE_ELEMS elements (a short rollout takes one).  The glue's temporaries shrink to 1 / 16 of their size."""
+    return max(-(-int(T) // _GLUE_PASSES), -(-_GLUE_ELEMS // max(int(row_elems), 1)), 1)
 
 
 class MacroRollout(torch.autograd.Function):
@@ -292,10 +315,14 @@ class MacroRollout(torch.autograd.Function):
     What example/inverse/macro.py does with one dMacroLane in a RoadNetwork (macro.py:34-68,
     _inverse.py:91-99), for L lanes at once: state set by set_state_vector_u, ghosts by
     set_leftmost_cell / set_rightmost_cell, T x RoadNetwork.forward, state read by get_state_vector (at chosen cells: the readings).
+    checkpoint (the last argument; None / False: the taped path; True: the plan's segment length; a positive int: that one): keep (r, y)
+    every so many steps instead of the tape, and let the reverse sweep replay one segment at a time with its interface products in LDS
+    (macro_ckpt_plan) -- the same outputs and gradients bit for bit, and the only buffer that grows with T besides the readings is 8 B
+    per cell per segment.  Not with want_hist, and not for lanes the reverse kernel's LDS cannot hold (ValueError).
     """
 
     @staticmethod
-    def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, det=None):
+    def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, det=None, checkpoint=None):
         L, N = r0.shape
         sched = ghost_r.dim() == 3
         if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
@@ -304,12 +331,28 @@ class MacroRollout(torch.autograd.Function):
         if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
             raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
         desc = macro_desc(L, N, dt, dx, u_max)
+        segment = _macro_checkpoint_segment(checkpoint, desc, T, want_hist, 0 if det is None else int(det.numel()))
         r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
         gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
         y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
         gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
         ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4], or [T][L][2][4]
         need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
+        ctx.segment = segment if need_grad else None
+        if ctx.segment is not None:
+            # the checkpointed pair: the checkpoint buffer, the readings if asked for and the fault record; no tape.  The replay reads the
+            # forward's inputs again: (y0, q0, ghost) stay alive beside what the taped path saves
+            ctx.ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=r0.device)
+            ctx.replay = (y0, q0, ghost)
+            err = new_error_record(r0.device)
+            (rT, yT, uT, qT), steps = macro_rollout_fwd_ckpt(desc, T, r0c, y0, u0c, q0, ghost, ctx.ckpt, segment=segment, det=det, err=err)
+            if check_faults:
+                raise_on_fault(err)
+            ctx.sched = sched
+            ctx.desc, ctx.T, ctx.u_max, ctx.tape, ctx.check_faults = desc, T, u_max, None, check_faults
+            ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, steps, det)
+            ctx.mark_non_differentiable(qT)
+            return (rT, yT, uT, qT) if steps is None else (rT, yT, uT, qT, steps)
         tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
         err = new_error_record(r0.device)
         if det is not None:
@@ -339,10 +382,18 @@ class MacroRollout(torch.autograd.Function):
         if g_uT is not None:
             macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
         gs = None
+        ckpt = ctx.segment is not None       # (its glue goes over the T-sized cotangents a part at a time: _glue_rows)
         if steps is not None and g_steps is not None and g_steps.numel():      # (T = 0: no row, and an empty tensor has no address)
-            gs = _per_step_cotangent(steps, g_steps, um)                         # [T][L][2][N], with detectors [T][L][2][D]
+            # [T][L][2][N], with detectors [T][L][2][D]
+            gs = _per_step_cotangent(steps, g_steps, um, rows=_glue_rows(T, L * steps.shape[3]) if ckpt else None)
         err = new_error_record(dev)
-        if gs is not None and det is not None:
+        if ckpt:
+            y0, q0, ghost = ctx.replay
+            taps = gs is not None and det is not None            # (no readings to look at: the plain sweep)
+            g_r0, g_y0, g_ghost = macro_rollout_bwd_ckpt(desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, segment=ctx.segment,
+                                                         det=det if taps else None, g_taps=gs if taps else None, err=err)
+            del gs                           # (the sweep is enqueued on this stream: the allocator may hand the block to the glue below)
+        elif gs is not None and det is not None:
             g_r0, g_y0, g_ghost = macro_rollout_bwd_taps(desc, T, ctx.tape, g_r, g_y, det, gs, sched=ctx.sched, err=err)
         else:                            # (no readings to look at: the plain sweep over the same tape)
             bwd = macro_rollout_bwd_sched if ctx.sched else macro_rollout_bwd
@@ -350,13 +401,35 @@ class MacroRollout(torch.autograd.Function):
         if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
             raise_on_fault(err)
         g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
-        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um)
-        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None, None
+        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um, rows=_glue_rows(T, 2 * L) if ckpt else None)
+        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None, None, None
+
+
+def _macro_checkpoint_segment(checkpoint, desc, T, want_hist, n_det):
+    """dhts.macro_rollout's `checkpoint` -> None (the taped path) or the segment length; ValueError otherwise, before a device is touched."""
+    if checkpoint is None or checkpoint is False:
+        return None
+
+    def plan(segment):
+        if macro_ckpt_plan(desc, T, n_det, 0)["max_segment"] < 1:
+            raise ValueError("lanes of %d cells do not fit the checkpointed reverse sweep (its LDS holds up to %d cells): "
+                             "use the taped path, checkpoint=None" % (desc.n_cells, MACRO_CKPT_MAX_CELLS))
+        return macro_ckpt_plan(desc, T, n_det, segment)
+    segment = _checkpoint_segment(checkpoint, plan)
+    if want_hist:
+        raise ValueError("want_hist and checkpoint exclude each other: the history is of size T anyway (checkpoint=None keeps the tape)")
+    return segment
 
 
 def _detector_indices(detectors, N, device):
     """dhts.macro_rollout's `detectors` -> int32 CUDA [D].  A sequence of ints or a CPU integer tensor is validated (ValueError) before
     anything touches a device; a CUDA int32 tensor is used as it is."""
+    cells = _detector_cells(detectors, N)
+    return cells if isinstance(cells, torch.Tensor) else torch.tensor(cells, dtype=torch.int32, device=device)
+
+
+def _detector_cells(detectors, N):
+    """The checks of _detector_indices without the upload -> the CUDA tensor as it is, or the list of cells."""
     if isinstance(detectors, torch.Tensor) and detectors.is_cuda:
         if detectors.dtype != torch.int32 or detectors.dim() != 1 or not 1 <= detectors.numel() <= N:
             raise ValueError("a CUDA `detectors` must be a one-dimensional int32 tensor of 1..%d entries" % N)
@@ -374,11 +447,12 @@ def _detector_indices(detectors, N, device):
         raise ValueError("`detectors` is empty")
     if cells[0] < 0 or cells[-1] >= N or any(a >= b for a, b in zip(cells, cells[1:])) or any(not 0 <= c < N for c in cells):
         raise ValueError("`detectors` must be strictly ascending cell indices in [0, %d) (got %s)" % (N, cells))
-    return torch.tensor(cells, dtype=torch.int32, device=device)
+    return cells
 
 
-def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None):
+def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None, checkpoint=None):
     """T fused differentiable steps of L straight ARZ lanes (MacroRollout): returns (rT, yT, uT, qT), with want_hist also hist [T][L][3][N].
+    checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape; MacroRollout).
 
     detectors: cell indices at which the state is read after every step -- a sequence of ints or a CPU integer tensor (non-empty, strictly
     ascending, in [0, N): checked, ValueError otherwise, then uploaded), or a CUDA int32 tensor, which is used as it is so that a graph
@@ -390,8 +464,13 @@ def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, c
     if detectors is not None:
         if want_hist:
             raise ValueError("want_hist and detectors exclude each other: the history holds every cell")
-        det = _detector_indices(detectors, int(r0.shape[-1]), r0.device)
-    return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist, check_faults, det)
+        det = _detector_cells(detectors, int(r0.shape[-1]))
+    if checkpoint is not None and checkpoint is not False and r0.dim() == 2:      # (ValueError before the detectors are uploaded)
+        _macro_checkpoint_segment(checkpoint, macro_desc(int(r0.shape[0]), int(r0.shape[1]), float(dt), float(dx), float(u_max)), int(T),
+                                  want_hist, 0 if det is None else len(det))
+    if isinstance(det, list):
+        det = torch.tensor(det, dtype=torch.int32, device=r0.device)
+    return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist, check_faults, det, checkpoint)
 
 
 # ---- forward mode: Jacobian-vector products over the rollout tape ---------------------------------------------------------------------
@@ -542,6 +621,108 @@ def macro_fwd_jvp_plan(desc, T, n_dir, n_det=0):
     plan = (C.c_int32 * 8)()
     check(_lib.lib().dhts_macro_fwd_jvp_plan(C.byref(desc), int(T), int(n_dir), int(n_det), C.byref(plan)), "dhts_macro_fwd_jvp_plan")
     return dict(zip(_MACRO_FWD_JVP_PLAN_KEYS, list(plan)))
+
+
+# ---- reverse mode from checkpoints: the interface products of one segment at a time, in LDS -------------------------------------------
+MACRO_CKPT_MAX_CELLS = 1319      # the longest lane whose records, planes and one ring step fit 160 KB (csrc/macro_ckpt.inc; the plan is the truth)
+_MACRO_CKPT_PLAN_KEYS = ("waves", "passes", "segment", "max_segment", "checkpoints", "fwd_lds_bytes", "bwd_lds_bytes", "bwd_groups_per_cu")
+
+
+def macro_ckpt_plan(desc, T, n_det=0, segment=0):
+    """What dhts_macro_rollout_fwd_ckpt / _bwd_ckpt launch for this shape (include/dhts.h): the lane mapping's wavefronts and passes, the
+    segment length used (the plan's own for segment = 0), the longest one the reverse kernel's LDS holds, the number of checkpoints
+    ceil(T / segment), the dynamic LDS bytes of the two kernels and the reverse workgroups a CU holds by LDS.  A lane too long for the
+    reverse kernel reports max_segment = 0 (and segment = 0).  ValueError: a segment outside 0 .. max_segment.  Needs no device."""
+    plan = (C.c_int32 * 8)()
+    if not 0 <= int(segment) <= 0x7fffffff:
+        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
+    status = _lib.lib().dhts_macro_ckpt_plan(C.byref(desc), int(T), int(n_det), int(segment), C.byref(plan))
+    if status == _lib.E_INVALID and int(segment) and _lib.lib().dhts_macro_ckpt_plan(C.byref(desc), int(T), int(n_det), 0, C.byref(plan)) == 0:
+        # the plan's own segment is accepted, so the descriptor, T and n_det are good and it is the segment that is not
+        raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment (%d) for lanes of %d cells" % (plan[3], desc.n_cells))
+    check(status, "dhts_macro_ckpt_plan")
+    return dict(zip(_MACRO_CKPT_PLAN_KEYS, list(plan)))
+
+
+def macro_ckpt_numel(desc, T, segment=0):
+    """float32 elements of the checkpoint buffer (opaque: the float32 (r, y) of every cell every `segment` steps, include/dhts.h)."""
+    return _lib.lib().dhts_macro_ckpt_bytes(C.byref(desc), int(T), int(segment)) // 4
+
+
+def _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost):
+    """What both raw wrappers check of the arguments they share -> (sched, contiguous r, y, u, ueq, ghost)."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    if macro_ckpt_plan(desc, T, 0, segment)["max_segment"] < 1:
+        raise ValueError("lanes of %d cells do not fit the checkpointed reverse sweep: use the taped path (checkpoint=None)" % N)
+    if ckpt.dtype != torch.float32 or ckpt.numel() != macro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
+        raise ValueError("ckpt must be a contiguous float32 [macro_ckpt_numel(desc, T, segment)]")
+    for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
+        if tuple(t.shape) != (L, N):
+            raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
+    sched = ghost.dim() == 4
+    want = (T, L, 2, 4) if sched else (L, 2, 4)
+    if tuple(ghost.shape) != want:
+        raise ValueError("ghost must have shape (%d, 2, 4) or, a schedule, (%d, %d, 2, 4)" % (L, T, L))
+    r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, "ghost")))
+    if sched and T == 0:        # an empty tensor has no address; the entry point wants one and reads no row
+        ghost = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
+    return sched, r, y, u, ueq, ghost
+
+
+def macro_rollout_fwd_ckpt(desc, T, r, y, u, ueq, ghost, ckpt, segment=0, det=None, err=None, out=None, taps=None):
+    """macro_rollout_fwd / _sched / _taps that fills the checkpoint buffer `ckpt` (float32 [macro_ckpt_numel(desc, T, segment)]) instead
+    of a tape (dhts_macro_rollout_fwd_ckpt): the same state and readings, bit for bit.  ghost [L][2][4], or a schedule [T][L][2][4].
+    Returns ((r, y, u, ueq) after T steps, taps [T][L][3][D] or None)."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    if det is None and taps is not None:
+        raise ValueError("taps without det")
+    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost)
+    D = 0
+    if det is not None:
+        det = _det_i32(det, N)
+        D = det.numel()
+        if taps is None:
+            taps = torch.empty(max(T, 1), L, 3, D, dtype=torch.float32, device=r.device)[:T]
+        elif tuple(taps.shape) != (T, L, 3, D) or taps.dtype != torch.float32 or not taps.is_cuda or not taps.is_contiguous():
+            raise ValueError("taps must be a contiguous float32 CUDA tensor of shape (%d, %d, 3, %d)" % (T, L, D))
+    if out is None:
+        out = tuple(torch.empty_like(r) for _ in range(4))
+    check(_lib.lib().dhts_macro_rollout_fwd_ckpt(C.byref(desc), T, int(segment), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(det), D,
+                                                 None if det is None else C.c_void_p(taps.data_ptr() or det.data_ptr()),
+                                                 _ptr(ckpt) if ckpt.numel() else None, _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt")
+    return out, taps
+
+
+def macro_rollout_bwd_ckpt(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment=0, det=None, g_taps=None, err=None, out=None):
+    """Reverse sweep from the checkpoints of macro_rollout_fwd_ckpt -> (g_r0, g_y0, g_ghost): macro_rollout_bwd / _sched / _taps' bits.
+    r, y, u, ueq, ghost, segment: the forward's.  det with g_taps [T][L][2][D], or neither.  g_ghost: float64 [L][2][2] summed over the
+    steps, or beside a schedule per step [T][L][2][2]."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    if (det is None) != (g_taps is None):
+        raise ValueError("det and g_taps go together")
+    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost)
+    D = 0
+    if det is not None:
+        det = _det_i32(det, N)
+        D = det.numel()
+        if tuple(g_taps.shape) != (T, L, 2, D):
+            raise ValueError("g_taps must have shape (%d, %d, 2, %d)" % (T, L, D))
+        g_taps = _f32c(g_taps, "g_taps")
+    g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
+    if tuple(g_r.shape) != (L, N) or tuple(g_y.shape) != (L, N):
+        raise ValueError("g_r and g_y must have shape (%d, %d)" % (L, N))
+    if out is None:
+        out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    if sched:
+        g_ghost = torch.empty(max(T, 1), L, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
+    else:
+        g_ghost = torch.zeros(L, 2, 2, dtype=torch.float64, device=g_r.device)
+    check(_lib.lib().dhts_macro_rollout_bwd_ckpt(C.byref(desc), T, int(segment), _ptr(ckpt) if ckpt.numel() else None, _ptr(r), _ptr(y),
+                                                 _ptr(u), _ptr(ueq), _ptr(ghost), int(sched), _ptr(g_r), _ptr(g_y), _ptr(det), D,
+                                                 None if det is None else C.c_void_p(g_taps.data_ptr() or det.data_ptr()),
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err), _stream()), "dhts_macro_rollout_bwd_ckpt")
+    return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -847,19 +1028,20 @@ def micro_rollout_bwd_ckpt(desc, T, ckpt, params, head, g_p, g_v, count=None, se
     return out[0], out[1], g_head
 
 
-def _checkpoint_segment(checkpoint, desc, T, want_params):
-    """The `checkpoint` argument of micro_rollout -> None (the taped path) or the segment length to run with; ValueError otherwise."""
+def _checkpoint_segment(checkpoint, plan):
+    """The `checkpoint` argument of micro_rollout / macro_rollout -> None (the taped path) or the segment length to run with; ValueError
+    otherwise.  plan(segment) -> the family's checkpoint plan (micro_ckpt_plan, macro_ckpt_plan), which raises for a segment it cannot run."""
     if checkpoint is None or checkpoint is False:
         return None
     if checkpoint is True:
-        return micro_ckpt_plan(desc, T, want_params)["segment"]
+        return plan(0)["segment"]
     try:
         segment = operator.index(checkpoint)
     except TypeError:
         segment = 0
     if segment < 1:
         raise ValueError("checkpoint must be None, False, True or a positive int (the segment length), not %r" % (checkpoint,))
-    return micro_ckpt_plan(desc, T, want_params, segment)["segment"]
+    return plan(segment)["segment"]
 
 
 def micro_step_bwd(desc, tape, g_p, g_v, count=None):
@@ -893,7 +1075,7 @@ class MicroRollout(torch.autograd.Function):
         L, V = p0.shape
         desc = micro_desc(L, V, dt)
         want_params = params.requires_grad
-        segment = _checkpoint_segment(checkpoint, desc, T, want_params)       # (ValueError before anything touches a device)
+        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, T, want_params, sg))      # (ValueError before a device is touched)
         p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
         need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or want_params
         if segment is not None and need_grad:

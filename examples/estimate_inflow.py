@@ -7,7 +7,9 @@ record the density after every step.  From those readings alone the [T] upstream
 on the detector READINGS (dhts.macro_rollout with detectors=...: the state at those cells after every step, nothing of size
 [T][L][N]) and its gradient reaches every step's boundary cell through the per-step boundary cotangent of the fused rollout
 (ghost_r, ghost_u of shape [T][L][2]).  --readings history takes the readings out of the full state history (want_hist=True)
-instead: the same numbers, log line for log line, at the cost of the history.  Every trial solves n_lane independent problems at
+instead: the same numbers, log line for log line, at the cost of the history.  --checkpoint [S] keeps the state every S steps
+instead of the rollout tape and replays a segment at a time in the reverse sweep: again the same log, for horizons whose tape does not
+fit the device.  Every trial solves n_lane independent problems at
 once.  What a detector at cell c can see of the profile ends c cells' travel time before the end of the horizon: the tail of the
 profile stays at its first guess.
 
@@ -43,8 +45,14 @@ def main():
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--readings", choices=("detectors", "history"), default="detectors",
                     help="read the detectors through dhts.macro_rollout(detectors=...) or out of the full state history")
+    ap.add_argument("--checkpoint", nargs="?", type=int, const=0, default=None, metavar="S",
+                    help="reverse mode from checkpoints instead of the tape (dhts.macro_rollout(checkpoint=...)): the same log, and no "
+                         "buffer of the rollout grows with --n_timestep faster than 8 B per cell per S steps; without S the plan's segment")
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
+    if args.checkpoint is not None and args.readings == "history":
+        ap.error("--checkpoint goes with --readings detectors: the state history is of size n_timestep anyway")
+    checkpoint = None if args.checkpoint is None else (True if args.checkpoint == 0 else args.checkpoint)
 
     dev = th.device("cuda", 0)
     if args.seed is not None:
@@ -62,7 +70,7 @@ def main():
     def densities(gr, gu):
         """[T][L][detectors]: the density at the detectors after every step."""
         if args.readings == "detectors":
-            return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, detectors=det32)[4][:, :, 0].contiguous()
+            return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, detectors=det32, checkpoint=checkpoint)[4][:, :, 0].contiguous()
         return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, want_hist=True)[4][:, :, 0][:, :, det]
 
     def u_eq(r):

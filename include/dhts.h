@@ -336,6 +336,53 @@ int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
                                const int32_t *det, int n_det, float *taps, float *t_taps,
                                dhts_error *err, dhts_error *err_jvp, void *stream);
 int dhts_macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]);
+
+/*
+ * Reverse mode of the same rollout WITHOUT a tape in memory: what dhts_macro_rollout_fwd (or _fwd_sched, or _fwd_taps) followed by
+ * dhts_macro_rollout_bwd (or _bwd_sched, or _bwd_taps) returns, bit for bit, from checkpoints.  Replaces the same T calls of
+ * dMacroForwardLayer.forward / .backward (road/lane/_macro_lane.py:83-146, road/lane/dmacro_lane.py:96-132 and :277-309).
+ * The forward keeps the float32 (r, y) every cell enters a step with each S steps (S = the segment); the reverse sweep runs a
+ * segment again from its checkpoint with the forward's own step -- the same device functions on the same float32 operands, so the
+ * interface products (A_i, B_i) are the taped forward's bits --, keeps them in on-chip memory for the S steps and sweeps them newest
+ * first with the general reverse sweep's expressions, then moves to the checkpoint before.  Segment 0 is replayed from the call's
+ * own inputs.
+ *     ckpt    dhts_macro_ckpt_bytes = C x n_lanes x n_cells x 8 B, C = ceil(T / S) (0 for T = 0); opaque
+ *             (the compact tape: dhts_macro_tape_bytes, about 46 B per cell and step)
+ *   segment   0 = the plan's choice, else 1 .. the max_segment dhts_macro_ckpt_plan reports (the reverse kernel's LDS holds the
+ *             products of a segment); the forward, the reverse sweep and dhts_macro_ckpt_bytes must be given the same value
+ *   dhts_macro_rollout_fwd_ckpt   r, y, u, ueq, ghost, ghost_is_sched, r_out .. ueq_out, det, n_det, taps, err as
+ *                                 dhts_macro_rollout_fwd_taps (same bits, DHTS_FAULT_CFL likewise), det and taps both NULL: no readings;
+ *                                 ckpt is filled (NULL is accepted for T = 0).  There is no state history.
+ *   dhts_macro_rollout_bwd_ckpt   r, y, u, ueq, ghost, ghost_is_sched: the forward's inputs (segment 0 and the boundary cells are read
+ *                                 from them); g_r, g_y, det, n_det, g_taps, g_r_out, g_y_out, g_ghost, err as dhts_macro_rollout_bwd_taps
+ *                                 (g_ghost [lane][2][2], or per step [T][lane][2][2] with ghost_is_sched; DHTS_FAULT_NAN likewise), det
+ *                                 and g_taps both NULL: no per-step cotangents.  The replay reports no fault a second time.
+ *                                 PRECONDITION: the entries of det inside [0, n_cells) are distinct.  This sweep adds ONE column of
+ *                                 g_taps to a cell (the last that names it), dhts_macro_rollout_bwd_taps every one: with a repeated
+ *                                 entry the two differ.  (dhts.macro_rollout checks a list of detectors; a device tensor it does not.)
+ * Both kernels use the two-phase lane kernel's mapping (one workgroup per lane; DHTS_OPT_MACRO_FWD_WAVES, _VARIANT and _GROUP do not
+ * apply).  A lane whose records, cotangent planes and ONE step of products exceed 160 KB of LDS (1320 cells and above) does not fit and
+ * keeps the taped pair.  T = 0: the state resp. the cotangents come back as they went in (g_ghost [lane][2][2]: zeros), no row of
+ * anything is addressed.
+ * A bad descriptor, T < 0, a segment outside 0 .. max_segment, a lane that does not fit, a NULL r / y / u / ueq / ghost / r_out / y_out /
+ * u_out / ueq_out resp. g_r / g_y / g_r_out / g_y_out (ckpt with T > 0; g_ghost with ghost_is_sched), det without taps resp. g_taps or
+ * the reverse, n_det outside 1 .. n_cells with det: DHTS_E_INVALID, nothing is dereferenced (dhts_macro_ckpt_bytes: 0).
+ * dhts_macro_ckpt_plan (n_det: 0 = no readings, else 1 .. n_cells; a pure function of its arguments, no device is needed):
+ *   plan[0] wavefronts per lane     plan[1] 64-cell passes per wavefront     plan[2] the segment used (the plan's own for segment = 0)
+ *   plan[3] max_segment (0: the lane does not fit; then only segment = 0 is answered, with plan[2], [4], [6], [7] = 0)
+ *   plan[4] checkpoints C     plan[5] dynamic LDS bytes of the forward     plan[6] ... of the reverse kernel at that segment
+ *   plan[7] reverse workgroups a CU holds by LDS
+ */
+int dhts_macro_ckpt_plan(const dhts_macro_desc *d, int T, int n_det, int segment, int32_t plan[8]);
+size_t dhts_macro_ckpt_bytes(const dhts_macro_desc *d, int T, int segment);
+int dhts_macro_rollout_fwd_ckpt(const dhts_macro_desc *d, int T, int segment,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream);
 /* tangent of y = r (u - u_eq(r)): t_y = (dy/dr) t_r + (dy/du) t_u, the partials dhts_macro_state_from_ru_bwd applies, in float32 */
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u,
                                  float *t_y, void *stream);
