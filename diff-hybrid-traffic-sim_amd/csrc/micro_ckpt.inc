@@ -18,6 +18,12 @@
 // (The dynamic LDS array of the two kernels has a name of its own, lds_ck: block-scope extern declarations of one name are one entity, and
 // an aligned(16) redeclaration of `lds` after micro_rollout_bwd_kernel pads that kernel's static LDS word from 4 to 16 bytes.)
 
+// micro_kernels.hip includes this file twice: with DHTS_MICRO_SAMPLES 0 for the two kernels described above, then with 1 for their
+// sampled forms (kSamp), micro_rollout_ckpt_fwd_samples_kernel / _bwd_samples_kernel, which take MicroProbes and a samples array
+// [T / every][L][2][n] in place of hist / g_hist -- siblings from one text, and the first two compile to the code they were before
+// the siblings existed (profiles/micro_samples_resources*.txt).
+
+#if !DHTS_MICRO_SAMPLES
 // dynamic LDS of the two kernels: the plan (micro_plan) and the kernels' own carving read these
 __host__ __device__ inline size_t micro_ckpt_fwd_lds_bytes(int V) { return sizeof(float2) * 2 * (size_t)(V + 1); }
 // reverse, fixed part: the replay's state hand-over S[2][V + 1] and the four cotangent arrays of V + 2 floats
@@ -29,6 +35,7 @@ __host__ __device__ inline size_t micro_ckpt_bwd_step_bytes(int V, bool params) 
 __host__ __device__ inline size_t micro_ckpt_bwd_lds_bytes(int V, int S, bool params) {
     return micro_ckpt_bwd_fixed_bytes(V) + (size_t)S * micro_ckpt_bwd_step_bytes(V, params);
 }
+#endif
 
 // grid = L workgroups (one traffic lane each) of blockDim.x >= V threads (V rounded up to 64): micro_rollout_fwd_jvp_kernel's mapping
 // without tangents -- one vehicle per thread, its float32 (p, v) and derived parameters in registers for all T steps, the new state left
@@ -37,10 +44,27 @@ __host__ __device__ inline size_t micro_ckpt_bwd_lds_bytes(int V, int S, bool pa
 // Before step c Sg every slot of the lane (live or not) stores its (p, v) to row c of ckpt.
 // err: DHTS_FAULT_COLLISION where idm_step reported one, as the forward kernel reports it.  A block smaller than the lane:
 // DHTS_FAULT_CAPACITY (index -3), outputs NaN (the launch sizes the block from the same plan: it does not happen).
+// kSamp (micro_rollout_ckpt_fwd_samples_kernel): instead of hist, row j of samples [T / every][L][2][n] takes (p, v) of the probe
+// slots after step (j + 1) every - 1 -- a thread finds its slot's column among the probes once, before the step loop, counts the steps
+// down to the next sampled one and moves a running pointer from row to row; a slot at or beyond count stores nothing.  ckpt may then
+// be NULL: no checkpoint is kept (a forward that nobody differentiates).
+#if !DHTS_MICRO_SAMPLES
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
     int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, float *__restrict__ hist, dhts_error *err) {
+    constexpr bool kSamp = false;
+    const MicroProbes pr = {};
+    float *const samples = nullptr;
+#else
+__global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
+    int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
+    const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
+    float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, MicroProbes pr, float *__restrict__ samples,
+    dhts_error *err) {
+    constexpr bool kSamp = true;
+    float *const hist = nullptr;
+#endif
     extern __shared__ __attribute__((aligned(16))) float lds_ck[];
     const int lane = blockIdx.x;
     const int k = threadIdx.x;
@@ -60,11 +84,13 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
     if (V > B) {
         const float nanf_ = __builtin_nanf("");
         for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
+        if constexpr (kSamp) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_);
         if (k == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);
         return;
     }
 
     float p = p_in[base + kc], v = v_in[base + kc];      // (a slot at or beyond count keeps them: the outputs pass it through)
+    const int col = kSamp ? micro_probe_column(pr, k, V) : -1;
     IdmDerived prm = {};
     double half_len = 0.;
     if (vk) {
@@ -87,9 +113,14 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
         if (vk) S[k] = make_float2(p, v);
         __syncthreads();
         float2 *ck = ckpt + (size_t)lane * Vp + k;       // this slot of row 0; a row is L Vp entries
-        int next_ck = 0;
+        int next_ck = (kSamp && ckpt == nullptr) ? -1 : 0;
+        float *sp = nullptr;                             // kSamp: this slot's column of the next row; a row is L 2 n floats
+        int cd = 0;                                      // ... and the steps until that row is due
+        if constexpr (kSamp) { sp = samples + (size_t)lane * 2 * pr.n + (col < 0 ? 0 : col); cd = pr.every; }
         for (int step = 0; step < T; ++step) {
             const int q = step & 1;
+            bool due = false;
+            if constexpr (kSamp) { due = --cd == 0; cd = due ? pr.every : cd; }
             if (step == next_ck) {
                 if (k < V) *ck = make_float2(p, v);
                 ck += (size_t)L * Vp;
@@ -106,9 +137,11 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
                 if (o.collided && fault_step < 0) fault_step = step;
                 p = o.np; v = o.nv;
                 S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
-                if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
+                if constexpr (kSamp) { if (due && col >= 0) { sp[0] = p; sp[pr.n] = v; } }
+                else if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS-only: checkpoint and hist stores stay in flight
+            if constexpr (kSamp) { if (due) sp += (size_t)L * 2 * pr.n; }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS-only: checkpoint, hist and samples stores stay in flight
         }
     }
     if (k < V) { p_out[base + k] = p; v_out[base + k] = v; }
@@ -125,12 +158,29 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
 // the leader's X[r][k + 1] is another thread's, and the barrier that ends the replay's last step is what it waits for.  The replay
 // raises no collision: the forward did.  g_hist rows travel two steps ahead in registers, as in micro_rollout_bwd_kernel.
 // err: DHTS_FAULT_NAN at the latest step, lowest vehicle, where a non-finite cotangent appeared.
+// kSamp (micro_rollout_ckpt_bwd_samples_kernel): g_samples [T / every][L][2][n] takes g_hist's place -- only the thread of a live probe
+// slot adds, and only at a sampled step.  Its rows travel two ROWS ahead in the same four registers (2 every steps: with every = 1
+// the g_hist pipeline), across segment boundaries like the countdown to the next sampled step, which starts at T mod every: the
+// trailing steps have no row.
 template <bool kParams>
+#if !DHTS_MICRO_SAMPLES
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
     int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, const float *__restrict__ g_hist, float *__restrict__ g_p_out, float *__restrict__ g_v_out,
     double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err) {
+    constexpr bool kSamp = false;
+    const MicroProbes pr = {};
+    const float *const g_samples = nullptr;
+#else
+__global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
+    int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
+    const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
+    const float *__restrict__ g_v_in, MicroProbes pr, const float *__restrict__ g_samples, float *__restrict__ g_p_out,
+    float *__restrict__ g_v_out, double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err) {
+    constexpr bool kSamp = true;
+    const float *const g_hist = nullptr;
+#endif
     extern __shared__ __attribute__((aligned(16))) float lds_ck[];
     const int lane = blockIdx.x;
     const int k = threadIdx.x;
@@ -196,6 +246,24 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
             const float *a = gh0 + (size_t)(T - 1) * h_stride, *b = gh0 + (size_t)(T > 1 ? T - 2 : 0) * h_stride;
             hp1 = a[0]; hv1 = a[V]; hp2 = b[0]; hv2 = b[V];
         }
+        // kSamp: does this thread add at a sampled step; its column of the row to load next (rows_left of them are still unloaded);
+        // steps to sweep before the next sampled one
+        bool probe = false;
+        const float *gs = nullptr;
+        int rows_left = 0, cd = 0;
+        const size_t s_row = kSamp ? (size_t)L * 2 * pr.n : 0;
+        if constexpr (kSamp) {
+            const int col = micro_probe_column(pr, k, V);
+            const int rows = T / pr.every;
+            probe = vk && col >= 0;
+            cd = T - rows * pr.every;
+            if (probe && rows > 0) {
+                gs = g_samples + (size_t)(rows - 1) * s_row + (size_t)lane * 2 * pr.n + col;
+                hp1 = gs[0]; hv1 = gs[pr.n];
+                rows_left = rows - 1;
+                if (rows_left > 0) { gs -= s_row; hp2 = gs[0]; hv2 = gs[pr.n]; --rows_left; }
+            }
+        }
         for (int c = C - 1; c >= 0; --c) {
             const int s0 = c * Sg, s1 = (T - s0 < Sg) ? T : s0 + Sg;
             float p = ck.x, v = ck.y;
@@ -225,8 +293,18 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
             for (int step = s1 - 1; step >= s0; --step) {
                 const int r = step - s0;
                 const float chp = hp1, chv = hv1;
-                hp1 = hp2; hv1 = hv2;
-                if (gh0) { const float *a = gh0 + (size_t)(step > 1 ? step - 2 : 0) * h_stride; hp2 = a[0]; hv2 = a[V]; }
+                bool due = false;
+                if constexpr (kSamp) {
+                    due = cd == 0;
+                    cd = due ? pr.every - 1 : cd - 1;
+                    if (due) {
+                        hp1 = hp2; hv1 = hv2;
+                        if (rows_left > 0) { gs -= s_row; hp2 = gs[0]; hv2 = gs[pr.n]; --rows_left; }      // (rows_left > 0 on a probe's thread only)
+                    }
+                } else {
+                    hp1 = hp2; hv1 = hv2;
+                    if (gh0) { const float *a = gh0 + (size_t)(step > 1 ? step - 2 : 0) * h_stride; hp2 = a[0]; hv2 = a[V]; }
+                }
                 MicroTape3 e = {0.f, 0.f, 0.f};
                 float2 cx = make_float2(0.f, 0.f);
                 float gv_step = 0.f;
@@ -234,7 +312,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
                     const float *er = R + (size_t)r * 3 * V + k;
                     e.e2 = er[0]; e.e3 = er[V]; e.l3 = er[2 * V];
                     float gp = Gp[k], gv = Gv[k];
-                    if (gh0) { gp += chp; gv += chv; }
+                    if constexpr (kSamp) { if (due && probe) { gp += chp; gv += chv; } }
+                    else if (gh0) { gp += chp; gv += chv; }
                     Gp[k] = dot2(1.f, gp, e.e2, gv);           // grad_ps[:-1] = dqs[:, 0]^T g
                     Gv[k] = dot2(dtf, gp, e.e3, gv);
                     C1p[k + 1] = dot2(0.f, gp, -e.e2, gv);     // grad_ps[1:] += dqs[:, 1]^T g

@@ -19,9 +19,15 @@
 //   t_p_in, t_v_in, t_p_out, t_v_out   [kK][L][V] float32      t_head [kK][L][2] double or NULL      t_params [kK][6][L][V] double
 //   hist [T][L][2][V] float32 or NULL (live slots only, as the forward)      t_hist [kK][T][L][2][V] float32 or NULL
 
+// micro_kernels.hip includes this file twice: with DHTS_MICRO_SAMPLES 0 for the kernel described above, then with 1 for its sampled
+// form (kSamp), micro_rollout_fwd_jvp_samples_kernel -- siblings from one text, and the first compiles to the code it was before the
+// sibling existed (profiles/micro_samples_resources*.txt).
+
+#if !DHTS_MICRO_SAMPLES
 __host__ __device__ inline size_t micro_fwd_jvp_lds_bytes(int V, int kK) {
     return sizeof(float2) * (size_t)(2 + 2 * kK) * (size_t)(V + 1) + 2 * sizeof(double) * (size_t)kK;
 }
+#endif
 
 // grid = L workgroups (one traffic lane each) of blockDim.x >= V threads (V rounded up to 64): one vehicle per thread, its float32
 // (p, v), its kK tangent pairs and its derived parameters in registers for all T steps.  After a step a thread leaves its new (p, v) in
@@ -33,13 +39,31 @@ __host__ __device__ inline size_t micro_fwd_jvp_lds_bytes(int V, int kK) {
 // err: DHTS_FAULT_COLLISION where idm_step reported one (what the forward kernel reports).  err_jvp: DHTS_FAULT_NAN with the EARLIEST
 // (step, vehicle) of the workgroup (what the tangent kernel reports, by the same LDS minimum).  A block smaller than the lane:
 // DHTS_FAULT_CAPACITY (index -3) on both records, every output NaN.
+// kSamp (micro_rollout_fwd_jvp_samples_kernel): instead of hist / t_hist, row j of samples [T / every][L][2][n] and of each direction of
+// t_samples [kK][T / every][L][2][n] takes the probe slots' (p, v) and tangents after step (j + 1) every - 1 -- a thread finds its
+// slot's column among the probes once, before the step loop, counts the steps down to the next sampled one and moves running pointers
+// from row to row.  samples: live slots only, or NULL (every launch of a call but the first); t_samples: slots at or beyond count 0.
 template <int kK, bool kParams>
+#if !DHTS_MICRO_SAMPLES
 __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
     int L, int V, int T, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ t_p_in,
     const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
     float *__restrict__ hist, float *__restrict__ t_hist, dhts_error *err, dhts_error *err_jvp) {
+    constexpr bool kSamp = false;
+    const MicroProbes pr = {};
+    float *const samples = nullptr, *const t_samples = nullptr;
+#else
+__global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
+    int L, int V, int T, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
+    const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ t_p_in,
+    const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
+    float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
+    MicroProbes pr, float *__restrict__ samples, float *__restrict__ t_samples, dhts_error *err, dhts_error *err_jvp) {
+    constexpr bool kSamp = true;
+    float *const hist = nullptr, *const t_hist = nullptr;
+#endif
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = blockIdx.x;
     const int k = threadIdx.x;
@@ -70,6 +94,11 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
             if (t_hist)
                 for (int s = 0; s < T; ++s)
                     for (int i = k; i < 2 * V; i += B) t_hist[d * h_dir + ((size_t)s * L + lane) * 2 * V + i] = nanf_;
+        }
+        if constexpr (kSamp) {
+            if (samples) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_);
+            for (int d = 0; d < n_act; ++d)
+                micro_samples_fill(t_samples + (size_t)d * (T / pr.every) * L * 2 * pr.n, pr, T, L, lane, k, B, nanf_);
         }
         if (k == 0) { raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3); raise_fault(err_jvp, DHTS_FAULT_CAPACITY, 0, lane, -3); }
         return;
@@ -133,8 +162,20 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
             }
         }
         __syncthreads();
+        // kSamp: this slot's column among the probes, its place `so` in the next row of samples and of direction 0 of t_samples (a row
+        // is L 2 n floats, a direction s_dir), and the steps until that row is due
+        int col = -1, cd = 0;
+        size_t so = 0, s_dir = 0;
+        if constexpr (kSamp) {
+            col = micro_probe_column(pr, k, V);
+            cd = pr.every;
+            s_dir = (size_t)(T / pr.every) * L * 2 * pr.n;
+            so = (size_t)lane * 2 * pr.n + (col < 0 ? 0 : col);
+        }
         for (int step = 0; step < T; ++step) {
             const int q = step & 1;
+            bool due = false;
+            if constexpr (kSamp) { due = --cd == 0; cd = due ? pr.every : cd; }
             if (vk) {
                 const float2 ls = S[q * P + k + 1];      // the leader's state before this step
                 const double pd = p, vd = v;
@@ -182,15 +223,26 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
                 if (bad_step < 0 && !fin) bad_step = step;
                 p = o.np; v = o.nv;
                 S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
-                if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
+                if constexpr (kSamp) { if (due && col >= 0 && samples) { samples[so] = p; samples[so + pr.n] = v; } }
+                else if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
             }
-            if (t_hist && k < V) {                       // slots at or beyond count: 0 (their tangents never left it)
+            if constexpr (kSamp) {
+                if (due) {
+                    if (col >= 0) {                      // (col >= 0 is a slot below V) slots at or beyond count: 0, as in t_hist
+                        float *hp = t_samples + so;
+#pragma unroll
+                        for (int d = 0; d < kK; ++d)
+                            if (d < n_act) { hp[d * s_dir] = tp[d]; hp[d * s_dir + pr.n] = tv[d]; }
+                    }
+                    so += (size_t)L * 2 * pr.n;
+                }
+            } else if (t_hist && k < V) {                // slots at or beyond count: 0 (their tangents never left it)
                 float *hp = t_hist + ((size_t)step * L + lane) * 2 * V + k;
 #pragma unroll
                 for (int d = 0; d < kK; ++d)
                     if (d < n_act) { hp[d * h_dir] = tp[d]; hp[d * h_dir + V] = tv[d]; }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS-only: hist and t_hist stores stay in flight
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS-only: hist / t_hist / samples stores stay in flight
         }
     }
     if (k < V) {

@@ -14,6 +14,8 @@
 // Fused (micro_rollout_fwd_jvp_kernel, micro_fwd_jvp.inc): the forward and K tangent directions stepped together, no tape at all.
 // Checkpointed (micro_rollout_ckpt_fwd_kernel / _bwd_kernel, micro_ckpt.inc): reverse mode with the state kept every S steps and the tape
 //   of one segment at a time rebuilt in LDS.
+// Sampled (micro_rollout_ckpt_fwd_samples_kernel / _bwd_samples_kernel, micro_rollout_fwd_jvp_samples_kernel): the two tape-free paths
+//   writing and reading probe samples [T / every][L][2][P] in place of a [T][L][2][V] history -- the same two files, included again.
 //
 // Reference: road/lane/_micro_lane.py:131-214, road/lane/dmicro_lane.py:87-127 and :271-298.
 #include <hip/hip_runtime.h>
@@ -494,10 +496,40 @@ __global__ void micro_step_tensor_fwd_kernel(int L, int V, double dt, const floa
 
 // ---- forward-mode tangent sweep over the rollout tape (dhts_micro_rollout_jvp) ----------------------------------
 #include "micro_jvp.inc"
+// ---- probe samples of the two tape-free paths (dhts_micro_rollout_*_samples) --------------------------------------
+// Which slots are observed and how often: row j of a samples array [T / every][L][2][n] holds (p, v) -- or their tangents, or their
+// cotangents -- of slot probes[i] in column i after step (j + 1) every - 1; the trailing T mod every steps have no row.
+struct MicroProbes {
+    const int32_t *probes;   // [n] distinct slots, or NULL: every slot, column i = slot i (n = V)
+    int n;                   // columns of a row
+    int every;               // >= 1
+};
+// The column slot k has among the probes, -1 for none: read once by the thread that owns the slot, before its step loop.  An entry
+// outside [0, V) equals no slot, so no address is ever formed from one and its column stays as the caller left it.
+__device__ inline int micro_probe_column(const MicroProbes &pr, int k, int V) {
+    if (k >= V) return -1;
+    if (pr.probes == nullptr) return k;
+    int col = -1;
+    for (int i = 0; i < pr.n; ++i) col = pr.probes[i] == k ? i : col;
+    return col;
+}
+// a block smaller than the lane (DHTS_FAULT_CAPACITY): the lane's part of every row of one samples array takes `value`
+__device__ inline void micro_samples_fill(float *samples, const MicroProbes &pr, int T, int L, int lane, int k, int B, float value) {
+    const int rows = T / pr.every;
+    for (int j = 0; j < rows; ++j)
+        for (int i = k; i < 2 * pr.n; i += B) samples[((size_t)j * L + lane) * 2 * pr.n + i] = value;
+}
 // ---- the rollout and its tangents in one kernel, no tape (dhts_micro_rollout_fwd_jvp) ----------------------------
+#define DHTS_MICRO_SAMPLES 0
 #include "micro_fwd_jvp.inc"
 // ---- reverse mode from checkpoints, the segment tape in LDS (dhts_micro_rollout_fwd_ckpt / _bwd_ckpt) -------------
 #include "micro_ckpt.inc"
+// ---- the sampled forms of the three kernels of the two files (dhts_micro_rollout_*_samples): the same text again ----
+#undef DHTS_MICRO_SAMPLES
+#define DHTS_MICRO_SAMPLES 1
+#include "micro_fwd_jvp.inc"
+#include "micro_ckpt.inc"
+#undef DHTS_MICRO_SAMPLES
 
 }  // namespace dhts
 
@@ -705,6 +737,67 @@ static int micro_ckpt_bwd_launch(const dhts_micro_desc *d, int T, int segment, c
     });
     return ok ? launch_status() : DHTS_E_LAUNCH;
 }
+// ---- the sampled forms of the three launches above: same plan, same LDS, samples in place of hist / g_hist / t_hist ----
+// the checks the three entry points share -> the kernels' MicroProbes (n = V without a list); false: DHTS_E_INVALID
+static bool micro_probes_ok(const dhts_micro_desc *d, const int32_t *probes, int n_probes, int every, MicroProbes *pr) {
+    if (every < 1 || (probes && (n_probes < 1 || n_probes > d->capacity))) return false;
+    *pr = MicroProbes{probes, probes ? n_probes : d->capacity, every};
+    return true;
+}
+static int micro_fwd_jvp_samples_launch(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                        const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                                        const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                        const MicroProbes &pr, float *samples, float *t_samples, dhts_error *err, dhts_error *err_jvp,
+                                        void *stream) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int L = d->n_lanes, V = d->capacity, kmax = pl.fwd_jvp_kmax[t_params ? 1 : 0];
+    const size_t dir_state = (size_t)L * V, dir_samples = (size_t)(T / pr.every) * L * 2 * pr.n;
+    bool lds_ok = true;
+    for (int k0 = 0; k0 < n_dir && lds_ok;) {
+        const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+        const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
+        float *o_s = t_samples ? t_samples + k0 * dir_samples : nullptr;
+        pick<4, 2, 1>(kk, [&](auto kv) {
+            constexpr int kK = decltype(kv)::value;
+            pick<0, 1>(t_params != nullptr, [&](auto pv) {
+                constexpr bool kParams = decltype(pv)::value != 0;
+                lds_ok = launch_lds(micro_rollout_fwd_jvp_samples_kernel<kK, kParams>, L, pl.fwd_jvp_block, micro_fwd_jvp_lds_bytes(V, kK),
+                                    kLdsDefault, stream, L, V, T, d->dt, p, v, count, params, head, t_p + k0 * dir_state, t_v + k0 * dir_state,
+                                    a_h, a_q, n_act, p_out, v_out, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, pr,
+                                    k0 == 0 ? samples : nullptr, o_s, k0 == 0 ? err : nullptr, err_jvp);
+            });
+        });
+        k0 += n_act;
+    }
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+static int micro_ckpt_fwd_samples_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                         const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
+                                         const MicroProbes &pr, float *samples, dhts_error *err, void *stream) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int S = micro_ckpt_segment(pl, segment, false);
+    if (S < 0) return DHTS_E_INVALID;
+    const bool ok = launch_lds(micro_rollout_ckpt_fwd_samples_kernel, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity),
+                               kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out,
+                               (float2 *)ckpt, pr, samples, err);
+    return ok ? launch_status() : DHTS_E_LAUNCH;
+}
+static int micro_ckpt_bwd_samples_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                         const double *params, const double *head, const float *g_p, const float *g_v, const MicroProbes &pr,
+                                         const float *g_samples, float *g_p_out, float *g_v_out, double *g_head, double *g_params,
+                                         dhts_error *err, void *stream) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int S = micro_ckpt_segment(pl, segment, g_params != nullptr);
+    if (S < 0) return DHTS_E_INVALID;
+    bool ok = true;
+    pick<0, 1>(g_params != nullptr, [&](auto pv) {
+        constexpr bool kParams = decltype(pv)::value != 0;
+        ok = launch_lds(micro_rollout_ckpt_bwd_samples_kernel<kParams>, d->n_lanes, pl.ckpt_block,
+                        micro_ckpt_bwd_lds_bytes(d->capacity, S, kParams), kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt,
+                        (const float2 *)ckpt, count, params, head, g_p, g_v, pr, g_samples, g_p_out, g_v_out, g_head, g_params, err);
+    });
+    return ok ? launch_status() : DHTS_E_LAUNCH;
+}
 template <bool kHeadOnly>
 static int micro_step_tensor_launch(const dhts_micro_desc *d, const float *p, const float *v, const int32_t *count, const double *params,
                                     const double *head, float *p_out, float *v_out, float *tape, dhts_error *err, void *stream) {
@@ -859,6 +952,39 @@ int dhts_micro_rollout_bwd_ckpt(const dhts_micro_desc *d, int T, int segment, co
                                 float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream) {
     if (!micro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !params || !head || !g_p || !g_v || !g_p_out || !g_v_out) return DHTS_E_INVALID;
     return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, g_params, err, stream);
+}
+// ---- probe samples on the two tape-free paths --------------------------------------------------------------------------------------
+int dhts_micro_rollout_fwd_ckpt_samples(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                        const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
+                                        const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err, void *stream) {
+    MicroProbes pr;
+    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || !head || !p_out || !v_out || !micro_probes_ok(d, probes, n_probes, every, &pr) ||
+        (T / every > 0 && !samples))
+        return DHTS_E_INVALID;
+    return micro_ckpt_fwd_samples_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt, pr, samples, err, stream);
+}
+int dhts_micro_rollout_bwd_ckpt_samples(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                        const double *params, const double *head, const float *g_p, const float *g_v, const int32_t *probes,
+                                        int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out, double *g_head,
+                                        double *g_params, dhts_error *err, void *stream) {
+    MicroProbes pr;
+    if (!micro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !params || !head || !g_p || !g_v || !g_p_out || !g_v_out ||
+        !micro_probes_ok(d, probes, n_probes, every, &pr) || (T / every > 0 && !g_samples))
+        return DHTS_E_INVALID;
+    return micro_ckpt_bwd_samples_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, pr, g_samples, g_p_out, g_v_out, g_head, g_params,
+                                         err, stream);
+}
+int dhts_micro_rollout_fwd_jvp_samples(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                       const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                                       const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                       const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
+                                       dhts_error *err_jvp, void *stream) {
+    MicroProbes pr;
+    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !p || !v || !params || !head || !t_p || !t_v || !p_out || !v_out || !t_p_out || !t_v_out ||
+        !micro_probes_ok(d, probes, n_probes, every, &pr) || (T / every > 0 && (!samples || !t_samples)))
+        return DHTS_E_INVALID;
+    return micro_fwd_jvp_samples_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out, pr,
+                                        samples, t_samples, err, err_jvp, stream);
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)
 int dhts_micro_step_fwd(const dhts_micro_desc *d,

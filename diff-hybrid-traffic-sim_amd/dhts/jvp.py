@@ -141,7 +141,7 @@ def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head):
 
 
 def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_params=None, t_head=None, count=None, want_hist=False,
-                      check_faults=True, fused=False):
+                      check_faults=True, fused=False, probes=None, every=1):
     """dhts.micro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((pT, vT[, hist]), (t_pT, t_vT[, t_hist])).  The primal outputs are those of dhts.micro_rollout(p0, v0, params, head, T, dt,
@@ -152,10 +152,21 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
     when t_params is given.  fused=True: the rollout and its tangents are stepped together by one kernel (dhts_micro_rollout_fwd_jvp)
     and neither the tape nor the parameter tape is allocated -- same return values, bit for bit, and the same two fault checks in the
     same order (the forward's, then the tangent sweep's).  Nothing returned here is differentiable (no autograd graph is recorded; the
-    inputs are read as constants): for gradients use dhts.micro_rollout."""
+    inputs are read as constants): for gradients use dhts.micro_rollout.
+
+    probes / every: as dhts.micro_rollout's (the same rules and ValueErrors; not together with want_hist).  With sampling on the call
+    returns ((pT, vT, samples), (t_pT, t_vT, t_samples)): samples [T // every][L][2][P] and t_samples [K][T // every][L][2][P], row j
+    = slot probes[i] after step (j + 1) every - 1, slots at or beyond count exactly 0 in both.  fused=True writes them from the kernel
+    (dhts_micro_rollout_fwd_jvp_samples) and nothing of size T x V is allocated; with fused=False, the taped path, the samples are cut
+    out of a dense history: ask for fused=True when memory matters."""
     T = int(T)
     K = _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head)
     L, V = p0.shape
+    sampling = ops.micro_sampling(probes, every, V, want_hist)
+    if sampling is not None and not fused:       # the taped path: both histories, cut
+        (pT, vT, hist), (t_pT, t_vT, t_hist) = micro_rollout_jvp(p0, v0, params, head, T, dt, t_p0=t_p0, t_v0=t_v0, t_params=t_params,
+                                                                 t_head=t_head, count=count, want_hist=True, check_faults=check_faults)
+        return (pT, vT, ops.cut_samples(hist, *sampling, count)), (t_pT, t_vT, ops.cut_samples(t_hist, *sampling, count))
     if tuple(v0.shape) != (L, V) or tuple(params.shape) != (6, L, V) or tuple(head.shape) != (L, 2):
         raise ValueError("v0 must have the shape of p0, params shape (6, %d, %d), head shape (%d, 2)" % (L, V, L))
     if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
@@ -178,6 +189,16 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
         tq = None if t_params is None else tan(t_params, (K, 6, L, V), torch.float64)
         if fused:                            # one kernel, no tape
             err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
+            if sampling is not None:         # the sampled kernel form: no history of either kind
+                slots = sampling[0]
+                if isinstance(slots, list):
+                    slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+                prim, tang = ops.micro_rollout_fwd_jvp_samples(desc, T, p0c, v0c, par, head.detach(), tp, tv, slots, sampling[1], count=count,
+                                                               t_head=th, t_params=tq, err=err, err_jvp=err_jvp)
+                if check_faults:
+                    ops.raise_on_fault(err)
+                    ops.raise_on_fault(err_jvp)
+                return prim, tang
             (pT, vT, hist), (t_pT, t_vT, t_hist) = ops.micro_rollout_fwd_jvp(desc, T, p0c, v0c, par, head.detach(), tp, tv, count=count,
                                                                              t_head=th, t_params=tq, want_hist=want_hist, err=err,
                                                                              err_jvp=err_jvp)

@@ -1028,6 +1028,194 @@ def micro_rollout_bwd_ckpt(desc, T, ckpt, params, head, g_p, g_v, count=None, se
     return out[0], out[1], g_head
 
 
+# ---- probe samples on the two tape-free paths (dhts_micro_rollout_*_samples) ------------------------------------------------------------
+def _samples_shape(desc, T, probes, every):
+    """The raw wrappers' checks of (probes, every) -> (rows, columns, n_probes for the C call).  probes: None (every slot) or a CUDA int32
+    tensor of distinct slots, used as it is (include/dhts.h: an entry outside [0, V) is skipped by the kernels)."""
+    V = desc.capacity
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError("every must be an int >= 1, not %r" % (every,))
+    if int(T) < 0:
+        raise ValueError("T must be >= 0")
+    if probes is None:
+        return int(T) // every, V, 0
+    if (not isinstance(probes, torch.Tensor) or not probes.is_cuda or probes.dtype != torch.int32 or probes.dim() != 1
+            or not 1 <= probes.numel() <= V or not probes.is_contiguous()):
+        raise ValueError("probes must be None or a contiguous one-dimensional CUDA int32 tensor of 1..%d slots" % V)
+    return int(T) // every, int(probes.numel()), int(probes.numel())
+
+
+def _samples_buffer(name, t, shape, device):
+    """A samples array handed in (checked) or a new zero-filled one: the kernels write live probe slots only."""
+    if t is None:
+        return torch.zeros(shape, dtype=torch.float32, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(shape)))
+    return t
+
+
+def micro_rollout_fwd_ckpt_samples(desc, T, p, v, params, head, ckpt, probes, every, count=None, segment=0, samples=None, err=None, out=None):
+    """micro_rollout_fwd_ckpt that writes, instead of a history, samples [T // every][L][2][P] (dhts_micro_rollout_fwd_ckpt_samples,
+    include/dhts.h): row j = (p, v) of slot probes[i] after step (j + 1) every - 1.  probes: a CUDA int32 tensor of distinct slots (not
+    validated: an entry outside [0, V) leaves its column as it is) or None = every slot.  samples: allocated zero-filled unless handed
+    in (live probe slots only are written).  ckpt=None: no checkpoint is kept.  Returns (pT, vT, samples)."""
+    L, V = desc.n_lanes, desc.capacity
+    rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    micro_ckpt_plan(desc, T, False, segment)
+    if ckpt is not None and (ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous()):
+        raise ValueError("ckpt must be None or a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
+    p, v = _f32c(p, "p"), _f32c(v, "v")
+    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
+        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
+    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
+        raise ValueError("params must be float64 [6][L][V]")
+    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
+        raise ValueError("head must be float64 [L][2]")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    params, head = params.contiguous(), head.contiguous()
+    samples = _samples_buffer("samples", samples, (rows, L, 2, n), p.device)
+    if out is None:
+        out = (torch.empty_like(p), torch.empty_like(v))
+    check(_lib.lib().dhts_micro_rollout_fwd_ckpt_samples(C.byref(desc), int(T), int(segment), _ptr(p), _ptr(v), _ptr(count), _ptr(params),
+                                                         _ptr(head), _ptr(out[0]), _ptr(out[1]),
+                                                         _ptr(ckpt) if ckpt is not None and ckpt.numel() else None, _ptr(probes), n_probes,
+                                                         every, _ptr(samples) if samples.numel() else None, _ptr(err), _stream()),
+          "dhts_micro_rollout_fwd_ckpt_samples")
+    return out[0], out[1], samples
+
+
+def micro_rollout_bwd_ckpt_samples(desc, T, ckpt, params, head, g_p, g_v, probes, every, g_samples, count=None, segment=0, err=None,
+                                   out=None, g_head=None, g_params=None):
+    """micro_rollout_bwd_ckpt with the cotangent g_samples [T // every][L][2][P] of micro_rollout_fwd_ckpt_samples' samples in place of
+    g_hist (dhts_micro_rollout_bwd_ckpt_samples): it enters the sweep at the sampled steps, at live probe slots.  probes, every,
+    count, segment: the forward's.  Returns (g_p0, g_v0, g_head)."""
+    L, V = desc.n_lanes, desc.capacity
+    rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    micro_ckpt_plan(desc, T, g_params is not None, segment)
+    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
+        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
+    for name, t in (("params", params), ("g_params", g_params)):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
+    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2) or not head.is_contiguous():
+        raise ValueError("head must be a contiguous float64 [L][2]")
+    if g_samples is None:
+        raise ValueError("g_samples is required: float32 [T // every][L][2][P]")
+    g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
+    g_samples = _samples_buffer("g_samples", g_samples, (rows, L, 2, n), g_p.device)
+    if out is None:
+        out = (torch.empty_like(g_p), torch.empty_like(g_v))
+    if g_head is None:
+        g_head = torch.zeros(L, 2, dtype=torch.float64, device=g_p.device)
+    check(_lib.lib().dhts_micro_rollout_bwd_ckpt_samples(C.byref(desc), int(T), int(segment), _ptr(ckpt) if ckpt.numel() else None,
+                                                         _ptr(count), _ptr(params), _ptr(head), _ptr(g_p), _ptr(g_v), _ptr(probes), n_probes,
+                                                         every, _ptr(g_samples) if g_samples.numel() else None, _ptr(out[0]), _ptr(out[1]),
+                                                         _ptr(g_head), _ptr(g_params), _ptr(err), _stream()),
+          "dhts_micro_rollout_bwd_ckpt_samples")
+    return out[0], out[1], g_head
+
+
+def micro_rollout_fwd_jvp_samples(desc, T, p, v, params, head, t_p, t_v, probes, every, count=None, t_head=None, t_params=None, err=None,
+                                  err_jvp=None, out=None):
+    """micro_rollout_fwd_jvp that writes, instead of the histories, samples [T // every][L][2][P] and t_samples [K][T // every][L][2][P]
+    (dhts_micro_rollout_fwd_jvp_samples): probes, every as micro_rollout_fwd_ckpt_samples.  out: (p_out, v_out, t_p_out, t_v_out[,
+    samples, t_samples]); the sample arrays are allocated zero-filled unless handed in (samples: live probe slots only are written;
+    t_samples: every probe slot, 0 at or beyond count).  Returns ((pT, vT, samples), (t_pT, t_vT, t_samples))."""
+    L, V, T = desc.n_lanes, desc.capacity, int(T)
+    rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    p, v = _f32c(p, "p"), _f32c(v, "v")
+    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
+        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
+    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
+        raise ValueError("params must be float64 [6][L][V]")
+    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
+        raise ValueError("head must be float64 [L][2]")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
+        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
+    K = int(t_p.shape[0])
+    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
+    if t_head is not None and (t_head.dtype != torch.float64 or tuple(t_head.shape) != (K, L, 2) or not t_head.is_contiguous()):
+        raise ValueError("t_head must be a contiguous float64 [%d][%d][2]" % (K, L))
+    if t_params is not None and (t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous()):
+        raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
+    params, head = params.contiguous(), head.contiguous()
+    out = tuple(out) if out is not None else ()
+    if len(out) not in (0, 4, 6):
+        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, samples, t_samples])")
+    samples = _samples_buffer("samples", out[4] if len(out) == 6 else None, (rows, L, 2, n), p.device)
+    t_samples = _samples_buffer("t_samples", out[5] if len(out) == 6 else None, (K, rows, L, 2, n), p.device)
+    if out:
+        state = out[:4]
+        for name, t, like in zip(("p_out", "v_out", "t_p_out", "t_v_out"), state, (p, v, t_p, t_v)):
+            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
+    else:
+        state = (torch.empty_like(p), torch.empty_like(v), torch.empty_like(t_p), torch.empty_like(t_v))
+    sptr = [_ptr(s) if s.numel() else None for s in (samples, t_samples)]      # (no row: an empty tensor has no address)
+    check(_lib.lib().dhts_micro_rollout_fwd_jvp_samples(C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
+                                                        _ptr(t_p), _ptr(t_v), _ptr(t_head), _ptr(t_params), _ptr(state[0]), _ptr(state[1]),
+                                                        _ptr(state[2]), _ptr(state[3]), _ptr(probes), n_probes, every, sptr[0], sptr[1],
+                                                        _ptr(err), _ptr(err_jvp), _stream()), "dhts_micro_rollout_fwd_jvp_samples")
+    return (state[0], state[1], samples), (state[2], state[3], t_samples)
+
+
+def _probe_slots(probes, V):
+    """The `probes` argument of dhts.micro_rollout / micro_rollout_jvp, checked as macro_rollout checks `detectors` -> the CUDA int32
+    tensor as it is (not validated), or the list of slots (non-empty, strictly ascending, in [0, V); ValueError otherwise)."""
+    if isinstance(probes, torch.Tensor) and probes.is_cuda:
+        if probes.dtype != torch.int32 or probes.dim() != 1 or not 1 <= probes.numel() <= V:
+            raise ValueError("a CUDA `probes` must be a one-dimensional int32 tensor of 1..%d entries" % V)
+        return probes.contiguous()
+    if isinstance(probes, torch.Tensor):
+        if probes.dim() != 1 or probes.dtype.is_floating_point or probes.dtype.is_complex or probes.dtype == torch.bool:
+            raise ValueError("`probes` must be a one-dimensional integer tensor")
+        slots = probes.tolist()
+    else:
+        slots = list(probes)
+        if any(isinstance(c, bool) or int(c) != c for c in slots):
+            raise ValueError("`probes` must hold integers")
+        slots = [int(c) for c in slots]
+    if not slots:
+        raise ValueError("`probes` is empty")
+    if any(a >= b for a, b in zip(slots, slots[1:])) or any(not 0 <= c < V for c in slots):
+        raise ValueError("`probes` must be strictly ascending vehicle slots in [0, %d) (got %s)" % (V, slots))
+    return slots
+
+
+def micro_sampling(probes, every, V, want_hist):
+    """The (probes, every) arguments of dhts.micro_rollout / micro_rollout_jvp -> None when sampling is off (probes is None and every is
+    1), else (slots, every) with slots None (every slot), a list of ints or a CUDA int32 tensor.  Every ValueError of the two arguments
+    is raised here, before anything touches a device."""
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError("every must be an int >= 1, not %r" % (every,))
+    if probes is None and every == 1:
+        return None
+    slots = None if probes is None else _probe_slots(probes, V)
+    if want_hist:
+        raise ValueError("want_hist and probes / every exclude each other: the history holds every vehicle and step")
+    return slots, every
+
+
+def cut_samples(hist, slots, every, count=None):
+    """The samples of a dense history [..][T][L][2][V] (the taped paths: no sampled kernel form exists there): rows every - 1, 2 every - 1,
+    ..., the probes' columns, exactly 0 at a slot at or beyond count (the forward leaves those of hist unwritten) and in the column of a
+    raw CUDA entry outside [0, V).  Differentiable: autograd scatters the cotangent back into a dense one."""
+    V = hist.shape[-1]
+    cut = hist[..., every - 1::every, :, :, :]
+    if count is not None:
+        live = torch.arange(V, device=hist.device)[None, :] < count[:, None]
+        cut = torch.where(live[:, None, :], cut, torch.zeros((), dtype=cut.dtype, device=cut.device))
+    if slots is None:
+        return cut.contiguous()
+    idx = slots.long() if isinstance(slots, torch.Tensor) else torch.tensor(slots, dtype=torch.int64, device=hist.device)
+    inside = (idx >= 0) & (idx < V)
+    cut = cut.index_select(-1, idx.clamp(0, V - 1))
+    return torch.where(inside, cut, torch.zeros((), dtype=cut.dtype, device=cut.device))
+
+
 def _checkpoint_segment(checkpoint, plan):
     """The `checkpoint` argument of micro_rollout / macro_rollout -> None (the taped path) or the segment length to run with; ValueError
     otherwise.  plan(segment) -> the family's checkpoint plan (micro_ckpt_plan, macro_ckpt_plan), which raises for a segment it cannot run."""
@@ -1157,9 +1345,79 @@ def micro_bwd_fault(warn=True):
     return step, lane, index
 
 
-def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None):
-    """MicroRollout.  checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape)."""
-    return MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), want_hist, bool(check_faults), checkpoint)
+class MicroRolloutSamples(torch.autograd.Function):
+    """MicroRollout's checkpointed call observed at probe slots: (p0, v0 [L][V]) -> (pT, vT, samples [T // every][L][2][P]), samples
+    row j = (p, v) of slot probes[i] after step (j + 1) every - 1, exactly 0 at a slot at or beyond the lane's count.  The forward writes
+    samples and the reverse sweep reads their cotangent directly (dhts_micro_rollout_fwd_ckpt_samples / _bwd_ckpt_samples): no
+    [T][L][2][V] history and no cotangent of one exists, what grows with T is the checkpoint buffer and T // every rows of L 2 P floats.
+    probes: None (every slot) or a CUDA int32 tensor; segment: the checkpoint segment length, as MicroRollout's `checkpoint`."""
+
+    @staticmethod
+    def forward(ctx, p0, v0, params, head, count, T, dt, check_faults, checkpoint, probes, every):
+        L, V = p0.shape
+        desc = micro_desc(L, V, dt)
+        want_params = params.requires_grad
+        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, T, want_params, sg))      # (ValueError before a device is touched)
+        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
+        dev = p0c.device
+        need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or want_params
+        ctx.params, ctx.head = params.detach().contiguous(), head.detach().contiguous()
+        # everything the pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand over)
+        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
+        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
+        err = new_error_record(dev)
+        pT, vT, samples = micro_rollout_fwd_ckpt_samples(desc, T, p0c, v0c, ctx.params, ctx.head, ctx.ckpt, probes, every, count=count,
+                                                         segment=segment, err=err)
+        if check_faults:                 # a collision is printed like the reference does, and tolerated
+            raise_on_fault(err)
+        ctx.desc, ctx.T, ctx.count, ctx.check_faults, ctx.segment, ctx.probes, ctx.every = desc, T, count, check_faults, segment, probes, every
+        ctx.err_bwd = new_error_record(dev) if need_grad else None
+        return pT, vT, samples
+
+    @staticmethod
+    def backward(ctx, g_pT, g_vT, g_samples):
+        desc, T = ctx.desc, ctx.T
+        dev = ctx.err_bwd.device
+        L, V = desc.n_lanes, desc.capacity
+        g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
+        g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
+        P = V if ctx.probes is None else int(ctx.probes.numel())
+        gs = g_samples.contiguous() if g_samples is not None else torch.zeros(T // ctx.every, L, 2, P, device=dev)
+        err = ctx.err_bwd
+        err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
+        g_p0, g_v0, g_head = micro_rollout_bwd_ckpt_samples(desc, T, ctx.ckpt, ctx.params, ctx.head, g_p, g_v, ctx.probes, ctx.every, gs,
+                                                            count=ctx.count, segment=ctx.segment, err=err, g_params=ctx.g_params)
+        if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
+            MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
+        return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None, None, None
+
+
+def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None, probes=None, every=1):
+    """MicroRollout.  checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape).
+
+    probes / every: observe the trajectory at a few vehicle slots every so many steps.  Sampling is on when probes is not None or
+    every != 1, and the call then returns (pT, vT, samples), samples [T // every][L][2][P] float32: row j holds (p, v) of slot probes[i]
+    after step (j + 1) every - 1; the trailing T mod every steps give no row (T < every: no row at all); a slot at or beyond a lane's
+    count reads exactly 0 and receives no gradient.  samples is differentiable like hist: its cotangent enters the reverse sweep at the
+    sampled steps only.  probes: None (every slot, P = V), a sequence of ints or a CPU integer tensor (non-empty, strictly ascending, in
+    [0, V): checked, ValueError otherwise, before anything touches a device, then uploaded), or a CUDA int32 tensor, which is used as it
+    is and NOT validated: its entries must be distinct, and the kernels never form an address from one outside [0, V) -- that column
+    stays 0.  every: an int >= 1.  Not together with want_hist (ValueError): the history holds every vehicle and step.
+    With checkpoint= the kernels write and read samples directly and nothing of size T x V is allocated (MicroRolloutSamples).  On the
+    taped path (checkpoint=None) the samples are cut out of a dense history: ask for checkpoint= when memory matters."""
+    sampling = micro_sampling(probes, every, int(p0.shape[-1]), want_hist)
+    if sampling is None:
+        return MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), want_hist, bool(check_faults), checkpoint)
+    slots, every = sampling
+    if checkpoint is None or checkpoint is False:
+        pT, vT, hist = MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), True, bool(check_faults), None)
+        return pT, vT, cut_samples(hist, slots, every, count)
+    if p0.dim() == 2:                    # (a bad `checkpoint` is a ValueError before the probes are uploaded)
+        desc = micro_desc(int(p0.shape[0]), int(p0.shape[1]), float(dt))
+        _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, int(T), params.requires_grad, sg))
+    if isinstance(slots, list):
+        slots = torch.tensor(slots, dtype=torch.int32, device=p0.device)
+    return MicroRolloutSamples.apply(p0, v0, params, head, count, int(T), float(dt), bool(check_faults), checkpoint, slots, every)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -13,6 +13,9 @@ equations are formed and solved on the device, a step is kept where it lowers th
 follows.  Same box, same log.  --fused steps the rollout and the five tangents in one kernel (fused=True): no tape, no parameter tape,
 the same numbers bit for bit.  --checkpoint [S] (Adam) runs the reverse mode from checkpoints (dhts.micro_rollout(checkpoint=...)): the
 state every S steps (the library's own S when none is given) instead of 20 B of tapes per vehicle-step, the same log bit for bit.
+--observe P,E: floating-car data instead of a dense history -- the truth and the fit both observe P evenly spaced probe slots of every
+lane every E-th step (dhts.micro_rollout(probes=, every=) / micro_rollout_jvp(probes=, every=)); residuals and Jacobian are then
+T // E x L x 2 x P numbers, and with --checkpoint / --fused nothing of size T x V is allocated.  Works with every method and path.
 Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt (lm: .../lm/trial_k.txt), like the other examples.
 """
 import argparse
@@ -45,6 +48,8 @@ def main():
     ap.add_argument("--fused", action="store_true", help="Levenberg-Marquardt: rollout and tangents in one tape-free kernel")
     ap.add_argument("--checkpoint", type=int, nargs="?", const=True, default=None, metavar="S",
                     help="Adam: reverse mode from checkpoints every S steps (no S: the library's choice) instead of the tapes")
+    ap.add_argument("--observe", default=None, metavar="P,E",
+                    help="observe P evenly spaced probe slots per lane every E-th step instead of every vehicle at every step")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
@@ -52,6 +57,15 @@ def main():
         ap.error("--fused belongs to --method lm")
     if args.checkpoint is not None and args.method != "adam":
         ap.error("--checkpoint belongs to --method adam")
+    sampled = {}                                  # the arguments of a sampled call; none: the dense history
+    if args.observe is not None:
+        try:
+            n_probe, every = (int(x) for x in args.observe.split(","))
+        except ValueError:
+            ap.error("--observe takes two integers: P,E")
+        if not (1 <= n_probe <= args.n_vehicle and every >= 1):
+            ap.error("--observe P,E needs 1 <= P <= n_vehicle and E >= 1")
+        sampled = dict(probes=[(2 * i + 1) * args.n_vehicle // (2 * n_probe) for i in range(n_probe)], every=every)
 
     dev = th.device("cuda", 0)
     th.manual_seed(args.seed)
@@ -66,6 +80,8 @@ def main():
 
     def rollout(theta):
         params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+        if sampled:      # (the fused fit's loss evaluations: the tape-free forward too, no grad is asked of it)
+            return dhts.micro_rollout(p0, v0, params, head, T, dt, checkpoint=True if args.fused else args.checkpoint, **sampled)[2]
         return dhts.micro_rollout(p0, v0, params, head, T, dt, want_hist=True, checkpoint=args.checkpoint)[2]
 
     for trial in range(args.n_trial):
@@ -84,10 +100,10 @@ def main():
                 unit[i, i] = 1.0
             for ep in range(args.n_episode):
                 params = th.cat([theta, length])[:, None, None].expand(6, L, V)
-                (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, head, T, dt, t_params=unit, want_hist=True,
-                                                                      fused=args.fused)
+                (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, head, T, dt, t_params=unit, want_hist=not sampled,
+                                                                      fused=args.fused, **sampled)
                 res = (hist - observed).reshape(-1).double()
-                jac = t_hist.reshape(5, -1).double()                        # [5][T L 2 V]: column i of the Jacobian
+                jac = t_hist.reshape(5, -1).double()                        # [5][T L 2 V] (observed: [5][T // E L 2 P]): column i of the Jacobian
                 loss = (res ** 2).mean()
                 err = ((theta - truth[:5]) / truth[:5]).abs().max()
                 lines.append("{} {}\n".format(err.item(), loss.item()))

@@ -609,6 +609,46 @@ int dhts_micro_rollout_bwd_ckpt(const dhts_micro_desc *d, int T, int segment, co
                                 const double *head, const float *g_p, const float *g_v, const float *g_hist, float *g_p_out,
                                 float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream);
 
+/*
+ * PROBE SAMPLES on the two tape-free paths: the trajectory of a few vehicle slots every so many steps, read, written and
+ * differentiated without a [T][L][2][V] history.  The three entry points are dhts_micro_rollout_fwd_ckpt, _bwd_ckpt and _fwd_jvp with
+ * hist / g_hist / t_hist replaced by
+ *   probes      [n_probes] int32 device, DISTINCT slots: column i of a row belongs to slot probes[i]; or NULL: every slot, column i =
+ *               slot i (n_probes is ignored, P = capacity).  An entry outside [0, capacity) is skipped: no address is formed from it
+ *               and its column is neither written nor read.  With a repeated entry only one of its columns is served.
+ *   n_probes    P = 1 .. capacity with a list
+ *   every       E >= 1: row j holds the state after step (j + 1) E - 1; the trailing T mod E steps have no row
+ *   samples / g_samples   [T / E][L][2][P] float32, (p, v) as hist holds them; t_samples [K][T / E][L][2][P]
+ * and otherwise their siblings' arguments, arithmetic, fault records and bits.
+ *   dhts_micro_rollout_fwd_ckpt_samples   the rollout of dMicroForwardLayer.forward (dmicro_lane.py:230-269 = MicroLane.forward
+ *       _micro_lane.py:131-214 + dMicroLane._backward :87-127), as dhts_micro_rollout_fwd_ckpt.  samples: written at live probe slots
+ *       only (a slot at or beyond count keeps what the buffer held: hand in zeros).  ckpt may be NULL here: no checkpoint is kept, for
+ *       a forward that nobody differentiates.
+ *   dhts_micro_rollout_bwd_ckpt_samples   the sweep of dMicroForwardLayer.backward (dmicro_lane.py:271-298, with the virtual-leader slot
+ *       of dMicroLane.vectorize_input :130-153; the parameter gradient that of road/lane/_micro_lane.py:131-214 over
+ *       IDM.compute_acceleration, model/micro/_idm.py:30-49), as dhts_micro_rollout_bwd_ckpt.  g_samples enters at the sampled steps
+ *       only, and only at live probe slots (the dense sweep adds a g_hist row at every step).
+ *   dhts_micro_rollout_fwd_jvp_samples    forward mode of the plain MicroLane rollout (road/lane/_micro_lane.py:131-214 over
+ *       IDM.compute_acceleration, model/micro/_idm.py:30-49; the blocks those of road/lane/dmicro_lane.py:87-127), as
+ *       dhts_micro_rollout_fwd_jvp.  The first launch alone writes samples; t_samples: probe slots at or beyond count exactly 0.
+ * DHTS_E_INVALID, nothing dereferenced and nothing launched: whatever the sibling rejects (but a NULL ckpt of the forward), every < 1,
+ * n_probes outside 1 .. capacity with a non-NULL list, a NULL samples / g_samples / t_samples when T / every > 0.
+ * Blocks, segments and dynamic LDS are the siblings': dhts_micro_ckpt_plan and dhts_micro_fwd_jvp_plan hold for the sampled forms too
+ * (the probe list needs no LDS: each thread reads its slot's column once, before its step loop).
+ */
+int dhts_micro_rollout_fwd_ckpt_samples(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                        const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
+                                        const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err, void *stream);
+int dhts_micro_rollout_bwd_ckpt_samples(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                        const double *params, const double *head, const float *g_p, const float *g_v, const int32_t *probes,
+                                        int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out, double *g_head,
+                                        double *g_params, dhts_error *err, void *stream);
+int dhts_micro_rollout_fwd_jvp_samples(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                       const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                                       const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                       const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
+                                       dhts_error *err_jvp, void *stream);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
