@@ -22,6 +22,14 @@
 // sampled forms (kSamp), micro_rollout_ckpt_fwd_samples_kernel / _bwd_samples_kernel, which take MicroProbes and a samples array
 // [T / every][L][2][n] in place of hist / g_hist -- siblings from one text, and the first two compile to the code they were before
 // the siblings existed (profiles/micro_samples_resources*.txt).
+//
+// kLead, a template parameter of the two SAMPLED forms only (dhts_micro_rollout_fwd_ckpt_lead / _bwd_ckpt_lead): the head vehicle
+// follows a recorded leader, MicroLead's lead [T][L][2] float32 = the (p, v) it is seen at in step t, as every other vehicle follows
+// the slot in front of it -- the same two expressions for (dp, dv), the same idm_step; half_len with lead_length (or the head's own
+// length); no head gap is read and no g_head written.  The head's thread owns the leader's slot n of S (and of X): it writes row
+// t + 1 there during step t, the row after that in flight in registers; the reverse sweep stores C1[n], the cotangent of the slot in
+// front of the head, as row t of g_lead [T][L][2] instead of folding it into the head.  A NULL samples / g_samples: nothing is observed.
+// kLead = false is the code the sampled forms were before (profiles/micro_lead_resources*.txt).
 
 #if !DHTS_MICRO_SAMPLES
 // dynamic LDS of the two kernels: the plan (micro_plan) and the kernels' own carving read these
@@ -53,15 +61,17 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
     int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, float *__restrict__ hist, dhts_error *err) {
-    constexpr bool kSamp = false;
+    constexpr bool kSamp = false, kLead = false;
     const MicroProbes pr = {};
     float *const samples = nullptr;
+    const MicroLead ld = {};
 #else
+template <bool kLead>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, MicroProbes pr, float *__restrict__ samples,
-    dhts_error *err) {
+    dhts_error *err, MicroLead ld) {
     constexpr bool kSamp = true;
     float *const hist = nullptr;
 #endif
@@ -84,13 +94,13 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     if (V > B) {
         const float nanf_ = __builtin_nanf("");
         for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
-        if constexpr (kSamp) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_);
+        if constexpr (kSamp) { if (!kLead || samples) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_); }
         if (k == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);
         return;
     }
 
     float p = p_in[base + kc], v = v_in[base + kc];      // (a slot at or beyond count keeps them: the outputs pass it through)
-    const int col = kSamp ? micro_probe_column(pr, k, V) : -1;
+    const int col = kSamp ? ((kLead && samples == nullptr) ? -1 : micro_probe_column(pr, k, V)) : -1;     // kLead, no samples: no column
     IdmDerived prm = {};
     double half_len = 0.;
     if (vk) {
@@ -102,8 +112,10 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
         idm_set_dt(prm, dt);
         const int kl = k + 1 < n ? k + 1 : k;
         half_len = (params[5 * plane + base + kl] + raw.length) * 0.5;
+        if constexpr (kLead) { if (is_head && ld.length) half_len = (ld.length[lane] + raw.length) * 0.5; }
     }
-    const double head_dp = head[(size_t)lane * 2], head_dv = head[(size_t)lane * 2 + 1];
+    double head_dp = 0., head_dv = 0.;
+    if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
 
     for (int i = k; i < 2 * P; i += B) S[i] = make_float2(0.f, 0.f);
     __syncthreads();
@@ -111,6 +123,17 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     int fault_step = -1;
     if (T > 0) {
         if (vk) S[k] = make_float2(p, v);
+        // kLead: the head's thread owns slot n of S -- row 0 now, row step + 1 during step `step`, the row after that in flight in (lx, ly)
+        const float *lrow = nullptr;
+        float lx = 0.f, ly = 0.f;
+        if constexpr (kLead) {
+            if (is_head) {
+                lrow = micro_lead_row(ld.lead, lane);
+                S[n] = make_float2(lrow[0], lrow[1]);
+                lrow += (size_t)L * 2;
+                if (T > 1) { lx = lrow[0]; ly = lrow[1]; }
+            }
+        }
         __syncthreads();
         float2 *ck = ckpt + (size_t)lane * Vp + k;       // this slot of row 0; a row is L Vp entries
         int next_ck = (kSamp && ckpt == nullptr) ? -1 : 0;
@@ -130,13 +153,20 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
                 const float2 ls = S[q * P + k + 1];      // the leader's state before this step
                 const double pd = p, vd = v;
                 // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
-                const double dp = is_head ? head_dp : fabs((double)ls.x - pd) - half_len;
-                const double dv = is_head ? head_dv : vd - (double)ls.y;
+                const double dp = (!kLead && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
+                const double dv = (!kLead && is_head) ? head_dv : vd - (double)ls.y;
                 IdmStep o;
                 idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
                 if (o.collided && fault_step < 0) fault_step = step;
                 p = o.np; v = o.nv;
                 S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
+                if constexpr (kLead) {
+                    if (is_head && step + 1 < T) {
+                        S[(q ^ 1) * P + n] = make_float2(lx, ly);      // ... and what its leader is seen at in step + 1
+                        lrow += (size_t)L * 2;
+                        if (step + 2 < T) { lx = lrow[0]; ly = lrow[1]; }
+                    }
+                }
                 if constexpr (kSamp) { if (due && col >= 0) { sp[0] = p; sp[pr.n] = v; } }
                 else if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
             }
@@ -150,7 +180,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
 
 // grid = L workgroups of blockDim.x >= V threads, one vehicle per thread.  Dynamic LDS (micro_ckpt_bwd_lds_bytes):
 //   float2 S[2][V + 1]             the replay's state hand-over, as in the forward
-//   float2 X[Sg][V + 1]            kParams: the (p, v) a vehicle entered step r of the segment with (slot V is never written nor used)
+//   float2 X[Sg][V + 1]            kParams: the (p, v) a vehicle entered step r of the segment with (slot V is never written nor used;
+//                                  kLead: slot n holds the leader the head saw in step r, written and read by the head's thread)
 //   float  Gp, Gv, C1p, C1v [V + 2]    the cotangents, as in micro_rollout_bwd_kernel (C1[i + 1] = dLeading[i]^T g[i])
 //   float  R[Sg][3][V]             the segment's tape: e2, e3, l3 of step r, one plane each
 // Segments c = C - 1 .. 0: load row c of ckpt (prefetched while the segment after it was swept), replay steps [c Sg, min(T, (c + 1) Sg))
@@ -162,22 +193,24 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
 // slot adds, and only at a sampled step.  Its rows travel two ROWS ahead in the same four registers (2 every steps: with every = 1
 // the g_hist pipeline), across segment boundaries like the countdown to the next sampled step, which starts at T mod every: the
 // trailing steps have no row.
-template <bool kParams>
 #if !DHTS_MICRO_SAMPLES
+template <bool kParams>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
     int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, const float *__restrict__ g_hist, float *__restrict__ g_p_out, float *__restrict__ g_v_out,
     double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err) {
-    constexpr bool kSamp = false;
+    constexpr bool kSamp = false, kLead = false;
     const MicroProbes pr = {};
     const float *const g_samples = nullptr;
+    const MicroLead ld = {};
 #else
+template <bool kParams, bool kLead>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
     int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, MicroProbes pr, const float *__restrict__ g_samples, float *__restrict__ g_p_out,
-    float *__restrict__ g_v_out, double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err) {
+    float *__restrict__ g_v_out, double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err, MicroLead ld) {
     constexpr bool kSamp = true;
     const float *const g_hist = nullptr;
 #endif
@@ -205,9 +238,11 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
     if (V > B) {
         const float nanf_ = __builtin_nanf("");
         for (int i = k; i < V; i += B) { g_p_out[base + i] = nanf_; g_v_out[base + i] = nanf_; }
+        if constexpr (kLead) micro_lead_fill(ld.g_lead, T, L, lane, k, B, nanf_);
         if (k == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);
         return;
     }
+    if constexpr (kLead) { if (n == 0) micro_lead_fill(ld.g_lead, T, L, lane, k, B, 0.f); }      // (no head: nobody else writes the rows)
 
     for (int i = k; i < P; i += B) { Gp[i] = 0.f; Gv[i] = 0.f; C1p[i] = 0.f; C1v[i] = 0.f; }
     for (int i = k; i < 2 * P1; i += B) S[i] = make_float2(0.f, 0.f);
@@ -228,8 +263,10 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
         idm_set_dt(prm, dt);
         if constexpr (kParams) pm = idm_param_derive(raw);
         half_len = (params[5 * plane + base + (k + 1 < n ? k + 1 : k)] + raw.length) * 0.5;
+        if constexpr (kLead) { if (is_head && ld.length) half_len = (ld.length[lane] + raw.length) * 0.5; }
     }
-    const double head_dp = head[(size_t)lane * 2], head_dv = head[(size_t)lane * 2 + 1];
+    double head_dp = 0., head_dv = 0.;
+    if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
     __syncthreads();
 
     double gh_p = 0., gh_v = 0.;       // held by the thread that owns the head vehicle
@@ -255,7 +292,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
         if constexpr (kSamp) {
             const int col = micro_probe_column(pr, k, V);
             const int rows = T / pr.every;
-            probe = vk && col >= 0;
+            probe = vk && col >= 0 && (!kLead || g_samples != nullptr);      // kLead, no g_samples: nothing was observed
             cd = T - rows * pr.every;
             if (probe && rows > 0) {
                 gs = g_samples + (size_t)(rows - 1) * s_row + (size_t)lane * 2 * pr.n + col;
@@ -264,12 +301,28 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                 if (rows_left > 0) { gs -= s_row; hp2 = gs[0]; hv2 = gs[pr.n]; --rows_left; }
             }
         }
+        // kLead: the head's thread owns slot n of S (and of X): the lead row of a segment's first step travels like ck, a segment
+        // ahead in (l0x, l0y); the rows of its later steps one replay step ahead in (l1x, l1y)
+        const float *const lead0 = (kLead && is_head) ? micro_lead_row(ld.lead, lane) : nullptr;
+        const size_t l_row = (size_t)L * 2;
+        float l0x = 0.f, l0y = 0.f, l1x = 0.f, l1y = 0.f;
+        if constexpr (kLead) {
+            if (is_head) { const float *a = lead0 + (size_t)(C - 1) * Sg * l_row; l0x = a[0]; l0y = a[1]; }
+        }
         for (int c = C - 1; c >= 0; --c) {
             const int s0 = c * Sg, s1 = (T - s0 < Sg) ? T : s0 + Sg;
             float p = ck.x, v = ck.y;
             ck = ck0[(size_t)(c > 0 ? c - 1 : 0) * row];         // the checkpoint before: in flight across the whole segment
             // ---- replay steps [s0, s1) into the ring ----
             if (vk) S[k] = make_float2(p, v);
+            if constexpr (kLead) {
+                if (is_head) {
+                    S[n] = make_float2(l0x, l0y);
+                    if (s0 + 1 < s1) { const float *a = lead0 + (size_t)(s0 + 1) * l_row; l1x = a[0]; l1y = a[1]; }
+                    const float *b = lead0 + (size_t)(c > 0 ? s0 - Sg : 0) * l_row;
+                    l0x = b[0]; l0y = b[1];
+                }
+            }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             for (int r = 0; r < s1 - s0; ++r) {
                 const int q = r & 1;
@@ -277,8 +330,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                     const float2 ls = S[q * P1 + k + 1];
                     const double pd = p, vd = v;
                     // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
-                    const double dp = is_head ? head_dp : fabs((double)ls.x - pd) - half_len;
-                    const double dv = is_head ? head_dv : vd - (double)ls.y;
+                    const double dp = (!kLead && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
+                    const double dv = (!kLead && is_head) ? head_dv : vd - (double)ls.y;
                     IdmStep o;
                     idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
                     float *e = R + (size_t)r * 3 * V + k;
@@ -286,6 +339,15 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                     if constexpr (kParams) X[(size_t)r * P1 + k] = make_float2(p, v);
                     p = o.np; v = o.nv;
                     S[(q ^ 1) * P1 + k] = make_float2(p, v);
+                    if constexpr (kLead) {
+                        if (is_head) {
+                            if constexpr (kParams) X[(size_t)r * P1 + n] = ls;      // the leader the head saw in this step
+                            if (s0 + r + 1 < s1) {
+                                S[(q ^ 1) * P1 + n] = make_float2(l1x, l1y);
+                                if (s0 + r + 2 < s1) { const float *a = lead0 + (size_t)(s0 + r + 2) * l_row; l1x = a[0]; l1y = a[1]; }
+                            }
+                        }
+                    }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             }
@@ -326,9 +388,9 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                         // compute_state_delta and the collision / clamp rules of the forward, _micro_lane.py:149-166, 201-212
                         const float2 xl = X[(size_t)r * P1 + k + 1];
                         const double pv = cx.y;
-                        double gap = is_head ? head_dp : fabs((double)xl.x - (double)cx.x) - half_len;
-                        double dv = is_head ? head_dv : pv - (double)xl.y;
-                        const bool live_gap = !is_head && gap >= 1e-5;       // else a constant: nothing flows to the lengths
+                        double gap = (!kLead && is_head) ? head_dp : fabs((double)xl.x - (double)cx.x) - half_len;
+                        double dv = (!kLead && is_head) ? head_dv : pv - (double)xl.y;
+                        const bool live_gap = (kLead || !is_head) && gap >= 1e-5;       // else a constant: nothing flows to the lengths
                         if (gap < 0) { gap = 0; dv = 0; }
                         gap = (1e-5 > gap) ? 1e-5 : gap;
                         if (!(e.e2 == 0.f && e.e3 == 0.f && e.l3 == 0.f)) {  // (the forward's acceleration clip zeroes all three)
@@ -344,7 +406,10 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                 if (vk) {
                     float np_ = Gp[k], nv_ = Gv[k];
                     if (k > 0) { np_ += C1p[k]; nv_ += C1v[k]; }
-                    if (is_head) {
+                    if constexpr (kLead) {
+                        // the prescribed leader's cotangent C1[n] is this step's row of g_lead: nothing returns to the head
+                        if (is_head) { float *gl = ld.g_lead + ((size_t)step * L + lane) * 2; gl[0] = C1p[n]; gl[1] = C1v[n]; }
+                    } else if (is_head) {
                         // virtual leader = (p_head + head_dp, v_head - head_dv): its cotangent C1[n] returns to the head
                         const float vp = C1p[n], vv = C1v[n];
                         gh_p += (double)vp;

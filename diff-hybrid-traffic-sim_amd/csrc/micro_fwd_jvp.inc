@@ -22,6 +22,13 @@
 // micro_kernels.hip includes this file twice: with DHTS_MICRO_SAMPLES 0 for the kernel described above, then with 1 for its sampled
 // form (kSamp), micro_rollout_fwd_jvp_samples_kernel -- siblings from one text, and the first compiles to the code it was before the
 // sibling existed (profiles/micro_samples_resources*.txt).
+//
+// kLead, a template parameter of the SAMPLED form only (dhts_micro_rollout_fwd_jvp_lead): the head vehicle follows a recorded leader,
+// MicroLead's lead [T][L][2] float32 and its tangents t_lead [kK][T][L][2] (NULL: zero), as every other vehicle follows the slot in
+// front of it; virtual_leader is not called, head / t_head are not read and TH stays zero.  The head's thread owns the leader's slot
+// n of S and of TN: it writes row t + 1 there during step t, the row after that in flight in registers.  The head's length tangent
+// carries its own share of the gap only, -t_len / 2.  NULL samples and t_samples (both): nothing is observed.  kLead = false is the
+// code the sampled form was before (profiles/micro_lead_resources*.txt).
 
 #if !DHTS_MICRO_SAMPLES
 __host__ __device__ inline size_t micro_fwd_jvp_lds_bytes(int V, int kK) {
@@ -43,24 +50,26 @@ __host__ __device__ inline size_t micro_fwd_jvp_lds_bytes(int V, int kK) {
 // t_samples [kK][T / every][L][2][n] takes the probe slots' (p, v) and tangents after step (j + 1) every - 1 -- a thread finds its
 // slot's column among the probes once, before the step loop, counts the steps down to the next sampled one and moves running pointers
 // from row to row.  samples: live slots only, or NULL (every launch of a call but the first); t_samples: slots at or beyond count 0.
-template <int kK, bool kParams>
 #if !DHTS_MICRO_SAMPLES
+template <int kK, bool kParams>
 __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
     int L, int V, int T, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ t_p_in,
     const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
     float *__restrict__ hist, float *__restrict__ t_hist, dhts_error *err, dhts_error *err_jvp) {
-    constexpr bool kSamp = false;
+    constexpr bool kSamp = false, kLead = false;
     const MicroProbes pr = {};
     float *const samples = nullptr, *const t_samples = nullptr;
+    const MicroLead ld = {};
 #else
+template <int kK, bool kParams, bool kLead>
 __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
     int L, int V, int T, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ t_p_in,
     const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
-    MicroProbes pr, float *__restrict__ samples, float *__restrict__ t_samples, dhts_error *err, dhts_error *err_jvp) {
+    MicroProbes pr, float *__restrict__ samples, float *__restrict__ t_samples, dhts_error *err, dhts_error *err_jvp, MicroLead ld) {
     constexpr bool kSamp = true;
     float *const hist = nullptr, *const t_hist = nullptr;
 #endif
@@ -98,7 +107,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         if constexpr (kSamp) {
             if (samples) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_);
             for (int d = 0; d < n_act; ++d)
-                micro_samples_fill(t_samples + (size_t)d * (T / pr.every) * L * 2 * pr.n, pr, T, L, lane, k, B, nanf_);
+                if (!kLead || t_samples) micro_samples_fill(t_samples + (size_t)d * (T / pr.every) * L * 2 * pr.n, pr, T, L, lane, k, B, nanf_);
         }
         if (k == 0) { raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3); raise_fault(err_jvp, DHTS_FAULT_CAPACITY, 0, lane, -3); }
         return;
@@ -132,6 +141,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         idm_set_dt(prm, dt);
         const int kl = k + 1 < n ? k + 1 : k;
         half_len = (params[5 * plane + base + kl] + raw.length) * 0.5;
+        if constexpr (kLead) { if (is_head && ld.length) half_len = (ld.length[lane] + raw.length) * 0.5; }
         if constexpr (kParams) {
             pm = idm_param_derive(raw);
 #pragma unroll
@@ -141,24 +151,56 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
 #pragma unroll
                     for (int q = 0; q < 5; ++q) tth[d][q] = tq[q * plane + k];
                     tth[d][5] = -(tq[5 * plane + kl] + tq[5 * plane + k]) * 0.5;
+                    if constexpr (kLead) { if (is_head) tth[d][5] = -tq[5 * plane + k] * 0.5; }      // the leader's length is a constant
                 }
             }
         }
     }
-    const double head_dp = head[(size_t)lane * 2], head_dv = head[(size_t)lane * 2 + 1];
+    double head_dp = 0., head_dv = 0.;
+    if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
 
     for (int i = k; i < (2 + 2 * kK) * P; i += B) S[i] = make_float2(0.f, 0.f);
-    if (k < 2 * kK) TH[k] = ((k >> 1) < n_act && t_head) ? t_head[((size_t)(k >> 1) * L + lane) * 2 + (k & 1)] : 0.;
+    if constexpr (kLead) { if (k < 2 * kK) TH[k] = 0.; }
+    else if (k < 2 * kK) TH[k] = ((k >> 1) < n_act && t_head) ? t_head[((size_t)(k >> 1) * L + lane) * 2 + (k & 1)] : 0.;
     __syncthreads();
 
     int fault_step = -1, bad_step = -1;
     if (T > 0) {
+        // kLead: the head's thread owns slot n of S and of TN -- row 0 now, row step + 1 during step `step`, the row after that in
+        // flight in (lx, ly) and (ltx, lty); a direction of t_lead is T L 2 floats, NULL = zero.  The widest form with the parameter
+        // term has no register left for eight more floats (128 VGPRs at 1024 threads): there the tangent rows are loaded in the
+        // step that hands them over (kTanAhead false), the state row still travels ahead.
+        constexpr bool kTanAhead = !(kParams && kK >= 4);
+        const float *lrow = nullptr, *ltrow = nullptr;
+        float lx = 0.f, ly = 0.f, ltx[kLead && kTanAhead ? kK : 1], lty[kLead && kTanAhead ? kK : 1];
+        const size_t lt_dir = (size_t)T * L * 2;
         if (vk) {
             S[k] = make_float2(p, v);
 #pragma unroll
             for (int d = 0; d < kK; ++d) {
                 TN[d * P + k] = make_float2(tp[d], tv[d]);
-                if (is_head) TN[d * P + k + 1] = virtual_leader(tp[d], tv[d], TH[2 * d], TH[2 * d + 1]);
+                if constexpr (!kLead) { if (is_head) TN[d * P + k + 1] = virtual_leader(tp[d], tv[d], TH[2 * d], TH[2 * d + 1]); }
+            }
+            if constexpr (kLead) {
+                if (is_head) {
+                    lrow = micro_lead_row(ld.lead, lane);
+                    ltrow = ld.t_lead ? micro_lead_row(ld.t_lead, lane) : nullptr;
+                    S[n] = make_float2(lrow[0], lrow[1]);
+#pragma unroll
+                    for (int d = 0; d < kK; ++d)
+                        TN[d * P + n] = (ltrow && d < n_act) ? make_float2(ltrow[d * lt_dir], ltrow[d * lt_dir + 1]) : make_float2(0.f, 0.f);
+                    lrow += (size_t)L * 2;
+                    if (ltrow) ltrow += (size_t)L * 2;
+                    const bool more = T > 1;
+                    lx = more ? lrow[0] : 0.f; ly = more ? lrow[1] : 0.f;
+                    if constexpr (kTanAhead) {
+#pragma unroll
+                        for (int d = 0; d < kK; ++d) {
+                            const bool on = more && ltrow && d < n_act;
+                            ltx[d] = on ? ltrow[d * lt_dir] : 0.f; lty[d] = on ? ltrow[d * lt_dir + 1] : 0.f;
+                        }
+                    }
+                }
             }
         }
         __syncthreads();
@@ -167,7 +209,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         int col = -1, cd = 0;
         size_t so = 0, s_dir = 0;
         if constexpr (kSamp) {
-            col = micro_probe_column(pr, k, V);
+            col = (kLead && t_samples == nullptr) ? -1 : micro_probe_column(pr, k, V);      // kLead, no sample arrays: no column
             cd = pr.every;
             s_dir = (size_t)(T / pr.every) * L * 2 * pr.n;
             so = (size_t)lane * 2 * pr.n + (col < 0 ? 0 : col);
@@ -180,8 +222,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                 const float2 ls = S[q * P + k + 1];      // the leader's state before this step
                 const double pd = p, vd = v;
                 // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
-                const double dp = is_head ? head_dp : fabs((double)ls.x - pd) - half_len;
-                const double dv = is_head ? head_dv : vd - (double)ls.y;
+                const double dp = (!kLead && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
+                const double dv = (!kLead && is_head) ? head_dv : vd - (double)ls.y;
                 IdmStep o;
                 idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
                 if (o.collided && fault_step < 0) fault_step = step;
@@ -193,7 +235,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                 bool has_x = false, live_gap = false;
                 if constexpr (kParams) {
                     double gap = dp, dvx = dv;
-                    live_gap = !is_head && gap >= 1e-5;      // else a constant: nothing flows to the lengths
+                    live_gap = (kLead || !is_head) && gap >= 1e-5;      // else a constant: nothing flows to the lengths
                     if (gap < 0) { gap = 0; dvx = 0; }
                     gap = (1e-5 > gap) ? 1e-5 : gap;
                     has_x = !(c.e2 == 0.f && c.e3 == 0.f && c.l3 == 0.f);      // (the forward's acceleration clip zeroes all three)
@@ -217,12 +259,33 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                     jvp_vehicle(c, dtf, tp[d], tv[d], tl.x, tl.y, x, np_, nv_);
                     tp[d] = np_; tv[d] = nv_;
                     TN[((q ^ 1) * kK + d) * P + k] = make_float2(np_, nv_);
-                    if (is_head) TN[((q ^ 1) * kK + d) * P + k + 1] = virtual_leader(np_, nv_, TH[2 * d], TH[2 * d + 1]);
+                    if constexpr (!kLead) { if (is_head) TN[((q ^ 1) * kK + d) * P + k + 1] = virtual_leader(np_, nv_, TH[2 * d], TH[2 * d + 1]); }
                     fin = fin && isfinite(np_) && isfinite(nv_);
                 }
                 if (bad_step < 0 && !fin) bad_step = step;
                 p = o.np; v = o.nv;
                 S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
+                if constexpr (kLead) {
+                    if (is_head && step + 1 < T) {           // ... and what its leader is seen at in step + 1, with its tangents
+                        S[(q ^ 1) * P + n] = make_float2(lx, ly);
+#pragma unroll
+                        for (int d = 0; d < kK; ++d) {
+                            if constexpr (kTanAhead) TN[((q ^ 1) * kK + d) * P + n] = make_float2(ltx[d], lty[d]);
+                            else TN[((q ^ 1) * kK + d) * P + n] = (ltrow && d < n_act) ? make_float2(ltrow[d * lt_dir], ltrow[d * lt_dir + 1])
+                                                                                       : make_float2(0.f, 0.f);
+                        }
+                        lrow += (size_t)L * 2;
+                        if (ltrow) ltrow += (size_t)L * 2;
+                        if (step + 2 < T) {
+                            lx = lrow[0]; ly = lrow[1];
+                            if constexpr (kTanAhead) {
+#pragma unroll
+                                for (int d = 0; d < kK; ++d)
+                                    if (ltrow && d < n_act) { ltx[d] = ltrow[d * lt_dir]; lty[d] = ltrow[d * lt_dir + 1]; }
+                            }
+                        }
+                    }
+                }
                 if constexpr (kSamp) { if (due && col >= 0 && samples) { samples[so] = p; samples[so + pr.n] = v; } }
                 else if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
             }

@@ -16,6 +16,8 @@
 //   of one segment at a time rebuilt in LDS.
 // Sampled (micro_rollout_ckpt_fwd_samples_kernel / _bwd_samples_kernel, micro_rollout_fwd_jvp_samples_kernel): the two tape-free paths
 //   writing and reading probe samples [T / every][L][2][P] in place of a [T][L][2][V] history -- the same two files, included again.
+// Recorded leader (the kLead = true instantiations of the three sampled kernels): the head vehicle follows lead [T][L][2], a vehicle
+//   given per step, instead of a constant head gap; its cotangent per step is g_lead, its tangents t_lead.
 //
 // Reference: road/lane/_micro_lane.py:131-214, road/lane/dmicro_lane.py:87-127 and :271-298.
 #include <hip/hip_runtime.h>
@@ -519,6 +521,27 @@ __device__ inline void micro_samples_fill(float *samples, const MicroProbes &pr,
     for (int j = 0; j < rows; ++j)
         for (int i = k; i < 2 * pr.n; i += B) samples[((size_t)j * L + lane) * 2 * pr.n + i] = value;
 }
+// ---- a recorded leader on the two tape-free paths (dhts_micro_rollout_*_lead) -------------------------------------
+// kLead forms of the three sampled kernels: the lane's head vehicle (slot count - 1) follows a prescribed vehicle whose state `in`
+// step t is row t of lead, as every other vehicle follows the slot in front of it; no virtual leader and no head gap exist.
+struct MicroLead {
+    const float *lead;       // [T][L][2] (p, v) the head sees in step t
+    const double *length;    // [L] the leader's length, or NULL: the head's own
+    float *g_lead;           // reverse sweep: [T][L][2], every row written
+    const float *t_lead;     // fused JVP: [kK][T][L][2] of this launch's directions, or NULL: zero
+};
+// This lane's entry of row 0 of a [T][L][2] array, for the ONE thread that walks the rows (the head vehicle's).  The address is the
+// same for a whole workgroup, so without the opaque zero the rows would be read by scalar loads, which the step's LDS-only wait
+// (lgkmcnt) also waits for; from a vector register they are vector loads and stay in flight across it, as g_hist rows do.
+__device__ inline const float *micro_lead_row(const float *rows, int lane) {
+    int z = 0;
+    asm volatile("" : "+v"(z));
+    return rows + (size_t)lane * 2 + z;
+}
+// the lane's entry of every row of g_lead takes `value` (a lane without a vehicle: 0; a block smaller than the lane: NaN)
+__device__ inline void micro_lead_fill(float *g_lead, int T, int L, int lane, int k, int B, float value) {
+    for (int t = k; t < T; t += B) { g_lead[((size_t)t * L + lane) * 2] = value; g_lead[((size_t)t * L + lane) * 2 + 1] = value; }
+}
 // ---- the rollout and its tangents in one kernel, no tape (dhts_micro_rollout_fwd_jvp) ----------------------------
 #define DHTS_MICRO_SAMPLES 0
 #include "micro_fwd_jvp.inc"
@@ -748,23 +771,28 @@ static int micro_fwd_jvp_samples_launch(const dhts_micro_desc *d, int T, int n_d
                                         const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
                                         const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
                                         const MicroProbes &pr, float *samples, float *t_samples, dhts_error *err, dhts_error *err_jvp,
-                                        void *stream) {
+                                        void *stream, const MicroLead *lead = nullptr) {
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
     const int L = d->n_lanes, V = d->capacity, kmax = pl.fwd_jvp_kmax[t_params ? 1 : 0];
-    const size_t dir_state = (size_t)L * V, dir_samples = (size_t)(T / pr.every) * L * 2 * pr.n;
+    const size_t dir_state = (size_t)L * V, dir_samples = (size_t)(T / pr.every) * L * 2 * pr.n, dir_lead = (size_t)T * L * 2;
     bool lds_ok = true;
     for (int k0 = 0; k0 < n_dir && lds_ok;) {
         const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
         const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
         float *o_s = t_samples ? t_samples + k0 * dir_samples : nullptr;
+        MicroLead ld = lead ? *lead : MicroLead{};
+        if (ld.t_lead) ld.t_lead += k0 * dir_lead;       // this launch's directions
         pick<4, 2, 1>(kk, [&](auto kv) {
             constexpr int kK = decltype(kv)::value;
             pick<0, 1>(t_params != nullptr, [&](auto pv) {
                 constexpr bool kParams = decltype(pv)::value != 0;
-                lds_ok = launch_lds(micro_rollout_fwd_jvp_samples_kernel<kK, kParams>, L, pl.fwd_jvp_block, micro_fwd_jvp_lds_bytes(V, kK),
-                                    kLdsDefault, stream, L, V, T, d->dt, p, v, count, params, head, t_p + k0 * dir_state, t_v + k0 * dir_state,
-                                    a_h, a_q, n_act, p_out, v_out, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, pr,
-                                    k0 == 0 ? samples : nullptr, o_s, k0 == 0 ? err : nullptr, err_jvp);
+                pick<0, 1>(lead != nullptr, [&](auto lv) {
+                    constexpr bool kLead = decltype(lv)::value != 0;
+                    lds_ok = launch_lds(micro_rollout_fwd_jvp_samples_kernel<kK, kParams, kLead>, L, pl.fwd_jvp_block,
+                                        micro_fwd_jvp_lds_bytes(V, kK), kLdsDefault, stream, L, V, T, d->dt, p, v, count, params, head,
+                                        t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q, n_act, p_out, v_out, t_p_out + k0 * dir_state,
+                                        t_v_out + k0 * dir_state, pr, k0 == 0 ? samples : nullptr, o_s, k0 == 0 ? err : nullptr, err_jvp, ld);
+                });
             });
         });
         k0 += n_act;
@@ -773,28 +801,37 @@ static int micro_fwd_jvp_samples_launch(const dhts_micro_desc *d, int T, int n_d
 }
 static int micro_ckpt_fwd_samples_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
                                          const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
-                                         const MicroProbes &pr, float *samples, dhts_error *err, void *stream) {
+                                         const MicroProbes &pr, float *samples, dhts_error *err, void *stream,
+                                         const MicroLead *lead = nullptr) {
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
     const int S = micro_ckpt_segment(pl, segment, false);
     if (S < 0) return DHTS_E_INVALID;
-    const bool ok = launch_lds(micro_rollout_ckpt_fwd_samples_kernel, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity),
-                               kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out,
-                               (float2 *)ckpt, pr, samples, err);
+    bool ok = true;
+    pick<0, 1>(lead != nullptr, [&](auto lv) {
+        constexpr bool kLead = decltype(lv)::value != 0;
+        ok = launch_lds(micro_rollout_ckpt_fwd_samples_kernel<kLead>, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity),
+                        kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out, (float2 *)ckpt,
+                        pr, samples, err, lead ? *lead : MicroLead{});
+    });
     return ok ? launch_status() : DHTS_E_LAUNCH;
 }
 static int micro_ckpt_bwd_samples_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
                                          const double *params, const double *head, const float *g_p, const float *g_v, const MicroProbes &pr,
                                          const float *g_samples, float *g_p_out, float *g_v_out, double *g_head, double *g_params,
-                                         dhts_error *err, void *stream) {
+                                         dhts_error *err, void *stream, const MicroLead *lead = nullptr) {
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
     const int S = micro_ckpt_segment(pl, segment, g_params != nullptr);
     if (S < 0) return DHTS_E_INVALID;
     bool ok = true;
     pick<0, 1>(g_params != nullptr, [&](auto pv) {
         constexpr bool kParams = decltype(pv)::value != 0;
-        ok = launch_lds(micro_rollout_ckpt_bwd_samples_kernel<kParams>, d->n_lanes, pl.ckpt_block,
-                        micro_ckpt_bwd_lds_bytes(d->capacity, S, kParams), kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt,
-                        (const float2 *)ckpt, count, params, head, g_p, g_v, pr, g_samples, g_p_out, g_v_out, g_head, g_params, err);
+        pick<0, 1>(lead != nullptr, [&](auto lv) {
+            constexpr bool kLead = decltype(lv)::value != 0;
+            ok = launch_lds(micro_rollout_ckpt_bwd_samples_kernel<kParams, kLead>, d->n_lanes, pl.ckpt_block,
+                            micro_ckpt_bwd_lds_bytes(d->capacity, S, kParams), kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt,
+                            (const float2 *)ckpt, count, params, head, g_p, g_v, pr, g_samples, g_p_out, g_v_out, g_head, g_params, err,
+                            lead ? *lead : MicroLead{});
+        });
     });
     return ok ? launch_status() : DHTS_E_LAUNCH;
 }
@@ -985,6 +1022,43 @@ int dhts_micro_rollout_fwd_jvp_samples(const dhts_micro_desc *d, int T, int n_di
         return DHTS_E_INVALID;
     return micro_fwd_jvp_samples_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out, pr,
                                         samples, t_samples, err, err_jvp, stream);
+}
+// ---- a recorded leader on the two tape-free paths: the kLead forms of the three sampled kernels ---------------------------------------
+int dhts_micro_rollout_fwd_ckpt_lead(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                     const double *params, const float *lead, const double *lead_length, float *p_out, float *v_out,
+                                     void *ckpt, const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err,
+                                     void *stream) {
+    MicroProbes pr;
+    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || (T > 0 && !lead) || !p_out || !v_out ||
+        !micro_probes_ok(d, probes, n_probes, every, &pr))
+        return DHTS_E_INVALID;
+    const MicroLead ld = {lead, lead_length, nullptr, nullptr};
+    return micro_ckpt_fwd_samples_launch(d, T, segment, p, v, count, params, nullptr, p_out, v_out, ckpt, pr, samples, err, stream, &ld);
+}
+int dhts_micro_rollout_bwd_ckpt_lead(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                     const double *params, const float *lead, const double *lead_length, const float *g_p, const float *g_v,
+                                     const int32_t *probes, int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out,
+                                     float *g_lead, double *g_params, dhts_error *err, void *stream) {
+    MicroProbes pr;
+    if (!micro_desc_ok(d) || T < 0 || (T > 0 && (!ckpt || !lead || !g_lead)) || !params || !g_p || !g_v || !g_p_out || !g_v_out ||
+        !micro_probes_ok(d, probes, n_probes, every, &pr))
+        return DHTS_E_INVALID;
+    const MicroLead ld = {lead, lead_length, g_lead, nullptr};
+    return micro_ckpt_bwd_samples_launch(d, T, segment, ckpt, count, params, nullptr, g_p, g_v, pr, g_samples, g_p_out, g_v_out, nullptr,
+                                         g_params, err, stream, &ld);
+}
+int dhts_micro_rollout_fwd_jvp_lead(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                    const double *params, const float *lead, const double *lead_length, const float *t_p, const float *t_v,
+                                    const float *t_lead, const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                    const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
+                                    dhts_error *err_jvp, void *stream) {
+    MicroProbes pr;
+    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !p || !v || !params || (T > 0 && !lead) || !t_p || !t_v || !p_out || !v_out || !t_p_out ||
+        !t_v_out || !micro_probes_ok(d, probes, n_probes, every, &pr) || (samples == nullptr) != (t_samples == nullptr))
+        return DHTS_E_INVALID;
+    const MicroLead ld = {lead, lead_length, nullptr, t_lead};
+    return micro_fwd_jvp_samples_launch(d, T, n_dir, p, v, count, params, nullptr, t_p, t_v, nullptr, t_params, p_out, v_out, t_p_out, t_v_out,
+                                        pr, samples, t_samples, err, err_jvp, stream, &ld);
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)
 int dhts_micro_step_fwd(const dhts_micro_desc *d,

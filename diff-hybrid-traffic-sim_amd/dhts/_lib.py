@@ -148,6 +148,9 @@ SIGNATURES = {
     "dhts_micro_rollout_fwd_ckpt_samples": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 9 + [C.c_int, C.c_int] + [_P] * 3),
     "dhts_micro_rollout_bwd_ckpt_samples": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 7 + [C.c_int, C.c_int] + [_P] * 7),
     "dhts_micro_rollout_fwd_jvp_samples": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 14 + [C.c_int, C.c_int] + [_P] * 5),
+    "dhts_micro_rollout_fwd_ckpt_lead": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 10 + [C.c_int, C.c_int] + [_P] * 3),
+    "dhts_micro_rollout_bwd_ckpt_lead": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 8 + [C.c_int, C.c_int] + [_P] * 7),
+    "dhts_micro_rollout_fwd_jvp_lead": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 15 + [C.c_int, C.c_int] + [_P] * 5),
     "dhts_micro_step_fwd": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor_head": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),

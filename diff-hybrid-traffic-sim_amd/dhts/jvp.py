@@ -121,11 +121,12 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
         return primal + (readings,), (t_rT, t_yT, t_uT, t_readings)
 
 
-def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head):
+def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head, t_lead=None, T=0):
     """Shape checks of dhts.micro_rollout_jvp's tangents (ValueError, before anything touches a device).  Returns K."""
-    given = [(n, t) for n, t in (("t_p0", t_p0), ("t_v0", t_v0), ("t_params", t_params), ("t_head", t_head)) if t is not None]
+    given = [(n, t) for n, t in (("t_p0", t_p0), ("t_v0", t_v0), ("t_params", t_params), ("t_head", t_head), ("t_lead", t_lead))
+             if t is not None]
     if not given:
-        raise ValueError("micro_rollout_jvp needs at least one of t_p0, t_v0, t_params, t_head")
+        raise ValueError("micro_rollout_jvp needs at least one of t_p0, t_v0, t_params, t_head, t_lead")
     if p0.dim() != 2:
         raise ValueError("p0 must be [L][V]")
     L, V = p0.shape
@@ -133,7 +134,7 @@ def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head):
         if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] < 1:
             raise ValueError("%s must be a tensor with a leading direction axis K >= 1" % n)
     K = int(given[0][1].shape[0])
-    want = dict(t_p0=(K, L, V), t_v0=(K, L, V), t_params=(K, 6, L, V), t_head=(K, L, 2))
+    want = dict(t_p0=(K, L, V), t_v0=(K, L, V), t_params=(K, 6, L, V), t_head=(K, L, 2), t_lead=(K, int(T), L, 2))
     for n, t in given:
         if tuple(t.shape) != want[n]:
             raise ValueError("%s must have shape %s (got %s): all tangents share K = %d" % (n, want[n], tuple(t.shape), K))
@@ -141,7 +142,7 @@ def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head):
 
 
 def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_params=None, t_head=None, count=None, want_hist=False,
-                      check_faults=True, fused=False, probes=None, every=1):
+                      check_faults=True, fused=False, probes=None, every=1, lead=None, lead_length=None, t_lead=None):
     """dhts.micro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((pT, vT[, hist]), (t_pT, t_vT[, t_hist])).  The primal outputs are those of dhts.micro_rollout(p0, v0, params, head, T, dt,
@@ -158,8 +159,18 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
     returns ((pT, vT, samples), (t_pT, t_vT, t_samples)): samples [T // every][L][2][P] and t_samples [K][T // every][L][2][P], row j
     = slot probes[i] after step (j + 1) every - 1, slots at or beyond count exactly 0 in both.  fused=True writes them from the kernel
     (dhts_micro_rollout_fwd_jvp_samples) and nothing of size T x V is allocated; with fused=False, the taped path, the samples are cut
-    out of a dense history: ask for fused=True when memory matters."""
+    out of a dense history: ask for fused=True when memory matters.
+
+    lead / lead_length / t_lead: as dhts.micro_rollout's `lead` (the head vehicle follows a recorded leader; `head` and t_head must be
+    None), with t_lead float32 [K][T][L][2] the leader's tangents per direction (None: zero).  It lives on the fused path only:
+    fused=True is required, want_hist is not accepted; t_lead without lead, or t_head together with lead, is a ValueError.  Without
+    probes / every the call returns ((pT, vT), (t_pT, t_vT))."""
     T = int(T)
+    if lead is None and (t_lead is not None or lead_length is not None):
+        raise ValueError("t_lead and lead_length need lead")
+    if lead is not None:
+        return _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t_head, count, want_hist, check_faults, fused,
+                                       probes, every, lead, lead_length, t_lead)
     K = _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head)
     L, V = p0.shape
     sampling = ops.micro_sampling(probes, every, V, want_hist)
@@ -224,3 +235,55 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
     if want_hist:
         return (pT, vT, hist), (t_pT, t_vT, t_hist)
     return (pT, vT), (t_pT, t_vT)
+
+
+def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t_head, count, want_hist, check_faults, fused, probes, every,
+                            lead, lead_length, t_lead):
+    """dhts.micro_rollout_jvp with a recorded leader: every ValueError first, then the kLead form of the fused kernel."""
+    if head is not None or t_head is not None:
+        raise ValueError("head and t_head must be None when lead is given: the head vehicle follows `lead`, no head gap exists")
+    if not fused:
+        raise ValueError("lead lives on the tape-free path only: pass fused=True")
+    if want_hist:
+        raise ValueError("lead does not take want_hist: the dense history is the sampled form, probes=range(V) with every=1")
+    K = _micro_jvp_tangents(p0, t_p0, t_v0, t_params, None, t_lead, T)
+    L, V = p0.shape
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    if not isinstance(lead, torch.Tensor) or lead.dtype != torch.float32 or tuple(lead.shape) != (T, L, 2):
+        raise ValueError("lead must be a float32 tensor of shape (T, L, 2) = (%d, %d, 2)" % (T, L))
+    if lead_length is not None and (not isinstance(lead_length, torch.Tensor) or lead_length.dtype != torch.float64
+                                    or tuple(lead_length.shape) != (L,)):
+        raise ValueError("lead_length must be None or a float64 tensor of shape (L,) = (%d,)" % L)
+    if tuple(v0.shape) != (L, V) or tuple(params.shape) != (6, L, V):
+        raise ValueError("v0 must have the shape of p0, params shape (6, %d, %d)" % (L, V))
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    sampling = ops.micro_sampling(probes, every, V, False)
+    desc = ops.micro_desc(L, V, dt)
+    with torch.no_grad():
+        p0c, v0c = ops._f32c(p0.detach(), "p0"), ops._f32c(v0.detach(), "v0")
+        dev = p0c.device
+
+        def tan(t, shape, dtype):
+            if t is None:
+                return torch.zeros(shape, dtype=dtype, device=dev)
+            return t.detach().to(device=dev, dtype=dtype).contiguous()
+
+        tp, tv = tan(t_p0, (K, L, V), torch.float32), tan(t_v0, (K, L, V), torch.float32)
+        tl = None if t_lead is None else tan(t_lead, (K, T, L, 2), torch.float32)
+        tq = None if t_params is None else tan(t_params, (K, 6, L, V), torch.float64)
+        ll = None if lead_length is None else lead_length.detach().to(device=dev).contiguous()
+        slots, ev = sampling if sampling is not None else (None, 1)
+        if isinstance(slots, list):
+            slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
+        prim, tang = ops.micro_rollout_fwd_jvp_lead(desc, T, p0c, v0c, params.detach(), ops._f32c(lead.detach(), "lead"), tp, tv, slots, ev,
+                                                    lead_length=ll, count=count, t_lead=tl, t_params=tq, observe=sampling is not None,
+                                                    err=err, err_jvp=err_jvp)
+        if check_faults:                 # the forward's record first (a collision is printed and tolerated), then the tangents'
+            ops.raise_on_fault(err)
+            ops.raise_on_fault(err_jvp)
+    if sampling is None:
+        return prim[:2], tang[:2]
+    return prim, tang

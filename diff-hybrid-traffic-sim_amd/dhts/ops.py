@@ -1162,6 +1162,129 @@ def micro_rollout_fwd_jvp_samples(desc, T, p, v, params, head, t_p, t_v, probes,
     return (state[0], state[1], samples), (state[2], state[3], t_samples)
 
 
+# ---- a recorded leader on the two tape-free paths (dhts_micro_rollout_*_lead) ------------------------------------------------------------
+def _lead_args(desc, T, lead, lead_length):
+    """The raw wrappers' checks of (lead, lead_length): lead a contiguous float32 [T][L][2], lead_length None or a contiguous float64 [L]."""
+    L = desc.n_lanes
+    if int(T) < 0:
+        raise ValueError("T must be >= 0")
+    if (not isinstance(lead, torch.Tensor) or lead.dtype != torch.float32 or tuple(lead.shape) != (int(T), L, 2)
+            or not lead.is_contiguous()):
+        raise ValueError("lead must be a contiguous float32 tensor of shape (%d, %d, 2)" % (int(T), L))
+    if lead_length is not None and (not isinstance(lead_length, torch.Tensor) or lead_length.dtype != torch.float64
+                                    or tuple(lead_length.shape) != (L,) or not lead_length.is_contiguous()):
+        raise ValueError("lead_length must be None or a contiguous float64 tensor of shape (%d,)" % L)
+
+
+def _lead_state_args(desc, p, v, params, count):
+    L, V = desc.n_lanes, desc.capacity
+    p, v = _f32c(p, "p"), _f32c(v, "v")
+    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
+        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
+    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
+        raise ValueError("params must be float64 [6][L][V]")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
+        raise ValueError("count must be int32 [L]")
+    return p, v, params.contiguous()
+
+
+def micro_rollout_fwd_ckpt_lead(desc, T, p, v, params, lead, ckpt, probes=None, every=1, lead_length=None, count=None, segment=0,
+                                samples=None, observe=True, err=None, out=None):
+    """micro_rollout_fwd_ckpt_samples whose head vehicle follows a recorded leader (dhts_micro_rollout_fwd_ckpt_lead, include/dhts.h):
+    lead float32 [T][L][2] = (p, v) of the vehicle in front of each lane's head as the head sees it in step t; lead_length float64 [L]
+    or None (the head's own length).  observe=False: no samples at all (the kernel is handed NULL; the returned samples is None);
+    probes=None, every=1 is the dense history.  Returns (pT, vT, samples)."""
+    L = desc.n_lanes
+    rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    _lead_args(desc, T, lead, lead_length)
+    micro_ckpt_plan(desc, T, False, segment)
+    if ckpt is not None and (ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous()):
+        raise ValueError("ckpt must be None or a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
+    p, v, params = _lead_state_args(desc, p, v, params, count)
+    samples = _samples_buffer("samples", samples, (rows, L, 2, n), p.device) if observe else None
+    if out is None:
+        out = (torch.empty_like(p), torch.empty_like(v))
+    check(_lib.lib().dhts_micro_rollout_fwd_ckpt_lead(C.byref(desc), int(T), int(segment), _ptr(p), _ptr(v), _ptr(count), _ptr(params),
+                                                      _ptr(lead) if lead.numel() else None, _ptr(lead_length), _ptr(out[0]), _ptr(out[1]),
+                                                      _ptr(ckpt) if ckpt is not None and ckpt.numel() else None, _ptr(probes), n_probes,
+                                                      every, _ptr(samples) if samples is not None and samples.numel() else None,
+                                                      _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt_lead")
+    return out[0], out[1], samples
+
+
+def micro_rollout_bwd_ckpt_lead(desc, T, ckpt, params, lead, g_p, g_v, probes=None, every=1, g_samples=None, lead_length=None, count=None,
+                                segment=0, err=None, out=None, g_lead=None, g_params=None):
+    """The reverse sweep of micro_rollout_fwd_ckpt_lead (dhts_micro_rollout_bwd_ckpt_lead) -> (g_p0, g_v0, g_lead): g_lead float32
+    [T][L][2], row t the cotangent of lead[t] (every row written; exactly 0 for a lane without a vehicle); nothing is folded into the
+    head.  g_samples=None: nothing was observed.  lead, lead_length, probes, every, count, segment: the forward's."""
+    L, V = desc.n_lanes, desc.capacity
+    rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    _lead_args(desc, T, lead, lead_length)
+    micro_ckpt_plan(desc, T, g_params is not None, segment)
+    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
+        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
+    for name, t in (("params", params), ("g_params", g_params)):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
+    g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
+    if g_samples is not None:
+        g_samples = _samples_buffer("g_samples", g_samples, (rows, L, 2, n), g_p.device)
+    if out is None:
+        out = (torch.empty_like(g_p), torch.empty_like(g_v))
+    if g_lead is None:
+        g_lead = torch.empty(int(T), L, 2, dtype=torch.float32, device=g_p.device)
+    elif g_lead.dtype != torch.float32 or tuple(g_lead.shape) != (int(T), L, 2) or not g_lead.is_contiguous():
+        raise ValueError("g_lead must be a contiguous float32 tensor of shape (%d, %d, 2)" % (int(T), L))
+    check(_lib.lib().dhts_micro_rollout_bwd_ckpt_lead(C.byref(desc), int(T), int(segment), _ptr(ckpt) if ckpt.numel() else None, _ptr(count),
+                                                      _ptr(params), _ptr(lead) if lead.numel() else None, _ptr(lead_length), _ptr(g_p),
+                                                      _ptr(g_v), _ptr(probes), n_probes, every,
+                                                      _ptr(g_samples) if g_samples is not None and g_samples.numel() else None,
+                                                      _ptr(out[0]), _ptr(out[1]), _ptr(g_lead) if g_lead.numel() else None, _ptr(g_params),
+                                                      _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_lead")
+    return out[0], out[1], g_lead
+
+
+def micro_rollout_fwd_jvp_lead(desc, T, p, v, params, lead, t_p, t_v, probes=None, every=1, lead_length=None, count=None, t_lead=None,
+                               t_params=None, observe=True, err=None, err_jvp=None, out=None):
+    """micro_rollout_fwd_jvp_samples whose head vehicle follows a recorded leader (dhts_micro_rollout_fwd_jvp_lead): lead, lead_length
+    as micro_rollout_fwd_ckpt_lead; t_lead float32 [K][T][L][2] or None (zero).  observe=False: no sample arrays (both returned as
+    None).  Returns ((pT, vT, samples), (t_pT, t_vT, t_samples))."""
+    L, V, T = desc.n_lanes, desc.capacity, int(T)
+    rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    _lead_args(desc, T, lead, lead_length)
+    p, v, params = _lead_state_args(desc, p, v, params, count)
+    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
+        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
+    K = int(t_p.shape[0])
+    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
+    if t_lead is not None and (t_lead.dtype != torch.float32 or tuple(t_lead.shape) != (K, T, L, 2) or not t_lead.is_contiguous()):
+        raise ValueError("t_lead must be a contiguous float32 [%d][%d][%d][2]" % (K, T, L))
+    if t_params is not None and (t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous()):
+        raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
+    out = tuple(out) if out is not None else ()
+    if len(out) not in (0, 4, 6) or (len(out) == 6 and not observe):
+        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, samples, t_samples])")
+    samples = t_samples = None
+    if observe:
+        samples = _samples_buffer("samples", out[4] if len(out) == 6 else None, (rows, L, 2, n), p.device)
+        t_samples = _samples_buffer("t_samples", out[5] if len(out) == 6 else None, (K, rows, L, 2, n), p.device)
+    if out:
+        state = out[:4]
+        for name, t, like in zip(("p_out", "v_out", "t_p_out", "t_v_out"), state, (p, v, t_p, t_v)):
+            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
+    else:
+        state = (torch.empty_like(p), torch.empty_like(v), torch.empty_like(t_p), torch.empty_like(t_v))
+    sptr = [_ptr(s) if s is not None and s.numel() else None for s in (samples, t_samples)]
+    check(_lib.lib().dhts_micro_rollout_fwd_jvp_lead(C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params),
+                                                     _ptr(lead) if lead.numel() else None, _ptr(lead_length), _ptr(t_p), _ptr(t_v),
+                                                     _ptr(t_lead) if t_lead is not None and t_lead.numel() else None, _ptr(t_params),
+                                                     _ptr(state[0]), _ptr(state[1]), _ptr(state[2]), _ptr(state[3]), _ptr(probes), n_probes,
+                                                     every, sptr[0], sptr[1], _ptr(err), _ptr(err_jvp), _stream()),
+          "dhts_micro_rollout_fwd_jvp_lead")
+    return (state[0], state[1], samples), (state[2], state[3], t_samples)
+
+
 def _probe_slots(probes, V):
     """The `probes` argument of dhts.micro_rollout / micro_rollout_jvp, checked as macro_rollout checks `detectors` -> the CUDA int32
     tensor as it is (not validated), or the list of slots (non-empty, strictly ascending, in [0, V); ValueError otherwise)."""
@@ -1392,7 +1515,76 @@ class MicroRolloutSamples(torch.autograd.Function):
         return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None, None, None
 
 
-def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None, probes=None, every=1):
+class MicroRolloutLead(torch.autograd.Function):
+    """MicroRolloutSamples whose head vehicle follows a recorded leader: (p0, v0 [L][V], lead [T][L][2]) -> (pT, vT[, samples]).  No head
+    gap exists; `lead` is differentiable, its gradient is the per-step cotangent of the slot in front of the head
+    (dhts_micro_rollout_fwd_ckpt_lead / _bwd_ckpt_lead).  observe False: no samples are written or returned."""
+
+    @staticmethod
+    def forward(ctx, p0, v0, params, lead, lead_length, count, T, dt, check_faults, checkpoint, probes, every, observe):
+        L, V = p0.shape
+        desc = micro_desc(L, V, dt)
+        want_params = params.requires_grad
+        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, T, want_params, sg))
+        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
+        dev = p0c.device
+        need_grad = p0.requires_grad or v0.requires_grad or lead.requires_grad or want_params
+        ctx.params, ctx.lead = params.detach().contiguous(), _f32c(lead.detach(), "lead")
+        ctx.lead_length = None if lead_length is None else lead_length.detach().to(device=dev, dtype=torch.float64).contiguous()
+        # everything the pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand over)
+        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
+        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
+        ctx.g_lead = torch.empty(T, L, 2, dtype=torch.float32, device=dev) if need_grad else None
+        err = new_error_record(dev)
+        pT, vT, samples = micro_rollout_fwd_ckpt_lead(desc, T, p0c, v0c, ctx.params, ctx.lead, ctx.ckpt, probes, every,
+                                                      lead_length=ctx.lead_length, count=count, segment=segment, observe=observe, err=err)
+        if check_faults:                 # a collision is printed like the reference does, and tolerated
+            raise_on_fault(err)
+        ctx.desc, ctx.T, ctx.count, ctx.check_faults, ctx.segment, ctx.probes, ctx.every = desc, T, count, check_faults, segment, probes, every
+        ctx.observe = observe
+        ctx.err_bwd = new_error_record(dev) if need_grad else None
+        return (pT, vT, samples) if observe else (pT, vT)
+
+    @staticmethod
+    def backward(ctx, g_pT, g_vT, g_samples=None):
+        desc, T = ctx.desc, ctx.T
+        dev = ctx.err_bwd.device
+        L, V = desc.n_lanes, desc.capacity
+        g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
+        g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
+        gs = g_samples.contiguous() if (ctx.observe and g_samples is not None) else None      # (None: nothing enters at the samples)
+        err = ctx.err_bwd
+        err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
+        g_p0, g_v0, g_lead = micro_rollout_bwd_ckpt_lead(desc, T, ctx.ckpt, ctx.params, ctx.lead, g_p, g_v, ctx.probes, ctx.every, gs,
+                                                         lead_length=ctx.lead_length, count=ctx.count, segment=ctx.segment, err=err,
+                                                         g_lead=ctx.g_lead, g_params=ctx.g_params)
+        if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
+            MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
+        return (g_p0, g_v0, ctx.g_params, g_lead) + (None,) * 9
+
+
+def _micro_lead_checks(p0, head, T, lead, lead_length, want_hist, checkpoint):
+    """Every ValueError of dhts.micro_rollout's `lead` / `lead_length`, raised before anything touches a device."""
+    if head is not None:
+        raise ValueError("head must be None when lead is given: the head vehicle follows `lead`, no head gap exists")
+    if want_hist:
+        raise ValueError("lead does not take want_hist: the dense history is the sampled form, probes=range(V) with every=1")
+    if checkpoint is None or checkpoint is False:
+        raise ValueError("lead lives on the tape-free path only: pass checkpoint=True (or a segment length)")
+    if p0.dim() != 2:
+        raise ValueError("p0 must be [L][V]")
+    L = int(p0.shape[0])
+    if not isinstance(lead, torch.Tensor) or lead.dtype != torch.float32 or tuple(lead.shape) != (int(T), L, 2):
+        raise ValueError("lead must be a float32 tensor of shape (T, L, 2) = (%d, %d, 2)" % (int(T), L))
+    if lead_length is not None and (not isinstance(lead_length, torch.Tensor) or lead_length.dtype != torch.float64
+                                    or tuple(lead_length.shape) != (L,)):
+        raise ValueError("lead_length must be None or a float64 tensor of shape (L,) = (%d,)" % L)
+    if lead_length is not None and lead_length.requires_grad:
+        raise ValueError("lead_length is not differentiable: pass it detached")
+
+
+def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None, probes=None, every=1,
+                  lead=None, lead_length=None):
     """MicroRollout.  checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape).
 
     probes / every: observe the trajectory at a few vehicle slots every so many steps.  Sampling is on when probes is not None or
@@ -1404,7 +1596,26 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
     is and NOT validated: its entries must be distinct, and the kernels never form an address from one outside [0, V) -- that column
     stays 0.  every: an int >= 1.  Not together with want_hist (ValueError): the history holds every vehicle and step.
     With checkpoint= the kernels write and read samples directly and nothing of size T x V is allocated (MicroRolloutSamples).  On the
-    taped path (checkpoint=None) the samples are cut out of a dense history: ask for checkpoint= when memory matters."""
+    taped path (checkpoint=None) the samples are cut out of a dense history: ask for checkpoint= when memory matters.
+
+    lead / lead_length: let the head vehicle of every lane follow a recorded leader instead of a constant head gap.  lead float32
+    [T][L][2]: lead[t][l] = (p, v) of the vehicle in front of lane l's head as the head sees it in step t; the head is then an ordinary
+    follower (the same gap, collision and clamp rules).  lead_length float64 [L] or None = the head's own length; not differentiable.
+    `head` must be None.  lead may require grad: its gradient [T][L][2] is the per-step cotangent of that leader.  It lives on the
+    checkpointed path only: checkpoint=True or a segment is required (ValueError otherwise), want_hist is not accepted (ValueError: the
+    dense history is probes=range(V), every=1), probes / every work as above; without them the call returns (pT, vT)."""
+    if lead is not None or lead_length is not None:
+        if lead is None:
+            raise ValueError("lead_length needs lead")
+        _micro_lead_checks(p0, head, T, lead, lead_length, want_hist, checkpoint)
+        sampling = micro_sampling(probes, every, int(p0.shape[-1]), False)
+        desc = micro_desc(int(p0.shape[0]), int(p0.shape[1]), float(dt))
+        _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, int(T), params.requires_grad, sg))
+        slots, ev = sampling if sampling is not None else (None, 1)
+        if isinstance(slots, list):
+            slots = torch.tensor(slots, dtype=torch.int32, device=p0.device)
+        return MicroRolloutLead.apply(p0, v0, params, lead, lead_length, count, int(T), float(dt), bool(check_faults), checkpoint, slots, ev,
+                                      sampling is not None)
     sampling = micro_sampling(probes, every, int(p0.shape[-1]), want_hist)
     if sampling is None:
         return MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), want_hist, bool(check_faults), checkpoint)

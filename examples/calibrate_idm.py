@@ -16,6 +16,10 @@ state every S steps (the library's own S when none is given) instead of 20 B of 
 --observe P,E: floating-car data instead of a dense history -- the truth and the fit both observe P evenly spaced probe slots of every
 lane every E-th step (dhts.micro_rollout(probes=, every=) / micro_rollout_jvp(probes=, every=)); residuals and Jacobian are then
 T // E x L x 2 x P numbers, and with --checkpoint / --fused nothing of size T x V is allocated.  Works with every method and path.
+--leader: "leader trajectory given, followers observed", the form of every real car-following data set -- the ground truth is a
+rollout of n_vehicle + 1 vehicles per lane on the existing path; the head vehicle's recorded trajectory becomes `lead`
+(dhts.micro_rollout(lead=, lead_length=) / micro_rollout_jvp(lead=, ...)), and the n_vehicle followers behind it are fitted.  A
+recorded leader lives on the tape-free paths: with --checkpoint (Adam) or --method lm --fused, each with or without --observe.
 Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt (lm: .../lm/trial_k.txt), like the other examples.
 """
 import argparse
@@ -50,6 +54,8 @@ def main():
                     help="Adam: reverse mode from checkpoints every S steps (no S: the library's choice) instead of the tapes")
     ap.add_argument("--observe", default=None, metavar="P,E",
                     help="observe P evenly spaced probe slots per lane every E-th step instead of every vehicle at every step")
+    ap.add_argument("--leader", action="store_true",
+                    help="fit the followers of a recorded leader: the truth has n_vehicle + 1 vehicles, its head's trajectory is given")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
@@ -57,6 +63,8 @@ def main():
         ap.error("--fused belongs to --method lm")
     if args.checkpoint is not None and args.method != "adam":
         ap.error("--checkpoint belongs to --method adam")
+    if args.leader and not (args.fused or args.checkpoint is not None):
+        ap.error("--leader lives on the tape-free paths: add --checkpoint (Adam) or --method lm --fused")
     sampled = {}                                  # the arguments of a sampled call; none: the dense history
     if args.observe is not None:
         try:
@@ -78,8 +86,14 @@ def main():
     length = truth[5:6]
     head = th.tensor([[1000.0, 0.0]], dtype=th.float64, device=dev).expand(L, 2).contiguous()
 
+    follow = {}                                   # --leader: the recorded leader of a trial (lead, lead_length), made with its truth
+    # with a leader the dense history is the sampled form of every slot at every step
+    observe = sampled or dict(probes=list(range(V)), every=1)
+
     def rollout(theta):
         params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+        if follow:
+            return dhts.micro_rollout(p0, v0, params, None, T, dt, checkpoint=True if args.fused else args.checkpoint, **follow, **observe)[2]
         if sampled:      # (the fused fit's loss evaluations: the tape-free forward too, no grad is asked of it)
             return dhts.micro_rollout(p0, v0, params, head, T, dt, checkpoint=True if args.fused else args.checkpoint, **sampled)[2]
         return dhts.micro_rollout(p0, v0, params, head, T, dt, want_hist=True, checkpoint=args.checkpoint)[2]
@@ -87,8 +101,18 @@ def main():
     for trial in range(args.n_trial):
         p0 = (th.arange(V, device=dev) * 4.0 * ln)[None, :] + th.rand(L, V, device=dev) * 2.0 * ln
         v0 = th.lerp(th.tensor(0.3 * um, device=dev), th.tensor(0.7 * um, device=dev), th.rand(L, V, device=dev))
-        with th.no_grad():
-            observed = rollout(truth[:5])
+        if args.leader:
+            # the truth: V + 1 vehicles on the existing path; the head's (p, v) before every step is the record the fit is given
+            p_all = th.cat([p0, p0[:, -1:] + 4.0 * ln + th.rand(L, 1, device=dev) * 2.0 * ln], 1)
+            v_all = th.cat([v0, th.lerp(th.tensor(0.3 * um, device=dev), th.tensor(0.7 * um, device=dev), th.rand(L, 1, device=dev))], 1)
+            with th.no_grad():
+                full = dhts.micro_rollout(p_all, v_all, truth[:, None, None].expand(6, L, V + 1), head, T, dt, want_hist=True)[2]
+            first = th.stack([p_all[:, V], v_all[:, V]], -1)[None]
+            follow = dict(lead=th.cat([first, full[:T - 1, :, :, V]], 0).contiguous(), lead_length=length.expand(L).contiguous())
+            observed = full[observe["every"] - 1::observe["every"]][..., th.tensor(observe["probes"], device=dev)].contiguous()
+        else:
+            with th.no_grad():
+                observed = rollout(truth[:5])
         guess = truth[:5] * (1.0 + 0.2 * (2.0 * th.rand(5, dtype=th.float64, device=dev) - 1.0))
         lo, hi = 0.5 * guess, 1.5 * guess
         lines = []
@@ -100,8 +124,12 @@ def main():
                 unit[i, i] = 1.0
             for ep in range(args.n_episode):
                 params = th.cat([theta, length])[:, None, None].expand(6, L, V)
-                (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, head, T, dt, t_params=unit, want_hist=not sampled,
-                                                                      fused=args.fused, **sampled)
+                if follow:
+                    (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, None, T, dt, t_params=unit, fused=True, **follow,
+                                                                          **observe)
+                else:
+                    (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, head, T, dt, t_params=unit, want_hist=not sampled,
+                                                                          fused=args.fused, **sampled)
                 res = (hist - observed).reshape(-1).double()
                 jac = t_hist.reshape(5, -1).double()                        # [5][T L 2 V] (observed: [5][T // E L 2 P]): column i of the Jacobian
                 loss = (res ** 2).mean()

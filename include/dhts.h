@@ -649,6 +649,48 @@ int dhts_micro_rollout_fwd_jvp_samples(const dhts_micro_desc *d, int T, int n_di
                                        const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
                                        dhts_error *err_jvp, void *stream);
 
+/*
+ * A RECORDED LEADER on the two tape-free paths: the lane's head vehicle (slot count - 1) follows a prescribed vehicle that moves, as
+ * every other vehicle follows the slot in front of it.  The three entry points are the _samples ones above with head / g_head / t_head
+ * replaced by
+ *   lead          [T][L][2] float32: (p, v) of the vehicle in front of lane l's head AS THE HEAD SEES IT IN step t -- what S[k + 1] is
+ *                 to follower k.  No virtual leader and no head gap exist: the head forms
+ *                     dp = fabs((double)lead_p - p) - half_len        dv = v - (double)lead_v
+ *                 calls the same idm_step, and the same collision / clamp rules and live-gap test (gap >= 1e-5) apply to it.
+ *   lead_length   [L] DOUBLE or NULL: half_len = (lead_length[l] + the head's own length) / 2; NULL = the head's own length for both,
+ *                 the value the head's half_len has in the siblings.  Not differentiated.
+ *   g_lead        [T][L][2] float32, written: row t = the cotangent of lead[t], i.e. the (C1p[n], C1v[n]) the sweep forms for the slot
+ *                 in front of the head at step t.  Nothing is folded back into the head.  EVERY row is written; rows of a lane without
+ *                 a vehicle are exactly 0.
+ *   t_lead        [K][T][L][2] float32 or NULL (zero): the tangents of lead per direction.  The head's length tangent carries its own
+ *                 share only: -(t_len / 2) where the gap is live; g_params[5] of the head likewise.
+ * and samples / g_samples / t_samples may be NULL: nothing is observed (samples and t_samples of _fwd_jvp_lead: both or neither).  A
+ * dense history is probes = NULL, every = 1.  Otherwise their siblings' arguments, arithmetic, fault records and bits:
+ *   dhts_micro_rollout_fwd_ckpt_lead   MicroLane.forward (_micro_lane.py:131-214) with the head's leader given per step, as
+ *       dhts_micro_rollout_fwd_ckpt_samples; DHTS_FAULT_COLLISION also where the head meets a leader behind it (gap < 0).
+ *   dhts_micro_rollout_bwd_ckpt_lead   the sweep of dMicroForwardLayer.backward (dmicro_lane.py:271-298) with the leader slot of
+ *       dMicroLane.vectorize_input (:130-153) returned per step instead of folded, as dhts_micro_rollout_bwd_ckpt_samples.
+ *   dhts_micro_rollout_fwd_jvp_lead    forward mode of the same rollout, as dhts_micro_rollout_fwd_jvp_samples.
+ * Exactly 0: g_p_out, g_v_out, g_params and t_p_out, t_v_out, t_samples at slots at or beyond count; g_lead rows of an empty lane.
+ * DHTS_E_INVALID, nothing dereferenced and nothing launched: whatever the sibling rejects (but NULL sample arrays), a NULL lead with
+ * T > 0, a NULL g_lead with T > 0, one of samples / t_samples NULL and the other not.
+ * Blocks, segments and dynamic LDS are the siblings': dhts_micro_ckpt_plan and dhts_micro_fwd_jvp_plan hold for these forms too (the
+ * leader's state travels in the slot V of the hand-over arrays that the virtual leader's tangents use in the siblings).
+ */
+int dhts_micro_rollout_fwd_ckpt_lead(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                     const double *params, const float *lead, const double *lead_length, float *p_out, float *v_out,
+                                     void *ckpt, const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err,
+                                     void *stream);
+int dhts_micro_rollout_bwd_ckpt_lead(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                     const double *params, const float *lead, const double *lead_length, const float *g_p, const float *g_v,
+                                     const int32_t *probes, int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out,
+                                     float *g_lead, double *g_params, dhts_error *err, void *stream);
+int dhts_micro_rollout_fwd_jvp_lead(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                    const double *params, const float *lead, const double *lead_length, const float *t_p, const float *t_v,
+                                    const float *t_lead, const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                    const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
+                                    dhts_error *err_jvp, void *stream);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
