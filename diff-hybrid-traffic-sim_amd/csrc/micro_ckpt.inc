@@ -30,8 +30,18 @@
 // t + 1 there during step t, the row after that in flight in registers; the reverse sweep stores C1[n], the cotangent of the slot in
 // front of the head, as row t of g_lead [T][L][2] instead of folding it into the head.  A NULL samples / g_samples: nothing is observed.
 // kLead = false is the code the sampled forms were before (profiles/micro_lead_resources*.txt).
+//
+// A third pass, DHTS_MICRO_SAMPLES 2, gives the TARGET forms (kTarget; dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target),
+// micro_rollout_ckpt_fwd_target_kernel<kLead> / _bwd_target_kernel<kParams, kLead>: the trajectory-fit loss inside the pair.  They
+// take target [T][L][2][V] float32 (hist's indexing: the observed (p, v) after step t; NaN = not observed) where the first pair takes
+// hist / g_hist, and neither array exists.  The forward sums, per thread and in step order, the squares (in double) of the float32
+// residuals x - target into two doubles, reduces them over the workgroup in a fixed order through the LDS the step loop is done with
+// and writes sse [L][2] double; the reverse replay forms the finished cotangent pair (float)(2 g_sse[l][c]) * (x - target) from the
+// post-step state it has just recomputed and keeps it in two more planes of R, from where the sweep adds it where g_hist is added.
+// Rows of target travel in registers ahead of the step that uses them, as the lead rows do.  kTarget = false (passes 0 and 1) is the
+// code the kernels were before (profiles/micro_target_resources*.txt).
 
-#if !DHTS_MICRO_SAMPLES
+#if DHTS_MICRO_SAMPLES == 0
 // dynamic LDS of the two kernels: the plan (micro_plan) and the kernels' own carving read these
 __host__ __device__ inline size_t micro_ckpt_fwd_lds_bytes(int V) { return sizeof(float2) * 2 * (size_t)(V + 1); }
 // reverse, fixed part: the replay's state hand-over S[2][V + 1] and the four cotangent arrays of V + 2 floats
@@ -42,6 +52,19 @@ __host__ __device__ inline size_t micro_ckpt_bwd_step_bytes(int V, bool params) 
 }
 __host__ __device__ inline size_t micro_ckpt_bwd_lds_bytes(int V, int S, bool params) {
     return micro_ckpt_bwd_fixed_bytes(V) + (size_t)S * micro_ckpt_bwd_step_bytes(V, params);
+}
+// the target forms: two more planes of R per step, the finished cotangent pair of the step; the forward reduces in S (16 V <= 16 (V + 1))
+__host__ __device__ inline size_t micro_ckpt_bwd_target_step_bytes(int V, bool params) {
+    return micro_ckpt_bwd_step_bytes(V, params) + sizeof(float) * 2 * (size_t)V;
+}
+__host__ __device__ inline size_t micro_ckpt_bwd_target_lds_bytes(int V, int S, bool params) {
+    return micro_ckpt_bwd_fixed_bytes(V) + (size_t)S * micro_ckpt_bwd_target_step_bytes(V, params);
+}
+// one observed entry pair of the forward: hist - observed in float32, squared and summed in double; a NaN entry is not observed
+__device__ inline void micro_target_add(float p, float v, float tp, float tv, double &ap, double &av) {
+    const float rp = p - tp, rv = v - tv;
+    if (tp == tp) ap += (double)rp * (double)rp;
+    if (tv == tv) av += (double)rv * (double)rv;
 }
 #endif
 
@@ -56,15 +79,31 @@ __host__ __device__ inline size_t micro_ckpt_bwd_lds_bytes(int V, int S, bool pa
 // slots after step (j + 1) every - 1 -- a thread finds its slot's column among the probes once, before the step loop, counts the steps
 // down to the next sampled one and moves a running pointer from row to row; a slot at or beyond count stores nothing.  ckpt may then
 // be NULL: no checkpoint is kept (a forward that nobody differentiates).
-#if !DHTS_MICRO_SAMPLES
+// kTarget (micro_rollout_ckpt_fwd_target_kernel): no hist and no samples; the thread of a live slot holds the next two rows of its
+// column of target in (tp1, tv1), (tp2, tv2) and adds the squared residuals of observed entries to (ap, av); sse [L][2] is written by
+// thread 0 after the block reduction (NaN where the block is smaller than the lane).  ckpt may be NULL as with kSamp.
+#if DHTS_MICRO_SAMPLES == 0
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
     int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, float *__restrict__ hist, dhts_error *err) {
-    constexpr bool kSamp = false, kLead = false;
+    constexpr bool kSamp = false, kLead = false, kTarget = false;
     const MicroProbes pr = {};
     float *const samples = nullptr;
     const MicroLead ld = {};
+    const float *const target = nullptr;
+    double *const sse = nullptr;
+#elif DHTS_MICRO_SAMPLES == 2
+template <bool kLead>
+__global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_target_kernel(
+    int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
+    const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
+    float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, const float *__restrict__ target,
+    double *__restrict__ sse, dhts_error *err, MicroLead ld) {
+    constexpr bool kSamp = false, kTarget = true;
+    const MicroProbes pr = {};
+    float *const samples = nullptr;
+    float *const hist = nullptr;
 #else
 template <bool kLead>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
@@ -72,8 +111,10 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, MicroProbes pr, float *__restrict__ samples,
     dhts_error *err, MicroLead ld) {
-    constexpr bool kSamp = true;
+    constexpr bool kSamp = true, kTarget = false;
     float *const hist = nullptr;
+    const float *const target = nullptr;
+    double *const sse = nullptr;
 #endif
     extern __shared__ __attribute__((aligned(16))) float lds_ck[];
     const int lane = blockIdx.x;
@@ -95,6 +136,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
         const float nanf_ = __builtin_nanf("");
         for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
         if constexpr (kSamp) { if (!kLead || samples) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_); }
+        if constexpr (kTarget) { if (k == 0) { sse[(size_t)lane * 2] = (double)nanf_; sse[(size_t)lane * 2 + 1] = (double)nanf_; } }
         if (k == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);
         return;
     }
@@ -121,6 +163,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     __syncthreads();
 
     int fault_step = -1;
+    double ap = 0., av = 0.;           // kTarget: this vehicle's squared residuals, summed in step order
     if (T > 0) {
         if (vk) S[k] = make_float2(p, v);
         // kLead: the head's thread owns slot n of S -- row 0 now, row step + 1 during step `step`, the row after that in flight in (lx, ly)
@@ -136,10 +179,24 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
         }
         __syncthreads();
         float2 *ck = ckpt + (size_t)lane * Vp + k;       // this slot of row 0; a row is L Vp entries
-        int next_ck = (kSamp && ckpt == nullptr) ? -1 : 0;
+        int next_ck = ((kSamp || kTarget) && ckpt == nullptr) ? -1 : 0;
         float *sp = nullptr;                             // kSamp: this slot's column of the next row; a row is L 2 n floats
         int cd = 0;                                      // ... and the steps until that row is due
         if constexpr (kSamp) { sp = samples + (size_t)lane * 2 * pr.n + (col < 0 ? 0 : col); cd = pr.every; }
+        // kTarget: this slot's column of the row to load next (a row is L 2 V floats); rows step and step + 1 are in the registers
+        const float *tg = nullptr;
+        float tp1 = 0.f, tv1 = 0.f, tp2 = 0.f, tv2 = 0.f;
+        if constexpr (kTarget) {
+            // (p, v) arrive here, before the first row of target is asked for: left pending across the loop's entry, their loads would
+            // make every step wait for every load issued since (the wait counter is one for all of them, in order)
+            asm volatile("" : "+v"(p), "+v"(v));
+            if (vk) {
+                tg = target + (size_t)lane * 2 * V + k;
+                tp1 = tg[0]; tv1 = tg[V];
+                tg += (size_t)L * 2 * V;
+                if (T > 1) { tp2 = tg[0]; tv2 = tg[V]; }
+            }
+        }
         for (int step = 0; step < T; ++step) {
             const int q = step & 1;
             bool due = false;
@@ -167,6 +224,12 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
                         if (step + 2 < T) { lx = lrow[0]; ly = lrow[1]; }
                     }
                 }
+                if constexpr (kTarget) {
+                    micro_target_add(p, v, tp1, tv1, ap, av);
+                    tp1 = tp2; tv1 = tv2;
+                    tg += (size_t)L * 2 * V;
+                    if (step + 2 < T) { tp2 = tg[0]; tv2 = tg[V]; }
+                }
                 if constexpr (kSamp) { if (due && col >= 0) { sp[0] = p; sp[pr.n] = v; } }
                 else if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
             }
@@ -176,6 +239,20 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     }
     if (k < V) { p_out[base + k] = p; v_out[base + k] = v; }
     if (fault_step >= 0) raise_fault(err, DHTS_FAULT_COLLISION, fault_step, lane, k);
+    if constexpr (kTarget) {
+        // the lane's two sums: a pairwise tree over the slots in a fixed order (no atomics: the same bits every run), in S -- every
+        // access of the step loop lies before a barrier all threads have passed, and V entries of 16 B fit its 2 (V + 1) of 8 B
+        double2 *A = reinterpret_cast<double2 *>(lds_ck);
+        if (k < V) A[k] = make_double2(ap, av);         // (a slot at or beyond count: 0)
+        __syncthreads();
+        int w = 512;
+        while (w >= V) w >>= 1;                          // the largest power of two below V (0 for V = 1)
+        for (; w > 0; w >>= 1) {
+            if (k < w && k + w < V) { const double2 a = A[k], b = A[k + w]; A[k] = make_double2(a.x + b.x, a.y + b.y); }
+            __syncthreads();
+        }
+        if (k == 0) { const double2 a = A[0]; sse[(size_t)lane * 2] = a.x; sse[(size_t)lane * 2 + 1] = a.y; }
+    }
 }
 
 // grid = L workgroups of blockDim.x >= V threads, one vehicle per thread.  Dynamic LDS (micro_ckpt_bwd_lds_bytes):
@@ -193,17 +270,34 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
 // slot adds, and only at a sampled step.  Its rows travel two ROWS ahead in the same four registers (2 every steps: with every = 1
 // the g_hist pipeline), across segment boundaries like the countdown to the next sampled step, which starts at T mod every: the
 // trailing steps have no row.
-#if !DHTS_MICRO_SAMPLES
+// kTarget (micro_rollout_ckpt_bwd_target_kernel): R has five planes per step -- the replay, which holds the post-step (p, v) of step r
+// in registers, adds (float)(2 g_sse[lane][c]) * (x - target) (0 for a NaN entry) as planes 3 and 4, and the sweep adds them where
+// g_hist is added: no global load in the sweep.  The target row of a segment's first step travels like ck, a segment ahead in
+// (t0p, t0v); the rows of its later steps one replay step ahead in (t1p, t1v) -- the lead rows' pipeline, on every live thread.
+#if DHTS_MICRO_SAMPLES == 0
 template <bool kParams>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
     int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, const float *__restrict__ g_hist, float *__restrict__ g_p_out, float *__restrict__ g_v_out,
     double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err) {
-    constexpr bool kSamp = false, kLead = false;
+    constexpr bool kSamp = false, kLead = false, kTarget = false;
     const MicroProbes pr = {};
     const float *const g_samples = nullptr;
     const MicroLead ld = {};
+    const float *const target = nullptr;
+    const double *const g_sse = nullptr;
+#elif DHTS_MICRO_SAMPLES == 2
+template <bool kParams, bool kLead>
+__global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_target_kernel(
+    int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
+    const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
+    const float *__restrict__ g_v_in, const float *__restrict__ target, const double *__restrict__ g_sse, float *__restrict__ g_p_out,
+    float *__restrict__ g_v_out, double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err, MicroLead ld) {
+    constexpr bool kSamp = false, kTarget = true;
+    const MicroProbes pr = {};
+    const float *const g_samples = nullptr;
+    const float *const g_hist = nullptr;
 #else
 template <bool kParams, bool kLead>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
@@ -211,8 +305,10 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, MicroProbes pr, const float *__restrict__ g_samples, float *__restrict__ g_p_out,
     float *__restrict__ g_v_out, double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err, MicroLead ld) {
-    constexpr bool kSamp = true;
+    constexpr bool kSamp = true, kTarget = false;
     const float *const g_hist = nullptr;
+    const float *const target = nullptr;
+    const double *const g_sse = nullptr;
 #endif
     extern __shared__ __attribute__((aligned(16))) float lds_ck[];
     const int lane = blockIdx.x;
@@ -224,6 +320,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
     float *Gp = reinterpret_cast<float *>(X + (kParams ? (size_t)Sg * P1 : 0));
     float *Gv = Gp + P, *C1p = Gp + 2 * P, *C1v = Gp + 3 * P;
     float *R = Gp + 4 * P;
+    constexpr int kPlanes = kTarget ? 5 : 3;            // of R per step
     const size_t base = (size_t)lane * V;
     const size_t plane = (size_t)L * V;
     const int Vp = (V + 63) & ~63;
@@ -303,6 +400,13 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
         }
         // kLead: the head's thread owns slot n of S (and of X): the lead row of a segment's first step travels like ck, a segment
         // ahead in (l0x, l0y); the rows of its later steps one replay step ahead in (l1x, l1y)
+        // kTarget: this slot's column of row 0 of target; twice the cotangent of the lane's two sums, in float32
+        const float *const tg0 = (kTarget && vk) ? target + (size_t)lane * 2 * V + k : nullptr;
+        float t0p = 0.f, t0v = 0.f, t1p = 0.f, t1v = 0.f, g2p = 0.f, g2v = 0.f;
+        if constexpr (kTarget) {
+            if (g_sse) { g2p = (float)(2. * g_sse[(size_t)lane * 2]); g2v = (float)(2. * g_sse[(size_t)lane * 2 + 1]); }
+            if (vk) { const float *a = tg0 + (size_t)(C - 1) * Sg * h_stride; t0p = a[0]; t0v = a[V]; }
+        }
         const float *const lead0 = (kLead && is_head) ? micro_lead_row(ld.lead, lane) : nullptr;
         const size_t l_row = (size_t)L * 2;
         float l0x = 0.f, l0y = 0.f, l1x = 0.f, l1y = 0.f;
@@ -323,6 +427,15 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                     l0x = b[0]; l0y = b[1];
                 }
             }
+            float tcp = 0.f, tcv = 0.f;                          // kTarget: the target row of the step the replay is at
+            if constexpr (kTarget) {
+                if (vk) {
+                    tcp = t0p; tcv = t0v;
+                    if (s0 + 1 < s1) { const float *a = tg0 + (size_t)(s0 + 1) * h_stride; t1p = a[0]; t1v = a[V]; }
+                    const float *b = tg0 + (size_t)(c > 0 ? s0 - Sg : 0) * h_stride;
+                    t0p = b[0]; t0v = b[V];
+                }
+            }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             for (int r = 0; r < s1 - s0; ++r) {
                 const int q = r & 1;
@@ -334,11 +447,20 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                     const double dv = (!kLead && is_head) ? head_dv : vd - (double)ls.y;
                     IdmStep o;
                     idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
-                    float *e = R + (size_t)r * 3 * V + k;
+                    float *e = R + (size_t)r * kPlanes * V + k;
                     e[0] = o.dE[2]; e[V] = o.dE[3]; e[2 * V] = o.dLd[3];
                     if constexpr (kParams) X[(size_t)r * P1 + k] = make_float2(p, v);
                     p = o.np; v = o.nv;
                     S[(q ^ 1) * P1 + k] = make_float2(p, v);
+                    if constexpr (kTarget) {
+                        // the finished cotangent pair of this step: 2 g (hist - observed), the forward's float32 residual
+                        e[3 * V] = (tcp == tcp) ? g2p * (p - tcp) : 0.f;
+                        e[4 * V] = (tcv == tcv) ? g2v * (v - tcv) : 0.f;
+                        if (s0 + r + 1 < s1) {
+                            tcp = t1p; tcv = t1v;
+                            if (s0 + r + 2 < s1) { const float *a = tg0 + (size_t)(s0 + r + 2) * h_stride; t1p = a[0]; t1v = a[V]; }
+                        }
+                    }
                     if constexpr (kLead) {
                         if (is_head) {
                             if constexpr (kParams) X[(size_t)r * P1 + n] = ls;      // the leader the head saw in this step
@@ -371,10 +493,11 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                 float2 cx = make_float2(0.f, 0.f);
                 float gv_step = 0.f;
                 if (vk) {
-                    const float *er = R + (size_t)r * 3 * V + k;
+                    const float *er = R + (size_t)r * kPlanes * V + k;
                     e.e2 = er[0]; e.e3 = er[V]; e.l3 = er[2 * V];
                     float gp = Gp[k], gv = Gv[k];
-                    if constexpr (kSamp) { if (due && probe) { gp += chp; gv += chv; } }
+                    if constexpr (kTarget) { gp += er[3 * V]; gv += er[4 * V]; }
+                    else if constexpr (kSamp) { if (due && probe) { gp += chp; gv += chv; } }
                     else if (gh0) { gp += chp; gv += chv; }
                     Gp[k] = dot2(1.f, gp, e.e2, gv);           // grad_ps[:-1] = dqs[:, 0]^T g
                     Gv[k] = dot2(dtf, gp, e.e3, gv);

@@ -553,6 +553,10 @@ __device__ inline void micro_lead_fill(float *g_lead, int T, int L, int lane, in
 #include "micro_fwd_jvp.inc"
 #include "micro_ckpt.inc"
 #undef DHTS_MICRO_SAMPLES
+// ---- the trajectory-fit loss inside the checkpointed pair (dhts_micro_rollout_*_ckpt_target): the text of micro_ckpt.inc once more ----
+#define DHTS_MICRO_SAMPLES 2
+#include "micro_ckpt.inc"
+#undef DHTS_MICRO_SAMPLES
 
 }  // namespace dhts
 
@@ -583,6 +587,9 @@ struct MicroPlan {
     int ckpt_max_segment[2]; // steps the reverse kernel's ring can hold within kCkptLdsBudget, [0] state-only, [1] with g_params
     int ckpt_segment;        // the segment length a caller gets who names none (one value for both reverse kernels: the forward
                              // that writes the checkpoints does not know which of them will read them)
+    // the target forms of the pair (dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target): the same block, a ring of five planes
+    int target_max_segment[2];
+    int target_segment;      // the same rule as ckpt_segment with the target forms' bytes per step
 };
 constexpr size_t kCkptLdsBudget = 160 * 1024;      // LDS of a CU: what one workgroup may take
 // The default segment: the longest, up to kCkptSegmentCap, whose reverse workgroup (sized with the parameter ring) still leaves
@@ -592,6 +599,9 @@ constexpr int kCkptSegmentCap = 16;
 constexpr int kCkptWavesPerCu = 16;
 static int micro_ckpt_max_segment(int V, bool params) {
     return (int)((kCkptLdsBudget - micro_ckpt_bwd_fixed_bytes(V)) / micro_ckpt_bwd_step_bytes(V, params));
+}
+static int micro_ckpt_target_max_segment(int V, bool params) {
+    return (int)((kCkptLdsBudget - micro_ckpt_bwd_fixed_bytes(V)) / micro_ckpt_bwd_target_step_bytes(V, params));
 }
 static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     MicroPlan pl;
@@ -622,12 +632,22 @@ static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     S = S > kCkptSegmentCap ? kCkptSegmentCap : S;
     S = S > pl.ckpt_max_segment[1] ? pl.ckpt_max_segment[1] : S;
     pl.ckpt_segment = S < 1 ? 1 : S;
+    pl.target_max_segment[0] = micro_ckpt_target_max_segment(d->capacity, false);
+    pl.target_max_segment[1] = micro_ckpt_target_max_segment(d->capacity, true);
+    S = room > 0 ? (int)(room / (long long)micro_ckpt_bwd_target_step_bytes(d->capacity, true)) : 0;
+    S = S > kCkptSegmentCap ? kCkptSegmentCap : S;
+    S = S > pl.target_max_segment[1] ? pl.target_max_segment[1] : S;
+    pl.target_segment = S < 1 ? 1 : S;
     return pl;
 }
 // the segment a call runs with: the caller's, or the plan's for 0; -1 where the reverse kernel's ring cannot hold it
 static int micro_ckpt_segment(const MicroPlan &pl, int segment, bool params) {
     if (segment < 0 || segment > pl.ckpt_max_segment[params ? 1 : 0]) return -1;
     return segment == 0 ? pl.ckpt_segment : segment;
+}
+static int micro_ckpt_target_segment(const MicroPlan &pl, int segment, bool params) {
+    if (segment < 0 || segment > pl.target_max_segment[params ? 1 : 0]) return -1;
+    return segment == 0 ? pl.target_segment : segment;
 }
 static int micro_ckpt_count(int T, int S) { return T > 0 ? (T + S - 1) / S : 0; }
 
@@ -831,6 +851,42 @@ static int micro_ckpt_bwd_samples_launch(const dhts_micro_desc *d, int T, int se
                             micro_ckpt_bwd_lds_bytes(d->capacity, S, kParams), kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt,
                             (const float2 *)ckpt, count, params, head, g_p, g_v, pr, g_samples, g_p_out, g_v_out, g_head, g_params, err,
                             lead ? *lead : MicroLead{});
+        });
+    });
+    return ok ? launch_status() : DHTS_E_LAUNCH;
+}
+// ---- the target forms of the checkpointed pair: their own segment plan and reverse LDS, the forward's LDS as it is ----
+static int micro_ckpt_fwd_target_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                        const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
+                                        const float *target, double *sse, dhts_error *err, void *stream, const MicroLead *lead) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int S = micro_ckpt_target_segment(pl, segment, false);
+    if (S < 0) return DHTS_E_INVALID;
+    bool ok = true;
+    pick<0, 1>(lead != nullptr, [&](auto lv) {
+        constexpr bool kLead = decltype(lv)::value != 0;
+        ok = launch_lds(micro_rollout_ckpt_fwd_target_kernel<kLead>, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity),
+                        kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out, (float2 *)ckpt,
+                        target, sse, err, lead ? *lead : MicroLead{});
+    });
+    return ok ? launch_status() : DHTS_E_LAUNCH;
+}
+static int micro_ckpt_bwd_target_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                        const double *params, const double *head, const float *g_p, const float *g_v, const float *target,
+                                        const double *g_sse, float *g_p_out, float *g_v_out, double *g_head, double *g_params,
+                                        dhts_error *err, void *stream, const MicroLead *lead) {
+    const MicroPlan pl = micro_plan(d, T, count != nullptr);
+    const int S = micro_ckpt_target_segment(pl, segment, g_params != nullptr);
+    if (S < 0) return DHTS_E_INVALID;
+    bool ok = true;
+    pick<0, 1>(g_params != nullptr, [&](auto pv) {
+        constexpr bool kParams = decltype(pv)::value != 0;
+        pick<0, 1>(lead != nullptr, [&](auto lv) {
+            constexpr bool kLead = decltype(lv)::value != 0;
+            ok = launch_lds(micro_rollout_ckpt_bwd_target_kernel<kParams, kLead>, d->n_lanes, pl.ckpt_block,
+                            micro_ckpt_bwd_target_lds_bytes(d->capacity, S, kParams), kLdsDefault, stream, d->n_lanes, d->capacity, T, S,
+                            d->dt, (const float2 *)ckpt, count, params, head, g_p, g_v, target, g_sse, g_p_out, g_v_out, g_head, g_params,
+                            err, lead ? *lead : MicroLead{});
         });
     });
     return ok ? launch_status() : DHTS_E_LAUNCH;
@@ -1046,6 +1102,46 @@ int dhts_micro_rollout_bwd_ckpt_lead(const dhts_micro_desc *d, int T, int segmen
     const MicroLead ld = {lead, lead_length, g_lead, nullptr};
     return micro_ckpt_bwd_samples_launch(d, T, segment, ckpt, count, params, nullptr, g_p, g_v, pr, g_samples, g_p_out, g_v_out, nullptr,
                                          g_params, err, stream, &ld);
+}
+// ---- the trajectory-fit loss inside the checkpointed pair: the kTarget forms ------------------------------------------------------------
+int dhts_micro_ckpt_target_plan(const dhts_micro_desc *d, int T, int want_params, int segment, int32_t plan[8]) {
+    if (!micro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
+    const MicroPlan pl = micro_plan(d, T, false);
+    const int S = micro_ckpt_target_segment(pl, segment, want_params != 0);
+    if (S < 0) return DHTS_E_INVALID;
+    const size_t bwd_lds = micro_ckpt_bwd_target_lds_bytes(d->capacity, S, want_params != 0);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.ckpt_block;
+    plan[1] = S;
+    plan[2] = pl.target_max_segment[want_params != 0 ? 1 : 0];
+    plan[3] = micro_ckpt_count(T, S);
+    plan[4] = (int32_t)micro_ckpt_fwd_lds_bytes(d->capacity);
+    plan[5] = (int32_t)bwd_lds;
+    plan[6] = (int32_t)(kCkptLdsBudget / bwd_lds);
+    return DHTS_OK;
+}
+int dhts_micro_rollout_fwd_ckpt_target(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                       const double *params, const double *head, const float *lead, const double *lead_length,
+                                       float *p_out, float *v_out, void *ckpt, const float *target, double *sse, dhts_error *err,
+                                       void *stream) {
+    // head or lead, exactly one; T = 0 reads no row of lead, and a NULL lead is then accepted as dhts_micro_rollout_fwd_ckpt_lead accepts it
+    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || (head && (lead || lead_length)) || (!head && !lead && T > 0) || !p_out ||
+        !v_out || (T > 0 && !target) || !sse)
+        return DHTS_E_INVALID;
+    const MicroLead ld = {lead, lead_length, nullptr, nullptr};
+    return micro_ckpt_fwd_target_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt, target, sse, err, stream,
+                                        head ? nullptr : &ld);
+}
+int dhts_micro_rollout_bwd_ckpt_target(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                       const double *params, const double *head, const float *lead, const double *lead_length,
+                                       const float *g_p, const float *g_v, const float *target, const double *g_sse, float *g_p_out,
+                                       float *g_v_out, double *g_head, float *g_lead, double *g_params, dhts_error *err, void *stream) {
+    if (!micro_desc_ok(d) || T < 0 || (T > 0 && (!ckpt || !target)) || !params || (head && (lead || lead_length || g_lead)) ||
+        (!head && (g_head || (T > 0 && (!lead || !g_lead)))) || !g_p || !g_v || !g_p_out || !g_v_out)
+        return DHTS_E_INVALID;
+    const MicroLead ld = {lead, lead_length, g_lead, nullptr};
+    return micro_ckpt_bwd_target_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, target, g_sse, g_p_out, g_v_out, g_head, g_params,
+                                        err, stream, head ? nullptr : &ld);
 }
 int dhts_micro_rollout_fwd_jvp_lead(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
                                     const double *params, const float *lead, const double *lead_length, const float *t_p, const float *t_v,

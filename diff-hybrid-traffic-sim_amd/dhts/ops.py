@@ -1285,6 +1285,119 @@ def micro_rollout_fwd_jvp_lead(desc, T, p, v, params, lead, t_p, t_v, probes=Non
     return (state[0], state[1], samples), (state[2], state[3], t_samples)
 
 
+# ---- the trajectory-fit loss inside the checkpointed pair (dhts_micro_rollout_*_ckpt_target) ----------------------------------------------
+def micro_ckpt_target_plan(desc, T, want_params=False, segment=0):
+    """micro_ckpt_plan for dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target (include/dhts.h): the same keys; the reverse kernel's
+    ring holds two more floats per vehicle-step, so max_segment and the default segment are shorter.  ValueError: a segment outside
+    0 .. max_segment."""
+    plan = (C.c_int32 * 8)()
+    if not 0 <= int(segment) <= 0x7fffffff:
+        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
+    status = _lib.lib().dhts_micro_ckpt_target_plan(C.byref(desc), int(T), int(bool(want_params)), int(segment), C.byref(plan))
+    if status == _lib.E_INVALID and int(T) >= 0:
+        raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment of the target forms for %d vehicle slots%s" %
+                         (desc.capacity, " with the parameter gradient" if want_params else ""))
+    check(status, "dhts_micro_ckpt_target_plan")
+    return dict(zip(_MICRO_CKPT_PLAN_KEYS, list(plan)))
+
+
+def _target_args(desc, T, target, want_params, segment, ckpt, ckpt_optional):
+    """The raw wrappers' checks of (target, segment, ckpt) -> the resolved segment.  target: a contiguous float32 [T][L][2][V]; ckpt: a
+    contiguous float32 [micro_ckpt_numel(desc, T, resolved segment)]."""
+    L, V = desc.n_lanes, desc.capacity
+    if int(T) < 0:
+        raise ValueError("T must be >= 0")
+    if (not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != (int(T), L, 2, V)
+            or not target.is_contiguous()):
+        raise ValueError("target must be a contiguous float32 tensor of shape (%d, %d, 2, %d)" % (int(T), L, V))
+    S = micro_ckpt_target_plan(desc, T, want_params, segment)["segment"]
+    if ckpt is None and ckpt_optional:
+        return S
+    if ckpt is None or ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, S) or not ckpt.is_contiguous():
+        raise ValueError("ckpt must be %sa contiguous float32 [micro_ckpt_numel(desc, T, segment)], segment the target plan's" %
+                         ("None or " if ckpt_optional else ""))
+    return S
+
+
+def micro_rollout_fwd_ckpt_target(desc, T, p, v, params, ckpt, target, head=None, lead=None, lead_length=None, count=None, segment=0,
+                                  sse=None, err=None, out=None):
+    """micro_rollout_fwd_ckpt (head given) or micro_rollout_fwd_ckpt_lead (lead given) -- exactly one of the two -- that reads the observed
+    trajectory `target` (float32 [T][L][2][V], hist's indexing, NaN = not observed) and returns the squared error
+    (dhts_micro_rollout_fwd_ckpt_target): (pT, vT, sse), sse float64 [L][2].  ckpt None: no checkpoint is kept.  segment 0: the default
+    of micro_ckpt_target_plan."""
+    L = desc.n_lanes
+    if (head is None) == (lead is None):
+        raise ValueError("exactly one of head and lead must be given")
+    S = _target_args(desc, T, target, False, segment, ckpt, True)
+    if lead is not None:
+        _lead_args(desc, T, lead, lead_length)
+    elif lead_length is not None:
+        raise ValueError("lead_length needs lead")
+    elif head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
+        raise ValueError("head must be float64 [L][2]")
+    p, v, params = _lead_state_args(desc, p, v, params, count)
+    head = None if head is None else head.contiguous()
+    if sse is None:
+        sse = torch.empty(L, 2, dtype=torch.float64, device=p.device)
+    elif sse.dtype != torch.float64 or tuple(sse.shape) != (L, 2) or not sse.is_contiguous():
+        raise ValueError("sse must be a contiguous float64 tensor of shape (%d, 2)" % L)
+    if out is None:
+        out = (torch.empty_like(p), torch.empty_like(v))
+    # (a T = 0 call with lead: no row exists; the library takes the lead form from the NULL head)
+    check(_lib.lib().dhts_micro_rollout_fwd_ckpt_target(C.byref(desc), int(T), S, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
+                                                        _ptr(lead) if lead is not None and lead.numel() else None, _ptr(lead_length),
+                                                        _ptr(out[0]), _ptr(out[1]),
+                                                        _ptr(ckpt) if ckpt is not None and ckpt.numel() else None,
+                                                        _ptr(target) if target.numel() else None, _ptr(sse), _ptr(err), _stream()),
+          "dhts_micro_rollout_fwd_ckpt_target")
+    return out[0], out[1], sse
+
+
+def micro_rollout_bwd_ckpt_target(desc, T, ckpt, params, g_p, g_v, target, g_sse=None, head=None, lead=None, lead_length=None, count=None,
+                                  segment=0, err=None, out=None, g_head=None, g_lead=None, g_params=None):
+    """The reverse sweep of micro_rollout_fwd_ckpt_target (dhts_micro_rollout_bwd_ckpt_target) -> (g_p0, g_v0, g_head) with head, or
+    (g_p0, g_v0, g_lead) with lead.  g_sse float64 [L][2] or None (zero): the cotangent of sse; the per-step cotangent
+    (float)(2 g_sse) * (x - target) is formed in the kernel.  target, head / lead, lead_length, count, segment: the forward's."""
+    L, V = desc.n_lanes, desc.capacity
+    if (head is None) == (lead is None):
+        raise ValueError("exactly one of head and lead must be given")
+    S = _target_args(desc, T, target, g_params is not None, segment, ckpt, False)
+    if lead is not None:
+        _lead_args(desc, T, lead, lead_length)
+    elif lead_length is not None:
+        raise ValueError("lead_length needs lead")
+    elif head.dtype != torch.float64 or tuple(head.shape) != (L, 2) or not head.is_contiguous():
+        raise ValueError("head must be a contiguous float64 [L][2]")
+    for name, t in (("params", params), ("g_params", g_params)):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
+    if g_sse is not None and (g_sse.dtype != torch.float64 or tuple(g_sse.shape) != (L, 2) or not g_sse.is_contiguous()):
+        raise ValueError("g_sse must be None or a contiguous float64 tensor of shape (%d, 2)" % L)
+    g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
+    if out is None:
+        out = (torch.empty_like(g_p), torch.empty_like(g_v))
+    if lead is None:
+        if g_lead is not None:
+            raise ValueError("g_lead needs lead")
+        if g_head is None:
+            g_head = torch.zeros(L, 2, dtype=torch.float64, device=g_p.device)
+    else:
+        if g_head is not None:
+            raise ValueError("g_head needs head")
+        if g_lead is None:
+            g_lead = torch.empty(int(T), L, 2, dtype=torch.float32, device=g_p.device)
+        elif g_lead.dtype != torch.float32 or tuple(g_lead.shape) != (int(T), L, 2) or not g_lead.is_contiguous():
+            raise ValueError("g_lead must be a contiguous float32 tensor of shape (%d, %d, 2)" % (int(T), L))
+    check(_lib.lib().dhts_micro_rollout_bwd_ckpt_target(C.byref(desc), int(T), S, _ptr(ckpt) if ckpt.numel() else None, _ptr(count),
+                                                        _ptr(params), _ptr(head),
+                                                        _ptr(lead) if lead is not None and lead.numel() else None, _ptr(lead_length),
+                                                        _ptr(g_p), _ptr(g_v), _ptr(target) if target.numel() else None, _ptr(g_sse),
+                                                        _ptr(out[0]), _ptr(out[1]), _ptr(g_head),
+                                                        _ptr(g_lead) if g_lead is not None and g_lead.numel() else None, _ptr(g_params),
+                                                        _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_target")
+    return out[0], out[1], (g_head if lead is None else g_lead)
+
+
 def _probe_slots(probes, V):
     """The `probes` argument of dhts.micro_rollout / micro_rollout_jvp, checked as macro_rollout checks `detectors` -> the CUDA int32
     tensor as it is (not validated), or the list of slots (non-empty, strictly ascending, in [0, V); ValueError otherwise)."""
@@ -1563,6 +1676,85 @@ class MicroRolloutLead(torch.autograd.Function):
         return (g_p0, g_v0, ctx.g_params, g_lead) + (None,) * 9
 
 
+class MicroRolloutTarget(torch.autograd.Function):
+    """MicroRollout's checkpointed call fitted to an observed trajectory inside the kernels: (p0, v0 [L][V], head [L][2] or lead
+    [T][L][2]) -> (pT, vT, sse [L][2] float64), sse[l] = the sums over observed entries of target of (x - target)^2 for positions and for
+    speeds (dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target).  No [T][L][2][V] history and no cotangent of one exists: the forward
+    accumulates, the reverse sweep forms 2 g_sse (x - target) from the state it replays.  Exactly one of head and lead is a tensor."""
+
+    @staticmethod
+    def forward(ctx, p0, v0, params, head, lead, lead_length, count, T, dt, check_faults, checkpoint, target):
+        L, V = p0.shape
+        desc = micro_desc(L, V, dt)
+        want_params = params.requires_grad
+        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_target_plan(desc, T, want_params, sg))   # (ValueError before a device is touched)
+        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
+        dev = p0c.device
+        boundary = head if lead is None else lead
+        need_grad = p0.requires_grad or v0.requires_grad or boundary.requires_grad or want_params
+        ctx.params = params.detach().contiguous()
+        ctx.head = None if head is None else head.detach().contiguous()
+        ctx.lead = None if lead is None else _f32c(lead.detach(), "lead")
+        ctx.lead_length = None if lead_length is None else lead_length.detach().to(device=dev, dtype=torch.float64).contiguous()
+        ctx.target = _f32c(target, "target")
+        # everything the pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand over)
+        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
+        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
+        ctx.g_lead = torch.empty(T, L, 2, dtype=torch.float32, device=dev) if (need_grad and lead is not None) else None
+        ctx.g_head = torch.zeros(L, 2, dtype=torch.float64, device=dev) if (need_grad and lead is None) else None
+        ctx.out_bwd = (torch.empty_like(p0c), torch.empty_like(v0c)) if need_grad else None
+        err = new_error_record(dev)
+        pT, vT, sse = micro_rollout_fwd_ckpt_target(desc, T, p0c, v0c, ctx.params, ctx.ckpt, ctx.target, head=ctx.head, lead=ctx.lead,
+                                                    lead_length=ctx.lead_length, count=count, segment=segment, err=err)
+        if check_faults:                 # a collision is printed like the reference does, and tolerated
+            raise_on_fault(err)
+        ctx.desc, ctx.T, ctx.count, ctx.check_faults, ctx.segment = desc, T, count, check_faults, segment
+        ctx.err_bwd = new_error_record(dev) if need_grad else None
+        return pT, vT, sse
+
+    @staticmethod
+    def backward(ctx, g_pT, g_vT, g_sse):
+        desc, T = ctx.desc, ctx.T
+        dev = ctx.err_bwd.device
+        L, V = desc.n_lanes, desc.capacity
+        g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
+        g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
+        gs = g_sse.contiguous() if g_sse is not None else None          # (None: the kernel takes zero)
+        err = ctx.err_bwd
+        err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
+        if ctx.g_head is not None:
+            ctx.g_head.zero_()
+        g_p0, g_v0, g_b = micro_rollout_bwd_ckpt_target(desc, T, ctx.ckpt, ctx.params, g_p, g_v, ctx.target, g_sse=gs, head=ctx.head,
+                                                        lead=ctx.lead, lead_length=ctx.lead_length, count=ctx.count, segment=ctx.segment,
+                                                        err=err, out=ctx.out_bwd, g_head=ctx.g_head, g_lead=ctx.g_lead,
+                                                        g_params=ctx.g_params)
+        if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
+            MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
+        g_head, g_lead = (g_b, None) if ctx.lead is None else (None, g_b)
+        return (g_p0, g_v0, ctx.g_params, g_head, g_lead) + (None,) * 7
+
+
+def _micro_target_checks(p0, T, target, want_hist, checkpoint, probes, every):
+    """Every ValueError of dhts.micro_rollout's `target`, raised before anything touches a device."""
+    if checkpoint is None or checkpoint is False:
+        raise ValueError("target lives on the checkpointed path only: pass checkpoint=True (or a segment length)")
+    if want_hist:
+        raise ValueError("target does not take want_hist: the history is what target= does without")
+    if probes is not None or every != 1:
+        raise ValueError("target does not take probes / every: it is the dense fit (NaN entries of target are the unobserved ones)")
+    if p0.dim() != 2:
+        raise ValueError("p0 must be [L][V]")
+    L, V = int(p0.shape[0]), int(p0.shape[1])
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != (int(T), L, 2, V):
+        raise ValueError("target must be a float32 tensor of shape (T, L, 2, V) = (%d, %d, 2, %d)" % (int(T), L, V))
+    if target.device != p0.device:
+        raise ValueError("target must live on p0's device (%s), not %s" % (p0.device, target.device))
+    if not target.is_contiguous():
+        raise ValueError("target must be contiguous: a copy of it is as large as the history it replaces")
+    if target.requires_grad:
+        raise ValueError("target is data and not differentiable: pass it detached")
+
+
 def _micro_lead_checks(p0, head, T, lead, lead_length, want_hist, checkpoint):
     """Every ValueError of dhts.micro_rollout's `lead` / `lead_length`, raised before anything touches a device."""
     if head is not None:
@@ -1584,7 +1776,7 @@ def _micro_lead_checks(p0, head, T, lead, lead_length, want_hist, checkpoint):
 
 
 def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None, probes=None, every=1,
-                  lead=None, lead_length=None):
+                  lead=None, lead_length=None, target=None):
     """MicroRollout.  checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape).
 
     probes / every: observe the trajectory at a few vehicle slots every so many steps.  Sampling is on when probes is not None or
@@ -1603,7 +1795,28 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
     follower (the same gap, collision and clamp rules).  lead_length float64 [L] or None = the head's own length; not differentiable.
     `head` must be None.  lead may require grad: its gradient [T][L][2] is the per-step cotangent of that leader.  It lives on the
     checkpointed path only: checkpoint=True or a segment is required (ValueError otherwise), want_hist is not accepted (ValueError: the
-    dense history is probes=range(V), every=1), probes / every work as above; without them the call returns (pT, vT)."""
+    dense history is probes=range(V), every=1), probes / every work as above; without them the call returns (pT, vT).
+
+    target: fit the whole trajectory without holding it.  target float32 [T][L][2][V], contiguous, on p0's device, not requiring grad:
+    target[t][l][0 / 1][k] = the observed (p, v) of slot k after step t (hist's indexing); a NaN entry is not observed.  The call returns
+    (pT, vT, sse), sse float64 [L][2]: per lane the sum over observed entries of (x - target)^2 for positions and for speeds -- the
+    float32 difference hist - target, squared and summed in double in a fixed order (the same bits every run; slots at or beyond count
+    are never read; T = 0 gives zeros).  sse is differentiable: mean((hist - target)^2) is sse.sum() / target.numel().  Neither hist nor
+    its cotangent exists; the kernels read target once per direction (MicroRolloutTarget).  checkpoint=True or a segment is required
+    (the segment plan is micro_ckpt_target_plan's: its reverse ring is wider), want_hist / probes / every are not accepted (ValueError),
+    lead / lead_length combine with it.  Without a leaf that requires grad no checkpoint is kept: a loss evaluation."""
+    if target is not None:
+        _micro_target_checks(p0, T, target, want_hist, checkpoint, probes, every)
+        if lead is not None or lead_length is not None:
+            if lead is None:
+                raise ValueError("lead_length needs lead")
+            _micro_lead_checks(p0, head, T, lead, lead_length, False, checkpoint)
+        elif head is None:
+            raise ValueError("head must be given (float64 [L][2]) unless lead is")
+        desc = micro_desc(int(p0.shape[0]), int(p0.shape[1]), float(dt))
+        _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_target_plan(desc, int(T), params.requires_grad, sg))
+        return MicroRolloutTarget.apply(p0, v0, params, head, lead, lead_length, count, int(T), float(dt), bool(check_faults), checkpoint,
+                                        target)
     if lead is not None or lead_length is not None:
         if lead is None:
             raise ValueError("lead_length needs lead")

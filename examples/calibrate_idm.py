@@ -20,6 +20,10 @@ T // E x L x 2 x P numbers, and with --checkpoint / --fused nothing of size T x 
 rollout of n_vehicle + 1 vehicles per lane on the existing path; the head vehicle's recorded trajectory becomes `lead`
 (dhts.micro_rollout(lead=, lead_length=) / micro_rollout_jvp(lead=, ...)), and the n_vehicle followers behind it are fitted.  A
 recorded leader lives on the tape-free paths: with --checkpoint (Adam) or --method lm --fused, each with or without --observe.
+--fused-loss (with --checkpoint, Adam, the dense fit, with or without --leader): the kernels read the observed trajectories themselves
+(dhts.micro_rollout(target=observed)) and return the squared error per lane, loss = sse.sum() / observed.numel(); neither the history
+nor its cotangent is allocated, so the fit holds `observed` and the checkpoints and nothing else of size T x V.  The same log up to
+the summation order of the loss (float64 in the kernels, float32 in torch.mean).
 Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt (lm: .../lm/trial_k.txt), like the other examples.
 """
 import argparse
@@ -56,6 +60,8 @@ def main():
                     help="observe P evenly spaced probe slots per lane every E-th step instead of every vehicle at every step")
     ap.add_argument("--leader", action="store_true",
                     help="fit the followers of a recorded leader: the truth has n_vehicle + 1 vehicles, its head's trajectory is given")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="Adam with --checkpoint: the squared error and its gradient inside the rollout kernels (target=), no history")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
@@ -65,6 +71,8 @@ def main():
         ap.error("--checkpoint belongs to --method adam")
     if args.leader and not (args.fused or args.checkpoint is not None):
         ap.error("--leader lives on the tape-free paths: add --checkpoint (Adam) or --method lm --fused")
+    if args.fused_loss and (args.checkpoint is None or args.observe is not None):
+        ap.error("--fused-loss is the dense fit on the checkpointed path: add --checkpoint, drop --observe")
     sampled = {}                                  # the arguments of a sampled call; none: the dense history
     if args.observe is not None:
         try:
@@ -97,6 +105,11 @@ def main():
         if sampled:      # (the fused fit's loss evaluations: the tape-free forward too, no grad is asked of it)
             return dhts.micro_rollout(p0, v0, params, head, T, dt, checkpoint=True if args.fused else args.checkpoint, **sampled)[2]
         return dhts.micro_rollout(p0, v0, params, head, T, dt, want_hist=True, checkpoint=args.checkpoint)[2]
+
+    def squared_error(theta):
+        """--fused-loss: sum((hist - observed)^2) [L][2] float64 from the kernels; hist is never written."""
+        params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+        return dhts.micro_rollout(p0, v0, params, None if follow else head, T, dt, checkpoint=args.checkpoint, target=observed, **follow)[2]
 
     for trial in range(args.n_trial):
         p0 = (th.arange(V, device=dev) * 4.0 * ln)[None, :] + th.rand(L, V, device=dev) * 2.0 * ln
@@ -147,7 +160,10 @@ def main():
             theta = guess.clone().requires_grad_(True)
             opt = th.optim.Adam([theta], lr=args.lr)
             for ep in range(args.n_episode):
-                loss = ((rollout(theta) - observed) ** 2).mean()
+                if args.fused_loss:
+                    loss = squared_error(theta).sum() / observed.numel()
+                else:
+                    loss = ((rollout(theta) - observed) ** 2).mean()
                 opt.zero_grad()
                 loss.backward()
                 err = ((theta.detach() - truth[:5]) / truth[:5]).abs().max()

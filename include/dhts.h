@@ -691,6 +691,48 @@ int dhts_micro_rollout_fwd_jvp_lead(const dhts_micro_desc *d, int T, int n_dir, 
                                     const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
                                     dhts_error *err_jvp, void *stream);
 
+/*
+ * THE TRAJECTORY-FIT LOSS inside the checkpointed pair: sum((hist - observed)^2) and its gradient without hist and without g_hist.
+ * The two entry points are dhts_micro_rollout_fwd_ckpt / _bwd_ckpt (head given) or _fwd_ckpt_lead / _bwd_ckpt_lead without probes (lead
+ * given; EXACTLY ONE of head and lead, lead_length only with lead) with hist / g_hist, samples / g_samples replaced by
+ *   target   [T][L][2][V] float32, hist's indexing: target[t][l][0 / 1][k] = the observed (p, v) of slot k AFTER step t.  A NaN entry is
+ *            not observed: it adds exactly 0 to sse and no cotangent.  Slots at or beyond count are never read.
+ *   sse      [L][2] DOUBLE, written: per lane the sum over observed entries of the squared position residual, and of the squared speed
+ *            residual.  The residual is the float32 difference x - target (what hist - observed is), squared and summed in double: each
+ *            thread sums its own vehicle in step order, the workgroup combines the per-thread sums pairwise in a fixed order through
+ *            LDS.  No atomics: two runs give the same bits.  T = 0 and an empty lane: 0.
+ *   g_sse    [L][2] DOUBLE or NULL (zero): the cotangent of sse.  The reverse sweep adds (float)(2 g_sse[l][c]) * r -- r the same float32
+ *            residual, recomputed from the replayed state; 0 for a NaN entry -- to the cotangent of slot k at step t where
+ *            dhts_micro_rollout_bwd_ckpt adds g_hist[t][l][c][k], with the same float32 add.
+ * and otherwise their siblings' arguments, arithmetic, fault records and bits (p_out, v_out and, for equal per-step cotangents, every
+ * gradient):
+ *   dhts_micro_rollout_fwd_ckpt_target   the rollout of dMicroForwardLayer.forward (dmicro_lane.py:230-269 = MicroLane.forward
+ *       _micro_lane.py:131-214 + dMicroLane._backward :87-127) and the loss of example/inverse/micro.py:36-118 on its trajectory.  ckpt
+ *       may be NULL: no checkpoint is kept (a loss evaluation that nobody differentiates).  A block smaller than the lane
+ *       (DHTS_FAULT_CAPACITY): sse of the lane is NaN.
+ *   dhts_micro_rollout_bwd_ckpt_target   the sweep of dMicroForwardLayer.backward (dmicro_lane.py:271-298, with the virtual-leader slot
+ *       of dMicroLane.vectorize_input :130-153 folded into the head, or returned per step as g_lead; the parameter gradient that of
+ *       road/lane/_micro_lane.py:131-214 over IDM.compute_acceleration, model/micro/_idm.py:30-49).  g_head with head, g_lead [T][L][2]
+ *       with lead; g_params optional.
+ * target is read once per direction, coalesced along k; nothing of size T x V is written.
+ * DHTS_E_INVALID, nothing dereferenced and nothing launched: a bad descriptor, T < 0, head and lead both given or (T > 0) neither,
+ * lead_length / g_lead with head, g_head with lead, a NULL target or ckpt (reverse) or g_lead (with lead) when T > 0, a NULL p / v /
+ * params / p_out / v_out / sse / g_p / g_v / g_p_out / g_v_out, a segment outside 0 .. the max_segment of dhts_micro_ckpt_target_plan.
+ * dhts_micro_ckpt_target_plan: dhts_micro_ckpt_plan's eight entries for these two kernels.  The reverse kernel's ring holds two more
+ * floats per vehicle-step (the finished cotangent pair), so max_segment and the default segment (the same rule: the longest that keeps
+ * 16 wavefronts resident on a CU by LDS, at most 16) are shorter; segment 0 at the two entry points is THIS plan's default.  The
+ * checkpoint buffer is dhts_micro_ckpt_bytes of the resolved segment plan[1].
+ */
+int dhts_micro_ckpt_target_plan(const dhts_micro_desc *d, int T, int want_params, int segment, int32_t plan[8]);
+int dhts_micro_rollout_fwd_ckpt_target(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                       const double *params, const double *head, const float *lead, const double *lead_length,
+                                       float *p_out, float *v_out, void *ckpt, const float *target, double *sse, dhts_error *err,
+                                       void *stream);
+int dhts_micro_rollout_bwd_ckpt_target(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                       const double *params, const double *head, const float *lead, const double *lead_length,
+                                       const float *g_p, const float *g_v, const float *target, const double *g_sse, float *g_p_out,
+                                       float *g_v_out, double *g_head, float *g_lead, double *g_params, dhts_error *err, void *stream);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
