@@ -28,6 +28,9 @@ constexpr int kDppWaveShl1 = 0x130;
 __device__ __forceinline__ float take_right(float x, float carry) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(carry), __float_as_int(x), kDppWaveShl1, 0xF, 0xF, false));
 }
+__device__ __forceinline__ unsigned take_right(unsigned x, unsigned carry) {
+    return (unsigned)__builtin_amdgcn_update_dpp((int)carry, (int)x, kDppWaveShl1, 0xF, 0xF, false);
+}
 __device__ __forceinline__ double take_right(double x, double carry) {
     const long long xb = __double_as_longlong(x), cb = __double_as_longlong(carry);
     const int lo = __builtin_amdgcn_update_dpp((int)(cb & 0xffffffffll), (int)(xb & 0xffffffffll), kDppWaveShl1, 0xF, 0xF, false);
@@ -677,13 +680,20 @@ __device__ __forceinline__ void tape_fill_slots(const float4 *row, const TapeGeo
 // whose interface carries the step's tag reads the products from there.  The cotangent of the own cell lives in a register;
 // what the neighbours contribute goes through C0 / C2.  XA / XB / STAMP / C0 / C2 alternate between two copies with the step
 // parity, so a step needs ONE barrier (LDS only: the tape loads stay in flight across it).  The tape entries are loaded
-// three steps before they are needed (three register sets trading places, no moves), the exception counts six.  The float32 arithmetic is that of the general kernel below
+// three steps before they are needed (three register sets trading places, no moves), the exception counts six.
+// WITHOUT per-step cotangents (kHist = kTaps = false) the trivial products take another road: every S entry is loaded once, by the
+// thread of its interface, the right interface's entry comes from lane t + 1 by DPP moves (lane 63: from SB in LDS), and six S sets
+// rotate through a six-step round (six = 2 LDS copies x 3 exception sets); the exceptions stay three sets deep.  Loads return in order: a wait for
+// an exception set also waits for every S set issued before it, so FOUR S sets are in flight, two hold data that has arrived.
+// The float32 arithmetic is that of the general kernel below
 // (cell_blocks, dot2) two components at a time (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: same operations, same roundings).
 // Dynamic LDS: float2 C0[2][N + 2], C2[2][N + 2] (index k + 1 = cell k; slot 1 of C2 and slot N of C0 are never written and
-// stay zero: the edge cells add 0) | float4 XA[2][N + 1], XB[2][N + 1] | u32 STAMP[2][N + 2].
+// stay zero: the edge cells add 0) | float4 XA[2][N + 1], XB[2][N + 1] | u32 STAMP[2][N + 2] | without per-step cotangents:
+// SEntry SB[2][kB / 64 + 1].
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef unsigned bits3 __attribute__((ext_vector_type(3)));
 typedef unsigned bits4 __attribute__((ext_vector_type(4)));
+struct alignas(16) SEntry { unsigned x, y, z; };      // an S entry in LDS: one 12-byte access at a 16-byte stride
 __device__ __forceinline__ TapeFp tape_fp_bits(bits3 b) { TapeFp f; f.f0 = __uint_as_float(b.x); f.f2 = __uint_as_float(b.y); f.f3 = __uint_as_float(b.z); return f; }
 __device__ __forceinline__ float4 f4_bits(bits4 b) { return make_float4(__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)); }
 __device__ __forceinline__ v2f pk_dot(v2f dlo, v2f dhi, v2f g) {           // (dot2(dlo.x, g.x, dhi.x, g.y), dot2(dlo.y, g.x, dhi.y, g.y))
@@ -691,8 +701,10 @@ __device__ __forceinline__ v2f pk_dot(v2f dlo, v2f dhi, v2f g) {           // (d
     return __builtin_elementwise_fma(dhi, gy, dlo * gx);
 }
 // (the planes are sized by the block, kB = 64 .. 512 threads >= N, so that every LDS address is a register plus a literal)
-__host__ __device__ inline size_t bwd_fast_lds_bytes(int kB) {
-    return 2 * 2 * 8 * (size_t)(kB + 2) + 2 * 2 * 16 * (size_t)(kB + 2) + 2 * 4 * (size_t)(kB + 2);
+// deep: the instantiations without per-step cotangents add SEntry SB[2][kB / 64 + 1] (16 bytes each), the hand-over of the S entries
+// at the wavefront boundaries
+__host__ __device__ inline size_t bwd_fast_lds_bytes(int kB, bool deep) {
+    return 2 * 2 * 8 * (size_t)(kB + 2) + 2 * 2 * 16 * (size_t)(kB + 2) + 2 * 4 * (size_t)(kB + 2) + (deep ? 2 * 16 * (size_t)(kB / 64 + 1) : 0);
 }
 // kHist: per-step cotangents g_hist [T][L][2][N] (a loss on the state history) are added to the cell's cotangent in front of
 // every step; they ride in the register sets of the trivial products, three steps ahead.
@@ -720,6 +732,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     float4 *XA = reinterpret_cast<float4 *>(lds), *XB = XA + 2 * P;                   // [copy][P]
     v2f *C0 = reinterpret_cast<v2f *>(XB + 2 * P), *C2 = C0 + 2 * P;                  // [copy][P]
     unsigned *STAMP = reinterpret_cast<unsigned *>(C2 + 2 * P);                       // [copy][P]
+    SEntry *SB = reinterpret_cast<SEntry *>(STAMP + 2 * P);                           // [copy][kB / 64 + 1], !kCot only (104 P bytes in: 16-byte aligned)
     const size_t base = (size_t)lane * N;
     const TapeGeom geo = tape_geom(N);
     const v2f cf = {(float)cc, (float)cc}, ncf = {(float)(-cc), (float)(-cc)};
@@ -746,6 +759,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         __syncthreads();
     }
     for (int i = t; i < 2 * P; i += B) { C0[i] = zero2; C2[i] = zero2; STAMP[i] = 0u; }
+    if constexpr (!kCot) { if (t < 2 * (kB / 64 + 1)) SB[t] = SEntry{0u, 0u, 0u}; }
     v2f g = zero2;
     if (vk) g = v2f{g_r_in[base + k], g_y_in[base + k]};
 
@@ -770,7 +784,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const size_t hstride = (size_t)L * 2 * (kTaps ? n_det : N);
     const float *hb = kHist ? g_hist + (size_t)lane * 2 * N + kl : (kTaps ? g_hist + (size_t)lane * 2 * n_det : nullptr);
     const float *pH = kCot ? hb + (size_t)(T > 5 ? T - 5 : 0) * hstride : nullptr;
-    const char *pS = tb + (size_t)(T > 5 ? T - 5 : 0) * stride;      // row of step - 4 in the interval of `step`
+    const char *pS = tb + (size_t)(kCot ? (T > 5 ? T - 5 : 0) : (T > 8 ? T - 8 : 0)) * stride;      // row of step - 4 in the interval of `step` (!kCot: of step - 7)
     const char *pE = tb + (size_t)(T > 6 ? T - 6 : 0) * stride;      // row of step - 5
     const char *pC = tb + (size_t)(T > 9 ? T - 9 : 0) * stride;      // row of step - 8
 #define DHTS_ROW(step_) (tb + (size_t)((step_) > 0 ? (step_) : 0) * stride)
@@ -834,11 +848,8 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // off that chain: the blocks of step s - 1 (trivial products in (sl_, sr_), exceptions scattered one interval ago), the
     // exceptions of step s - 2 from (ea_ .. ec_) to LDS, and the refills: exceptions of step s - 5 (their count cq_ arrived three
     // intervals ago), the count of step s - 8, the trivial products of step s - 4.  Everything read from the tape is in flight
-    // for three intervals (2 workgroups x 3 steps x 9 KB per CU: what 6 TB/s at ~2 us of latency need).
-#define DHTS_STEP(CL, s_, Q, R, sl_, sr_, gh_, ea_, eb_, ix_, ec_, cq_)                  \
-    {                                                                                    \
-        if (kSched) gs_run -= 2 * (size_t)L;                                             \
-        if (vk) {                                                                        \
+    // for three intervals.  (This describes DHTS_STEP, the three-set interval; DHTS_CELL is shared with DHTS_STEP6, which has its own comment.)
+#define DHTS_CELL(Q, R)                                                                  \
             g = (c1v + C2[(R) * P + k + 1]) + C0[(R) * P + k + 1];                       \
             if (kCot) g += gh_cur;                 /* the cotangent of the state after step s, if the loss looks at it */ \
             n_fin += (isfinite(g.x) && isfinite(g.y)) ? 1 : 0;                           \
@@ -855,7 +866,12 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 if (k == 0) { gh_r += (double)c0.x; gh_y += (double)c0.y; }              \
                 if (k == N - 1) { gh_r += (double)c2v.x; gh_y += (double)c2v.y; }        \
                 }                                                                        \
-            }                                                                            \
+            }
+#define DHTS_STEP(CL, s_, Q, R, sl_, sr_, gh_, ea_, eb_, ix_, ec_, cq_)                  \
+    {                                                                                    \
+        if (kSched) gs_run -= 2 * (size_t)L;                                             \
+        if (vk) {                                                                        \
+            DHTS_CELL(Q, R)                                                              \
             if (!(CL) || (s_) >= 1) DHTS_BLOCKS((s_) - 1, R, sl_, sr_)                   \
             if (kCot) gh_cur = gh_;                /* of step s - 1: the set is refilled below */ \
         }                                                                                \
@@ -870,6 +886,15 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         pC -= (!(CL) || (s_) > 8) ? stride : 0;                                          \
         lds_only_barrier();                                                              \
     }
+    // after step 0, whose copy is Q = (T - 1) & 1
+#define DHTS_LAST                                                                        \
+    if (vk) {                                                                            \
+        const int oq = ((T - 1) & 1) * P;                                                \
+        g = (c1v + C2[oq + k + 1]) + C0[oq + k + 1];                                     \
+        n_fin += (isfinite(g.x) && isfinite(g.y)) ? 1 : 0;                               \
+    }
+    if constexpr (kCot) {
+    // ---- with per-step cotangents: the trivial products of both interfaces and the cotangent ride in three sets (sl, sr, gh)
     // register set A serves the steps T - 1, T - 4, ..., set B the steps T - 2, T - 5, ..., set C the steps T - 3, T - 6, ...
     TapeFp slA, srA, slB, srB, slC, srC;
     float4 eaA = zero4, ebA = zero4, eaB = zero4, ebB = zero4, eaC = zero4, ebC = zero4;
@@ -926,11 +951,157 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     }
     if (step >= 0) DHTS_STEP(1, step, q, q ^ 1, slB, srB, ghB, eaC, ebC, ixC, ecC, cqC)
     if (step >= 1) DHTS_STEP(1, step - 1, q ^ 1, q, slC, srC, ghC, eaA, ebA, ixA, ecA, cqA)
-    if (vk) {                                            // after step 0, whose copy is Q = (T - 1) & 1
-        const int oq = ((T - 1) & 1) * P;
-        g = (c1v + C2[oq + k + 1]) + C0[oq + k + 1];
-        n_fin += (isfinite(g.x) && isfinite(g.y)) ? 1 : 0;
+    DHTS_LAST
+    } else {
+    // ---- without per-step cotangents: every S entry is loaded ONCE, by the thread of its interface; six S sets rotate, four are in flight.
+    // The right interface's entry comes from lane t + 1 (three wave_shl:1 DPP moves); lane 63 takes interface 64 (w + 1)'s from
+    // SB [copy][wave], where lane 0 of every wavefront leaves its entry one interval before it is used (copy Q, like the exceptions:
+    // same barrier).  SB [..][kB / 64] is never written: interface kB is interface N or past it, an exception whose STAMP test
+    // picks XA / XB, like every interface N (whose thread holds the clamped entry N - 1 instead).
+    // A set is three registers as loaded; S(x) is loaded in the interval of x + 7, handed over in that of x + 2, used in that of
+    // x + 1.  The exceptions stay three sets deep; a set's count is a vector register while it is in flight and a scalar once it has
+    // arrived, so nothing loaded is copied while it is in flight and the loop needs no wait at its back edge.
+    constexpr int kNW1 = kB / 64 + 1;
+    const unsigned wv = (unsigned)t >> 6;
+#define DHTS_LOAD_S1(rb_, s_) s_ = __builtin_amdgcn_raw_buffer_load_b96(DHTS_RSRC(rb_), off_sl, 0, 0);
+#define DHTS_HAND(Q, s_) if ((t & 63) == 0) SB[(Q) * kNW1 + wv] = SEntry{s_.x, s_.y, s_.z};
+#define DHTS_BLOCKS1(st_, Q, s_)                                                         \
+    {                                                                                    \
+        const SEntry cw_ = SB[(Q) * kNW1 + wv + 1];                                      \
+        const bits3 r_ = {take_right(s_.x, cw_.x), take_right(s_.y, cw_.y), take_right(s_.z, cw_.z)}; \
+        const TapeFp sl1_ = tape_fp_bits(s_), sr1_ = tape_fp_bits(r_);                   \
+        DHTS_BLOCKS(st_, Q, sl1_, sr1_)                                                  \
     }
+    // More exceptions than threads: the rest, without prefetch, through the row's buffer descriptor.  (scatter_rest's per-thread
+    // 64-bit addresses are hoisted out of the step loop as running pointers, two per unrolled step: 24 registers in a six-step round.
+    // Here the thread's place in the row is a 32-bit offset, formed from the thread's number where it is needed: the empty asm
+    // keeps the compiler from forming it once in front of the step loop and holding it in registers.)
+    auto scatter_rest1 = [&](int step, int cnt, float4 *xa, float4 *xb, unsigned *st) {
+        const __amdgpu_buffer_rsrc_t rs = DHTS_RSRC(DHTS_ROW(step));
+        if (cnt > N + 1) cnt = N + 1;
+        int t0 = t;
+        asm volatile("" : "+v"(t0));
+        for (int j = t0 + B; j < cnt; j += B) {
+            const unsigned i = __builtin_amdgcn_raw_buffer_load_b16(rs, off_c + 8u + 2u * (unsigned)j, 0, 0);
+            if (i <= (unsigned)N) {
+                const unsigned oe = 16u * (geo.s_f4 + geo.h_f4) + 32u * (unsigned)j;
+                xa[i] = f4_bits(__builtin_amdgcn_raw_buffer_load_b128(rs, oe, 0, 0));
+                xb[i] = f4_bits(__builtin_amdgcn_raw_buffer_load_b128(rs, oe + 16u, 0, 0));
+                st[i] = (unsigned)step + 1u;
+            }
+        }
+    };
+#define DHTS_SCATTER1(step_, Q, c_, ea_, eb_, ix_)                                       \
+    {                                                                                    \
+        if ((t < (c_)) & (ix_ <= (unsigned)N)) {                                         \
+            XA[(Q) * P + ix_] = ea_; XB[(Q) * P + ix_] = eb_; STAMP[(Q) * P + ix_] = (unsigned)(step_) + 1u; \
+        }                                                                                \
+        if ((c_) > B) scatter_rest1(step_, c_, XA + (Q) * P, XB + (Q) * P, STAMP + (Q) * P); \
+    }
+    // a row's count is the same in every thread: once it has arrived it moves to a scalar register
+#define DHTS_ARRIVED(h_, v_) h_ = __builtin_amdgcn_readfirstlane(v_);
+    // One interval of step s as above; sb_ = S(s - 1), refilled with S(s - 7); sh_ = S(s - 2); h_ the count of the exceptions held
+    // in (ea_, eb_, ix_), of step s - 2 and then of step s - 5; v_ the count of step s - 5, then that of step s - 8 in flight.
+#define DHTS_STEP6(CL, s_, Q, R, sb_, sh_, ea_, eb_, ix_, h_, v_)                        \
+    {                                                                                    \
+        if (kSched) gs_run -= 2 * (size_t)L;                                             \
+        if (vk) {                                                                        \
+            DHTS_CELL(Q, R)                                                              \
+            if (!(CL) || (s_) >= 1) DHTS_BLOCKS1((s_) - 1, R, sb_)                       \
+        }                                                                                \
+        /* the blocks are formed HERE: without a branch behind them (the masked forms have one) the compiler puts off the products */ \
+        /* with cc until they are used, behind the barrier, and holds the sixteen factors instead of the twelve blocks */ \
+        if (kFull) asm volatile("" : "+v"(d0lo), "+v"(d0hi), "+v"(d1lo), "+v"(d1hi), "+v"(d2lo), "+v"(d2hi)); \
+        if (!(CL) || (s_) >= 2) DHTS_SCATTER1((s_) - 2, Q, h_, ea_, eb_, ix_);            \
+        DHTS_ARRIVED(h_, v_)                                                             \
+        DHTS_LOAD_E(pE, h_, ea_, eb_, ix_);                                              \
+        DHTS_LOAD_CNT(pC, v_);                                                           \
+        DHTS_LOAD_S1(pS, sb_);                                                           \
+        pS -= (!(CL) || (s_) > 7) ? stride : 0;                                          \
+        pE -= (!(CL) || (s_) > 5) ? stride : 0;                                          \
+        pC -= (!(CL) || (s_) > 8) ? stride : 0;                                          \
+        DHTS_HAND(Q, sh_)                                                                \
+        lds_only_barrier();                                                              \
+    }
+    // the six steps of a round: S sets (B, C) (C, D) (D, E) (E, F) (F, A) (A, B), exception sets C A B C A B, LDS copies 0 1 0 1 0 1
+#define DHTS_ROUND6(CL, X)                                                               \
+        DHTS_STEP6(CL, step, 0, 1, sB, sC, eaC, ebC, ixC, hC, vC)                        \
+        X(1) DHTS_STEP6(CL, step - 1, 1, 0, sC, sD, eaA, ebA, ixA, hA, vA)               \
+        X(2) DHTS_STEP6(CL, step - 2, 0, 1, sD, sE, eaB, ebB, ixB, hB, vB)               \
+        X(3) DHTS_STEP6(CL, step - 3, 1, 0, sE, sF, eaC, ebC, ixC, hC, vC)               \
+        X(4) DHTS_STEP6(CL, step - 4, 0, 1, sF, sA, eaA, ebA, ixA, hA, vA)               \
+        X(5) DHTS_STEP6(CL, step - 5, 1, 0, sA, sB, eaB, ebB, ixB, hB, vB)
+    bits3 sA, sB, sC, sD, sE, sF;                        // S set A serves the steps T - 1, T - 7, ..., set F the steps T - 6, T - 12, ...
+    float4 eaA = zero4, ebA = zero4, eaB = zero4, ebB = zero4, eaC = zero4, ebC = zero4;      // exception sets as above
+    unsigned short ixA = 0, ixB = 0, ixC = 0;            // 16 bits as loaded: widened where it is used, not behind the load (a wait)
+    int hA, hB, hC, vA, vB, vC;
+    v2f d0lo = zero2, d0hi = zero2, d1lo = zero2, d1hi = zero2, d2lo = zero2, d2hi = zero2;
+    v2f c1v = g;                                          // "after step T": the incoming cotangent; C0 / C2 are zero
+    const v2f gh_cur = zero2;                             // (DHTS_CELL names it; no per-step cotangent here)
+    DHTS_LOAD_CNT(DHTS_ROW(T - 1), vA);
+    DHTS_LOAD_CNT(DHTS_ROW(T - 2), vB);
+    DHTS_LOAD_CNT(DHTS_ROW(T - 3), vC);
+    DHTS_ARRIVED(hA, vA)
+    DHTS_ARRIVED(hB, vB)
+    DHTS_ARRIVED(hC, vC)
+    DHTS_LOAD_CNT(DHTS_ROW(T - 4), vA);
+    DHTS_LOAD_CNT(DHTS_ROW(T - 5), vB);
+    DHTS_LOAD_CNT(DHTS_ROW(T - 6), vC);
+    DHTS_LOAD_E(DHTS_ROW(T - 1), hA, eaA, ebA, ixA);
+    DHTS_LOAD_E(DHTS_ROW(T - 2), hB, eaB, ebB, ixB);
+    DHTS_LOAD_E(DHTS_ROW(T - 3), hC, eaC, ebC, ixC);
+    DHTS_LOAD_S1(DHTS_ROW(T - 1), sA);
+    DHTS_LOAD_S1(DHTS_ROW(T - 2), sB);
+    DHTS_LOAD_S1(DHTS_ROW(T - 3), sC);
+    DHTS_LOAD_S1(DHTS_ROW(T - 4), sD);
+    DHTS_LOAD_S1(DHTS_ROW(T - 5), sE);
+    DHTS_LOAD_S1(DHTS_ROW(T - 6), sF);
+    __syncthreads();                                     // the zeroed planes
+    DHTS_SCATTER1(T - 1, 0, hA, eaA, ebA, ixA);
+    if (T >= 2) DHTS_SCATTER1(T - 2, 1, hB, eaB, ebB, ixB);
+    DHTS_HAND(0, sA)
+    DHTS_HAND(1, sB)
+    DHTS_ARRIVED(hA, vA)
+    DHTS_ARRIVED(hB, vB)
+    DHTS_LOAD_E(DHTS_ROW(T - 4), hA, eaA, ebA, ixA);
+    DHTS_LOAD_E(DHTS_ROW(T - 5), hB, eaB, ebB, ixB);
+    DHTS_LOAD_CNT(DHTS_ROW(T - 7), vA);
+    DHTS_LOAD_CNT(DHTS_ROW(T - 8), vB);
+    lds_only_barrier();
+    if (vk) DHTS_BLOCKS1(T - 1, 0, sA)
+    DHTS_LOAD_S1(DHTS_ROW(T - 7), sA);
+    lds_only_barrier();                                  // (the first interval scatters step T - 3 into the copy these blocks were read from)
+    // on entry to a round at step s: the blocks of s are in registers, the exceptions of s - 1 and SB of S(s - 1) in LDS copy 1;
+    // sB .. sF, sA = S(s - 1) .. S(s - 6); set C holds E(s - 2), hC of them, and vC is the count of s - 5; set A holds E(s - 3)
+    // and vA the count of s - 6; set B holds E(s - 4) and vB the count of s - 7.
+    // A round is an even number of steps, so the LDS copies are literals.
+    int step = T - 1;
+    // the main loop: every row a step prefetches from exists (step - 5 > 8), so the running pointers move without end-of-tape
+    // clamps and the "is there a step s - 1 / s - 2" tests are literals
+#define DHTS_NO_EXIT(i_)
+#define DHTS_EXIT(i_) if (step < (i_)) break;
+    // The first round stands in front of the loop: the compiler sizes every wait in the loop for the fewest loads that can be
+    // behind the awaited one on any path to it, and on the path from the prologue those are few -- entered from a round, the loop
+    // sees the same loads in flight on both paths, and its back edge carries no wait (the three-set code above drains every load
+    // there: its sets are copied at the back edge).
+    if (step >= 14) {
+        DHTS_ROUND6(0, DHTS_NO_EXIT)
+        step -= 6;
+        for (; step >= 14; step -= 6) { DHTS_ROUND6(0, DHTS_NO_EXIT) }
+    }
+    for (; step >= 0; step -= 6) { DHTS_ROUND6(1, DHTS_EXIT) }
+#undef DHTS_ARRIVED
+#undef DHTS_NO_EXIT
+#undef DHTS_EXIT
+#undef DHTS_ROUND6
+#undef DHTS_STEP6
+#undef DHTS_BLOCKS1
+#undef DHTS_HAND
+#undef DHTS_LOAD_S1
+#undef DHTS_SCATTER1
+    DHTS_LAST
+    }
+#undef DHTS_LAST
 #undef DHTS_BLOCKS
 #undef DHTS_ROW
 #undef DHTS_LOAD_CNT
@@ -938,6 +1109,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #undef DHTS_LOAD_S
 #undef DHTS_LOAD_E
 #undef DHTS_SCATTER
+#undef DHTS_CELL
 #undef DHTS_STEP
     if (vk) { g_r_out[base + k] = g.x; g_y_out[base + k] = g.y; }
     if (!kSched && g_ghost) {
@@ -1432,7 +1604,7 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
         pl.bwd = kMacroBwdFast;
         pl.bwd_block = N <= 64 ? 64 : (N <= 128 ? 128 : (N <= 256 ? 256 : (N <= 512 ? 512 : 1024)));
         pl.bwd_full = !want_hist && N == pl.bwd_block && N >= 128 && N <= 512;
-        pl.lds_bwd = bwd_fast_lds_bytes(pl.bwd_block);
+        pl.lds_bwd = bwd_fast_lds_bytes(pl.bwd_block, !want_hist && !taps);
     } else if (N > 1025 && N <= 2048 && T > 0 && T < (1 << 20) - 1 && !want_hist && !taps) {
         // the two-cells-per-thread sweep (1024 threads): lanes of 1026 .. 2048 cells without per-step cotangents (the step tag has 20 bits)
         pl.bwd = kMacroBwdFast2;
