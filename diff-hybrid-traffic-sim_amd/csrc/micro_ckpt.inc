@@ -46,19 +46,13 @@
 __host__ __device__ inline size_t micro_ckpt_fwd_lds_bytes(int V) { return sizeof(float2) * 2 * (size_t)(V + 1); }
 // reverse, fixed part: the replay's state hand-over S[2][V + 1] and the four cotangent arrays of V + 2 floats
 __host__ __device__ inline size_t micro_ckpt_bwd_fixed_bytes(int V) { return sizeof(float2) * 2 * (size_t)(V + 1) + sizeof(float) * 4 * (size_t)(V + 2); }
-// ... and per step of the segment ring: the entry (e2, e3, l3) per vehicle, with kParams also the pre-step (p, v) over V + 1 slots
-__host__ __device__ inline size_t micro_ckpt_bwd_step_bytes(int V, bool params) {
-    return sizeof(MicroTape3) * (size_t)V + (params ? sizeof(float2) * (size_t)(V + 1) : 0);
+// ... and per step of the segment ring: the entry (e2, e3, l3) per vehicle, with kParams also the pre-step (p, v) over V + 1 slots,
+// in the target forms two more planes of R, the finished cotangent pair of the step (their forward reduces in S: 16 V <= 16 (V + 1))
+__host__ __device__ inline size_t micro_ckpt_bwd_step_bytes(int V, bool params, bool target) {
+    return sizeof(MicroTape3) * (size_t)V + (params ? sizeof(float2) * (size_t)(V + 1) : 0) + (target ? sizeof(float) * 2 * (size_t)V : 0);
 }
-__host__ __device__ inline size_t micro_ckpt_bwd_lds_bytes(int V, int S, bool params) {
-    return micro_ckpt_bwd_fixed_bytes(V) + (size_t)S * micro_ckpt_bwd_step_bytes(V, params);
-}
-// the target forms: two more planes of R per step, the finished cotangent pair of the step; the forward reduces in S (16 V <= 16 (V + 1))
-__host__ __device__ inline size_t micro_ckpt_bwd_target_step_bytes(int V, bool params) {
-    return micro_ckpt_bwd_step_bytes(V, params) + sizeof(float) * 2 * (size_t)V;
-}
-__host__ __device__ inline size_t micro_ckpt_bwd_target_lds_bytes(int V, int S, bool params) {
-    return micro_ckpt_bwd_fixed_bytes(V) + (size_t)S * micro_ckpt_bwd_target_step_bytes(V, params);
+__host__ __device__ inline size_t micro_ckpt_bwd_lds_bytes(int V, int S, bool params, bool target) {
+    return micro_ckpt_bwd_fixed_bytes(V) + (size_t)S * micro_ckpt_bwd_step_bytes(V, params, target);
 }
 // one observed entry pair of the forward: hist - observed in float32, squared and summed in double; a NaN entry is not observed
 __device__ inline void micro_target_add(float p, float v, float tp, float tv, double &ap, double &av) {

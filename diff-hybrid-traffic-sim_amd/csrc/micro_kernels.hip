@@ -584,12 +584,12 @@ struct MicroPlan {
     int fwd_jvp_kmax[2];     // directions a launch may carry, [0] state-only, [1] with t_params
     // the checkpointed pair (dhts_micro_rollout_fwd_ckpt / _bwd_ckpt, micro_ckpt.inc)
     int ckpt_block;          // threads per lane of both kernels: the whole lane, one vehicle per thread
-    int ckpt_max_segment[2]; // steps the reverse kernel's ring can hold within kCkptLdsBudget, [0] state-only, [1] with g_params
-    int ckpt_segment;        // the segment length a caller gets who names none (one value for both reverse kernels: the forward
+    struct Ring {
+        int max_segment[2];  // steps the reverse kernel's ring can hold within kCkptLdsBudget, [0] state-only, [1] with g_params
+        int segment;         // the segment length a caller gets who names none (one value for both reverse kernels: the forward
                              // that writes the checkpoints does not know which of them will read them)
-    // the target forms of the pair (dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target): the same block, a ring of five planes
-    int target_max_segment[2];
-    int target_segment;      // the same rule as ckpt_segment with the target forms' bytes per step
+    } ckpt[2];               // [0] the hist and sampled forms, [1] the target forms (dhts_micro_rollout_*_ckpt_target): the same
+                             // block and rule, a ring with the two target planes
 };
 constexpr size_t kCkptLdsBudget = 160 * 1024;      // LDS of a CU: what one workgroup may take
 // The default segment: the longest, up to kCkptSegmentCap, whose reverse workgroup (sized with the parameter ring) still leaves
@@ -597,12 +597,6 @@ constexpr size_t kCkptLdsBudget = 160 * 1024;      // LDS of a CU: what one work
 // chain of LDS-only barriers that only other resident workgroups hide (DESIGN.md section 4e has the sweep both were set from).
 constexpr int kCkptSegmentCap = 16;
 constexpr int kCkptWavesPerCu = 16;
-static int micro_ckpt_max_segment(int V, bool params) {
-    return (int)((kCkptLdsBudget - micro_ckpt_bwd_fixed_bytes(V)) / micro_ckpt_bwd_step_bytes(V, params));
-}
-static int micro_ckpt_target_max_segment(int V, bool params) {
-    return (int)((kCkptLdsBudget - micro_ckpt_bwd_fixed_bytes(V)) / micro_ckpt_bwd_target_step_bytes(V, params));
-}
 static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     MicroPlan pl;
     // wavefronts per lane: one wave keeps the whole lane free of barriers; with few lanes per SIMD more waves per lane buy
@@ -623,33 +617,44 @@ static MicroPlan micro_plan(const dhts_micro_desc *d, int T, bool has_count) {
     pl.fwd_jvp_kmax[0] = 4;
     pl.fwd_jvp_kmax[1] = 4;
     pl.ckpt_block = padded64(d->capacity);
-    pl.ckpt_max_segment[0] = micro_ckpt_max_segment(d->capacity, false);
-    pl.ckpt_max_segment[1] = micro_ckpt_max_segment(d->capacity, true);
     const int waves = pl.ckpt_block / 64;
     const int groups = (kCkptWavesPerCu + waves - 1) / waves;                    // workgroups per CU that make kCkptWavesPerCu
-    const long long room = (long long)(kCkptLdsBudget / groups) - (long long)micro_ckpt_bwd_fixed_bytes(d->capacity);
-    int S = room > 0 ? (int)(room / (long long)micro_ckpt_bwd_step_bytes(d->capacity, true)) : 0;
-    S = S > kCkptSegmentCap ? kCkptSegmentCap : S;
-    S = S > pl.ckpt_max_segment[1] ? pl.ckpt_max_segment[1] : S;
-    pl.ckpt_segment = S < 1 ? 1 : S;
-    pl.target_max_segment[0] = micro_ckpt_target_max_segment(d->capacity, false);
-    pl.target_max_segment[1] = micro_ckpt_target_max_segment(d->capacity, true);
-    S = room > 0 ? (int)(room / (long long)micro_ckpt_bwd_target_step_bytes(d->capacity, true)) : 0;
-    S = S > kCkptSegmentCap ? kCkptSegmentCap : S;
-    S = S > pl.target_max_segment[1] ? pl.target_max_segment[1] : S;
-    pl.target_segment = S < 1 ? 1 : S;
+    const size_t fixed = micro_ckpt_bwd_fixed_bytes(d->capacity);
+    const long long room = (long long)(kCkptLdsBudget / groups) - (long long)fixed;
+    for (int target = 0; target < 2; ++target) {
+        MicroPlan::Ring &ring = pl.ckpt[target];
+        for (int q = 0; q < 2; ++q)
+            ring.max_segment[q] = (int)((kCkptLdsBudget - fixed) / micro_ckpt_bwd_step_bytes(d->capacity, q != 0, target != 0));
+        int S = room > 0 ? (int)(room / (long long)micro_ckpt_bwd_step_bytes(d->capacity, true, target != 0)) : 0;
+        S = S > kCkptSegmentCap ? kCkptSegmentCap : S;
+        S = S > ring.max_segment[1] ? ring.max_segment[1] : S;
+        ring.segment = S < 1 ? 1 : S;
+    }
     return pl;
 }
 // the segment a call runs with: the caller's, or the plan's for 0; -1 where the reverse kernel's ring cannot hold it
-static int micro_ckpt_segment(const MicroPlan &pl, int segment, bool params) {
-    if (segment < 0 || segment > pl.ckpt_max_segment[params ? 1 : 0]) return -1;
-    return segment == 0 ? pl.ckpt_segment : segment;
-}
-static int micro_ckpt_target_segment(const MicroPlan &pl, int segment, bool params) {
-    if (segment < 0 || segment > pl.target_max_segment[params ? 1 : 0]) return -1;
-    return segment == 0 ? pl.target_segment : segment;
+static int micro_ckpt_segment(const MicroPlan::Ring &ring, int segment, bool params) {
+    if (segment < 0 || segment > ring.max_segment[params ? 1 : 0]) return -1;
+    return segment == 0 ? ring.segment : segment;
 }
 static int micro_ckpt_count(int T, int S) { return T > 0 ? (T + S - 1) / S : 0; }
+// the 8 ints of dhts_micro_ckpt_plan (target false) and dhts_micro_ckpt_target_plan (true)
+static int micro_ckpt_plan_fill(const dhts_micro_desc *d, int T, bool params, int segment, bool target, int32_t plan[8]) {
+    if (!micro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
+    const MicroPlan pl = micro_plan(d, T, false);
+    const int S = micro_ckpt_segment(pl.ckpt[target], segment, params);
+    if (S < 0) return DHTS_E_INVALID;
+    const size_t bwd_lds = micro_ckpt_bwd_lds_bytes(d->capacity, S, params, target);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.ckpt_block;
+    plan[1] = S;
+    plan[2] = pl.ckpt[target].max_segment[params ? 1 : 0];
+    plan[3] = micro_ckpt_count(T, S);
+    plan[4] = (int32_t)micro_ckpt_fwd_lds_bytes(d->capacity);
+    plan[5] = (int32_t)bwd_lds;
+    plan[6] = (int32_t)(kCkptLdsBudget / bwd_lds);
+    return DHTS_OK;
+}
 
 template <bool kCompact, bool kParams = false>
 static int micro_fwd_launch(const dhts_micro_desc *d, int T,
@@ -690,16 +695,27 @@ static int micro_bwd_params_launch(const dhts_micro_desc *d, int T, const float 
            d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, 1, err, ptape, params, g_params);
     return launch_status();
 }
-// n_dir directions as launches of 4, then 2, then 1 (jvp_width: a remainder of 3 rides in ONE launch of 4 with a slot masked)
+// n_dir directions as launches of 4, then 2, then 1 (jvp_width: a remainder of 3 rides in ONE launch of 4 with a slot masked):
+// f(k0, integral_constant<kK>, n_act) per launch -- first direction, the instantiation's slots, the directions it carries -- until
+// one returns false (-> false)
+template <class F>
+static bool micro_jvp_each_group(int n_dir, int kmax, F &&f) {
+    bool ok = true;
+    for (int k0 = 0; k0 < n_dir && ok;) {
+        const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+        pick<4, 2, 1>(kk, [&](auto kv) { ok = f(k0, kv, n_act); });
+        k0 += n_act;
+    }
+    return ok;
+}
 struct MicroJvpGroups { int widest, launches; };
 static MicroJvpGroups micro_jvp_groups(int kmax, int n_dir) {
     MicroJvpGroups g = {0, 0};
-    for (int rem = n_dir; rem > 0;) {
-        const int k = jvp_width(rem, kmax);
-        if (!g.launches) g.widest = k;
-        rem -= k < rem ? k : rem;
+    micro_jvp_each_group(n_dir, kmax, [&](int, auto kv, int) {
+        if (!g.launches) g.widest = decltype(kv)::value;
         ++g.launches;
-    }
+        return true;
+    });
     return g;
 }
 static int micro_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const float *tape, const char *ptape, const int32_t *count,
@@ -708,185 +724,190 @@ static int micro_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const fl
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
     const int L = d->n_lanes, V = d->capacity;
     const size_t dir_state = (size_t)L * V, dir_hist = (size_t)T * L * 2 * V;
-    bool lds_ok = true;
-    for (int k0 = 0; k0 < n_dir && lds_ok;) {
-        const int kk = jvp_width(n_dir - k0, pl.jvp_kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+    const bool lds_ok = micro_jvp_each_group(n_dir, pl.jvp_kmax, [&](int k0, auto kv, int n_act) {
+        constexpr int kK = decltype(kv)::value;
         const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
         float *o_h = t_hist ? t_hist + k0 * dir_hist : nullptr;
-        pick<4, 2, 1>(kk, [&](auto kv) {
-            constexpr int kK = decltype(kv)::value;
-            pick<0, 1>(t_params != nullptr, [&](auto pv) {
-                constexpr bool kParams = decltype(pv)::value != 0;
-                lds_ok = launch_lds(micro_rollout_jvp_kernel<kK, kParams>, L, pl.jvp_block, micro_jvp_lds_bytes(V, kK, kParams), kLdsDefault,
-                                    stream, L, V, T, d->dt, tape, ptape, count, params, t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q,
-                                    n_act, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, o_h, err);
-            });
+        bool ok = true;
+        pick<0, 1>(t_params != nullptr, [&](auto pv) {
+            constexpr bool kParams = decltype(pv)::value != 0;
+            ok = launch_lds(micro_rollout_jvp_kernel<kK, kParams>, L, pl.jvp_block, micro_jvp_lds_bytes(V, kK, kParams), kLdsDefault,
+                            stream, L, V, T, d->dt, tape, ptape, count, params, t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q,
+                            n_act, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, o_h, err);
         });
-        k0 += n_act;
-    }
-    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
-}
-// the same grouping under the fused kernel's own cap; every launch recomputes the primal (same bits), the first one alone is handed
-// hist and the forward's fault record
-static int micro_fwd_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
-                                const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
-                                const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out, float *hist,
-                                float *t_hist, dhts_error *err, dhts_error *err_jvp, void *stream) {
-    const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int L = d->n_lanes, V = d->capacity, kmax = pl.fwd_jvp_kmax[t_params ? 1 : 0];
-    const size_t dir_state = (size_t)L * V, dir_hist = (size_t)T * L * 2 * V;
-    bool lds_ok = true;
-    for (int k0 = 0; k0 < n_dir && lds_ok;) {
-        const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
-        const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
-        float *o_h = t_hist ? t_hist + k0 * dir_hist : nullptr;
-        pick<4, 2, 1>(kk, [&](auto kv) {
-            constexpr int kK = decltype(kv)::value;
-            pick<0, 1>(t_params != nullptr, [&](auto pv) {
-                constexpr bool kParams = decltype(pv)::value != 0;
-                lds_ok = launch_lds(micro_rollout_fwd_jvp_kernel<kK, kParams>, L, pl.fwd_jvp_block, micro_fwd_jvp_lds_bytes(V, kK), kLdsDefault,
-                                    stream, L, V, T, d->dt, p, v, count, params, head, t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q,
-                                    n_act, p_out, v_out, t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, k0 == 0 ? hist : nullptr, o_h,
-                                    k0 == 0 ? err : nullptr, err_jvp);
-            });
-        });
-        k0 += n_act;
-    }
-    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
-}
-// the checkpointed pair: both read block and segment off the plan; the reverse kernel asks for its LDS above 64 KB
-static int micro_ckpt_fwd_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
-                                 const double *params, const double *head, float *p_out, float *v_out, void *ckpt, float *hist,
-                                 dhts_error *err, void *stream) {
-    const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int S = micro_ckpt_segment(pl, segment, false);        // (a forward is valid for every segment some reverse kernel can take)
-    if (S < 0) return DHTS_E_INVALID;
-    const bool ok = launch_lds(micro_rollout_ckpt_fwd_kernel, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity), kLdsDefault,
-                               stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out, (float2 *)ckpt, hist, err);
-    return ok ? launch_status() : DHTS_E_LAUNCH;
-}
-static int micro_ckpt_bwd_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count, const double *params,
-                                 const double *head, const float *g_p, const float *g_v, const float *g_hist, float *g_p_out,
-                                 float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream) {
-    const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int S = micro_ckpt_segment(pl, segment, g_params != nullptr);
-    if (S < 0) return DHTS_E_INVALID;
-    bool ok = true;
-    pick<0, 1>(g_params != nullptr, [&](auto pv) {
-        constexpr bool kParams = decltype(pv)::value != 0;
-        ok = launch_lds(micro_rollout_ckpt_bwd_kernel<kParams>, d->n_lanes, pl.ckpt_block, micro_ckpt_bwd_lds_bytes(d->capacity, S, kParams),
-                        kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, (const float2 *)ckpt, count, params, head, g_p, g_v, g_hist,
-                        g_p_out, g_v_out, g_head, g_params, err);
+        return ok;
     });
-    return ok ? launch_status() : DHTS_E_LAUNCH;
+    return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
-// ---- the sampled forms of the three launches above: same plan, same LDS, samples in place of hist / g_hist / t_hist ----
-// the checks the three entry points share -> the kernels' MicroProbes (n = V without a list); false: DHTS_E_INVALID
+
+// The instantiations of the tape-free kernels, named once in the order the code object has held them since each form was added.  The
+// launches below name them again by form; without this list their order in the code object would follow the launches, and bench.py's
+// fingerprint of the device code (profiles/issue_counters.json) is over its bytes.  A new instantiation goes at the end.
+[[maybe_unused]] static const void *const kMicroTapeFreeKernels[] = {
+    (const void *)micro_rollout_fwd_jvp_kernel<1, true>,
+    (const void *)micro_rollout_fwd_jvp_kernel<1, false>,
+    (const void *)micro_rollout_fwd_jvp_kernel<2, true>,
+    (const void *)micro_rollout_fwd_jvp_kernel<2, false>,
+    (const void *)micro_rollout_fwd_jvp_kernel<4, true>,
+    (const void *)micro_rollout_fwd_jvp_kernel<4, false>,
+    (const void *)micro_rollout_ckpt_bwd_kernel<true>,
+    (const void *)micro_rollout_ckpt_bwd_kernel<false>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, true, true>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, true, false>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, false, true>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, false, false>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, true, true>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, true, false>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, true>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, false>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, true>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, false>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, true>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, false>,
+    (const void *)micro_rollout_ckpt_fwd_samples_kernel<true>,
+    (const void *)micro_rollout_ckpt_fwd_samples_kernel<false>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<true, true>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<true, false>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<false, true>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<false, false>,
+    (const void *)micro_rollout_ckpt_fwd_target_kernel<true>,
+    (const void *)micro_rollout_ckpt_fwd_target_kernel<false>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<true, true>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<true, false>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<false, true>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<false, false>};
+// ---- the tape-free paths: the fused forward + tangent kernel and the checkpointed pair, every form through three launches ----------
+// The form a call runs in, host only (unpacked into the kernels' parameter lists at the launch): what it observes -- the dense
+// history, probe samples or the fit to a target -- with the arrays of that kind, and the recorded leader where the head follows one.
+enum MicroObserve { kObserveHist, kObserveSamples, kObserveTarget };
+struct MicroForm {
+    MicroObserve kind;
+    MicroProbes pr;          // kObserveSamples: which slots, how often
+    float *obs;              // forward: hist or samples
+    float *t_obs;            // fused forward + tangent: t_hist or t_samples
+    const float *g_obs;      // reverse: g_hist or g_samples
+    const float *target;     // kObserveTarget, both directions
+    double *sse;             // ... forward
+    const double *g_sse;     // ... reverse
+    const MicroLead *lead;   // or NULL: the constant head gap
+};
+static MicroForm micro_form_hist(float *hist, float *t_hist, const float *g_hist) {
+    MicroForm f = {};
+    f.kind = kObserveHist; f.obs = hist; f.t_obs = t_hist; f.g_obs = g_hist;
+    return f;
+}
+static MicroForm micro_form_samples(const MicroProbes &pr, float *samples, float *t_samples, const float *g_samples, const MicroLead *lead) {
+    MicroForm f = {};
+    f.kind = kObserveSamples; f.pr = pr; f.obs = samples; f.t_obs = t_samples; f.g_obs = g_samples; f.lead = lead;
+    return f;
+}
+static MicroForm micro_form_target(const float *target, double *sse, const double *g_sse, const MicroLead *lead) {
+    MicroForm f = {};
+    f.kind = kObserveTarget; f.target = target; f.sse = sse; f.g_sse = g_sse; f.lead = lead;
+    return f;
+}
+// the checks the sampled entry points share -> the kernels' MicroProbes (n = V without a list); false: DHTS_E_INVALID
 static bool micro_probes_ok(const dhts_micro_desc *d, const int32_t *probes, int n_probes, int every, MicroProbes *pr) {
     if (every < 1 || (probes && (n_probes < 1 || n_probes > d->capacity))) return false;
     *pr = MicroProbes{probes, probes ? n_probes : d->capacity, every};
     return true;
 }
-static int micro_fwd_jvp_samples_launch(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
-                                        const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
-                                        const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
-                                        const MicroProbes &pr, float *samples, float *t_samples, dhts_error *err, dhts_error *err_jvp,
-                                        void *stream, const MicroLead *lead = nullptr) {
+// ... and the ones every forward and every reverse entry point of the two paths has
+static bool micro_fwd_args_ok(const dhts_micro_desc *d, int T, const float *p, const float *v, const double *params, const float *p_out,
+                              const float *v_out) {
+    return micro_desc_ok(d) && T >= 0 && p && v && params && p_out && v_out;
+}
+static bool micro_bwd_args_ok(const dhts_micro_desc *d, int T, const double *params, const float *g_p, const float *g_v,
+                              const float *g_p_out, const float *g_v_out) {
+    return micro_desc_ok(d) && T >= 0 && params && g_p && g_v && g_p_out && g_v_out;
+}
+static bool micro_tangent_args_ok(int n_dir, const float *t_p, const float *t_v, const float *t_p_out, const float *t_v_out) {
+    return n_dir >= 1 && t_p && t_v && t_p_out && t_v_out;
+}
+// The fused kernel under its own cap on the directions of a launch; every launch recomputes the primal (same bits), the first one
+// alone is handed hist / samples and the forward's fault record, each its own directions of t_head, t_params, t_lead and
+// t_hist / t_samples.
+static int micro_fwd_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                                const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out, const MicroForm &f,
+                                dhts_error *err, dhts_error *err_jvp, void *stream) {
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int L = d->n_lanes, V = d->capacity, kmax = pl.fwd_jvp_kmax[t_params ? 1 : 0];
-    const size_t dir_state = (size_t)L * V, dir_samples = (size_t)(T / pr.every) * L * 2 * pr.n, dir_lead = (size_t)T * L * 2;
-    bool lds_ok = true;
-    for (int k0 = 0; k0 < n_dir && lds_ok;) {
-        const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+    const int L = d->n_lanes, V = d->capacity;
+    const bool samp = f.kind == kObserveSamples;
+    const size_t dir_state = (size_t)L * V, dir_lead = (size_t)T * L * 2;
+    const size_t dir_obs = samp ? (size_t)(T / f.pr.every) * L * 2 * f.pr.n : (size_t)T * L * 2 * V;
+    const bool lds_ok = micro_jvp_each_group(n_dir, pl.fwd_jvp_kmax[t_params ? 1 : 0], [&](int k0, auto kv, int n_act) {
+        constexpr int kK = decltype(kv)::value;
         const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
-        float *o_s = t_samples ? t_samples + k0 * dir_samples : nullptr;
-        MicroLead ld = lead ? *lead : MicroLead{};
+        float *obs = k0 == 0 ? f.obs : nullptr, *t_obs = f.t_obs ? f.t_obs + k0 * dir_obs : nullptr;
+        dhts_error *err_fwd = k0 == 0 ? err : nullptr;
+        MicroLead ld = f.lead ? *f.lead : MicroLead{};
         if (ld.t_lead) ld.t_lead += k0 * dir_lead;       // this launch's directions
-        pick<4, 2, 1>(kk, [&](auto kv) {
-            constexpr int kK = decltype(kv)::value;
-            pick<0, 1>(t_params != nullptr, [&](auto pv) {
-                constexpr bool kParams = decltype(pv)::value != 0;
-                pick<0, 1>(lead != nullptr, [&](auto lv) {
-                    constexpr bool kLead = decltype(lv)::value != 0;
-                    lds_ok = launch_lds(micro_rollout_fwd_jvp_samples_kernel<kK, kParams, kLead>, L, pl.fwd_jvp_block,
-                                        micro_fwd_jvp_lds_bytes(V, kK), kLdsDefault, stream, L, V, T, d->dt, p, v, count, params, head,
-                                        t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q, n_act, p_out, v_out, t_p_out + k0 * dir_state,
-                                        t_v_out + k0 * dir_state, pr, k0 == 0 ? samples : nullptr, o_s, k0 == 0 ? err : nullptr, err_jvp, ld);
-                });
+        bool ok = true;
+        pick<0, 1>(t_params != nullptr, [&](auto pv) {
+            constexpr bool kParams = decltype(pv)::value != 0;
+            auto go = [&](auto kernel, const auto &...observed) {
+                ok = launch_lds(kernel, L, pl.fwd_jvp_block, micro_fwd_jvp_lds_bytes(V, kK), kLdsDefault, stream, L, V, T, d->dt, p, v, count,
+                                params, head, t_p + k0 * dir_state, t_v + k0 * dir_state, a_h, a_q, n_act, p_out, v_out,
+                                t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, observed...);
+            };
+            if (!samp) go(micro_rollout_fwd_jvp_kernel<kK, kParams>, obs, t_obs, err_fwd, err_jvp);
+            else pick<0, 1>(f.lead != nullptr, [&](auto lv) {
+                go(micro_rollout_fwd_jvp_samples_kernel<kK, kParams, decltype(lv)::value != 0>, f.pr, obs, t_obs, err_fwd, err_jvp, ld);
             });
         });
-        k0 += n_act;
-    }
+        return ok;
+    });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
-static int micro_ckpt_fwd_samples_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
-                                         const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
-                                         const MicroProbes &pr, float *samples, dhts_error *err, void *stream,
-                                         const MicroLead *lead = nullptr) {
+// The checkpointed pair: both read block and segment (the form's ring) off the plan; the reverse kernel asks for its LDS above 64 KB.
+static int micro_ckpt_fwd_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                 const double *params, const double *head, float *p_out, float *v_out, void *ckpt, const MicroForm &f,
+                                 dhts_error *err, void *stream) {
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int S = micro_ckpt_segment(pl, segment, false);
+    // (a forward is valid for every segment some reverse kernel of its form can take)
+    const int S = micro_ckpt_segment(pl.ckpt[f.kind == kObserveTarget], segment, false);
     if (S < 0) return DHTS_E_INVALID;
+    const int L = d->n_lanes, V = d->capacity;
+    const MicroLead ld = f.lead ? *f.lead : MicroLead{};
     bool ok = true;
-    pick<0, 1>(lead != nullptr, [&](auto lv) {
+    auto go = [&](auto kernel, const auto &...observed) {
+        ok = launch_lds(kernel, L, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(V), kLdsDefault, stream, L, V, T, S, d->dt, p, v, count, params,
+                        head, p_out, v_out, (float2 *)ckpt, observed...);
+    };
+    if (f.kind == kObserveHist) go(micro_rollout_ckpt_fwd_kernel, f.obs, err);
+    else pick<0, 1>(f.lead != nullptr, [&](auto lv) {
         constexpr bool kLead = decltype(lv)::value != 0;
-        ok = launch_lds(micro_rollout_ckpt_fwd_samples_kernel<kLead>, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity),
-                        kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out, (float2 *)ckpt,
-                        pr, samples, err, lead ? *lead : MicroLead{});
+        if (f.kind == kObserveSamples) go(micro_rollout_ckpt_fwd_samples_kernel<kLead>, f.pr, f.obs, err, ld);
+        else go(micro_rollout_ckpt_fwd_target_kernel<kLead>, f.target, f.sse, err, ld);
     });
     return ok ? launch_status() : DHTS_E_LAUNCH;
 }
-static int micro_ckpt_bwd_samples_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
-                                         const double *params, const double *head, const float *g_p, const float *g_v, const MicroProbes &pr,
-                                         const float *g_samples, float *g_p_out, float *g_v_out, double *g_head, double *g_params,
-                                         dhts_error *err, void *stream, const MicroLead *lead = nullptr) {
+static int micro_ckpt_bwd_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count, const double *params,
+                                 const double *head, const float *g_p, const float *g_v, float *g_p_out, float *g_v_out, double *g_head,
+                                 double *g_params, const MicroForm &f, dhts_error *err, void *stream) {
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int S = micro_ckpt_segment(pl, segment, g_params != nullptr);
+    const bool target = f.kind == kObserveTarget;
+    const int S = micro_ckpt_segment(pl.ckpt[target], segment, g_params != nullptr);
     if (S < 0) return DHTS_E_INVALID;
+    const int L = d->n_lanes, V = d->capacity;
+    const float2 *ck = (const float2 *)ckpt;
+    const MicroLead ld = f.lead ? *f.lead : MicroLead{};
     bool ok = true;
     pick<0, 1>(g_params != nullptr, [&](auto pv) {
         constexpr bool kParams = decltype(pv)::value != 0;
-        pick<0, 1>(lead != nullptr, [&](auto lv) {
+        const size_t lds = micro_ckpt_bwd_lds_bytes(V, S, kParams, target);
+        if (f.kind == kObserveHist)
+            ok = launch_lds(micro_rollout_ckpt_bwd_kernel<kParams>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S, d->dt, ck, count,
+                            params, head, g_p, g_v, f.g_obs, g_p_out, g_v_out, g_head, g_params, err);
+        else pick<0, 1>(f.lead != nullptr, [&](auto lv) {
             constexpr bool kLead = decltype(lv)::value != 0;
-            ok = launch_lds(micro_rollout_ckpt_bwd_samples_kernel<kParams, kLead>, d->n_lanes, pl.ckpt_block,
-                            micro_ckpt_bwd_lds_bytes(d->capacity, S, kParams), kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt,
-                            (const float2 *)ckpt, count, params, head, g_p, g_v, pr, g_samples, g_p_out, g_v_out, g_head, g_params, err,
-                            lead ? *lead : MicroLead{});
-        });
-    });
-    return ok ? launch_status() : DHTS_E_LAUNCH;
-}
-// ---- the target forms of the checkpointed pair: their own segment plan and reverse LDS, the forward's LDS as it is ----
-static int micro_ckpt_fwd_target_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
-                                        const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
-                                        const float *target, double *sse, dhts_error *err, void *stream, const MicroLead *lead) {
-    const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int S = micro_ckpt_target_segment(pl, segment, false);
-    if (S < 0) return DHTS_E_INVALID;
-    bool ok = true;
-    pick<0, 1>(lead != nullptr, [&](auto lv) {
-        constexpr bool kLead = decltype(lv)::value != 0;
-        ok = launch_lds(micro_rollout_ckpt_fwd_target_kernel<kLead>, d->n_lanes, pl.ckpt_block, micro_ckpt_fwd_lds_bytes(d->capacity),
-                        kLdsDefault, stream, d->n_lanes, d->capacity, T, S, d->dt, p, v, count, params, head, p_out, v_out, (float2 *)ckpt,
-                        target, sse, err, lead ? *lead : MicroLead{});
-    });
-    return ok ? launch_status() : DHTS_E_LAUNCH;
-}
-static int micro_ckpt_bwd_target_launch(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
-                                        const double *params, const double *head, const float *g_p, const float *g_v, const float *target,
-                                        const double *g_sse, float *g_p_out, float *g_v_out, double *g_head, double *g_params,
-                                        dhts_error *err, void *stream, const MicroLead *lead) {
-    const MicroPlan pl = micro_plan(d, T, count != nullptr);
-    const int S = micro_ckpt_target_segment(pl, segment, g_params != nullptr);
-    if (S < 0) return DHTS_E_INVALID;
-    bool ok = true;
-    pick<0, 1>(g_params != nullptr, [&](auto pv) {
-        constexpr bool kParams = decltype(pv)::value != 0;
-        pick<0, 1>(lead != nullptr, [&](auto lv) {
-            constexpr bool kLead = decltype(lv)::value != 0;
-            ok = launch_lds(micro_rollout_ckpt_bwd_target_kernel<kParams, kLead>, d->n_lanes, pl.ckpt_block,
-                            micro_ckpt_bwd_target_lds_bytes(d->capacity, S, kParams), kLdsDefault, stream, d->n_lanes, d->capacity, T, S,
-                            d->dt, (const float2 *)ckpt, count, params, head, g_p, g_v, target, g_sse, g_p_out, g_v_out, g_head, g_params,
-                            err, lead ? *lead : MicroLead{});
+            if (f.kind == kObserveSamples)
+                ok = launch_lds(micro_rollout_ckpt_bwd_samples_kernel<kParams, kLead>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S,
+                                d->dt, ck, count, params, head, g_p, g_v, f.pr, f.g_obs, g_p_out, g_v_out, g_head, g_params, err, ld);
+            else
+                ok = launch_lds(micro_rollout_ckpt_bwd_target_kernel<kParams, kLead>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S,
+                                d->dt, ck, count, params, head, g_p, g_v, f.target, f.g_sse, g_p_out, g_v_out, g_head, g_params, err, ld);
         });
     });
     return ok ? launch_status() : DHTS_E_LAUNCH;
@@ -995,10 +1016,10 @@ int dhts_micro_rollout_fwd_jvp(const dhts_micro_desc *d, int T, int n_dir, const
                                const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
                                const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out, float *hist,
                                float *t_hist, dhts_error *err, dhts_error *err_jvp, void *stream) {
-    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !p || !v || !params || !head || !t_p || !t_v || !p_out || !v_out || !t_p_out || !t_v_out)
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !micro_tangent_args_ok(n_dir, t_p, t_v, t_p_out, t_v_out) || !head)
         return DHTS_E_INVALID;
-    return micro_fwd_jvp_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out, hist,
-                                t_hist, err, err_jvp, stream);
+    return micro_fwd_jvp_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out,
+                                micro_form_hist(hist, t_hist, nullptr), err, err_jvp, stream);
 }
 int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]) {
     if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !plan) return DHTS_E_INVALID;
@@ -1013,59 +1034,49 @@ int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want
 }
 // ---- reverse mode from checkpoints, the segment tape in LDS ----------------------------------------------------------------------
 int dhts_micro_ckpt_plan(const dhts_micro_desc *d, int T, int want_params, int segment, int32_t plan[8]) {
-    if (!micro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
-    const MicroPlan pl = micro_plan(d, T, false);
-    const int S = micro_ckpt_segment(pl, segment, want_params != 0);
-    if (S < 0) return DHTS_E_INVALID;
-    const size_t bwd_lds = micro_ckpt_bwd_lds_bytes(d->capacity, S, want_params != 0);
-    for (int k = 0; k < 8; ++k) plan[k] = 0;
-    plan[0] = pl.ckpt_block;
-    plan[1] = S;
-    plan[2] = pl.ckpt_max_segment[want_params != 0 ? 1 : 0];
-    plan[3] = micro_ckpt_count(T, S);
-    plan[4] = (int32_t)micro_ckpt_fwd_lds_bytes(d->capacity);
-    plan[5] = (int32_t)bwd_lds;
-    plan[6] = (int32_t)(kCkptLdsBudget / bwd_lds);
-    return DHTS_OK;
+    return micro_ckpt_plan_fill(d, T, want_params != 0, segment, false, plan);
 }
 size_t dhts_micro_ckpt_bytes(const dhts_micro_desc *d, int T, int segment) {
     if (!micro_desc_ok(d) || T < 0) return 0;
-    const int S = micro_ckpt_segment(micro_plan(d, T, false), segment, false);
+    const int S = micro_ckpt_segment(micro_plan(d, T, false).ckpt[0], segment, false);
     if (S < 0) return 0;
     return (size_t)micro_ckpt_count(T, S) * d->n_lanes * padded64(d->capacity) * sizeof(float2);
 }
 int dhts_micro_rollout_fwd_ckpt(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
                                 const double *params, const double *head, float *p_out, float *v_out, void *ckpt, float *hist,
                                 dhts_error *err, void *stream) {
-    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || !head || !p_out || !v_out || (T > 0 && !ckpt)) return DHTS_E_INVALID;
-    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt, hist, err, stream);
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !head || (T > 0 && !ckpt)) return DHTS_E_INVALID;
+    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt, micro_form_hist(hist, nullptr, nullptr), err,
+                                 stream);
 }
 int dhts_micro_rollout_bwd_ckpt(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count, const double *params,
                                 const double *head, const float *g_p, const float *g_v, const float *g_hist, float *g_p_out,
                                 float *g_v_out, double *g_head, double *g_params, dhts_error *err, void *stream) {
-    if (!micro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !params || !head || !g_p || !g_v || !g_p_out || !g_v_out) return DHTS_E_INVALID;
-    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, g_params, err, stream);
+    if (!micro_bwd_args_ok(d, T, params, g_p, g_v, g_p_out, g_v_out) || (T > 0 && !ckpt) || !head) return DHTS_E_INVALID;
+    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, g_p_out, g_v_out, g_head, g_params,
+                                 micro_form_hist(nullptr, nullptr, g_hist), err, stream);
 }
 // ---- probe samples on the two tape-free paths --------------------------------------------------------------------------------------
 int dhts_micro_rollout_fwd_ckpt_samples(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
                                         const double *params, const double *head, float *p_out, float *v_out, void *ckpt,
                                         const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err, void *stream) {
     MicroProbes pr;
-    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || !head || !p_out || !v_out || !micro_probes_ok(d, probes, n_probes, every, &pr) ||
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !head || !micro_probes_ok(d, probes, n_probes, every, &pr) ||
         (T / every > 0 && !samples))
         return DHTS_E_INVALID;
-    return micro_ckpt_fwd_samples_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt, pr, samples, err, stream);
+    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt,
+                                 micro_form_samples(pr, samples, nullptr, nullptr, nullptr), err, stream);
 }
 int dhts_micro_rollout_bwd_ckpt_samples(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
                                         const double *params, const double *head, const float *g_p, const float *g_v, const int32_t *probes,
                                         int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out, double *g_head,
                                         double *g_params, dhts_error *err, void *stream) {
     MicroProbes pr;
-    if (!micro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !params || !head || !g_p || !g_v || !g_p_out || !g_v_out ||
+    if (!micro_bwd_args_ok(d, T, params, g_p, g_v, g_p_out, g_v_out) || (T > 0 && !ckpt) || !head ||
         !micro_probes_ok(d, probes, n_probes, every, &pr) || (T / every > 0 && !g_samples))
         return DHTS_E_INVALID;
-    return micro_ckpt_bwd_samples_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, pr, g_samples, g_p_out, g_v_out, g_head, g_params,
-                                         err, stream);
+    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, g_p_out, g_v_out, g_head, g_params,
+                                 micro_form_samples(pr, nullptr, nullptr, g_samples, nullptr), err, stream);
 }
 int dhts_micro_rollout_fwd_jvp_samples(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
                                        const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
@@ -1073,11 +1084,11 @@ int dhts_micro_rollout_fwd_jvp_samples(const dhts_micro_desc *d, int T, int n_di
                                        const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
                                        dhts_error *err_jvp, void *stream) {
     MicroProbes pr;
-    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !p || !v || !params || !head || !t_p || !t_v || !p_out || !v_out || !t_p_out || !t_v_out ||
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !micro_tangent_args_ok(n_dir, t_p, t_v, t_p_out, t_v_out) || !head ||
         !micro_probes_ok(d, probes, n_probes, every, &pr) || (T / every > 0 && (!samples || !t_samples)))
         return DHTS_E_INVALID;
-    return micro_fwd_jvp_samples_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out, pr,
-                                        samples, t_samples, err, err_jvp, stream);
+    return micro_fwd_jvp_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out,
+                                micro_form_samples(pr, samples, t_samples, nullptr, nullptr), err, err_jvp, stream);
 }
 // ---- a recorded leader on the two tape-free paths: the kLead forms of the three sampled kernels ---------------------------------------
 int dhts_micro_rollout_fwd_ckpt_lead(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
@@ -1085,63 +1096,50 @@ int dhts_micro_rollout_fwd_ckpt_lead(const dhts_micro_desc *d, int T, int segmen
                                      void *ckpt, const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err,
                                      void *stream) {
     MicroProbes pr;
-    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || (T > 0 && !lead) || !p_out || !v_out ||
-        !micro_probes_ok(d, probes, n_probes, every, &pr))
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || (T > 0 && !lead) || !micro_probes_ok(d, probes, n_probes, every, &pr))
         return DHTS_E_INVALID;
     const MicroLead ld = {lead, lead_length, nullptr, nullptr};
-    return micro_ckpt_fwd_samples_launch(d, T, segment, p, v, count, params, nullptr, p_out, v_out, ckpt, pr, samples, err, stream, &ld);
+    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, nullptr, p_out, v_out, ckpt,
+                                 micro_form_samples(pr, samples, nullptr, nullptr, &ld), err, stream);
 }
 int dhts_micro_rollout_bwd_ckpt_lead(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
                                      const double *params, const float *lead, const double *lead_length, const float *g_p, const float *g_v,
                                      const int32_t *probes, int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out,
                                      float *g_lead, double *g_params, dhts_error *err, void *stream) {
     MicroProbes pr;
-    if (!micro_desc_ok(d) || T < 0 || (T > 0 && (!ckpt || !lead || !g_lead)) || !params || !g_p || !g_v || !g_p_out || !g_v_out ||
+    if (!micro_bwd_args_ok(d, T, params, g_p, g_v, g_p_out, g_v_out) || (T > 0 && (!ckpt || !lead || !g_lead)) ||
         !micro_probes_ok(d, probes, n_probes, every, &pr))
         return DHTS_E_INVALID;
     const MicroLead ld = {lead, lead_length, g_lead, nullptr};
-    return micro_ckpt_bwd_samples_launch(d, T, segment, ckpt, count, params, nullptr, g_p, g_v, pr, g_samples, g_p_out, g_v_out, nullptr,
-                                         g_params, err, stream, &ld);
+    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, nullptr, g_p, g_v, g_p_out, g_v_out, nullptr, g_params,
+                                 micro_form_samples(pr, nullptr, nullptr, g_samples, &ld), err, stream);
 }
 // ---- the trajectory-fit loss inside the checkpointed pair: the kTarget forms ------------------------------------------------------------
 int dhts_micro_ckpt_target_plan(const dhts_micro_desc *d, int T, int want_params, int segment, int32_t plan[8]) {
-    if (!micro_desc_ok(d) || T < 0 || !plan) return DHTS_E_INVALID;
-    const MicroPlan pl = micro_plan(d, T, false);
-    const int S = micro_ckpt_target_segment(pl, segment, want_params != 0);
-    if (S < 0) return DHTS_E_INVALID;
-    const size_t bwd_lds = micro_ckpt_bwd_target_lds_bytes(d->capacity, S, want_params != 0);
-    for (int k = 0; k < 8; ++k) plan[k] = 0;
-    plan[0] = pl.ckpt_block;
-    plan[1] = S;
-    plan[2] = pl.target_max_segment[want_params != 0 ? 1 : 0];
-    plan[3] = micro_ckpt_count(T, S);
-    plan[4] = (int32_t)micro_ckpt_fwd_lds_bytes(d->capacity);
-    plan[5] = (int32_t)bwd_lds;
-    plan[6] = (int32_t)(kCkptLdsBudget / bwd_lds);
-    return DHTS_OK;
+    return micro_ckpt_plan_fill(d, T, want_params != 0, segment, true, plan);
 }
 int dhts_micro_rollout_fwd_ckpt_target(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
                                        const double *params, const double *head, const float *lead, const double *lead_length,
                                        float *p_out, float *v_out, void *ckpt, const float *target, double *sse, dhts_error *err,
                                        void *stream) {
     // head or lead, exactly one; T = 0 reads no row of lead, and a NULL lead is then accepted as dhts_micro_rollout_fwd_ckpt_lead accepts it
-    if (!micro_desc_ok(d) || T < 0 || !p || !v || !params || (head && (lead || lead_length)) || (!head && !lead && T > 0) || !p_out ||
-        !v_out || (T > 0 && !target) || !sse)
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || (head && (lead || lead_length)) || (!head && !lead && T > 0) ||
+        (T > 0 && !target) || !sse)
         return DHTS_E_INVALID;
     const MicroLead ld = {lead, lead_length, nullptr, nullptr};
-    return micro_ckpt_fwd_target_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt, target, sse, err, stream,
-                                        head ? nullptr : &ld);
+    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, head, p_out, v_out, ckpt,
+                                 micro_form_target(target, sse, nullptr, head ? nullptr : &ld), err, stream);
 }
 int dhts_micro_rollout_bwd_ckpt_target(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
                                        const double *params, const double *head, const float *lead, const double *lead_length,
                                        const float *g_p, const float *g_v, const float *target, const double *g_sse, float *g_p_out,
                                        float *g_v_out, double *g_head, float *g_lead, double *g_params, dhts_error *err, void *stream) {
-    if (!micro_desc_ok(d) || T < 0 || (T > 0 && (!ckpt || !target)) || !params || (head && (lead || lead_length || g_lead)) ||
-        (!head && (g_head || (T > 0 && (!lead || !g_lead)))) || !g_p || !g_v || !g_p_out || !g_v_out)
+    if (!micro_bwd_args_ok(d, T, params, g_p, g_v, g_p_out, g_v_out) || (T > 0 && (!ckpt || !target)) ||
+        (head && (lead || lead_length || g_lead)) || (!head && (g_head || (T > 0 && (!lead || !g_lead)))))
         return DHTS_E_INVALID;
     const MicroLead ld = {lead, lead_length, g_lead, nullptr};
-    return micro_ckpt_bwd_target_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, target, g_sse, g_p_out, g_v_out, g_head, g_params,
-                                        err, stream, head ? nullptr : &ld);
+    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, head, g_p, g_v, g_p_out, g_v_out, g_head, g_params,
+                                 micro_form_target(target, nullptr, g_sse, head ? nullptr : &ld), err, stream);
 }
 int dhts_micro_rollout_fwd_jvp_lead(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
                                     const double *params, const float *lead, const double *lead_length, const float *t_p, const float *t_v,
@@ -1149,12 +1147,12 @@ int dhts_micro_rollout_fwd_jvp_lead(const dhts_micro_desc *d, int T, int n_dir, 
                                     const int32_t *probes, int n_probes, int every, float *samples, float *t_samples, dhts_error *err,
                                     dhts_error *err_jvp, void *stream) {
     MicroProbes pr;
-    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !p || !v || !params || (T > 0 && !lead) || !t_p || !t_v || !p_out || !v_out || !t_p_out ||
-        !t_v_out || !micro_probes_ok(d, probes, n_probes, every, &pr) || (samples == nullptr) != (t_samples == nullptr))
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !micro_tangent_args_ok(n_dir, t_p, t_v, t_p_out, t_v_out) ||
+        (T > 0 && !lead) || !micro_probes_ok(d, probes, n_probes, every, &pr) || (samples == nullptr) != (t_samples == nullptr))
         return DHTS_E_INVALID;
     const MicroLead ld = {lead, lead_length, nullptr, t_lead};
-    return micro_fwd_jvp_samples_launch(d, T, n_dir, p, v, count, params, nullptr, t_p, t_v, nullptr, t_params, p_out, v_out, t_p_out, t_v_out,
-                                        pr, samples, t_samples, err, err_jvp, stream, &ld);
+    return micro_fwd_jvp_launch(d, T, n_dir, p, v, count, params, nullptr, t_p, t_v, nullptr, t_params, p_out, v_out, t_p_out, t_v_out,
+                                micro_form_samples(pr, samples, t_samples, nullptr, &ld), err, err_jvp, stream);
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)
 int dhts_micro_step_fwd(const dhts_micro_desc *d,

@@ -201,9 +201,7 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
         if fused:                            # one kernel, no tape
             err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
             if sampling is not None:         # the sampled kernel form: no history of either kind
-                slots = sampling[0]
-                if isinstance(slots, list):
-                    slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+                slots = ops._device_slots(sampling[0], dev)
                 prim, tang = ops.micro_rollout_fwd_jvp_samples(desc, T, p0c, v0c, par, head.detach(), tp, tv, slots, sampling[1], count=count,
                                                                t_head=th, t_params=tq, err=err, err_jvp=err_jvp)
                 if check_faults:
@@ -275,8 +273,7 @@ def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t
         tq = None if t_params is None else tan(t_params, (K, 6, L, V), torch.float64)
         ll = None if lead_length is None else lead_length.detach().to(device=dev).contiguous()
         slots, ev = sampling if sampling is not None else (None, 1)
-        if isinstance(slots, list):
-            slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        slots = ops._device_slots(slots, dev)
         err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
         prim, tang = ops.micro_rollout_fwd_jvp_lead(desc, T, p0c, v0c, params.detach(), ops._f32c(lead.detach(), "lead"), tp, tv, slots, ev,
                                                     lead_length=ll, count=count, t_lead=tl, t_params=tq, observe=sampling is not None,

@@ -850,8 +850,7 @@ def micro_rollout_jvp(desc, T, tape, t_p, t_v, count=None, t_head=None, ptape=No
     t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
     if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
         raise ValueError("count must be int32 [L]")
-    if t_head is not None and (t_head.dtype != torch.float64 or tuple(t_head.shape) != (K, L, 2) or not t_head.is_contiguous()):
-        raise ValueError("t_head must be a contiguous float64 [%d][%d][2]" % (K, L))
+    _dir_arg("t_head", t_head, torch.float64, (K, L, 2))
     if ptape is not None or params is not None or t_params is not None:
         if ptape is None or params is None or t_params is None:
             raise ValueError("ptape, params and t_params go together")
@@ -859,8 +858,7 @@ def micro_rollout_jvp(desc, T, tape, t_p, t_v, count=None, t_head=None, ptape=No
             raise ValueError("ptape must be float32 [micro_param_tape_numel(desc, T)]")
         if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V) or not params.is_contiguous():
             raise ValueError("params must be a contiguous float64 [6][L][V]")
-        if t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous():
-            raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
+        _dir_arg("t_params", t_params, torch.float64, (K, 6, L, V))
     if T > 0 and tape is None:
         raise ValueError("a sweep of T > 0 steps needs the rollout's tape")
     if tape is not None and (tape.dtype != torch.float32 or tape.numel() != micro_tape_numel(desc, T)):
@@ -898,51 +896,7 @@ def micro_rollout_fwd_jvp(desc, T, p, v, params, head, t_p, t_v, count=None, t_h
     err: the forward's fault record (collisions), err_jvp: the tangent sweep's (the earliest non-finite tangent); each may be None.
     out: (p_out, v_out, t_p_out, t_v_out[, hist, t_hist]) buffers to fill; hist [T][L][2][V] and t_hist [K][T][L][2][V] are allocated
     with want_hist unless handed in.  Returns ((pT, vT, hist), (t_pT, t_vT, t_hist)), the histories None unless asked for."""
-    L, V, T = desc.n_lanes, desc.capacity, int(T)
-    p, v = _f32c(p, "p"), _f32c(v, "v")
-    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
-        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
-    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
-        raise ValueError("params must be float64 [6][L][V]")
-    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
-        raise ValueError("head must be float64 [L][2]")
-    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
-        raise ValueError("count must be int32 [L]")
-    if T < 0:
-        raise ValueError("T must be >= 0")
-    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
-        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
-    K = int(t_p.shape[0])
-    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
-    if t_head is not None and (t_head.dtype != torch.float64 or tuple(t_head.shape) != (K, L, 2) or not t_head.is_contiguous()):
-        raise ValueError("t_head must be a contiguous float64 [%d][%d][2]" % (K, L))
-    if t_params is not None and (t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous()):
-        raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
-    params, head = params.contiguous(), head.contiguous()
-    out = tuple(out) if out is not None else ()
-    if len(out) not in (0, 4, 6):
-        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, hist, t_hist])")
-    hist, t_hist = (out[4], out[5]) if len(out) == 6 else (None, None)
-    for name, t, shape in (("hist", hist, (T, L, 2, V)), ("t_hist", t_hist, (K, T, L, 2, V))):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, shape))
-    if want_hist and hist is None:
-        hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=p.device)
-    if want_hist and t_hist is None:
-        t_hist = torch.empty(K, T, L, 2, V, dtype=torch.float32, device=p.device)
-    if out:
-        state = out[:4]
-        for name, t, like in zip(("p_out", "v_out", "t_p_out", "t_v_out"), state, (p, v, t_p, t_v)):
-            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
-    else:
-        state = (torch.empty_like(p), torch.empty_like(v), torch.empty_like(t_p), torch.empty_like(t_v))
-    hptr = [None if h is None or not h.numel() else _ptr(h) for h in (hist, t_hist)]      # (T = 0: an empty tensor has no address)
-    check(_lib.lib().dhts_micro_rollout_fwd_jvp(C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head), _ptr(t_p),
-                                                _ptr(t_v), _ptr(t_head), _ptr(t_params), _ptr(state[0]), _ptr(state[1]), _ptr(state[2]),
-                                                _ptr(state[3]), hptr[0], hptr[1], _ptr(err), _ptr(err_jvp), _stream()),
-          "dhts_micro_rollout_fwd_jvp")
-    return (state[0], state[1], hist), (state[2], state[3], t_hist)
+    return _micro_fwd_jvp("hist", desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, head=head, t_head=t_head, want_hist=want_hist)
 
 
 def micro_fwd_jvp_plan(desc, T, n_dir, want_params=False):
@@ -962,15 +916,7 @@ def micro_ckpt_plan(desc, T, want_params=False, segment=0):
     own for segment = 0), the longest one the reverse kernel's LDS holds (shorter with want_params), the number of checkpoints
     ceil(T / segment), the dynamic LDS bytes of the two kernels and the reverse workgroups a CU holds by LDS.  ValueError: a segment
     outside 0 .. max_segment."""
-    plan = (C.c_int32 * 8)()
-    if not 0 <= int(segment) <= 0x7fffffff:
-        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
-    status = _lib.lib().dhts_micro_ckpt_plan(C.byref(desc), int(T), int(bool(want_params)), int(segment), C.byref(plan))
-    if status == _lib.E_INVALID and int(T) >= 0:
-        raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment for %d vehicle slots%s" %
-                         (desc.capacity, " with the parameter gradient" if want_params else ""))
-    check(status, "dhts_micro_ckpt_plan")
-    return dict(zip(_MICRO_CKPT_PLAN_KEYS, list(plan)))
+    return _micro_ckpt_plan("dhts_micro_ckpt_plan", "", desc, T, want_params, segment)
 
 
 def micro_ckpt_numel(desc, T, segment=0):
@@ -978,57 +924,29 @@ def micro_ckpt_numel(desc, T, segment=0):
     return _lib.lib().dhts_micro_ckpt_bytes(C.byref(desc), int(T), int(segment)) // 4
 
 
-def micro_rollout_fwd_ckpt(desc, T, p, v, params, head, ckpt, count=None, segment=0, hist=None, err=None, out=None):
-    """micro_rollout_fwd that fills the checkpoint buffer `ckpt` (float32 [micro_ckpt_numel(desc, T, segment)]) instead of a tape
-    (dhts_micro_rollout_fwd_ckpt): the same (pT, vT) and hist, bit for bit."""
-    L, V = desc.n_lanes, desc.capacity
-    micro_ckpt_plan(desc, T, False, segment)
-    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
-        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
-    p, v = _f32c(p, "p"), _f32c(v, "v")
-    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
-        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
-    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
-        raise ValueError("params must be float64 [6][L][V]")
-    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
-        raise ValueError("head must be float64 [L][2]")
-    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
-        raise ValueError("count must be int32 [L]")
-    params, head = params.contiguous(), head.contiguous()
-    if out is None:
-        out = (torch.empty_like(p), torch.empty_like(v))
-    check(_lib.lib().dhts_micro_rollout_fwd_ckpt(C.byref(desc), int(T), int(segment), _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
-                                                 _ptr(out[0]), _ptr(out[1]), _ptr(ckpt) if ckpt.numel() else None,
-                                                 _ptr(hist) if hist is not None and hist.numel() else None, _ptr(err), _stream()),
-          "dhts_micro_rollout_fwd_ckpt")
-    return out
+# ---- the tape-free paths' raw layer: every check once, then _micro_ckpt_fwd / _micro_ckpt_bwd / _micro_fwd_jvp for every form -----------
+# A form: "hist" (the dense history, a constant head gap), "samples" (probe samples in its place), "lead" (samples, the head follows a
+# recorded leader) or "target" (the trajectory fit of the checkpointed pair; head or lead).
 
 
-def micro_rollout_bwd_ckpt(desc, T, ckpt, params, head, g_p, g_v, count=None, segment=0, g_hist=None, err=None, out=None, g_head=None,
-                           g_params=None):
-    """Reverse sweep from the checkpoints of micro_rollout_fwd_ckpt -> (g_p0, g_v0, g_head): micro_rollout_bwd's bits.  params, head,
-    count, segment: the forward's.  g_params (float64 [6][L][V], filled here): also the gradient w.r.t. the driver parameters."""
-    L, V = desc.n_lanes, desc.capacity
-    micro_ckpt_plan(desc, T, g_params is not None, segment)
-    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
-        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
-    for name, t in (("params", params), ("g_params", g_params)):
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
-    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2) or not head.is_contiguous():
-        raise ValueError("head must be a contiguous float64 [L][2]")
-    g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
-    if out is None:
-        out = (torch.empty_like(g_p), torch.empty_like(g_v))
-    if g_head is None:
-        g_head = torch.zeros(L, 2, dtype=torch.float64, device=g_p.device)
-    check(_lib.lib().dhts_micro_rollout_bwd_ckpt(C.byref(desc), int(T), int(segment), _ptr(ckpt) if ckpt.numel() else None, _ptr(count),
-                                                 _ptr(params), _ptr(head), _ptr(g_p), _ptr(g_v), _ptr(g_hist), _ptr(out[0]), _ptr(out[1]),
-                                                 _ptr(g_head), _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt")
-    return out[0], out[1], g_head
+def _micro_ckpt_plan(entry, forms, desc, T, want_params, segment):
+    """micro_ckpt_plan (forms "") and micro_ckpt_target_plan (" of the target forms")."""
+    plan = (C.c_int32 * 8)()
+    if not 0 <= int(segment) <= 0x7fffffff:
+        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
+    status = getattr(_lib.lib(), entry)(C.byref(desc), int(T), int(bool(want_params)), int(segment), C.byref(plan))
+    if status == _lib.E_INVALID and int(T) >= 0:
+        raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment%s for %d vehicle slots%s" %
+                         (forms, desc.capacity, " with the parameter gradient" if want_params else ""))
+    check(status, entry)
+    return dict(zip(_MICRO_CKPT_PLAN_KEYS, list(plan)))
 
 
-# ---- probe samples on the two tape-free paths (dhts_micro_rollout_*_samples) ------------------------------------------------------------
+def _data(t):
+    """The address the library gets for an optional array: NULL for None and for a tensor without an element (it has no address)."""
+    return None if t is None or not t.numel() else _ptr(t)
+
+
 def _samples_shape(desc, T, probes, every):
     """The raw wrappers' checks of (probes, every) -> (rows, columns, n_probes for the C call).  probes: None (every slot) or a CUDA int32
     tensor of distinct slots, used as it is (include/dhts.h: an entry outside [0, V) is skipped by the kernels)."""
@@ -1045,124 +963,16 @@ def _samples_shape(desc, T, probes, every):
     return int(T) // every, int(probes.numel()), int(probes.numel())
 
 
-def _samples_buffer(name, t, shape, device):
-    """A samples array handed in (checked) or a new zero-filled one: the kernels write live probe slots only."""
+def _obs_buffer(name, t, shape, device, new=torch.zeros):
+    """An observation array handed in (checked), or one made by `new` (None: none).  Samples are zero-filled: the kernels write live
+    probe slots only."""
     if t is None:
-        return torch.zeros(shape, dtype=torch.float32, device=device)
+        return None if new is None else new(shape, dtype=torch.float32, device=device)
     if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
         raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(shape)))
     return t
 
 
-def micro_rollout_fwd_ckpt_samples(desc, T, p, v, params, head, ckpt, probes, every, count=None, segment=0, samples=None, err=None, out=None):
-    """micro_rollout_fwd_ckpt that writes, instead of a history, samples [T // every][L][2][P] (dhts_micro_rollout_fwd_ckpt_samples,
-    include/dhts.h): row j = (p, v) of slot probes[i] after step (j + 1) every - 1.  probes: a CUDA int32 tensor of distinct slots (not
-    validated: an entry outside [0, V) leaves its column as it is) or None = every slot.  samples: allocated zero-filled unless handed
-    in (live probe slots only are written).  ckpt=None: no checkpoint is kept.  Returns (pT, vT, samples)."""
-    L, V = desc.n_lanes, desc.capacity
-    rows, n, n_probes = _samples_shape(desc, T, probes, every)
-    micro_ckpt_plan(desc, T, False, segment)
-    if ckpt is not None and (ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous()):
-        raise ValueError("ckpt must be None or a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
-    p, v = _f32c(p, "p"), _f32c(v, "v")
-    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
-        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
-    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
-        raise ValueError("params must be float64 [6][L][V]")
-    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
-        raise ValueError("head must be float64 [L][2]")
-    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
-        raise ValueError("count must be int32 [L]")
-    params, head = params.contiguous(), head.contiguous()
-    samples = _samples_buffer("samples", samples, (rows, L, 2, n), p.device)
-    if out is None:
-        out = (torch.empty_like(p), torch.empty_like(v))
-    check(_lib.lib().dhts_micro_rollout_fwd_ckpt_samples(C.byref(desc), int(T), int(segment), _ptr(p), _ptr(v), _ptr(count), _ptr(params),
-                                                         _ptr(head), _ptr(out[0]), _ptr(out[1]),
-                                                         _ptr(ckpt) if ckpt is not None and ckpt.numel() else None, _ptr(probes), n_probes,
-                                                         every, _ptr(samples) if samples.numel() else None, _ptr(err), _stream()),
-          "dhts_micro_rollout_fwd_ckpt_samples")
-    return out[0], out[1], samples
-
-
-def micro_rollout_bwd_ckpt_samples(desc, T, ckpt, params, head, g_p, g_v, probes, every, g_samples, count=None, segment=0, err=None,
-                                   out=None, g_head=None, g_params=None):
-    """micro_rollout_bwd_ckpt with the cotangent g_samples [T // every][L][2][P] of micro_rollout_fwd_ckpt_samples' samples in place of
-    g_hist (dhts_micro_rollout_bwd_ckpt_samples): it enters the sweep at the sampled steps, at live probe slots.  probes, every,
-    count, segment: the forward's.  Returns (g_p0, g_v0, g_head)."""
-    L, V = desc.n_lanes, desc.capacity
-    rows, n, n_probes = _samples_shape(desc, T, probes, every)
-    micro_ckpt_plan(desc, T, g_params is not None, segment)
-    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
-        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
-    for name, t in (("params", params), ("g_params", g_params)):
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
-    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2) or not head.is_contiguous():
-        raise ValueError("head must be a contiguous float64 [L][2]")
-    if g_samples is None:
-        raise ValueError("g_samples is required: float32 [T // every][L][2][P]")
-    g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
-    g_samples = _samples_buffer("g_samples", g_samples, (rows, L, 2, n), g_p.device)
-    if out is None:
-        out = (torch.empty_like(g_p), torch.empty_like(g_v))
-    if g_head is None:
-        g_head = torch.zeros(L, 2, dtype=torch.float64, device=g_p.device)
-    check(_lib.lib().dhts_micro_rollout_bwd_ckpt_samples(C.byref(desc), int(T), int(segment), _ptr(ckpt) if ckpt.numel() else None,
-                                                         _ptr(count), _ptr(params), _ptr(head), _ptr(g_p), _ptr(g_v), _ptr(probes), n_probes,
-                                                         every, _ptr(g_samples) if g_samples.numel() else None, _ptr(out[0]), _ptr(out[1]),
-                                                         _ptr(g_head), _ptr(g_params), _ptr(err), _stream()),
-          "dhts_micro_rollout_bwd_ckpt_samples")
-    return out[0], out[1], g_head
-
-
-def micro_rollout_fwd_jvp_samples(desc, T, p, v, params, head, t_p, t_v, probes, every, count=None, t_head=None, t_params=None, err=None,
-                                  err_jvp=None, out=None):
-    """micro_rollout_fwd_jvp that writes, instead of the histories, samples [T // every][L][2][P] and t_samples [K][T // every][L][2][P]
-    (dhts_micro_rollout_fwd_jvp_samples): probes, every as micro_rollout_fwd_ckpt_samples.  out: (p_out, v_out, t_p_out, t_v_out[,
-    samples, t_samples]); the sample arrays are allocated zero-filled unless handed in (samples: live probe slots only are written;
-    t_samples: every probe slot, 0 at or beyond count).  Returns ((pT, vT, samples), (t_pT, t_vT, t_samples))."""
-    L, V, T = desc.n_lanes, desc.capacity, int(T)
-    rows, n, n_probes = _samples_shape(desc, T, probes, every)
-    p, v = _f32c(p, "p"), _f32c(v, "v")
-    if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
-        raise ValueError("p, v must have shape (%d, %d)" % (L, V))
-    if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
-        raise ValueError("params must be float64 [6][L][V]")
-    if head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
-        raise ValueError("head must be float64 [L][2]")
-    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
-        raise ValueError("count must be int32 [L]")
-    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
-        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
-    K = int(t_p.shape[0])
-    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
-    if t_head is not None and (t_head.dtype != torch.float64 or tuple(t_head.shape) != (K, L, 2) or not t_head.is_contiguous()):
-        raise ValueError("t_head must be a contiguous float64 [%d][%d][2]" % (K, L))
-    if t_params is not None and (t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous()):
-        raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
-    params, head = params.contiguous(), head.contiguous()
-    out = tuple(out) if out is not None else ()
-    if len(out) not in (0, 4, 6):
-        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, samples, t_samples])")
-    samples = _samples_buffer("samples", out[4] if len(out) == 6 else None, (rows, L, 2, n), p.device)
-    t_samples = _samples_buffer("t_samples", out[5] if len(out) == 6 else None, (K, rows, L, 2, n), p.device)
-    if out:
-        state = out[:4]
-        for name, t, like in zip(("p_out", "v_out", "t_p_out", "t_v_out"), state, (p, v, t_p, t_v)):
-            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
-    else:
-        state = (torch.empty_like(p), torch.empty_like(v), torch.empty_like(t_p), torch.empty_like(t_v))
-    sptr = [_ptr(s) if s.numel() else None for s in (samples, t_samples)]      # (no row: an empty tensor has no address)
-    check(_lib.lib().dhts_micro_rollout_fwd_jvp_samples(C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
-                                                        _ptr(t_p), _ptr(t_v), _ptr(t_head), _ptr(t_params), _ptr(state[0]), _ptr(state[1]),
-                                                        _ptr(state[2]), _ptr(state[3]), _ptr(probes), n_probes, every, sptr[0], sptr[1],
-                                                        _ptr(err), _ptr(err_jvp), _stream()), "dhts_micro_rollout_fwd_jvp_samples")
-    return (state[0], state[1], samples), (state[2], state[3], t_samples)
-
-
-# ---- a recorded leader on the two tape-free paths (dhts_micro_rollout_*_lead) ------------------------------------------------------------
 def _lead_args(desc, T, lead, lead_length):
     """The raw wrappers' checks of (lead, lead_length): lead a contiguous float32 [T][L][2], lead_length None or a contiguous float64 [L]."""
     L = desc.n_lanes
@@ -1176,207 +986,152 @@ def _lead_args(desc, T, lead, lead_length):
         raise ValueError("lead_length must be None or a contiguous float64 tensor of shape (%d,)" % L)
 
 
-def _lead_state_args(desc, p, v, params, count):
+def _head_arg(desc, head, contiguous):
+    if head.dtype != torch.float64 or tuple(head.shape) != (desc.n_lanes, 2) or (contiguous and not head.is_contiguous()):
+        raise ValueError("head must be %sfloat64 [L][2]" % ("a contiguous " if contiguous else ""))
+
+
+def _target_args(desc, T, target, head, lead):
+    """What the target forms check first: head or lead, exactly one, and target, a contiguous float32 [T][L][2][V]."""
+    L, V = desc.n_lanes, desc.capacity
+    if (head is None) == (lead is None):
+        raise ValueError("exactly one of head and lead must be given")
+    if int(T) < 0:
+        raise ValueError("T must be >= 0")
+    if (not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != (int(T), L, 2, V)
+            or not target.is_contiguous()):
+        raise ValueError("target must be a contiguous float32 tensor of shape (%d, %d, 2, %d)" % (int(T), L, V))
+
+
+def _boundary_args(desc, T, head, lead, lead_length, contiguous):
+    """... and after ckpt: whichever of head and lead the head vehicle follows."""
+    if lead is not None:
+        _lead_args(desc, T, lead, lead_length)
+    elif lead_length is not None:
+        raise ValueError("lead_length needs lead")
+    else:
+        _head_arg(desc, head, contiguous)
+
+
+def _ckpt_args(form, desc, T, want_params, segment, ckpt, optional):
+    """(segment, ckpt) against the form's segment plan -> the resolved segment.  ckpt: a contiguous float32
+    [micro_ckpt_numel(desc, T, resolved segment)], or None where the forward may run without one."""
+    S = (micro_ckpt_target_plan if form == "target" else micro_ckpt_plan)(desc, T, want_params, segment)["segment"]
+    if ckpt is None and optional:
+        return S
+    if (ckpt is None and form == "target") or ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, S) \
+            or not ckpt.is_contiguous():
+        raise ValueError("ckpt must be %sa contiguous float32 [micro_ckpt_numel(desc, T, segment)]%s" %
+                         ("None or " if optional else "", ", segment the target plan's" if form == "target" else ""))
+    return S
+
+
+def _state_args(desc, p, v, params, head, count, check_head=True):
+    """(p, v, params, head, count) of a forward -> (p, v, params, head) as the library reads them; head None: the lead forms;
+    check_head False: _boundary_args has checked it."""
     L, V = desc.n_lanes, desc.capacity
     p, v = _f32c(p, "p"), _f32c(v, "v")
     if tuple(p.shape) != (L, V) or tuple(v.shape) != (L, V):
         raise ValueError("p, v must have shape (%d, %d)" % (L, V))
     if params.dtype != torch.float64 or tuple(params.shape) != (6, L, V):
         raise ValueError("params must be float64 [6][L][V]")
+    if head is not None and check_head:
+        _head_arg(desc, head, False)
     if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
         raise ValueError("count must be int32 [L]")
-    return p, v, params.contiguous()
+    return p, v, params.contiguous(), None if head is None else head.contiguous()
 
 
-def micro_rollout_fwd_ckpt_lead(desc, T, p, v, params, lead, ckpt, probes=None, every=1, lead_length=None, count=None, segment=0,
-                                samples=None, observe=True, err=None, out=None):
-    """micro_rollout_fwd_ckpt_samples whose head vehicle follows a recorded leader (dhts_micro_rollout_fwd_ckpt_lead, include/dhts.h):
-    lead float32 [T][L][2] = (p, v) of the vehicle in front of each lane's head as the head sees it in step t; lead_length float64 [L]
-    or None (the head's own length).  observe=False: no samples at all (the kernel is handed NULL; the returned samples is None);
-    probes=None, every=1 is the dense history.  Returns (pT, vT, samples)."""
+def _dir_arg(name, t, dtype, shape):
+    """An optional per-direction tangent array: contiguous, of `dtype` and `shape`."""
+    if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s %s" % (name, str(dtype)[6:], "".join("[%d]" % s for s in shape)))
+
+
+def _state_out(names, out, likes):
+    """The state buffers of `out` (checked against the inputs they mirror), or new ones."""
+    if not out:
+        return tuple(torch.empty_like(t) for t in likes)
+    for name, t, like in zip(names, out, likes):
+        if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
+    return tuple(out[:len(likes)])
+
+
+def _micro_ckpt_fwd(form, desc, T, p, v, params, ckpt, count, segment, err, out, head=None, hist=None, probes=None, every=1, samples=None,
+                    observe=True, lead=None, lead_length=None, target=None, sse=None):
+    """The checkpointed forward of every form: checks, buffers and the one C call -> (out, samples or sse).  ckpt may be None (no
+    checkpoint is kept) in every form but "hist"."""
     L = desc.n_lanes
-    rows, n, n_probes = _samples_shape(desc, T, probes, every)
-    _lead_args(desc, T, lead, lead_length)
-    micro_ckpt_plan(desc, T, False, segment)
-    if ckpt is not None and (ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous()):
-        raise ValueError("ckpt must be None or a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
-    p, v, params = _lead_state_args(desc, p, v, params, count)
-    samples = _samples_buffer("samples", samples, (rows, L, 2, n), p.device) if observe else None
-    if out is None:
-        out = (torch.empty_like(p), torch.empty_like(v))
-    check(_lib.lib().dhts_micro_rollout_fwd_ckpt_lead(C.byref(desc), int(T), int(segment), _ptr(p), _ptr(v), _ptr(count), _ptr(params),
-                                                      _ptr(lead) if lead.numel() else None, _ptr(lead_length), _ptr(out[0]), _ptr(out[1]),
-                                                      _ptr(ckpt) if ckpt is not None and ckpt.numel() else None, _ptr(probes), n_probes,
-                                                      every, _ptr(samples) if samples is not None and samples.numel() else None,
-                                                      _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt_lead")
-    return out[0], out[1], samples
-
-
-def micro_rollout_bwd_ckpt_lead(desc, T, ckpt, params, lead, g_p, g_v, probes=None, every=1, g_samples=None, lead_length=None, count=None,
-                                segment=0, err=None, out=None, g_lead=None, g_params=None):
-    """The reverse sweep of micro_rollout_fwd_ckpt_lead (dhts_micro_rollout_bwd_ckpt_lead) -> (g_p0, g_v0, g_lead): g_lead float32
-    [T][L][2], row t the cotangent of lead[t] (every row written; exactly 0 for a lane without a vehicle); nothing is folded into the
-    head.  g_samples=None: nothing was observed.  lead, lead_length, probes, every, count, segment: the forward's."""
-    L, V = desc.n_lanes, desc.capacity
-    rows, n, n_probes = _samples_shape(desc, T, probes, every)
-    _lead_args(desc, T, lead, lead_length)
-    micro_ckpt_plan(desc, T, g_params is not None, segment)
-    if ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, segment) or not ckpt.is_contiguous():
-        raise ValueError("ckpt must be a contiguous float32 [micro_ckpt_numel(desc, T, segment)]")
-    for name, t in (("params", params), ("g_params", g_params)):
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
-    g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
-    if g_samples is not None:
-        g_samples = _samples_buffer("g_samples", g_samples, (rows, L, 2, n), g_p.device)
-    if out is None:
-        out = (torch.empty_like(g_p), torch.empty_like(g_v))
-    if g_lead is None:
-        g_lead = torch.empty(int(T), L, 2, dtype=torch.float32, device=g_p.device)
-    elif g_lead.dtype != torch.float32 or tuple(g_lead.shape) != (int(T), L, 2) or not g_lead.is_contiguous():
-        raise ValueError("g_lead must be a contiguous float32 tensor of shape (%d, %d, 2)" % (int(T), L))
-    check(_lib.lib().dhts_micro_rollout_bwd_ckpt_lead(C.byref(desc), int(T), int(segment), _ptr(ckpt) if ckpt.numel() else None, _ptr(count),
-                                                      _ptr(params), _ptr(lead) if lead.numel() else None, _ptr(lead_length), _ptr(g_p),
-                                                      _ptr(g_v), _ptr(probes), n_probes, every,
-                                                      _ptr(g_samples) if g_samples is not None and g_samples.numel() else None,
-                                                      _ptr(out[0]), _ptr(out[1]), _ptr(g_lead) if g_lead.numel() else None, _ptr(g_params),
-                                                      _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_lead")
-    return out[0], out[1], g_lead
-
-
-def micro_rollout_fwd_jvp_lead(desc, T, p, v, params, lead, t_p, t_v, probes=None, every=1, lead_length=None, count=None, t_lead=None,
-                               t_params=None, observe=True, err=None, err_jvp=None, out=None):
-    """micro_rollout_fwd_jvp_samples whose head vehicle follows a recorded leader (dhts_micro_rollout_fwd_jvp_lead): lead, lead_length
-    as micro_rollout_fwd_ckpt_lead; t_lead float32 [K][T][L][2] or None (zero).  observe=False: no sample arrays (both returned as
-    None).  Returns ((pT, vT, samples), (t_pT, t_vT, t_samples))."""
-    L, V, T = desc.n_lanes, desc.capacity, int(T)
-    rows, n, n_probes = _samples_shape(desc, T, probes, every)
-    _lead_args(desc, T, lead, lead_length)
-    p, v, params = _lead_state_args(desc, p, v, params, count)
-    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
-        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
-    K = int(t_p.shape[0])
-    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
-    if t_lead is not None and (t_lead.dtype != torch.float32 or tuple(t_lead.shape) != (K, T, L, 2) or not t_lead.is_contiguous()):
-        raise ValueError("t_lead must be a contiguous float32 [%d][%d][%d][2]" % (K, T, L))
-    if t_params is not None and (t_params.dtype != torch.float64 or tuple(t_params.shape) != (K, 6, L, V) or not t_params.is_contiguous()):
-        raise ValueError("t_params must be a contiguous float64 [%d][6][%d][%d]" % (K, L, V))
-    out = tuple(out) if out is not None else ()
-    if len(out) not in (0, 4, 6) or (len(out) == 6 and not observe):
-        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, samples, t_samples])")
-    samples = t_samples = None
-    if observe:
-        samples = _samples_buffer("samples", out[4] if len(out) == 6 else None, (rows, L, 2, n), p.device)
-        t_samples = _samples_buffer("t_samples", out[5] if len(out) == 6 else None, (K, rows, L, 2, n), p.device)
-    if out:
-        state = out[:4]
-        for name, t, like in zip(("p_out", "v_out", "t_p_out", "t_v_out"), state, (p, v, t_p, t_v)):
-            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
-    else:
-        state = (torch.empty_like(p), torch.empty_like(v), torch.empty_like(t_p), torch.empty_like(t_v))
-    sptr = [_ptr(s) if s is not None and s.numel() else None for s in (samples, t_samples)]
-    check(_lib.lib().dhts_micro_rollout_fwd_jvp_lead(C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params),
-                                                     _ptr(lead) if lead.numel() else None, _ptr(lead_length), _ptr(t_p), _ptr(t_v),
-                                                     _ptr(t_lead) if t_lead is not None and t_lead.numel() else None, _ptr(t_params),
-                                                     _ptr(state[0]), _ptr(state[1]), _ptr(state[2]), _ptr(state[3]), _ptr(probes), n_probes,
-                                                     every, sptr[0], sptr[1], _ptr(err), _ptr(err_jvp), _stream()),
-          "dhts_micro_rollout_fwd_jvp_lead")
-    return (state[0], state[1], samples), (state[2], state[3], t_samples)
-
-
-# ---- the trajectory-fit loss inside the checkpointed pair (dhts_micro_rollout_*_ckpt_target) ----------------------------------------------
-def micro_ckpt_target_plan(desc, T, want_params=False, segment=0):
-    """micro_ckpt_plan for dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target (include/dhts.h): the same keys; the reverse kernel's
-    ring holds two more floats per vehicle-step, so max_segment and the default segment are shorter.  ValueError: a segment outside
-    0 .. max_segment."""
-    plan = (C.c_int32 * 8)()
-    if not 0 <= int(segment) <= 0x7fffffff:
-        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
-    status = _lib.lib().dhts_micro_ckpt_target_plan(C.byref(desc), int(T), int(bool(want_params)), int(segment), C.byref(plan))
-    if status == _lib.E_INVALID and int(T) >= 0:
-        raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment of the target forms for %d vehicle slots%s" %
-                         (desc.capacity, " with the parameter gradient" if want_params else ""))
-    check(status, "dhts_micro_ckpt_target_plan")
-    return dict(zip(_MICRO_CKPT_PLAN_KEYS, list(plan)))
-
-
-def _target_args(desc, T, target, want_params, segment, ckpt, ckpt_optional):
-    """The raw wrappers' checks of (target, segment, ckpt) -> the resolved segment.  target: a contiguous float32 [T][L][2][V]; ckpt: a
-    contiguous float32 [micro_ckpt_numel(desc, T, resolved segment)]."""
-    L, V = desc.n_lanes, desc.capacity
-    if int(T) < 0:
-        raise ValueError("T must be >= 0")
-    if (not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != (int(T), L, 2, V)
-            or not target.is_contiguous()):
-        raise ValueError("target must be a contiguous float32 tensor of shape (%d, %d, 2, %d)" % (int(T), L, V))
-    S = micro_ckpt_target_plan(desc, T, want_params, segment)["segment"]
-    if ckpt is None and ckpt_optional:
-        return S
-    if ckpt is None or ckpt.dtype != torch.float32 or ckpt.numel() != micro_ckpt_numel(desc, T, S) or not ckpt.is_contiguous():
-        raise ValueError("ckpt must be %sa contiguous float32 [micro_ckpt_numel(desc, T, segment)], segment the target plan's" %
-                         ("None or " if ckpt_optional else ""))
-    return S
-
-
-def micro_rollout_fwd_ckpt_target(desc, T, p, v, params, ckpt, target, head=None, lead=None, lead_length=None, count=None, segment=0,
-                                  sse=None, err=None, out=None):
-    """micro_rollout_fwd_ckpt (head given) or micro_rollout_fwd_ckpt_lead (lead given) -- exactly one of the two -- that reads the observed
-    trajectory `target` (float32 [T][L][2][V], hist's indexing, NaN = not observed) and returns the squared error
-    (dhts_micro_rollout_fwd_ckpt_target): (pT, vT, sse), sse float64 [L][2].  ckpt None: no checkpoint is kept.  segment 0: the default
-    of micro_ckpt_target_plan."""
-    L = desc.n_lanes
-    if (head is None) == (lead is None):
-        raise ValueError("exactly one of head and lead must be given")
-    S = _target_args(desc, T, target, False, segment, ckpt, True)
-    if lead is not None:
+    sampled = form in ("samples", "lead")
+    if form == "target":
+        _target_args(desc, T, target, head, lead)
+    if sampled:
+        rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    if form == "lead":
         _lead_args(desc, T, lead, lead_length)
-    elif lead_length is not None:
-        raise ValueError("lead_length needs lead")
-    elif head.dtype != torch.float64 or tuple(head.shape) != (L, 2):
-        raise ValueError("head must be float64 [L][2]")
-    p, v, params = _lead_state_args(desc, p, v, params, count)
-    head = None if head is None else head.contiguous()
-    if sse is None:
-        sse = torch.empty(L, 2, dtype=torch.float64, device=p.device)
-    elif sse.dtype != torch.float64 or tuple(sse.shape) != (L, 2) or not sse.is_contiguous():
-        raise ValueError("sse must be a contiguous float64 tensor of shape (%d, 2)" % L)
+    S = _ckpt_args(form, desc, T, False, segment, ckpt, form != "hist")
+    if form == "target":
+        _boundary_args(desc, T, head, lead, lead_length, False)
+    p, v, params, head = _state_args(desc, p, v, params, head, count, form != "target")
+    if sampled:
+        samples = _obs_buffer("samples", samples, (rows, L, 2, n), p.device) if observe else None
+    if form == "target":
+        if sse is None:
+            sse = torch.empty(L, 2, dtype=torch.float64, device=p.device)
+        elif sse.dtype != torch.float64 or tuple(sse.shape) != (L, 2) or not sse.is_contiguous():
+            raise ValueError("sse must be a contiguous float64 tensor of shape (%d, 2)" % L)
     if out is None:
         out = (torch.empty_like(p), torch.empty_like(v))
+    # include/dhts.h: desc T segment p v count params | head, or lead lead_length, or all three | p_out v_out ckpt | observed | err stream
+    lib, a, z = _lib.lib(), (C.byref(desc), int(T), S, _ptr(p), _ptr(v), _ptr(count), _ptr(params)), (_ptr(out[0]), _ptr(out[1]), _data(ckpt))
+    if form == "hist":
+        check(lib.dhts_micro_rollout_fwd_ckpt(*a, _ptr(head), *z, _data(hist), _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt")
+        return out, None
+    if form == "samples":
+        check(lib.dhts_micro_rollout_fwd_ckpt_samples(*a, _ptr(head), *z, _ptr(probes), n_probes, every, _data(samples), _ptr(err), _stream()),
+              "dhts_micro_rollout_fwd_ckpt_samples")
+        return out, samples
+    if form == "lead":
+        check(lib.dhts_micro_rollout_fwd_ckpt_lead(*a, _data(lead), _ptr(lead_length), *z, _ptr(probes), n_probes, every, _data(samples),
+                                                   _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt_lead")
+        return out, samples
     # (a T = 0 call with lead: no row exists; the library takes the lead form from the NULL head)
-    check(_lib.lib().dhts_micro_rollout_fwd_ckpt_target(C.byref(desc), int(T), S, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
-                                                        _ptr(lead) if lead is not None and lead.numel() else None, _ptr(lead_length),
-                                                        _ptr(out[0]), _ptr(out[1]),
-                                                        _ptr(ckpt) if ckpt is not None and ckpt.numel() else None,
-                                                        _ptr(target) if target.numel() else None, _ptr(sse), _ptr(err), _stream()),
-          "dhts_micro_rollout_fwd_ckpt_target")
-    return out[0], out[1], sse
+    check(lib.dhts_micro_rollout_fwd_ckpt_target(*a, _ptr(head), _data(lead), _ptr(lead_length), *z, _data(target), _ptr(sse), _ptr(err),
+                                                 _stream()), "dhts_micro_rollout_fwd_ckpt_target")
+    return out, sse
 
 
-def micro_rollout_bwd_ckpt_target(desc, T, ckpt, params, g_p, g_v, target, g_sse=None, head=None, lead=None, lead_length=None, count=None,
-                                  segment=0, err=None, out=None, g_head=None, g_lead=None, g_params=None):
-    """The reverse sweep of micro_rollout_fwd_ckpt_target (dhts_micro_rollout_bwd_ckpt_target) -> (g_p0, g_v0, g_head) with head, or
-    (g_p0, g_v0, g_lead) with lead.  g_sse float64 [L][2] or None (zero): the cotangent of sse; the per-step cotangent
-    (float)(2 g_sse) * (x - target) is formed in the kernel.  target, head / lead, lead_length, count, segment: the forward's."""
+def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, head=None, g_head=None, g_hist=None,
+                    probes=None, every=1, g_samples=None, lead=None, lead_length=None, g_lead=None, target=None, g_sse=None):
+    """The reverse sweep from checkpoints of every form -> (g_p0, g_v0, g_head or g_lead).  g_samples is required in the "samples"
+    form and optional (None: nothing was observed) in the "lead" form."""
     L, V = desc.n_lanes, desc.capacity
-    if (head is None) == (lead is None):
-        raise ValueError("exactly one of head and lead must be given")
-    S = _target_args(desc, T, target, g_params is not None, segment, ckpt, False)
-    if lead is not None:
+    sampled = form in ("samples", "lead")
+    if form == "target":
+        _target_args(desc, T, target, head, lead)
+    if sampled:
+        rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    if form == "lead":
         _lead_args(desc, T, lead, lead_length)
-    elif lead_length is not None:
-        raise ValueError("lead_length needs lead")
-    elif head.dtype != torch.float64 or tuple(head.shape) != (L, 2) or not head.is_contiguous():
-        raise ValueError("head must be a contiguous float64 [L][2]")
+    S = _ckpt_args(form, desc, T, g_params is not None, segment, ckpt, False)
+    if form == "target":
+        _boundary_args(desc, T, head, lead, lead_length, True)
     for name, t in (("params", params), ("g_params", g_params)):
         if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
             raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
+    if form in ("hist", "samples"):
+        _head_arg(desc, head, True)
+    if form == "samples" and g_samples is None:
+        raise ValueError("g_samples is required: float32 [T // every][L][2][P]")
     if g_sse is not None and (g_sse.dtype != torch.float64 or tuple(g_sse.shape) != (L, 2) or not g_sse.is_contiguous()):
         raise ValueError("g_sse must be None or a contiguous float64 tensor of shape (%d, 2)" % L)
     g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
+    if g_samples is not None:
+        g_samples = _obs_buffer("g_samples", g_samples, (rows, L, 2, n), g_p.device)
     if out is None:
         out = (torch.empty_like(g_p), torch.empty_like(g_v))
-    if lead is None:
+    if lead is None:                     # the cotangent of whichever the head follows
         if g_lead is not None:
             raise ValueError("g_lead needs lead")
         if g_head is None:
@@ -1388,14 +1143,170 @@ def micro_rollout_bwd_ckpt_target(desc, T, ckpt, params, g_p, g_v, target, g_sse
             g_lead = torch.empty(int(T), L, 2, dtype=torch.float32, device=g_p.device)
         elif g_lead.dtype != torch.float32 or tuple(g_lead.shape) != (int(T), L, 2) or not g_lead.is_contiguous():
             raise ValueError("g_lead must be a contiguous float32 tensor of shape (%d, %d, 2)" % (int(T), L))
-    check(_lib.lib().dhts_micro_rollout_bwd_ckpt_target(C.byref(desc), int(T), S, _ptr(ckpt) if ckpt.numel() else None, _ptr(count),
-                                                        _ptr(params), _ptr(head),
-                                                        _ptr(lead) if lead is not None and lead.numel() else None, _ptr(lead_length),
-                                                        _ptr(g_p), _ptr(g_v), _ptr(target) if target.numel() else None, _ptr(g_sse),
-                                                        _ptr(out[0]), _ptr(out[1]), _ptr(g_head),
-                                                        _ptr(g_lead) if g_lead is not None and g_lead.numel() else None, _ptr(g_params),
-                                                        _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_target")
+    # include/dhts.h: desc T segment ckpt count params | head, or lead lead_length, or all three | g_p g_v | observed | g_p_out g_v_out |
+    # g_head, or g_lead, or both | g_params err stream
+    lib, a = _lib.lib(), (C.byref(desc), int(T), S, _data(ckpt), _ptr(count), _ptr(params))
+    g, z = (_ptr(g_p), _ptr(g_v)), (_ptr(out[0]), _ptr(out[1]))
+    if form == "hist":
+        check(lib.dhts_micro_rollout_bwd_ckpt(*a, _ptr(head), *g, _ptr(g_hist), *z, _ptr(g_head), _ptr(g_params), _ptr(err), _stream()),
+              "dhts_micro_rollout_bwd_ckpt")
+    elif form == "samples":
+        check(lib.dhts_micro_rollout_bwd_ckpt_samples(*a, _ptr(head), *g, _ptr(probes), n_probes, every, _data(g_samples), *z, _ptr(g_head),
+                                                      _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_samples")
+    elif form == "lead":
+        check(lib.dhts_micro_rollout_bwd_ckpt_lead(*a, _data(lead), _ptr(lead_length), *g, _ptr(probes), n_probes, every, _data(g_samples), *z,
+                                                   _data(g_lead), _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_lead")
+    else:
+        check(lib.dhts_micro_rollout_bwd_ckpt_target(*a, _ptr(head), _data(lead), _ptr(lead_length), *g, _data(target), _ptr(g_sse), *z,
+                                                     _ptr(g_head), _data(g_lead), _ptr(g_params), _ptr(err), _stream()),
+              "dhts_micro_rollout_bwd_ckpt_target")
     return out[0], out[1], (g_head if lead is None else g_lead)
+
+
+def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, head=None, t_head=None, want_hist=False,
+                   probes=None, every=1, observe=True, lead=None, lead_length=None, t_lead=None):
+    """The fused rollout + tangent call of the "hist", "samples" and "lead" forms -> ((pT, vT, observed), (t_pT, t_vT, t_observed)),
+    observed = the histories (None unless asked for or handed in) or the sample arrays (None with observe False)."""
+    L, V, T = desc.n_lanes, desc.capacity, int(T)
+    sampled = form != "hist"
+    if sampled:
+        rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    if form == "lead":
+        _lead_args(desc, T, lead, lead_length)
+    p, v, params, head = _state_args(desc, p, v, params, head, count)
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    if t_p.dim() != 3 or tuple(t_p.shape[1:]) != (L, V) or t_p.shape[0] < 1 or t_v.shape != t_p.shape:
+        raise ValueError("t_p and t_v must have shape (K, %d, %d) with K >= 1" % (L, V))
+    K = int(t_p.shape[0])
+    t_p, t_v = _f32c(t_p, "t_p"), _f32c(t_v, "t_v")
+    _dir_arg("t_lead", t_lead, torch.float32, (K, T, L, 2))
+    _dir_arg("t_head", t_head, torch.float64, (K, L, 2))
+    _dir_arg("t_params", t_params, torch.float64, (K, 6, L, V))
+    out = tuple(out) if out is not None else ()
+    names = ("samples", "t_samples") if sampled else ("hist", "t_hist")
+    if len(out) not in (0, 4, 6) or (len(out) == 6 and not observe):
+        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, %s, %s])" % names)
+    shape = (rows, L, 2, n) if sampled else (T, L, 2, V)
+    new = (torch.zeros if observe else None) if sampled else (torch.empty if want_hist else None)
+    obs = [_obs_buffer(name, t, shp, p.device, new) for name, t, shp in zip(names, out[4:6] or (None, None), (shape, (K,) + shape))]
+    state = _state_out(("p_out", "v_out", "t_p_out", "t_v_out"), out, (p, v, t_p, t_v))
+    # include/dhts.h: desc T n_dir p v count params | head, or lead lead_length | t_p t_v | t_head, or t_lead | t_params | the four outputs |
+    # probes n_probes every (sampled) | the two observed arrays | err err_jvp stream
+    lib, a, t = _lib.lib(), (C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params)), (_ptr(t_p), _ptr(t_v))
+    z = (_ptr(state[0]), _ptr(state[1]), _ptr(state[2]), _ptr(state[3]))
+    e = (_data(obs[0]), _data(obs[1]), _ptr(err), _ptr(err_jvp), _stream())
+    if form == "hist":
+        check(lib.dhts_micro_rollout_fwd_jvp(*a, _ptr(head), *t, _ptr(t_head), _ptr(t_params), *z, *e), "dhts_micro_rollout_fwd_jvp")
+    elif form == "samples":
+        check(lib.dhts_micro_rollout_fwd_jvp_samples(*a, _ptr(head), *t, _ptr(t_head), _ptr(t_params), *z, _ptr(probes), n_probes, every, *e),
+              "dhts_micro_rollout_fwd_jvp_samples")
+    else:
+        check(lib.dhts_micro_rollout_fwd_jvp_lead(*a, _data(lead), _ptr(lead_length), *t, _data(t_lead), _ptr(t_params), *z, _ptr(probes),
+                                                  n_probes, every, *e), "dhts_micro_rollout_fwd_jvp_lead")
+    return (state[0], state[1], obs[0]), (state[2], state[3], obs[1])
+
+
+def micro_rollout_fwd_ckpt(desc, T, p, v, params, head, ckpt, count=None, segment=0, hist=None, err=None, out=None):
+    """micro_rollout_fwd that fills the checkpoint buffer `ckpt` (float32 [micro_ckpt_numel(desc, T, segment)]) instead of a tape
+    (dhts_micro_rollout_fwd_ckpt): the same (pT, vT) and hist, bit for bit."""
+    return _micro_ckpt_fwd("hist", desc, T, p, v, params, ckpt, count, segment, err, out, head=head, hist=hist)[0]
+
+
+def micro_rollout_bwd_ckpt(desc, T, ckpt, params, head, g_p, g_v, count=None, segment=0, g_hist=None, err=None, out=None, g_head=None,
+                           g_params=None):
+    """Reverse sweep from the checkpoints of micro_rollout_fwd_ckpt -> (g_p0, g_v0, g_head): micro_rollout_bwd's bits.  params, head,
+    count, segment: the forward's.  g_params (float64 [6][L][V], filled here): also the gradient w.r.t. the driver parameters."""
+    return _micro_ckpt_bwd("hist", desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, head=head, g_head=g_head,
+                           g_hist=g_hist)
+
+
+# ---- probe samples on the two tape-free paths (dhts_micro_rollout_*_samples) ------------------------------------------------------------
+def micro_rollout_fwd_ckpt_samples(desc, T, p, v, params, head, ckpt, probes, every, count=None, segment=0, samples=None, err=None, out=None):
+    """micro_rollout_fwd_ckpt that writes, instead of a history, samples [T // every][L][2][P] (dhts_micro_rollout_fwd_ckpt_samples,
+    include/dhts.h): row j = (p, v) of slot probes[i] after step (j + 1) every - 1.  probes: a CUDA int32 tensor of distinct slots (not
+    validated: an entry outside [0, V) leaves its column as it is) or None = every slot.  samples: allocated zero-filled unless handed
+    in (live probe slots only are written).  ckpt=None: no checkpoint is kept.  Returns (pT, vT, samples)."""
+    out, samples = _micro_ckpt_fwd("samples", desc, T, p, v, params, ckpt, count, segment, err, out, head=head, probes=probes, every=every,
+                                   samples=samples)
+    return out[0], out[1], samples
+
+
+def micro_rollout_bwd_ckpt_samples(desc, T, ckpt, params, head, g_p, g_v, probes, every, g_samples, count=None, segment=0, err=None,
+                                   out=None, g_head=None, g_params=None):
+    """micro_rollout_bwd_ckpt with the cotangent g_samples [T // every][L][2][P] of micro_rollout_fwd_ckpt_samples' samples in place of
+    g_hist (dhts_micro_rollout_bwd_ckpt_samples): it enters the sweep at the sampled steps, at live probe slots.  probes, every,
+    count, segment: the forward's.  Returns (g_p0, g_v0, g_head)."""
+    return _micro_ckpt_bwd("samples", desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, head=head, g_head=g_head,
+                           probes=probes, every=every, g_samples=g_samples)
+
+
+def micro_rollout_fwd_jvp_samples(desc, T, p, v, params, head, t_p, t_v, probes, every, count=None, t_head=None, t_params=None, err=None,
+                                  err_jvp=None, out=None):
+    """micro_rollout_fwd_jvp that writes, instead of the histories, samples [T // every][L][2][P] and t_samples [K][T // every][L][2][P]
+    (dhts_micro_rollout_fwd_jvp_samples): probes, every as micro_rollout_fwd_ckpt_samples.  out: (p_out, v_out, t_p_out, t_v_out[,
+    samples, t_samples]); the sample arrays are allocated zero-filled unless handed in (samples: live probe slots only are written;
+    t_samples: every probe slot, 0 at or beyond count).  Returns ((pT, vT, samples), (t_pT, t_vT, t_samples))."""
+    return _micro_fwd_jvp("samples", desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, head=head, t_head=t_head,
+                          probes=probes, every=every)
+
+
+# ---- a recorded leader on the two tape-free paths (dhts_micro_rollout_*_lead) ------------------------------------------------------------
+def micro_rollout_fwd_ckpt_lead(desc, T, p, v, params, lead, ckpt, probes=None, every=1, lead_length=None, count=None, segment=0,
+                                samples=None, observe=True, err=None, out=None):
+    """micro_rollout_fwd_ckpt_samples whose head vehicle follows a recorded leader (dhts_micro_rollout_fwd_ckpt_lead, include/dhts.h):
+    lead float32 [T][L][2] = (p, v) of the vehicle in front of each lane's head as the head sees it in step t; lead_length float64 [L]
+    or None (the head's own length).  observe=False: no samples at all (the kernel is handed NULL; the returned samples is None);
+    probes=None, every=1 is the dense history.  Returns (pT, vT, samples)."""
+    out, samples = _micro_ckpt_fwd("lead", desc, T, p, v, params, ckpt, count, segment, err, out, probes=probes, every=every,
+                                   samples=samples, observe=observe, lead=lead, lead_length=lead_length)
+    return out[0], out[1], samples
+
+
+def micro_rollout_bwd_ckpt_lead(desc, T, ckpt, params, lead, g_p, g_v, probes=None, every=1, g_samples=None, lead_length=None, count=None,
+                                segment=0, err=None, out=None, g_lead=None, g_params=None):
+    """The reverse sweep of micro_rollout_fwd_ckpt_lead (dhts_micro_rollout_bwd_ckpt_lead) -> (g_p0, g_v0, g_lead): g_lead float32
+    [T][L][2], row t the cotangent of lead[t] (every row written; exactly 0 for a lane without a vehicle); nothing is folded into the
+    head.  g_samples=None: nothing was observed.  lead, lead_length, probes, every, count, segment: the forward's."""
+    return _micro_ckpt_bwd("lead", desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, probes=probes, every=every,
+                           g_samples=g_samples, lead=lead, lead_length=lead_length, g_lead=g_lead)
+
+
+def micro_rollout_fwd_jvp_lead(desc, T, p, v, params, lead, t_p, t_v, probes=None, every=1, lead_length=None, count=None, t_lead=None,
+                               t_params=None, observe=True, err=None, err_jvp=None, out=None):
+    """micro_rollout_fwd_jvp_samples whose head vehicle follows a recorded leader (dhts_micro_rollout_fwd_jvp_lead): lead, lead_length
+    as micro_rollout_fwd_ckpt_lead; t_lead float32 [K][T][L][2] or None (zero).  observe=False: no sample arrays (both returned as
+    None).  Returns ((pT, vT, samples), (t_pT, t_vT, t_samples))."""
+    return _micro_fwd_jvp("lead", desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, probes=probes, every=every,
+                          observe=observe, lead=lead, lead_length=lead_length, t_lead=t_lead)
+
+
+# ---- the trajectory-fit loss inside the checkpointed pair (dhts_micro_rollout_*_ckpt_target) ----------------------------------------------
+def micro_ckpt_target_plan(desc, T, want_params=False, segment=0):
+    """micro_ckpt_plan for dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target (include/dhts.h): the same keys; the reverse kernel's
+    ring holds two more floats per vehicle-step, so max_segment and the default segment are shorter.  ValueError: a segment outside
+    0 .. max_segment."""
+    return _micro_ckpt_plan("dhts_micro_ckpt_target_plan", " of the target forms", desc, T, want_params, segment)
+
+
+def micro_rollout_fwd_ckpt_target(desc, T, p, v, params, ckpt, target, head=None, lead=None, lead_length=None, count=None, segment=0,
+                                  sse=None, err=None, out=None):
+    """micro_rollout_fwd_ckpt (head given) or micro_rollout_fwd_ckpt_lead (lead given) -- exactly one of the two -- that reads the observed
+    trajectory `target` (float32 [T][L][2][V], hist's indexing, NaN = not observed) and returns the squared error
+    (dhts_micro_rollout_fwd_ckpt_target): (pT, vT, sse), sse float64 [L][2].  ckpt None: no checkpoint is kept.  segment 0: the default
+    of micro_ckpt_target_plan."""
+    out, sse = _micro_ckpt_fwd("target", desc, T, p, v, params, ckpt, count, segment, err, out, head=head, lead=lead,
+                               lead_length=lead_length, target=target, sse=sse)
+    return out[0], out[1], sse
+
+
+def micro_rollout_bwd_ckpt_target(desc, T, ckpt, params, g_p, g_v, target, g_sse=None, head=None, lead=None, lead_length=None, count=None,
+                                  segment=0, err=None, out=None, g_head=None, g_lead=None, g_params=None):
+    """The reverse sweep of micro_rollout_fwd_ckpt_target (dhts_micro_rollout_bwd_ckpt_target) -> (g_p0, g_v0, g_head) with head, or
+    (g_p0, g_v0, g_lead) with lead.  g_sse float64 [L][2] or None (zero): the cotangent of sse; the per-step cotangent
+    (float)(2 g_sse) * (x - target) is formed in the kernel.  target, head / lead, lead_length, count, segment: the forward's."""
+    return _micro_ckpt_bwd("target", desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, head=head, g_head=g_head,
+                           lead=lead, lead_length=lead_length, g_lead=g_lead, target=target, g_sse=g_sse)
 
 
 def _probe_slots(probes, V):
@@ -1479,6 +1390,51 @@ def micro_step_bwd(desc, tape, g_p, g_v, count=None):
     return out[0], out[1], g_virtual
 
 
+# ---- what the micro autograd Functions share: the forward set-up of a checkpointed call, the fault check, the backward's seeds ----------
+def _micro_segment(p0, params, T, dt, checkpoint, plan):
+    """-> (desc, the segment `checkpoint` asks for or None): a ValueError before a device is touched."""
+    L, V = p0.shape
+    desc = micro_desc(L, V, dt)
+    return desc, _checkpoint_segment(checkpoint, lambda sg: plan(desc, T, params.requires_grad, sg))
+
+
+def _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad):
+    """Everything every checkpointed pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand
+    over): the checkpoint buffer -- none when nothing requires grad --, g_params and, with _micro_fwd_done behind the forward call, the
+    two fault records; neither tape exists.  -> (p0c, v0c, the forward's record)."""
+    p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
+    dev = p0c.device
+    ctx.desc, ctx.T, ctx.segment = desc, T, segment
+    ctx.params = params.detach().contiguous()
+    ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
+    ctx.g_params = torch.empty(6, desc.n_lanes, desc.capacity, dtype=torch.float64, device=dev) if params.requires_grad else None
+    return p0c, v0c, new_error_record(dev)
+
+
+def _micro_fwd_done(ctx, err, count, check_faults, need_grad):
+    if check_faults:                     # a collision is printed like the reference does, and tolerated
+        raise_on_fault(err)
+    ctx.count, ctx.check_faults = count, check_faults
+    ctx.err_bwd = new_error_record(err.device) if need_grad else None
+
+
+def _micro_bwd_seeds(ctx, g_pT, g_vT):
+    """-> (g_p, g_v, the reverse sweep's record, cleared)."""
+    L, V, dev = ctx.desc.n_lanes, ctx.desc.capacity, ctx.err_bwd.device
+    g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
+    g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
+    ctx.err_bwd.zero_()                  # (first fault wins: a second backward with retain_graph must not report the first one's)
+    return g_p, g_v, ctx.err_bwd
+
+
+def _micro_bwd_done(ctx):
+    # The record only feeds a warning (the reference's micro backward returns NaNs silently, dmicro_lane.py:271-298): it is not
+    # read back here -- that would be a host synchronisation per reverse sweep -- unless the gradient that is being returned
+    # anyway is non-finite, which the caller's next use of it would synchronise on as well.
+    if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
+        MicroRollout.last_bwd_record = ctx.err_bwd           # (dhts.ops.micro_bwd_fault() reads it on demand)
+
+
 class MicroRollout(torch.autograd.Function):
     """T fused differentiable IDM steps of L independent lanes with a fixed head gap.
 
@@ -1497,13 +1453,12 @@ class MicroRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p0, v0, params, head, count, T, dt, want_hist=False, check_faults=True, checkpoint=None):
         L, V = p0.shape
-        desc = micro_desc(L, V, dt)
+        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_plan)
         want_params = params.requires_grad
-        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, T, want_params, sg))      # (ValueError before a device is touched)
-        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
         need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or want_params
         if segment is not None and need_grad:
-            return MicroRollout._forward_ckpt(ctx, p0c, v0c, params, head, count, desc, T, want_hist, check_faults, segment, want_params)
+            return MicroRollout._forward_ckpt(ctx, p0, v0, params, head, count, desc, T, want_hist, check_faults, segment)
+        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
         ctx.segment = None
         tape = torch.empty(micro_tape_numel(desc, T), dtype=torch.float32, device=p0.device) if need_grad else None
         hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=p0.device) if want_hist else None
@@ -1526,44 +1481,28 @@ class MicroRollout(torch.autograd.Function):
         return pT, vT
 
     @staticmethod
-    def _forward_ckpt(ctx, p0c, v0c, params, head, count, desc, T, want_hist, check_faults, segment, want_params):
-        """The forward of a checkpointed call: everything the pair needs is made here -- the checkpoint buffer, hist, g_params and the two
-        fault records; neither tape exists."""
-        L, V, dev = desc.n_lanes, desc.capacity, p0c.device
+    def _forward_ckpt(ctx, p0, v0, params, head, count, desc, T, want_hist, check_faults, segment):
+        """The forward of a checkpointed call (one that requires grad): _micro_ckpt_setup's buffers and hist."""
+        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, True)
         ctx.tape = ctx.ptape = None
-        ctx.params, ctx.head = params.detach().contiguous(), head.detach().contiguous()
-        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
-        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev)
-        hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=dev) if want_hist else None
-        err = new_error_record(dev)
+        ctx.head, ctx.want_hist = head.detach().contiguous(), want_hist
+        hist = torch.empty(T, desc.n_lanes, 2, desc.capacity, dtype=torch.float32, device=p0c.device) if want_hist else None
         pT, vT = micro_rollout_fwd_ckpt(desc, T, p0c, v0c, ctx.params, ctx.head, ctx.ckpt, count=count, segment=segment, hist=hist, err=err)
-        if check_faults:
-            raise_on_fault(err)
-        ctx.desc, ctx.T, ctx.count, ctx.want_hist, ctx.check_faults, ctx.segment = desc, T, count, want_hist, check_faults, segment
-        ctx.err_bwd = new_error_record(dev)
+        _micro_fwd_done(ctx, err, count, check_faults, True)
         return (pT, vT, hist) if want_hist else (pT, vT)
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_hist=None):
         desc, T = ctx.desc, ctx.T
-        dev = ctx.err_bwd.device
-        L, V = desc.n_lanes, desc.capacity
-        g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
-        g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
+        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
         gh = g_hist.contiguous() if (ctx.want_hist and g_hist is not None) else None
-        err = ctx.err_bwd
-        err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
         if ctx.segment is not None:
             g_p0, g_v0, g_head = micro_rollout_bwd_ckpt(desc, T, ctx.ckpt, ctx.params, ctx.head, g_p, g_v, count=ctx.count,
                                                         segment=ctx.segment, g_hist=gh, err=err, g_params=ctx.g_params)
         else:
             g_p0, g_v0, g_head = micro_rollout_bwd(desc, T, ctx.tape, g_p, g_v, count=ctx.count, g_hist=gh, err=err,
                                                    ptape=ctx.ptape, params=ctx.params, g_params=ctx.g_params)
-        # The record only feeds a warning (the reference's micro backward returns NaNs silently, dmicro_lane.py:271-298): it is not
-        # read back here -- that would be a host synchronisation per reverse sweep -- unless the gradient that is being returned
-        # anyway is non-finite, which the caller's next use of it would synchronise on as well.
-        if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
-            MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
+        _micro_bwd_done(ctx)
         return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None, None
 
 
@@ -1590,41 +1529,24 @@ class MicroRolloutSamples(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, head, count, T, dt, check_faults, checkpoint, probes, every):
-        L, V = p0.shape
-        desc = micro_desc(L, V, dt)
-        want_params = params.requires_grad
-        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, T, want_params, sg))      # (ValueError before a device is touched)
-        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
-        dev = p0c.device
-        need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or want_params
-        ctx.params, ctx.head = params.detach().contiguous(), head.detach().contiguous()
-        # everything the pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand over)
-        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
-        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
-        err = new_error_record(dev)
+        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_plan)
+        need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or params.requires_grad
+        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
+        ctx.head, ctx.probes, ctx.every = head.detach().contiguous(), probes, every
         pT, vT, samples = micro_rollout_fwd_ckpt_samples(desc, T, p0c, v0c, ctx.params, ctx.head, ctx.ckpt, probes, every, count=count,
                                                          segment=segment, err=err)
-        if check_faults:                 # a collision is printed like the reference does, and tolerated
-            raise_on_fault(err)
-        ctx.desc, ctx.T, ctx.count, ctx.check_faults, ctx.segment, ctx.probes, ctx.every = desc, T, count, check_faults, segment, probes, every
-        ctx.err_bwd = new_error_record(dev) if need_grad else None
+        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
         return pT, vT, samples
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_samples):
         desc, T = ctx.desc, ctx.T
-        dev = ctx.err_bwd.device
-        L, V = desc.n_lanes, desc.capacity
-        g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
-        g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
-        P = V if ctx.probes is None else int(ctx.probes.numel())
-        gs = g_samples.contiguous() if g_samples is not None else torch.zeros(T // ctx.every, L, 2, P, device=dev)
-        err = ctx.err_bwd
-        err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
+        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
+        P = desc.capacity if ctx.probes is None else int(ctx.probes.numel())
+        gs = g_samples.contiguous() if g_samples is not None else torch.zeros(T // ctx.every, desc.n_lanes, 2, P, device=err.device)
         g_p0, g_v0, g_head = micro_rollout_bwd_ckpt_samples(desc, T, ctx.ckpt, ctx.params, ctx.head, g_p, g_v, ctx.probes, ctx.every, gs,
                                                             count=ctx.count, segment=ctx.segment, err=err, g_params=ctx.g_params)
-        if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
-            MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
+        _micro_bwd_done(ctx)
         return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None, None, None
 
 
@@ -1635,44 +1557,26 @@ class MicroRolloutLead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, lead, lead_length, count, T, dt, check_faults, checkpoint, probes, every, observe):
-        L, V = p0.shape
-        desc = micro_desc(L, V, dt)
-        want_params = params.requires_grad
-        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, T, want_params, sg))
-        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
+        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_plan)
+        need_grad = p0.requires_grad or v0.requires_grad or lead.requires_grad or params.requires_grad
+        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
         dev = p0c.device
-        need_grad = p0.requires_grad or v0.requires_grad or lead.requires_grad or want_params
-        ctx.params, ctx.lead = params.detach().contiguous(), _f32c(lead.detach(), "lead")
+        ctx.lead, ctx.probes, ctx.every, ctx.observe = _f32c(lead.detach(), "lead"), probes, every, observe
         ctx.lead_length = None if lead_length is None else lead_length.detach().to(device=dev, dtype=torch.float64).contiguous()
-        # everything the pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand over)
-        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
-        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
-        ctx.g_lead = torch.empty(T, L, 2, dtype=torch.float32, device=dev) if need_grad else None
-        err = new_error_record(dev)
+        ctx.g_lead = torch.empty(T, desc.n_lanes, 2, dtype=torch.float32, device=dev) if need_grad else None
         pT, vT, samples = micro_rollout_fwd_ckpt_lead(desc, T, p0c, v0c, ctx.params, ctx.lead, ctx.ckpt, probes, every,
                                                       lead_length=ctx.lead_length, count=count, segment=segment, observe=observe, err=err)
-        if check_faults:                 # a collision is printed like the reference does, and tolerated
-            raise_on_fault(err)
-        ctx.desc, ctx.T, ctx.count, ctx.check_faults, ctx.segment, ctx.probes, ctx.every = desc, T, count, check_faults, segment, probes, every
-        ctx.observe = observe
-        ctx.err_bwd = new_error_record(dev) if need_grad else None
+        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
         return (pT, vT, samples) if observe else (pT, vT)
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_samples=None):
-        desc, T = ctx.desc, ctx.T
-        dev = ctx.err_bwd.device
-        L, V = desc.n_lanes, desc.capacity
-        g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
-        g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
+        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
         gs = g_samples.contiguous() if (ctx.observe and g_samples is not None) else None      # (None: nothing enters at the samples)
-        err = ctx.err_bwd
-        err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
-        g_p0, g_v0, g_lead = micro_rollout_bwd_ckpt_lead(desc, T, ctx.ckpt, ctx.params, ctx.lead, g_p, g_v, ctx.probes, ctx.every, gs,
-                                                         lead_length=ctx.lead_length, count=ctx.count, segment=ctx.segment, err=err,
+        g_p0, g_v0, g_lead = micro_rollout_bwd_ckpt_lead(ctx.desc, ctx.T, ctx.ckpt, ctx.params, ctx.lead, g_p, g_v, ctx.probes, ctx.every,
+                                                         gs, lead_length=ctx.lead_length, count=ctx.count, segment=ctx.segment, err=err,
                                                          g_lead=ctx.g_lead, g_params=ctx.g_params)
-        if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
-            MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
+        _micro_bwd_done(ctx)
         return (g_p0, g_v0, ctx.g_params, g_lead) + (None,) * 9
 
 
@@ -1684,52 +1588,35 @@ class MicroRolloutTarget(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, head, lead, lead_length, count, T, dt, check_faults, checkpoint, target):
-        L, V = p0.shape
-        desc = micro_desc(L, V, dt)
-        want_params = params.requires_grad
-        segment = _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_target_plan(desc, T, want_params, sg))   # (ValueError before a device is touched)
-        p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
-        dev = p0c.device
+        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_target_plan)
         boundary = head if lead is None else lead
-        need_grad = p0.requires_grad or v0.requires_grad or boundary.requires_grad or want_params
-        ctx.params = params.detach().contiguous()
+        need_grad = p0.requires_grad or v0.requires_grad or boundary.requires_grad or params.requires_grad
+        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
+        L, dev = desc.n_lanes, p0c.device
         ctx.head = None if head is None else head.detach().contiguous()
         ctx.lead = None if lead is None else _f32c(lead.detach(), "lead")
         ctx.lead_length = None if lead_length is None else lead_length.detach().to(device=dev, dtype=torch.float64).contiguous()
         ctx.target = _f32c(target, "target")
-        # everything the pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand over)
-        ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
-        ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if want_params else None
+        # ... and here also the reverse sweep's outputs
         ctx.g_lead = torch.empty(T, L, 2, dtype=torch.float32, device=dev) if (need_grad and lead is not None) else None
         ctx.g_head = torch.zeros(L, 2, dtype=torch.float64, device=dev) if (need_grad and lead is None) else None
         ctx.out_bwd = (torch.empty_like(p0c), torch.empty_like(v0c)) if need_grad else None
-        err = new_error_record(dev)
         pT, vT, sse = micro_rollout_fwd_ckpt_target(desc, T, p0c, v0c, ctx.params, ctx.ckpt, ctx.target, head=ctx.head, lead=ctx.lead,
                                                     lead_length=ctx.lead_length, count=count, segment=segment, err=err)
-        if check_faults:                 # a collision is printed like the reference does, and tolerated
-            raise_on_fault(err)
-        ctx.desc, ctx.T, ctx.count, ctx.check_faults, ctx.segment = desc, T, count, check_faults, segment
-        ctx.err_bwd = new_error_record(dev) if need_grad else None
+        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
         return pT, vT, sse
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_sse):
-        desc, T = ctx.desc, ctx.T
-        dev = ctx.err_bwd.device
-        L, V = desc.n_lanes, desc.capacity
-        g_p = g_pT.contiguous() if g_pT is not None else torch.zeros(L, V, device=dev)
-        g_v = g_vT.contiguous() if g_vT is not None else torch.zeros(L, V, device=dev)
+        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
         gs = g_sse.contiguous() if g_sse is not None else None          # (None: the kernel takes zero)
-        err = ctx.err_bwd
-        err.zero_()                      # (first fault wins: a second backward with retain_graph must not report the first one's)
         if ctx.g_head is not None:
             ctx.g_head.zero_()
-        g_p0, g_v0, g_b = micro_rollout_bwd_ckpt_target(desc, T, ctx.ckpt, ctx.params, g_p, g_v, ctx.target, g_sse=gs, head=ctx.head,
+        g_p0, g_v0, g_b = micro_rollout_bwd_ckpt_target(ctx.desc, ctx.T, ctx.ckpt, ctx.params, g_p, g_v, ctx.target, g_sse=gs, head=ctx.head,
                                                         lead=ctx.lead, lead_length=ctx.lead_length, count=ctx.count, segment=ctx.segment,
                                                         err=err, out=ctx.out_bwd, g_head=ctx.g_head, g_lead=ctx.g_lead,
                                                         g_params=ctx.g_params)
-        if ctx.check_faults and not torch.cuda.is_current_stream_capturing():
-            MicroRollout.last_bwd_record = err           # (dhts.ops.micro_bwd_fault() reads it on demand)
+        _micro_bwd_done(ctx)
         g_head, g_lead = (g_b, None) if ctx.lead is None else (None, g_b)
         return (g_p0, g_v0, ctx.g_params, g_head, g_lead) + (None,) * 7
 
@@ -1775,6 +1662,11 @@ def _micro_lead_checks(p0, head, T, lead, lead_length, want_hist, checkpoint):
         raise ValueError("lead_length is not differentiable: pass it detached")
 
 
+def _device_slots(slots, device):
+    """The probes micro_sampling returned, uploaded where they are a checked list (after every ValueError of the call)."""
+    return torch.tensor(slots, dtype=torch.int32, device=device) if isinstance(slots, list) else slots
+
+
 def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None, probes=None, every=1,
                   lead=None, lead_length=None, target=None):
     """MicroRollout.  checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape).
@@ -1813,8 +1705,7 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
             _micro_lead_checks(p0, head, T, lead, lead_length, False, checkpoint)
         elif head is None:
             raise ValueError("head must be given (float64 [L][2]) unless lead is")
-        desc = micro_desc(int(p0.shape[0]), int(p0.shape[1]), float(dt))
-        _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_target_plan(desc, int(T), params.requires_grad, sg))
+        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_target_plan)
         return MicroRolloutTarget.apply(p0, v0, params, head, lead, lead_length, count, int(T), float(dt), bool(check_faults), checkpoint,
                                         target)
     if lead is not None or lead_length is not None:
@@ -1822,13 +1713,10 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
             raise ValueError("lead_length needs lead")
         _micro_lead_checks(p0, head, T, lead, lead_length, want_hist, checkpoint)
         sampling = micro_sampling(probes, every, int(p0.shape[-1]), False)
-        desc = micro_desc(int(p0.shape[0]), int(p0.shape[1]), float(dt))
-        _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, int(T), params.requires_grad, sg))
+        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_plan)
         slots, ev = sampling if sampling is not None else (None, 1)
-        if isinstance(slots, list):
-            slots = torch.tensor(slots, dtype=torch.int32, device=p0.device)
-        return MicroRolloutLead.apply(p0, v0, params, lead, lead_length, count, int(T), float(dt), bool(check_faults), checkpoint, slots, ev,
-                                      sampling is not None)
+        return MicroRolloutLead.apply(p0, v0, params, lead, lead_length, count, int(T), float(dt), bool(check_faults), checkpoint,
+                                      _device_slots(slots, p0.device), ev, sampling is not None)
     sampling = micro_sampling(probes, every, int(p0.shape[-1]), want_hist)
     if sampling is None:
         return MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), want_hist, bool(check_faults), checkpoint)
@@ -1837,11 +1725,9 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
         pT, vT, hist = MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), True, bool(check_faults), None)
         return pT, vT, cut_samples(hist, slots, every, count)
     if p0.dim() == 2:                    # (a bad `checkpoint` is a ValueError before the probes are uploaded)
-        desc = micro_desc(int(p0.shape[0]), int(p0.shape[1]), float(dt))
-        _checkpoint_segment(checkpoint, lambda sg: micro_ckpt_plan(desc, int(T), params.requires_grad, sg))
-    if isinstance(slots, list):
-        slots = torch.tensor(slots, dtype=torch.int32, device=p0.device)
-    return MicroRolloutSamples.apply(p0, v0, params, head, count, int(T), float(dt), bool(check_faults), checkpoint, slots, every)
+        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_plan)
+    return MicroRolloutSamples.apply(p0, v0, params, head, count, int(T), float(dt), bool(check_faults), checkpoint,
+                                     _device_slots(slots, p0.device), every)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -23,8 +23,10 @@ sys.path.insert(0, ROOT)
 MACRO_CELLS = (1, 63, 64, 65, 127, 128, 129, 256, 512, 1000, 1024, 1025, 1026, 2048, 2500)
 MACRO_LANES = (1, 255, 256, 1024, 1536, 4096)
 MACRO_T = (0, 1, 1000)
-MICRO_CAP = (1, 64, 65, 128, 129, 256, 1024)
+MICRO_CAP = (1, 63, 64, 65, 128, 129, 256, 1023, 1024)
 MICRO_LANES = (1, 4096, 4097)
+MICRO_T = (0, 1, 7, 1000)
+MICRO_DIRS = (1, 2, 3, 4, 5, 9)
 HYBRID_NETS = ("hybrid_rv_b", "hybrid_rv_d", "hybrid_p3", "hybrid_l10", "hybrid_n2", "hybrid_p2", "hybrid", "hybrid_s2")
 # every option: the values just inside and just outside what it accepts (and a few in between)
 OPTION_VALUES = {
@@ -76,6 +78,24 @@ def sweep(hybrid):
             rc = lib.dhts_micro_rollout_plan(C.byref(d), T, cnt, C.byref(plan))
             out["micro w%d V%d L%d T%d c%d" % (waves, V, L, T, cnt)] = [rc] + list(plan)
     assert opt("OPT_MICRO_FWD_WAVES", 0) == 0
+    # the tape-free micro paths: the two segment plans (and the checkpoint bytes that follow from the first) at the edges of what a
+    # ring holds, the direction grouping of the two tangent sweeps
+    for V, T, want in itertools.product(MICRO_CAP, MICRO_T, (0, 1)):
+        d = _lib.MicroDesc(4, V, 0.01)
+        for kind, fn in (("ckpt", lib.dhts_micro_ckpt_plan), ("ckpt_target", lib.dhts_micro_ckpt_target_plan)):
+            assert fn(C.byref(d), T, want, 0, C.byref(plan)) == 0
+            longest = plan[2]
+            for segment in (0, 1, longest, longest + 1, -1):
+                for k in range(8):
+                    plan[k] = -7                                  # (a refused call leaves the plan as it was: seen as -7)
+                rc = fn(C.byref(d), T, want, segment, C.byref(plan))
+                out["%s V%d T%d q%d s%d" % (kind, V, T, want, segment)] = [rc] + list(plan)
+                if kind == "ckpt" and not want:
+                    out["ckpt_bytes V%d T%d s%d" % (V, T, segment)] = [int(lib.dhts_micro_ckpt_bytes(C.byref(d), T, segment))]
+        for kind, fn in (("jvp", lib.dhts_micro_jvp_plan), ("fwd_jvp", lib.dhts_micro_fwd_jvp_plan)):
+            for n_dir in MICRO_DIRS:
+                rc = fn(C.byref(d), T, n_dir, want, C.byref(plan))
+                out["%s V%d T%d q%d k%d" % (kind, V, T, want, n_dir)] = [rc] + list(plan)
     if hybrid:
         import numpy as np
         import torch
