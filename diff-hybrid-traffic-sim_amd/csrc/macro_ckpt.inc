@@ -16,7 +16,15 @@
 // cell_blocks, the detector columns, six dot2, the hand-over (G + c2_left) + c0_right, the boundary addends in double, the NaN record.
 //
 // (The dynamic LDS array of the two kernels has a name of its own, smem_ck: block-scope extern declarations of one name are one entity.)
+//
+// The file is included twice.  DHTS_MACRO_TARGET 0 gives the pair above and the byte helpers; DHTS_MACRO_TARGET 1 the TARGET forms
+// (kTarget; dhts_macro_rollout_fwd_ckpt_target / _bwd_ckpt_target), macro_rollout_ckpt_fwd_target_kernel<kP, kSched> and
+// macro_rollout_ckpt_bwd_target_kernel<kSched>, from the same text: no detectors (kTaps is false there), `target` [T][L][2][N] -- the
+// observed density and speed of every cell after every step, NaN = not observed -- read by the kernels themselves, the forward's sums
+// of squared residuals sse [L][2] out and their cotangent g_sse back in.  In the first pass kTarget is false and what the second adds
+// sits under it.
 
+#if DHTS_MACRO_TARGET == 0
 // dynamic LDS: the plan (macro_ckpt_plan) and the kernels' own carving read these
 __host__ __device__ inline size_t macro_ckpt_fwd_lds_bytes(int N) { return fwd_jvp_rec_bytes(N); }
 // reverse, fixed part: BwdTail, the lane kernel's records and the general sweep's six cotangent planes of N + 2 floats
@@ -27,17 +35,20 @@ struct __attribute__((aligned(16))) BwdTail {
     float *g_r_out, *g_y_out;
     double *g_ghost;
     dhts_error *err;
-    ptrdiff_t gt_stride;      // kTaps: floats between two rows of g_taps (read back once per sweep step)
+    ptrdiff_t gt_stride;      // kTaps: floats between two rows of g_taps (read back once per sweep step); kTarget: ... of target
     ptrdiff_t ck_stride;      // float2 entries between two rows of ckpt (once per segment)
 };
 __host__ __device__ inline size_t macro_ckpt_bwd_fixed_bytes(int N) { return fwd_jvp_rec_bytes(N) + macro_ckpt_planes_bytes(N) + sizeof(BwdTail); }
-// ... and per step of the segment ring: (A, B) of the N + 1 interfaces
-__host__ __device__ inline size_t macro_ckpt_bwd_step_bytes(int N) { return 2 * sizeof(float4) * (size_t)(N + 1); }
-__host__ __device__ inline size_t macro_ckpt_bwd_lds_bytes(int N, int S) {
-    return macro_ckpt_bwd_fixed_bytes(N) + (size_t)S * macro_ckpt_bwd_step_bytes(N);
+// ... and per step of the segment ring: (A, B) of the N + 1 interfaces; the target form: and the finished cotangent pair of the N cells
+__host__ __device__ inline size_t macro_ckpt_bwd_step_bytes(int N, bool target = false) {
+    return 2 * sizeof(float4) * (size_t)(N + 1) + (target ? 2 * sizeof(float) * (size_t)N : 0);
+}
+__host__ __device__ inline size_t macro_ckpt_bwd_lds_bytes(int N, int S, bool target = false) {
+    return macro_ckpt_bwd_fixed_bytes(N) + (size_t)S * macro_ckpt_bwd_step_bytes(N, target);
 }
 // bytes of one checkpoint row of one lane
 __host__ __device__ inline size_t macro_ckpt_row_bytes(int N) { return sizeof(float2) * (size_t)N; }
+#endif
 
 // grid = L workgroups (one traffic lane each) of W = blockDim.x / 64 wavefronts, the lane kernel's mapping: wave w owns the cells
 // [64 kP w, 64 kP (w + 1)), thread t of its pass j the cell 64 kP w + 64 j + t and that cell's LEFT interface.  kP: 64-cell passes per
@@ -47,14 +58,34 @@ __host__ __device__ inline size_t macro_ckpt_row_bytes(int N) { return sizeof(fl
 // copies for T = 0).  At most 12 wavefronts, as macro_rollout_fwd_jvp_kernel: the longest lane the reverse kernel takes has 11.
 // err: DHTS_FAULT_CFL (step, lane, interface), as the lane kernel raises it.
 // Dynamic LDS: the lane kernel's records (CellRec [N + 2] | flux double2 [N + 1] | queue int [N + 2] | 2 counters).
+// kTarget (macro_rollout_ckpt_fwd_target_kernel): in the update the owner of a cell holds the state after step n - 1, row n - 1 of the
+// history, and beside it in registers that row's two entries of target, asked for a whole step earlier through a per-thread running
+// pointer (no global load on the step's dependent chain); the squared float32 residuals of its valid cells are summed in double in step
+// order and combined per lane behind the loop.  ckpt may be NULL: no checkpoint is stored.
+#if DHTS_MACRO_TARGET == 0
 template <int kP, bool kSched, bool kTaps>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_kernel(
+#else
+template <int kP, bool kSched>
+__global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
+#endif
     int L, int N, int T, int Sg, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
     const float *__restrict__ q_in, const float *__restrict__ ghost,
     float *__restrict__ r_out, float *__restrict__ y_out, float *__restrict__ u_out, float *__restrict__ q_out,
     float2 *__restrict__ ckpt, dhts_error *err,
+#if DHTS_MACRO_TARGET == 0
     const int32_t *__restrict__ det, int n_det, float *__restrict__ taps) {
+    constexpr bool kTarget = false;
+    const float *const target = nullptr;
+    double *const sse = nullptr;
+#else
+    const float *__restrict__ target, double *__restrict__ sse) {
+    constexpr bool kTaps = false, kTarget = true;
+    const int32_t *const det = nullptr;
+    constexpr int n_det = 0;
+    float *const taps = nullptr;
+#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_ck[];
     const int lane = blockIdx.x;
     const int tid = threadIdx.x;
@@ -103,6 +134,19 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_kernel(
     if constexpr (kSched) {
         sched_p = reinterpret_cast<const float4 *>(ghost) + ((size_t)L + lane) * 2 + (tid & 1);
         if (tid < 2 && T > 1) sched_st = *sched_p;
+    }
+    // kTarget: this thread's cells in the row of target that is loaded next (running pointers; a row is L 2 N floats, the speed plane
+    // N floats behind the density plane), the row the next update is held against, and the thread's two sums
+    const float *tgp[kP];
+    float tg_r[kP], tg_u[kP];
+    double sse_r = 0., sse_u = 0.;
+    if constexpr (kTarget) {
+#pragma unroll
+        for (int j = 0; j < kP; ++j) {
+            const int i = lo + (j << 6) + t;
+            tgp[j] = target + (size_t)lane * 2 * N + (i < N ? i : N - 1);
+            tg_r[j] = tgp[j][0]; tg_u[j] = tgp[j][N];
+        }
     }
     // kTaps: thread (blockDim - 1 - tid) takes detector slot tap_j (+ blockDim per further one); tap_wave: this wavefront holds any
     const int tap_j = (int)blockDim.x - 1 - tid;
@@ -153,12 +197,20 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_kernel(
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
                 if (vc && solve) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
                 else if (kTaps && vc) own->st = st;          // the final step's state, for the taps below
+                if constexpr (kTarget) {
+                    // st is row n - 1 of the history: the float32 residuals against that row of target (NaN: not observed), squared
+                    // and summed in double; then row n leaves for the registers, a whole step ahead of the update that reads it
+                    const float er = isnan(tg_r[j]) ? 0.f : st.x - tg_r[j];
+                    const float eu = isnan(tg_u[j]) ? 0.f : st.z - tg_u[j];
+                    if (vc) { sse_r += (double)er * (double)er; sse_u += (double)eu * (double)eu; }
+                    if (solve) { tgp[j] += (size_t)L * 2 * N; tg_r[j] = tgp[j][0]; tg_u[j] = tgp[j][N]; }
+                }
             }
             if (!solve) {
                 if (vc) { r_out[base + i] = st.x; y_out[base + i] = st.y; u_out[base + i] = st.z; q_out[base + i] = st.w; }
                 continue;
             }
-            if (ck_now && vc) ck_row[i] = make_float2(st.x, st.y);
+            if (ck_now && vc && (!kTarget || ckpt)) ck_row[i] = make_float2(st.x, st.y);
             // the left neighbour at this time level: written just above by the lane below, or in the previous pass (a wave's
             // LDS operations complete in order); the first cell of the chunk has its left neighbour in another wave: queued
             wave_lds_handoff();
@@ -215,6 +267,21 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_kernel(
     for (int n = 1; n < T; ++n) body(yes{}, yes{}, n);
     body(yes{}, no{}, T);
     if (fault_step >= 0) raise_fault(err, DHTS_FAULT_CFL, fault_step, lane, fault_index);
+    if constexpr (kTarget) {
+        // the lane's two sums: over the wavefront by the butterfly 32, 16 .. 1, then thread 0 over the wavefronts in their order, through
+        // the LDS the step loop is done with -- one fixed tree for a given launch shape, no atomics
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { sse_r += __shfl_xor(sse_r, o); sse_u += __shfl_xor(sse_u, o); }
+        __syncthreads();
+        double2 *part = reinterpret_cast<double2 *>(smem_ck);
+        if (t == 0) part[wv] = make_double2(sse_r, sse_u);
+        __syncthreads();
+        if (tid == 0) {
+            double2 a = part[0];
+            for (int w = 1; w < Wc; ++w) { a.x += part[w].x; a.y += part[w].y; }
+            sse[(size_t)lane * 2] = a.x; sse[(size_t)lane * 2 + 1] = a.y;
+        }
+    }
 }
 
 // grid = L workgroups of the forward's W wavefronts, the same mapping.  Dynamic LDS (macro_ckpt_bwd_lds_bytes):
@@ -238,14 +305,38 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_kernel(
 // Scalar registers: the replay's step takes about 100 of the 106 by itself, so what the sweep walks (ckpt, g_taps, g_ghost, the
 // schedule) goes through per-thread running pointers in vector registers, and BwdTail holds what is needed once.
 // err: DHTS_FAULT_NAN as macro_rollout_bwd_kernel raises it (every thread reports the first non-finite cotangent it met: the latest step).
+// kTarget (macro_rollout_ckpt_bwd_target_kernel; it excludes kTaps): the per-step cotangent is that of sse, formed here.  The replay of
+// step n holds, in its update (the checkpoint's record for n = s0), the state (r, y, u) after step n - 1 = row n - 1 of the history: its
+// owner loads that row of target at the top of the pass, and at the bottom forms gr = g2r (r - t_r), gy = 0, glue_u_bwd(r, y, um,
+// g2u (u - t_u), gr, gy) -- g2r, g2u = (float)(2 g_sse[lane][0 / 1]), a NaN entry's residual 0: the float32 operations of the dense
+// path's glue on a dense g_hist -- and leaves the pair in two more float planes of the ring, TP[n - s0][0 / 1][cell], since the replay's
+// owner of a cell is not the sweep's.  The sweep adds the pair of row step - 1 behind the hand-over of step, where the columns of kTaps go.
+// Row T - 1 is the forward's final state, which the caller has: fin_r, fin_y, fin_u are read once in front of the loop and the pair goes
+// into the incoming cotangent, as the last row of g_taps does.  The sweep itself takes no global load beyond what it has.
+#if DHTS_MACRO_TARGET == 0
 template <bool kSched, bool kTaps>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
+#else
+template <bool kSched>
+__global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
+#endif
     int L, int N, int T, int Sg, int p, double dt, double dx, double um, const float2 *__restrict__ ckpt,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
     const float *__restrict__ q_in, const float *__restrict__ ghost,
     const float *__restrict__ g_r_in, const float *__restrict__ g_y_in, const float *__restrict__ g_taps,
     float *__restrict__ g_r_out, float *__restrict__ g_y_out, double *__restrict__ g_ghost, dhts_error *err,
+#if DHTS_MACRO_TARGET == 0
     const int32_t *__restrict__ det, int n_det) {
+    constexpr bool kTarget = false;
+    const float *const target = nullptr, *const fin_r = nullptr, *const fin_y = nullptr, *const fin_u = nullptr;
+    const double *const g_sse = nullptr;
+#else
+    const float *__restrict__ target, const double *__restrict__ g_sse,
+    const float *__restrict__ fin_r, const float *__restrict__ fin_y, const float *__restrict__ fin_u) {
+    constexpr bool kTaps = false, kTarget = true;
+    const int32_t *const det = nullptr;
+    constexpr int n_det = 0;
+#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_ck[];
     const int lane = blockIdx.x;
     const int tid = threadIdx.x;
@@ -267,8 +358,10 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
     IfaceConst kc;
     kc.set_um(um); kc.set_grid(dt, dx);
 
-    if (tid == 0) *tail = BwdTail{g_r_out + base, g_y_out + base, g_ghost ? g_ghost + (size_t)lane * 4 : nullptr, err, (ptrdiff_t)L * 2 * n_det,
-                                   (ptrdiff_t)L * N};
+    // kTarget: the cotangent pairs of the ring, float TP[Sg][2][N] behind the planes (macro_ckpt_bwd_step_bytes(N, true) per step in all)
+    float *const TP = pl.Gr + ((6 * P + 3) & ~3);
+    if (tid == 0) *tail = BwdTail{g_r_out + base, g_y_out + base, g_ghost ? g_ghost + (size_t)lane * 4 : nullptr, err,
+                                   kTarget ? (ptrdiff_t)L * 2 * N : (ptrdiff_t)L * 2 * n_det, (ptrdiff_t)L * N};
     for (int k = tid; k < P; k += B) { C0r[k] = 0.f; C0y[k] = 0.f; C2r[k] = 0.f; C2y[k] = 0.f; Gr[k] = 0.f; Gy[k] = 0.f; }
     __syncthreads();
     // kTaps: the sweep's owner of cell k = tid + m B (2 B >= N) adds the detector columns to it itself, so it looks its cells up in
@@ -290,18 +383,38 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
 #pragma unroll
         for (int m = 0; m < 2; ++m) gtp[m] = g_taps + ((size_t)(T - 1) * L + lane) * 2 * n_det + (col[m] >= 0 ? col[m] : 0);
     }
+    // kTarget: twice the cotangent of the lane's two sums, in float32 (per thread: the scalar registers are the replay's)
+    float g2r = 0.f, g2u = 0.f;
+    if constexpr (kTarget) {
+        g2r = (float)(2. * g_sse[(size_t)lane * 2]); g2u = (float)(2. * g_sse[(size_t)lane * 2 + 1]);
+        asm volatile("" : "+v"(g2r), "+v"(g2u));         // (held in vector registers from here on)
+    }
+    // the cotangent pair of one history row at one cell, from the state (r, y, u) there and the row's two entries of target
+    auto fit_pair = [&](const float r, const float y, const float u, const float t_r, const float t_u, float &gr, float &gy) {
+        gr = isnan(t_r) ? 0.f : g2r * (r - t_r);
+        gy = 0.f;
+        glue_u_bwd(r, y, (float)um, isnan(t_u) ? 0.f : g2u * (u - t_u), gr, gy);
+    };
     // the cotangent of the final state, and in front of step T - 1 its detector columns (macro_rollout_bwd_kernel: Gr[det[j] + 1] += gt[j])
+    // resp. (kTarget) the pair of row T - 1, from the forward's final state
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const int k = tid + m * B;
         if (k < N) {
             float gr = g_r_in[base + k], gy = g_y_in[base + k];
             if (kTaps && col[m] >= 0) { gr += gtp[m][0]; gy += gtp[m][n_det]; }
+            if constexpr (kTarget) {
+                const float *tg = target + ((size_t)(T - 1) * L + lane) * 2 * N + k;
+                float ar, ay;
+                fit_pair(fin_r[base + k], fin_y[base + k], fin_u[base + k], tg[0], tg[N], ar, ay);
+                gr += ar; gy += ay;
+            }
             Gr[k + 1] = gr; Gy[k + 1] = gy;
         }
     }
     __syncthreads();
 
+    if constexpr (kTarget) __builtin_assume(p >= 1 && p <= 2);      // (the plan names no other: the pass loops' entry tests hold no scalar registers)
     const int lo = wv * (p << 6);
     const double c = dt / dx;
     const float cf = (float)c, ncf = (float)(-c);
@@ -319,6 +432,13 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
 
     double ghl_r = 0., ghl_y = 0., ghr_r = 0., ghr_y = 0.;   // ghost cotangent sums (thread 0 / thread of cell N-1)
     int bad_step = -1, bad_cell = 0;     // first non-finite cotangent this thread meets (the reverse sweep's first = the latest step)
+    // kTarget: the thread's first cell in the row of target the replay reads next (a per-thread running pointer), and where the pairs of
+    // that step go in the ring
+    const int own0 = lo + t;
+    const float *tg_run = nullptr;
+    float *tp0 = TP + own0;              // (per thread, and opaque to the compiler from here on: a vector register, like g2r / g2u)
+    if constexpr (kTarget) asm volatile("" : "+v"(tp0));
+    float *tp_run = tp0;
 
     // the replay of step n, s_end = one past the segment's last step; RA / RB = the ring entry of step n
     auto body = [&](auto upd_c, const int n, const int s_end, float4 *RA, float4 *RB) {
@@ -341,6 +461,11 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
             const unsigned ic = (unsigned)(vc ? i : N - 1);
             CellRec *own = CR + ic + 1;
             float4 st = own->st;
+            // kTarget: row n - 1 of target at this cell, asked for here and used at the bottom of the pass
+            float t_r = 0.f, t_u = 0.f;
+            if constexpr (kTarget) {
+                if (n > 0) { const float *tg = tg_run + ((int)ic - own0); t_r = tg[0]; t_u = tg[N]; }
+            }
             if (upd) {
                 // Godunov update, _macro_lane.py:109-112, float32 store :327-334
                 const double2 Fl = FX[ic], Fr = FX[ic + 1];
@@ -369,7 +494,15 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
             }
             const bool nt = vc & !triv;
             if (nt) Q[atomicAdd(cnt, 1)] = i;
+            if constexpr (kTarget) {
+                if (n > 0) {                 // st is row n - 1 of the history: its finished cotangent pair, for the sweep's owner of the cell
+                    float ar, ay;
+                    fit_pair(st.x, st.y, st.z, t_r, t_u, ar, ay);
+                    if (vc) { float *tp = tp_run + ((int)ic - own0); tp[0] = ar; tp[N] = ay; }
+                }
+            }
         }
+        if constexpr (kTarget) { tg_run += tail->gt_stride; tp_run += 2 * N; }
         lds_only_barrier();
         // ---- phase 2: the queued interfaces ----
         int k0 = tid - (rot << 6);
@@ -421,13 +554,19 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
         CellRec *gr = CR + (tid ? N + 1 : 0);
         gr->st = st; gr->sh = make_double2(cg.s, cg.h); gr->q0 = make_double2(cg.q0, 0.);
     }
+    // kTarget: the row in front of the last segment's first step; the replay moves the pointer a row per step, and behind it the pointer
+    // goes back to the row in front of the segment before (for segment 0 that is no row, and nothing is read there)
+    if constexpr (kTarget) tg_run = target + (size_t)lane * 2 * N + own0 + ((ptrdiff_t)(C - 1) * Sg - 1) * ((ptrdiff_t)L * 2 * N);
     for (int seg = C - 1; seg >= 0; --seg) {
         const int s0 = seg * Sg, s1 = (T - s0 < Sg) ? T : s0 + Sg;
         // ---- the records step s0 starts from ----
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int i = lo + (j << 6) + t;
-            const bool vc = j < p && i < N;
+            int i = lo + (j << 6) + t, pj = p;
+            // (kTarget: opaque, so that the masks below are formed here, once per segment, and hold no scalar registers across the
+            // replay and the sweep, where this form has none to spare)
+            if constexpr (kTarget) asm volatile("" : "+v"(i), "+v"(pj));
+            const bool vc = j < pj && i < N;
             const unsigned ic = (unsigned)(vc ? i : N - 1);
             float4 st;
             CellPre cp;
@@ -454,6 +593,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
             if (tid < 2 && s0 + 1 < s1) sched_st = *sched_p;
         }
         if (tid == 0) { Q[0] = N; CNT[0] = 1; CNT[1] = 1; }      // entry 0 of every step's queue: interface N
+        if constexpr (kTarget) tp_run = tp0;
         lds_only_barrier();
         // ---- replay steps [s0, s1) into the ring ----
         body(no{}, s0, s1, R, R + (N + 1));
@@ -461,6 +601,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
             float4 *RA = R + (size_t)(n - s0) * 2 * (N + 1);
             body(yes{}, n, s1, RA, RA + (N + 1));
         }
+        if constexpr (kTarget) tg_run -= (ptrdiff_t)(s1 - s0 + Sg) * tail->gt_stride;
         // ---- sweep them newest first, out of the ring: macro_rollout_bwd_kernel's step ----
         for (int step = s1 - 1; step >= s0; --step) {
             const float4 *RA = R + (size_t)(step - s0) * 2 * (N + 1), *RB = RA + (N + 1);
@@ -506,6 +647,9 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
                     float ny = (Gy[k + 1] + c2ly) + c0ry;
                     if (bad_step < 0 && !(isfinite(nr) && isfinite(ny))) { bad_step = step; bad_cell = k; }
                     if (kTaps && step > 0 && col[m] >= 0) { nr += ar[m]; ny += ay[m]; }      // in front of step - 1: Gr[det[j] + 1] += gt[j]
+                    if constexpr (kTarget) {
+                        if (step > 0) { const float *tp = tp0 + ((step - s0) * 2 * N + k - own0); nr += tp[0]; ny += tp[N]; }      // row step - 1
+                    }
                     Gr[k + 1] = nr; Gy[k + 1] = ny;
                 }
             }

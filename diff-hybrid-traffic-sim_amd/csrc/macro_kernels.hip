@@ -1521,7 +1521,13 @@ __global__ void macro_u_tap_bwd_kernel(int64_t n, float um, const float *__restr
 #include "macro_fwd_jvp.inc"
 
 // ---- reverse mode from checkpoints, the segment's interface products in LDS (dhts_macro_rollout_fwd_ckpt / _bwd_ckpt) ----
+#define DHTS_MACRO_TARGET 0
 #include "macro_ckpt.inc"
+#undef DHTS_MACRO_TARGET
+// ---- the dense-fit loss inside the checkpointed pair (dhts_macro_rollout_*_ckpt_target): the text of macro_ckpt.inc once more ----
+#define DHTS_MACRO_TARGET 1
+#include "macro_ckpt.inc"
+#undef DHTS_MACRO_TARGET
 
 }  // namespace dhts
 
@@ -1919,7 +1925,8 @@ struct MacroCkptPlan {
     int max_segment;      // the longest one the reverse kernel's LDS holds; 0: the lane does not fit
     size_t lds_fwd;
 };
-static MacroCkptPlan macro_ckpt_plan(const dhts_macro_desc *d) {
+// target: the plan of the target forms (dhts_macro_ckpt_target_plan), whose ring step is two float planes wider: the same rule
+static MacroCkptPlan macro_ckpt_plan(const dhts_macro_desc *d, bool target = false) {
     MacroCkptPlan pl = {};
     const int N = d->n_cells;
     int W = (N + 127) / 128;
@@ -1927,7 +1934,7 @@ static MacroCkptPlan macro_ckpt_plan(const dhts_macro_desc *d) {
     pl.p = (N + 64 * W - 1) / (64 * W);
     pl.W = (N + 64 * pl.p - 1) / (64 * pl.p);
     pl.lds_fwd = macro_ckpt_fwd_lds_bytes(N);
-    const size_t fixed = macro_ckpt_bwd_fixed_bytes(N), step = macro_ckpt_bwd_step_bytes(N);
+    const size_t fixed = macro_ckpt_bwd_fixed_bytes(N), step = macro_ckpt_bwd_step_bytes(N, target);
     pl.max_segment = fixed + step <= kMacroCkptLdsBudget && pl.p <= 2 ? (int)((kMacroCkptLdsBudget - fixed) / step) : 0;
     const int by_regs = (kMacroCkptWavesPerCu + pl.W - 1) / pl.W;               // workgroups per CU that make kMacroCkptWavesPerCu
     const int at_one = (int)(kMacroCkptLdsBudget / (fixed + step));             // ... that a one-step ring leaves
@@ -1946,20 +1953,31 @@ static int macro_ckpt_segment(const MacroCkptPlan &pl, int segment) {
 }
 static int macro_ckpt_count(int T, int S) { return T > 0 ? (T + S - 1) / S : 0; }
 
+// What a call of the target forms fits (host only): target [T][L][2][N] with the forward's sums sse [L][2] resp. the reverse sweep's
+// g_sse [L][2] and the forward's final state; `target` NULL: not a target form (the detector arguments apply then)
+struct MacroFit {
+    const float *target;
+    double *sse;
+    const double *g_sse;
+    const float *fin_r, *fin_y, *fin_u;
+};
 static int macro_ckpt_fwd_launch(const dhts_macro_desc *d, int T, int S, const MacroCkptPlan &pl,
                                  const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
                                  float *r_out, float *y_out, float *u_out, float *ueq_out, const int32_t *det, int n_det, float *taps,
-                                 void *ckpt, dhts_error *err, void *stream) {
+                                 void *ckpt, dhts_error *err, void *stream, const MacroFit &fit = MacroFit{}) {
     const int L = d->n_lanes, N = d->n_cells;
     bool lds_ok = true;
+    auto go = [&](auto kernel, auto... tail) {
+        lds_ok = launch_lds(kernel, L, 64 * pl.W, pl.lds_fwd, kLdsDefault, stream, L, N, T, S, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, r_out,
+                            y_out, u_out, ueq_out, reinterpret_cast<float2 *>(ckpt), err, tail...);
+    };
     pick<1, 2>(pl.p, [&](auto pv) {
         pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
-            pick<0, 1>(det != nullptr, [&](auto tap) {
-                constexpr int kP = decltype(pv)::value;
-                constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
-                lds_ok = launch_lds(macro_rollout_ckpt_fwd_kernel<kP, kS, kT>, L, 64 * pl.W, pl.lds_fwd, kLdsDefault, stream, L, N, T, S, d->dt,
-                                    d->dx, d->u_max, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, reinterpret_cast<float2 *>(ckpt), err,
-                                    det, n_det, taps);
+            pick<0, 1, 2>(fit.target ? 2 : det != nullptr, [&](auto tap) {
+                constexpr int kP = decltype(pv)::value, kForm = decltype(tap)::value;
+                constexpr bool kS = decltype(sc)::value != 0;
+                if constexpr (kForm == 2) go(macro_rollout_ckpt_fwd_target_kernel<kP, kS>, fit.target, fit.sse);
+                else go(macro_rollout_ckpt_fwd_kernel<kP, kS, kForm != 0>, det, n_det, taps);
             });
         });
     });
@@ -1968,15 +1986,20 @@ static int macro_ckpt_fwd_launch(const dhts_macro_desc *d, int T, int S, const M
 static int macro_ckpt_bwd_launch(const dhts_macro_desc *d, int T, int S, const MacroCkptPlan &pl, const void *ckpt,
                                  const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
                                  const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
-                                 float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
+                                 float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream, const MacroFit &fit = MacroFit{}) {
     const int L = d->n_lanes, N = d->n_cells;
     bool lds_ok = true;
+    auto go = [&](auto kernel, size_t lds, auto... tail) {
+        lds_ok = launch_lds(kernel, L, 64 * pl.W, lds, kLdsDefault, stream, L, N, T, S, pl.p, d->dt, d->dx, d->u_max,
+                            reinterpret_cast<const float2 *>(ckpt), r, y, u, ueq, ghost, g_r, g_y, g_taps, g_r_out, g_y_out, g_ghost, err, tail...);
+    };
     pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
-        pick<0, 1>(det != nullptr, [&](auto tap) {
-            constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
-            lds_ok = launch_lds(macro_rollout_ckpt_bwd_kernel<kS, kT>, L, 64 * pl.W, macro_ckpt_bwd_lds_bytes(N, S), kLdsDefault, stream, L, N, T, S,
-                                pl.p, d->dt, d->dx, d->u_max, reinterpret_cast<const float2 *>(ckpt), r, y, u, ueq, ghost, g_r, g_y, g_taps,
-                                g_r_out, g_y_out, g_ghost, err, det, n_det);
+        pick<0, 1, 2>(fit.target ? 2 : det != nullptr, [&](auto tap) {
+            constexpr bool kS = decltype(sc)::value != 0;
+            constexpr int kForm = decltype(tap)::value;
+            if constexpr (kForm == 2)
+                go(macro_rollout_ckpt_bwd_target_kernel<kS>, macro_ckpt_bwd_lds_bytes(N, S, true), fit.target, fit.g_sse, fit.fin_r, fit.fin_y, fit.fin_u);
+            else go(macro_rollout_ckpt_bwd_kernel<kS, kForm != 0>, macro_ckpt_bwd_lds_bytes(N, S), det, n_det);
         });
     });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
@@ -2244,6 +2267,56 @@ int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, co
     }
     return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, det, det ? n_det : 0, g_taps, g_r_out, g_y_out,
                                  g_ghost, err, stream);
+}
+// ---- the dense-fit loss inside the checkpointed pair ----------------------------------------------------------------------------
+int dhts_macro_ckpt_target_plan(const dhts_macro_desc *d, int T, int segment, int32_t plan[8]) {
+    if (!macro_desc_ok(d) || T < 0 || !plan || segment < 0) return DHTS_E_INVALID;
+    const MacroCkptPlan pl = macro_ckpt_plan(d, true);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.W; plan[1] = pl.p; plan[3] = pl.max_segment; plan[5] = (int32_t)pl.lds_fwd;
+    if (pl.max_segment < 1) return segment == 0 ? DHTS_OK : DHTS_E_INVALID;       // the lane does not fit: max_segment = 0 says so
+    const int S = macro_ckpt_segment(pl, segment);
+    if (S < 0) return DHTS_E_INVALID;
+    const size_t bwd_lds = macro_ckpt_bwd_lds_bytes(d->n_cells, S, true);
+    plan[2] = S;
+    plan[4] = macro_ckpt_count(T, S);
+    plan[6] = (int32_t)bwd_lds;
+    plan[7] = (int32_t)(kMacroCkptLdsBudget / bwd_lds);
+    return DHTS_OK;
+}
+int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segment,
+                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                       float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const float *target, double *sse,
+                                       dhts_error *err, void *stream) {
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || !sse || (T > 0 && !target)) return DHTS_E_INVALID;
+    const MacroCkptPlan pl = macro_ckpt_plan(d, true);
+    const int S = macro_ckpt_segment(pl, segment);
+    if (S < 0) return DHTS_E_INVALID;
+    if (T == 0) {                                                // no step: no row is addressed, and the empty sums are 0
+        if (hipMemsetAsync(sse, 0, sizeof(double) * 2 * (size_t)d->n_lanes, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
+    }
+    return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, ghost_is_sched, r_out, y_out, u_out, ueq_out, nullptr, 0, nullptr, ckpt, err,
+                                 stream, MacroFit{target, sse, nullptr, nullptr, nullptr, nullptr});
+}
+int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                       const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
+                                       const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out, double *g_ghost,
+                                       dhts_error *err, void *stream) {
+    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !r || !y || !u || !ueq || !ghost || !g_r || !g_y || !g_r_out || !g_y_out ||
+        (ghost_is_sched && !g_ghost))
+        return DHTS_E_INVALID;
+    // the fit's cotangent needs the observations and the forward's final state (row T - 1 of the history)
+    if (T > 0 && (!target || (g_sse && (!r_fin || !y_fin || !u_fin)))) return DHTS_E_INVALID;
+    const MacroCkptPlan pl = macro_ckpt_plan(d, true);
+    const int S = macro_ckpt_segment(pl, segment);
+    if (S < 0) return DHTS_E_INVALID;
+    if (T == 0 || !g_sse)            // no step, or no cotangent of the sums: the plain sweep (the segment is the TARGET plan's, which fits it)
+        return dhts_macro_rollout_bwd_ckpt(d, T, S, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, nullptr, 0, nullptr, g_r_out, g_y_out,
+                                           g_ghost, err, stream);
+    return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, nullptr, 0, nullptr, g_r_out, g_y_out, g_ghost,
+                                 err, stream, MacroFit{target, nullptr, g_sse, r_fin, y_fin, u_fin});
 }
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,
                                  void *stream) {

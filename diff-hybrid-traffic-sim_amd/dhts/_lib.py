@@ -104,6 +104,9 @@ SIGNATURES = {
     "dhts_macro_ckpt_bytes": (C.c_size_t, [C.POINTER(MacroDesc), C.c_int, C.c_int]),
     "dhts_macro_rollout_fwd_ckpt": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 4),
     "dhts_macro_rollout_bwd_ckpt": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 6 + [C.c_int] + [_P] * 3 + [C.c_int] + [_P] * 6),
+    "dhts_macro_ckpt_target_plan": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
+    "dhts_macro_rollout_fwd_ckpt_target": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 9),
+    "dhts_macro_rollout_bwd_ckpt_target": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 6 + [C.c_int] + [_P] * 12),
     "dhts_macro_state_from_ru_jvp": (C.c_int, [C.c_int64, C.c_double] + [_P] * 6),
     "dhts_macro_u_tap_jvp": (C.c_int, [C.c_int64, C.c_double] + [_P] * 6),
     "dhts_macro_tape_expand": (C.c_int, [C.POINTER(MacroDesc), C.c_int] + [_P] * 3),

@@ -405,6 +405,103 @@ class MacroRollout(torch.autograd.Function):
         return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None, None, None
 
 
+class MacroRolloutTarget(torch.autograd.Function):
+    """MacroRollout's checkpointed call fitted to an observed space-time field inside the kernels: (r0, u0 [L][N], ghost_r, ghost_u [L][2]
+    or a schedule [T][L][2]) -> (rT, yT, uT, qT, sse [L][2] float64), sse[l] = the sums over observed entries of target [T][L][2][N] of
+    (x - target)^2 for the density and for the speed after every step (dhts_macro_rollout_fwd_ckpt_target / _bwd_ckpt_target).  No
+    [T][L][3][N] history and no cotangent of one exists: the forward accumulates, the reverse sweep forms 2 g_sse (x - target) from the
+    state it replays.  Every buffer of both directions is made in forward; without a leaf that requires grad none is."""
+
+    @staticmethod
+    def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, check_faults, checkpoint, target):
+        L, N = r0.shape
+        sched = ghost_r.dim() == 3
+        if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
+            raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
+        want = (int(T), L, 2) if sched else (L, 2)
+        if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
+            raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
+        desc = macro_desc(L, N, dt, dx, u_max)
+        segment = _macro_target_segment(checkpoint, desc, T)
+        dev = r0.device
+        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+        gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
+        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
+        gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
+        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4], or [T][L][2][4]
+        del gy
+        need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
+        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
+        err = new_error_record(dev)
+        (rT, yT, uT, qT), sse = macro_rollout_fwd_ckpt_target(desc, T, r0c, y0, u0c, q0, ghost, ckpt, target, segment=segment, err=err)
+        if check_faults:
+            raise_on_fault(err)
+        if need_grad:
+            # ... and here also the reverse sweep's outputs
+            ctx.out_bwd = (torch.empty(L, N, dtype=torch.float32, device=dev), torch.empty(L, N, dtype=torch.float32, device=dev))
+            ctx.g_ghost = torch.empty((max(int(T), 1), L, 2, 2) if sched else (L, 2, 2), dtype=torch.float64, device=dev)
+            ctx.ckpt, ctx.replay, ctx.target = ckpt, (y0, q0, ghost), target
+            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
+            ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, uT)
+        ctx.mark_non_differentiable(qT)
+        return rT, yT, uT, qT, sse
+
+    @staticmethod
+    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_sse):
+        r0, u0, gr, gu, gq, rT, yT, uT = ctx.saved_tensors
+        desc, T, um = ctx.desc, ctx.T, ctx.u_max
+        L, N = desc.n_lanes, desc.n_cells
+        dev = r0.device
+        g_r = g_rT.contiguous().clone() if g_rT is not None else torch.zeros(L, N, device=dev)
+        g_y = g_yT.contiguous().clone() if g_yT is not None else torch.zeros(L, N, device=dev)
+        if g_uT is not None:
+            macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
+        err = new_error_record(dev)
+        y0, q0, ghost = ctx.replay
+        g_r0, g_y0, g_ghost = macro_rollout_bwd_ckpt_target(desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, ctx.target,
+                                                            g_sse=g_sse.contiguous() if g_sse is not None else None, final=(rT, yT, uT),
+                                                            segment=ctx.segment, err=err, out=ctx.out_bwd, g_ghost=ctx.g_ghost)
+        del y0, q0, ghost                # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
+        ctx.replay = ctx.ckpt = None
+        if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
+            raise_on_fault(err)
+        g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
+        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um, rows=_glue_rows(T, 2 * L))
+        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None, None
+
+
+def _macro_target_segment(checkpoint, desc, T):
+    """dhts.macro_rollout's `checkpoint` beside `target` -> the segment length of the target forms' own plan; ValueError otherwise."""
+    def plan(segment):
+        if macro_ckpt_target_plan(desc, T, 0)["max_segment"] < 1:
+            raise ValueError("lanes of %d cells do not fit the target forms of the checkpointed sweep (the reverse LDS of the target plan "
+                             "holds up to %d cells): fit the want_hist=True history instead" % (desc.n_cells, MACRO_CKPT_TARGET_MAX_CELLS))
+        return macro_ckpt_target_plan(desc, T, segment)
+    return _checkpoint_segment(checkpoint, plan)
+
+
+def _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint):
+    """Every ValueError of dhts.macro_rollout's `target`, raised before anything touches a device."""
+    if checkpoint is None or checkpoint is False:
+        raise ValueError("target lives on the checkpointed path only: pass checkpoint=True (or a segment length)")
+    if want_hist:
+        raise ValueError("target does not take want_hist: the history is what target= does without")
+    if detectors is not None:
+        raise ValueError("target does not take detectors: it is the dense fit (NaN entries of target are the unobserved ones)")
+    if r0.dim() != 2:
+        raise ValueError("r0 must be [L][N]")
+    L, N = int(r0.shape[0]), int(r0.shape[1])
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != (int(T), L, 2, N):
+        raise ValueError("target must be a float32 tensor of shape (T, L, 2, N) = (%d, %d, 2, %d)" % (int(T), L, N))
+    if target.device != r0.device:
+        raise ValueError("target must live on r0's device (%s), not %s" % (r0.device, target.device))
+    if not target.is_contiguous():
+        raise ValueError("target must be contiguous: a copy of it is as large as the history it replaces")
+    if target.requires_grad:
+        raise ValueError("target is data and not differentiable: pass it detached")
+    _macro_target_segment(checkpoint, macro_desc(L, N, float(dt), float(dx), float(u_max)), int(T))
+
+
 def _macro_checkpoint_segment(checkpoint, desc, T, want_hist, n_det):
     """dhts.macro_rollout's `checkpoint` -> None (the taped path) or the segment length; ValueError otherwise, before a device is touched."""
     if checkpoint is None or checkpoint is False:
@@ -450,7 +547,8 @@ def _detector_cells(detectors, N):
     return cells
 
 
-def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None, checkpoint=None):
+def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None, target=None,
+                  checkpoint=None):
     """T fused differentiable steps of L straight ARZ lanes (MacroRollout): returns (rT, yT, uT, qT), with want_hist also hist [T][L][3][N].
     checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape; MacroRollout).
 
@@ -459,7 +557,16 @@ def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, c
     capture sees no upload and no synchronisation and which is therefore NOT validated: the kernels skip an index outside [0, N) (its
     column of the readings stays unwritten) and never form an address from one.  Returns (rT, yT, uT, qT, readings) then, readings
     [T][L][3][D] = (r, y, u) of cell detectors[j] after every step, differentiable in all three; no [T][L][N] history is written or
-    read.  Not together with want_hist (ValueError): a caller who wants every cell has the history."""
+    read.  Not together with want_hist (ValueError): a caller who wants every cell has the history.
+
+    target (with checkpoint only; not with want_hist or detectors): the observed field, float32 [T][L][2][N] on r0's device, contiguous,
+    not requiring grad -- target[t][l][0][k] the density of cell k after step t (hist[t][l][0][k]), target[t][l][1][k] the speed
+    (hist[t][l][2][k]), NaN = not observed.  Returns (rT, yT, uT, qT, sse) then: sse float64 [L][2], per lane the sum of the squared
+    float32 density residuals and of the squared speed residuals, differentiable; the kernels read target themselves and neither a
+    history nor its cotangent exists (MacroRolloutTarget).  The segment is that of macro_ckpt_target_plan."""
+    if target is not None:
+        _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
+        return MacroRolloutTarget.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), check_faults, checkpoint, target)
     det = None
     if detectors is not None:
         if want_hist:
@@ -722,6 +829,106 @@ def macro_rollout_bwd_ckpt(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment
                                                  _ptr(u), _ptr(ueq), _ptr(ghost), int(sched), _ptr(g_r), _ptr(g_y), _ptr(det), D,
                                                  None if det is None else C.c_void_p(g_taps.data_ptr() or det.data_ptr()),
                                                  _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err), _stream()), "dhts_macro_rollout_bwd_ckpt")
+    return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
+
+
+# ---- the dense-fit loss inside the checkpointed pair (dhts_macro_rollout_*_ckpt_target) ------------------------------------------------
+MACRO_CKPT_TARGET_MAX_CELLS = 1239      # the longest lane the target forms' reverse LDS holds (one ring step of 32 (N + 1) + 8 N bytes; the plan is the truth)
+
+
+def macro_ckpt_target_plan(desc, T, segment=0):
+    """macro_ckpt_plan for dhts_macro_rollout_fwd_ckpt_target / _bwd_ckpt_target (include/dhts.h): the same keys; the reverse kernel's
+    ring holds two more floats per cell-step, so max_segment and the default segment are shorter and fewer lanes fit (max_segment = 0).
+    ValueError: a segment outside 0 .. max_segment.  Needs no device."""
+    plan = (C.c_int32 * 8)()
+    if not 0 <= int(segment) <= 0x7fffffff:
+        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
+    status = _lib.lib().dhts_macro_ckpt_target_plan(C.byref(desc), int(T), int(segment), C.byref(plan))
+    if status == _lib.E_INVALID and int(segment) and _lib.lib().dhts_macro_ckpt_target_plan(C.byref(desc), int(T), 0, C.byref(plan)) == 0:
+        raise ValueError("segment must be 0 (the plan's choice) or 1 .. the max_segment of the target forms (%d) for lanes of %d cells"
+                         % (plan[3], desc.n_cells))
+    check(status, "dhts_macro_ckpt_target_plan")
+    return dict(zip(_MACRO_CKPT_PLAN_KEYS, list(plan)))
+
+
+def _macro_target_args(desc, T, segment, ckpt, target, need_ckpt):
+    """What both raw target wrappers check of ckpt and target before _macro_ckpt_args -> the resolved segment."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    plan = macro_ckpt_target_plan(desc, T, segment)
+    if plan["max_segment"] < 1:
+        raise ValueError("lanes of %d cells do not fit the target forms of the checkpointed sweep (their LDS holds up to %d cells)"
+                         % (N, MACRO_CKPT_TARGET_MAX_CELLS))
+    if ckpt is None and need_ckpt:
+        raise ValueError("ckpt must be a contiguous float32 [macro_ckpt_numel(desc, T, segment)]")
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != (T, L, 2, N) or \
+            not target.is_contiguous():
+        raise ValueError("target must be a contiguous float32 tensor of shape (%d, %d, 2, %d)" % (T, L, N))
+    return plan["segment"]
+
+
+def macro_rollout_fwd_ckpt_target(desc, T, r, y, u, ueq, ghost, ckpt, target, segment=0, sse=None, err=None, out=None):
+    """macro_rollout_fwd_ckpt that reads the observed field `target` (float32 [T][L][2][N]: density and speed after every step, NaN = not
+    observed) and returns the squared error (dhts_macro_rollout_fwd_ckpt_target): ((r, y, u, ueq) after T steps, sse float64 [L][2]).
+    ckpt: float32 [macro_ckpt_numel(desc, T, S)] with S the resolved segment of macro_ckpt_target_plan, or None: no checkpoint is kept.
+    segment 0: that plan's default."""
+    L, T = desc.n_lanes, int(T)
+    S = _macro_target_args(desc, T, segment, ckpt, target, False)
+    keep = ckpt if ckpt is not None else torch.empty(macro_ckpt_numel(desc, T, S), dtype=torch.float32, device="meta")
+    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, S, keep, r, y, u, ueq, ghost)
+    if sse is None:
+        sse = torch.empty(L, 2, dtype=torch.float64, device=r.device)
+    elif tuple(sse.shape) != (L, 2) or sse.dtype != torch.float64 or not sse.is_cuda or not sse.is_contiguous():
+        raise ValueError("sse must be a contiguous float64 CUDA tensor of shape (%d, 2)" % L)
+    if not target.is_cuda:
+        raise TypeError("target is not a CUDA tensor")
+    if out is None:
+        out = tuple(torch.empty_like(r) for _ in range(4))
+    check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target(C.byref(desc), T, S, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
+                                                        _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                                                        _ptr(ckpt) if ckpt is not None and ckpt.numel() else None,
+                                                        _ptr(target) if target.numel() else None, _ptr(sse), _ptr(err), _stream()),
+          "dhts_macro_rollout_fwd_ckpt_target")
+    return out, sse
+
+
+def macro_rollout_bwd_ckpt_target(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, target, g_sse=None, final=None, segment=0, err=None,
+                                  out=None, g_ghost=None):
+    """The reverse sweep of macro_rollout_fwd_ckpt_target (dhts_macro_rollout_bwd_ckpt_target) -> (g_r0, g_y0, g_ghost) as
+    macro_rollout_bwd_ckpt.  g_sse float64 [L][2] or None (zero: the plain sweep): the cotangent of sse; the per-step cotangent
+    (float)(2 g_sse) * (x - target), through the speed's glue, is formed in the kernel.  final: the forward's (r, y, u) after T steps,
+    needed with g_sse.  r, y, u, ueq, ghost, target, segment: the forward's."""
+    L, N, T = desc.n_lanes, desc.n_cells, int(T)
+    S = _macro_target_args(desc, T, segment, ckpt, target, True)
+    if g_sse is not None:
+        if tuple(g_sse.shape) != (L, 2) or g_sse.dtype != torch.float64:
+            raise ValueError("g_sse must be a float64 tensor of shape (%d, 2)" % L)
+        if final is None or len(final) != 3 or any(tuple(t.shape) != (L, N) for t in final):
+            raise ValueError("g_sse needs final = the forward's (r, y, u) after T steps, each of shape (%d, %d)" % (L, N))
+    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, S, ckpt, r, y, u, ueq, ghost)
+    if g_sse is not None:
+        g_sse = g_sse.contiguous()
+        final = tuple(_f32c(t, n) for t, n in zip(final, ("final r", "final y", "final u")))
+    else:
+        final = (None, None, None)
+    g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
+    if tuple(g_r.shape) != (L, N) or tuple(g_y.shape) != (L, N):
+        raise ValueError("g_r and g_y must have shape (%d, %d)" % (L, N))
+    if not target.is_cuda:
+        raise TypeError("target is not a CUDA tensor")
+    if out is None:
+        out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
+    if g_ghost is None:
+        g_ghost = torch.empty(want, dtype=torch.float64, device=g_r.device)         # a schedule's: every row is written
+    elif tuple(g_ghost.shape) != want or g_ghost.dtype != torch.float64 or not g_ghost.is_contiguous():
+        raise ValueError("g_ghost must be a contiguous float64 tensor of shape %s" % (want,))
+    if not sched:
+        g_ghost.zero_()
+    check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target(C.byref(desc), T, S, _ptr(ckpt) if ckpt.numel() else None, _ptr(r), _ptr(y), _ptr(u),
+                                                        _ptr(ueq), _ptr(ghost), int(sched), _ptr(g_r), _ptr(g_y),
+                                                        _ptr(target) if target.numel() else None, _ptr(g_sse), _ptr(final[0]),
+                                                        _ptr(final[1]), _ptr(final[2]), _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err),
+                                                        _stream()), "dhts_macro_rollout_bwd_ckpt_target")
     return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
 
 

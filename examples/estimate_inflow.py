@@ -9,7 +9,11 @@ on the detector READINGS (dhts.macro_rollout with detectors=...: the state at th
 (ghost_r, ghost_u of shape [T][L][2]).  --readings history takes the readings out of the full state history (want_hist=True)
 instead: the same numbers, log line for log line, at the cost of the history.  --checkpoint [S] keeps the state every S steps
 instead of the rollout tape and replays a segment at a time in the reverse sweep: again the same log, for horizons whose tape does not
-fit the device.  Every trial solves n_lane independent problems at
+fit the device.  --readings field fits the whole density field instead of a few detectors (a density field from video or trajectory
+data): the loss, summed in double, is on the density plane of the want_hist=True history; with --checkpoint [S] --fused-loss the
+checkpointed kernels read the observed field themselves (dhts.macro_rollout(checkpoint=..., target=...); its speed plane is NaN, not
+observed) and return the sums, so that neither the history nor its cotangent exists: the same profile errors and, to the rounding of a
+double sum, the same losses.  Every trial solves n_lane independent problems at
 once.  What a detector at cell c can see of the profile ends c cells' travel time before the end of the horizon: the tail of the
 profile stays at its first guess.
 
@@ -43,15 +47,22 @@ def main():
     ap.add_argument("--n_detector", type=int, default=4)
     ap.add_argument("--lr", type=float, default=2e-2)
     ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--readings", choices=("detectors", "history"), default="detectors",
-                    help="read the detectors through dhts.macro_rollout(detectors=...) or out of the full state history")
+    ap.add_argument("--readings", choices=("detectors", "history", "field"), default="detectors",
+                    help="read the detectors through dhts.macro_rollout(detectors=...) or out of the full state history; field: fit the "
+                         "density of every cell after every step")
     ap.add_argument("--checkpoint", nargs="?", type=int, const=0, default=None, metavar="S",
                     help="reverse mode from checkpoints instead of the tape (dhts.macro_rollout(checkpoint=...)): the same log, and no "
                          "buffer of the rollout grows with --n_timestep faster than 8 B per cell per S steps; without S the plan's segment")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="with --readings field --checkpoint: the squared error and its gradient inside the checkpointed kernels "
+                         "(dhts.macro_rollout(target=...)), no state history")
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
-    if args.checkpoint is not None and args.readings == "history":
-        ap.error("--checkpoint goes with --readings detectors: the state history is of size n_timestep anyway")
+    if args.fused_loss and (args.readings != "field" or args.checkpoint is None):
+        ap.error("--fused-loss goes with --readings field --checkpoint [S]")
+    if args.checkpoint is not None and (args.readings == "history" or (args.readings == "field" and not args.fused_loss)):
+        ap.error("--checkpoint goes with --readings detectors, or with --readings field --fused-loss: the state history is of size "
+                 "n_timestep anyway")
     checkpoint = None if args.checkpoint is None else (True if args.checkpoint == 0 else args.checkpoint)
 
     dev = th.device("cuda", 0)
@@ -71,7 +82,16 @@ def main():
         """[T][L][detectors]: the density at the detectors after every step."""
         if args.readings == "detectors":
             return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, detectors=det32, checkpoint=checkpoint)[4][:, :, 0].contiguous()
+        if args.readings == "field":
+            return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, want_hist=True)[4][:, :, 0]
         return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, want_hist=True)[4][:, :, 0][:, :, det]
+
+    def loss_of(gr, gu):
+        if args.fused_loss:                    # the kernels hold the rollout against `target` themselves: sse [L][2] in double
+            return dhts.macro_rollout(r0, u0, gr, gu, T, dt, dx, um, checkpoint=checkpoint, target=target)[4][:, 0].sum()
+        if args.readings == "field":
+            return ((densities(gr, gu).double() - obs.double()) ** 2).sum()
+        return ((densities(gr, gu) - obs) ** 2).sum()
 
     def u_eq(r):
         return um * (1.0 - th.sqrt(r + 1e-5))
@@ -91,13 +111,15 @@ def main():
         up_true = r_base + peak * th.exp(-((tt - mid) / wid) ** 2)     # [T][L]
         with th.no_grad():
             obs = densities(*schedule(up_true)).clone()                # the density readings
+            if args.fused_loss:                                        # [T][L][2][N]: the observed densities; no speed is observed
+                target = th.stack([obs, th.full_like(obs, float("nan"))], dim=2).contiguous()
         up_est = th.full((T, L), r_base, device=dev, requires_grad=True)
         opt = th.optim.Adam([up_est], lr=args.lr)
         lines = []
         t0 = time.time()
         for ep in range(args.n_episode):
             gr, gu = schedule(up_est)
-            loss = ((densities(gr, gu) - obs) ** 2).sum()
+            loss = loss_of(gr, gu)
             err = ((up_est.detach() - up_true) ** 2).sum()
             opt.zero_grad(set_to_none=False)
             loss.backward()

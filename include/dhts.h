@@ -383,6 +383,53 @@ int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, co
                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
                                 const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
                                 float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream);
+
+/*
+ * THE DENSE-FIT LOSS inside the checkpointed pair: sum((hist - observed)^2) over the density and the speed plane of the history and its
+ * gradient, without hist and without g_hist.  The two entry points are dhts_macro_rollout_fwd_ckpt / _bwd_ckpt without det / n_det /
+ * taps / g_taps, with
+ *   target   [T][L][2][N] float32: target[t][l][0][k] = the observed density of cell k AFTER step t (what hist[t][l][0][k] holds),
+ *            target[t][l][1][k] the observed speed (hist[t][l][2][k]).  A NaN entry is not observed: it adds exactly 0 to sse and no
+ *            cotangent (NaN in the whole speed plane: a density-only fit).
+ *   sse      [L][2] DOUBLE, written: per lane the sum over observed entries of the squared density residual, and of the squared speed
+ *            residual.  The residual is the float32 difference x - target (what hist - observed is), squared and summed in double: each
+ *            thread sums its own cells in step order, the wavefront combines its threads' sums pairwise (partners 32, 16 .. 1 apart) and
+ *            thread 0 adds the wavefronts' sums in their order, through LDS.  No atomics: two runs give the same bits, and so do runs
+ *            with different segments.  T = 0: 0.
+ *   g_sse    [L][2] DOUBLE or NULL (zero: the sweep is then dhts_macro_rollout_bwd_ckpt's plain one): the cotangent of sse.  The
+ *            cotangent of row t at cell k is gr = (float)(2 g_sse[l][0]) * (r - target_r), gy = 0, then the float32 glue of
+ *            dhts_macro_u_tap_bwd with g_u = (float)(2 g_sse[l][1]) * (u - target_u) on the replayed (r, y) -- residual 0 for a NaN
+ *            entry --, added where dhts_macro_rollout_bwd adds g_hist[t][l][:][k], with the same float32 add.
+ *   r_fin, y_fin, u_fin   [L][N]: the forward's r_out, y_out, u_out = row T - 1 of the history, which the replay does not recompute;
+ *            its cotangent goes into (g_r, g_y) in front of the sweep.  Needed with g_sse (T > 0).
+ * and otherwise their siblings' arguments, arithmetic, fault records and bits (r_out .. ueq_out and, for equal per-step cotangents,
+ * every gradient):
+ *   dhts_macro_rollout_fwd_ckpt_target   the T calls of dMacroForwardLayer.forward (road/lane/_macro_lane.py:83-146,
+ *       road/lane/dmacro_lane.py:96-132) and the loss of example/inverse/macro.py:34-68 on every cell and step.  ckpt may be NULL: no
+ *       checkpoint is kept (a loss evaluation that nobody differentiates).
+ *   dhts_macro_rollout_bwd_ckpt_target   the sweep of dMacroForwardLayer.backward (road/lane/dmacro_lane.py:277-309) with the loss's
+ *       cotangent entering at every step.
+ * target is read once per direction, coalesced along k; nothing of size T x N is written.
+ * DHTS_E_INVALID, nothing dereferenced and nothing launched: whatever the siblings reject (but a NULL ckpt of the forward), a NULL sse,
+ * a NULL target when T > 0, g_sse without r_fin / y_fin / u_fin when T > 0, a segment outside 0 .. the max_segment of
+ * dhts_macro_ckpt_target_plan, a lane that plan does not fit.  T = 0: state and cotangents come back as they went in, sse = 0, no row
+ * of anything is addressed.
+ * dhts_macro_ckpt_target_plan: dhts_macro_ckpt_plan's eight entries for these two kernels (a pure function, no device).  The reverse
+ * kernel's ring holds two more floats per cell-step (the finished cotangent pair: 32 (N + 1) + 8 N bytes a step), so max_segment and the
+ * default segment (the same rule with that step size) are shorter, and the first lane that does not fit has 1240 cells (1320 for the
+ * siblings); segment 0 at the two entry points is THIS plan's default.  The checkpoint buffer is dhts_macro_ckpt_bytes of the resolved
+ * segment plan[2].
+ */
+int dhts_macro_ckpt_target_plan(const dhts_macro_desc *d, int T, int segment, int32_t plan[8]);
+int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segment,
+                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                       float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const float *target, double *sse,
+                                       dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                       const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
+                                       const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out, double *g_ghost,
+                                       dhts_error *err, void *stream);
 /* tangent of y = r (u - u_eq(r)): t_y = (dy/dr) t_r + (dy/du) t_u, the partials dhts_macro_state_from_ru_bwd applies, in float32 */
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u,
                                  float *t_y, void *stream);
