@@ -74,6 +74,29 @@ inline int jvp_width(int rem, int kmax) {
     while (k > rem) k >>= 1;
     return k;
 }
+// n_dir directions as those launches: f(k0, integral_constant<kK>, n_act) per launch -- first direction, the instantiation's slots,
+// the directions it carries -- until one returns false (-> false).  kmax = 0 (no launch fits the lane): f is not called.
+template <class F>
+inline bool jvp_each_group(int n_dir, int kmax, F &&f) {
+    bool ok = true;
+    for (int k0 = 0; k0 < n_dir && kmax > 0 && ok;) {
+        const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
+        pick<4, 2, 1>(kk, [&](auto kv) { ok = f(k0, kv, n_act); });
+        k0 += n_act;
+    }
+    return ok;
+}
+// ... and what a plan says of them: the slots of the widest (the first) launch, the number of launches
+struct JvpGroups { int widest, launches; };
+inline JvpGroups jvp_groups(int kmax, int n_dir) {
+    JvpGroups g = {0, 0};
+    jvp_each_group(n_dir, kmax, [&](int, auto kv, int) {
+        if (!g.launches) g.widest = decltype(kv)::value;
+        ++g.launches;
+        return true;
+    });
+    return g;
+}
 
 }  // namespace dhts
 

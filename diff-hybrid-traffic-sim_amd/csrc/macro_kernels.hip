@@ -1565,6 +1565,16 @@ static inline int macro_fwd3_group(const dhts_macro_desc *d, bool want_hist) {
     return G;
 }
 
+// The lane mapping of the two-phase lane kernel, which the fused forward + tangent kernel and the checkpointed pair share: W wavefronts
+// per lane, each of p 64-cell passes -- of the W0 a caller asks for at most `cap`, then the fewest wavefronts that cover the lane with
+// that many passes.  W0 (with or without DHTS_OPT_MACRO_FWD_WAVES) and the cap are the caller's.
+struct MacroLaneMap { int W, p; };
+static MacroLaneMap macro_lane_map(int N, int W0, int cap) {
+    const int W = W0 > cap ? cap : (W0 < 1 ? 1 : W0);
+    const int p = (N + 64 * W - 1) / (64 * W);
+    return {(N + 64 * p - 1) / (64 * p), p};
+}
+
 // Which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for a shape, decided here once: the launches switch on these fields
 // and dhts_macro_rollout_plan copies them out.
 enum { kMacroFwdLane = 0, kMacroFwdOnePhase = 1, kMacroFwdPair = 2 };      // plan[0]
@@ -1595,11 +1605,8 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
         // resident at once (4 per CU) instead of taking two rounds.  Measured (tools/sweep_fwd_waves.py, forward ms for 1 / 2 / 4 / 8 /
         // 16 waves per lane; literal pass counts 1, 2, run-time above):
         //   1024 x 512: 7.5 / 3.95 / 3.50 / 4.07 / -      4096 x 256: 9.3 / 7.50 / 7.93 / - / -      256 x 2048: 19.6 / 10.7 / 6.0 / 4.09 / 3.54
-        int W = dhts_fwd_waves_override > 0 ? dhts_fwd_waves_override : (N + 127) / 128;
-        if (W > 16) W = 16;
-        if (W < 1) W = 1;
-        pl.p = (N + 64 * W - 1) / (64 * W);
-        pl.W = (N + 64 * pl.p - 1) / (64 * pl.p);
+        const MacroLaneMap m = macro_lane_map(N, dhts_fwd_waves_override > 0 ? dhts_fwd_waves_override : (N + 127) / 128, 16);
+        pl.W = m.W; pl.p = m.p;
         pl.dense = (pl.p == 1 || pl.p == 2) && N == 64 * pl.p * pl.W && !want_hist;
         const int G = macro_fwd3_group(d, want_hist);
         pl.fwd = G > 0 ? kMacroFwdPair : kMacroFwdLane;
@@ -1625,27 +1632,44 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
     return pl;
 }
 
-// The form of a rollout call: what it takes besides the state, the boundary cells and the tape.  The six rollout entry points fill one
-// and hand it to macro_rollout_fwd_launch resp. macro_rollout_bwd_launch; kSched and kTaps of the kernels are picked from it like every
-// other template argument, so a further form is one more field here and one more pick there.
+// The form of a rollout call: what it takes besides the state, the boundary cells and the tape or the checkpoints.  Every rollout entry
+// point -- taped, tangent, fused and checkpointed -- fills one and hands it to its launcher; kSched, kTaps and the target kernels are
+// picked from it like every other template argument, so a further form is one more field here and one more pick there.
 struct MacroForm {
     bool sched;           // the boundary cells are a schedule [T][L][2][4]; g_ghost is per step [T][L][2][2]
     const int32_t *det;   // detector cells [n_det], NULL: none
     int n_det;
     float *hist, *taps;   // forward: the state history [T][L][3][N] (not with detectors) resp. the readings [T][L][3][n_det]
     const float *g_cot;   // reverse: the per-step cotangents, g_hist [T][L][2][N] or with detectors g_taps [T][L][2][n_det]; NULL: none
+    // the dense fit of the checkpointed pair: target [T][L][2][N] with the forward's sums sse [L][2] resp. the reverse sweep's g_sse
+    // [L][2] and the forward's final state; `target` NULL: not a target form
+    const float *target;
+    double *sse;
+    const double *g_sse;
+    const float *fin_r, *fin_y, *fin_u;
 };
+static MacroForm macro_form(int ghost_is_sched, const int32_t *det = nullptr, int n_det = 0) {
+    MacroForm f = {};
+    f.sched = ghost_is_sched != 0; f.det = det; f.n_det = det ? n_det : 0;
+    return f;
+}
+// detectors and the array that goes with them (readings, their tangents or cotangents) come together or not at all
+static inline bool macro_det_pair_ok(const dhts_macro_desc *d, const int32_t *det, int n_det, const void *with) {
+    return (det != nullptr) == (with != nullptr) && (!det || (n_det >= 1 && n_det <= d->n_cells));
+}
 
-// T == 0 of the _sched and _taps entry points: no step and no row of a schedule, of the tape or of the readings to address, so the state
-// comes back as it went in (what the constant-boundary rollout's kernel does with T = 0)
+// T == 0 of every entry point but the constant-boundary rollout's: no step and no row of a schedule, of the tape or of the readings to
+// address, so what the call carries through the steps comes back as it went in (what that rollout's kernel does with T = 0)
+static bool macro_copy_back(void *dst, const void *src, size_t bytes, void *stream) {
+    return dst == src || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess;
+}
 static int macro_state_copy(const dhts_macro_desc *d, const float *r, const float *y, const float *u, const float *ueq,
                             float *r_out, float *y_out, float *u_out, float *ueq_out, void *stream) {
     const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
     const float *src[4] = {r, y, u, ueq};
     float *dst[4] = {r_out, y_out, u_out, ueq_out};
     for (int k = 0; k < 4; ++k)
-        if (dst[k] != src[k] && hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-            return DHTS_E_LAUNCH;
+        if (!macro_copy_back(dst[k], src[k], bytes, stream)) return DHTS_E_LAUNCH;
     return DHTS_OK;
 }
 
@@ -1797,46 +1821,57 @@ static JvpPlan macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir) {
         pl.block = padded64(N) > 512 ? 512 : padded64(N);
         while (pl.kmax > 0 && jvp_general_lds_bytes(N, pl.kmax) > 160 * 1024) pl.kmax >>= 1;
     }
-    for (int rem = n_dir; rem > 0 && pl.kmax > 0;) {
-        int k = jvp_width(rem, pl.kmax);
-        if (!pl.launches) pl.widest = k;
-        rem -= k < rem ? k : rem;
-        ++pl.launches;
-    }
-    if (T == 0) pl.launches = 0;          // nothing to sweep: the entry point copies the tangents
+    const JvpGroups g = jvp_groups(pl.kmax, n_dir);
+    pl.widest = g.widest;
+    pl.launches = T == 0 ? 0 : g.launches;      // (T = 0: nothing to sweep, the entry point copies the tangents)
     return pl;
 }
 
-static int macro_rollout_jvp_launch(const dhts_macro_desc *d, int T, const float *tape, int n_dir, const float *t_r, const float *t_y,
-                                    const float *t_ghost, int ghost_is_sched, float *t_r_out, float *t_y_out,
-                                    const int32_t *det, int n_det, float *t_taps, dhts_error *err, void *stream) {
+// The per-direction arrays of the two tangent entry points, [K] outermost: the tangents of (r, y) in and out, t_ghost [K][L][2][2] or
+// beside a schedule [K][T][L][2][2] (NULL: zero), the tangent readings [K][T][L][2][n_det] (with detectors).  ..._at: those of one
+// launch, which starts at direction k0.
+struct MacroTangents {
+    const float *r, *y, *ghost;
+    float *r_out, *y_out, *taps;
+};
+static MacroTangents macro_tangents_at(const MacroTangents &t, int k0, const dhts_macro_desc *d, int T, const MacroForm &f) {
+    const size_t dir_state = (size_t)d->n_lanes * d->n_cells, dir_ghost = (f.sched ? (size_t)T : 1) * d->n_lanes * 4,
+                 dir_taps = (size_t)T * d->n_lanes * 2 * f.n_det;
+    return {t.r + k0 * dir_state, t.y + k0 * dir_state, t.ghost ? t.ghost + k0 * dir_ghost : nullptr,
+            t.r_out + k0 * dir_state, t.y_out + k0 * dir_state, f.det ? t.taps + k0 * dir_taps : nullptr};
+}
+// how the kernels read t_ghost: 0 none, 1 the same in front of every step, 2 a schedule
+static int macro_ghost_mode(const MacroTangents &t, const MacroForm &f) { return !t.ghost ? 0 : (f.sched ? 2 : 1); }
+// T == 0 of both: the tangents come back as they went in, no row is read or written
+static bool macro_tangents_copy(const dhts_macro_desc *d, int n_dir, const MacroTangents &t, void *stream) {
+    const size_t bytes = sizeof(float) * (size_t)n_dir * d->n_lanes * d->n_cells;
+    return macro_copy_back(t.r_out, t.r, bytes, stream) && macro_copy_back(t.y_out, t.y, bytes, stream);
+}
+
+static int macro_rollout_jvp_launch(const dhts_macro_desc *d, int T, const float *tape, int n_dir, const MacroTangents &t, const MacroForm &f,
+                                    dhts_error *err, void *stream) {
     const JvpPlan pl = macro_jvp_plan(d, T, n_dir);
     if (pl.kmax < 1) return DHTS_E_INVALID;
     const int L = d->n_lanes, N = d->n_cells, B = pl.block;
     const float4 *tp = reinterpret_cast<const float4 *>(tape);
     const double cc = d->dt / d->dx;
-    const int ghost_mode = !t_ghost ? 0 : (ghost_is_sched ? 2 : 1);
-    const size_t dir_state = (size_t)L * N, dir_ghost = (ghost_mode == 2 ? (size_t)T : 1) * L * 4, dir_taps = (size_t)T * L * 2 * n_det;
-    bool lds_ok = true;
-    for (int k0 = 0; k0 < n_dir && lds_ok;) {
-        const int kk = jvp_width(n_dir - k0, pl.kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
-        const float *a_r = t_r + k0 * dir_state, *a_y = t_y + k0 * dir_state, *a_g = t_ghost ? t_ghost + k0 * dir_ghost : nullptr;
-        float *o_r = t_r_out + k0 * dir_state, *o_y = t_y_out + k0 * dir_state, *o_t = det ? t_taps + k0 * dir_taps : nullptr;
-        pick<4, 2, 1>(kk, [&](auto kv) {
-            constexpr int kK = decltype(kv)::value;
-            if (pl.fast) {
-                pick<64, 128, 256, 512, 1024>(B, [&](auto bv) {
-                    constexpr int kB = decltype(bv)::value;
-                    lds_ok = launch_lds(macro_rollout_jvp_fast_kernel<kB, kK>, L, B, jvp_fast_lds_bytes(kB, kK), kLdsDefault, stream, L, N, T, cc,
-                                        tp, a_r, a_y, a_g, ghost_mode, n_act, o_r, o_y, det, n_det, o_t, err);
-                });
-            } else {
-                lds_ok = launch_lds(macro_rollout_jvp_kernel<kK>, L, B, jvp_general_lds_bytes(N, kK), kLdsDefault, stream, L, N, T, cc, tp, a_r,
-                                    a_y, a_g, ghost_mode, n_act, o_r, o_y, det, n_det, o_t, err);
-            }
-        });
-        k0 += n_act;
-    }
+    const int ghost_mode = macro_ghost_mode(t, f);
+    const bool lds_ok = jvp_each_group(n_dir, pl.kmax, [&](int k0, auto kv, int n_act) {
+        constexpr int kK = decltype(kv)::value;
+        const MacroTangents a = macro_tangents_at(t, k0, d, T, f);
+        bool ok = true;
+        if (pl.fast) {
+            pick<64, 128, 256, 512, 1024>(B, [&](auto bv) {
+                constexpr int kB = decltype(bv)::value;
+                ok = launch_lds(macro_rollout_jvp_fast_kernel<kB, kK>, L, B, jvp_fast_lds_bytes(kB, kK), kLdsDefault, stream, L, N, T, cc, tp, a.r,
+                                a.y, a.ghost, ghost_mode, n_act, a.r_out, a.y_out, f.det, f.n_det, a.taps, err);
+            });
+        } else {
+            ok = launch_lds(macro_rollout_jvp_kernel<kK>, L, B, jvp_general_lds_bytes(N, kK), kLdsDefault, stream, L, N, T, cc, tp, a.r, a.y,
+                            a.ghost, ghost_mode, n_act, a.r_out, a.y_out, f.det, f.n_det, a.taps, err);
+        }
+        return ok;
+    });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
@@ -1853,56 +1888,45 @@ struct FwdJvpPlan {
 static FwdJvpPlan macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir) {
     FwdJvpPlan pl = {};
     const int N = d->n_cells;
-    int W = dhts_fwd_waves_override > 0 ? dhts_fwd_waves_override : (N + 127) / 128;
-    if (W > 12) W = 12;                   // (the kernel's launch bound; no lane that fits has more without DHTS_OPT_MACRO_FWD_WAVES)
-    if (W < 1) W = 1;
-    pl.p = (N + 64 * W - 1) / (64 * W);
-    pl.W = (N + 64 * pl.p - 1) / (64 * pl.p);
+    // (12: the kernel's launch bound; no lane that fits has more without DHTS_OPT_MACRO_FWD_WAVES)
+    const MacroLaneMap m = macro_lane_map(N, dhts_fwd_waves_override > 0 ? dhts_fwd_waves_override : (N + 127) / 128, 12);
+    pl.W = m.W; pl.p = m.p;
     pl.kmax = 4;
     while (pl.kmax > 0 && fwd_jvp_lds_bytes(N, pl.kmax) > 160 * 1024) pl.kmax >>= 1;
-    for (int rem = n_dir; rem > 0 && pl.kmax > 0;) {
-        const int k = jvp_width(rem, pl.kmax);
-        if (!pl.launches) pl.widest = k;
-        rem -= k < rem ? k : rem;
-        ++pl.launches;
-    }
-    if (T == 0) pl.launches = 0;          // no step: the entry point copies the state and the tangents
+    const JvpGroups g = jvp_groups(pl.kmax, n_dir);
+    pl.widest = g.widest;
+    pl.launches = T == 0 ? 0 : g.launches;      // (T = 0: no step, the entry point copies the state and the tangents)
     pl.lds = pl.widest > 0 ? fwd_jvp_lds_bytes(N, pl.widest) : 0;
     return pl;
 }
 
+// f.taps: the primal readings; t.taps: their tangents
 static int macro_fwd_jvp_launch(const dhts_macro_desc *d, int T, int n_dir, const float *r, const float *y, const float *u, const float *ueq,
-                                const float *ghost, int ghost_is_sched, const float *t_r, const float *t_y, const float *t_ghost,
-                                float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
-                                const int32_t *det, int n_det, float *taps, float *t_taps, dhts_error *err, dhts_error *err_jvp, void *stream) {
+                                const float *ghost, const MacroTangents &t, float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                const MacroForm &f, dhts_error *err, dhts_error *err_jvp, void *stream) {
     const FwdJvpPlan pl = macro_fwd_jvp_plan(d, T, n_dir);
     if (pl.kmax < 1) return DHTS_E_INVALID;
     const int L = d->n_lanes, N = d->n_cells;
-    const int ghost_mode = !t_ghost ? 0 : (ghost_is_sched ? 2 : 1);
-    const size_t dir_state = (size_t)L * N, dir_ghost = (ghost_mode == 2 ? (size_t)T : 1) * L * 4, dir_taps = (size_t)T * L * 2 * n_det;
-    bool lds_ok = true;
-    for (int k0 = 0; k0 < n_dir && lds_ok;) {
-        const int kk = jvp_width(n_dir - k0, pl.kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
-        const float *a_r = t_r + k0 * dir_state, *a_y = t_y + k0 * dir_state, *a_g = t_ghost ? t_ghost + k0 * dir_ghost : nullptr;
-        float *o_r = t_r_out + k0 * dir_state, *o_y = t_y_out + k0 * dir_state, *o_t = det ? t_taps + k0 * dir_taps : nullptr;
+    const int ghost_mode = macro_ghost_mode(t, f);
+    const bool lds_ok = jvp_each_group(n_dir, pl.kmax, [&](int k0, auto kv, int n_act) {
+        const MacroTangents a = macro_tangents_at(t, k0, d, T, f);
         // every launch recomputes the primal and writes the same bits; the first one alone is handed the readings and the forward's record
-        float *o_taps = k0 == 0 ? taps : nullptr;
+        float *o_taps = k0 == 0 ? f.taps : nullptr;
         dhts_error *o_err = k0 == 0 ? err : nullptr;
-        pick<4, 2, 1>(kk, [&](auto kv) {
-            pick<0, 1, 2>(pl.p <= 2 ? pl.p : 0, [&](auto pv) {
-                pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
-                    pick<0, 1>(det != nullptr, [&](auto tap) {
-                        constexpr int kK = decltype(kv)::value, kP = decltype(pv)::value;
-                        constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
-                        lds_ok = launch_lds(macro_rollout_fwd_jvp_kernel<kK, kP, kS, kT>, L, 64 * pl.W, fwd_jvp_lds_bytes(N, kK), kLdsDefault,
-                                            stream, L, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, a_r, a_y, a_g, ghost_mode, n_act,
-                                            r_out, y_out, u_out, ueq_out, o_r, o_y, det, n_det, o_taps, o_t, o_err, err_jvp);
-                    });
+        bool ok = true;
+        pick<0, 1, 2>(pl.p <= 2 ? pl.p : 0, [&](auto pv) {
+            pick<0, 1>(f.sched, [&](auto sc) {
+                pick<0, 1>(f.det != nullptr, [&](auto tap) {
+                    constexpr int kK = decltype(kv)::value, kP = decltype(pv)::value;
+                    constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
+                    ok = launch_lds(macro_rollout_fwd_jvp_kernel<kK, kP, kS, kT>, L, 64 * pl.W, fwd_jvp_lds_bytes(N, kK), kLdsDefault, stream, L,
+                                    N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, a.r, a.y, a.ghost, ghost_mode, n_act, r_out, y_out,
+                                    u_out, ueq_out, a.r_out, a.y_out, f.det, f.n_det, o_taps, a.taps, o_err, err_jvp);
                 });
             });
         });
-        k0 += n_act;
-    }
+        return ok;
+    });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 
@@ -1929,10 +1953,8 @@ struct MacroCkptPlan {
 static MacroCkptPlan macro_ckpt_plan(const dhts_macro_desc *d, bool target = false) {
     MacroCkptPlan pl = {};
     const int N = d->n_cells;
-    int W = (N + 127) / 128;
-    if (W > 12) W = 12;
-    pl.p = (N + 64 * W - 1) / (64 * W);
-    pl.W = (N + 64 * pl.p - 1) / (64 * pl.p);
+    const MacroLaneMap m = macro_lane_map(N, (N + 127) / 128, 12);
+    pl.W = m.W; pl.p = m.p;
     pl.lds_fwd = macro_ckpt_fwd_lds_bytes(N);
     const size_t fixed = macro_ckpt_bwd_fixed_bytes(N), step = macro_ckpt_bwd_step_bytes(N, target);
     pl.max_segment = fixed + step <= kMacroCkptLdsBudget && pl.p <= 2 ? (int)((kMacroCkptLdsBudget - fixed) / step) : 0;
@@ -1952,19 +1974,27 @@ static int macro_ckpt_segment(const MacroCkptPlan &pl, int segment) {
     return segment == 0 ? pl.segment : segment;
 }
 static int macro_ckpt_count(int T, int S) { return T > 0 ? (T + S - 1) / S : 0; }
+// what dhts_macro_ckpt_plan and dhts_macro_ckpt_target_plan answer, each after its own argument check
+static int macro_ckpt_plan_fill(const dhts_macro_desc *d, int T, int segment, bool target, int32_t plan[8]) {
+    const MacroCkptPlan pl = macro_ckpt_plan(d, target);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = pl.W; plan[1] = pl.p; plan[3] = pl.max_segment; plan[5] = (int32_t)pl.lds_fwd;
+    if (pl.max_segment < 1) return segment == 0 ? DHTS_OK : DHTS_E_INVALID;       // the lane does not fit: max_segment = 0 says so
+    const int S = macro_ckpt_segment(pl, segment);
+    if (S < 0) return DHTS_E_INVALID;
+    const size_t bwd_lds = macro_ckpt_bwd_lds_bytes(d->n_cells, S, target);
+    plan[2] = S;
+    plan[4] = macro_ckpt_count(T, S);
+    plan[6] = (int32_t)bwd_lds;
+    plan[7] = (int32_t)(kMacroCkptLdsBudget / bwd_lds);
+    return DHTS_OK;
+}
 
-// What a call of the target forms fits (host only): target [T][L][2][N] with the forward's sums sse [L][2] resp. the reverse sweep's
-// g_sse [L][2] and the forward's final state; `target` NULL: not a target form (the detector arguments apply then)
-struct MacroFit {
-    const float *target;
-    double *sse;
-    const double *g_sse;
-    const float *fin_r, *fin_y, *fin_u;
-};
+// f.target: the target kernels (f.sse resp. f.g_sse and the final state); else f.det with f.taps resp. the cotangents f.g_cot, or neither
 static int macro_ckpt_fwd_launch(const dhts_macro_desc *d, int T, int S, const MacroCkptPlan &pl,
-                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
-                                 float *r_out, float *y_out, float *u_out, float *ueq_out, const int32_t *det, int n_det, float *taps,
-                                 void *ckpt, dhts_error *err, void *stream, const MacroFit &fit = MacroFit{}) {
+                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
+                                 float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const MacroForm &f, dhts_error *err,
+                                 void *stream) {
     const int L = d->n_lanes, N = d->n_cells;
     bool lds_ok = true;
     auto go = [&](auto kernel, auto... tail) {
@@ -1972,34 +2002,34 @@ static int macro_ckpt_fwd_launch(const dhts_macro_desc *d, int T, int S, const M
                             y_out, u_out, ueq_out, reinterpret_cast<float2 *>(ckpt), err, tail...);
     };
     pick<1, 2>(pl.p, [&](auto pv) {
-        pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
-            pick<0, 1, 2>(fit.target ? 2 : det != nullptr, [&](auto tap) {
+        pick<0, 1>(f.sched, [&](auto sc) {
+            pick<0, 1, 2>(f.target ? 2 : f.det != nullptr, [&](auto tap) {
                 constexpr int kP = decltype(pv)::value, kForm = decltype(tap)::value;
                 constexpr bool kS = decltype(sc)::value != 0;
-                if constexpr (kForm == 2) go(macro_rollout_ckpt_fwd_target_kernel<kP, kS>, fit.target, fit.sse);
-                else go(macro_rollout_ckpt_fwd_kernel<kP, kS, kForm != 0>, det, n_det, taps);
+                if constexpr (kForm == 2) go(macro_rollout_ckpt_fwd_target_kernel<kP, kS>, f.target, f.sse);
+                else go(macro_rollout_ckpt_fwd_kernel<kP, kS, kForm != 0>, f.det, f.n_det, f.taps);
             });
         });
     });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
 }
 static int macro_ckpt_bwd_launch(const dhts_macro_desc *d, int T, int S, const MacroCkptPlan &pl, const void *ckpt,
-                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
-                                 const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
-                                 float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream, const MacroFit &fit = MacroFit{}) {
+                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
+                                 const float *g_r, const float *g_y, float *g_r_out, float *g_y_out, double *g_ghost, const MacroForm &f,
+                                 dhts_error *err, void *stream) {
     const int L = d->n_lanes, N = d->n_cells;
     bool lds_ok = true;
     auto go = [&](auto kernel, size_t lds, auto... tail) {
         lds_ok = launch_lds(kernel, L, 64 * pl.W, lds, kLdsDefault, stream, L, N, T, S, pl.p, d->dt, d->dx, d->u_max,
-                            reinterpret_cast<const float2 *>(ckpt), r, y, u, ueq, ghost, g_r, g_y, g_taps, g_r_out, g_y_out, g_ghost, err, tail...);
+                            reinterpret_cast<const float2 *>(ckpt), r, y, u, ueq, ghost, g_r, g_y, f.g_cot, g_r_out, g_y_out, g_ghost, err, tail...);
     };
-    pick<0, 1>(ghost_is_sched != 0, [&](auto sc) {
-        pick<0, 1, 2>(fit.target ? 2 : det != nullptr, [&](auto tap) {
+    pick<0, 1>(f.sched, [&](auto sc) {
+        pick<0, 1, 2>(f.target ? 2 : f.det != nullptr, [&](auto tap) {
             constexpr bool kS = decltype(sc)::value != 0;
             constexpr int kForm = decltype(tap)::value;
             if constexpr (kForm == 2)
-                go(macro_rollout_ckpt_bwd_target_kernel<kS>, macro_ckpt_bwd_lds_bytes(N, S, true), fit.target, fit.g_sse, fit.fin_r, fit.fin_y, fit.fin_u);
-            else go(macro_rollout_ckpt_bwd_kernel<kS, kForm != 0>, macro_ckpt_bwd_lds_bytes(N, S), det, n_det);
+                go(macro_rollout_ckpt_bwd_target_kernel<kS>, macro_ckpt_bwd_lds_bytes(N, S, true), f.target, f.g_sse, f.fin_r, f.fin_y, f.fin_u);
+            else go(macro_rollout_ckpt_bwd_kernel<kS, kForm != 0>, macro_ckpt_bwd_lds_bytes(N, S), f.det, f.n_det);
         });
     });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
@@ -2085,16 +2115,14 @@ int dhts_macro_rollout_fwd_sched(const dhts_macro_desc *d, int T,
                                  float *tape, float *hist, dhts_error *err, void *stream) {
     if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out)) return DHTS_E_INVALID;
     if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
-    MacroForm f = {};
-    f.sched = true;
+    MacroForm f = macro_form(true);
     f.hist = hist;
     return macro_rollout_fwd_launch(d, T, r, y, u, ueq, ghost_sched, r_out, y_out, u_out, ueq_out, tape, f, err, stream);
 }
 int dhts_macro_rollout_bwd_sched(const dhts_macro_desc *d, int T, const float *tape,
                                  const float *g_r, const float *g_y, const float *g_hist,
                                  float *g_r_out, float *g_y_out, double *g_ghost_sched, dhts_error *err, void *stream) {
-    MacroForm f = {};
-    f.sched = true;
+    MacroForm f = macro_form(true);
     f.g_cot = g_hist;
     return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_r_out, g_y_out, g_ghost_sched, f, err, stream);
 }
@@ -2110,18 +2138,16 @@ int dhts_macro_rollout_fwd_taps(const dhts_macro_desc *d, int T,
     if (!macro_taps_ok(d, det, n_det) || !taps || !macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out))
         return DHTS_E_INVALID;
     if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
-    MacroForm f = {};
-    f.sched = ghost_is_sched != 0;
-    f.det = det; f.n_det = n_det; f.taps = taps;
+    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    f.taps = taps;
     return macro_rollout_fwd_launch(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, tape, f, err, stream);
 }
 int dhts_macro_rollout_bwd_taps(const dhts_macro_desc *d, int T, const float *tape, const float *g_r, const float *g_y,
                                 const int32_t *det, int n_det, const float *g_taps,
                                 float *g_r_out, float *g_y_out, double *g_ghost, int ghost_is_sched, dhts_error *err, void *stream) {
     if (!macro_taps_ok(d, det, n_det) || !g_taps) return DHTS_E_INVALID;
-    MacroForm f = {};
-    f.sched = ghost_is_sched != 0;
-    f.det = det; f.n_det = n_det; f.g_cot = g_taps;
+    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    f.g_cot = g_taps;
     return macro_rollout_bwd_launch(d, T, tape, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
 }
 // which kernel instantiations the rollout entry points launch for a shape: the plan the launches read, as include/dhts.h lays it out
@@ -2163,16 +2189,11 @@ int dhts_macro_rollout_jvp(const dhts_macro_desc *d, int T, const float *tape, i
                            const float *t_ghost, int ghost_is_sched, float *t_r_out, float *t_y_out,
                            const int32_t *det, int n_det, float *t_taps, dhts_error *err, void *stream) {
     if (!macro_desc_ok(d) || T < 0 || n_dir < 1 || (T > 0 && !tape) || !t_r || !t_y || !t_r_out || !t_y_out) return DHTS_E_INVALID;
-    if ((det != nullptr) != (t_taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells))) return DHTS_E_INVALID;
+    if (!macro_det_pair_ok(d, det, n_det, t_taps)) return DHTS_E_INVALID;
     if (ghost_is_sched && !t_ghost) return DHTS_E_INVALID;       // a schedule that is not there (zero boundary tangents: NULL with 0)
-    if (T == 0) {                                                // no step: the tangents come back as they went in, no row is read or written
-        const size_t bytes = sizeof(float) * (size_t)n_dir * d->n_lanes * d->n_cells;
-        if (t_r_out != t_r && hipMemcpyAsync(t_r_out, t_r, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
-        if (t_y_out != t_y && hipMemcpyAsync(t_y_out, t_y, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
-        return DHTS_OK;
-    }
-    return macro_rollout_jvp_launch(d, T, tape, n_dir, t_r, t_y, t_ghost, ghost_is_sched, t_r_out, t_y_out, det, det ? n_det : 0, t_taps, err,
-                                    stream);
+    const MacroTangents t = {t_r, t_y, t_ghost, t_r_out, t_y_out, t_taps};
+    if (T == 0) return macro_tangents_copy(d, n_dir, t, stream) ? DHTS_OK : DHTS_E_LAUNCH;
+    return macro_rollout_jvp_launch(d, T, tape, n_dir, t, macro_form(ghost_is_sched, det, n_det), err, stream);
 }
 int dhts_macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || n_dir < 1 || !plan || n_det < 0 || n_det > d->n_cells) return DHTS_E_INVALID;
@@ -2191,17 +2212,16 @@ int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
                                dhts_error *err, dhts_error *err_jvp, void *stream) {
     if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || n_dir < 1 || !t_r || !t_y || !t_r_out || !t_y_out)
         return DHTS_E_INVALID;
-    if ((det != nullptr) != (taps != nullptr) || (det != nullptr) != (t_taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells)))
-        return DHTS_E_INVALID;
+    if (!macro_det_pair_ok(d, det, n_det, taps) || !macro_det_pair_ok(d, det, n_det, t_taps)) return DHTS_E_INVALID;
     if (macro_fwd_jvp_plan(d, T, n_dir).kmax < 1) return DHTS_E_INVALID;       // the lane does not fit: the taped pair covers it
+    const MacroTangents t = {t_r, t_y, t_ghost, t_r_out, t_y_out, t_taps};
     if (T == 0) {                                                // no step: state and tangents come back as they went in, no row is addressed
-        const size_t bytes = sizeof(float) * (size_t)n_dir * d->n_lanes * d->n_cells;
-        if (t_r_out != t_r && hipMemcpyAsync(t_r_out, t_r, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
-        if (t_y_out != t_y && hipMemcpyAsync(t_y_out, t_y, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        if (!macro_tangents_copy(d, n_dir, t, stream)) return DHTS_E_LAUNCH;
         return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
     }
-    return macro_fwd_jvp_launch(d, T, n_dir, r, y, u, ueq, ghost, ghost_is_sched, t_r, t_y, t_ghost, r_out, y_out, u_out, ueq_out, t_r_out,
-                                t_y_out, det, det ? n_det : 0, taps, t_taps, err, err_jvp, stream);
+    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    f.taps = taps;
+    return macro_fwd_jvp_launch(d, T, n_dir, r, y, u, ueq, ghost, t, r_out, y_out, u_out, ueq_out, f, err, err_jvp, stream);
 }
 int dhts_macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || n_dir < 1 || !plan || n_det < 0 || n_det > d->n_cells) return DHTS_E_INVALID;
@@ -2213,18 +2233,7 @@ int dhts_macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_de
 // ---- reverse mode from checkpoints, the segment's interface products in LDS ------------------------------------------------------
 int dhts_macro_ckpt_plan(const dhts_macro_desc *d, int T, int n_det, int segment, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || !plan || n_det < 0 || n_det > d->n_cells || segment < 0) return DHTS_E_INVALID;
-    const MacroCkptPlan pl = macro_ckpt_plan(d);
-    for (int k = 0; k < 8; ++k) plan[k] = 0;
-    plan[0] = pl.W; plan[1] = pl.p; plan[3] = pl.max_segment; plan[5] = (int32_t)pl.lds_fwd;
-    if (pl.max_segment < 1) return segment == 0 ? DHTS_OK : DHTS_E_INVALID;       // the lane does not fit: max_segment = 0 says so
-    const int S = macro_ckpt_segment(pl, segment);
-    if (S < 0) return DHTS_E_INVALID;
-    const size_t bwd_lds = macro_ckpt_bwd_lds_bytes(d->n_cells, S);
-    plan[2] = S;
-    plan[4] = macro_ckpt_count(T, S);
-    plan[6] = (int32_t)bwd_lds;
-    plan[7] = (int32_t)(kMacroCkptLdsBudget / bwd_lds);
-    return DHTS_OK;
+    return macro_ckpt_plan_fill(d, T, segment, false, plan);
 }
 size_t dhts_macro_ckpt_bytes(const dhts_macro_desc *d, int T, int segment) {
     if (!macro_desc_ok(d) || T < 0) return 0;
@@ -2237,52 +2246,47 @@ int dhts_macro_rollout_fwd_ckpt(const dhts_macro_desc *d, int T, int segment,
                                 float *r_out, float *y_out, float *u_out, float *ueq_out,
                                 const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream) {
     if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || (T > 0 && !ckpt)) return DHTS_E_INVALID;
-    if ((det != nullptr) != (taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells))) return DHTS_E_INVALID;
+    if (!macro_det_pair_ok(d, det, n_det, taps)) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d);
     const int S = macro_ckpt_segment(pl, segment);
     if (S < 0) return DHTS_E_INVALID;
     if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
-    return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, ghost_is_sched, r_out, y_out, u_out, ueq_out, det, det ? n_det : 0, taps, ckpt,
-                                 err, stream);
+    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    f.taps = taps;
+    return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, ckpt, f, err, stream);
+}
+// what both checkpointed reverse entry points ask of the replay's inputs, the seeds and the outputs
+static inline bool macro_replay_args_ok(const dhts_macro_desc *d, int T, const void *ckpt, const float *r, const float *y, const float *u,
+                                        const float *ueq, const float *ghost, int ghost_is_sched, const float *g_r, const float *g_y,
+                                        const float *g_r_out, const float *g_y_out, const double *g_ghost) {
+    return macro_desc_ok(d) && T >= 0 && (T == 0 || ckpt) && r && y && u && ueq && ghost && g_r && g_y && g_r_out && g_y_out &&
+           (!ghost_is_sched || g_ghost);
 }
 int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
                                 const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
                                 float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
-    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !r || !y || !u || !ueq || !ghost || !g_r || !g_y || !g_r_out || !g_y_out ||
-        (ghost_is_sched && !g_ghost))
-        return DHTS_E_INVALID;
-    if ((det != nullptr) != (g_taps != nullptr) || (det && (n_det < 1 || n_det > d->n_cells))) return DHTS_E_INVALID;
+    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
+    if (!macro_det_pair_ok(d, det, n_det, g_taps)) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d);
     const int S = macro_ckpt_segment(pl, segment);
     if (S < 0) return DHTS_E_INVALID;
     if (T == 0) {        // no step: the cotangents come back as they went in, the boundary sums are zero, no row is addressed
         const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
-        if (g_r_out != g_r && hipMemcpyAsync(g_r_out, g_r, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
-        if (g_y_out != g_y && hipMemcpyAsync(g_y_out, g_y, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
+        if (!macro_copy_back(g_r_out, g_r, bytes, stream) || !macro_copy_back(g_y_out, g_y, bytes, stream)) return DHTS_E_LAUNCH;
         if (!ghost_is_sched && g_ghost &&
             hipMemsetAsync(g_ghost, 0, sizeof(double) * 4 * (size_t)d->n_lanes, (hipStream_t)stream) != hipSuccess)
             return DHTS_E_LAUNCH;
         return DHTS_OK;
     }
-    return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, det, det ? n_det : 0, g_taps, g_r_out, g_y_out,
-                                 g_ghost, err, stream);
+    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    f.g_cot = g_taps;
+    return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
 }
 // ---- the dense-fit loss inside the checkpointed pair ----------------------------------------------------------------------------
 int dhts_macro_ckpt_target_plan(const dhts_macro_desc *d, int T, int segment, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || !plan || segment < 0) return DHTS_E_INVALID;
-    const MacroCkptPlan pl = macro_ckpt_plan(d, true);
-    for (int k = 0; k < 8; ++k) plan[k] = 0;
-    plan[0] = pl.W; plan[1] = pl.p; plan[3] = pl.max_segment; plan[5] = (int32_t)pl.lds_fwd;
-    if (pl.max_segment < 1) return segment == 0 ? DHTS_OK : DHTS_E_INVALID;       // the lane does not fit: max_segment = 0 says so
-    const int S = macro_ckpt_segment(pl, segment);
-    if (S < 0) return DHTS_E_INVALID;
-    const size_t bwd_lds = macro_ckpt_bwd_lds_bytes(d->n_cells, S, true);
-    plan[2] = S;
-    plan[4] = macro_ckpt_count(T, S);
-    plan[6] = (int32_t)bwd_lds;
-    plan[7] = (int32_t)(kMacroCkptLdsBudget / bwd_lds);
-    return DHTS_OK;
+    return macro_ckpt_plan_fill(d, T, segment, true, plan);
 }
 int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segment,
                                        const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
@@ -2296,17 +2300,16 @@ int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segm
         if (hipMemsetAsync(sse, 0, sizeof(double) * 2 * (size_t)d->n_lanes, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
         return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
     }
-    return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, ghost_is_sched, r_out, y_out, u_out, ueq_out, nullptr, 0, nullptr, ckpt, err,
-                                 stream, MacroFit{target, sse, nullptr, nullptr, nullptr, nullptr});
+    MacroForm f = macro_form(ghost_is_sched);
+    f.target = target; f.sse = sse;
+    return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, ckpt, f, err, stream);
 }
 int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
                                        const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
                                        const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
                                        const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out, double *g_ghost,
                                        dhts_error *err, void *stream) {
-    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !ckpt) || !r || !y || !u || !ueq || !ghost || !g_r || !g_y || !g_r_out || !g_y_out ||
-        (ghost_is_sched && !g_ghost))
-        return DHTS_E_INVALID;
+    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
     // the fit's cotangent needs the observations and the forward's final state (row T - 1 of the history)
     if (T > 0 && (!target || (g_sse && (!r_fin || !y_fin || !u_fin)))) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d, true);
@@ -2315,8 +2318,9 @@ int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segm
     if (T == 0 || !g_sse)            // no step, or no cotangent of the sums: the plain sweep (the segment is the TARGET plan's, which fits it)
         return dhts_macro_rollout_bwd_ckpt(d, T, S, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, nullptr, 0, nullptr, g_r_out, g_y_out,
                                            g_ghost, err, stream);
-    return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, nullptr, 0, nullptr, g_r_out, g_y_out, g_ghost,
-                                 err, stream, MacroFit{target, nullptr, g_sse, r_fin, y_fin, u_fin});
+    MacroForm f = macro_form(ghost_is_sched);
+    f.target = target; f.g_sse = g_sse; f.fin_r = r_fin; f.fin_y = y_fin; f.fin_u = u_fin;
+    return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
 }
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,
                                  void *stream) {

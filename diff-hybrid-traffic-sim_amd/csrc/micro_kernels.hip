@@ -695,36 +695,13 @@ static int micro_bwd_params_launch(const dhts_micro_desc *d, int T, const float 
            d->n_lanes, d->capacity, T, d->dt, tape, count, g_p, g_v, g_hist, g_p_out, g_v_out, g_head, 1, err, ptape, params, g_params);
     return launch_status();
 }
-// n_dir directions as launches of 4, then 2, then 1 (jvp_width: a remainder of 3 rides in ONE launch of 4 with a slot masked):
-// f(k0, integral_constant<kK>, n_act) per launch -- first direction, the instantiation's slots, the directions it carries -- until
-// one returns false (-> false)
-template <class F>
-static bool micro_jvp_each_group(int n_dir, int kmax, F &&f) {
-    bool ok = true;
-    for (int k0 = 0; k0 < n_dir && ok;) {
-        const int kk = jvp_width(n_dir - k0, kmax), n_act = kk < n_dir - k0 ? kk : n_dir - k0;
-        pick<4, 2, 1>(kk, [&](auto kv) { ok = f(k0, kv, n_act); });
-        k0 += n_act;
-    }
-    return ok;
-}
-struct MicroJvpGroups { int widest, launches; };
-static MicroJvpGroups micro_jvp_groups(int kmax, int n_dir) {
-    MicroJvpGroups g = {0, 0};
-    micro_jvp_each_group(n_dir, kmax, [&](int, auto kv, int) {
-        if (!g.launches) g.widest = decltype(kv)::value;
-        ++g.launches;
-        return true;
-    });
-    return g;
-}
 static int micro_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const float *tape, const char *ptape, const int32_t *count,
                             const double *params, const float *t_p, const float *t_v, const double *t_head, const double *t_params,
                             float *t_p_out, float *t_v_out, float *t_hist, dhts_error *err, void *stream) {
     const MicroPlan pl = micro_plan(d, T, count != nullptr);
     const int L = d->n_lanes, V = d->capacity;
     const size_t dir_state = (size_t)L * V, dir_hist = (size_t)T * L * 2 * V;
-    const bool lds_ok = micro_jvp_each_group(n_dir, pl.jvp_kmax, [&](int k0, auto kv, int n_act) {
+    const bool lds_ok = jvp_each_group(n_dir, pl.jvp_kmax, [&](int k0, auto kv, int n_act) {
         constexpr int kK = decltype(kv)::value;
         const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
         float *o_h = t_hist ? t_hist + k0 * dir_hist : nullptr;
@@ -836,7 +813,7 @@ static int micro_fwd_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, cons
     const bool samp = f.kind == kObserveSamples;
     const size_t dir_state = (size_t)L * V, dir_lead = (size_t)T * L * 2;
     const size_t dir_obs = samp ? (size_t)(T / f.pr.every) * L * 2 * f.pr.n : (size_t)T * L * 2 * V;
-    const bool lds_ok = micro_jvp_each_group(n_dir, pl.fwd_jvp_kmax[t_params ? 1 : 0], [&](int k0, auto kv, int n_act) {
+    const bool lds_ok = jvp_each_group(n_dir, pl.fwd_jvp_kmax[t_params ? 1 : 0], [&](int k0, auto kv, int n_act) {
         constexpr int kK = decltype(kv)::value;
         const double *a_h = t_head ? t_head + (size_t)k0 * L * 2 : nullptr, *a_q = t_params ? t_params + k0 * 6 * dir_state : nullptr;
         float *obs = k0 == 0 ? f.obs : nullptr, *t_obs = f.t_obs ? f.t_obs + k0 * dir_obs : nullptr;
@@ -1003,7 +980,7 @@ int dhts_micro_rollout_jvp(const dhts_micro_desc *d, int T, int n_dir, const flo
 int dhts_micro_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]) {
     if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !plan) return DHTS_E_INVALID;
     const MicroPlan pl = micro_plan(d, T, false);
-    const MicroJvpGroups g = micro_jvp_groups(pl.jvp_kmax, n_dir);
+    const JvpGroups g = jvp_groups(pl.jvp_kmax, n_dir);
     for (int k = 0; k < 8; ++k) plan[k] = 0;
     plan[0] = pl.jvp_block;
     plan[1] = g.widest;
@@ -1024,7 +1001,7 @@ int dhts_micro_rollout_fwd_jvp(const dhts_micro_desc *d, int T, int n_dir, const
 int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]) {
     if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !plan) return DHTS_E_INVALID;
     const MicroPlan pl = micro_plan(d, T, false);
-    const MicroJvpGroups g = micro_jvp_groups(pl.fwd_jvp_kmax[want_params != 0 ? 1 : 0], n_dir);
+    const JvpGroups g = jvp_groups(pl.fwd_jvp_kmax[want_params != 0 ? 1 : 0], n_dir);
     for (int k = 0; k < 8; ++k) plan[k] = 0;
     plan[0] = pl.fwd_jvp_block;
     plan[1] = g.widest;

@@ -64,11 +64,7 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
         raise ValueError("macro_rollout_jvp(fused=True): a lane of %d cells does not fit the fused forward + tangent kernel (its records, "
                          "the interface products and the tangent copies exceed the LDS of a workgroup); fused=False covers it" % N)
     with torch.no_grad():
-        r0c, u0c = ops._f32c(r0.detach(), "r0"), ops._f32c(u0.detach(), "u0")
-        gr, gu = ops._f32c(ghost_r.detach(), "ghost_r"), ops._f32c(ghost_u.detach(), "ghost_u")
-        y0, q0 = ops.macro_state_from_ru(r0c, u0c, u_max)
-        gy, gq = ops.macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
-        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()
+        r0c, u0c, gr, gu, _, y0, q0, ghost = ops._macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
         readings = None
         if not fused:
             # the forward rollout with a tape, as MacroRollout.forward runs it

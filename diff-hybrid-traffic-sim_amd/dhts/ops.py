@@ -35,6 +35,32 @@ def _f32c(t, name):
     return t.contiguous()
 
 
+# ---- what the raw wrappers of both models share: optional arrays, observation buffers, state outputs ----
+def _data(t):
+    """The address the library gets for an optional array: NULL for None and for a tensor without an element (it has no address)."""
+    return None if t is None or not t.numel() else C.c_void_p(t.data_ptr())
+
+
+def _obs_buffer(name, t, shape, device, new=torch.zeros):
+    """An observation array handed in (checked), or one made by `new` (None: none).  Samples are zero-filled: the kernels write live
+    probe slots only."""
+    if t is None:
+        return None if new is None else new(shape, dtype=torch.float32, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(shape)))
+    return t
+
+
+def _state_out(names, out, likes):
+    """The state buffers of `out` (checked against the inputs they mirror), or new ones."""
+    if not out:
+        return tuple(torch.empty_like(t) for t in likes)
+    for name, t, like in zip(names, out, likes):
+        if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
+    return tuple(out[:len(likes)])
+
+
 def new_error_record(device):
     """Device-side sticky fault record (dhts_error): int32 [code, step, lane, index]."""
     return torch.zeros(4, dtype=torch.int32, device=device)
@@ -136,6 +162,17 @@ def _det_i32(det, N):
     return det.contiguous()
 
 
+def _with_det(t, det):
+    """The address of the array that goes with detectors (readings, their tangents or cotangents); the entry points want one even for
+    T = 0, where the tensor has no element and no address, and read no row."""
+    return None if t is None else C.c_void_p(t.data_ptr() or det.data_ptr())
+
+
+def _empty_rows(shape, **kw):
+    """torch.empty for [T][...] observations, a row allocated even for T = 0."""
+    return torch.empty((max(shape[0], 1),) + tuple(shape[1:]), **kw)[:shape[0]]
+
+
 def _macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, ghost_name, sched, tape, err, out, hist=None, det=None, taps=None):
     """The forward rollout of every form (include/dhts.h): ghost [L][2][4], or with `sched` a schedule [T][L][2][4]; with `det` the
     detector form, which writes `taps` instead of `hist`.  Returns (out, taps)."""
@@ -153,18 +190,14 @@ def _macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, ghost_name, sched, tape, er
         ghost = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
     if det is not None:
         D = det.numel()
-        if taps is None:
-            taps = torch.empty(max(T, 1), L, 3, D, dtype=torch.float32, device=r.device)[:T]
-        elif tuple(taps.shape) != (T, L, 3, D) or taps.dtype != torch.float32 or not taps.is_cuda or not taps.is_contiguous():
-            raise ValueError("taps must be a contiguous float32 CUDA tensor of shape (%d, %d, 3, %d)" % (T, L, D))
+        taps = _obs_buffer("taps", taps, (T, L, 3, D), r.device, new=_empty_rows)
     if out is None:
         out = tuple(torch.empty_like(r) for _ in range(4))
     state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost))
     outs = tuple(_ptr(o) for o in out)
     if det is not None:
         check(_lib.lib().dhts_macro_rollout_fwd_taps(C.byref(desc), T, *state, int(sched), *outs, _ptr(tape), _ptr(det), D,
-                                                     C.c_void_p(taps.data_ptr() or det.data_ptr()),      # (T = 0: no address, no row)
-                                                     _ptr(err), _stream()), "dhts_macro_rollout_fwd_taps")
+                                                     _with_det(taps, det), _ptr(err), _stream()), "dhts_macro_rollout_fwd_taps")
     else:
         entry = "dhts_macro_rollout_fwd_sched" if sched else "dhts_macro_rollout_fwd"
         check(getattr(_lib.lib(), entry)(C.byref(desc), T, *state, *outs, _ptr(tape), _ptr(hist), _ptr(err), _stream()), entry)
@@ -193,9 +226,9 @@ def _macro_rollout_bwd(desc, T, tape, g_r, g_y, sched, err, out, g_hist=None, de
         g_ghost = torch.zeros(L, 2, 2, dtype=torch.float64, device=g_r.device)
     grads = (_ptr(tape), _ptr(g_r), _ptr(g_y))
     if det is not None:
-        check(_lib.lib().dhts_macro_rollout_bwd_taps(C.byref(desc), T, *grads, _ptr(det), D,
-                                                     C.c_void_p(g_taps.data_ptr() or det.data_ptr()), _ptr(out[0]), _ptr(out[1]),
-                                                     _ptr(g_ghost), int(bool(sched)), _ptr(err), _stream()), "dhts_macro_rollout_bwd_taps")
+        check(_lib.lib().dhts_macro_rollout_bwd_taps(C.byref(desc), T, *grads, _ptr(det), D, _with_det(g_taps, det),
+                                                     _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), int(bool(sched)), _ptr(err), _stream()),
+              "dhts_macro_rollout_bwd_taps")
     else:
         entry = "dhts_macro_rollout_bwd_sched" if sched else "dhts_macro_rollout_bwd"
         check(getattr(_lib.lib(), entry)(C.byref(desc), T, *grads, _ptr(g_hist), _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err),
@@ -324,69 +357,48 @@ class MacroRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, det=None, checkpoint=None):
         L, N = r0.shape
-        sched = ghost_r.dim() == 3
-        if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
-            raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
-        want = (int(T), L, 2) if sched else (L, 2)
-        if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
-            raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
+        sched = _macro_boundary_form(L, ghost_r, ghost_u, T)
         desc = macro_desc(L, N, dt, dx, u_max)
         segment = _macro_checkpoint_segment(checkpoint, desc, T, want_hist, 0 if det is None else int(det.numel()))
-        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
-        gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
-        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
-        gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
-        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4], or [T][L][2][4]
+        r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
         need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
         ctx.segment = segment if need_grad else None
+        err = new_error_record(r0.device)
+        tape = None
         if ctx.segment is not None:
             # the checkpointed pair: the checkpoint buffer, the readings if asked for and the fault record; no tape.  The replay reads the
             # forward's inputs again: (y0, q0, ghost) stay alive beside what the taped path saves
             ctx.ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=r0.device)
             ctx.replay = (y0, q0, ghost)
-            err = new_error_record(r0.device)
             (rT, yT, uT, qT), steps = macro_rollout_fwd_ckpt(desc, T, r0c, y0, u0c, q0, ghost, ctx.ckpt, segment=segment, det=det, err=err)
-            if check_faults:
-                raise_on_fault(err)
-            ctx.sched = sched
-            ctx.desc, ctx.T, ctx.u_max, ctx.tape, ctx.check_faults = desc, T, u_max, None, check_faults
-            ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, steps, det)
-            ctx.mark_non_differentiable(qT)
-            return (rT, yT, uT, qT) if steps is None else (rT, yT, uT, qT, steps)
-        tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
-        err = new_error_record(r0.device)
-        if det is not None:
-            (rT, yT, uT, qT), steps = macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
         else:
-            steps = torch.empty(T, L, 3, N, dtype=torch.float32, device=r0.device) if want_hist else None
-            fwd = macro_rollout_fwd_sched if sched else macro_rollout_fwd
-            rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=steps, err=err)
+            tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
+            if det is not None:
+                (rT, yT, uT, qT), steps = macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
+            else:
+                steps = torch.empty(T, L, 3, N, dtype=torch.float32, device=r0.device) if want_hist else None
+                fwd = macro_rollout_fwd_sched if sched else macro_rollout_fwd
+                rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=steps, err=err)
         if check_faults:
             raise_on_fault(err)
         ctx.sched = sched
         ctx.desc, ctx.T, ctx.u_max, ctx.tape, ctx.check_faults = desc, T, u_max, tape, check_faults
         ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, steps, det)
         ctx.mark_non_differentiable(qT)
-        if steps is not None:
-            return rT, yT, uT, qT, steps
-        return rT, yT, uT, qT
+        return (rT, yT, uT, qT) if steps is None else (rT, yT, uT, qT, steps)
 
     @staticmethod
     def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_steps=None):
         r0, u0, gr, gu, gq, rT, yT, steps, det = ctx.saved_tensors
         desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        L, N = desc.n_lanes, desc.n_cells
-        dev = r0.device
-        g_r = g_rT.contiguous().clone() if g_rT is not None else torch.zeros(L, N, device=dev)
-        g_y = g_yT.contiguous().clone() if g_yT is not None else torch.zeros(L, N, device=dev)
-        if g_uT is not None:
-            macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
+        L = desc.n_lanes
+        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
         gs = None
         ckpt = ctx.segment is not None       # (its glue goes over the T-sized cotangents a part at a time: _glue_rows)
         if steps is not None and g_steps is not None and g_steps.numel():      # (T = 0: no row, and an empty tensor has no address)
             # [T][L][2][N], with detectors [T][L][2][D]
             gs = _per_step_cotangent(steps, g_steps, um, rows=_glue_rows(T, L * steps.shape[3]) if ckpt else None)
-        err = new_error_record(dev)
+        err = new_error_record(r0.device)
         if ckpt:
             y0, q0, ghost = ctx.replay
             taps = gs is not None and det is not None            # (no readings to look at: the plain sweep)
@@ -398,11 +410,7 @@ class MacroRollout(torch.autograd.Function):
         else:                            # (no readings to look at: the plain sweep over the same tape)
             bwd = macro_rollout_bwd_sched if ctx.sched else macro_rollout_bwd
             g_r0, g_y0, g_ghost = bwd(desc, T, ctx.tape, g_r, g_y, g_hist=gs, err=err)      # [L][2][2], or [T][L][2][2] per step
-        if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
-            raise_on_fault(err)
-        g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
-        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um, rows=_glue_rows(T, 2 * L) if ckpt else None)
-        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None, None, None
+        return _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * L) if ckpt else None) + (None,) * 8
 
 
 class MacroRolloutTarget(torch.autograd.Function):
@@ -415,21 +423,11 @@ class MacroRolloutTarget(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, check_faults, checkpoint, target):
         L, N = r0.shape
-        sched = ghost_r.dim() == 3
-        if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
-            raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
-        want = (int(T), L, 2) if sched else (L, 2)
-        if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
-            raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
+        sched = _macro_boundary_form(L, ghost_r, ghost_u, T)
         desc = macro_desc(L, N, dt, dx, u_max)
         segment = _macro_target_segment(checkpoint, desc, T)
         dev = r0.device
-        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
-        gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
-        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
-        gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
-        ghost = torch.stack([gr, gy, gu, gq], dim=-1).contiguous()            # [L][2][4], or [T][L][2][4]
-        del gy
+        r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
         need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
         ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
         err = new_error_record(dev)
@@ -450,34 +448,74 @@ class MacroRolloutTarget(torch.autograd.Function):
     def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_sse):
         r0, u0, gr, gu, gq, rT, yT, uT = ctx.saved_tensors
         desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        L, N = desc.n_lanes, desc.n_cells
-        dev = r0.device
-        g_r = g_rT.contiguous().clone() if g_rT is not None else torch.zeros(L, N, device=dev)
-        g_y = g_yT.contiguous().clone() if g_yT is not None else torch.zeros(L, N, device=dev)
-        if g_uT is not None:
-            macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
-        err = new_error_record(dev)
+        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
+        err = new_error_record(r0.device)
         y0, q0, ghost = ctx.replay
         g_r0, g_y0, g_ghost = macro_rollout_bwd_ckpt_target(desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, ctx.target,
                                                             g_sse=g_sse.contiguous() if g_sse is not None else None, final=(rT, yT, uT),
                                                             segment=ctx.segment, err=err, out=ctx.out_bwd, g_ghost=ctx.g_ghost)
         del y0, q0, ghost                # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
         ctx.replay = ctx.ckpt = None
-        if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
-            raise_on_fault(err)
-        g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, um)
-        g_gr, g_gu = _ghost_ry_to_ru(g_ghost, gr, gu, gq, um, rows=_glue_rows(T, 2 * L))
-        return g_r0, g_u0, g_gr, g_gu, None, None, None, None, None, None, None
+        return _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * desc.n_lanes)) + (None,) * 7
+
+
+# ---- what the two macro autograd Functions (and dhts.jvp.macro_rollout_jvp) share: the leaves, the backward's seeds and tail, the segment ----
+def _macro_boundary_form(L, ghost_r, ghost_u, T):
+    """-> whether (ghost_r, ghost_u) are a schedule [T][L][2] (else [L][2]); ValueError for anything else."""
+    sched = ghost_r.dim() == 3
+    if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
+        raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
+    want = (int(T), L, 2) if sched else (L, 2)
+    if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want:
+        raise ValueError("ghost_r and ghost_u must have shape %s (got %s and %s)" % (want, tuple(ghost_r.shape), tuple(ghost_u.shape)))
+    return sched
+
+
+def _macro_leaves(r0, u0, ghost_r, ghost_u, u_max):
+    """The leaves as the kernels read them -> (r0c, u0c, gr, gu, gq, y0, q0, ghost): detached contiguous float32, y and the equilibrium
+    speed of the state and of the boundary cells, ghost = (r, y, u, ueq) stacked, [L][2][4] or [T][L][2][4]."""
+    r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+    gr, gu = _f32c(ghost_r.detach(), "ghost_r"), _f32c(ghost_u.detach(), "ghost_u")
+    y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
+    gy, gq = macro_state_from_ru(gr, gu, u_max) if gr.numel() else (gr.clone(), gr.clone())
+    return r0c, u0c, gr, gu, gq, y0, q0, torch.stack([gr, gy, gu, gq], dim=-1).contiguous()
+
+
+def _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um):
+    """The cotangents of (rT, yT, uT) -> fresh (g_r, g_y) for the reverse sweep, uT's folded in through the speed's glue."""
+    g_r = g_rT.contiguous().clone() if g_rT is not None else torch.zeros_like(rT)
+    g_y = g_yT.contiguous().clone() if g_yT is not None else torch.zeros_like(rT)
+    if g_uT is not None:
+        macro_u_tap_bwd(rT, yT, g_uT.contiguous(), g_r, g_y, um)
+    return g_r, g_y
+
+
+def _macro_bwd_done(ctx, err, leaves, g_r0, g_y0, g_ghost, rows):
+    """The fault check and the glue back to the leaves -> (g_r0, g_u0, g_ghost_r, g_ghost_u); rows: _ghost_ry_to_ru's."""
+    r0, u0, gr, gu, gq = leaves
+    if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
+        raise_on_fault(err)
+    g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, ctx.u_max)
+    return (g_r0, g_u0) + _ghost_ry_to_ru(g_ghost, gr, gu, gq, ctx.u_max, rows=rows)
+
+
+def _macro_segment(checkpoint, desc, T, form, n_det=0):
+    """dhts.macro_rollout's `checkpoint` -> the segment length of the form's plan ("target": the target forms' own); ValueError otherwise."""
+    def plan(segment):
+        ask = (lambda sg: macro_ckpt_target_plan(desc, T, sg)) if form == "target" else (lambda sg: macro_ckpt_plan(desc, T, n_det, sg))
+        if ask(0)["max_segment"] >= 1:
+            return ask(segment)
+        if form == "target":
+            raise ValueError("lanes of %d cells do not fit the target forms of the checkpointed sweep (the reverse LDS of the target plan "
+                             "holds up to %d cells): fit the want_hist=True history instead" % (desc.n_cells, MACRO_CKPT_TARGET_MAX_CELLS))
+        raise ValueError("lanes of %d cells do not fit the checkpointed reverse sweep (its LDS holds up to %d cells): "
+                         "use the taped path, checkpoint=None" % (desc.n_cells, MACRO_CKPT_MAX_CELLS))
+    return _checkpoint_segment(checkpoint, plan)
 
 
 def _macro_target_segment(checkpoint, desc, T):
     """dhts.macro_rollout's `checkpoint` beside `target` -> the segment length of the target forms' own plan; ValueError otherwise."""
-    def plan(segment):
-        if macro_ckpt_target_plan(desc, T, 0)["max_segment"] < 1:
-            raise ValueError("lanes of %d cells do not fit the target forms of the checkpointed sweep (the reverse LDS of the target plan "
-                             "holds up to %d cells): fit the want_hist=True history instead" % (desc.n_cells, MACRO_CKPT_TARGET_MAX_CELLS))
-        return macro_ckpt_target_plan(desc, T, segment)
-    return _checkpoint_segment(checkpoint, plan)
+    return _macro_segment(checkpoint, desc, T, "target")
 
 
 def _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint):
@@ -506,13 +544,7 @@ def _macro_checkpoint_segment(checkpoint, desc, T, want_hist, n_det):
     """dhts.macro_rollout's `checkpoint` -> None (the taped path) or the segment length; ValueError otherwise, before a device is touched."""
     if checkpoint is None or checkpoint is False:
         return None
-
-    def plan(segment):
-        if macro_ckpt_plan(desc, T, n_det, 0)["max_segment"] < 1:
-            raise ValueError("lanes of %d cells do not fit the checkpointed reverse sweep (its LDS holds up to %d cells): "
-                             "use the taped path, checkpoint=None" % (desc.n_cells, MACRO_CKPT_MAX_CELLS))
-        return macro_ckpt_plan(desc, T, n_det, segment)
-    segment = _checkpoint_segment(checkpoint, plan)
+    segment = _macro_segment(checkpoint, desc, T, "plain", n_det)
     if want_hist:
         raise ValueError("want_hist and checkpoint exclude each other: the history is of size T anyway (checkpoint=None keeps the tape)")
     return segment
@@ -603,41 +635,56 @@ def macro_u_tap_jvp(r, y, t_r, t_y, u_max):
     return t_u
 
 
+def _macro_directions(desc, t_r, t_y):
+    """The two tangent wrappers' check of (t_r, t_y) -> K."""
+    L, N = desc.n_lanes, desc.n_cells
+    if t_r.dim() != 3 or tuple(t_r.shape[1:]) != (L, N) or t_r.shape[0] < 1 or t_y.shape != t_r.shape:
+        raise ValueError("t_r and t_y must have shape (K, %d, %d) with K >= 1" % (L, N))
+    return int(t_r.shape[0])
+
+
+def _macro_t_ghost(t_ghost, want, message):
+    """... of t_ghost against the shape `want` (ValueError(message)) -> contiguous, or None: zero boundary tangents."""
+    if t_ghost is None:
+        return None
+    if tuple(t_ghost.shape) != want:
+        raise ValueError(message)
+    t_ghost = _f32c(t_ghost, "t_ghost")
+    return t_ghost if t_ghost.numel() else None          # (a schedule of no steps: no row, and an empty tensor has no address)
+
+
+def _macro_readings(desc, T, K, det, device, without, t_taps, taps=None, primal=False):
+    """... of det and the readings -> (det, D, taps, t_taps): with det t_taps [K][T][L][2][D] and, for `primal`, taps [T][L][3][D] are
+    checked or made; without det, handing one in is ValueError(without)."""
+    if det is None:
+        if taps is not None or t_taps is not None:
+            raise ValueError(without)
+        return None, 0, None, None
+    L, det = desc.n_lanes, _det_i32(det, desc.n_cells)
+    D = det.numel()
+    if primal:
+        taps = _obs_buffer("taps", taps, (T, L, 3, D), device, new=torch.empty)
+    return det, D, taps, _obs_buffer("t_taps", t_taps, (K, T, L, 2, D), device, new=torch.empty)
+
+
 def macro_rollout_jvp(desc, T, tape, t_r, t_y, t_ghost=None, det=None, err=None, out=None, t_taps=None):
     """The tangent sweep over a rollout tape (include/dhts.h): t_r, t_y [K][L][N]; t_ghost None (zero), [K][L][2][2] (the same tangent in
     front of every step) or a schedule [K][T][L][2][2], (left, right) x (r, y); det int32 CUDA [D] or None.  Returns (t_rT, t_yT, t_taps):
     t_taps [K][T][L][2][D] = the tangent of (r, y) of cell det[j] after every step, None without det."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
-    if t_r.dim() != 3 or tuple(t_r.shape[1:]) != (L, N) or t_r.shape[0] < 1 or t_y.shape != t_r.shape:
-        raise ValueError("t_r and t_y must have shape (K, %d, %d) with K >= 1" % (L, N))
-    K = int(t_r.shape[0])
+    K = _macro_directions(desc, t_r, t_y)
     t_r, t_y = _f32c(t_r, "t_r"), _f32c(t_y, "t_y")
-    sched = False
-    if t_ghost is not None:
-        sched = t_ghost.dim() == 5
-        want = (K, T, L, 2, 2) if sched else (K, L, 2, 2)
-        if tuple(t_ghost.shape) != want:
-            raise ValueError("t_ghost must have shape (%d, %d, 2, 2) or (%d, %d, %d, 2, 2)" % (K, L, K, T, L))
-        t_ghost = _f32c(t_ghost, "t_ghost")
-        if not t_ghost.numel():          # (a schedule of no steps: no row, and an empty tensor has no address)
-            t_ghost, sched = None, False
-    D = 0
-    if det is not None:
-        det = _det_i32(det, N)
-        D = det.numel()
-        if t_taps is None:
-            t_taps = torch.empty(K, T, L, 2, D, dtype=torch.float32, device=t_r.device)
-        elif tuple(t_taps.shape) != (K, T, L, 2, D) or t_taps.dtype != torch.float32 or not t_taps.is_cuda or not t_taps.is_contiguous():
-            raise ValueError("t_taps must be a contiguous float32 CUDA tensor of shape (%d, %d, %d, 2, %d)" % (K, T, L, D))
-    elif t_taps is not None:
-        raise ValueError("t_taps without det")
+    sched = t_ghost is not None and t_ghost.dim() == 5
+    t_ghost = _macro_t_ghost(t_ghost, (K, T, L, 2, 2) if sched else (K, L, 2, 2),
+                             "t_ghost must have shape (%d, %d, 2, 2) or (%d, %d, %d, 2, 2)" % (K, L, K, T, L))
+    sched = sched and t_ghost is not None
+    det, D, _, t_taps = _macro_readings(desc, T, K, det, t_r.device, "t_taps without det", t_taps)
     if T > 0 and tape is None:
         raise ValueError("a sweep of T > 0 steps needs the rollout's tape")
     if out is None:
         out = (torch.empty_like(t_r), torch.empty_like(t_y))
-    taps_ptr = None if det is None else C.c_void_p(t_taps.data_ptr() or det.data_ptr())      # (T = 0: no address, no row)
     check(_lib.lib().dhts_macro_rollout_jvp(C.byref(desc), T, _ptr(tape), K, _ptr(t_r), _ptr(t_y), _ptr(t_ghost), int(sched),
-                                            _ptr(out[0]), _ptr(out[1]), _ptr(det), D, taps_ptr, _ptr(err), _stream()),
+                                            _ptr(out[0]), _ptr(out[1]), _ptr(det), D, _with_det(t_taps, det), _ptr(err), _stream()),
           "dhts_macro_rollout_jvp")
     return out[0], out[1], t_taps
 
@@ -675,9 +722,7 @@ def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, 
     want = (T, L, 2, 4) if sched else (L, 2, 4)
     if tuple(ghost.shape) != want:
         raise ValueError("ghost must have shape (%d, 2, 4) or (%d, %d, 2, 4)" % (L, T, L))
-    if t_r.dim() != 3 or tuple(t_r.shape[1:]) != (L, N) or t_r.shape[0] < 1 or t_y.shape != t_r.shape:
-        raise ValueError("t_r and t_y must have shape (K, %d, %d) with K >= 1" % (L, N))
-    K = int(t_r.shape[0])
+    K = _macro_directions(desc, t_r, t_y)
     if macro_fwd_jvp_plan(desc, T, K)["dirs_per_launch"] < 1:
         raise ValueError("a lane of %d cells does not fit the fused forward + tangent kernel (its records, the interface products and "
                          "the tangent copies exceed the LDS of a workgroup); fused=False, the taped pair, covers it" % N)
@@ -685,39 +730,18 @@ def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, 
     t_r, t_y = _f32c(t_r, "t_r"), _f32c(t_y, "t_y")
     if sched and T == 0:        # an empty tensor has no address; the entry point wants one and reads no row
         ghost = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
-    if t_ghost is not None:
-        want = (K, T, L, 2, 2) if sched else (K, L, 2, 2)
-        if tuple(t_ghost.shape) != want:
-            raise ValueError("t_ghost must have shape %s: it follows the form of ghost" % (want,))
-        t_ghost = _f32c(t_ghost, "t_ghost")
-        if not t_ghost.numel():          # (a schedule of no steps: no row, and an empty tensor has no address)
-            t_ghost = None
-    D = 0
-    if det is not None:
-        det = _det_i32(det, N)
-        D = det.numel()
-        for name, t, shape in (("taps", taps, (T, L, 3, D)), ("t_taps", t_taps, (K, T, L, 2, D))):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, shape))
-        if taps is None:
-            taps = torch.empty(T, L, 3, D, dtype=torch.float32, device=r.device)
-        if t_taps is None:
-            t_taps = torch.empty(K, T, L, 2, D, dtype=torch.float32, device=r.device)
-    elif taps is not None or t_taps is not None:
-        raise ValueError("taps / t_taps without det")
-    if out is None:
-        out = tuple(torch.empty_like(r) for _ in range(4)) + (torch.empty_like(t_r), torch.empty_like(t_y))
-    else:
+    want = (K, T, L, 2, 2) if sched else (K, L, 2, 2)
+    t_ghost = _macro_t_ghost(t_ghost, want, "t_ghost must have shape %s: it follows the form of ghost" % (want,))
+    det, D, taps, t_taps = _macro_readings(desc, T, K, det, r.device, "taps / t_taps without det", t_taps, taps, primal=True)
+    if out is not None:
         out = tuple(out)
         if len(out) != 6:
             raise ValueError("out must be (r_out, y_out, u_out, ueq_out, t_r_out, t_y_out)")
-        for name, t, like in zip(("r_out", "y_out", "u_out", "ueq_out", "t_r_out", "t_y_out"), out, (r, y, u, ueq, t_r, t_y)):
-            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
-    tptr = [None if h is None else C.c_void_p(h.data_ptr() or det.data_ptr()) for h in (taps, t_taps)]      # (T = 0: no address, no row)
+    out = _state_out(("r_out", "y_out", "u_out", "ueq_out", "t_r_out", "t_y_out"), out, (r, y, u, ueq, t_r, t_y))
     check(_lib.lib().dhts_macro_rollout_fwd_jvp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                _ptr(t_r), _ptr(t_y), _ptr(t_ghost), *(_ptr(o) for o in out), _ptr(det), D, tptr[0],
-                                                tptr[1], _ptr(err), _ptr(err_jvp), _stream()), "dhts_macro_rollout_fwd_jvp")
+                                                _ptr(t_r), _ptr(t_y), _ptr(t_ghost), *(_ptr(o) for o in out), _ptr(det), D,
+                                                _with_det(taps, det), _with_det(t_taps, det), _ptr(err), _ptr(err_jvp), _stream()),
+          "dhts_macro_rollout_fwd_jvp")
     return (out[0], out[1], out[2], out[3], taps), (out[4], out[5], t_taps)
 
 
@@ -740,14 +764,20 @@ def macro_ckpt_plan(desc, T, n_det=0, segment=0):
     segment length used (the plan's own for segment = 0), the longest one the reverse kernel's LDS holds, the number of checkpoints
     ceil(T / segment), the dynamic LDS bytes of the two kernels and the reverse workgroups a CU holds by LDS.  A lane too long for the
     reverse kernel reports max_segment = 0 (and segment = 0).  ValueError: a segment outside 0 .. max_segment.  Needs no device."""
+    return _macro_ckpt_plan("dhts_macro_ckpt_plan", "max_segment", desc, (T, n_det), segment)
+
+
+def _macro_ckpt_plan(entry, forms, desc, shape, segment):
+    """macro_ckpt_plan (shape = (T, n_det)) and macro_ckpt_target_plan (shape = (T,), forms "the max_segment of the target forms")."""
     plan = (C.c_int32 * 8)()
     if not 0 <= int(segment) <= 0x7fffffff:
         raise ValueError("segment must be 0 (the plan's choice) or a positive int")
-    status = _lib.lib().dhts_macro_ckpt_plan(C.byref(desc), int(T), int(n_det), int(segment), C.byref(plan))
-    if status == _lib.E_INVALID and int(segment) and _lib.lib().dhts_macro_ckpt_plan(C.byref(desc), int(T), int(n_det), 0, C.byref(plan)) == 0:
+    ask, shape = getattr(_lib.lib(), entry), tuple(int(v) for v in shape)
+    status = ask(C.byref(desc), *shape, int(segment), C.byref(plan))
+    if status == _lib.E_INVALID and int(segment) and ask(C.byref(desc), *shape, 0, C.byref(plan)) == 0:
         # the plan's own segment is accepted, so the descriptor, T and n_det are good and it is the segment that is not
-        raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment (%d) for lanes of %d cells" % (plan[3], desc.n_cells))
-    check(status, "dhts_macro_ckpt_plan")
+        raise ValueError("segment must be 0 (the plan's choice) or 1 .. %s (%d) for lanes of %d cells" % (forms, plan[3], desc.n_cells))
+    check(status, entry)
     return dict(zip(_MACRO_CKPT_PLAN_KEYS, list(plan)))
 
 
@@ -776,37 +806,55 @@ def _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost):
     return sched, r, y, u, ueq, ghost
 
 
-def macro_rollout_fwd_ckpt(desc, T, r, y, u, ueq, ghost, ckpt, segment=0, det=None, err=None, out=None, taps=None):
-    """macro_rollout_fwd / _sched / _taps that fills the checkpoint buffer `ckpt` (float32 [macro_ckpt_numel(desc, T, segment)]) instead
-    of a tape (dhts_macro_rollout_fwd_ckpt): the same state and readings, bit for bit.  ghost [L][2][4], or a schedule [T][L][2][4].
-    Returns ((r, y, u, ueq) after T steps, taps [T][L][3][D] or None)."""
+def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out, det=None, taps=None, target=None, sse=None):
+    """The checkpointed forward of both forms ("plain": detectors or nothing, "target": the dense fit): checks, buffers and the one C call
+    -> (out, taps or sse).  ckpt may be None (no checkpoint is kept) in the target form."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
-    if det is None and taps is not None:
+    fit, keep = form == "target", ckpt
+    if fit:
+        segment = _macro_target_args(desc, T, segment, ckpt, target, False)
+        if ckpt is None:
+            keep = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device="meta")
+    elif det is None and taps is not None:
         raise ValueError("taps without det")
-    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost)
+    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, segment, keep, r, y, u, ueq, ghost)
     D = 0
     if det is not None:
         det = _det_i32(det, N)
         D = det.numel()
-        if taps is None:
-            taps = torch.empty(max(T, 1), L, 3, D, dtype=torch.float32, device=r.device)[:T]
-        elif tuple(taps.shape) != (T, L, 3, D) or taps.dtype != torch.float32 or not taps.is_cuda or not taps.is_contiguous():
-            raise ValueError("taps must be a contiguous float32 CUDA tensor of shape (%d, %d, 3, %d)" % (T, L, D))
+        taps = _obs_buffer("taps", taps, (T, L, 3, D), r.device, new=_empty_rows)
+    if fit and sse is None:
+        sse = torch.empty(L, 2, dtype=torch.float64, device=r.device)
+    elif fit and (tuple(sse.shape) != (L, 2) or sse.dtype != torch.float64 or not sse.is_cuda or not sse.is_contiguous()):
+        raise ValueError("sse must be a contiguous float64 CUDA tensor of shape (%d, 2)" % L)
+    if fit and not target.is_cuda:
+        raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = tuple(torch.empty_like(r) for _ in range(4))
+    if fit:
+        check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target(C.byref(desc), T, segment, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
+                                                            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _data(ckpt), _data(target),
+                                                            _ptr(sse), _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt_target")
+        return out, sse
     check(_lib.lib().dhts_macro_rollout_fwd_ckpt(C.byref(desc), T, int(segment), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(det), D,
-                                                 None if det is None else C.c_void_p(taps.data_ptr() or det.data_ptr()),
-                                                 _ptr(ckpt) if ckpt.numel() else None, _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt")
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(det), D, _with_det(taps, det),
+                                                 _data(ckpt), _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt")
     return out, taps
 
 
-def macro_rollout_bwd_ckpt(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment=0, det=None, g_taps=None, err=None, out=None):
-    """Reverse sweep from the checkpoints of macro_rollout_fwd_ckpt -> (g_r0, g_y0, g_ghost): macro_rollout_bwd / _sched / _taps' bits.
-    r, y, u, ueq, ghost, segment: the forward's.  det with g_taps [T][L][2][D], or neither.  g_ghost: float64 [L][2][2] summed over the
-    steps, or beside a schedule per step [T][L][2][2]."""
+def _macro_ckpt_bwd(form, desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, det=None, g_taps=None, target=None, g_sse=None,
+                    final=None, g_ghost=None):
+    """The checkpointed reverse sweep of both forms, as above -> (g_r0, g_y0, g_ghost)."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
-    if (det is None) != (g_taps is None):
+    fit = form == "target"
+    if fit:
+        segment = _macro_target_args(desc, T, segment, ckpt, target, True)
+        if g_sse is not None:
+            if tuple(g_sse.shape) != (L, 2) or g_sse.dtype != torch.float64:
+                raise ValueError("g_sse must be a float64 tensor of shape (%d, 2)" % L)
+            if final is None or len(final) != 3 or any(tuple(t.shape) != (L, N) for t in final):
+                raise ValueError("g_sse needs final = the forward's (r, y, u) after T steps, each of shape (%d, %d)" % (L, N))
+    elif (det is None) != (g_taps is None):
         raise ValueError("det and g_taps go together")
     sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost)
     D = 0
@@ -816,20 +864,49 @@ def macro_rollout_bwd_ckpt(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment
         if tuple(g_taps.shape) != (T, L, 2, D):
             raise ValueError("g_taps must have shape (%d, %d, 2, %d)" % (T, L, D))
         g_taps = _f32c(g_taps, "g_taps")
+    if g_sse is not None:
+        g_sse = g_sse.contiguous()
+        final = tuple(_f32c(t, n) for t, n in zip(final, ("final r", "final y", "final u")))
+    else:
+        final = (None, None, None)
     g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
     if tuple(g_r.shape) != (L, N) or tuple(g_y.shape) != (L, N):
         raise ValueError("g_r and g_y must have shape (%d, %d)" % (L, N))
+    if fit and not target.is_cuda:
+        raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = (torch.empty_like(g_r), torch.empty_like(g_y))
-    if sched:
-        g_ghost = torch.empty(max(T, 1), L, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
+    want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
+    if g_ghost is None:              # (a schedule's: every row is written; the sums are added to)
+        g_ghost = (torch.empty if sched else torch.zeros)(want, dtype=torch.float64, device=g_r.device)
+    elif tuple(g_ghost.shape) != want or g_ghost.dtype != torch.float64 or not g_ghost.is_contiguous():
+        raise ValueError("g_ghost must be a contiguous float64 tensor of shape %s" % (want,))
+    elif not sched:
+        g_ghost.zero_()
+    if fit:
+        check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target(C.byref(desc), T, segment, _data(ckpt), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost),
+                                                            int(sched), _ptr(g_r), _ptr(g_y), _data(target), _ptr(g_sse), _ptr(final[0]),
+                                                            _ptr(final[1]), _ptr(final[2]), _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err),
+                                                            _stream()), "dhts_macro_rollout_bwd_ckpt_target")
     else:
-        g_ghost = torch.zeros(L, 2, 2, dtype=torch.float64, device=g_r.device)
-    check(_lib.lib().dhts_macro_rollout_bwd_ckpt(C.byref(desc), T, int(segment), _ptr(ckpt) if ckpt.numel() else None, _ptr(r), _ptr(y),
-                                                 _ptr(u), _ptr(ueq), _ptr(ghost), int(sched), _ptr(g_r), _ptr(g_y), _ptr(det), D,
-                                                 None if det is None else C.c_void_p(g_taps.data_ptr() or det.data_ptr()),
-                                                 _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err), _stream()), "dhts_macro_rollout_bwd_ckpt")
+        check(_lib.lib().dhts_macro_rollout_bwd_ckpt(C.byref(desc), T, int(segment), _data(ckpt), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost),
+                                                     int(sched), _ptr(g_r), _ptr(g_y), _ptr(det), D, _with_det(g_taps, det), _ptr(out[0]),
+                                                     _ptr(out[1]), _ptr(g_ghost), _ptr(err), _stream()), "dhts_macro_rollout_bwd_ckpt")
     return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
+
+
+def macro_rollout_fwd_ckpt(desc, T, r, y, u, ueq, ghost, ckpt, segment=0, det=None, err=None, out=None, taps=None):
+    """macro_rollout_fwd / _sched / _taps that fills the checkpoint buffer `ckpt` (float32 [macro_ckpt_numel(desc, T, segment)]) instead
+    of a tape (dhts_macro_rollout_fwd_ckpt): the same state and readings, bit for bit.  ghost [L][2][4], or a schedule [T][L][2][4].
+    Returns ((r, y, u, ueq) after T steps, taps [T][L][3][D] or None)."""
+    return _macro_ckpt_fwd("plain", desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out, det, taps)
+
+
+def macro_rollout_bwd_ckpt(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment=0, det=None, g_taps=None, err=None, out=None):
+    """Reverse sweep from the checkpoints of macro_rollout_fwd_ckpt -> (g_r0, g_y0, g_ghost): macro_rollout_bwd / _sched / _taps' bits.
+    r, y, u, ueq, ghost, segment: the forward's.  det with g_taps [T][L][2][D], or neither.  g_ghost: float64 [L][2][2] summed over the
+    steps, or beside a schedule per step [T][L][2][2]."""
+    return _macro_ckpt_bwd("plain", desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, det, g_taps)
 
 
 # ---- the dense-fit loss inside the checkpointed pair (dhts_macro_rollout_*_ckpt_target) ------------------------------------------------
@@ -840,15 +917,7 @@ def macro_ckpt_target_plan(desc, T, segment=0):
     """macro_ckpt_plan for dhts_macro_rollout_fwd_ckpt_target / _bwd_ckpt_target (include/dhts.h): the same keys; the reverse kernel's
     ring holds two more floats per cell-step, so max_segment and the default segment are shorter and fewer lanes fit (max_segment = 0).
     ValueError: a segment outside 0 .. max_segment.  Needs no device."""
-    plan = (C.c_int32 * 8)()
-    if not 0 <= int(segment) <= 0x7fffffff:
-        raise ValueError("segment must be 0 (the plan's choice) or a positive int")
-    status = _lib.lib().dhts_macro_ckpt_target_plan(C.byref(desc), int(T), int(segment), C.byref(plan))
-    if status == _lib.E_INVALID and int(segment) and _lib.lib().dhts_macro_ckpt_target_plan(C.byref(desc), int(T), 0, C.byref(plan)) == 0:
-        raise ValueError("segment must be 0 (the plan's choice) or 1 .. the max_segment of the target forms (%d) for lanes of %d cells"
-                         % (plan[3], desc.n_cells))
-    check(status, "dhts_macro_ckpt_target_plan")
-    return dict(zip(_MACRO_CKPT_PLAN_KEYS, list(plan)))
+    return _macro_ckpt_plan("dhts_macro_ckpt_target_plan", "the max_segment of the target forms", desc, (T,), segment)
 
 
 def _macro_target_args(desc, T, segment, ckpt, target, need_ckpt):
@@ -871,24 +940,7 @@ def macro_rollout_fwd_ckpt_target(desc, T, r, y, u, ueq, ghost, ckpt, target, se
     observed) and returns the squared error (dhts_macro_rollout_fwd_ckpt_target): ((r, y, u, ueq) after T steps, sse float64 [L][2]).
     ckpt: float32 [macro_ckpt_numel(desc, T, S)] with S the resolved segment of macro_ckpt_target_plan, or None: no checkpoint is kept.
     segment 0: that plan's default."""
-    L, T = desc.n_lanes, int(T)
-    S = _macro_target_args(desc, T, segment, ckpt, target, False)
-    keep = ckpt if ckpt is not None else torch.empty(macro_ckpt_numel(desc, T, S), dtype=torch.float32, device="meta")
-    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, S, keep, r, y, u, ueq, ghost)
-    if sse is None:
-        sse = torch.empty(L, 2, dtype=torch.float64, device=r.device)
-    elif tuple(sse.shape) != (L, 2) or sse.dtype != torch.float64 or not sse.is_cuda or not sse.is_contiguous():
-        raise ValueError("sse must be a contiguous float64 CUDA tensor of shape (%d, 2)" % L)
-    if not target.is_cuda:
-        raise TypeError("target is not a CUDA tensor")
-    if out is None:
-        out = tuple(torch.empty_like(r) for _ in range(4))
-    check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target(C.byref(desc), T, S, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                        _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
-                                                        _ptr(ckpt) if ckpt is not None and ckpt.numel() else None,
-                                                        _ptr(target) if target.numel() else None, _ptr(sse), _ptr(err), _stream()),
-          "dhts_macro_rollout_fwd_ckpt_target")
-    return out, sse
+    return _macro_ckpt_fwd("target", desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out, None, None, target, sse)
 
 
 def macro_rollout_bwd_ckpt_target(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, target, g_sse=None, final=None, segment=0, err=None,
@@ -897,39 +949,7 @@ def macro_rollout_bwd_ckpt_target(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, 
     macro_rollout_bwd_ckpt.  g_sse float64 [L][2] or None (zero: the plain sweep): the cotangent of sse; the per-step cotangent
     (float)(2 g_sse) * (x - target), through the speed's glue, is formed in the kernel.  final: the forward's (r, y, u) after T steps,
     needed with g_sse.  r, y, u, ueq, ghost, target, segment: the forward's."""
-    L, N, T = desc.n_lanes, desc.n_cells, int(T)
-    S = _macro_target_args(desc, T, segment, ckpt, target, True)
-    if g_sse is not None:
-        if tuple(g_sse.shape) != (L, 2) or g_sse.dtype != torch.float64:
-            raise ValueError("g_sse must be a float64 tensor of shape (%d, 2)" % L)
-        if final is None or len(final) != 3 or any(tuple(t.shape) != (L, N) for t in final):
-            raise ValueError("g_sse needs final = the forward's (r, y, u) after T steps, each of shape (%d, %d)" % (L, N))
-    sched, r, y, u, ueq, ghost = _macro_ckpt_args(desc, T, S, ckpt, r, y, u, ueq, ghost)
-    if g_sse is not None:
-        g_sse = g_sse.contiguous()
-        final = tuple(_f32c(t, n) for t, n in zip(final, ("final r", "final y", "final u")))
-    else:
-        final = (None, None, None)
-    g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
-    if tuple(g_r.shape) != (L, N) or tuple(g_y.shape) != (L, N):
-        raise ValueError("g_r and g_y must have shape (%d, %d)" % (L, N))
-    if not target.is_cuda:
-        raise TypeError("target is not a CUDA tensor")
-    if out is None:
-        out = (torch.empty_like(g_r), torch.empty_like(g_y))
-    want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
-    if g_ghost is None:
-        g_ghost = torch.empty(want, dtype=torch.float64, device=g_r.device)         # a schedule's: every row is written
-    elif tuple(g_ghost.shape) != want or g_ghost.dtype != torch.float64 or not g_ghost.is_contiguous():
-        raise ValueError("g_ghost must be a contiguous float64 tensor of shape %s" % (want,))
-    if not sched:
-        g_ghost.zero_()
-    check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target(C.byref(desc), T, S, _ptr(ckpt) if ckpt.numel() else None, _ptr(r), _ptr(y), _ptr(u),
-                                                        _ptr(ueq), _ptr(ghost), int(sched), _ptr(g_r), _ptr(g_y),
-                                                        _ptr(target) if target.numel() else None, _ptr(g_sse), _ptr(final[0]),
-                                                        _ptr(final[1]), _ptr(final[2]), _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err),
-                                                        _stream()), "dhts_macro_rollout_bwd_ckpt_target")
-    return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
+    return _macro_ckpt_bwd("target", desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, None, None, target, g_sse, final, g_ghost)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -1149,11 +1169,6 @@ def _micro_ckpt_plan(entry, forms, desc, T, want_params, segment):
     return dict(zip(_MICRO_CKPT_PLAN_KEYS, list(plan)))
 
 
-def _data(t):
-    """The address the library gets for an optional array: NULL for None and for a tensor without an element (it has no address)."""
-    return None if t is None or not t.numel() else _ptr(t)
-
-
 def _samples_shape(desc, T, probes, every):
     """The raw wrappers' checks of (probes, every) -> (rows, columns, n_probes for the C call).  probes: None (every slot) or a CUDA int32
     tensor of distinct slots, used as it is (include/dhts.h: an entry outside [0, V) is skipped by the kernels)."""
@@ -1168,16 +1183,6 @@ def _samples_shape(desc, T, probes, every):
             or not 1 <= probes.numel() <= V or not probes.is_contiguous()):
         raise ValueError("probes must be None or a contiguous one-dimensional CUDA int32 tensor of 1..%d slots" % V)
     return int(T) // every, int(probes.numel()), int(probes.numel())
-
-
-def _obs_buffer(name, t, shape, device, new=torch.zeros):
-    """An observation array handed in (checked), or one made by `new` (None: none).  Samples are zero-filled: the kernels write live
-    probe slots only."""
-    if t is None:
-        return None if new is None else new(shape, dtype=torch.float32, device=device)
-    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-        raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(shape)))
-    return t
 
 
 def _lead_args(desc, T, lead, lead_length):
@@ -1253,16 +1258,6 @@ def _dir_arg(name, t, dtype, shape):
     """An optional per-direction tangent array: contiguous, of `dtype` and `shape`."""
     if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
         raise ValueError("%s must be a contiguous %s %s" % (name, str(dtype)[6:], "".join("[%d]" % s for s in shape)))
-
-
-def _state_out(names, out, likes):
-    """The state buffers of `out` (checked against the inputs they mirror), or new ones."""
-    if not out:
-        return tuple(torch.empty_like(t) for t in likes)
-    for name, t, like in zip(names, out, likes):
-        if t.shape != like.shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, tuple(like.shape)))
-    return tuple(out[:len(likes)])
 
 
 def _micro_ckpt_fwd(form, desc, T, p, v, params, ckpt, count, segment, err, out, head=None, hist=None, probes=None, every=1, samples=None,

@@ -245,6 +245,27 @@ def test_value_errors_come_before_any_device_use():
         ops.macro_rollout_bwd_ckpt(desc, T, good, z, z, z, z, ghost, z, z, segment=1)
     with pytest.raises(ValueError):
         ops.macro_rollout_bwd_ckpt(desc, T, good, z, z, z, z, ghost, z, z, segment=2, det=torch.zeros(2, dtype=torch.int32))   # det without g_taps
+    # ... in this order, with these texts: the detector pairing, the lane, the buffer, the state, the boundary cells; then the device
+    bad_z, bad_ghost, taps = torch.zeros(L, N + 1), torch.zeros(T + 1, L, 2, 4), torch.zeros(T, L, 3, 2)
+    with pytest.raises(ValueError, match="^taps without det$"):
+        ops.macro_rollout_fwd_ckpt(desc, T, bad_z, z, z, z, ghost, torch.zeros(3), segment=2, taps=taps)
+    for pair in (dict(det=torch.zeros(2, dtype=torch.int32)), dict(g_taps=taps)):
+        with pytest.raises(ValueError, match="^det and g_taps go together$"):
+            ops.macro_rollout_bwd_ckpt(desc, T, torch.zeros(3), bad_z, z, z, z, ghost, z, z, segment=2, **pair)
+    for call in (lambda **kw: ops.macro_rollout_fwd_ckpt(desc, T, kw.get("r", z), z, z, kw.get("q", z), kw.get("ghost", ghost),
+                                                         kw.get("ckpt", good), segment=2),
+                 lambda **kw: ops.macro_rollout_bwd_ckpt(desc, T, kw.get("ckpt", good), kw.get("r", z), z, z, kw.get("q", z),
+                                                         kw.get("ghost", ghost), bad_z, bad_z, segment=2)):
+        with pytest.raises(ValueError, match=r"^ckpt must be a contiguous float32 \[macro_ckpt_numel\(desc, T, segment\)\]$"):
+            call(ckpt=torch.zeros(3), r=bad_z)
+        with pytest.raises(ValueError, match=r"^r must have shape \(2, 8\)$"):
+            call(r=bad_z, q=bad_z, ghost=bad_ghost)
+        with pytest.raises(ValueError, match=r"^ueq must have shape \(2, 8\)$"):
+            call(q=bad_z, ghost=bad_ghost)
+        with pytest.raises(ValueError, match=r"^ghost must have shape \(2, 2, 4\) or, a schedule, \(5, 2, 2, 4\)$"):
+            call(ghost=bad_ghost)
+        with pytest.raises(TypeError, match="^r must be a float32 CUDA tensor"):      # past these ValueErrors: the first thing that wants a device
+            call()
     long = ops.macro_desc(L, MAX_CELLS + 1, 0.01, 5.0, 30.0)
     zl = torch.zeros(L, MAX_CELLS + 1)
     with pytest.raises(ValueError, match="checkpoint=None"):

@@ -178,6 +178,30 @@ def test_value_errors_of_the_operator_are_unchanged_with_fused():
             run(torch.zeros(N), torch.zeros(N), gr, gu, T, 0.01, 5.0, 30.0, t_r0=tr)
         with pytest.raises(TypeError):
             run(r0, u0, gr, gu, T, 0.01, 5.0, 30.0, tr)                 # tangents are keyword-only
+    # the raw wrappers' own, in their order: the state, the boundary cells, the tangents; the readings only behind the device check
+    from dhts import ops
+    desc = ops.macro_desc(L, N, 0.01, 5.0, 30.0)
+    z, ghost, taps = torch.zeros(L, N), torch.zeros(L, 2, 4), torch.zeros(T, L, 3, 2)
+
+    def raw(r=z, q=z, ghost=ghost, t_r=tr, T=T, **kw):
+        return ops.macro_rollout_fwd_jvp(desc, T, r, z, z, q, ghost, t_r, tr, **kw)
+    with pytest.raises(ValueError, match="^T must be >= 0$"):
+        raw(T=-1, r=torch.zeros(L, N + 1))
+    with pytest.raises(ValueError, match=r"^r must have shape \(2, 8\)$"):
+        raw(r=torch.zeros(L, N + 1), q=torch.zeros(L), ghost=torch.zeros(L, 2), taps=taps)
+    with pytest.raises(ValueError, match=r"^ueq must have shape \(2, 8\)$"):
+        raw(q=torch.zeros(L), ghost=torch.zeros(L, 2), taps=taps)
+    with pytest.raises(ValueError, match=r"^ghost must have shape \(2, 2, 4\) or \(5, 2, 2, 4\)$"):
+        raw(ghost=torch.zeros(T + 1, L, 2, 4), t_r=torch.zeros(L, N))
+    for t_r in (torch.zeros(L, N), torch.zeros(0, L, N), torch.zeros(K + 1, L, N)):
+        for call in (lambda: raw(t_r=t_r, taps=taps), lambda: ops.macro_rollout_jvp(desc, T, None, t_r, tr, t_taps=taps)):
+            with pytest.raises(ValueError, match=r"^t_r and t_y must have shape \(K, 2, 8\) with K >= 1$"):
+                call()
+    for call in (lambda: raw(taps=taps), lambda: raw(t_ghost=torch.zeros(K, L, 2)),
+                 lambda: ops.macro_rollout_jvp(desc, T, None, tr, tr, t_taps=taps),
+                 lambda: ops.macro_rollout_jvp(desc, T, None, tr, tr, t_ghost=torch.zeros(K, L, 2))):
+        with pytest.raises(TypeError, match="must be a float32 CUDA tensor"):
+            call()
 
 
 def test_a_lane_that_does_not_fit_is_a_value_error_before_any_device():

@@ -339,6 +339,69 @@ def test_a_lane_that_does_not_fit_is_refused_and_the_taped_path_still_runs(cuda)
     assert tuple(tang[0].shape) == (2, L, N) and bool(torch.isfinite(tang[0]).all()) and float(tang[0].abs().max()) > 0
 
 
+def test_the_raw_tape_free_wrappers_keep_their_errors_texts_and_order(cuda):
+    """What the raw wrappers of the tangent and checkpointed paths raise once their tensors are on the device (nothing is launched):
+    each message word for word, and where two things are wrong the one that is reported."""
+    import re
+    import torch
+    from dhts import ops
+    L, N, T, K = 2, 8, 5, 3
+    desc = ops.macro_desc(L, N, DT, DX, UM)
+    f32 = dict(dtype=torch.float32, device=cuda)
+    z, ghost, tr = torch.zeros(L, N, **f32), torch.zeros(L, 2, 4, **f32), torch.zeros(K, L, N, **f32)
+    det = torch.tensor([0, 7], dtype=torch.int32, device=cuda)
+    many = torch.arange(N + 1, dtype=torch.int32, device=cuda)
+    taps, t_taps, g_taps = torch.zeros(T, L, 3, 2, **f32), torch.zeros(K, T, L, 2, 2, **f32), torch.zeros(T, L, 2, 2, **f32)
+    ckpt = torch.zeros(ops.macro_ckpt_numel(desc, T, 2), **f32)
+    target = torch.zeros(T, L, 2, N, **f32)
+    six = [torch.zeros(L, N, **f32) for _ in range(4)] + [torch.zeros(K, L, N, **f32) for _ in range(2)]
+
+    def raises(kind, text, call):
+        with pytest.raises(kind, match="^" + re.escape(text) + "$"):
+            call()
+
+    def fused(**kw):
+        return ops.macro_rollout_fwd_jvp(desc, T, z, z, z, z, ghost, tr, tr, **kw)
+
+    def swept(**kw):
+        return ops.macro_rollout_jvp(desc, T, kw.pop("tape", z), tr, tr, **kw)
+    bad_tg = torch.zeros(K, T, L, 2, 2, **f32)            # a schedule's tangents beside constant boundary cells
+    raises(ValueError, "t_ghost must have shape (3, 2, 2, 2): it follows the form of ghost", lambda: fused(t_ghost=bad_tg, det=many))
+    raises(ValueError, "det must hold 1..8 cell indices (got 9)", lambda: fused(det=many, out=six[:5]))
+    raises(ValueError, "det must be a one-dimensional int32 CUDA tensor", lambda: fused(det=det.long(), taps=taps[1:]))
+    raises(ValueError, "taps must be a contiguous float32 CUDA tensor of shape (5, 2, 3, 2)", lambda: fused(det=det, taps=taps[1:], t_taps=t_taps[1:]))
+    raises(ValueError, "t_taps must be a contiguous float32 CUDA tensor of shape (3, 5, 2, 2, 2)", lambda: fused(det=det, taps=taps, t_taps=t_taps.double()))
+    for kw in (dict(taps=taps), dict(t_taps=t_taps)):
+        raises(ValueError, "taps / t_taps without det", lambda: fused(out=six[:5], **kw))
+    raises(ValueError, "out must be (r_out, y_out, u_out, ueq_out, t_r_out, t_y_out)", lambda: fused(out=six[:5]))
+    raises(ValueError, "t_r_out must be a contiguous float32 CUDA tensor of shape (3, 2, 8)", lambda: fused(out=six[:4] + [six[0], six[0]]))
+    raises(ValueError, "u_out must be a contiguous float32 CUDA tensor of shape (2, 8)", lambda: fused(out=six[:2] + [six[2].double()] + six[3:]))
+    raises(ValueError, "t_ghost must have shape (3, 2, 2, 2) or (3, 5, 2, 2, 2)", lambda: swept(t_ghost=torch.zeros(K, L, 2, **f32), det=many))
+    raises(ValueError, "det must hold 1..8 cell indices (got 9)", lambda: swept(det=many, tape=None))
+    raises(ValueError, "t_taps must be a contiguous float32 CUDA tensor of shape (3, 5, 2, 2, 2)", lambda: swept(det=det, t_taps=t_taps[:, 1:], tape=None))
+    raises(ValueError, "t_taps without det", lambda: swept(t_taps=t_taps, tape=None))
+    raises(ValueError, "a sweep of T > 0 steps needs the rollout's tape", lambda: swept(tape=None, det=det))
+    # the checkpointed pair and its target forms
+    fwd = lambda **kw: ops.macro_rollout_fwd_ckpt(desc, T, z, z, z, z, ghost, ckpt, segment=2, **kw)      # noqa: E731
+    bwd = lambda g_r=z, **kw: ops.macro_rollout_bwd_ckpt(desc, T, ckpt, z, z, z, z, ghost, g_r, z, segment=2, **kw)      # noqa: E731
+    raises(ValueError, "det must hold 1..8 cell indices (got 9)", lambda: fwd(det=many, taps=taps[1:]))
+    raises(ValueError, "taps must be a contiguous float32 CUDA tensor of shape (5, 2, 3, 2)", lambda: fwd(det=det, taps=taps[1:]))
+    raises(ValueError, "det must be a one-dimensional int32 CUDA tensor", lambda: bwd(det=det.long(), g_taps=g_taps[1:]))
+    raises(ValueError, "g_taps must have shape (5, 2, 2, 2)", lambda: bwd(g_r=tr, det=det, g_taps=g_taps[1:]))
+    raises(ValueError, "g_r and g_y must have shape (2, 8)", lambda: bwd(g_r=tr, det=det, g_taps=g_taps))
+    raises(ValueError, "g_r and g_y must have shape (2, 8)", lambda: bwd(g_r=tr))
+    fit = lambda **kw: ops.macro_rollout_fwd_ckpt_target(desc, T, z, z, z, z, ghost, ckpt, kw.pop("target", target), segment=2, **kw)      # noqa: E731
+    back = lambda g_r=z, **kw: ops.macro_rollout_bwd_ckpt_target(desc, T, ckpt, z, z, z, z, ghost, g_r, z, kw.pop("target", target),      # noqa: E731
+                                                                 segment=2, **kw)
+    raises(ValueError, "sse must be a contiguous float64 CUDA tensor of shape (2, 2)", lambda: fit(sse=torch.zeros(L, 2, **f32), target=target.cpu()))
+    raises(TypeError, "target is not a CUDA tensor", lambda: fit(target=target.cpu()))
+    raises(ValueError, "g_r and g_y must have shape (2, 8)", lambda: back(g_r=tr, target=target.cpu()))
+    raises(TypeError, "target is not a CUDA tensor", lambda: back(target=target.cpu(), g_ghost=torch.zeros(L, 2, **f32)))
+    raises(ValueError, "g_ghost must be a contiguous float64 tensor of shape (2, 2, 2)", lambda: back(g_ghost=torch.zeros(L, 2, **f32)))
+    raises(TypeError, "final u must be a float32 CUDA tensor (got torch.float64 on %s)" % z.device,
+           lambda: back(g_r=tr, g_sse=torch.zeros(L, 2, dtype=torch.float64, device=cuda), final=(z, z, z.double())))
+
+
 # ---- 8. the example ----------------------------------------------------------------------------------------------------------------------
 def test_fit_pulse_fused_writes_the_taped_run_s_trial_file(cuda, tmp_path):
     """Both runs take --seed 1: the example draws the pulse it hides from torch's generator, and two unseeded runs fit different pulses."""

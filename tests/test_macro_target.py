@@ -111,6 +111,8 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.dhts_macro_ckpt_plan(C.byref(ok), 5, 0, 0, C.byref(sib)) == 0
     assert 1 <= plan[3] < sib[3]
     assert bwd(C.byref(ok), 5, plan[3] + 1, *call_args(BWD, some)) == _lib.E_INVALID
+    # ... also without a cotangent of the sums, where the plain sweep (whose own plan would take that segment) does the work
+    assert bwd(C.byref(ok), 5, plan[3] + 1, *call_args(BWD, some, g_sse=None)) == _lib.E_INVALID
     assert fwd(C.byref(ok), 5, plan[3] + 1, *call_args(FWD, some)) == _lib.E_INVALID
     assert lib.dhts_macro_ckpt_target_plan(C.byref(ok), 5, plan[3] + 1, C.byref(sib)) == _lib.E_INVALID
     assert lib.dhts_macro_ckpt_target_plan(C.byref(ok), 5, 0, None) == _lib.E_INVALID

@@ -23,6 +23,8 @@ sys.path.insert(0, ROOT)
 MACRO_CELLS = (1, 63, 64, 65, 127, 128, 129, 256, 512, 1000, 1024, 1025, 1026, 2048, 2500)
 MACRO_LANES = (1, 255, 256, 1024, 1536, 4096)
 MACRO_T = (0, 1, 1000)
+MACRO_JVP_CELLS = (997, 998, 1239, 1240, 1410, 1411)
+MACRO_CKPT_CELLS = (1, 2, 64, 65, 128, 1239, 1240, 1319, 1320, 2048)
 MICRO_CAP = (1, 63, 64, 65, 128, 129, 256, 1023, 1024)
 MICRO_LANES = (1, 4096, 4097)
 MICRO_T = (0, 1, 7, 1000)
@@ -35,6 +37,7 @@ OPTION_VALUES = {
     "OPT_MACRO_FWD_VARIANT": (-1, 0, 1, 2, 3),
     "OPT_MACRO_FWD_GROUP": (-1, 0, 1, 2, 3, 4, 5, 8),
     "OPT_MACRO_FWD_ROTATE": (-1, 0, 1, 2),
+    "OPT_MACRO_JVP_VARIANT": (-1, 0, 1, 2),
     "OPT_NETSTEP_LDS_KB": (-1, 0, 1, 48, 158, 159, 160),
     "OPT_NETSTEP_BLOCK": (-1, 0, 1, 64, 128, 255, 256, 257, 512, 768, 1024, 1025, 2048),
     "OPT_HYB_PACK": (-1, 0, 1, 2, 3),
@@ -96,6 +99,32 @@ def sweep(hybrid):
             for n_dir in MICRO_DIRS:
                 rc = fn(C.byref(d), T, n_dir, want, C.byref(plan))
                 out["%s V%d T%d q%d k%d" % (kind, V, T, want, n_dir)] = [rc] + list(plan)
+    # the tape-free macro paths, the same way: the two tangent plans at the lane lengths where a launch loses directions (997 / 998,
+    # 1239 / 1240, 1410 / 1411), under every forced wave count and both tangent kernels; the two segment plans and the checkpoint bytes
+    # at the lengths where the passes, the target ring and the plain ring change (64 / 65, 1239 / 1240, 1319 / 1320)
+    for waves, general in itertools.product(range(17), (0, 1)):
+        assert opt("OPT_MACRO_FWD_WAVES", waves) == 0 and opt("OPT_MACRO_JVP_VARIANT", general) == 0
+        for N, T, n_dir in itertools.product(MACRO_CELLS + MACRO_JVP_CELLS, MACRO_T, MICRO_DIRS):
+            d = _lib.MacroDesc(4, N, 0.01, 5.0, 30.0)
+            for kind, fn in (("macro_jvp", lib.dhts_macro_jvp_plan), ("macro_fwd_jvp", lib.dhts_macro_fwd_jvp_plan)):
+                for k in range(8):
+                    plan[k] = -7
+                rc = fn(C.byref(d), T, n_dir, 0, C.byref(plan))
+                out["%s w%d j%d N%d T%d k%d" % (kind, waves, general, N, T, n_dir)] = [rc] + list(plan)
+    assert opt("OPT_MACRO_FWD_WAVES", 0) == 0 and opt("OPT_MACRO_JVP_VARIANT", 0) == 0
+    for N, T in itertools.product(MACRO_CKPT_CELLS, MICRO_T):
+        d = _lib.MacroDesc(4, N, 0.01, 5.0, 30.0)
+        for kind, fn in (("macro_ckpt", lambda *a: lib.dhts_macro_ckpt_plan(a[0], a[1], 0, *a[2:])),
+                         ("macro_ckpt_target", lib.dhts_macro_ckpt_target_plan)):
+            assert fn(C.byref(d), T, 0, C.byref(plan)) == 0
+            longest = plan[3]
+            for segment in (0, 1, longest, longest + 1, -1):
+                for k in range(8):
+                    plan[k] = -7
+                rc = fn(C.byref(d), T, segment, C.byref(plan))
+                out["%s N%d T%d s%d" % (kind, N, T, segment)] = [rc] + list(plan)
+                if kind == "macro_ckpt":
+                    out["macro_ckpt_bytes N%d T%d s%d" % (N, T, segment)] = [int(lib.dhts_macro_ckpt_bytes(C.byref(d), T, segment))]
     if hybrid:
         import numpy as np
         import torch
