@@ -31,6 +31,16 @@
 // front of the head, as row t of g_lead [T][L][2] instead of folding it into the head.  A NULL samples / g_samples: nothing is observed.
 // kLead = false is the code the sampled forms were before (profiles/micro_lead_resources*.txt).
 //
+// The boundary is three-valued: the template parameter of the sampled and the target forms is MicroBoundary kB (micro_kernels.hip), and
+// kHeadGap / kLead / kRing below name its values.  kRing (dhts_micro_rollout_fwd_ckpt_ring / _bwd_ckpt_ring and the _target_ring pair): a
+// ring road.  The head follows the image of the lane's own tail one circumference ahead, ((float)((double)p_tail + ring[lane]), v_tail)
+// of the tail's state before the step, by the followers' expressions; half_len of the head is (length[0] + length[head]) / 2.  The
+// TAIL's thread (k == 0) owns slot n of S: row 0 before the first barrier, S[(q ^ 1) P + n] from its new (p, v) beside its own store in
+// every step -- no global load, nothing in flight; the head's thread still records X[r][n] = ls under kParams.  The reverse sweep adds
+// C1[n] to the tail's (np_, nv_) in the same sweep step (the float cast has derivative 1) and nothing to the head; no g_head, no g_lead;
+// g_params[5][0] = -0.5 (A[0] + A[n - 1]).  ring is read once per lane.  kB = kBoundHead / kBoundLead are the code the forms were before
+// (profiles/micro_ring_resources*.txt).
+//
 // A third pass, DHTS_MICRO_SAMPLES 2, gives the TARGET forms (kTarget; dhts_micro_rollout_fwd_ckpt_target / _bwd_ckpt_target),
 // micro_rollout_ckpt_fwd_target_kernel<kLead> / _bwd_target_kernel<kParams, kLead>: the trajectory-fit loss inside the pair.  They
 // take target [T][L][2][V] float32 (hist's indexing: the observed (p, v) after step t; NaN = not observed) where the first pair takes
@@ -81,31 +91,31 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_kernel(
     int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, float *__restrict__ hist, dhts_error *err) {
-    constexpr bool kSamp = false, kLead = false, kTarget = false;
+    constexpr bool kSamp = false, kLead = false, kRing = false, kHeadGap = true, kTarget = false;
     const MicroProbes pr = {};
     float *const samples = nullptr;
     const MicroLead ld = {};
     const float *const target = nullptr;
     double *const sse = nullptr;
 #elif DHTS_MICRO_SAMPLES == 2
-template <bool kLead>
+template <MicroBoundary kB>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_target_kernel(
     int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, const float *__restrict__ target,
     double *__restrict__ sse, dhts_error *err, MicroLead ld) {
-    constexpr bool kSamp = false, kTarget = true;
+    constexpr bool kSamp = false, kTarget = true, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead;
     const MicroProbes pr = {};
     float *const samples = nullptr;
     float *const hist = nullptr;
 #else
-template <bool kLead>
+template <MicroBoundary kB>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     int L, int V, int T, int Sg, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in,
     const int32_t *__restrict__ count, const double *__restrict__ params, const double *__restrict__ head,
     float *__restrict__ p_out, float *__restrict__ v_out, float2 *__restrict__ ckpt, MicroProbes pr, float *__restrict__ samples,
     dhts_error *err, MicroLead ld) {
-    constexpr bool kSamp = true, kTarget = false;
+    constexpr bool kSamp = true, kTarget = false, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead;
     float *const hist = nullptr;
     const float *const target = nullptr;
     double *const sse = nullptr;
@@ -129,14 +139,14 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     if (V > B) {
         const float nanf_ = __builtin_nanf("");
         for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
-        if constexpr (kSamp) { if (!kLead || samples) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_); }
+        if constexpr (kSamp) { if (kHeadGap || samples) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_); }
         if constexpr (kTarget) { if (k == 0) { sse[(size_t)lane * 2] = (double)nanf_; sse[(size_t)lane * 2 + 1] = (double)nanf_; } }
         if (k == 0) raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3);
         return;
     }
 
     float p = p_in[base + kc], v = v_in[base + kc];      // (a slot at or beyond count keeps them: the outputs pass it through)
-    const int col = kSamp ? ((kLead && samples == nullptr) ? -1 : micro_probe_column(pr, k, V)) : -1;     // kLead, no samples: no column
+    const int col = kSamp ? ((!kHeadGap && samples == nullptr) ? -1 : micro_probe_column(pr, k, V)) : -1;     // kLead, kRing, no samples: no column
     IdmDerived prm = {};
     double half_len = 0.;
     if (vk) {
@@ -146,12 +156,13 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
         raw.time_pref = params[4 * plane + base + k]; raw.length = params[5 * plane + base + k];
         prm = idm_derive(raw);
         idm_set_dt(prm, dt);
-        const int kl = k + 1 < n ? k + 1 : k;
+        const int kl = k + 1 < n ? k + 1 : (kRing ? 0 : k);      // kRing: the head's leader is the tail
         half_len = (params[5 * plane + base + kl] + raw.length) * 0.5;
         if constexpr (kLead) { if (is_head && ld.length) half_len = (ld.length[lane] + raw.length) * 0.5; }
     }
-    double head_dp = 0., head_dv = 0.;
-    if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
+    double head_dp = 0., head_dv = 0., ring = 0.;
+    if constexpr (kRing) ring = ld.ring[lane];
+    else if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
 
     for (int i = k; i < 2 * P; i += B) S[i] = make_float2(0.f, 0.f);
     __syncthreads();
@@ -160,6 +171,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
     double ap = 0., av = 0.;           // kTarget: this vehicle's squared residuals, summed in step order
     if (T > 0) {
         if (vk) S[k] = make_float2(p, v);
+        // kRing: the TAIL's thread owns slot n of S -- its own state one circumference ahead, beside every store of its own
+        if constexpr (kRing) { if (vk && k == 0) S[n] = make_float2((float)((double)p + ring), v); }
         // kLead: the head's thread owns slot n of S -- row 0 now, row step + 1 during step `step`, the row after that in flight in (lx, ly)
         const float *lrow = nullptr;
         float lx = 0.f, ly = 0.f;
@@ -204,13 +217,14 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_fwd_samples_kernel(
                 const float2 ls = S[q * P + k + 1];      // the leader's state before this step
                 const double pd = p, vd = v;
                 // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
-                const double dp = (!kLead && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
-                const double dv = (!kLead && is_head) ? head_dv : vd - (double)ls.y;
+                const double dp = (kHeadGap && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
+                const double dv = (kHeadGap && is_head) ? head_dv : vd - (double)ls.y;
                 IdmStep o;
                 idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
                 if (o.collided && fault_step < 0) fault_step = step;
                 p = o.np; v = o.nv;
                 S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
+                if constexpr (kRing) { if (k == 0) S[(q ^ 1) * P + n] = make_float2((float)((double)p + ring), v); }
                 if constexpr (kLead) {
                     if (is_head && step + 1 < T) {
                         S[(q ^ 1) * P + n] = make_float2(lx, ly);      // ... and what its leader is seen at in step + 1
@@ -275,31 +289,31 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_kernel(
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, const float *__restrict__ g_hist, float *__restrict__ g_p_out, float *__restrict__ g_v_out,
     double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err) {
-    constexpr bool kSamp = false, kLead = false, kTarget = false;
+    constexpr bool kSamp = false, kLead = false, kRing = false, kHeadGap = true, kTarget = false;
     const MicroProbes pr = {};
     const float *const g_samples = nullptr;
     const MicroLead ld = {};
     const float *const target = nullptr;
     const double *const g_sse = nullptr;
 #elif DHTS_MICRO_SAMPLES == 2
-template <bool kParams, bool kLead>
+template <bool kParams, MicroBoundary kB>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_target_kernel(
     int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, const float *__restrict__ target, const double *__restrict__ g_sse, float *__restrict__ g_p_out,
     float *__restrict__ g_v_out, double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err, MicroLead ld) {
-    constexpr bool kSamp = false, kTarget = true;
+    constexpr bool kSamp = false, kTarget = true, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead;
     const MicroProbes pr = {};
     const float *const g_samples = nullptr;
     const float *const g_hist = nullptr;
 #else
-template <bool kParams, bool kLead>
+template <bool kParams, MicroBoundary kB>
 __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
     int L, int V, int T, int Sg, double dt, const float2 *__restrict__ ckpt, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ g_p_in,
     const float *__restrict__ g_v_in, MicroProbes pr, const float *__restrict__ g_samples, float *__restrict__ g_p_out,
     float *__restrict__ g_v_out, double *__restrict__ g_head, double *__restrict__ g_params, dhts_error *err, MicroLead ld) {
-    constexpr bool kSamp = true, kTarget = false;
+    constexpr bool kSamp = true, kTarget = false, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead;
     const float *const g_hist = nullptr;
     const float *const target = nullptr;
     const double *const g_sse = nullptr;
@@ -353,11 +367,12 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
         prm = idm_derive(raw);
         idm_set_dt(prm, dt);
         if constexpr (kParams) pm = idm_param_derive(raw);
-        half_len = (params[5 * plane + base + (k + 1 < n ? k + 1 : k)] + raw.length) * 0.5;
+        half_len = (params[5 * plane + base + (k + 1 < n ? k + 1 : (kRing ? 0 : k))] + raw.length) * 0.5;
         if constexpr (kLead) { if (is_head && ld.length) half_len = (ld.length[lane] + raw.length) * 0.5; }
     }
-    double head_dp = 0., head_dv = 0.;
-    if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
+    double head_dp = 0., head_dv = 0., ring = 0.;
+    if constexpr (kRing) ring = ld.ring[lane];
+    else if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
     __syncthreads();
 
     double gh_p = 0., gh_v = 0.;       // held by the thread that owns the head vehicle
@@ -383,7 +398,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
         if constexpr (kSamp) {
             const int col = micro_probe_column(pr, k, V);
             const int rows = T / pr.every;
-            probe = vk && col >= 0 && (!kLead || g_samples != nullptr);      // kLead, no g_samples: nothing was observed
+            probe = vk && col >= 0 && (kHeadGap || g_samples != nullptr);      // kLead, kRing, no g_samples: nothing was observed
             cd = T - rows * pr.every;
             if (probe && rows > 0) {
                 gs = g_samples + (size_t)(rows - 1) * s_row + (size_t)lane * 2 * pr.n + col;
@@ -413,6 +428,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
             ck = ck0[(size_t)(c > 0 ? c - 1 : 0) * row];         // the checkpoint before: in flight across the whole segment
             // ---- replay steps [s0, s1) into the ring ----
             if (vk) S[k] = make_float2(p, v);
+            if constexpr (kRing) { if (vk && k == 0) S[n] = make_float2((float)((double)p + ring), v); }      // the tail, one circumference ahead
             if constexpr (kLead) {
                 if (is_head) {
                     S[n] = make_float2(l0x, l0y);
@@ -437,8 +453,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                     const float2 ls = S[q * P1 + k + 1];
                     const double pd = p, vd = v;
                     // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
-                    const double dp = (!kLead && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
-                    const double dv = (!kLead && is_head) ? head_dv : vd - (double)ls.y;
+                    const double dp = (kHeadGap && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
+                    const double dv = (kHeadGap && is_head) ? head_dv : vd - (double)ls.y;
                     IdmStep o;
                     idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
                     float *e = R + (size_t)r * kPlanes * V + k;
@@ -446,6 +462,10 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                     if constexpr (kParams) X[(size_t)r * P1 + k] = make_float2(p, v);
                     p = o.np; v = o.nv;
                     S[(q ^ 1) * P1 + k] = make_float2(p, v);
+                    if constexpr (kRing) {
+                        if (k == 0) S[(q ^ 1) * P1 + n] = make_float2((float)((double)p + ring), v);
+                        if constexpr (kParams) { if (is_head) X[(size_t)r * P1 + n] = ls; }      // the image the head saw in this step
+                    }
                     if constexpr (kTarget) {
                         // the finished cotangent pair of this step: 2 g (hist - observed), the forward's float32 residual
                         e[3 * V] = (tcp == tcp) ? g2p * (p - tcp) : 0.f;
@@ -505,9 +525,9 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                         // compute_state_delta and the collision / clamp rules of the forward, _micro_lane.py:149-166, 201-212
                         const float2 xl = X[(size_t)r * P1 + k + 1];
                         const double pv = cx.y;
-                        double gap = (!kLead && is_head) ? head_dp : fabs((double)xl.x - (double)cx.x) - half_len;
-                        double dv = (!kLead && is_head) ? head_dv : pv - (double)xl.y;
-                        const bool live_gap = (kLead || !is_head) && gap >= 1e-5;       // else a constant: nothing flows to the lengths
+                        double gap = (kHeadGap && is_head) ? head_dp : fabs((double)xl.x - (double)cx.x) - half_len;
+                        double dv = (kHeadGap && is_head) ? head_dv : pv - (double)xl.y;
+                        const bool live_gap = (!kHeadGap || !is_head) && gap >= 1e-5;       // else a constant: nothing flows to the lengths
                         if (gap < 0) { gap = 0; dv = 0; }
                         gap = (1e-5 > gap) ? 1e-5 : gap;
                         if (!(e.e2 == 0.f && e.e3 == 0.f && e.l3 == 0.f)) {  // (the forward's acceleration clip zeroes all three)
@@ -526,6 +546,9 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
                     if constexpr (kLead) {
                         // the prescribed leader's cotangent C1[n] is this step's row of g_lead: nothing returns to the head
                         if (is_head) { float *gl = ld.g_lead + ((size_t)step * L + lane) * 2; gl[0] = C1p[n]; gl[1] = C1v[n]; }
+                    } else if constexpr (kRing) {
+                        // the image is the tail's own state (the float cast has derivative 1): C1[n] returns to the tail, nothing to the head
+                        if (k == 0) { np_ += C1p[n]; nv_ += C1v[n]; }
                     } else if (is_head) {
                         // virtual leader = (p_head + head_dp, v_head - head_dv): its cotangent C1[n] returns to the head
                         const float vp = C1p[n], vv = C1v[n];
@@ -554,7 +577,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_ckpt_bwd_samples_kernel(
         if (k < V) {
 #pragma unroll
             for (int q = 0; q < 5; ++q) g_params[q * plane + base + k] = vk ? sum[q] : 0.;
-            g_params[5 * plane + base + k] = vk ? -0.5 * (A[k] + (k > 0 ? A[k - 1] : 0.)) : 0.;
+            // (kRing: the tail is the head's leader, its length is in the head's gap as well)
+            g_params[5 * plane + base + k] = vk ? -0.5 * (A[k] + (k > 0 ? A[k - 1] : (kRing ? A[n - 1] : 0.))) : 0.;
         }
     }
     if (g_head) {

@@ -29,6 +29,14 @@
 // n of S and of TN: it writes row t + 1 there during step t, the row after that in flight in registers.  The head's length tangent
 // carries its own share of the gap only, -t_len / 2.  NULL samples and t_samples (both): nothing is observed.  kLead = false is the
 // code the sampled form was before (profiles/micro_lead_resources*.txt).
+//
+// The boundary is three-valued: the template parameter of the sampled form is MicroBoundary kB (micro_kernels.hip), and kHeadGap / kLead /
+// kRing below name its values.  kRing (dhts_micro_rollout_fwd_jvp_ring): a ring road -- the head follows the image of the lane's own
+// tail one circumference ahead, ((float)((double)p_tail + ring[lane]), v_tail), whose tangents are the tail's state tangents before the
+// step.  The TAIL's thread (k == 0) owns slot n of S and of TN: it writes them beside its own stores, before the first barrier and in
+// every step; nothing is loaded.  virtual_leader is not called and TH stays zero; the head's length tangent is
+// -(t_len[tail] + t_len[head]) / 2, the followers' expression with the tail as its leader.  kB = kBoundHead / kBoundLead are the code
+// the form was before (profiles/micro_ring_resources*.txt).
 
 #if !DHTS_MICRO_SAMPLES
 __host__ __device__ inline size_t micro_fwd_jvp_lds_bytes(int V, int kK) {
@@ -58,19 +66,19 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
     const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
     float *__restrict__ hist, float *__restrict__ t_hist, dhts_error *err, dhts_error *err_jvp) {
-    constexpr bool kSamp = false, kLead = false;
+    constexpr bool kSamp = false, kLead = false, kRing = false, kHeadGap = true;
     const MicroProbes pr = {};
     float *const samples = nullptr, *const t_samples = nullptr;
     const MicroLead ld = {};
 #else
-template <int kK, bool kParams, bool kLead>
+template <int kK, bool kParams, MicroBoundary kB>
 __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
     int L, int V, int T, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
     const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ t_p_in,
     const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
     MicroProbes pr, float *__restrict__ samples, float *__restrict__ t_samples, dhts_error *err, dhts_error *err_jvp, MicroLead ld) {
-    constexpr bool kSamp = true;
+    constexpr bool kSamp = true, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead;
     float *const hist = nullptr, *const t_hist = nullptr;
 #endif
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -107,7 +115,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         if constexpr (kSamp) {
             if (samples) micro_samples_fill(samples, pr, T, L, lane, k, B, nanf_);
             for (int d = 0; d < n_act; ++d)
-                if (!kLead || t_samples) micro_samples_fill(t_samples + (size_t)d * (T / pr.every) * L * 2 * pr.n, pr, T, L, lane, k, B, nanf_);
+                if (kHeadGap || t_samples) micro_samples_fill(t_samples + (size_t)d * (T / pr.every) * L * 2 * pr.n, pr, T, L, lane, k, B, nanf_);
         }
         if (k == 0) { raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3); raise_fault(err_jvp, DHTS_FAULT_CAPACITY, 0, lane, -3); }
         return;
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         raw.time_pref = params[4 * plane + base + k]; raw.length = params[5 * plane + base + k];
         prm = idm_derive(raw);
         idm_set_dt(prm, dt);
-        const int kl = k + 1 < n ? k + 1 : k;
+        const int kl = k + 1 < n ? k + 1 : (kRing ? 0 : k);      // kRing: the head's leader is the tail, its length tangent is live
         half_len = (params[5 * plane + base + kl] + raw.length) * 0.5;
         if constexpr (kLead) { if (is_head && ld.length) half_len = (ld.length[lane] + raw.length) * 0.5; }
         if constexpr (kParams) {
@@ -156,11 +164,12 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
             }
         }
     }
-    double head_dp = 0., head_dv = 0.;
-    if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
+    double head_dp = 0., head_dv = 0., ring = 0.;
+    if constexpr (kRing) ring = ld.ring[lane];
+    else if constexpr (!kLead) { head_dp = head[(size_t)lane * 2]; head_dv = head[(size_t)lane * 2 + 1]; }
 
     for (int i = k; i < (2 + 2 * kK) * P; i += B) S[i] = make_float2(0.f, 0.f);
-    if constexpr (kLead) { if (k < 2 * kK) TH[k] = 0.; }
+    if constexpr (!kHeadGap) { if (k < 2 * kK) TH[k] = 0.; }
     else if (k < 2 * kK) TH[k] = ((k >> 1) < n_act && t_head) ? t_head[((size_t)(k >> 1) * L + lane) * 2 + (k & 1)] : 0.;
     __syncthreads();
 
@@ -179,8 +188,11 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
 #pragma unroll
             for (int d = 0; d < kK; ++d) {
                 TN[d * P + k] = make_float2(tp[d], tv[d]);
-                if constexpr (!kLead) { if (is_head) TN[d * P + k + 1] = virtual_leader(tp[d], tv[d], TH[2 * d], TH[2 * d + 1]); }
+                if constexpr (kHeadGap) { if (is_head) TN[d * P + k + 1] = virtual_leader(tp[d], tv[d], TH[2 * d], TH[2 * d + 1]); }
+                if constexpr (kRing) { if (k == 0) TN[d * P + n] = make_float2(tp[d], tv[d]); }
             }
+            // kRing: the TAIL's thread owns slot n of S and of TN -- its own state one circumference ahead and its own tangents
+            if constexpr (kRing) { if (k == 0) S[n] = make_float2((float)((double)p + ring), v); }
             if constexpr (kLead) {
                 if (is_head) {
                     lrow = micro_lead_row(ld.lead, lane);
@@ -209,7 +221,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         int col = -1, cd = 0;
         size_t so = 0, s_dir = 0;
         if constexpr (kSamp) {
-            col = (kLead && t_samples == nullptr) ? -1 : micro_probe_column(pr, k, V);      // kLead, no sample arrays: no column
+            col = (!kHeadGap && t_samples == nullptr) ? -1 : micro_probe_column(pr, k, V);      // kLead, kRing, no sample arrays: no column
             cd = pr.every;
             s_dir = (size_t)(T / pr.every) * L * 2 * pr.n;
             so = (size_t)lane * 2 * pr.n + (col < 0 ? 0 : col);
@@ -222,8 +234,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                 const float2 ls = S[q * P + k + 1];      // the leader's state before this step
                 const double pd = p, vd = v;
                 // compute_state_delta, _micro_lane.py:201-212, in the forward kernel's expressions
-                const double dp = (!kLead && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
-                const double dv = (!kLead && is_head) ? head_dv : vd - (double)ls.y;
+                const double dp = (kHeadGap && is_head) ? head_dp : fabs((double)ls.x - pd) - half_len;
+                const double dv = (kHeadGap && is_head) ? head_dv : vd - (double)ls.y;
                 IdmStep o;
                 idm_step(pd, vd, dp, dv, prm, dt, inv_dt, o);
                 if (o.collided && fault_step < 0) fault_step = step;
@@ -235,7 +247,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                 bool has_x = false, live_gap = false;
                 if constexpr (kParams) {
                     double gap = dp, dvx = dv;
-                    live_gap = (kLead || !is_head) && gap >= 1e-5;      // else a constant: nothing flows to the lengths
+                    live_gap = (!kHeadGap || !is_head) && gap >= 1e-5;      // else a constant: nothing flows to the lengths
                     if (gap < 0) { gap = 0; dvx = 0; }
                     gap = (1e-5 > gap) ? 1e-5 : gap;
                     has_x = !(c.e2 == 0.f && c.e3 == 0.f && c.l3 == 0.f);      // (the forward's acceleration clip zeroes all three)
@@ -259,12 +271,14 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                     jvp_vehicle(c, dtf, tp[d], tv[d], tl.x, tl.y, x, np_, nv_);
                     tp[d] = np_; tv[d] = nv_;
                     TN[((q ^ 1) * kK + d) * P + k] = make_float2(np_, nv_);
-                    if constexpr (!kLead) { if (is_head) TN[((q ^ 1) * kK + d) * P + k + 1] = virtual_leader(np_, nv_, TH[2 * d], TH[2 * d + 1]); }
+                    if constexpr (kHeadGap) { if (is_head) TN[((q ^ 1) * kK + d) * P + k + 1] = virtual_leader(np_, nv_, TH[2 * d], TH[2 * d + 1]); }
+                    if constexpr (kRing) { if (k == 0) TN[((q ^ 1) * kK + d) * P + n] = make_float2(np_, nv_); }
                     fin = fin && isfinite(np_) && isfinite(nv_);
                 }
                 if (bad_step < 0 && !fin) bad_step = step;
                 p = o.np; v = o.nv;
                 S[(q ^ 1) * P + k] = make_float2(p, v);      // what this vehicle enters step + 1 with
+                if constexpr (kRing) { if (k == 0) S[(q ^ 1) * P + n] = make_float2((float)((double)p + ring), v); }
                 if constexpr (kLead) {
                     if (is_head && step + 1 < T) {           // ... and what its leader is seen at in step + 1, with its tangents
                         S[(q ^ 1) * P + n] = make_float2(lx, ly);

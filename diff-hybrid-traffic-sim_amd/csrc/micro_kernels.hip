@@ -18,6 +18,8 @@
 //   writing and reading probe samples [T / every][L][2][P] in place of a [T][L][2][V] history -- the same two files, included again.
 // Recorded leader (the kLead = true instantiations of the three sampled kernels): the head vehicle follows lead [T][L][2], a vehicle
 //   given per step, instead of a constant head gap; its cotangent per step is g_lead, its tangents t_lead.
+// Ring road (the kBoundRing instantiations of the same kernels and of the two target kernels): the head follows the lane's own tail
+//   one circumference ahead; the image's cotangent returns to the tail, its tangents are the tail's.
 //
 // Reference: road/lane/_micro_lane.py:131-214, road/lane/dmicro_lane.py:87-127 and :271-298.
 #include <hip/hip_runtime.h>
@@ -529,7 +531,13 @@ struct MicroLead {
     const double *length;    // [L] the leader's length, or NULL: the head's own
     float *g_lead;           // reverse sweep: [T][L][2], every row written
     const float *t_lead;     // fused JVP: [kK][T][L][2] of this launch's directions, or NULL: zero
+    const double *ring;      // kBoundRing: [L] the circumference of each lane's ring; the four above are then unused
 };
+// What the head vehicle (slot count - 1) follows, a template parameter of the three sampled and the two target kernels: the constant
+// head gap, the recorded leader above, or -- the ring road, dhts_micro_rollout_*_ring -- the image of the lane's own tail (slot 0) one
+// circumference ahead: slot n of S holds ((float)((double)p_tail + ring[lane]), v_tail), written by the TAIL's thread beside its own
+// store, and the head is an ordinary follower of it (include/dhts.h).  Positions stay unwrapped.
+enum MicroBoundary { kBoundHead = 0, kBoundLead = 1, kBoundRing = 2 };
 // This lane's entry of row 0 of a [T][L][2] array, for the ONE thread that walks the rows (the head vehicle's).  The address is the
 // same for a whole workgroup, so without the opaque zero the rows would be read by scalar loads, which the step's LDS-only wait
 // (lgkmcnt) also waits for; from a vector register they are vector loads and stay in flight across it, as g_hist rows do.
@@ -729,30 +737,42 @@ static int micro_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const fl
     (const void *)micro_rollout_fwd_jvp_kernel<4, false>,
     (const void *)micro_rollout_ckpt_bwd_kernel<true>,
     (const void *)micro_rollout_ckpt_bwd_kernel<false>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, true, true>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, true, false>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, false, true>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, false, false>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, true, true>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, true, false>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, true>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, false>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, true>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, false>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, true>,
-    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, false>,
-    (const void *)micro_rollout_ckpt_fwd_samples_kernel<true>,
-    (const void *)micro_rollout_ckpt_fwd_samples_kernel<false>,
-    (const void *)micro_rollout_ckpt_bwd_samples_kernel<true, true>,
-    (const void *)micro_rollout_ckpt_bwd_samples_kernel<true, false>,
-    (const void *)micro_rollout_ckpt_bwd_samples_kernel<false, true>,
-    (const void *)micro_rollout_ckpt_bwd_samples_kernel<false, false>,
-    (const void *)micro_rollout_ckpt_fwd_target_kernel<true>,
-    (const void *)micro_rollout_ckpt_fwd_target_kernel<false>,
-    (const void *)micro_rollout_ckpt_bwd_target_kernel<true, true>,
-    (const void *)micro_rollout_ckpt_bwd_target_kernel<true, false>,
-    (const void *)micro_rollout_ckpt_bwd_target_kernel<false, true>,
-    (const void *)micro_rollout_ckpt_bwd_target_kernel<false, false>};
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, true, kBoundLead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, true, kBoundHead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, false, kBoundLead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, false, kBoundHead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, true, kBoundLead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, true, kBoundHead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, kBoundLead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, kBoundHead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, kBoundLead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, kBoundHead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, kBoundLead>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, kBoundHead>,
+    (const void *)micro_rollout_ckpt_fwd_samples_kernel<kBoundLead>,
+    (const void *)micro_rollout_ckpt_fwd_samples_kernel<kBoundHead>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<true, kBoundLead>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<true, kBoundHead>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<false, kBoundLead>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<false, kBoundHead>,
+    (const void *)micro_rollout_ckpt_fwd_target_kernel<kBoundLead>,
+    (const void *)micro_rollout_ckpt_fwd_target_kernel<kBoundHead>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<true, kBoundLead>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<true, kBoundHead>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<false, kBoundLead>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<false, kBoundHead>,
+    (const void *)micro_rollout_ckpt_fwd_samples_kernel<kBoundRing>,
+    (const void *)micro_rollout_ckpt_fwd_target_kernel<kBoundRing>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<true, kBoundRing>,
+    (const void *)micro_rollout_ckpt_bwd_samples_kernel<false, kBoundRing>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<true, kBoundRing>,
+    (const void *)micro_rollout_ckpt_bwd_target_kernel<false, kBoundRing>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, true, kBoundRing>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<1, false, kBoundRing>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, true, kBoundRing>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, kBoundRing>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, kBoundRing>,
+    (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, kBoundRing>};
 // ---- the tape-free paths: the fused forward + tangent kernel and the checkpointed pair, every form through three launches ----------
 // The form a call runs in, host only (unpacked into the kernels' parameter lists at the launch): what it observes -- the dense
 // history, probe samples or the fit to a target -- with the arrays of that kind, and the recorded leader where the head follows one.
@@ -766,8 +786,10 @@ struct MicroForm {
     const float *target;     // kObserveTarget, both directions
     double *sse;             // ... forward
     const double *g_sse;     // ... reverse
-    const MicroLead *lead;   // or NULL: the constant head gap
+    const MicroLead *lead;   // the recorded leader, or (with its `ring` set) the ring road; NULL: the constant head gap
 };
+// which of the three the form's head vehicle follows
+static int micro_form_boundary(const MicroForm &f) { return !f.lead ? kBoundHead : (f.lead->ring ? kBoundRing : kBoundLead); }
 static MicroForm micro_form_hist(float *hist, float *t_hist, const float *g_hist) {
     MicroForm f = {};
     f.kind = kObserveHist; f.obs = hist; f.t_obs = t_hist; f.g_obs = g_hist;
@@ -829,8 +851,8 @@ static int micro_fwd_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, cons
                                 t_p_out + k0 * dir_state, t_v_out + k0 * dir_state, observed...);
             };
             if (!samp) go(micro_rollout_fwd_jvp_kernel<kK, kParams>, obs, t_obs, err_fwd, err_jvp);
-            else pick<0, 1>(f.lead != nullptr, [&](auto lv) {
-                go(micro_rollout_fwd_jvp_samples_kernel<kK, kParams, decltype(lv)::value != 0>, f.pr, obs, t_obs, err_fwd, err_jvp, ld);
+            else pick<0, 1, 2>(micro_form_boundary(f), [&](auto bv) {
+                go(micro_rollout_fwd_jvp_samples_kernel<kK, kParams, (MicroBoundary) decltype(bv)::value>, f.pr, obs, t_obs, err_fwd, err_jvp, ld);
             });
         });
         return ok;
@@ -853,10 +875,10 @@ static int micro_ckpt_fwd_launch(const dhts_micro_desc *d, int T, int segment, c
                         head, p_out, v_out, (float2 *)ckpt, observed...);
     };
     if (f.kind == kObserveHist) go(micro_rollout_ckpt_fwd_kernel, f.obs, err);
-    else pick<0, 1>(f.lead != nullptr, [&](auto lv) {
-        constexpr bool kLead = decltype(lv)::value != 0;
-        if (f.kind == kObserveSamples) go(micro_rollout_ckpt_fwd_samples_kernel<kLead>, f.pr, f.obs, err, ld);
-        else go(micro_rollout_ckpt_fwd_target_kernel<kLead>, f.target, f.sse, err, ld);
+    else pick<0, 1, 2>(micro_form_boundary(f), [&](auto bv) {
+        constexpr MicroBoundary kB = (MicroBoundary) decltype(bv)::value;
+        if (f.kind == kObserveSamples) go(micro_rollout_ckpt_fwd_samples_kernel<kB>, f.pr, f.obs, err, ld);
+        else go(micro_rollout_ckpt_fwd_target_kernel<kB>, f.target, f.sse, err, ld);
     });
     return ok ? launch_status() : DHTS_E_LAUNCH;
 }
@@ -877,13 +899,13 @@ static int micro_ckpt_bwd_launch(const dhts_micro_desc *d, int T, int segment, c
         if (f.kind == kObserveHist)
             ok = launch_lds(micro_rollout_ckpt_bwd_kernel<kParams>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S, d->dt, ck, count,
                             params, head, g_p, g_v, f.g_obs, g_p_out, g_v_out, g_head, g_params, err);
-        else pick<0, 1>(f.lead != nullptr, [&](auto lv) {
-            constexpr bool kLead = decltype(lv)::value != 0;
+        else pick<0, 1, 2>(micro_form_boundary(f), [&](auto bv) {
+            constexpr MicroBoundary kB = (MicroBoundary) decltype(bv)::value;
             if (f.kind == kObserveSamples)
-                ok = launch_lds(micro_rollout_ckpt_bwd_samples_kernel<kParams, kLead>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S,
+                ok = launch_lds(micro_rollout_ckpt_bwd_samples_kernel<kParams, kB>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S,
                                 d->dt, ck, count, params, head, g_p, g_v, f.pr, f.g_obs, g_p_out, g_v_out, g_head, g_params, err, ld);
             else
-                ok = launch_lds(micro_rollout_ckpt_bwd_target_kernel<kParams, kLead>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S,
+                ok = launch_lds(micro_rollout_ckpt_bwd_target_kernel<kParams, kB>, L, pl.ckpt_block, lds, kLdsDefault, stream, L, V, T, S,
                                 d->dt, ck, count, params, head, g_p, g_v, f.target, f.g_sse, g_p_out, g_v_out, g_head, g_params, err, ld);
         });
     });
@@ -1130,6 +1152,59 @@ int dhts_micro_rollout_fwd_jvp_lead(const dhts_micro_desc *d, int T, int n_dir, 
     const MicroLead ld = {lead, lead_length, nullptr, t_lead};
     return micro_fwd_jvp_launch(d, T, n_dir, p, v, count, params, nullptr, t_p, t_v, nullptr, t_params, p_out, v_out, t_p_out, t_v_out,
                                 micro_form_samples(pr, samples, t_samples, nullptr, &ld), err, err_jvp, stream);
+}
+// ---- a ring road on the two tape-free paths: the kBoundRing forms of the three sampled and the two target kernels ------------------------
+// (ring is read by the kernels once per lane; head, lead and every cotangent or tangent of them do not exist)
+int dhts_micro_rollout_fwd_ckpt_ring(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                     const double *params, const double *ring, float *p_out, float *v_out, void *ckpt,
+                                     const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err, void *stream) {
+    MicroProbes pr;
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !ring || !micro_probes_ok(d, probes, n_probes, every, &pr))
+        return DHTS_E_INVALID;
+    const MicroLead ld = {nullptr, nullptr, nullptr, nullptr, ring};
+    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, nullptr, p_out, v_out, ckpt,
+                                 micro_form_samples(pr, samples, nullptr, nullptr, &ld), err, stream);
+}
+int dhts_micro_rollout_bwd_ckpt_ring(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                     const double *params, const double *ring, const float *g_p, const float *g_v, const int32_t *probes,
+                                     int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out, double *g_params,
+                                     dhts_error *err, void *stream) {
+    MicroProbes pr;
+    if (!micro_bwd_args_ok(d, T, params, g_p, g_v, g_p_out, g_v_out) || (T > 0 && !ckpt) || !ring ||
+        !micro_probes_ok(d, probes, n_probes, every, &pr))
+        return DHTS_E_INVALID;
+    const MicroLead ld = {nullptr, nullptr, nullptr, nullptr, ring};
+    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, nullptr, g_p, g_v, g_p_out, g_v_out, nullptr, g_params,
+                                 micro_form_samples(pr, nullptr, nullptr, g_samples, &ld), err, stream);
+}
+int dhts_micro_rollout_fwd_jvp_ring(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                    const double *params, const double *ring, const float *t_p, const float *t_v, const double *t_params,
+                                    float *p_out, float *v_out, float *t_p_out, float *t_v_out, const int32_t *probes, int n_probes,
+                                    int every, float *samples, float *t_samples, dhts_error *err, dhts_error *err_jvp, void *stream) {
+    MicroProbes pr;
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !micro_tangent_args_ok(n_dir, t_p, t_v, t_p_out, t_v_out) || !ring ||
+        !micro_probes_ok(d, probes, n_probes, every, &pr) || (samples == nullptr) != (t_samples == nullptr))
+        return DHTS_E_INVALID;
+    const MicroLead ld = {nullptr, nullptr, nullptr, nullptr, ring};
+    return micro_fwd_jvp_launch(d, T, n_dir, p, v, count, params, nullptr, t_p, t_v, nullptr, t_params, p_out, v_out, t_p_out, t_v_out,
+                                micro_form_samples(pr, samples, t_samples, nullptr, &ld), err, err_jvp, stream);
+}
+int dhts_micro_rollout_fwd_ckpt_target_ring(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v,
+                                            const int32_t *count, const double *params, const double *ring, float *p_out, float *v_out,
+                                            void *ckpt, const float *target, double *sse, dhts_error *err, void *stream) {
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !ring || (T > 0 && !target) || !sse) return DHTS_E_INVALID;
+    const MicroLead ld = {nullptr, nullptr, nullptr, nullptr, ring};
+    return micro_ckpt_fwd_launch(d, T, segment, p, v, count, params, nullptr, p_out, v_out, ckpt, micro_form_target(target, sse, nullptr, &ld),
+                                 err, stream);
+}
+int dhts_micro_rollout_bwd_ckpt_target_ring(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                            const double *params, const double *ring, const float *g_p, const float *g_v,
+                                            const float *target, const double *g_sse, float *g_p_out, float *g_v_out, double *g_params,
+                                            dhts_error *err, void *stream) {
+    if (!micro_bwd_args_ok(d, T, params, g_p, g_v, g_p_out, g_v_out) || (T > 0 && (!ckpt || !target)) || !ring) return DHTS_E_INVALID;
+    const MicroLead ld = {nullptr, nullptr, nullptr, nullptr, ring};
+    return micro_ckpt_bwd_launch(d, T, segment, ckpt, count, params, nullptr, g_p, g_v, g_p_out, g_v_out, nullptr, g_params,
+                                 micro_form_target(target, nullptr, g_sse, &ld), err, stream);
 }
 // the single-step operator keeps the reference's dqs[a][2][2][2] (32 B per vehicle)
 int dhts_micro_step_fwd(const dhts_micro_desc *d,

@@ -138,7 +138,7 @@ def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head, t_lead=None, T=0):
 
 
 def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_params=None, t_head=None, count=None, want_hist=False,
-                      check_faults=True, fused=False, probes=None, every=1, lead=None, lead_length=None, t_lead=None):
+                      check_faults=True, fused=False, probes=None, every=1, lead=None, lead_length=None, t_lead=None, ring=None):
     """dhts.micro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((pT, vT[, hist]), (t_pT, t_vT[, t_hist])).  The primal outputs are those of dhts.micro_rollout(p0, v0, params, head, T, dt,
@@ -160,8 +160,17 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
     lead / lead_length / t_lead: as dhts.micro_rollout's `lead` (the head vehicle follows a recorded leader; `head` and t_head must be
     None), with t_lead float32 [K][T][L][2] the leader's tangents per direction (None: zero).  It lives on the fused path only:
     fused=True is required, want_hist is not accepted; t_lead without lead, or t_head together with lead, is a ValueError.  Without
-    probes / every the call returns ((pT, vT), (t_pT, t_vT))."""
+    probes / every the call returns ((pT, vT), (t_pT, t_vT)).
+
+    ring: as dhts.micro_rollout's `ring` (float64 [L]; the head vehicle follows the image of the tail one circumference ahead, whose
+    tangents are the tail's; the tail's length tangent is in the head's gap).  It lives on the fused path only: fused=True is required,
+    want_hist is not accepted, and head, t_head, lead (with lead_length) and t_lead must be None.  probes / every combine with it."""
     T = int(T)
+    if ring is not None:
+        if lead is not None or lead_length is not None or t_lead is not None:
+            raise ValueError("lead, lead_length and t_lead must be None when ring is given: the head vehicle follows the tail")
+        return _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t_head, count, want_hist, check_faults, fused,
+                                       probes, every, None, None, None, ring)
     if lead is None and (t_lead is not None or lead_length is not None):
         raise ValueError("t_lead and lead_length need lead")
     if lead is not None:
@@ -232,19 +241,23 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
 
 
 def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t_head, count, want_hist, check_faults, fused, probes, every,
-                            lead, lead_length, t_lead):
-    """dhts.micro_rollout_jvp with a recorded leader: every ValueError first, then the kLead form of the fused kernel."""
+                            lead, lead_length, t_lead, ring=None):
+    """dhts.micro_rollout_jvp with a recorded leader, or (ring given, lead None) on a ring road: every ValueError first, then the lead
+    or the ring form of the fused kernel."""
+    what, follows = ("lead", "`lead`") if ring is None else ("ring", "the tail")
     if head is not None or t_head is not None:
-        raise ValueError("head and t_head must be None when lead is given: the head vehicle follows `lead`, no head gap exists")
+        raise ValueError("head and t_head must be None when %s is given: the head vehicle follows %s, no head gap exists" % (what, follows))
     if not fused:
-        raise ValueError("lead lives on the tape-free path only: pass fused=True")
+        raise ValueError("%s lives on the tape-free path only: pass fused=True" % what)
     if want_hist:
-        raise ValueError("lead does not take want_hist: the dense history is the sampled form, probes=range(V) with every=1")
+        raise ValueError("%s does not take want_hist: the dense history is the sampled form, probes=range(V) with every=1" % what)
     K = _micro_jvp_tangents(p0, t_p0, t_v0, t_params, None, t_lead, T)
     L, V = p0.shape
     if T < 0:
         raise ValueError("T must be >= 0")
-    if not isinstance(lead, torch.Tensor) or lead.dtype != torch.float32 or tuple(lead.shape) != (T, L, 2):
+    if ring is not None and (not isinstance(ring, torch.Tensor) or ring.dtype != torch.float64 or tuple(ring.shape) != (L,)):
+        raise ValueError("ring must be a float64 tensor of shape (L,) = (%d,)" % L)
+    if ring is None and (not isinstance(lead, torch.Tensor) or lead.dtype != torch.float32 or tuple(lead.shape) != (T, L, 2)):
         raise ValueError("lead must be a float32 tensor of shape (T, L, 2) = (%d, %d, 2)" % (T, L))
     if lead_length is not None and (not isinstance(lead_length, torch.Tensor) or lead_length.dtype != torch.float64
                                     or tuple(lead_length.shape) != (L,)):
@@ -271,12 +284,18 @@ def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t
         slots, ev = sampling if sampling is not None else (None, 1)
         slots = ops._device_slots(slots, dev)
         err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
-        prim, tang = ops.micro_rollout_fwd_jvp_lead(desc, T, p0c, v0c, params.detach(), ops._f32c(lead.detach(), "lead"), tp, tv, slots, ev,
-                                                    lead_length=ll, count=count, t_lead=tl, t_params=tq, observe=sampling is not None,
-                                                    err=err, err_jvp=err_jvp)
+        if ring is not None:
+            prim, tang = ops.micro_rollout_fwd_jvp_ring(desc, T, p0c, v0c, params.detach(), ring.detach().to(device=dev).contiguous(), tp,
+                                                        tv, slots, ev, count=count, t_params=tq, observe=sampling is not None, err=err,
+                                                        err_jvp=err_jvp)
+        else:
+            prim, tang = ops.micro_rollout_fwd_jvp_lead(desc, T, p0c, v0c, params.detach(), ops._f32c(lead.detach(), "lead"), tp, tv, slots,
+                                                        ev, lead_length=ll, count=count, t_lead=tl, t_params=tq,
+                                                        observe=sampling is not None, err=err, err_jvp=err_jvp)
         if check_faults:                 # the forward's record first (a collision is printed and tolerated), then the tangents'
             ops.raise_on_fault(err)
             ops.raise_on_fault(err_jvp)
     if sampling is None:
         return prim[:2], tang[:2]
     return prim, tang
+

@@ -1153,7 +1153,8 @@ def micro_ckpt_numel(desc, T, segment=0):
 
 # ---- the tape-free paths' raw layer: every check once, then _micro_ckpt_fwd / _micro_ckpt_bwd / _micro_fwd_jvp for every form -----------
 # A form: "hist" (the dense history, a constant head gap), "samples" (probe samples in its place), "lead" (samples, the head follows a
-# recorded leader) or "target" (the trajectory fit of the checkpointed pair; head or lead).
+# recorded leader), "ring" (samples, the head follows the lane's own tail one circumference ahead) or "target" (the trajectory fit of
+# the checkpointed pair; head, lead or ring).
 
 
 def _micro_ckpt_plan(entry, forms, desc, T, want_params, segment):
@@ -1198,15 +1199,25 @@ def _lead_args(desc, T, lead, lead_length):
         raise ValueError("lead_length must be None or a contiguous float64 tensor of shape (%d,)" % L)
 
 
+def _ring_arg(desc, ring):
+    """The raw wrappers' check of ring: a contiguous float64 [L], the circumference of each lane's ring."""
+    if (not isinstance(ring, torch.Tensor) or ring.dtype != torch.float64 or tuple(ring.shape) != (desc.n_lanes,)
+            or not ring.is_contiguous()):
+        raise ValueError("ring must be a contiguous float64 tensor of shape (%d,)" % desc.n_lanes)
+
+
 def _head_arg(desc, head, contiguous):
     if head.dtype != torch.float64 or tuple(head.shape) != (desc.n_lanes, 2) or (contiguous and not head.is_contiguous()):
         raise ValueError("head must be %sfloat64 [L][2]" % ("a contiguous " if contiguous else ""))
 
 
-def _target_args(desc, T, target, head, lead):
-    """What the target forms check first: head or lead, exactly one, and target, a contiguous float32 [T][L][2][V]."""
+def _target_args(desc, T, target, head, lead, ring=None):
+    """What the target forms check first: head or lead, exactly one (neither on a ring), and target, a contiguous float32 [T][L][2][V]."""
     L, V = desc.n_lanes, desc.capacity
-    if (head is None) == (lead is None):
+    if ring is not None:
+        if head is not None or lead is not None:
+            raise ValueError("ring takes neither head nor lead: the head vehicle follows the tail")
+    elif (head is None) == (lead is None):
         raise ValueError("exactly one of head and lead must be given")
     if int(T) < 0:
         raise ValueError("T must be >= 0")
@@ -1215,9 +1226,13 @@ def _target_args(desc, T, target, head, lead):
         raise ValueError("target must be a contiguous float32 tensor of shape (%d, %d, 2, %d)" % (int(T), L, V))
 
 
-def _boundary_args(desc, T, head, lead, lead_length, contiguous):
-    """... and after ckpt: whichever of head and lead the head vehicle follows."""
-    if lead is not None:
+def _boundary_args(desc, T, head, lead, lead_length, contiguous, ring=None):
+    """... and after ckpt: whichever of head, lead and ring the head vehicle follows."""
+    if ring is not None:
+        if lead_length is not None:
+            raise ValueError("lead_length needs lead")
+        _ring_arg(desc, ring)
+    elif lead is not None:
         _lead_args(desc, T, lead, lead_length)
     elif lead_length is not None:
         raise ValueError("lead_length needs lead")
@@ -1261,20 +1276,22 @@ def _dir_arg(name, t, dtype, shape):
 
 
 def _micro_ckpt_fwd(form, desc, T, p, v, params, ckpt, count, segment, err, out, head=None, hist=None, probes=None, every=1, samples=None,
-                    observe=True, lead=None, lead_length=None, target=None, sse=None):
+                    observe=True, lead=None, lead_length=None, target=None, sse=None, ring=None):
     """The checkpointed forward of every form: checks, buffers and the one C call -> (out, samples or sse).  ckpt may be None (no
     checkpoint is kept) in every form but "hist"."""
     L = desc.n_lanes
-    sampled = form in ("samples", "lead")
+    sampled = form in ("samples", "lead", "ring")
     if form == "target":
-        _target_args(desc, T, target, head, lead)
+        _target_args(desc, T, target, head, lead, ring)
     if sampled:
         rows, n, n_probes = _samples_shape(desc, T, probes, every)
     if form == "lead":
         _lead_args(desc, T, lead, lead_length)
+    if form == "ring":
+        _ring_arg(desc, ring)
     S = _ckpt_args(form, desc, T, False, segment, ckpt, form != "hist")
     if form == "target":
-        _boundary_args(desc, T, head, lead, lead_length, False)
+        _boundary_args(desc, T, head, lead, lead_length, False, ring)
     p, v, params, head = _state_args(desc, p, v, params, head, count, form != "target")
     if sampled:
         samples = _obs_buffer("samples", samples, (rows, L, 2, n), p.device) if observe else None
@@ -1285,7 +1302,8 @@ def _micro_ckpt_fwd(form, desc, T, p, v, params, ckpt, count, segment, err, out,
             raise ValueError("sse must be a contiguous float64 tensor of shape (%d, 2)" % L)
     if out is None:
         out = (torch.empty_like(p), torch.empty_like(v))
-    # include/dhts.h: desc T segment p v count params | head, or lead lead_length, or all three | p_out v_out ckpt | observed | err stream
+    # include/dhts.h: desc T segment p v count params | head, or lead lead_length, or all three, or ring | p_out v_out ckpt | observed |
+    # err stream
     lib, a, z = _lib.lib(), (C.byref(desc), int(T), S, _ptr(p), _ptr(v), _ptr(count), _ptr(params)), (_ptr(out[0]), _ptr(out[1]), _data(ckpt))
     if form == "hist":
         check(lib.dhts_micro_rollout_fwd_ckpt(*a, _ptr(head), *z, _data(hist), _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt")
@@ -1298,6 +1316,14 @@ def _micro_ckpt_fwd(form, desc, T, p, v, params, ckpt, count, segment, err, out,
         check(lib.dhts_micro_rollout_fwd_ckpt_lead(*a, _data(lead), _ptr(lead_length), *z, _ptr(probes), n_probes, every, _data(samples),
                                                    _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt_lead")
         return out, samples
+    if form == "ring":
+        check(lib.dhts_micro_rollout_fwd_ckpt_ring(*a, _ptr(ring), *z, _ptr(probes), n_probes, every, _data(samples), _ptr(err), _stream()),
+              "dhts_micro_rollout_fwd_ckpt_ring")
+        return out, samples
+    if ring is not None:
+        check(lib.dhts_micro_rollout_fwd_ckpt_target_ring(*a, _ptr(ring), *z, _data(target), _ptr(sse), _ptr(err), _stream()),
+              "dhts_micro_rollout_fwd_ckpt_target_ring")
+        return out, sse
     # (a T = 0 call with lead: no row exists; the library takes the lead form from the NULL head)
     check(lib.dhts_micro_rollout_fwd_ckpt_target(*a, _ptr(head), _data(lead), _ptr(lead_length), *z, _data(target), _ptr(sse), _ptr(err),
                                                  _stream()), "dhts_micro_rollout_fwd_ckpt_target")
@@ -1305,20 +1331,22 @@ def _micro_ckpt_fwd(form, desc, T, p, v, params, ckpt, count, segment, err, out,
 
 
 def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, head=None, g_head=None, g_hist=None,
-                    probes=None, every=1, g_samples=None, lead=None, lead_length=None, g_lead=None, target=None, g_sse=None):
-    """The reverse sweep from checkpoints of every form -> (g_p0, g_v0, g_head or g_lead).  g_samples is required in the "samples"
-    form and optional (None: nothing was observed) in the "lead" form."""
+                    probes=None, every=1, g_samples=None, lead=None, lead_length=None, g_lead=None, target=None, g_sse=None, ring=None):
+    """The reverse sweep from checkpoints of every form -> (g_p0, g_v0, g_head or g_lead; None on a ring).  g_samples is required in
+    the "samples" form and optional (None: nothing was observed) in the "lead" and "ring" forms."""
     L, V = desc.n_lanes, desc.capacity
-    sampled = form in ("samples", "lead")
+    sampled = form in ("samples", "lead", "ring")
     if form == "target":
-        _target_args(desc, T, target, head, lead)
+        _target_args(desc, T, target, head, lead, ring)
     if sampled:
         rows, n, n_probes = _samples_shape(desc, T, probes, every)
     if form == "lead":
         _lead_args(desc, T, lead, lead_length)
+    if form == "ring":
+        _ring_arg(desc, ring)
     S = _ckpt_args(form, desc, T, g_params is not None, segment, ckpt, False)
     if form == "target":
-        _boundary_args(desc, T, head, lead, lead_length, True)
+        _boundary_args(desc, T, head, lead, lead_length, True, ring)
     for name, t in (("params", params), ("g_params", g_params)):
         if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous()):
             raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
@@ -1333,7 +1361,10 @@ def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, 
         g_samples = _obs_buffer("g_samples", g_samples, (rows, L, 2, n), g_p.device)
     if out is None:
         out = (torch.empty_like(g_p), torch.empty_like(g_v))
-    if lead is None:                     # the cotangent of whichever the head follows
+    if ring is not None:                 # the image's cotangent returns to the tail inside the sweep
+        if g_head is not None or g_lead is not None:
+            raise ValueError("a ring has neither g_head nor g_lead")
+    elif lead is None:                   # the cotangent of whichever the head follows
         if g_lead is not None:
             raise ValueError("g_lead needs lead")
         if g_head is None:
@@ -1345,8 +1376,8 @@ def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, 
             g_lead = torch.empty(int(T), L, 2, dtype=torch.float32, device=g_p.device)
         elif g_lead.dtype != torch.float32 or tuple(g_lead.shape) != (int(T), L, 2) or not g_lead.is_contiguous():
             raise ValueError("g_lead must be a contiguous float32 tensor of shape (%d, %d, 2)" % (int(T), L))
-    # include/dhts.h: desc T segment ckpt count params | head, or lead lead_length, or all three | g_p g_v | observed | g_p_out g_v_out |
-    # g_head, or g_lead, or both | g_params err stream
+    # include/dhts.h: desc T segment ckpt count params | head, or lead lead_length, or all three, or ring | g_p g_v | observed |
+    # g_p_out g_v_out | g_head, or g_lead, or both, or neither | g_params err stream
     lib, a = _lib.lib(), (C.byref(desc), int(T), S, _data(ckpt), _ptr(count), _ptr(params))
     g, z = (_ptr(g_p), _ptr(g_v)), (_ptr(out[0]), _ptr(out[1]))
     if form == "hist":
@@ -1358,16 +1389,22 @@ def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, 
     elif form == "lead":
         check(lib.dhts_micro_rollout_bwd_ckpt_lead(*a, _data(lead), _ptr(lead_length), *g, _ptr(probes), n_probes, every, _data(g_samples), *z,
                                                    _data(g_lead), _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_lead")
+    elif form == "ring":
+        check(lib.dhts_micro_rollout_bwd_ckpt_ring(*a, _ptr(ring), *g, _ptr(probes), n_probes, every, _data(g_samples), *z, _ptr(g_params),
+                                                   _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_ring")
+    elif ring is not None:
+        check(lib.dhts_micro_rollout_bwd_ckpt_target_ring(*a, _ptr(ring), *g, _data(target), _ptr(g_sse), *z, _ptr(g_params), _ptr(err),
+                                                          _stream()), "dhts_micro_rollout_bwd_ckpt_target_ring")
     else:
         check(lib.dhts_micro_rollout_bwd_ckpt_target(*a, _ptr(head), _data(lead), _ptr(lead_length), *g, _data(target), _ptr(g_sse), *z,
                                                      _ptr(g_head), _data(g_lead), _ptr(g_params), _ptr(err), _stream()),
               "dhts_micro_rollout_bwd_ckpt_target")
-    return out[0], out[1], (g_head if lead is None else g_lead)
+    return out[0], out[1], (None if ring is not None else g_head if lead is None else g_lead)
 
 
 def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, head=None, t_head=None, want_hist=False,
-                   probes=None, every=1, observe=True, lead=None, lead_length=None, t_lead=None):
-    """The fused rollout + tangent call of the "hist", "samples" and "lead" forms -> ((pT, vT, observed), (t_pT, t_vT, t_observed)),
+                   probes=None, every=1, observe=True, lead=None, lead_length=None, t_lead=None, ring=None):
+    """The fused rollout + tangent call of the "hist", "samples", "lead" and "ring" forms -> ((pT, vT, observed), (t_pT, t_vT, t_observed)),
     observed = the histories (None unless asked for or handed in) or the sample arrays (None with observe False)."""
     L, V, T = desc.n_lanes, desc.capacity, int(T)
     sampled = form != "hist"
@@ -1375,6 +1412,8 @@ def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, 
         rows, n, n_probes = _samples_shape(desc, T, probes, every)
     if form == "lead":
         _lead_args(desc, T, lead, lead_length)
+    if form == "ring":
+        _ring_arg(desc, ring)
     p, v, params, head = _state_args(desc, p, v, params, head, count)
     if T < 0:
         raise ValueError("T must be >= 0")
@@ -1393,7 +1432,8 @@ def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, 
     new = (torch.zeros if observe else None) if sampled else (torch.empty if want_hist else None)
     obs = [_obs_buffer(name, t, shp, p.device, new) for name, t, shp in zip(names, out[4:6] or (None, None), (shape, (K,) + shape))]
     state = _state_out(("p_out", "v_out", "t_p_out", "t_v_out"), out, (p, v, t_p, t_v))
-    # include/dhts.h: desc T n_dir p v count params | head, or lead lead_length | t_p t_v | t_head, or t_lead | t_params | the four outputs |
+    # include/dhts.h: desc T n_dir p v count params | head, or lead lead_length, or ring | t_p t_v | t_head, or t_lead, or neither |
+    # t_params | the four outputs |
     # probes n_probes every (sampled) | the two observed arrays | err err_jvp stream
     lib, a, t = _lib.lib(), (C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params)), (_ptr(t_p), _ptr(t_v))
     z = (_ptr(state[0]), _ptr(state[1]), _ptr(state[2]), _ptr(state[3]))
@@ -1403,6 +1443,9 @@ def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, 
     elif form == "samples":
         check(lib.dhts_micro_rollout_fwd_jvp_samples(*a, _ptr(head), *t, _ptr(t_head), _ptr(t_params), *z, _ptr(probes), n_probes, every, *e),
               "dhts_micro_rollout_fwd_jvp_samples")
+    elif form == "ring":
+        check(lib.dhts_micro_rollout_fwd_jvp_ring(*a, _ptr(ring), *t, _ptr(t_params), *z, _ptr(probes), n_probes, every, *e),
+              "dhts_micro_rollout_fwd_jvp_ring")
     else:
         check(lib.dhts_micro_rollout_fwd_jvp_lead(*a, _data(lead), _ptr(lead_length), *t, _data(t_lead), _ptr(t_params), *z, _ptr(probes),
                                                   n_probes, every, *e), "dhts_micro_rollout_fwd_jvp_lead")
@@ -1509,6 +1552,47 @@ def micro_rollout_bwd_ckpt_target(desc, T, ckpt, params, g_p, g_v, target, g_sse
     (float)(2 g_sse) * (x - target) is formed in the kernel.  target, head / lead, lead_length, count, segment: the forward's."""
     return _micro_ckpt_bwd("target", desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, head=head, g_head=g_head,
                            lead=lead, lead_length=lead_length, g_lead=g_lead, target=target, g_sse=g_sse)
+
+
+# ---- a ring road on the two tape-free paths (dhts_micro_rollout_*_ring) -------------------------------------------------------------------
+def micro_rollout_fwd_ckpt_ring(desc, T, p, v, params, ring, ckpt, probes=None, every=1, count=None, segment=0, samples=None, observe=True,
+                                err=None, out=None):
+    """micro_rollout_fwd_ckpt_lead on a closed lane (dhts_micro_rollout_fwd_ckpt_ring, include/dhts.h): ring float64 [L] = the
+    circumference of each lane's ring; the head vehicle follows the image of the tail (slot 0) one circumference ahead, positions stay
+    unwrapped.  observe, probes, every, ckpt as micro_rollout_fwd_ckpt_lead.  Returns (pT, vT, samples)."""
+    out, samples = _micro_ckpt_fwd("ring", desc, T, p, v, params, ckpt, count, segment, err, out, probes=probes, every=every,
+                                   samples=samples, observe=observe, ring=ring)
+    return out[0], out[1], samples
+
+
+def micro_rollout_bwd_ckpt_ring(desc, T, ckpt, params, ring, g_p, g_v, probes=None, every=1, g_samples=None, count=None, segment=0, err=None,
+                                out=None, g_params=None):
+    """The reverse sweep of micro_rollout_fwd_ckpt_ring (dhts_micro_rollout_bwd_ckpt_ring) -> (g_p0, g_v0): the cotangent of the image
+    returns to the tail inside the sweep; no g_head and no g_lead exist.  g_samples=None: nothing was observed.  With g_params the tail's
+    length also collects the head's share of the gap.  ring, probes, every, count, segment: the forward's."""
+    return _micro_ckpt_bwd("ring", desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, probes=probes, every=every,
+                           g_samples=g_samples, ring=ring)[:2]
+
+
+def micro_rollout_fwd_jvp_ring(desc, T, p, v, params, ring, t_p, t_v, probes=None, every=1, count=None, t_params=None, observe=True, err=None,
+                               err_jvp=None, out=None):
+    """micro_rollout_fwd_jvp_lead on a closed lane (dhts_micro_rollout_fwd_jvp_ring): the image's tangents are the tail's; no t_head and
+    no t_lead exist.  Returns ((pT, vT, samples), (t_pT, t_vT, t_samples))."""
+    return _micro_fwd_jvp("ring", desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, probes=probes, every=every,
+                          observe=observe, ring=ring)
+
+
+def micro_rollout_fwd_ckpt_target_ring(desc, T, p, v, params, ring, ckpt, target, count=None, segment=0, sse=None, err=None, out=None):
+    """micro_rollout_fwd_ckpt_target on a closed lane (dhts_micro_rollout_fwd_ckpt_target_ring) -> (pT, vT, sse)."""
+    out, sse = _micro_ckpt_fwd("target", desc, T, p, v, params, ckpt, count, segment, err, out, target=target, sse=sse, ring=ring)
+    return out[0], out[1], sse
+
+
+def micro_rollout_bwd_ckpt_target_ring(desc, T, ckpt, params, ring, g_p, g_v, target, g_sse=None, count=None, segment=0, err=None, out=None,
+                                       g_params=None):
+    """The reverse sweep of micro_rollout_fwd_ckpt_target_ring (dhts_micro_rollout_bwd_ckpt_target_ring) -> (g_p0, g_v0)."""
+    return _micro_ckpt_bwd("target", desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, target=target, g_sse=g_sse,
+                           ring=ring)[:2]
 
 
 def _probe_slots(probes, V):
@@ -1823,6 +1907,81 @@ class MicroRolloutTarget(torch.autograd.Function):
         return (g_p0, g_v0, ctx.g_params, g_head, g_lead) + (None,) * 7
 
 
+class MicroRolloutRing(torch.autograd.Function):
+    """MicroRolloutLead on a closed lane: (p0, v0 [L][V]) -> (pT, vT[, samples]) with the head vehicle following the image of the tail one
+    circumference `ring` [L] ahead (dhts_micro_rollout_fwd_ckpt_ring / _bwd_ckpt_ring).  The dependence of the head on the tail is inside
+    the kernels: the image's cotangent returns to the tail in the sweep, and no head gap, leader row or gradient of one exists.  ring is
+    data.  observe False: no samples are written or returned."""
+
+    @staticmethod
+    def forward(ctx, p0, v0, params, ring, count, T, dt, check_faults, checkpoint, probes, every, observe):
+        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_plan)
+        need_grad = p0.requires_grad or v0.requires_grad or params.requires_grad
+        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
+        ctx.ring, ctx.probes, ctx.every, ctx.observe = ring.detach().to(device=p0c.device).contiguous(), probes, every, observe
+        pT, vT, samples = micro_rollout_fwd_ckpt_ring(desc, T, p0c, v0c, ctx.params, ctx.ring, ctx.ckpt, probes, every, count=count,
+                                                      segment=segment, observe=observe, err=err)
+        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
+        return (pT, vT, samples) if observe else (pT, vT)
+
+    @staticmethod
+    def backward(ctx, g_pT, g_vT, g_samples=None):
+        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
+        gs = g_samples.contiguous() if (ctx.observe and g_samples is not None) else None      # (None: nothing enters at the samples)
+        g_p0, g_v0 = micro_rollout_bwd_ckpt_ring(ctx.desc, ctx.T, ctx.ckpt, ctx.params, ctx.ring, g_p, g_v, ctx.probes, ctx.every, gs,
+                                                 count=ctx.count, segment=ctx.segment, err=err, g_params=ctx.g_params)
+        _micro_bwd_done(ctx)
+        return (g_p0, g_v0, ctx.g_params) + (None,) * 9
+
+
+class MicroRolloutRingTarget(torch.autograd.Function):
+    """MicroRolloutTarget on a closed lane: (p0, v0 [L][V]) -> (pT, vT, sse [L][2] float64), the trajectory fit of MicroRolloutRing's
+    rollout inside the kernels (dhts_micro_rollout_fwd_ckpt_target_ring / _bwd_ckpt_target_ring)."""
+
+    @staticmethod
+    def forward(ctx, p0, v0, params, ring, count, T, dt, check_faults, checkpoint, target):
+        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_target_plan)
+        need_grad = p0.requires_grad or v0.requires_grad or params.requires_grad
+        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
+        ctx.ring, ctx.target = ring.detach().to(device=p0c.device).contiguous(), _f32c(target, "target")
+        ctx.out_bwd = (torch.empty_like(p0c), torch.empty_like(v0c)) if need_grad else None
+        pT, vT, sse = micro_rollout_fwd_ckpt_target_ring(desc, T, p0c, v0c, ctx.params, ctx.ring, ctx.ckpt, ctx.target, count=count,
+                                                         segment=segment, err=err)
+        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
+        return pT, vT, sse
+
+    @staticmethod
+    def backward(ctx, g_pT, g_vT, g_sse):
+        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
+        gs = g_sse.contiguous() if g_sse is not None else None          # (None: the kernel takes zero)
+        g_p0, g_v0 = micro_rollout_bwd_ckpt_target_ring(ctx.desc, ctx.T, ctx.ckpt, ctx.params, ctx.ring, g_p, g_v, ctx.target, g_sse=gs,
+                                                        count=ctx.count, segment=ctx.segment, err=err, out=ctx.out_bwd,
+                                                        g_params=ctx.g_params)
+        _micro_bwd_done(ctx)
+        return (g_p0, g_v0, ctx.g_params) + (None,) * 7
+
+
+def _micro_ring_checks(p0, head, T, ring, lead, lead_length, want_hist, checkpoint):
+    """Every ValueError of dhts.micro_rollout's `ring`, raised before anything touches a device."""
+    if head is not None:
+        raise ValueError("head must be None when ring is given: the head vehicle follows the tail, no head gap exists")
+    if lead is not None or lead_length is not None:
+        raise ValueError("lead / lead_length must be None when ring is given: the head vehicle follows the tail")
+    if want_hist:
+        raise ValueError("ring does not take want_hist: the dense history is the sampled form, probes=range(V) with every=1")
+    if checkpoint is None or checkpoint is False:
+        raise ValueError("ring lives on the tape-free path only: pass checkpoint=True (or a segment length)")
+    if p0.dim() != 2:
+        raise ValueError("p0 must be [L][V]")
+    L = int(p0.shape[0])
+    if int(T) < 0:
+        raise ValueError("T must be >= 0")
+    if not isinstance(ring, torch.Tensor) or ring.dtype != torch.float64 or tuple(ring.shape) != (L,):
+        raise ValueError("ring must be a float64 tensor of shape (L,) = (%d,)" % L)
+    if ring.requires_grad:
+        raise ValueError("ring is not differentiable: pass it detached")
+
+
 def _micro_target_checks(p0, T, target, want_hist, checkpoint, probes, every):
     """Every ValueError of dhts.micro_rollout's `target`, raised before anything touches a device."""
     if checkpoint is None or checkpoint is False:
@@ -1870,7 +2029,7 @@ def _device_slots(slots, device):
 
 
 def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, check_faults=True, checkpoint=None, probes=None, every=1,
-                  lead=None, lead_length=None, target=None):
+                  lead=None, lead_length=None, ring=None, target=None):
     """MicroRollout.  checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape).
 
     probes / every: observe the trajectory at a few vehicle slots every so many steps.  Sampling is on when probes is not None or
@@ -1891,6 +2050,15 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
     checkpointed path only: checkpoint=True or a segment is required (ValueError otherwise), want_hist is not accepted (ValueError: the
     dense history is probes=range(V), every=1), probes / every work as above; without them the call returns (pT, vT).
 
+    ring: close the lane.  ring float64 [L] = the circumference of each lane's ring in metres (data: not differentiable).  The lane's
+    count vehicles drive on a ring road: the head (slot count - 1) follows the image of the tail (slot 0) one circumference ahead, with
+    the gap, collision and clamp rules of every follower and half the sum of the tail's and its own length; the gradient flows from the
+    head to the tail inside the kernels (MicroRolloutRing).  Positions stay unwrapped -- no modulo is taken, p keeps growing as on an open
+    lane.  One vehicle follows its own image; an empty lane passes through.  A ring too short for its vehicles shows as the collision
+    fault of every rollout.  `head`, lead and lead_length must be None; checkpoint=True or a segment is required (ValueError otherwise:
+    the taped kernels have no ring form), want_hist is not accepted (the dense history is probes=range(V), every=1); probes / every and
+    target work as above, and the call returns (pT, vT), (pT, vT, samples) or (pT, vT, sse).
+
     target: fit the whole trajectory without holding it.  target float32 [T][L][2][V], contiguous, on p0's device, not requiring grad:
     target[t][l][0 / 1][k] = the observed (p, v) of slot k after step t (hist's indexing); a NaN entry is not observed.  The call returns
     (pT, vT, sse), sse float64 [L][2]: per lane the sum over observed entries of (x - target)^2 for positions and for speeds -- the
@@ -1898,7 +2066,18 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
     are never read; T = 0 gives zeros).  sse is differentiable: mean((hist - target)^2) is sse.sum() / target.numel().  Neither hist nor
     its cotangent exists; the kernels read target once per direction (MicroRolloutTarget).  checkpoint=True or a segment is required
     (the segment plan is micro_ckpt_target_plan's: its reverse ring is wider), want_hist / probes / every are not accepted (ValueError),
-    lead / lead_length combine with it.  Without a leaf that requires grad no checkpoint is kept: a loss evaluation."""
+    lead / lead_length and ring combine with it.  Without a leaf that requires grad no checkpoint is kept: a loss evaluation."""
+    if ring is not None:
+        _micro_ring_checks(p0, head, T, ring, lead, lead_length, want_hist, checkpoint)
+        if target is not None:
+            _micro_target_checks(p0, T, target, want_hist, checkpoint, probes, every)
+            _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_target_plan)
+            return MicroRolloutRingTarget.apply(p0, v0, params, ring, count, int(T), float(dt), bool(check_faults), checkpoint, target)
+        sampling = micro_sampling(probes, every, int(p0.shape[-1]), False)
+        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_plan)
+        slots, ev = sampling if sampling is not None else (None, 1)
+        return MicroRolloutRing.apply(p0, v0, params, ring, count, int(T), float(dt), bool(check_faults), checkpoint,
+                                      _device_slots(slots, p0.device), ev, sampling is not None)
     if target is not None:
         _micro_target_checks(p0, T, target, want_hist, checkpoint, probes, every)
         if lead is not None or lead_length is not None:

@@ -24,6 +24,10 @@ recorded leader lives on the tape-free paths: with --checkpoint (Adam) or --meth
 (dhts.micro_rollout(target=observed)) and return the squared error per lane, loss = sse.sum() / observed.numel(); neither the history
 nor its cotangent is allocated, so the fit holds `observed` and the checkpoints and nothing else of size T x V.  The same log up to
 the summation order of the loss (float64 in the kernels, float32 in torch.mean).
+--ring C: the closed experiment of car-following research -- n_vehicle drivers on a ring road of circumference C metres, the head
+following the tail one circumference ahead (dhts.micro_rollout(ring=) / micro_rollout_jvp(ring=)).  The truth is a ring rollout of a
+perturbed platoon (even spacing C / n_vehicle with a jitter, random speeds: what grows into stop-and-go waves), and the fit runs on the
+same ring.  A ring lives on the tape-free paths: with --checkpoint (Adam, optionally --fused-loss or --observe) or --method lm --fused.
 Log lines "{parameter_error} {loss}" per iteration in result/calibrate/<run>/gd/trial_k.txt (lm: .../lm/trial_k.txt), like the other examples.
 """
 import argparse
@@ -62,6 +66,8 @@ def main():
                     help="fit the followers of a recorded leader: the truth has n_vehicle + 1 vehicles, its head's trajectory is given")
     ap.add_argument("--fused-loss", action="store_true",
                     help="Adam with --checkpoint: the squared error and its gradient inside the rollout kernels (target=), no history")
+    ap.add_argument("--ring", type=float, default=None, metavar="C",
+                    help="a ring road of circumference C metres: the head vehicle follows the tail (needs --checkpoint or --method lm --fused)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--run_name", default=None)
     args = ap.parse_args()
@@ -71,6 +77,12 @@ def main():
         ap.error("--checkpoint belongs to --method adam")
     if args.leader and not (args.fused or args.checkpoint is not None):
         ap.error("--leader lives on the tape-free paths: add --checkpoint (Adam) or --method lm --fused")
+    if args.ring is not None and not (args.fused or args.checkpoint is not None):
+        ap.error("--ring lives on the tape-free paths: add --checkpoint (Adam, optionally --fused-loss or --observe) or --method lm --fused")
+    if args.ring is not None and args.leader:
+        ap.error("--ring and --leader exclude each other: on a ring the head vehicle follows the tail")
+    if args.ring is not None and args.ring < 2.0 * args.vehicle_length * args.n_vehicle:
+        ap.error("--ring C is too short for n_vehicle vehicles: give each at least two vehicle lengths")
     if args.fused_loss and (args.checkpoint is None or args.observe is not None):
         ap.error("--fused-loss is the dense fit on the checkpointed path: add --checkpoint, drop --observe")
     sampled = {}                                  # the arguments of a sampled call; none: the dense history
@@ -94,8 +106,9 @@ def main():
     length = truth[5:6]
     head = th.tensor([[1000.0, 0.0]], dtype=th.float64, device=dev).expand(L, 2).contiguous()
 
-    follow = {}                                   # --leader: the recorded leader of a trial (lead, lead_length), made with its truth
-    # with a leader the dense history is the sampled form of every slot at every step
+    # --leader: the recorded leader of a trial (lead, lead_length), made with its truth; --ring: the circumference of every lane's ring
+    follow = {} if args.ring is None else dict(ring=th.full((L,), args.ring, dtype=th.float64, device=dev))
+    # with a leader or on a ring the dense history is the sampled form of every slot at every step
     observe = sampled or dict(probes=list(range(V)), every=1)
 
     def rollout(theta):
@@ -114,6 +127,10 @@ def main():
     for trial in range(args.n_trial):
         p0 = (th.arange(V, device=dev) * 4.0 * ln)[None, :] + th.rand(L, V, device=dev) * 2.0 * ln
         v0 = th.lerp(th.tensor(0.3 * um, device=dev), th.tensor(0.7 * um, device=dev), th.rand(L, V, device=dev))
+        if args.ring is not None:
+            # a perturbed platoon all around the ring: even spacing, each vehicle up to a quarter of the free road ahead of its mark
+            spacing = args.ring / V
+            p0 = (th.arange(V, device=dev) * spacing)[None, :] + th.rand(L, V, device=dev) * 0.25 * (spacing - ln)
         if args.leader:
             # the truth: V + 1 vehicles on the existing path; the head's (p, v) before every step is the record the fit is given
             p_all = th.cat([p0, p0[:, -1:] + 4.0 * ln + th.rand(L, 1, device=dev) * 2.0 * ln], 1)

@@ -780,6 +780,59 @@ int dhts_micro_rollout_bwd_ckpt_target(const dhts_micro_desc *d, int T, int segm
                                        const float *g_p, const float *g_v, const float *target, const double *g_sse, float *g_p_out,
                                        float *g_v_out, double *g_head, float *g_lead, double *g_params, dhts_error *err, void *stream);
 
+/*
+ * A RING ROAD on the two tape-free paths: the lane is closed.  Its n = clamp(count[l], 0, V) vehicles drive on a ring of circumference
+ * ring[l], and the head (slot n - 1) follows the IMAGE OF THE TAIL (slot 0) one circumference ahead, as every other vehicle follows the
+ * slot in front of it.  The five entry points are the _lead ones and the _target pair above, each with the same argument order, with
+ * (lead, lead_length) -- and head, in the target pair -- replaced by
+ *   ring          [L] DOUBLE, the circumference of each lane's ring in metres; read once per lane; NOT differentiated.  Positions stay
+ *                 UNWRAPPED: no modulo is taken anywhere, p keeps growing as on an open lane, and the caller wraps for display.
+ * and without g_head / g_lead / t_head / t_lead: none of them exists.  In step t the head sees
+ *       image = ((float)((double)p_tail + ring[l]), v_tail)        (p_tail, v_tail): the tail's float32 state BEFORE step t
+ * which is exactly what S[k + 1] is to follower k, and forms with the expressions of every follower
+ *       dp = fabs((double)image_p - p) - half_len        dv = v - (double)image_v        half_len = (length[slot 0] + length[head]) / 2
+ * calls the same idm_step, and the same collision / clamp rules and live-gap test (gap >= 1e-5) apply to it.  The tail's length is a
+ * LIVE parameter here (lead_length is not).  n = 1: the vehicle follows its own image, half_len is its own length.  n = 0: nothing
+ * happens, the state passes through and every gradient and tangent of the lane is exactly 0.
+ *   reverse mode   the cotangent (C1p[n], C1v[n]) the sweep forms for the slot in front of the head is added to the TAIL's cotangent in
+ *                  the same sweep step (the float cast has derivative 1, like every float32 state store).  Nothing returns to the head
+ *                  (no virtual leader) and no per-step row is written.  With g_params the head's gap term is live, as with lead, and the
+ *                  tail's length also collects the head's share: g_params[5][slot 0] = -0.5 (A[0] + A[n - 1]), A[k] the gap sum of
+ *                  slot k; n = 1: -A[0].
+ *   forward mode   the tangents of the image are the tail's state tangents before the step; the head's length tangent is
+ *                  -(t_len[head] + t_len[tail]) / 2 where the gap is live.
+ * A ring too short for its vehicles is the caller's error: it shows as the sticky DHTS_FAULT_COLLISION record of the siblings, same
+ * step, lane and vehicle rules.  samples / g_samples / t_samples may be NULL: nothing is observed (samples and t_samples of
+ * _fwd_jvp_ring: both or neither).  Otherwise the siblings' arguments, arithmetic, fault records and bits:
+ *   dhts_micro_rollout_fwd_ckpt_ring          MicroLane.forward (_micro_lane.py:131-214) with the head's leader taken from the tail.
+ *   dhts_micro_rollout_bwd_ckpt_ring          the sweep of dMicroForwardLayer.backward (dmicro_lane.py:230-298) with the leader slot of
+ *       dMicroLane.vectorize_input (:130-153) returned to the tail instead of folded into the head.
+ *   dhts_micro_rollout_fwd_jvp_ring           forward mode of the same rollout, as dhts_micro_rollout_fwd_jvp_lead.
+ *   dhts_micro_rollout_fwd_ckpt_target_ring / _bwd_ckpt_target_ring   the trajectory fit above on the ring (dhts_micro_ckpt_target_plan).
+ * DHTS_E_INVALID, nothing dereferenced and nothing launched: whatever the sibling rejects (but NULL sample arrays), a NULL ring.
+ * Blocks, segments and dynamic LDS are the siblings': dhts_micro_ckpt_plan, dhts_micro_ckpt_target_plan and dhts_micro_fwd_jvp_plan hold
+ * as they are (the image travels in slot V of the hand-over arrays, written by the tail's thread; one LDS-only barrier per step).
+ * Not built: the taped kernels and the taped JVP, a gradient or tangent of ring, wrap-around of positions, the network kernels.
+ */
+int dhts_micro_rollout_fwd_ckpt_ring(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
+                                     const double *params, const double *ring, float *p_out, float *v_out, void *ckpt,
+                                     const int32_t *probes, int n_probes, int every, float *samples, dhts_error *err, void *stream);
+int dhts_micro_rollout_bwd_ckpt_ring(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                     const double *params, const double *ring, const float *g_p, const float *g_v, const int32_t *probes,
+                                     int n_probes, int every, const float *g_samples, float *g_p_out, float *g_v_out, double *g_params,
+                                     dhts_error *err, void *stream);
+int dhts_micro_rollout_fwd_jvp_ring(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                    const double *params, const double *ring, const float *t_p, const float *t_v, const double *t_params,
+                                    float *p_out, float *v_out, float *t_p_out, float *t_v_out, const int32_t *probes, int n_probes,
+                                    int every, float *samples, float *t_samples, dhts_error *err, dhts_error *err_jvp, void *stream);
+int dhts_micro_rollout_fwd_ckpt_target_ring(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v,
+                                            const int32_t *count, const double *params, const double *ring, float *p_out, float *v_out,
+                                            void *ckpt, const float *target, double *sse, dhts_error *err, void *stream);
+int dhts_micro_rollout_bwd_ckpt_target_ring(const dhts_micro_desc *d, int T, int segment, const void *ckpt, const int32_t *count,
+                                            const double *params, const double *ring, const float *g_p, const float *g_v,
+                                            const float *target, const double *g_sse, float *g_p_out, float *g_v_out, double *g_params,
+                                            dhts_error *err, void *stream);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
