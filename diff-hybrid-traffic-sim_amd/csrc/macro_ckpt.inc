@@ -14,12 +14,13 @@
 // interface leaves tape_trivial_A(TapeFp{fp[0], fp[2], fp[3]}) and a zero B in the ring, a queued one its (f.A, f.B) -- what
 // macro_fwd_jvp.inc keeps in PA / PB and what the compact tape expands to.  The sweep is macro_rollout_bwd_kernel's body on those entries:
 // cell_blocks, the detector columns, six dot2, the hand-over (G + c2_left) + c0_right, the boundary addends in double, the NaN record.
+// On a ring (kRing) the two hand-over terms that are 0 at the ends of an open lane are read at wrapped slots and no boundary addend exists.
 //
 // (The dynamic LDS array of the two kernels has a name of its own, smem_ck: block-scope extern declarations of one name are one entity.)
 //
 // The file is included twice.  DHTS_MACRO_TARGET 0 gives the pair above and the byte helpers; DHTS_MACRO_TARGET 1 the TARGET forms
-// (kTarget; dhts_macro_rollout_fwd_ckpt_target / _bwd_ckpt_target), macro_rollout_ckpt_fwd_target_kernel<kP, kSched> and
-// macro_rollout_ckpt_bwd_target_kernel<kSched>, from the same text: no detectors (kTaps is false there), `target` [T][L][2][N] -- the
+// (kTarget; dhts_macro_rollout_fwd_ckpt_target / _bwd_ckpt_target), macro_rollout_ckpt_fwd_target_kernel<kP, kBound> and
+// macro_rollout_ckpt_bwd_target_kernel<kBound>, from the same text: no detectors (kTaps is false there), `target` [T][L][2][N] -- the
 // observed density and speed of every cell after every step, NaN = not observed -- read by the kernels themselves, the forward's sums
 // of squared residuals sse [L][2] out and their cotangent g_sse back in.  In the first pass kTarget is false and what the second adds
 // sits under it.
@@ -52,7 +53,8 @@ __host__ __device__ inline size_t macro_ckpt_row_bytes(int N) { return sizeof(fl
 
 // grid = L workgroups (one traffic lane each) of W = blockDim.x / 64 wavefronts, the lane kernel's mapping: wave w owns the cells
 // [64 kP w, 64 kP (w + 1)), thread t of its pass j the cell 64 kP w + 64 j + t and that cell's LEFT interface.  kP: 64-cell passes per
-// wavefront (1 or 2: the plan names no other); kSched / kTaps as in macro_rollout_fwd2_kernel.  Two LDS-only barriers per step, the queue
+// wavefront (1 or 2: the plan names no other); kBound: constant boundary cells, a schedule (kSched, as in macro_rollout_fwd2_kernel) or a
+// ring (kRing: slots 0 and N + 1 are copies of cells N - 1 and 0, ring_rec_copies in macro_fwd_jvp.inc; DESIGN 4l); kTaps as there.  Two LDS-only barriers per step, the queue
 // and the priority rotation as there; no tape and no history.  In phase 1 of step n, n a multiple of Sg, the owner of a cell stores the
 // (r, y) the step starts from to row n / Sg of ckpt (consecutive threads, consecutive float2: coalesced).  T >= 1 (the entry point
 // copies for T = 0).  At most 12 wavefronts, as macro_rollout_fwd_jvp_kernel: the longest lane the reverse kernel takes has 11.
@@ -63,10 +65,10 @@ __host__ __device__ inline size_t macro_ckpt_row_bytes(int N) { return sizeof(fl
 // pointer (no global load on the step's dependent chain); the squared float32 residuals of its valid cells are summed in double in step
 // order and combined per lane behind the loop.  ckpt may be NULL: no checkpoint is stored.
 #if DHTS_MACRO_TARGET == 0
-template <int kP, bool kSched, bool kTaps>
+template <int kP, MacroBoundary kBound, bool kTaps>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_kernel(
 #else
-template <int kP, bool kSched>
+template <int kP, MacroBoundary kBound>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
 #endif
     int L, int N, int T, int Sg, double dt, double dx, double um,
@@ -86,6 +88,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
     constexpr int n_det = 0;
     float *const taps = nullptr;
 #endif
+    constexpr bool kSched = kBound == kBoundSched, kRing = kBound == kBoundRing;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_ck[];
     const int lane = blockIdx.x;
     const int tid = threadIdx.x;
@@ -103,7 +106,10 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
 
     for (int k = tid; k < N + 2; k += blockDim.x) {
         float4 st;
-        if (k == 0 || k == N + 1) {
+        if (kRing && (k == 0 || k == N + 1)) {           // a ring: slot 0 is cell N - 1, slot N + 1 is cell 0
+            const size_t w = base + (k ? 0 : N - 1);
+            st = make_float4(r_in[w], y_in[w], u_in[w], q_in[w]);
+        } else if (k == 0 || k == N + 1) {
             const float *g = ghost + (size_t)lane * 8 + (k ? 4 : 0);
             st = make_float4(g[0], g[1], g[2], g[3]);
         } else {
@@ -197,6 +203,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
                 if (vc && solve) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
                 else if (kTaps && vc) own->st = st;          // the final step's state, for the taps below
+                if constexpr (kRing && solve) ring_rec_copies_direct(CR, N, vc, ic, st, cp);
                 if constexpr (kTarget) {
                     // st is row n - 1 of the history: the float32 residuals against that row of target (NaN: not observed), squared
                     // and summed in double; then row n leaves for the registers, a whole step ahead of the update that reads it
@@ -253,7 +260,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
             arz_interface_fast_pre((double)ls.x, (double)ls.y, (double)ls.z, (double)ls.w, cl,
                                    (double)rs.x, (double)rs.y, (double)rs.z, (double)rs.w, cr, kc, f);
             FX[i] = make_double2(f.Fr, f.Fy);
-            if (f.cfl_bad && fault_step < 0) { fault_step = n; fault_index = (int)i; }
+            if (f.cfl_bad && fault_step < 0) { fault_step = n; fault_index = (kRing && i == (unsigned)N) ? 0 : (int)i; }      // (a ring: N is 0)
         }
         __builtin_amdgcn_s_setprio(0);
         if constexpr (kTaps && upd) tap(n - 1);
@@ -314,10 +321,10 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
 // Row T - 1 is the forward's final state, which the caller has: fin_r, fin_y, fin_u are read once in front of the loop and the pair goes
 // into the incoming cotangent, as the last row of g_taps does.  The sweep itself takes no global load beyond what it has.
 #if DHTS_MACRO_TARGET == 0
-template <bool kSched, bool kTaps>
+template <MacroBoundary kBound, bool kTaps>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
 #else
-template <bool kSched>
+template <MacroBoundary kBound>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
 #endif
     int L, int N, int T, int Sg, int p, double dt, double dx, double um, const float2 *__restrict__ ckpt,
@@ -337,6 +344,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
     const int32_t *const det = nullptr;
     constexpr int n_det = 0;
 #endif
+    constexpr bool kSched = kBound == kBoundSched, kRing = kBound == kBoundRing;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_ck[];
     const int lane = blockIdx.x;
     const int tid = threadIdx.x;
@@ -421,6 +429,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
     const float umf = (float)um;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     int rot = 0;
+    const int Nv = kRing ? ring_len(N) : N;          // (a ring: see ring_rec_copies)
     float4 sched_st = zero4;
     const float4 *sched_p = nullptr;
     // kSched: this lane's boundary cell (tid & 1) of row 0 of the schedule (a per-thread pointer: threads 0 and 1 use it)
@@ -474,6 +483,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
                 CellPre cp;
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
                 if (vc) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
+                if constexpr (kRing) ring_rec_copies(CR, Nv, vc, ic, st, cp);
             }
             wave_lds_handoff();
             const CellRec *lf = CR + ic;
@@ -546,7 +556,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
         ckp[j] = ckpt + (size_t)(C > 1 ? C - 1 : 0) * ((size_t)L * N) + base + ic;
         ck[j] = C > 1 ? *ckp[j] : make_float2(0.f, 0.f);
     }
-    if (!kSched && tid < 2) {                        // constant boundary cells: their records once
+    if (kBound == kBoundConst && tid < 2) {          // constant boundary cells: their records once
         const float *g = ghost + (size_t)lane * 8 + (tid ? 4 : 0);
         const float4 st = make_float4(g[0], g[1], g[2], g[3]);
         CellPre cg;
@@ -579,6 +589,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
                 arz_cell_pre((double)st.x, um, cp);
             }
             if (vc) { CellRec *own = CR + ic + 1; own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
+            if constexpr (kRing) ring_rec_copies(CR, Nv, vc, ic, st, cp);
         }
         if constexpr (kSched) sched_p = sched_lane + (size_t)s0 * L * 2;
         if (kSched && tid < 2) {                         // a schedule: row s0
@@ -627,10 +638,11 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
                 C0r[k] = c0r; C0y[k] = c0y;
                 C2r[k + 2] = c2r; C2y[k + 2] = c2y;
                 Gr[k + 1] = c1r; Gy[k + 1] = c1y;
+                // (a ring has no boundary cotangent: slot 0's goes to cell N - 1 and slot N + 1's to cell 0 in the hand-over below)
                 if constexpr (kSched) {
                     if (k == 0) gs_run[0] = make_double2((double)c0r, (double)c0y);               // (thread 0: gs_run is the row's entry 0)
                     if (k == N - 1) gs_run[1 - (tid & 1)] = make_double2((double)c2r, (double)c2y);
-                } else {
+                } else if constexpr (!kRing) {
                     if (k == 0) { ghl_r += (double)c0r; ghl_y += (double)c0y; }
                     if (k == N - 1) { ghr_r += (double)c2r; ghr_y += (double)c2y; }
                 }
@@ -641,8 +653,14 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
             for (int m = 0; m < 2; ++m) {
                 const int k = tid + m * B;
                 if (k < N) {
-                    const float c2lr = (k > 0) ? C2r[k + 1] : 0.f, c2ly = (k > 0) ? C2y[k + 1] : 0.f;
-                    const float c0rr = (k < N - 1) ? C0r[k + 1] : 0.f, c0ry = (k < N - 1) ? C0y[k + 1] : 0.f;
+                    float c2lr, c2ly, c0rr, c0ry;
+                    if constexpr (kRing) {           // the seam: c2 of cell N - 1 (slot N + 1) comes to cell 0, c0 of cell 0 (slot 0) to cell N - 1
+                        const int kl = (k > 0) ? k + 1 : N + 1, kr = (k < N - 1) ? k + 1 : 0;
+                        c2lr = C2r[kl]; c2ly = C2y[kl]; c0rr = C0r[kr]; c0ry = C0y[kr];
+                    } else {
+                        c2lr = (k > 0) ? C2r[k + 1] : 0.f; c2ly = (k > 0) ? C2y[k + 1] : 0.f;
+                        c0rr = (k < N - 1) ? C0r[k + 1] : 0.f; c0ry = (k < N - 1) ? C0y[k + 1] : 0.f;
+                    }
                     float nr = (Gr[k + 1] + c2lr) + c0rr;
                     float ny = (Gy[k + 1] + c2ly) + c0ry;
                     if (bad_step < 0 && !(isfinite(nr) && isfinite(ny))) { bad_step = step; bad_cell = k; }
@@ -658,7 +676,7 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
     }
     const BwdTail tl = *tail;                        // (read back: see BwdTail)
     for (int k = tid; k < N; k += B) { tl.g_r_out[k] = Gr[k + 1]; tl.g_y_out[k] = Gy[k + 1]; }
-    if (!kSched && tl.g_ghost) {
+    if (kBound == kBoundConst && tl.g_ghost) {
         if (tid == 0) { tl.g_ghost[0] = ghl_r; tl.g_ghost[1] = ghl_y; }
         if (tid == (N - 1) % B) { tl.g_ghost[2] = ghr_r; tl.g_ghost[3] = ghr_y; }
     }

@@ -29,6 +29,34 @@
 // copies for T = 0).
 // Dynamic LDS: the lane kernel's records (CellRec [N + 2] | flux double2 [N + 1] | queue int [N + 2] | 2 counters, rounded up to 16 B)
 //   | float4 PA [N + 1], PB [N + 1] | float2 TN [2 copies][kK][N + 2]   (index k + 1 of a copy = cell k)
+// kBoundRing (a closed lane, DESIGN 4l): behind its own record the owner of cell N - 1 writes the same record to slot 0 and the owner
+// of cell 0 to slot N + 1 -- the copies that interfaces 0 and N are solved from in phase 2, behind the barrier.  No thread reads slot
+// N + 1 in phase 1; slot 0 is read there by thread 0 alone, whose interface is queued whatever it finds.
+// Nv: the lane length in a VECTOR register (ring_len): the two slots are addressed from the thread's own one, N records below resp.
+// above it, so that the seam holds no scalar register across the step loop, where these kernels have none to spare.
+__device__ __forceinline__ int ring_len(int N) {
+    int Nv = N;
+    asm volatile("" : "+v"(Nv));
+    return Nv;
+}
+// One test per pass (ring_seam) covers both copies: an end cell that owns one of them only (N > 1) writes its own slot again in the
+// other's place (ring_lo / ring_hi = 0), the same bits it has just stored there.
+__device__ __forceinline__ bool ring_seam(int Nv, bool vc, unsigned ic) { return vc && (ic == 0u || (int)ic == Nv - 1); }
+__device__ __forceinline__ int ring_lo(int Nv, unsigned ic) { return (int)ic == Nv - 1 ? -Nv : 0; }       // slot 0 from cell N - 1's own
+__device__ __forceinline__ int ring_hi(int Nv, unsigned ic) { return ic == 0u ? Nv : 0; }                 // slot N + 1 from cell 0's own
+__device__ __forceinline__ void ring_rec_copies(CellRec *CR, int Nv, bool vc, unsigned ic, const float4 &st, const CellPre &cp) {
+    if (ring_seam(Nv, vc, ic)) {
+        CellRec *own = CR + ic + 1, *w = own + ring_lo(Nv, ic);
+        w->st = st; w->sh = make_double2(cp.s, cp.h); w->q0 = make_double2(cp.q0, 0.);
+        w = own + ring_hi(Nv, ic);
+        w->st = st; w->sh = make_double2(cp.s, cp.h); w->q0 = make_double2(cp.q0, 0.);
+    }
+}
+// ... and where scalar registers are to spare (the checkpointed forward): the two slots at their own addresses, a test each
+__device__ __forceinline__ void ring_rec_copies_direct(CellRec *CR, int N, bool vc, unsigned ic, const float4 &st, const CellPre &cp) {
+    if (vc && ic == (unsigned)(N - 1)) { CR[0].st = st; CR[0].sh = make_double2(cp.s, cp.h); CR[0].q0 = make_double2(cp.q0, 0.); }
+    if (vc && ic == 0u) { CR[N + 1].st = st; CR[N + 1].sh = make_double2(cp.s, cp.h); CR[N + 1].q0 = make_double2(cp.q0, 0.); }
+}
 __host__ __device__ inline size_t fwd_jvp_rec_bytes(int N) {       // = fwd2_lds_bytes(N) rounded up to 16
     return (sizeof(CellRec) * (size_t)(N + 2) + 16 * (size_t)(N + 1) + sizeof(int) * (size_t)(N + 2) + 16 + 15) & ~(size_t)15;
 }
@@ -38,13 +66,14 @@ __host__ __device__ inline size_t fwd_jvp_lds_bytes(int N, int kK) {
 
 // grid = L workgroups (one traffic lane each) of W = blockDim.x / 64 wavefronts, the lane kernel's mapping: wave w owns the cells
 // [64 p w, 64 p (w + 1)), thread t of its pass j the cell 64 p w + 64 j + t and that cell's LEFT interface.  kP: 64-cell passes per
-// wavefront as a literal (1 or 2; 0 = the run-time value p_arg), kSched / kTaps as in macro_rollout_fwd2_kernel (validity masks are
+// wavefront as a literal (1 or 2; 0 = the run-time value p_arg), kBound: constant boundary cells, a schedule (kSched) or a ring (kRing),
+// kSched / kTaps as in macro_rollout_fwd2_kernel (validity masks are
 // always on: the lane kernel's kFull saves a few selects and changes no value).  At most 12 wavefronts: the longest lane whose LDS fits
 // (1410 cells) has 12, and three wavefronts per SIMD leave the kernel 168 VGPRs -- two interleaved passes beside four directions
 // spill under the 128 of a 1024-thread block.
 // err: DHTS_FAULT_CFL (step, lane, interface), as the lane kernel raises it.  err_jvp: DHTS_FAULT_NAN with the lane's EARLIEST
 // (step, cell) of a non-finite tangent (jvp_raise_first).
-template <int kK, int kP, bool kSched, bool kTaps>
+template <int kK, int kP, MacroBoundary kBound, bool kTaps>
 __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     int L, int N, int T, int p_arg, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
@@ -54,6 +83,7 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     float *__restrict__ t_r_out, float *__restrict__ t_y_out,
     const int32_t *__restrict__ det, int n_det, float *__restrict__ taps, float *__restrict__ t_taps,
     dhts_error *err, dhts_error *err_jvp) {
+    constexpr bool kSched = kBound == kBoundSched, kRing = kBound == kBoundRing;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = blockIdx.x;
     const int tid = threadIdx.x;
@@ -77,11 +107,12 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
 
     for (int k = tid; k < N + 2; k += blockDim.x) {
         float4 st;
-        if (k == 0 || k == N + 1) {
+        if (!kRing && (k == 0 || k == N + 1)) {
             const float *g = ghost + (size_t)lane * 8 + (k ? 4 : 0);
             st = make_float4(g[0], g[1], g[2], g[3]);
         } else {
-            st = make_float4(r_in[base + k - 1], y_in[base + k - 1], u_in[base + k - 1], q_in[base + k - 1]);
+            const int kc_ = kRing ? (k == 0 ? N : (k == N + 1 ? 1 : k)) : k;      // a ring: slot 0 is cell N - 1, slot N + 1 is cell 0
+            st = make_float4(r_in[base + kc_ - 1], y_in[base + kc_ - 1], u_in[base + kc_ - 1], q_in[base + kc_ - 1]);
         }
         CellPre c;
         arz_cell_pre((double)st.x, um, c);
@@ -94,8 +125,14 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     __syncthreads();
     // the tangents of the initial state into copy 0
     for (int d = 0; d < n_act; ++d)
-        for (int k = tid; k < N; k += blockDim.x)
-            TN[d * P + k + 1] = make_float2(t_r_in[d * dir_state + base + k], t_y_in[d * dir_state + base + k]);
+        for (int k = tid; k < N; k += blockDim.x) {
+            const float2 v = make_float2(t_r_in[d * dir_state + base + k], t_y_in[d * dir_state + base + k]);
+            TN[d * P + k + 1] = v;
+            if constexpr (kRing) {
+                if (k == N - 1) TN[d * P] = v;
+                if (k == 0) TN[d * P + N + 1] = v;
+            }
+        }
 
     const int p = kP > 0 ? kP : p_arg;
     const int lo = wv * (p << 6);                    // first cell of this wave
@@ -107,6 +144,7 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     int bad_step = -1, bad_cell = 0;
     int rot = 0;                                     // the cell wave that takes the head of the queue rotates with the step
 
+    const int Nv = kRing && kTaps ? ring_len(N) : N; // (a ring with detectors, where no scalar register is to spare: see ring_rec_copies)
     constexpr bool kKeep = kP > 0;
     double rd_own[kP > 0 ? kP : 1], yd_own[kP > 0 ? kP : 1];
 
@@ -125,7 +163,7 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
         tap_wave = __builtin_amdgcn_readfirstlane((Wc - 1 - wv) << 6) < n_det;
         if (tap_j < n_det) det_own = det[tap_j];
     }
-    const bool bnd = ghost_mode != 0 && tap_j < 2 * kK && (tap_j >> 1) < n_act;
+    const bool bnd = !kRing && ghost_mode != 0 && tap_j < 2 * kK && (tap_j >> 1) < n_act;       // (a ring has no boundary tangent)
     const int bnd_slot = (tap_j >> 1) * P + ((tap_j & 1) ? N + 1 : 0);
     const float *bnd_src = bnd ? t_ghost + (size_t)(tap_j >> 1) * dir_ghost + (size_t)lane * 4 + 2 * (tap_j & 1) : nullptr;
     const size_t bnd_stride = (size_t)L * 4;
@@ -193,12 +231,19 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
                 JvpBlocks b;
                 cell_blocks(aL, bL, aR, bR, cf, ncf, b.d0, b.d1, b.d2);
                 bool fin = true;
+                const bool seam = kRing && ring_seam(Nv, vc, ic);
 #pragma unroll
                 for (int d = 0; d < kK; ++d) {
                     const float2 tl = tq[d * P + ic], tc = tq[d * P + ic + 1], tr = tq[d * P + ic + 2];
                     float nr, ny;
                     jvp_cell(b, tl.x, tl.y, tc.x, tc.y, tr.x, tr.y, nr, ny);
                     if (vc) tw[d * P + ic + 1] = make_float2(nr, ny);
+                    if constexpr (kRing) {                   // the copy step n reads: slot 0 is cell N - 1, slot N + 1 is cell 0
+                        if (seam) {
+                            float2 *own_t = tw + d * P + ic + 1;
+                            own_t[ring_lo(Nv, ic)] = make_float2(nr, ny); own_t[ring_hi(Nv, ic)] = make_float2(nr, ny);
+                        }
+                    }
                     fin = fin && isfinite(nr) && isfinite(ny);
                     if (!solve && vc && d < n_act) { t_r_out[d * dir_state + base + i] = nr; t_y_out[d * dir_state + base + i] = ny; }
                 }
@@ -212,6 +257,7 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
                 if (vc && solve) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
                 else if (kTaps && vc) own->st = st;          // the final step's state, for the taps below
+                if constexpr (kRing && solve) ring_rec_copies(CR, Nv, vc, ic, st, cp);
             }
             if (!solve) {
                 if (vc) { r_out[base + i] = st.x; y_out[base + i] = st.y; u_out[base + i] = st.z; q_out[base + i] = st.w; }
@@ -264,11 +310,11 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
             FX[i] = make_double2(f.Fr, f.Fy);
             PA[i] = make_float4(f.A[0], f.A[1], f.A[2], f.A[3]);
             PB[i] = make_float4(f.B[0], f.B[1], f.B[2], f.B[3]);
-            if (f.cfl_bad && fault_step < 0) { fault_step = n; fault_index = (int)i; }
+            if (f.cfl_bad && fault_step < 0) { fault_step = n; fault_index = (kRing && i == (unsigned)N) ? 0 : (int)i; }      // (a ring: N is 0)
         }
         __builtin_amdgcn_s_setprio(0);
         if constexpr (kTaps && upd) tap(n - 1);
-        if (ghost_mode == 2 && bnd && n + 1 < T) {           // row n + 1 into the copy step n + 1 reads
+        if (!kRing && ghost_mode == 2 && bnd && n + 1 < T) {           // row n + 1 into the copy step n + 1 reads
             TN[((n + 1) & 1) * kK * P + bnd_slot] = bnd_next;
             if (n + 2 < T) bnd_next = *reinterpret_cast<const float2 *>(bnd_src + (size_t)(n + 2) * bnd_stride);
         }

@@ -1517,6 +1517,10 @@ __global__ void macro_u_tap_bwd_kernel(int64_t n, float um, const float *__restr
 // ---- forward-mode tangent sweep over the rollout tape (dhts_macro_rollout_jvp) and its glue ----------------------
 #include "macro_jvp.inc"
 
+// How a lane of the tape-free kernels (macro_fwd_jvp.inc, macro_ckpt.inc) ends: in two boundary cells that are data -- constant, or a
+// schedule [T][L][2][4], what `bool kSched` says in the taped kernels above -- or in itself, a ring.
+enum MacroBoundary { kBoundConst = 0, kBoundSched = 1, kBoundRing = 2 };
+
 // ---- the rollout and its tangents in one kernel, no tape (dhts_macro_rollout_fwd_jvp) ----------------------------
 #include "macro_fwd_jvp.inc"
 
@@ -1636,7 +1640,9 @@ static MacroPlan macro_plan(const dhts_macro_desc *d, int T, bool want_hist, boo
 // point -- taped, tangent, fused and checkpointed -- fills one and hands it to its launcher; kSched, kTaps and the target kernels are
 // picked from it like every other template argument, so a further form is one more field here and one more pick there.
 struct MacroForm {
-    bool sched;           // the boundary cells are a schedule [T][L][2][4]; g_ghost is per step [T][L][2][2]
+    MacroBoundary bound;  // kBoundSched: the boundary cells are a schedule [T][L][2][4]; g_ghost is per step [T][L][2][2].  kBoundRing (the
+                          // tape-free launchers only): no boundary cells -- `ghost`, g_ghost and the boundary tangents are NULL
+    bool sched() const { return bound == kBoundSched; }
     const int32_t *det;   // detector cells [n_det], NULL: none
     int n_det;
     float *hist, *taps;   // forward: the state history [T][L][3][N] (not with detectors) resp. the readings [T][L][3][n_det]
@@ -1650,7 +1656,13 @@ struct MacroForm {
 };
 static MacroForm macro_form(int ghost_is_sched, const int32_t *det = nullptr, int n_det = 0) {
     MacroForm f = {};
-    f.sched = ghost_is_sched != 0; f.det = det; f.n_det = det ? n_det : 0;
+    f.bound = ghost_is_sched ? kBoundSched : kBoundConst; f.det = det; f.n_det = det ? n_det : 0;
+    return f;
+}
+// ... and of the tape-free entry points, which also take a ring
+static MacroForm macro_bound_form(MacroBoundary bound, const int32_t *det = nullptr, int n_det = 0) {
+    MacroForm f = macro_form(0, det, n_det);
+    f.bound = bound;
     return f;
 }
 // detectors and the array that goes with them (readings, their tangents or cotangents) come together or not at all
@@ -1697,7 +1709,7 @@ static int macro_fwd_launch(bool iface, const dhts_macro_desc *d, int T,
     W = (N + (64 * p - 1) - 1) / (64 * p - 1);
     bool lds_ok = true;
     pick<1, 0>(iface, [&](auto fc) {
-        pick<0, 1>(f.sched, [&](auto sc) {
+        pick<0, 1>(f.sched(), [&](auto sc) {
             pick<0, 1>(f.det != nullptr, [&](auto tp) {
                 constexpr bool kIface = decltype(fc)::value != 0, kS = decltype(sc)::value != 0, kT = decltype(tp)::value != 0;
                 if constexpr (kIface || (!kS && !kT))
@@ -1720,7 +1732,7 @@ static int macro_rollout_fwd_launch(const dhts_macro_desc *d, int T,
     const int N = d->n_cells;
     float4 *tp = reinterpret_cast<float4 *>(tape);
     bool lds_ok = true;
-    pick<0, 1>(f.sched, [&](auto sc) {
+    pick<0, 1>(f.sched(), [&](auto sc) {
         pick<0, 1>(f.det != nullptr, [&](auto tap) {
             constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
             if (pl.fwd == kMacroFwdLane) {
@@ -1764,14 +1776,14 @@ static int macro_blocks_bwd_launch(const dhts_macro_desc *d, int T, const float 
 // The reverse sweep of every form, as above.
 static int macro_rollout_bwd_launch(const dhts_macro_desc *d, int T, const float *tape, const float *g_r, const float *g_y,
                                     float *g_r_out, float *g_y_out, double *g_ghost, const MacroForm &f, dhts_error *err, void *stream) {
-    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out || (f.sched && !g_ghost)) return DHTS_E_INVALID;
+    if (!macro_desc_ok(d) || T < 0 || (T > 0 && !tape) || !g_r || !g_y || !g_r_out || !g_y_out || (f.sched() && !g_ghost)) return DHTS_E_INVALID;
     const MacroPlan pl = macro_plan(d, T, f.g_cot != nullptr && !f.det, tape != nullptr, f.det != nullptr);
     const int N = d->n_cells, B = pl.bwd_block;
     const float4 *tp = reinterpret_cast<const float4 *>(tape);
     const double cc = d->dt / d->dx;
     if (pl.lds_bwd > 160 * 1024) return DHTS_E_INVALID;
     bool lds_ok = true;
-    pick<0, 1>(f.sched, [&](auto sc) {
+    pick<0, 1>(f.sched(), [&](auto sc) {
         pick<0, 1>(f.det != nullptr, [&](auto tap) {
             constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
             if (pl.bwd == kMacroBwdFast) {
@@ -1835,13 +1847,13 @@ struct MacroTangents {
     float *r_out, *y_out, *taps;
 };
 static MacroTangents macro_tangents_at(const MacroTangents &t, int k0, const dhts_macro_desc *d, int T, const MacroForm &f) {
-    const size_t dir_state = (size_t)d->n_lanes * d->n_cells, dir_ghost = (f.sched ? (size_t)T : 1) * d->n_lanes * 4,
+    const size_t dir_state = (size_t)d->n_lanes * d->n_cells, dir_ghost = (f.sched() ? (size_t)T : 1) * d->n_lanes * 4,
                  dir_taps = (size_t)T * d->n_lanes * 2 * f.n_det;
     return {t.r + k0 * dir_state, t.y + k0 * dir_state, t.ghost ? t.ghost + k0 * dir_ghost : nullptr,
             t.r_out + k0 * dir_state, t.y_out + k0 * dir_state, f.det ? t.taps + k0 * dir_taps : nullptr};
 }
 // how the kernels read t_ghost: 0 none, 1 the same in front of every step, 2 a schedule
-static int macro_ghost_mode(const MacroTangents &t, const MacroForm &f) { return !t.ghost ? 0 : (f.sched ? 2 : 1); }
+static int macro_ghost_mode(const MacroTangents &t, const MacroForm &f) { return !t.ghost ? 0 : (f.sched() ? 2 : 1); }
 // T == 0 of both: the tangents come back as they went in, no row is read or written
 static bool macro_tangents_copy(const dhts_macro_desc *d, int n_dir, const MacroTangents &t, void *stream) {
     const size_t bytes = sizeof(float) * (size_t)n_dir * d->n_lanes * d->n_cells;
@@ -1915,10 +1927,11 @@ static int macro_fwd_jvp_launch(const dhts_macro_desc *d, int T, int n_dir, cons
         dhts_error *o_err = k0 == 0 ? err : nullptr;
         bool ok = true;
         pick<0, 1, 2>(pl.p <= 2 ? pl.p : 0, [&](auto pv) {
-            pick<0, 1>(f.sched, [&](auto sc) {
+            pick<kBoundConst, kBoundSched, kBoundRing>(f.bound, [&](auto bc) {
                 pick<0, 1>(f.det != nullptr, [&](auto tap) {
                     constexpr int kK = decltype(kv)::value, kP = decltype(pv)::value;
-                    constexpr bool kS = decltype(sc)::value != 0, kT = decltype(tap)::value != 0;
+                    constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
+                    constexpr bool kT = decltype(tap)::value != 0;
                     ok = launch_lds(macro_rollout_fwd_jvp_kernel<kK, kP, kS, kT>, L, 64 * pl.W, fwd_jvp_lds_bytes(N, kK), kLdsDefault, stream, L,
                                     N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, a.r, a.y, a.ghost, ghost_mode, n_act, r_out, y_out,
                                     u_out, ueq_out, a.r_out, a.y_out, f.det, f.n_det, o_taps, a.taps, o_err, err_jvp);
@@ -2002,10 +2015,10 @@ static int macro_ckpt_fwd_launch(const dhts_macro_desc *d, int T, int S, const M
                             y_out, u_out, ueq_out, reinterpret_cast<float2 *>(ckpt), err, tail...);
     };
     pick<1, 2>(pl.p, [&](auto pv) {
-        pick<0, 1>(f.sched, [&](auto sc) {
+        pick<kBoundConst, kBoundSched, kBoundRing>(f.bound, [&](auto bc) {
             pick<0, 1, 2>(f.target ? 2 : f.det != nullptr, [&](auto tap) {
                 constexpr int kP = decltype(pv)::value, kForm = decltype(tap)::value;
-                constexpr bool kS = decltype(sc)::value != 0;
+                constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
                 if constexpr (kForm == 2) go(macro_rollout_ckpt_fwd_target_kernel<kP, kS>, f.target, f.sse);
                 else go(macro_rollout_ckpt_fwd_kernel<kP, kS, kForm != 0>, f.det, f.n_det, f.taps);
             });
@@ -2023,9 +2036,9 @@ static int macro_ckpt_bwd_launch(const dhts_macro_desc *d, int T, int S, const M
         lds_ok = launch_lds(kernel, L, 64 * pl.W, lds, kLdsDefault, stream, L, N, T, S, pl.p, d->dt, d->dx, d->u_max,
                             reinterpret_cast<const float2 *>(ckpt), r, y, u, ueq, ghost, g_r, g_y, f.g_cot, g_r_out, g_y_out, g_ghost, err, tail...);
     };
-    pick<0, 1>(f.sched, [&](auto sc) {
+    pick<kBoundConst, kBoundSched, kBoundRing>(f.bound, [&](auto bc) {
         pick<0, 1, 2>(f.target ? 2 : f.det != nullptr, [&](auto tap) {
-            constexpr bool kS = decltype(sc)::value != 0;
+            constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
             constexpr int kForm = decltype(tap)::value;
             if constexpr (kForm == 2)
                 go(macro_rollout_ckpt_bwd_target_kernel<kS>, macro_ckpt_bwd_lds_bytes(N, S, true), f.target, f.g_sse, f.fin_r, f.fin_y, f.fin_u);
@@ -2204,13 +2217,17 @@ int dhts_macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, i
     return DHTS_OK;
 }
 // ---- the rollout and its tangents in one kernel, no tape ------------------------------------------------------------------------
-int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
-                               const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+// (the bodies of the tape-free entry points take the form's boundary: of a ring, `ghost`, t_ghost and g_ghost are NULL and nothing is
+// asked of them -- ring_or(bound, r, ghost) hands the shared checks a pointer they accept in the boundary cells' place)
+static inline const float *ring_or(MacroBoundary bound, const float *r, const float *ghost) { return bound == kBoundRing ? r : ghost; }
+static int macro_rollout_fwd_jvp_entry(const dhts_macro_desc *d, int T, int n_dir,
+                               const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                const float *t_r, const float *t_y, const float *t_ghost,
                                float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
                                const int32_t *det, int n_det, float *taps, float *t_taps,
                                dhts_error *err, dhts_error *err_jvp, void *stream) {
-    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || n_dir < 1 || !t_r || !t_y || !t_r_out || !t_y_out)
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ring_or(bound, r, ghost), r_out, y_out, u_out, ueq_out) || n_dir < 1 || !t_r || !t_y ||
+        !t_r_out || !t_y_out)
         return DHTS_E_INVALID;
     if (!macro_det_pair_ok(d, det, n_det, taps) || !macro_det_pair_ok(d, det, n_det, t_taps)) return DHTS_E_INVALID;
     if (macro_fwd_jvp_plan(d, T, n_dir).kmax < 1) return DHTS_E_INVALID;       // the lane does not fit: the taped pair covers it
@@ -2219,9 +2236,26 @@ int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
         if (!macro_tangents_copy(d, n_dir, t, stream)) return DHTS_E_LAUNCH;
         return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
     }
-    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    MacroForm f = macro_bound_form(bound, det, n_det);
     f.taps = taps;
     return macro_fwd_jvp_launch(d, T, n_dir, r, y, u, ueq, ghost, t, r_out, y_out, u_out, ueq_out, f, err, err_jvp, stream);
+}
+int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
+                               const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                               const float *t_r, const float *t_y, const float *t_ghost,
+                               float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                               const int32_t *det, int n_det, float *taps, float *t_taps,
+                               dhts_error *err, dhts_error *err_jvp, void *stream) {
+    return macro_rollout_fwd_jvp_entry(d, T, n_dir, r, y, u, ueq, ghost, ghost_is_sched ? kBoundSched : kBoundConst, t_r, t_y, t_ghost, r_out,
+                                       y_out, u_out, ueq_out, t_r_out, t_y_out, det, n_det, taps, t_taps, err, err_jvp, stream);
+}
+int dhts_macro_rollout_fwd_jvp_ring(const dhts_macro_desc *d, int T, int n_dir,
+                                    const float *r, const float *y, const float *u, const float *ueq, const float *t_r, const float *t_y,
+                                    float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                                    const int32_t *det, int n_det, float *taps, float *t_taps,
+                                    dhts_error *err, dhts_error *err_jvp, void *stream) {
+    return macro_rollout_fwd_jvp_entry(d, T, n_dir, r, y, u, ueq, nullptr, kBoundRing, t_r, t_y, nullptr, r_out, y_out, u_out, ueq_out,
+                                       t_r_out, t_y_out, det, n_det, taps, t_taps, err, err_jvp, stream);
 }
 int dhts_macro_fwd_jvp_plan(const dhts_macro_desc *d, int T, int n_dir, int n_det, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || n_dir < 1 || !plan || n_det < 0 || n_det > d->n_cells) return DHTS_E_INVALID;
@@ -2241,32 +2275,46 @@ size_t dhts_macro_ckpt_bytes(const dhts_macro_desc *d, int T, int segment) {
     if (S < 0) return 0;
     return (size_t)macro_ckpt_count(T, S) * d->n_lanes * macro_ckpt_row_bytes(d->n_cells);
 }
-int dhts_macro_rollout_fwd_ckpt(const dhts_macro_desc *d, int T, int segment,
-                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+static int macro_rollout_fwd_ckpt_entry(const dhts_macro_desc *d, int T, int segment,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                 float *r_out, float *y_out, float *u_out, float *ueq_out,
                                 const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream) {
-    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || (T > 0 && !ckpt)) return DHTS_E_INVALID;
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ring_or(bound, r, ghost), r_out, y_out, u_out, ueq_out) || (T > 0 && !ckpt)) return DHTS_E_INVALID;
     if (!macro_det_pair_ok(d, det, n_det, taps)) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d);
     const int S = macro_ckpt_segment(pl, segment);
     if (S < 0) return DHTS_E_INVALID;
     if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
-    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    MacroForm f = macro_bound_form(bound, det, n_det);
     f.taps = taps;
     return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, ckpt, f, err, stream);
 }
+int dhts_macro_rollout_fwd_ckpt(const dhts_macro_desc *d, int T, int segment,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream) {
+    return macro_rollout_fwd_ckpt_entry(d, T, segment, r, y, u, ueq, ghost, ghost_is_sched ? kBoundSched : kBoundConst, r_out, y_out, u_out,
+                                        ueq_out, det, n_det, taps, ckpt, err, stream);
+}
+int dhts_macro_rollout_fwd_ckpt_ring(const dhts_macro_desc *d, int T, int segment,
+                                     const float *r, const float *y, const float *u, const float *ueq,
+                                     float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                     const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream) {
+    return macro_rollout_fwd_ckpt_entry(d, T, segment, r, y, u, ueq, nullptr, kBoundRing, r_out, y_out, u_out, ueq_out, det, n_det, taps,
+                                        ckpt, err, stream);
+}
 // what both checkpointed reverse entry points ask of the replay's inputs, the seeds and the outputs
 static inline bool macro_replay_args_ok(const dhts_macro_desc *d, int T, const void *ckpt, const float *r, const float *y, const float *u,
-                                        const float *ueq, const float *ghost, int ghost_is_sched, const float *g_r, const float *g_y,
+                                        const float *ueq, const float *ghost, MacroBoundary bound, const float *g_r, const float *g_y,
                                         const float *g_r_out, const float *g_y_out, const double *g_ghost) {
-    return macro_desc_ok(d) && T >= 0 && (T == 0 || ckpt) && r && y && u && ueq && ghost && g_r && g_y && g_r_out && g_y_out &&
-           (!ghost_is_sched || g_ghost);
+    return macro_desc_ok(d) && T >= 0 && (T == 0 || ckpt) && r && y && u && ueq && ring_or(bound, r, ghost) && g_r && g_y && g_r_out &&
+           g_y_out && (bound != kBoundSched || g_ghost);
 }
-int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
-                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+static int macro_rollout_bwd_ckpt_entry(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                 const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
                                 float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
-    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
+    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
     if (!macro_det_pair_ok(d, det, n_det, g_taps)) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d);
     const int S = macro_ckpt_segment(pl, segment);
@@ -2274,25 +2322,40 @@ int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, co
     if (T == 0) {        // no step: the cotangents come back as they went in, the boundary sums are zero, no row is addressed
         const size_t bytes = sizeof(float) * (size_t)d->n_lanes * d->n_cells;
         if (!macro_copy_back(g_r_out, g_r, bytes, stream) || !macro_copy_back(g_y_out, g_y, bytes, stream)) return DHTS_E_LAUNCH;
-        if (!ghost_is_sched && g_ghost &&
+        if (bound == kBoundConst && g_ghost &&
             hipMemsetAsync(g_ghost, 0, sizeof(double) * 4 * (size_t)d->n_lanes, (hipStream_t)stream) != hipSuccess)
             return DHTS_E_LAUNCH;
         return DHTS_OK;
     }
-    MacroForm f = macro_form(ghost_is_sched, det, n_det);
+    MacroForm f = macro_bound_form(bound, det, n_det);
     f.g_cot = g_taps;
     return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
+}
+int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
+    return macro_rollout_bwd_ckpt_entry(d, T, segment, ckpt, r, y, u, ueq, ghost, ghost_is_sched ? kBoundSched : kBoundConst, g_r, g_y, det,
+                                        n_det, g_taps, g_r_out, g_y_out, g_ghost, err, stream);
+}
+int dhts_macro_rollout_bwd_ckpt_ring(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                     const float *r, const float *y, const float *u, const float *ueq,
+                                     const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                     float *g_r_out, float *g_y_out, dhts_error *err, void *stream) {
+    return macro_rollout_bwd_ckpt_entry(d, T, segment, ckpt, r, y, u, ueq, nullptr, kBoundRing, g_r, g_y, det, n_det, g_taps, g_r_out,
+                                        g_y_out, nullptr, err, stream);
 }
 // ---- the dense-fit loss inside the checkpointed pair ----------------------------------------------------------------------------
 int dhts_macro_ckpt_target_plan(const dhts_macro_desc *d, int T, int segment, int32_t plan[8]) {
     if (!macro_desc_ok(d) || T < 0 || !plan || segment < 0) return DHTS_E_INVALID;
     return macro_ckpt_plan_fill(d, T, segment, true, plan);
 }
-int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segment,
-                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+static int macro_rollout_fwd_ckpt_target_entry(const dhts_macro_desc *d, int T, int segment,
+                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                        float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const float *target, double *sse,
                                        dhts_error *err, void *stream) {
-    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out) || !sse || (T > 0 && !target)) return DHTS_E_INVALID;
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ring_or(bound, r, ghost), r_out, y_out, u_out, ueq_out) || !sse || (T > 0 && !target))
+        return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d, true);
     const int S = macro_ckpt_segment(pl, segment);
     if (S < 0) return DHTS_E_INVALID;
@@ -2300,27 +2363,57 @@ int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segm
         if (hipMemsetAsync(sse, 0, sizeof(double) * 2 * (size_t)d->n_lanes, (hipStream_t)stream) != hipSuccess) return DHTS_E_LAUNCH;
         return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
     }
-    MacroForm f = macro_form(ghost_is_sched);
+    MacroForm f = macro_bound_form(bound);
     f.target = target; f.sse = sse;
     return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, ckpt, f, err, stream);
 }
-int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segment,
                                        const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                       float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const float *target, double *sse,
+                                       dhts_error *err, void *stream) {
+    return macro_rollout_fwd_ckpt_target_entry(d, T, segment, r, y, u, ueq, ghost, ghost_is_sched ? kBoundSched : kBoundConst, r_out, y_out,
+                                               u_out, ueq_out, ckpt, target, sse, err, stream);
+}
+int dhts_macro_rollout_fwd_ckpt_target_ring(const dhts_macro_desc *d, int T, int segment,
+                                            const float *r, const float *y, const float *u, const float *ueq,
+                                            float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const float *target,
+                                            double *sse, dhts_error *err, void *stream) {
+    return macro_rollout_fwd_ckpt_target_entry(d, T, segment, r, y, u, ueq, nullptr, kBoundRing, r_out, y_out, u_out, ueq_out, ckpt, target,
+                                               sse, err, stream);
+}
+static int macro_rollout_bwd_ckpt_target_entry(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                        const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
                                        const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out, double *g_ghost,
                                        dhts_error *err, void *stream) {
-    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
+    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
     // the fit's cotangent needs the observations and the forward's final state (row T - 1 of the history)
     if (T > 0 && (!target || (g_sse && (!r_fin || !y_fin || !u_fin)))) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d, true);
     const int S = macro_ckpt_segment(pl, segment);
     if (S < 0) return DHTS_E_INVALID;
     if (T == 0 || !g_sse)            // no step, or no cotangent of the sums: the plain sweep (the segment is the TARGET plan's, which fits it)
-        return dhts_macro_rollout_bwd_ckpt(d, T, S, ckpt, r, y, u, ueq, ghost, ghost_is_sched, g_r, g_y, nullptr, 0, nullptr, g_r_out, g_y_out,
-                                           g_ghost, err, stream);
-    MacroForm f = macro_form(ghost_is_sched);
+        return macro_rollout_bwd_ckpt_entry(d, T, S, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, nullptr, 0, nullptr, g_r_out, g_y_out,
+                                            g_ghost, err, stream);
+    MacroForm f = macro_bound_form(bound);
     f.target = target; f.g_sse = g_sse; f.fin_r = r_fin; f.fin_y = y_fin; f.fin_u = u_fin;
     return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
+}
+int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                       const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                       const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
+                                       const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out, double *g_ghost,
+                                       dhts_error *err, void *stream) {
+    return macro_rollout_bwd_ckpt_target_entry(d, T, segment, ckpt, r, y, u, ueq, ghost, ghost_is_sched ? kBoundSched : kBoundConst, g_r, g_y,
+                                               target, g_sse, r_fin, y_fin, u_fin, g_r_out, g_y_out, g_ghost, err, stream);
+}
+int dhts_macro_rollout_bwd_ckpt_target_ring(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                            const float *r, const float *y, const float *u, const float *ueq,
+                                            const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
+                                            const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out,
+                                            dhts_error *err, void *stream) {
+    return macro_rollout_bwd_ckpt_target_entry(d, T, segment, ckpt, r, y, u, ueq, nullptr, kBoundRing, g_r, g_y, target, g_sse, r_fin, y_fin,
+                                               u_fin, g_r_out, g_y_out, nullptr, err, stream);
 }
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,
                                  void *stream) {

@@ -157,6 +157,11 @@ SIGNATURES = {
     "dhts_micro_ckpt_target_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
     "dhts_micro_rollout_fwd_ckpt_target": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 14),
     "dhts_micro_rollout_bwd_ckpt_target": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 17),
+    "dhts_macro_rollout_fwd_ckpt_ring": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 9 + [C.c_int] + [_P] * 4),
+    "dhts_macro_rollout_bwd_ckpt_ring": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 8 + [C.c_int] + [_P] * 5),
+    "dhts_macro_rollout_fwd_ckpt_target_ring": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 13),
+    "dhts_macro_rollout_bwd_ckpt_target_ring": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 16),
+    "dhts_macro_rollout_fwd_jvp_ring": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 13 + [C.c_int] + [_P] * 5),
     "dhts_micro_rollout_fwd_ckpt_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 9 + [C.c_int, C.c_int] + [_P] * 3),
     "dhts_micro_rollout_bwd_ckpt_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 7 + [C.c_int, C.c_int] + [_P] * 6),
     "dhts_micro_rollout_fwd_jvp_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 13 + [C.c_int, C.c_int] + [_P] * 5),

@@ -19,7 +19,7 @@ def _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u):
         if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] < 1:
             raise ValueError("%s must be a tensor with a leading direction axis K >= 1" % n)
     K = int(given[0][1].shape[0])
-    want_g = (K, int(T), L, 2) if ghost_r.dim() == 3 else (K, L, 2)
+    want_g = (K, int(T), L, 2) if ghost_r is not None and ghost_r.dim() == 3 else (K, L, 2)
     for n, t in given:
         want = (K, L, N) if n in ("t_r0", "t_u0") else want_g
         if tuple(t.shape) != want:
@@ -29,7 +29,7 @@ def _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u):
 
 
 def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, t_u0=None, t_ghost_r=None, t_ghost_u=None,
-                      detectors=None, check_faults=True, fused=False):
+                      detectors=None, check_faults=True, fused=False, ring=False):
     """dhts.macro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((rT, yT, uT, qT[, readings]), (t_rT, t_yT, t_uT[, t_readings])).  The primal outputs are those of
@@ -48,15 +48,21 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
     fused=False for every K (1.04x, 1.08x at K = 1, 2; 1.8x at K = 3, 4; 2.4x at K = 8); at 4096 x 64 x 1000 with four detectors it
     takes 0.74, 0.79 of the taped time at K = 1, 2 and 1.16 .. 1.61 from K = 3 on (0.89 at K = 3, 4 at 3328 lanes, which
     a launch of four holds on the chip at once).  Choose it when the tape is what limits T, or for few directions on short lanes.
-    Lanes of more than 1410 cells do not fit it (ValueError before anything is launched; fused=False covers them)."""
-    if ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3):
+    Lanes of more than 1410 cells do not fit it (ValueError before anything is launched; fused=False covers them).
+
+    ring=True (with fused=True only; ghost_r, ghost_u, t_ghost_r and t_ghost_u None): the lane is closed as in dhts.macro_rollout(ring=True)
+    (dhts_macro_rollout_fwd_jvp_ring); the tangents of the two end cells are each other's boundary tangents."""
+    ops._macro_ring_checks(ring, ghost_r, ghost_u, t_ghost_r, t_ghost_u, fused=fused, r0=r0, u0=u0)
+    if not ring and (ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3)):
         raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
     T = int(T)
     K = _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u)
     L, N = r0.shape
-    sched = ghost_r.dim() == 3
+    sched = not ring and ghost_r.dim() == 3
     want = (T, L, 2) if sched else (L, 2)
-    if tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want or tuple(u0.shape) != (L, N):
+    if ring and tuple(u0.shape) != (L, N):
+        raise ValueError("u0 must have the shape of r0")
+    if not ring and (tuple(ghost_r.shape) != want or tuple(ghost_u.shape) != want or tuple(u0.shape) != (L, N)):
         raise ValueError("u0 must have the shape of r0, ghost_r and ghost_u shape %s" % (want,))
     det = None if detectors is None else ops._detector_indices(detectors, N, r0.device)
     desc = ops.macro_desc(L, N, dt, dx, u_max)
@@ -64,7 +70,11 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
         raise ValueError("macro_rollout_jvp(fused=True): a lane of %d cells does not fit the fused forward + tangent kernel (its records, "
                          "the interface products and the tangent copies exceed the LDS of a workgroup); fused=False covers it" % N)
     with torch.no_grad():
-        r0c, u0c, gr, gu, _, y0, q0, ghost = ops._macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
+        if ring:                             # no boundary cells: ghost None is the ring form of ops.macro_rollout_fwd_jvp
+            r0c, u0c = ops._f32c(r0.detach(), "r0"), ops._f32c(u0.detach(), "u0")
+            (y0, q0), ghost = ops.macro_state_from_ru(r0c, u0c, u_max), None
+        else:
+            r0c, u0c, gr, gu, _, y0, q0, ghost = ops._macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
         readings = None
         if not fused:
             # the forward rollout with a tape, as MacroRollout.forward runs it

@@ -459,6 +459,118 @@ class MacroRolloutTarget(torch.autograd.Function):
         return _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * desc.n_lanes)) + (None,) * 7
 
 
+class MacroRolloutRing(torch.autograd.Function):
+    """MacroRollout's checkpointed call on a closed lane: (r0, u0 [L][N]) -> (rT, yT, uT, qT[, readings [T][L][3][D]]) with cell N - 1 the
+    left neighbour of cell 0 (dhts_macro_rollout_fwd_ckpt_ring / _bwd_ckpt_ring).  The dependence of each end on the other is inside the
+    kernels: what the sweep sends through an end arrives at the other end in the same step; no boundary cell and no gradient of one
+    exists."""
+
+    @staticmethod
+    def forward(ctx, r0, u0, T, dt, dx, u_max, check_faults, det, checkpoint):
+        L, N = r0.shape
+        desc = macro_desc(L, N, dt, dx, u_max)
+        segment = _macro_checkpoint_segment(checkpoint, desc, T, False, 0 if det is None else int(det.numel()))
+        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
+        need_grad = r0.requires_grad or u0.requires_grad
+        err = new_error_record(r0.device)
+        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=r0.device)
+        (rT, yT, uT, qT), steps = macro_rollout_fwd_ckpt_ring(desc, T, r0c, y0, u0c, q0, ckpt, segment=segment, det=det, err=err)
+        if check_faults:
+            raise_on_fault(err)
+        if need_grad:
+            ctx.ckpt, ctx.replay = ckpt, (y0, q0)
+            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
+            ctx.save_for_backward(r0c, u0c, rT, yT, steps, det)
+        ctx.mark_non_differentiable(qT)
+        return (rT, yT, uT, qT) if steps is None else (rT, yT, uT, qT, steps)
+
+    @staticmethod
+    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_steps=None):
+        r0, u0, rT, yT, steps, det = ctx.saved_tensors
+        desc, T, um = ctx.desc, ctx.T, ctx.u_max
+        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
+        gs = None
+        if steps is not None and g_steps is not None and g_steps.numel():      # (T = 0: no row, and an empty tensor has no address)
+            gs = _per_step_cotangent(steps, g_steps, um, rows=_glue_rows(T, desc.n_lanes * steps.shape[3]))
+        err = new_error_record(r0.device)
+        y0, q0 = ctx.replay
+        g_r0, g_y0 = macro_rollout_bwd_ckpt_ring(desc, T, ctx.ckpt, r0, y0, u0, q0, g_r, g_y, segment=ctx.segment,
+                                                 det=det if gs is not None else None, g_taps=gs, err=err)
+        del gs, y0, q0                   # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
+        ctx.replay = ctx.ckpt = None
+        return _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0) + (None,) * 7
+
+
+class MacroRolloutRingTarget(torch.autograd.Function):
+    """MacroRolloutTarget on a closed lane: (r0, u0 [L][N]) -> (rT, yT, uT, qT, sse [L][2] float64)
+    (dhts_macro_rollout_fwd_ckpt_target_ring / _bwd_ckpt_target_ring)."""
+
+    @staticmethod
+    def forward(ctx, r0, u0, T, dt, dx, u_max, check_faults, checkpoint, target):
+        L, N = r0.shape
+        desc = macro_desc(L, N, dt, dx, u_max)
+        segment = _macro_target_segment(checkpoint, desc, T)
+        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
+        need_grad = r0.requires_grad or u0.requires_grad
+        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=r0.device) if need_grad else None
+        err = new_error_record(r0.device)
+        (rT, yT, uT, qT), sse = macro_rollout_fwd_ckpt_target_ring(desc, T, r0c, y0, u0c, q0, ckpt, target, segment=segment, err=err)
+        if check_faults:
+            raise_on_fault(err)
+        if need_grad:
+            ctx.ckpt, ctx.replay, ctx.target = ckpt, (y0, q0), target
+            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
+            ctx.save_for_backward(r0c, u0c, rT, yT, uT)
+        ctx.mark_non_differentiable(qT)
+        return rT, yT, uT, qT, sse
+
+    @staticmethod
+    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_sse):
+        r0, u0, rT, yT, uT = ctx.saved_tensors
+        desc, T, um = ctx.desc, ctx.T, ctx.u_max
+        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
+        err = new_error_record(r0.device)
+        y0, q0 = ctx.replay
+        g_r0, g_y0 = macro_rollout_bwd_ckpt_target_ring(desc, T, ctx.ckpt, r0, y0, u0, q0, g_r, g_y, ctx.target,
+                                                        g_sse=g_sse.contiguous() if g_sse is not None else None, final=(rT, yT, uT),
+                                                        segment=ctx.segment, err=err)
+        del y0, q0
+        ctx.replay = ctx.ckpt = None
+        return _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0) + (None,) * 7
+
+
+def _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0):
+    """_macro_bwd_done without boundary cells -> (g_r0, g_u0)."""
+    if ctx.check_faults:
+        raise_on_fault(err)
+    return g_r0, macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, ctx.u_max)
+
+
+def _macro_ring_checks(ring, ghost_r, ghost_u, t_ghost_r=None, t_ghost_u=None, want_hist=False, checkpoint=None, fused=None, r0=None,
+                       u0=None):
+    """Every ValueError of `ring=True` of dhts.macro_rollout (fused None) and dhts.macro_rollout_jvp (checkpoint None), raised before
+    anything touches a device.  Without `ring` nothing is checked here but `ring` itself: it is a bool (whoever hands `target` or
+    `checkpoint` over by position, where `ring` now stands in front of them, is told so instead of getting another rollout)."""
+    if not isinstance(ring, bool):
+        raise ValueError("ring must be True or False (got %s): target= and checkpoint= are passed by keyword" % type(ring).__name__)
+    if not ring:
+        return
+    if fused is None and (checkpoint is None or checkpoint is False):
+        raise ValueError("ring lives on the checkpointed path only: pass checkpoint=True (or a segment length)")
+    if fused is not None and not fused:
+        raise ValueError("ring lives on the fused forward + tangent kernel only: pass fused=True")
+    if ghost_r is not None or ghost_u is not None:
+        raise ValueError("ghost_r and ghost_u must be None when ring: a closed lane has no boundary cells")
+    if t_ghost_r is not None or t_ghost_u is not None:
+        raise ValueError("t_ghost_r and t_ghost_u must be None when ring: a closed lane has no boundary cells")
+    if want_hist:
+        raise ValueError("ring does not take want_hist: pass target= for the dense fit, or detectors=range(N) for every cell's readings")
+    if r0 is not None and (r0.dim() != 2 or tuple(u0.shape) != tuple(r0.shape)):
+        raise ValueError("r0 must be [L][N] and u0 must have its shape (got %s and %s)" % (tuple(r0.shape), tuple(u0.shape)))
+
+
 # ---- what the two macro autograd Functions (and dhts.jvp.macro_rollout_jvp) share: the leaves, the backward's seeds and tail, the segment ----
 def _macro_boundary_form(L, ghost_r, ghost_u, T):
     """-> whether (ghost_r, ghost_u) are a schedule [T][L][2] (else [L][2]); ValueError for anything else."""
@@ -579,8 +691,8 @@ def _detector_cells(detectors, N):
     return cells
 
 
-def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None, target=None,
-                  checkpoint=None):
+def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None, ring=False,
+                  target=None, checkpoint=None):
     """T fused differentiable steps of L straight ARZ lanes (MacroRollout): returns (rT, yT, uT, qT), with want_hist also hist [T][L][3][N].
     checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape; MacroRollout).
 
@@ -595,7 +707,23 @@ def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, c
     not requiring grad -- target[t][l][0][k] the density of cell k after step t (hist[t][l][0][k]), target[t][l][1][k] the speed
     (hist[t][l][2][k]), NaN = not observed.  Returns (rT, yT, uT, qT, sse) then: sse float64 [L][2], per lane the sum of the squared
     float32 density residuals and of the squared speed residuals, differentiable; the kernels read target themselves and neither a
-    history nor its cotangent exists (MacroRolloutTarget).  The segment is that of macro_ckpt_target_plan."""
+    history nor its cotangent exists (MacroRolloutTarget).  The segment is that of macro_ckpt_target_plan.
+
+    ring=True (with checkpoint only; ghost_r and ghost_u None; not with want_hist): the lane is closed, cell N - 1 is the left neighbour
+    of cell 0 and the circumference is N dx (MacroRolloutRing, MacroRolloutRingTarget).  detectors and target as above.  The
+    lane's mass sum_k r[k] is conserved up to the float32 store of each cell, and the gradient carries the dependence of each end on the
+    other."""
+    _macro_ring_checks(ring, ghost_r, ghost_u, want_hist=want_hist, checkpoint=checkpoint, r0=r0, u0=u0)
+    if ring:
+        if target is not None:
+            _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
+            return MacroRolloutRingTarget.apply(r0, u0, int(T), float(dt), float(dx), float(u_max), check_faults, checkpoint, target)
+        det = None if detectors is None else _detector_cells(detectors, int(r0.shape[-1]))
+        _macro_checkpoint_segment(checkpoint, macro_desc(int(r0.shape[0]), int(r0.shape[1]), float(dt), float(dx), float(u_max)), int(T),
+                                  False, 0 if det is None else len(det))
+        if isinstance(det, list):
+            det = torch.tensor(det, dtype=torch.int32, device=r0.device)
+        return MacroRolloutRing.apply(r0, u0, int(T), float(dt), float(dx), float(u_max), check_faults, det, checkpoint)
     if target is not None:
         _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
         return MacroRolloutTarget.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), check_faults, checkpoint, target)
@@ -718,15 +846,19 @@ def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, 
     for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
         if tuple(t.shape) != (L, N):
             raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
-    sched = ghost.dim() == 4
+    ring = ghost is None             # (macro_rollout_fwd_jvp_ring)
+    sched = not ring and ghost.dim() == 4
     want = (T, L, 2, 4) if sched else (L, 2, 4)
-    if tuple(ghost.shape) != want:
+    if not ring and tuple(ghost.shape) != want:
         raise ValueError("ghost must have shape (%d, 2, 4) or (%d, %d, 2, 4)" % (L, T, L))
+    if ring and t_ghost is not None:
+        raise ValueError("a ring has no boundary cells and no t_ghost")
     K = _macro_directions(desc, t_r, t_y)
     if macro_fwd_jvp_plan(desc, T, K)["dirs_per_launch"] < 1:
         raise ValueError("a lane of %d cells does not fit the fused forward + tangent kernel (its records, the interface products and "
                          "the tangent copies exceed the LDS of a workgroup); fused=False, the taped pair, covers it" % N)
-    r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, "ghost")))
+    r, y, u, ueq = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq")))
+    ghost = None if ring else _f32c(ghost, "ghost")
     t_r, t_y = _f32c(t_r, "t_r"), _f32c(t_y, "t_y")
     if sched and T == 0:        # an empty tensor has no address; the entry point wants one and reads no row
         ghost = torch.zeros(1, L, 2, 4, dtype=torch.float32, device=r.device)
@@ -738,6 +870,11 @@ def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, 
         if len(out) != 6:
             raise ValueError("out must be (r_out, y_out, u_out, ueq_out, t_r_out, t_y_out)")
     out = _state_out(("r_out", "y_out", "u_out", "ueq_out", "t_r_out", "t_y_out"), out, (r, y, u, ueq, t_r, t_y))
+    if ring:
+        check(_lib.lib().dhts_macro_rollout_fwd_jvp_ring(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(t_r), _ptr(t_y),
+                                                         *(_ptr(o) for o in out), _ptr(det), D, _with_det(taps, det), _with_det(t_taps, det),
+                                                         _ptr(err), _ptr(err_jvp), _stream()), "dhts_macro_rollout_fwd_jvp_ring")
+        return (out[0], out[1], out[2], out[3], taps), (out[4], out[5], t_taps)
     check(_lib.lib().dhts_macro_rollout_fwd_jvp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
                                                 _ptr(t_r), _ptr(t_y), _ptr(t_ghost), *(_ptr(o) for o in out), _ptr(det), D,
                                                 _with_det(taps, det), _with_det(t_taps, det), _ptr(err), _ptr(err_jvp), _stream()),
@@ -787,7 +924,8 @@ def macro_ckpt_numel(desc, T, segment=0):
 
 
 def _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost):
-    """What both raw wrappers check of the arguments they share -> (sched, contiguous r, y, u, ueq, ghost)."""
+    """What both raw wrappers check of the arguments they share -> (sched, contiguous r, y, u, ueq, ghost).  ghost None: a ring (the
+    _ring wrappers), which has no boundary cells; it comes back as None."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
     if macro_ckpt_plan(desc, T, 0, segment)["max_segment"] < 1:
         raise ValueError("lanes of %d cells do not fit the checkpointed reverse sweep: use the taped path (checkpoint=None)" % N)
@@ -796,6 +934,8 @@ def _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost):
     for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
         if tuple(t.shape) != (L, N):
             raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
+    if ghost is None:
+        return (False,) + tuple(_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"))) + (None,)
     sched = ghost.dim() == 4
     want = (T, L, 2, 4) if sched else (L, 2, 4)
     if tuple(ghost.shape) != want:
@@ -808,7 +948,7 @@ def _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost):
 
 def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out, det=None, taps=None, target=None, sse=None):
     """The checkpointed forward of both forms ("plain": detectors or nothing, "target": the dense fit): checks, buffers and the one C call
-    -> (out, taps or sse).  ckpt may be None (no checkpoint is kept) in the target form."""
+    -> (out, taps or sse).  ckpt may be None (no checkpoint is kept) in the target form.  ghost None: the ring entry points."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
     fit, keep = form == "target", ckpt
     if fit:
@@ -831,6 +971,15 @@ def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out,
         raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = tuple(torch.empty_like(r) for _ in range(4))
+    if ghost is None:
+        state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]))
+        if fit:
+            check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target_ring(C.byref(desc), T, segment, *state, _data(ckpt), _data(target), _ptr(sse),
+                                                                     _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt_target_ring")
+            return out, sse
+        check(_lib.lib().dhts_macro_rollout_fwd_ckpt_ring(C.byref(desc), T, int(segment), *state, _ptr(det), D, _with_det(taps, det), _data(ckpt),
+                                                          _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt_ring")
+        return out, taps
     if fit:
         check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target(C.byref(desc), T, segment, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
                                                             _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _data(ckpt), _data(target),
@@ -844,7 +993,7 @@ def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out,
 
 def _macro_ckpt_bwd(form, desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, det=None, g_taps=None, target=None, g_sse=None,
                     final=None, g_ghost=None):
-    """The checkpointed reverse sweep of both forms, as above -> (g_r0, g_y0, g_ghost)."""
+    """The checkpointed reverse sweep of both forms, as above -> (g_r0, g_y0, g_ghost); g_ghost is None for a ring (ghost None)."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
     fit = form == "target"
     if fit:
@@ -876,6 +1025,19 @@ def _macro_ckpt_bwd(form, desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment,
         raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    if ghost is None:
+        if g_ghost is not None:
+            raise ValueError("a ring has no boundary cells and no g_ghost")
+        state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(g_r), _ptr(g_y))
+        if fit:
+            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target_ring(C.byref(desc), T, segment, _data(ckpt), *state, _data(target), _ptr(g_sse),
+                                                                     _ptr(final[0]), _ptr(final[1]), _ptr(final[2]), _ptr(out[0]), _ptr(out[1]),
+                                                                     _ptr(err), _stream()), "dhts_macro_rollout_bwd_ckpt_target_ring")
+        else:
+            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_ring(C.byref(desc), T, int(segment), _data(ckpt), *state, _ptr(det), D,
+                                                              _with_det(g_taps, det), _ptr(out[0]), _ptr(out[1]), _ptr(err), _stream()),
+                  "dhts_macro_rollout_bwd_ckpt_ring")
+        return out[0], out[1], None
     want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
     if g_ghost is None:              # (a schedule's: every row is written; the sums are added to)
         g_ghost = (torch.empty if sched else torch.zeros)(want, dtype=torch.float64, device=g_r.device)
@@ -950,6 +1112,35 @@ def macro_rollout_bwd_ckpt_target(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, 
     (float)(2 g_sse) * (x - target), through the speed's glue, is formed in the kernel.  final: the forward's (r, y, u) after T steps,
     needed with g_sse.  r, y, u, ueq, ghost, target, segment: the forward's."""
     return _macro_ckpt_bwd("target", desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, None, None, target, g_sse, final, g_ghost)
+
+
+# ---- ring roads on the tape-free paths (dhts_macro_rollout_*_ring): the lane is closed, there are no boundary cells ----------------------
+def macro_rollout_fwd_ckpt_ring(desc, T, r, y, u, ueq, ckpt, segment=0, det=None, err=None, out=None, taps=None):
+    """macro_rollout_fwd_ckpt of a ring (dhts_macro_rollout_fwd_ckpt_ring, include/dhts.h): cell N - 1 is the left neighbour of cell 0.
+    Returns ((r, y, u, ueq) after T steps, taps [T][L][3][D] or None)."""
+    return _macro_ckpt_fwd("plain", desc, T, r, y, u, ueq, None, ckpt, segment, err, out, det, taps)
+
+
+def macro_rollout_bwd_ckpt_ring(desc, T, ckpt, r, y, u, ueq, g_r, g_y, segment=0, det=None, g_taps=None, err=None, out=None):
+    """Reverse sweep from the checkpoints of macro_rollout_fwd_ckpt_ring -> (g_r0, g_y0): what leaves through an end of the lane arrives
+    at the other end (dhts_macro_rollout_bwd_ckpt_ring)."""
+    return _macro_ckpt_bwd("plain", desc, T, ckpt, r, y, u, ueq, None, g_r, g_y, segment, err, out, det, g_taps)[:2]
+
+
+def macro_rollout_fwd_ckpt_target_ring(desc, T, r, y, u, ueq, ckpt, target, segment=0, sse=None, err=None, out=None):
+    """macro_rollout_fwd_ckpt_target of a ring -> ((r, y, u, ueq) after T steps, sse float64 [L][2])."""
+    return _macro_ckpt_fwd("target", desc, T, r, y, u, ueq, None, ckpt, segment, err, out, None, None, target, sse)
+
+
+def macro_rollout_bwd_ckpt_target_ring(desc, T, ckpt, r, y, u, ueq, g_r, g_y, target, g_sse=None, final=None, segment=0, err=None, out=None):
+    """The reverse sweep of macro_rollout_fwd_ckpt_target_ring -> (g_r0, g_y0), as macro_rollout_bwd_ckpt_target."""
+    return _macro_ckpt_bwd("target", desc, T, ckpt, r, y, u, ueq, None, g_r, g_y, segment, err, out, None, None, target, g_sse, final)[:2]
+
+
+def macro_rollout_fwd_jvp_ring(desc, T, r, y, u, ueq, t_r, t_y, det=None, err=None, err_jvp=None, out=None, taps=None, t_taps=None):
+    """macro_rollout_fwd_jvp of a ring (dhts_macro_rollout_fwd_jvp_ring): no ghost and no t_ghost; the tangents of the two end cells are
+    each other's boundary tangents.  Returns ((rT, yT, uT, qT, taps), (t_rT, t_yT, t_taps))."""
+    return macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, None, t_r, t_y, None, det, err, err_jvp, out, taps, t_taps)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -430,6 +430,53 @@ int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segm
                                        const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
                                        const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out, double *g_ghost,
                                        dhts_error *err, void *stream);
+/* RING ROADS on the tape-free paths: the lane is closed, cell n_cells - 1 is the left neighbour of cell 0.  A ring lane has
+ * n_cells >= 1 cells and the circumference n_cells dx: it takes no parameter.  In every step t the boundary record in front of cell 0
+ * is a COPY of the record of cell n_cells - 1 as step t finds it -- (r, y, u, u_eq) and what the kernels derive from them, exactly
+ * what cell k - 1 is to cell k -- and the one behind cell n_cells - 1 a copy of cell 0's; in step 0 these are the call's own inputs
+ * of those cells.  Nothing else changes: same step, same float32 stores, same CFL rule, same fault records.  Interfaces 0 and n_cells
+ * are the one seam: both are solved, from operands with equal bits, so their fluxes are equal bit for bit and the lane's mass
+ * sum_k r[k] is conserved up to the float32 store of each cell.  (The record of a scheduled boundary cell is made from a float32 row,
+ * the ring's copy is that of an interior cell: a ring agrees with a scheduled lane fed its own end cells within rounding, not in
+ * every bit by contract.)
+ *   n_cells = 1: the cell is its own neighbour on both sides and its state never changes.  n_cells = 2: each cell is the other's
+ *   left and right neighbour.  T = 0: outputs, cotangents and tangents come back as they went in.
+ * The five entry points are their siblings WITHOUT ghost, ghost_is_sched, g_ghost and t_ghost -- there is no boundary cell, hence no
+ * cotangent and no tangent of one -- and with the siblings' other arguments, arithmetic, plans and DHTS_E_INVALID rules:
+ *   dhts_macro_rollout_fwd_ckpt_ring          as dhts_macro_rollout_fwd_ckpt (det / n_det / taps or none).
+ *   dhts_macro_rollout_bwd_ckpt_ring          as dhts_macro_rollout_bwd_ckpt.  The cotangent the sweep forms for the slot in front of
+ *       cell 0 in a step goes to cell n_cells - 1, the one for the slot behind cell n_cells - 1 to cell 0, both in the same sweep step
+ *       inside the hand-over (G + c2_left) + c0_right, whose order of additions is kept: for cell 0 the left term is that of cell
+ *       n_cells - 1, for cell n_cells - 1 the right term is that of cell 0.
+ *   dhts_macro_rollout_fwd_ckpt_target_ring / _bwd_ckpt_target_ring   the dense fit above on the ring (dhts_macro_ckpt_target_plan).
+ *   dhts_macro_rollout_fwd_jvp_ring           as dhts_macro_rollout_fwd_jvp: the two boundary slots of the tangents a step reads hold
+ *       the tangents of cells n_cells - 1 and 0.
+ * dhts_macro_ckpt_plan, dhts_macro_ckpt_target_plan, dhts_macro_fwd_jvp_plan and dhts_macro_ckpt_bytes hold for the ring forms as
+ * they stand (no LDS, no barrier and no global load is added), and so do the cell limits (1320 / 1240 / 1410).
+ * DHTS_FAULT_CFL at the seam: interfaces 0 and n_cells fail together; the record names interface 0 (the kernels record a fault of
+ * interface n_cells as one of interface 0: on a ring they are the same interface), with the step and lane as on an open lane. */
+int dhts_macro_rollout_fwd_ckpt_ring(const dhts_macro_desc *d, int T, int segment,
+                                     const float *r, const float *y, const float *u, const float *ueq,
+                                     float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                     const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_ckpt_ring(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                     const float *r, const float *y, const float *u, const float *ueq,
+                                     const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                     float *g_r_out, float *g_y_out, dhts_error *err, void *stream);
+int dhts_macro_rollout_fwd_ckpt_target_ring(const dhts_macro_desc *d, int T, int segment,
+                                            const float *r, const float *y, const float *u, const float *ueq,
+                                            float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const float *target,
+                                            double *sse, dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_ckpt_target_ring(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                            const float *r, const float *y, const float *u, const float *ueq,
+                                            const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
+                                            const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out,
+                                            dhts_error *err, void *stream);
+int dhts_macro_rollout_fwd_jvp_ring(const dhts_macro_desc *d, int T, int n_dir,
+                                    const float *r, const float *y, const float *u, const float *ueq, const float *t_r, const float *t_y,
+                                    float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                                    const int32_t *det, int n_det, float *taps, float *t_taps,
+                                    dhts_error *err, dhts_error *err_jvp, void *stream);
 /* tangent of y = r (u - u_eq(r)): t_y = (dy/dr) t_r + (dy/du) t_u, the partials dhts_macro_state_from_ru_bwd applies, in float32 */
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u,
                                  float *t_y, void *stream);
