@@ -24,6 +24,17 @@
 // observed density and speed of every cell after every step, NaN = not observed -- read by the kernels themselves, the forward's sums
 // of squared residuals sse [L][2] out and their cotangent g_sse back in.  In the first pass kTarget is false and what the second adds
 // sits under it.
+//
+// kRamp (the last template argument of all four kernels; dhts_macro_rollout_*_ckpt_ramp / _ckpt_target_ramp, DESIGN 4m): a source in
+// chosen cells.  ramps [n_ramp] cell indices shared by all lanes, inflow [T][L][n_ramp] the density rate of cell ramps[j] of lane l in
+// step t: behind the Godunov update of step t, whose float32 store is unchanged, the owner of the cell forms
+// r' = (float)((double)r + dt * (double)inflow[t][l][j]), y' = y, and only then calls the glue, so every reader of "the state after
+// step t" -- the next step, the ring's copies, the checkpoint row, the readings, the target residual, the outputs -- sees (r', y).
+// The source is identity in (r, y): the sweep is unchanged, and its owner of the cell writes g_inflow[t][l][j] = (float)(dt *
+// (double)Gr) from the cotangent in front of step t, behind that row's detector column or target pair.  Row t + 1 of inflow is asked
+// for a step ahead of the update that adds it; no barrier in the step loop (the reverse kernel's prologue takes one more, once per
+// launch, between writing the columns into the records and their first read), no LDS and no atomic is added.  With kRamp false every kernel is the
+// parent's, instruction for instruction but for the offset of one hidden kernel argument.
 
 #if DHTS_MACRO_TARGET == 0
 // dynamic LDS: the plan (macro_ckpt_plan) and the kernels' own carving read these
@@ -49,6 +60,18 @@ __host__ __device__ inline size_t macro_ckpt_bwd_lds_bytes(int N, int S, bool ta
 }
 // bytes of one checkpoint row of one lane
 __host__ __device__ inline size_t macro_ckpt_row_bytes(int N) { return sizeof(float2) * (size_t)N; }
+// kRamp: where a cell's column of ramps[] + 1 waits (0: the cell is no ramp) -- the second half of its record's q0,
+// which every step writes as 0. and none reads; the ramp forms write the first half alone.  Looked up by cell, so the replay's owner
+// and the sweep's owner of a cell, two threads, read the same word, and neither carries it in a register.  The eight bytes are
+// cleared as the double they are declared as (ramp_col_clear); the column goes into and comes out of their first four as bytes
+// (memcpy: one 4-byte LDS access, and no object is accessed through a pointer of another type).
+__device__ __forceinline__ void ramp_col_clear(CellRec *CR, unsigned cell) { CR[cell + 1].q0.y = 0.; }
+__device__ __forceinline__ void ramp_col_set(CellRec *CR, unsigned cell, int col1) { __builtin_memcpy(&CR[cell + 1].q0.y, &col1, sizeof(int)); }
+__device__ __forceinline__ int ramp_col_get(const CellRec *CR, unsigned cell) {
+    int col1;
+    __builtin_memcpy(&col1, &CR[cell + 1].q0.y, sizeof(int));
+    return col1;
+}
 #endif
 
 // grid = L workgroups (one traffic lane each) of W = blockDim.x / 64 wavefronts, the lane kernel's mapping: wave w owns the cells
@@ -65,10 +88,10 @@ __host__ __device__ inline size_t macro_ckpt_row_bytes(int N) { return sizeof(fl
 // pointer (no global load on the step's dependent chain); the squared float32 residuals of its valid cells are summed in double in step
 // order and combined per lane behind the loop.  ckpt may be NULL: no checkpoint is stored.
 #if DHTS_MACRO_TARGET == 0
-template <int kP, MacroBoundary kBound, bool kTaps>
+template <int kP, MacroBoundary kBound, bool kTaps, bool kRamp>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_kernel(
 #else
-template <int kP, MacroBoundary kBound>
+template <int kP, MacroBoundary kBound, bool kRamp>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
 #endif
     int L, int N, int T, int Sg, double dt, double dx, double um,
@@ -77,12 +100,14 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
     float *__restrict__ r_out, float *__restrict__ y_out, float *__restrict__ u_out, float *__restrict__ q_out,
     float2 *__restrict__ ckpt, dhts_error *err,
 #if DHTS_MACRO_TARGET == 0
-    const int32_t *__restrict__ det, int n_det, float *__restrict__ taps) {
+    const int32_t *__restrict__ det, int n_det, float *__restrict__ taps,
+    const int32_t *__restrict__ ramps, int n_ramp, const float *__restrict__ inflow) {
     constexpr bool kTarget = false;
     const float *const target = nullptr;
     double *const sse = nullptr;
 #else
-    const float *__restrict__ target, double *__restrict__ sse) {
+    const float *__restrict__ target, double *__restrict__ sse,
+    const int32_t *__restrict__ ramps, int n_ramp, const float *__restrict__ inflow) {
     constexpr bool kTaps = false, kTarget = true;
     const int32_t *const det = nullptr;
     constexpr int n_det = 0;
@@ -154,6 +179,25 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
             tg_r[j] = tgp[j][0]; tg_u[j] = tgp[j][N];
         }
     }
+    // kRamp: thread q puts column q + 1 of ramps[q] into that cell's record once (ramp_col_set: the word the reverse kernel uses; an
+    // entry outside [0, N) is compared as an unsigned value and forms no address), so the owner of a cell finds its column with the
+    // record it updates and carries none.  src[j]: the entry of the row of inflow the next update adds, asked for a whole step earlier;
+    // the row's address is formed from the step count where it is loaded.  The ramp forms write the first half of q0 alone.
+    float src[kP];
+    const float *const rin = kRamp ? inflow + (size_t)lane * n_ramp : nullptr;      // this lane's part of row 0
+    if constexpr (kRamp) {
+        for (int q = tid; q < n_ramp; q += blockDim.x) {
+            const unsigned rc = (unsigned)ramps[q];
+            if (rc < (unsigned)N) ramp_col_set(CR, rc, q + 1);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kP; ++j) {
+            const int i = lo + (j << 6) + t;
+            const int rc = i < N ? ramp_col_get(CR, (unsigned)i) : 0;
+            src[j] = rc ? rin[rc - 1] : 0.f;
+        }
+    }
     // kTaps: thread (blockDim - 1 - tid) takes detector slot tap_j (+ blockDim per further one); tap_wave: this wavefront holds any
     const int tap_j = (int)blockDim.x - 1 - tid;
     int det_own = -1;
@@ -198,10 +242,22 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
                 const double2 Fl = FX[ic], Fr = FX[ic + 1];
                 st.x = (float)(rd_own[j] + (Fl.x - Fr.x) * c);
                 st.y = (float)(yd_own[j] + (Fl.y - Fr.y) * c);
+                if constexpr (kRamp) {
+                    // the on-ramp's source of step n - 1, one more float32 operation behind the step's own store (DESIGN 4m); then
+                    // row n leaves for the register
+                    const int rc = vc ? ramp_col_get(CR, ic) : 0;
+                    if (rc) {
+                        st.x = (float)((double)st.x + dt * (double)src[j]);
+                        if (solve) src[j] = rin[(size_t)n * L * n_ramp + (rc - 1)];
+                    }
+                }
                 rd_own[j] = (double)st.x; yd_own[j] = (double)st.y;
                 CellPre cp;
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
-                if (vc && solve) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
+                if (vc && solve) {
+                    own->st = st; own->sh = make_double2(cp.s, cp.h);
+                    if constexpr (kRamp) own->q0.x = cp.q0; else own->q0 = make_double2(cp.q0, 0.);
+                }
                 else if (kTaps && vc) own->st = st;          // the final step's state, for the taps below
                 if constexpr (kRing && solve) ring_rec_copies_direct(CR, N, vc, ic, st, cp);
                 if constexpr (kTarget) {
@@ -321,10 +377,10 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_fwd_target_kernel(
 // Row T - 1 is the forward's final state, which the caller has: fin_r, fin_y, fin_u are read once in front of the loop and the pair goes
 // into the incoming cotangent, as the last row of g_taps does.  The sweep itself takes no global load beyond what it has.
 #if DHTS_MACRO_TARGET == 0
-template <MacroBoundary kBound, bool kTaps>
+template <MacroBoundary kBound, bool kTaps, bool kRamp>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_kernel(
 #else
-template <MacroBoundary kBound>
+template <MacroBoundary kBound, bool kRamp>
 __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
 #endif
     int L, int N, int T, int Sg, int p, double dt, double dx, double um, const float2 *__restrict__ ckpt,
@@ -333,13 +389,15 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
     const float *__restrict__ g_r_in, const float *__restrict__ g_y_in, const float *__restrict__ g_taps,
     float *__restrict__ g_r_out, float *__restrict__ g_y_out, double *__restrict__ g_ghost, dhts_error *err,
 #if DHTS_MACRO_TARGET == 0
-    const int32_t *__restrict__ det, int n_det) {
+    const int32_t *__restrict__ det, int n_det,
+    const int32_t *__restrict__ ramps, int n_ramp, const float *__restrict__ inflow, float *__restrict__ g_inflow) {
     constexpr bool kTarget = false;
     const float *const target = nullptr, *const fin_r = nullptr, *const fin_y = nullptr, *const fin_u = nullptr;
     const double *const g_sse = nullptr;
 #else
     const float *__restrict__ target, const double *__restrict__ g_sse,
-    const float *__restrict__ fin_r, const float *__restrict__ fin_y, const float *__restrict__ fin_u) {
+    const float *__restrict__ fin_r, const float *__restrict__ fin_y, const float *__restrict__ fin_u,
+    const int32_t *__restrict__ ramps, int n_ramp, const float *__restrict__ inflow, float *__restrict__ g_inflow) {
     constexpr bool kTaps = false, kTarget = true;
     const int32_t *const det = nullptr;
     constexpr int n_det = 0;
@@ -371,6 +429,8 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
     if (tid == 0) *tail = BwdTail{g_r_out + base, g_y_out + base, g_ghost ? g_ghost + (size_t)lane * 4 : nullptr, err,
                                    kTarget ? (ptrdiff_t)L * 2 * N : (ptrdiff_t)L * 2 * n_det, (ptrdiff_t)L * N};
     for (int k = tid; k < P; k += B) { C0r[k] = 0.f; C0y[k] = 0.f; C2r[k] = 0.f; C2y[k] = 0.f; Gr[k] = 0.f; Gy[k] = 0.f; }
+    if constexpr (kRamp)
+        for (int k = tid; k < N; k += B) ramp_col_clear(CR, (unsigned)k);
     __syncthreads();
     // kTaps: the sweep's owner of cell k = tid + m B (2 B >= N) adds the detector columns to it itself, so it looks its cells up in
     // det[] once: col[m] = the column j with det[j] == k, -1 without one (an entry outside [0, N) matches no cell; it is compared as an
@@ -391,6 +451,21 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
 #pragma unroll
         for (int m = 0; m < 2; ++m) gtp[m] = g_taps + ((size_t)(T - 1) * L + lane) * 2 * n_det + (col[m] >= 0 ? col[m] : 0);
     }
+    // kRamp: the owner of a ramp cell, in the replay and in the sweep, finds the cell's column in the records (ramp_col_get): thread q writes
+    // column q + 1 there once, here.  An entry of ramps outside [0, N) is compared as an unsigned value and forms no address; with a
+    // repeated entry one of its columns stays (PRECONDITION, include/dhts.h).  src0 / src1: the replay's entries of inflow for its pass
+    // 0 / 1, asked for a whole step ahead of the update that adds them.  The rows of inflow and g_inflow are addressed from the step
+    // count where they are used: that is scalar work, and no running pointer is carried.
+    float src0 = 0.f, src1 = 0.f;
+    if constexpr (kRamp) {
+        for (int q = tid; q < n_ramp; q += B) {          // (the words were cleared in front of the barrier above)
+            const unsigned rc = (unsigned)ramps[q];
+            if (rc < (unsigned)N) ramp_col_set(CR, rc, q + 1);
+        }
+        __syncthreads();
+    }
+    const float *const rin = kRamp ? inflow + (size_t)lane * n_ramp : nullptr;      // this lane's part of row 0
+    float *const gin = kRamp ? g_inflow + (size_t)lane * n_ramp : nullptr;
     // kTarget: twice the cotangent of the lane's two sums, in float32 (per thread: the scalar registers are the replay's)
     float g2r = 0.f, g2u = 0.f;
     if constexpr (kTarget) {
@@ -416,6 +491,10 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
                 float ar, ay;
                 fit_pair(fin_r[base + k], fin_y[base + k], fin_u[base + k], tg[0], tg[N], ar, ay);
                 gr += ar; gy += ay;
+            }
+            if constexpr (kRamp) {                       // row T - 1: the source is identity in (r, y)
+                const int rc = ramp_col_get(CR, (unsigned)k);
+                if (rc) gin[(size_t)(T - 1) * L * n_ramp + (rc - 1)] = (float)(dt * (double)gr);
             }
             Gr[k + 1] = gr; Gy[k + 1] = gy;
         }
@@ -470,6 +549,8 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
             const unsigned ic = (unsigned)(vc ? i : N - 1);
             CellRec *own = CR + ic + 1;
             float4 st = own->st;
+            int rsj = 0;
+            if constexpr (kRamp && upd) rsj = vc ? ramp_col_get(CR, ic) : 0;
             // kTarget: row n - 1 of target at this cell, asked for here and used at the bottom of the pass
             float t_r = 0.f, t_u = 0.f;
             if constexpr (kTarget) {
@@ -480,10 +561,23 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
                 const double2 Fl = FX[ic], Fr = FX[ic + 1];
                 st.x = (float)((double)st.x + (Fl.x - Fr.x) * c);
                 st.y = (float)((double)st.y + (Fl.y - Fr.y) * c);
+                if constexpr (kRamp) {
+                    // the forward's float32 source of step n - 1 on the same operands; then row n leaves for the register
+                    if (rsj) {
+                        st.x = (float)((double)st.x + dt * (double)(j ? src1 : src0));
+                        if (n + 1 < s_end) {
+                            const float nx = rin[(size_t)n * L * n_ramp + (rsj - 1)];
+                            if (j) src1 = nx; else src0 = nx;
+                        }
+                    }
+                }
                 CellPre cp;
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
-                if (vc) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
-                if constexpr (kRing) ring_rec_copies(CR, Nv, vc, ic, st, cp);
+                if (vc) {
+                    own->st = st; own->sh = make_double2(cp.s, cp.h);
+                    if constexpr (kRamp) own->q0.x = cp.q0; else own->q0 = make_double2(cp.q0, 0.);
+                }
+                if constexpr (kRing) ring_rec_copies<kRamp>(CR, Nv, vc, ic, st, cp);
             }
             wave_lds_handoff();
             const CellRec *lf = CR + ic;
@@ -588,8 +682,16 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
                 st = st0[j];
                 arz_cell_pre((double)st.x, um, cp);
             }
-            if (vc) { CellRec *own = CR + ic + 1; own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
-            if constexpr (kRing) ring_rec_copies(CR, Nv, vc, ic, st, cp);
+            if (vc) {
+                CellRec *own = CR + ic + 1;
+                own->st = st; own->sh = make_double2(cp.s, cp.h);
+                if constexpr (kRamp) own->q0.x = cp.q0; else own->q0 = make_double2(cp.q0, 0.);
+            }
+            if constexpr (kRing) ring_rec_copies<kRamp>(CR, Nv, vc, ic, st, cp);
+            if constexpr (kRamp) {                       // row s0, for the update in the call of step s0 + 1: a whole step ahead
+                const int rc = vc ? ramp_col_get(CR, ic) : 0;
+                if (rc) { const float nx = rin[(size_t)s0 * L * n_ramp + (rc - 1)]; if (j) src1 = nx; else src0 = nx; }
+            }
         }
         if constexpr (kSched) sched_p = sched_lane + (size_t)s0 * L * 2;
         if (kSched && tid < 2) {                         // a schedule: row s0
@@ -667,6 +769,11 @@ __global__ __launch_bounds__(768) void macro_rollout_ckpt_bwd_target_kernel(
                     if (kTaps && step > 0 && col[m] >= 0) { nr += ar[m]; ny += ay[m]; }      // in front of step - 1: Gr[det[j] + 1] += gt[j]
                     if constexpr (kTarget) {
                         if (step > 0) { const float *tp = tp0 + ((step - s0) * 2 * N + k - own0); nr += tp[0]; ny += tp[N]; }      // row step - 1
+                    }
+                    // kRamp: nr is now the cotangent of r in the state after step - 1, where that step's source went in
+                    if constexpr (kRamp) {
+                        const int rc = ramp_col_get(CR, (unsigned)k);
+                        if (step > 0 && rc) gin[(size_t)(step - 1) * L * n_ramp + (rc - 1)] = (float)(dt * (double)nr);
                     }
                     Gr[k + 1] = nr; Gy[k + 1] = ny;
                 }

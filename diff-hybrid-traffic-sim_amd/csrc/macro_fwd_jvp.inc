@@ -44,12 +44,17 @@ __device__ __forceinline__ int ring_len(int N) {
 __device__ __forceinline__ bool ring_seam(int Nv, bool vc, unsigned ic) { return vc && (ic == 0u || (int)ic == Nv - 1); }
 __device__ __forceinline__ int ring_lo(int Nv, unsigned ic) { return (int)ic == Nv - 1 ? -Nv : 0; }       // slot 0 from cell N - 1's own
 __device__ __forceinline__ int ring_hi(int Nv, unsigned ic) { return ic == 0u ? Nv : 0; }                 // slot N + 1 from cell 0's own
+// kKeepPad: the second half of q0, which no step reads, is left as it is (the checkpointed reverse kernel's ramp forms keep a cell's
+// ramp column there, macro_ckpt.inc)
+template <bool kKeepPad = false>
 __device__ __forceinline__ void ring_rec_copies(CellRec *CR, int Nv, bool vc, unsigned ic, const float4 &st, const CellPre &cp) {
     if (ring_seam(Nv, vc, ic)) {
         CellRec *own = CR + ic + 1, *w = own + ring_lo(Nv, ic);
-        w->st = st; w->sh = make_double2(cp.s, cp.h); w->q0 = make_double2(cp.q0, 0.);
+        w->st = st; w->sh = make_double2(cp.s, cp.h);
+        if constexpr (kKeepPad) w->q0.x = cp.q0; else w->q0 = make_double2(cp.q0, 0.);
         w = own + ring_hi(Nv, ic);
-        w->st = st; w->sh = make_double2(cp.s, cp.h); w->q0 = make_double2(cp.q0, 0.);
+        w->st = st; w->sh = make_double2(cp.s, cp.h);
+        if constexpr (kKeepPad) w->q0.x = cp.q0; else w->q0 = make_double2(cp.q0, 0.);
     }
 }
 // ... and where scalar registers are to spare (the checkpointed forward): the two slots at their own addresses, a test each

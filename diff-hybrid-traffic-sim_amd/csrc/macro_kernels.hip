@@ -280,7 +280,9 @@ __device__ __forceinline__ void wave_lds_handoff() {
 struct __attribute__((aligned(16))) CellRec {
     float4 st;       // r, y, u, u_eq  (FullQ, _arz.py:10-115)
     double2 sh;      // CellPre s, h
-    double2 q0;      // CellPre q0 (+ padding: every access is a conflict-free 16-byte one)
+    double2 q0;      // CellPre q0 (+ padding: every access is a conflict-free 16-byte one).  The padding q0.y is read by no step; the
+                     // checkpointed reverse kernel's ramp forms keep the cell's ramp column in its first four bytes (ramp_col_get / _set,
+                     // macro_ckpt.inc) and write q0.x alone
 };
 static_assert(sizeof(CellRec) == 48, "CellRec layout");
 
@@ -1653,6 +1655,12 @@ struct MacroForm {
     double *sse;
     const double *g_sse;
     const float *fin_r, *fin_y, *fin_u;
+    // on-ramps of the checkpointed pair: cells ramps [n_ramp] shared by all lanes, the density rates inflow [T][L][n_ramp] and, reverse,
+    // their cotangent g_inflow [T][L][n_ramp]; `ramps` NULL: not a ramp form
+    const int32_t *ramps;
+    int n_ramp;
+    const float *inflow;
+    float *g_inflow;
 };
 static MacroForm macro_form(int ghost_is_sched, const int32_t *det = nullptr, int n_det = 0) {
     MacroForm f = {};
@@ -2017,10 +2025,13 @@ static int macro_ckpt_fwd_launch(const dhts_macro_desc *d, int T, int S, const M
     pick<1, 2>(pl.p, [&](auto pv) {
         pick<kBoundConst, kBoundSched, kBoundRing>(f.bound, [&](auto bc) {
             pick<0, 1, 2>(f.target ? 2 : f.det != nullptr, [&](auto tap) {
-                constexpr int kP = decltype(pv)::value, kForm = decltype(tap)::value;
-                constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
-                if constexpr (kForm == 2) go(macro_rollout_ckpt_fwd_target_kernel<kP, kS>, f.target, f.sse);
-                else go(macro_rollout_ckpt_fwd_kernel<kP, kS, kForm != 0>, f.det, f.n_det, f.taps);
+                pick<0, 1>(f.ramps != nullptr, [&](auto rv) {
+                    constexpr int kP = decltype(pv)::value, kForm = decltype(tap)::value;
+                    constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
+                    constexpr bool kR = decltype(rv)::value != 0;
+                    if constexpr (kForm == 2) go(macro_rollout_ckpt_fwd_target_kernel<kP, kS, kR>, f.target, f.sse, f.ramps, f.n_ramp, f.inflow);
+                    else go(macro_rollout_ckpt_fwd_kernel<kP, kS, kForm != 0, kR>, f.det, f.n_det, f.taps, f.ramps, f.n_ramp, f.inflow);
+                });
             });
         });
     });
@@ -2038,11 +2049,17 @@ static int macro_ckpt_bwd_launch(const dhts_macro_desc *d, int T, int S, const M
     };
     pick<kBoundConst, kBoundSched, kBoundRing>(f.bound, [&](auto bc) {
         pick<0, 1, 2>(f.target ? 2 : f.det != nullptr, [&](auto tap) {
-            constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
-            constexpr int kForm = decltype(tap)::value;
-            if constexpr (kForm == 2)
-                go(macro_rollout_ckpt_bwd_target_kernel<kS>, macro_ckpt_bwd_lds_bytes(N, S, true), f.target, f.g_sse, f.fin_r, f.fin_y, f.fin_u);
-            else go(macro_rollout_ckpt_bwd_kernel<kS, kForm != 0>, macro_ckpt_bwd_lds_bytes(N, S), f.det, f.n_det);
+            pick<0, 1>(f.ramps != nullptr, [&](auto rv) {
+                constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
+                constexpr int kForm = decltype(tap)::value;
+                constexpr bool kR = decltype(rv)::value != 0;
+                if constexpr (kForm == 2)
+                    go(macro_rollout_ckpt_bwd_target_kernel<kS, kR>, macro_ckpt_bwd_lds_bytes(N, S, true), f.target, f.g_sse, f.fin_r, f.fin_y,
+                       f.fin_u, f.ramps, f.n_ramp, f.inflow, f.g_inflow);
+                else
+                    go(macro_rollout_ckpt_bwd_kernel<kS, kForm != 0, kR>, macro_ckpt_bwd_lds_bytes(N, S), f.det, f.n_det, f.ramps, f.n_ramp, f.inflow,
+                       f.g_inflow);
+            });
         });
     });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
@@ -2275,18 +2292,43 @@ size_t dhts_macro_ckpt_bytes(const dhts_macro_desc *d, int T, int segment) {
     if (S < 0) return 0;
     return (size_t)macro_ckpt_count(T, S) * d->n_lanes * macro_ckpt_row_bytes(d->n_cells);
 }
+// The on-ramp arguments of the _ramp entry points (on: the call is one of them); the entry functions below serve both kinds.
+struct MacroRamps {
+    bool on;
+    const int32_t *ramps;
+    int n_ramp;
+    const float *inflow;
+    float *g_inflow;
+};
+// n_ramp in 1 .. n_cells whatever T is; the arrays only where a step reads or writes them.  d: checked by the caller
+static inline bool macro_ramps_ok(const dhts_macro_desc *d, int T, const MacroRamps &ra, bool reverse) {
+    if (!ra.on) return true;
+    if (ra.n_ramp < 1 || ra.n_ramp > d->n_cells) return false;
+    return T <= 0 || (ra.ramps && ra.inflow && (!reverse || ra.g_inflow));
+}
+static inline void macro_ramps_form(MacroForm &f, const MacroRamps &ra) {
+    if (!ra.on) return;
+    f.ramps = ra.ramps; f.n_ramp = ra.n_ramp; f.inflow = ra.inflow; f.g_inflow = ra.g_inflow;
+}
+// the reverse sweep's owner of a ramp cell writes that cell's column of g_inflow; a column whose index is outside [0, N) has no owner
+// and keeps the zero it gets here
+static inline bool macro_ramps_clear(const dhts_macro_desc *d, int T, const MacroRamps &ra, void *stream) {
+    return !ra.on || hipMemsetAsync(ra.g_inflow, 0, sizeof(float) * (size_t)T * d->n_lanes * ra.n_ramp, (hipStream_t)stream) == hipSuccess;
+}
 static int macro_rollout_fwd_ckpt_entry(const dhts_macro_desc *d, int T, int segment,
                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                 float *r_out, float *y_out, float *u_out, float *ueq_out,
-                                const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream) {
+                                const int32_t *det, int n_det, float *taps, void *ckpt, dhts_error *err, void *stream,
+                                const MacroRamps &ra = {}) {
     if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ring_or(bound, r, ghost), r_out, y_out, u_out, ueq_out) || (T > 0 && !ckpt)) return DHTS_E_INVALID;
-    if (!macro_det_pair_ok(d, det, n_det, taps)) return DHTS_E_INVALID;
+    if (!macro_det_pair_ok(d, det, n_det, taps) || !macro_ramps_ok(d, T, ra, false)) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d);
     const int S = macro_ckpt_segment(pl, segment);
     if (S < 0) return DHTS_E_INVALID;
     if (T == 0) return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
     MacroForm f = macro_bound_form(bound, det, n_det);
     f.taps = taps;
+    macro_ramps_form(f, ra);
     return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, ckpt, f, err, stream);
 }
 int dhts_macro_rollout_fwd_ckpt(const dhts_macro_desc *d, int T, int segment,
@@ -2313,9 +2355,9 @@ static inline bool macro_replay_args_ok(const dhts_macro_desc *d, int T, const v
 static int macro_rollout_bwd_ckpt_entry(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
                                 const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                 const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
-                                float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream) {
+                                float *g_r_out, float *g_y_out, double *g_ghost, dhts_error *err, void *stream, const MacroRamps &ra = {}) {
     if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
-    if (!macro_det_pair_ok(d, det, n_det, g_taps)) return DHTS_E_INVALID;
+    if (!macro_det_pair_ok(d, det, n_det, g_taps) || !macro_ramps_ok(d, T, ra, true)) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d);
     const int S = macro_ckpt_segment(pl, segment);
     if (S < 0) return DHTS_E_INVALID;
@@ -2329,6 +2371,8 @@ static int macro_rollout_bwd_ckpt_entry(const dhts_macro_desc *d, int T, int seg
     }
     MacroForm f = macro_bound_form(bound, det, n_det);
     f.g_cot = g_taps;
+    macro_ramps_form(f, ra);
+    if (!macro_ramps_clear(d, T, ra, stream)) return DHTS_E_LAUNCH;
     return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
 }
 int dhts_macro_rollout_bwd_ckpt(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
@@ -2353,8 +2397,9 @@ int dhts_macro_ckpt_target_plan(const dhts_macro_desc *d, int T, int segment, in
 static int macro_rollout_fwd_ckpt_target_entry(const dhts_macro_desc *d, int T, int segment,
                                        const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                        float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt, const float *target, double *sse,
-                                       dhts_error *err, void *stream) {
-    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ring_or(bound, r, ghost), r_out, y_out, u_out, ueq_out) || !sse || (T > 0 && !target))
+                                       dhts_error *err, void *stream, const MacroRamps &ra = {}) {
+    if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ring_or(bound, r, ghost), r_out, y_out, u_out, ueq_out) || !sse || (T > 0 && !target) ||
+        !macro_ramps_ok(d, T, ra, false))
         return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d, true);
     const int S = macro_ckpt_segment(pl, segment);
@@ -2365,6 +2410,7 @@ static int macro_rollout_fwd_ckpt_target_entry(const dhts_macro_desc *d, int T, 
     }
     MacroForm f = macro_bound_form(bound);
     f.target = target; f.sse = sse;
+    macro_ramps_form(f, ra);
     return macro_ckpt_fwd_launch(d, T, S, pl, r, y, u, ueq, ghost, r_out, y_out, u_out, ueq_out, ckpt, f, err, stream);
 }
 int dhts_macro_rollout_fwd_ckpt_target(const dhts_macro_desc *d, int T, int segment,
@@ -2385,8 +2431,9 @@ static int macro_rollout_bwd_ckpt_target_entry(const dhts_macro_desc *d, int T, 
                                        const float *r, const float *y, const float *u, const float *ueq, const float *ghost, MacroBoundary bound,
                                        const float *g_r, const float *g_y, const float *target, const double *g_sse, const float *r_fin,
                                        const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out, double *g_ghost,
-                                       dhts_error *err, void *stream) {
-    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, g_r_out, g_y_out, g_ghost)) return DHTS_E_INVALID;
+                                       dhts_error *err, void *stream, const MacroRamps &ra = {}) {
+    if (!macro_replay_args_ok(d, T, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, g_r_out, g_y_out, g_ghost) || !macro_ramps_ok(d, T, ra, true))
+        return DHTS_E_INVALID;
     // the fit's cotangent needs the observations and the forward's final state (row T - 1 of the history)
     if (T > 0 && (!target || (g_sse && (!r_fin || !y_fin || !u_fin)))) return DHTS_E_INVALID;
     const MacroCkptPlan pl = macro_ckpt_plan(d, true);
@@ -2394,9 +2441,11 @@ static int macro_rollout_bwd_ckpt_target_entry(const dhts_macro_desc *d, int T, 
     if (S < 0) return DHTS_E_INVALID;
     if (T == 0 || !g_sse)            // no step, or no cotangent of the sums: the plain sweep (the segment is the TARGET plan's, which fits it)
         return macro_rollout_bwd_ckpt_entry(d, T, S, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, nullptr, 0, nullptr, g_r_out, g_y_out,
-                                            g_ghost, err, stream);
+                                            g_ghost, err, stream, ra);
     MacroForm f = macro_bound_form(bound);
     f.target = target; f.g_sse = g_sse; f.fin_r = r_fin; f.fin_y = y_fin; f.fin_u = u_fin;
+    macro_ramps_form(f, ra);
+    if (!macro_ramps_clear(d, T, ra, stream)) return DHTS_E_LAUNCH;
     return macro_ckpt_bwd_launch(d, T, S, pl, ckpt, r, y, u, ueq, ghost, g_r, g_y, g_r_out, g_y_out, g_ghost, f, err, stream);
 }
 int dhts_macro_rollout_bwd_ckpt_target(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
@@ -2414,6 +2463,55 @@ int dhts_macro_rollout_bwd_ckpt_target_ring(const dhts_macro_desc *d, int T, int
                                             dhts_error *err, void *stream) {
     return macro_rollout_bwd_ckpt_target_entry(d, T, segment, ckpt, r, y, u, ueq, nullptr, kBoundRing, g_r, g_y, target, g_sse, r_fin, y_fin,
                                                u_fin, g_r_out, g_y_out, nullptr, err, stream);
+}
+// ---- on-ramp inflow at chosen cells of the checkpointed pair -------------------------------------------------------
+// ring != 0: a closed lane, which has no boundary cells (ghost must be NULL); else ghost is a schedule where ghost_is_sched
+static inline bool macro_ramp_bound(int ring, const float *ghost, int ghost_is_sched, MacroBoundary &bound) {
+    bound = ring ? kBoundRing : (ghost_is_sched ? kBoundSched : kBoundConst);
+    return !ring || !ghost;
+}
+int dhts_macro_rollout_fwd_ckpt_ramp(const dhts_macro_desc *d, int T, int segment,
+                                     const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                     float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                     const int32_t *det, int n_det, float *taps, void *ckpt,
+                                     const int32_t *ramps, int n_ramp, const float *inflow, int ring, dhts_error *err, void *stream) {
+    MacroBoundary bound;
+    if (!macro_ramp_bound(ring, ghost, ghost_is_sched, bound)) return DHTS_E_INVALID;
+    return macro_rollout_fwd_ckpt_entry(d, T, segment, r, y, u, ueq, ghost, bound, r_out, y_out, u_out, ueq_out, det, n_det, taps, ckpt, err,
+                                        stream, MacroRamps{true, ramps, n_ramp, inflow, nullptr});
+}
+int dhts_macro_rollout_bwd_ckpt_ramp(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                     const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                     const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                     float *g_r_out, float *g_y_out, double *g_ghost,
+                                     const int32_t *ramps, int n_ramp, const float *inflow, float *g_inflow, int ring, dhts_error *err,
+                                     void *stream) {
+    MacroBoundary bound;
+    if (!macro_ramp_bound(ring, ghost, ghost_is_sched, bound)) return DHTS_E_INVALID;
+    return macro_rollout_bwd_ckpt_entry(d, T, segment, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, det, n_det, g_taps, g_r_out, g_y_out,
+                                        ring ? nullptr : g_ghost, err, stream, MacroRamps{true, ramps, n_ramp, inflow, g_inflow});
+}
+int dhts_macro_rollout_fwd_ckpt_target_ramp(const dhts_macro_desc *d, int T, int segment,
+                                            const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
+                                            int ghost_is_sched, float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt,
+                                            const float *target, double *sse,
+                                            const int32_t *ramps, int n_ramp, const float *inflow, int ring, dhts_error *err, void *stream) {
+    MacroBoundary bound;
+    if (!macro_ramp_bound(ring, ghost, ghost_is_sched, bound)) return DHTS_E_INVALID;
+    return macro_rollout_fwd_ckpt_target_entry(d, T, segment, r, y, u, ueq, ghost, bound, r_out, y_out, u_out, ueq_out, ckpt, target, sse, err,
+                                               stream, MacroRamps{true, ramps, n_ramp, inflow, nullptr});
+}
+int dhts_macro_rollout_bwd_ckpt_target_ramp(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                            const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
+                                            int ghost_is_sched, const float *g_r, const float *g_y, const float *target, const double *g_sse,
+                                            const float *r_fin, const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out,
+                                            double *g_ghost, const int32_t *ramps, int n_ramp, const float *inflow, float *g_inflow, int ring,
+                                            dhts_error *err, void *stream) {
+    MacroBoundary bound;
+    if (!macro_ramp_bound(ring, ghost, ghost_is_sched, bound)) return DHTS_E_INVALID;
+    return macro_rollout_bwd_ckpt_target_entry(d, T, segment, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, target, g_sse, r_fin, y_fin, u_fin,
+                                               g_r_out, g_y_out, ring ? nullptr : g_ghost, err, stream,
+                                               MacroRamps{true, ramps, n_ramp, inflow, g_inflow});
 }
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,
                                  void *stream) {

@@ -167,6 +167,15 @@ SIGNATURES = {
     "dhts_micro_rollout_fwd_jvp_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 13 + [C.c_int, C.c_int] + [_P] * 5),
     "dhts_micro_rollout_fwd_ckpt_target_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 12),
     "dhts_micro_rollout_bwd_ckpt_target_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 13),
+    # the siblings' arguments, then ramps, n_ramp, inflow (reverse: and g_inflow), ring, err, stream
+    "dhts_macro_rollout_fwd_ckpt_ramp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 5 + [C.c_int] +
+                                         [_P] * 3 + [C.c_int, _P, C.c_int] + [_P] * 2),
+    "dhts_macro_rollout_bwd_ckpt_ramp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 6 + [C.c_int] + [_P] * 3 + [C.c_int] +
+                                         [_P] * 5 + [C.c_int, _P, _P, C.c_int] + [_P] * 2),
+    "dhts_macro_rollout_fwd_ckpt_target_ramp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 8 +
+                                                [C.c_int, _P, C.c_int] + [_P] * 2),
+    "dhts_macro_rollout_bwd_ckpt_target_ramp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 6 + [C.c_int] + [_P] * 11 +
+                                                [C.c_int, _P, _P, C.c_int] + [_P] * 2),
     "dhts_micro_step_fwd": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor_head": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),

@@ -541,6 +541,96 @@ class MacroRolloutRingTarget(torch.autograd.Function):
         return _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0) + (None,) * 7
 
 
+class MacroRolloutRamp(torch.autograd.Function):
+    """The checkpointed rollout with on-ramps (dhts_macro_rollout_*_ckpt_ramp), every form of it: (r0, u0 [L][N], ghost_r,
+    ghost_u [L][2], a schedule [T][L][2] or None: a ring, inflow [T][L][R]) -> (rT, yT, uT, qT[, readings [T][L][3][D] | sse [L][2]]).
+    inflow is a leaf like the others: its gradient comes back float32 [T][L][R], written by the reverse sweep itself."""
+
+    @staticmethod
+    def forward(ctx, r0, u0, ghost_r, ghost_u, inflow, T, dt, dx, u_max, check_faults, det, checkpoint, target, ramps):
+        L, N = r0.shape
+        ring, fit = ghost_r is None, target is not None
+        desc = macro_desc(L, N, dt, dx, u_max)
+        if fit:
+            segment = _macro_target_segment(checkpoint, desc, T)
+        else:
+            segment = _macro_checkpoint_segment(checkpoint, desc, T, False, 0 if det is None else int(det.numel()))
+        gr = gu = gq = ghost = None
+        if ring:
+            r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+            y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
+        else:
+            _macro_boundary_form(L, ghost_r, ghost_u, T)
+            r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
+        inf = _f32c(inflow.detach(), "inflow")
+        need_grad = any(t is not None and t.requires_grad for t in (r0, u0, ghost_r, ghost_u, inflow))
+        dev = r0.device
+        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev)
+        err = new_error_record(dev)
+        (rT, yT, uT, qT), extra = macro_rollout_fwd_ckpt_ramp(desc, T, r0c, y0, u0c, q0, ghost, ckpt, ramps, inf, segment=segment, det=det,
+                                                              target=target, err=err)
+        if check_faults:
+            raise_on_fault(err)
+        if need_grad:
+            ctx.ckpt, ctx.replay, ctx.target, ctx.ring = ckpt, (y0, q0, ghost), target, ring
+            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
+            ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, uT, None if fit else extra, det, ramps, inf)
+        ctx.mark_non_differentiable(qT)
+        return (rT, yT, uT, qT) if extra is None else (rT, yT, uT, qT, extra)
+
+    @staticmethod
+    def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_extra=None):
+        r0, u0, gr, gu, gq, rT, yT, uT, steps, det, ramps, inf = ctx.saved_tensors
+        desc, T, um = ctx.desc, ctx.T, ctx.u_max
+        fit = ctx.target is not None
+        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
+        gs = g_sse = None
+        if fit:
+            g_sse = g_extra.contiguous() if g_extra is not None else None
+        elif steps is not None and g_extra is not None and g_extra.numel():      # (T = 0: no row, and an empty tensor has no address)
+            gs = _per_step_cotangent(steps, g_extra, um, rows=_glue_rows(T, desc.n_lanes * steps.shape[3]))
+        err = new_error_record(r0.device)
+        y0, q0, ghost = ctx.replay
+        g_r0, g_y0, g_ghost, g_inflow = macro_rollout_bwd_ckpt_ramp(
+            desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, ramps, inf, segment=ctx.segment, det=det if gs is not None else None,
+            g_taps=gs, target=ctx.target, g_sse=g_sse, final=(rT, yT, uT) if fit else None, err=err)
+        del gs, y0, q0, ghost            # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
+        ctx.replay = ctx.ckpt = None
+        if ctx.ring:
+            grads = _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0) + (None, None)
+        else:
+            grads = _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * desc.n_lanes))
+        return grads + (g_inflow,) + (None,) * 9
+
+
+def _macro_ramp_checks(r0, T, ramps, inflow, want_hist, checkpoint):
+    """Every ValueError of dhts.macro_rollout's `ramps` / `inflow`, raised before anything touches a device -> the cells (a list, or the
+    CUDA tensor as it is), or None without ramps."""
+    if (ramps is None) != (inflow is None):
+        raise ValueError("ramps and inflow go together: the cells, and inflow [T][L][R] with the rate each of them gets in every step "
+                         "(target= and checkpoint= are passed by keyword: they stay the last two arguments)")
+    if ramps is None:
+        return None
+    if isinstance(inflow, (bool, int)) or (isinstance(ramps, torch.Tensor) and ramps.dim() == 4):
+        # (what a caller gets who hands target and checkpoint over by position, where ramps and inflow now stand in front of them)
+        raise ValueError("ramps must be cell indices and inflow a float32 tensor [T][L][R] (got %s and %s): target= and checkpoint= are "
+                         "passed by keyword" % (type(ramps).__name__, type(inflow).__name__))
+    if checkpoint is None or checkpoint is False:
+        raise ValueError("ramps live on the checkpointed path only: pass checkpoint=True (or a segment length)")
+    if want_hist:
+        raise ValueError("ramps do not take want_hist: pass target= for the dense fit, or detectors= for the readings")
+    if r0.dim() != 2:
+        raise ValueError("r0 must be [L][N]")
+    L, N = int(r0.shape[0]), int(r0.shape[1])
+    cells = _detector_cells(ramps, N, "ramps")
+    R = cells.numel() if isinstance(cells, torch.Tensor) else len(cells)
+    if not isinstance(inflow, torch.Tensor) or inflow.dtype != torch.float32 or tuple(inflow.shape) != (int(T), L, R):
+        raise ValueError("inflow must be a float32 tensor of shape (T, L, R) = (%d, %d, %d)" % (int(T), L, R))
+    if inflow.device != r0.device:
+        raise ValueError("inflow must live on r0's device (%s), not %s" % (r0.device, inflow.device))
+    return cells
+
+
 def _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0):
     """_macro_bwd_done without boundary cells -> (g_r0, g_u0)."""
     if ctx.check_faults:
@@ -669,30 +759,31 @@ def _detector_indices(detectors, N, device):
     return cells if isinstance(cells, torch.Tensor) else torch.tensor(cells, dtype=torch.int32, device=device)
 
 
-def _detector_cells(detectors, N):
-    """The checks of _detector_indices without the upload -> the CUDA tensor as it is, or the list of cells."""
+def _detector_cells(detectors, N, name="detectors"):
+    """The checks of _detector_indices without the upload -> the CUDA tensor as it is, or the list of cells.  name: what the messages call
+    the argument (`ramps` of dhts.macro_rollout is a list of cells of the same kind)."""
     if isinstance(detectors, torch.Tensor) and detectors.is_cuda:
         if detectors.dtype != torch.int32 or detectors.dim() != 1 or not 1 <= detectors.numel() <= N:
-            raise ValueError("a CUDA `detectors` must be a one-dimensional int32 tensor of 1..%d entries" % N)
+            raise ValueError("a CUDA `%s` must be a one-dimensional int32 tensor of 1..%d entries" % (name, N))
         return detectors.contiguous()
     if isinstance(detectors, torch.Tensor):
         if detectors.dim() != 1 or detectors.dtype.is_floating_point or detectors.dtype.is_complex or detectors.dtype == torch.bool:
-            raise ValueError("`detectors` must be a one-dimensional integer tensor")
+            raise ValueError("`%s` must be a one-dimensional integer tensor" % name)
         cells = detectors.tolist()
     else:
         cells = list(detectors)
         if any(isinstance(c, bool) or int(c) != c for c in cells):
-            raise ValueError("`detectors` must hold integers")
+            raise ValueError("`%s` must hold integers" % name)
         cells = [int(c) for c in cells]
     if not cells:
-        raise ValueError("`detectors` is empty")
+        raise ValueError("`%s` is empty" % name)
     if cells[0] < 0 or cells[-1] >= N or any(a >= b for a, b in zip(cells, cells[1:])) or any(not 0 <= c < N for c in cells):
-        raise ValueError("`detectors` must be strictly ascending cell indices in [0, %d) (got %s)" % (N, cells))
+        raise ValueError("`%s` must be strictly ascending cell indices in [0, %d) (got %s)" % (name, N, cells))
     return cells
 
 
 def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, check_faults=True, detectors=None, ring=False,
-                  target=None, checkpoint=None):
+                  ramps=None, inflow=None, target=None, checkpoint=None):
     """T fused differentiable steps of L straight ARZ lanes (MacroRollout): returns (rT, yT, uT, qT), with want_hist also hist [T][L][3][N].
     checkpoint=None: the taped reverse mode; True or a segment length: the checkpointed one (same bits, no tape; MacroRollout).
 
@@ -712,8 +803,32 @@ def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, c
     ring=True (with checkpoint only; ghost_r and ghost_u None; not with want_hist): the lane is closed, cell N - 1 is the left neighbour
     of cell 0 and the circumference is N dx (MacroRolloutRing, MacroRolloutRingTarget).  detectors and target as above.  The
     lane's mass sum_k r[k] is conserved up to the float32 store of each cell, and the gradient carries the dependence of each end on the
-    other."""
+    other.
+
+    ramps with inflow (with checkpoint only; not with want_hist; with ring=True or either boundary form, and with detectors, target or
+    neither): on-ramps.  ramps: cell indices shared by all lanes, validated exactly as detectors are (a CUDA int32 tensor is used as it
+    is; an index outside [0, N) then names no cell).  inflow: float32 [T][L][R] on r0's device, inflow[t][l][j] the density rate
+    (normalised density per second) cell ramps[j] of lane l gets in step t, added behind the step's own float32 store as
+    (float)((double)r + dt (double)inflow) with y unchanged; a negative entry is an off-ramp, nothing is clamped.  The
+    return tuple is the form's own; inflow is a differentiable leaf and inflow.grad is float32 [T][L][R] (MacroRolloutRamp)."""
     _macro_ring_checks(ring, ghost_r, ghost_u, want_hist=want_hist, checkpoint=checkpoint, r0=r0, u0=u0)
+    cells = _macro_ramp_checks(r0, T, ramps, inflow, want_hist, checkpoint)
+    if cells is not None:
+        det = None
+        desc = macro_desc(int(r0.shape[0]), int(r0.shape[1]), float(dt), float(dx), float(u_max))
+        if target is not None:
+            _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
+        else:
+            det = None if detectors is None else _detector_cells(detectors, int(r0.shape[-1]))
+            _macro_checkpoint_segment(checkpoint, desc, int(T), False, 0 if det is None else len(det))
+        if not ring:
+            _macro_boundary_form(int(r0.shape[0]), ghost_r, ghost_u, int(T))
+        if isinstance(det, list):
+            det = torch.tensor(det, dtype=torch.int32, device=r0.device)
+        if isinstance(cells, list):
+            cells = torch.tensor(cells, dtype=torch.int32, device=r0.device)
+        return MacroRolloutRamp.apply(r0, u0, ghost_r, ghost_u, inflow, int(T), float(dt), float(dx), float(u_max), check_faults, det,
+                                      checkpoint, target, cells)
     if ring:
         if target is not None:
             _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
@@ -946,11 +1061,35 @@ def _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost):
     return sched, r, y, u, ueq, ghost
 
 
-def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out, det=None, taps=None, target=None, sse=None):
+def _macro_ramp_args(desc, T, ramps, inflow, g_inflow=None, reverse=False):
+    """What both raw wrappers check of the on-ramp arguments -> (ramps, R, inflow[, g_inflow]); g_inflow None: a new one."""
+    L, N = desc.n_lanes, desc.n_cells
+    if not isinstance(ramps, torch.Tensor) or ramps.dtype != torch.int32 or not ramps.is_cuda or ramps.dim() != 1:
+        raise ValueError("ramps must be a one-dimensional int32 CUDA tensor")
+    R = ramps.numel()
+    if not 1 <= R <= N:
+        raise ValueError("ramps must hold 1..%d cell indices (got %d)" % (N, R))
+    if not isinstance(inflow, torch.Tensor) or tuple(inflow.shape) != (T, L, R):
+        raise ValueError("inflow must have shape (%d, %d, %d)" % (T, L, R))
+    ramps, inflow = ramps.contiguous(), _f32c(inflow, "inflow")
+    if not reverse:
+        return ramps, R, inflow
+    if g_inflow is None:
+        g_inflow = torch.empty(T, L, R, dtype=torch.float32, device=inflow.device)
+    elif tuple(g_inflow.shape) != (T, L, R) or g_inflow.dtype != torch.float32 or not g_inflow.is_cuda or not g_inflow.is_contiguous():
+        raise ValueError("g_inflow must be a contiguous float32 CUDA tensor of shape (%d, %d, %d)" % (T, L, R))
+    return ramps, R, inflow, g_inflow
+
+
+def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out, det=None, taps=None, target=None, sse=None, ramps=None,
+                    inflow=None):
     """The checkpointed forward of both forms ("plain": detectors or nothing, "target": the dense fit): checks, buffers and the one C call
-    -> (out, taps or sse).  ckpt may be None (no checkpoint is kept) in the target form.  ghost None: the ring entry points."""
+    -> (out, taps or sse).  ckpt may be None (no checkpoint is kept) in the target form.  ghost None: the ring entry points.  ramps with
+    inflow: the on-ramp entry points (dhts_macro_rollout_fwd_ckpt_ramp / _target_ramp), which take all three boundary forms."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
     fit, keep = form == "target", ckpt
+    if (ramps is None) != (inflow is None):
+        raise ValueError("ramps and inflow go together")
     if fit:
         segment = _macro_target_args(desc, T, segment, ckpt, target, False)
         if ckpt is None:
@@ -971,6 +1110,18 @@ def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out,
         raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = tuple(torch.empty_like(r) for _ in range(4))
+    if ramps is not None:
+        ramps, R, inflow = _macro_ramp_args(desc, T, ramps, inflow)
+        head = (C.byref(desc), T, int(segment), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched), _ptr(out[0]), _ptr(out[1]),
+                _ptr(out[2]), _ptr(out[3]))
+        tail = (_ptr(ramps), R, _data(inflow), int(ghost is None), _ptr(err), _stream())
+        if fit:
+            check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target_ramp(*head, _data(ckpt), _data(target), _ptr(sse), *tail),
+                  "dhts_macro_rollout_fwd_ckpt_target_ramp")
+            return out, sse
+        check(_lib.lib().dhts_macro_rollout_fwd_ckpt_ramp(*head, _ptr(det), D, _with_det(taps, det), _data(ckpt), *tail),
+              "dhts_macro_rollout_fwd_ckpt_ramp")
+        return out, taps
     if ghost is None:
         state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]))
         if fit:
@@ -992,10 +1143,13 @@ def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out,
 
 
 def _macro_ckpt_bwd(form, desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, det=None, g_taps=None, target=None, g_sse=None,
-                    final=None, g_ghost=None):
-    """The checkpointed reverse sweep of both forms, as above -> (g_r0, g_y0, g_ghost); g_ghost is None for a ring (ghost None)."""
+                    final=None, g_ghost=None, ramps=None, inflow=None, g_inflow=None):
+    """The checkpointed reverse sweep of both forms, as above -> (g_r0, g_y0, g_ghost); g_ghost is None for a ring (ghost None).  ramps with
+    inflow: the on-ramp entry points -> (g_r0, g_y0, g_ghost, g_inflow [T][L][R])."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
     fit = form == "target"
+    if (ramps is None) != (inflow is None):
+        raise ValueError("ramps and inflow go together")
     if fit:
         segment = _macro_target_args(desc, T, segment, ckpt, target, True)
         if g_sse is not None:
@@ -1025,6 +1179,29 @@ def _macro_ckpt_bwd(form, desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment,
         raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    if ramps is not None:
+        ramps, R, inflow, g_inflow = _macro_ramp_args(desc, T, ramps, inflow, g_inflow, True)
+        if ghost is None and g_ghost is not None:
+            raise ValueError("a ring has no boundary cells and no g_ghost")
+        if ghost is not None:
+            want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
+            if g_ghost is None:
+                g_ghost = (torch.empty if sched else torch.zeros)(want, dtype=torch.float64, device=g_r.device)
+            elif tuple(g_ghost.shape) != want or g_ghost.dtype != torch.float64 or not g_ghost.is_contiguous():
+                raise ValueError("g_ghost must be a contiguous float64 tensor of shape %s" % (want,))
+            elif not sched:
+                g_ghost.zero_()
+        head = (C.byref(desc), T, int(segment), _data(ckpt), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched), _ptr(g_r),
+                _ptr(g_y))
+        tail = (_ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(ramps), R, _data(inflow), _data(g_inflow), int(ghost is None), _ptr(err),
+                _stream())
+        if fit:
+            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target_ramp(*head, _data(target), _ptr(g_sse), _ptr(final[0]), _ptr(final[1]),
+                                                                     _ptr(final[2]), *tail), "dhts_macro_rollout_bwd_ckpt_target_ramp")
+        else:
+            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_ramp(*head, _ptr(det), D, _with_det(g_taps, det), *tail),
+                  "dhts_macro_rollout_bwd_ckpt_ramp")
+        return out[0], out[1], (None if ghost is None else (g_ghost[:T] if sched else g_ghost)), g_inflow
     if ghost is None:
         if g_ghost is not None:
             raise ValueError("a ring has no boundary cells and no g_ghost")
@@ -1135,6 +1312,26 @@ def macro_rollout_fwd_ckpt_target_ring(desc, T, r, y, u, ueq, ckpt, target, segm
 def macro_rollout_bwd_ckpt_target_ring(desc, T, ckpt, r, y, u, ueq, g_r, g_y, target, g_sse=None, final=None, segment=0, err=None, out=None):
     """The reverse sweep of macro_rollout_fwd_ckpt_target_ring -> (g_r0, g_y0), as macro_rollout_bwd_ckpt_target."""
     return _macro_ckpt_bwd("target", desc, T, ckpt, r, y, u, ueq, None, g_r, g_y, segment, err, out, None, None, target, g_sse, final)[:2]
+
+
+# ---- on-ramp inflow at chosen cells of the checkpointed pair (dhts_macro_rollout_*_ckpt_ramp, DESIGN 4m) ---------------------------------
+def macro_rollout_fwd_ckpt_ramp(desc, T, r, y, u, ueq, ghost, ckpt, ramps, inflow, segment=0, det=None, target=None, err=None, out=None,
+                                taps=None, sse=None):
+    """macro_rollout_fwd_ckpt (target given: macro_rollout_fwd_ckpt_target) with a source in chosen cells: ramps int32 CUDA [R] cell
+    indices shared by all lanes, inflow float32 [T][L][R] the density rate cell ramps[j] of lane l gets in step t, added behind the
+    step's own float32 store as (float)((double)r + dt (double)inflow) (include/dhts.h).  ghost [L][2][4], a schedule [T][L][2][4], or
+    None: a ring.  Returns ((r, y, u, ueq) after T steps, taps [T][L][3][D] or sse [L][2] or None)."""
+    return _macro_ckpt_fwd("plain" if target is None else "target", desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out, det, taps, target,
+                           sse, ramps, inflow)
+
+
+def macro_rollout_bwd_ckpt_ramp(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, ramps, inflow, segment=0, det=None, g_taps=None, target=None,
+                                g_sse=None, final=None, err=None, out=None, g_ghost=None, g_inflow=None):
+    """The reverse sweep of macro_rollout_fwd_ckpt_ramp -> (g_r0, g_y0, g_ghost or None for a ring, g_inflow float32 [T][L][R]):
+    g_inflow[t][l][j] = (float)(dt (double)G_r) with G_r the cotangent of r at cell ramps[j] of the state after step t; the column of an
+    index outside [0, N) is 0.  The other arguments as macro_rollout_bwd_ckpt resp. (target given) macro_rollout_bwd_ckpt_target."""
+    return _macro_ckpt_bwd("plain" if target is None else "target", desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, det,
+                           g_taps, target, g_sse, final, g_ghost, ramps, inflow, g_inflow)
 
 
 def macro_rollout_fwd_jvp_ring(desc, T, r, y, u, ueq, t_r, t_y, det=None, err=None, err_jvp=None, out=None, taps=None, t_taps=None):

@@ -477,6 +477,53 @@ int dhts_macro_rollout_fwd_jvp_ring(const dhts_macro_desc *d, int T, int n_dir,
                                     float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
                                     const int32_t *det, int n_det, float *taps, float *t_taps,
                                     dhts_error *err, dhts_error *err_jvp, void *stream);
+/* ---- on-ramp inflow at chosen cells of the checkpointed pair ----
+ * A source term in chosen cells: ramps [n_ramp] are cell indices shared by all lanes, inflow [T][n_lanes][n_ramp] float32 the density
+ * rate (normalised density per second) that cell ramps[j] of lane l gets in step t.  Behind the Godunov update of step t, whose
+ * float32 store is unchanged, the owner of a ramp cell forms
+ *     r' = (float)((double)r + dt * (double)inflow[t][l][j]),   y' = y,
+ * and (u, u_eq) of the cell are the step's glue of (r', y): two roundings, the step's own and the source's.  Everything that reads
+ * "the state after step t" -- the next step, a ring's copies of its end cells, the checkpoint rows, the readings, the residual against
+ * `target`, the outputs -- sees (r', y).  A negative entry is an off-ramp; nothing is clamped and no fault code is added: keeping r
+ * inside (0, 1) is the caller's business, and DHTS_FAULT_CFL still catches a runaway.
+ * Reverse: the source is identity in (r, y), so the sweep is the siblings' and
+ *     g_inflow[t][l][j] = (float)(dt * (double)G_r),
+ * G_r the cotangent of r at cell ramps[j] of the state after step t, that row's detector column or target pair included (row T - 1:
+ * of the incoming cotangent).  g_inflow [T][n_lanes][n_ramp] float32: every entry is written.
+ *   dhts_macro_rollout_fwd_ckpt_ramp          as dhts_macro_rollout_fwd_ckpt        (ring: as dhts_macro_rollout_fwd_ckpt_ring)
+ *   dhts_macro_rollout_bwd_ckpt_ramp          as dhts_macro_rollout_bwd_ckpt        (ring: as dhts_macro_rollout_bwd_ckpt_ring)
+ *   dhts_macro_rollout_fwd_ckpt_target_ramp   as dhts_macro_rollout_fwd_ckpt_target (ring: as ..._fwd_ckpt_target_ring)
+ *   dhts_macro_rollout_bwd_ckpt_target_ramp   as dhts_macro_rollout_bwd_ckpt_target (ring: as ..._bwd_ckpt_target_ring)
+ * with the siblings' arguments, plans (dhts_macro_ckpt_plan resp. dhts_macro_ckpt_target_plan, dhts_macro_ckpt_bytes: no LDS is added),
+ * arithmetic and DHTS_E_INVALID rules, plus ramps / n_ramp / inflow (reverse: and g_inflow) and `ring`: nonzero = the lane is closed,
+ * `ghost` must be NULL, ghost_is_sched is not read and g_ghost is not written.
+ * DHTS_E_INVALID besides: n_ramp outside 1 .. n_cells; with T > 0 a NULL ramps or inflow, reverse also a NULL g_inflow; ring with a
+ * ghost.  Nothing is dereferenced or launched then.  T = 0: state and cotangents come back as they went in, no row is addressed.
+ * An index of ramps outside [0, n_cells) names no cell: nothing is added for it, no address is formed from it, and its column of
+ * g_inflow is 0.  PRECONDITION (as for det of the reverse sweep): the entries of ramps inside [0, n_cells) are distinct; with a
+ * repeated entry one of its columns is used and the result is unspecified, but memory-safe. */
+int dhts_macro_rollout_fwd_ckpt_ramp(const dhts_macro_desc *d, int T, int segment,
+                                     const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                     float *r_out, float *y_out, float *u_out, float *ueq_out,
+                                     const int32_t *det, int n_det, float *taps, void *ckpt,
+                                     const int32_t *ramps, int n_ramp, const float *inflow, int ring, dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_ckpt_ramp(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                     const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                     const float *g_r, const float *g_y, const int32_t *det, int n_det, const float *g_taps,
+                                     float *g_r_out, float *g_y_out, double *g_ghost,
+                                     const int32_t *ramps, int n_ramp, const float *inflow, float *g_inflow, int ring, dhts_error *err,
+                                     void *stream);
+int dhts_macro_rollout_fwd_ckpt_target_ramp(const dhts_macro_desc *d, int T, int segment,
+                                            const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
+                                            int ghost_is_sched, float *r_out, float *y_out, float *u_out, float *ueq_out, void *ckpt,
+                                            const float *target, double *sse,
+                                            const int32_t *ramps, int n_ramp, const float *inflow, int ring, dhts_error *err, void *stream);
+int dhts_macro_rollout_bwd_ckpt_target_ramp(const dhts_macro_desc *d, int T, int segment, const void *ckpt,
+                                            const float *r, const float *y, const float *u, const float *ueq, const float *ghost,
+                                            int ghost_is_sched, const float *g_r, const float *g_y, const float *target, const double *g_sse,
+                                            const float *r_fin, const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out,
+                                            double *g_ghost, const int32_t *ramps, int n_ramp, const float *inflow, float *g_inflow, int ring,
+                                            dhts_error *err, void *stream);
 /* tangent of y = r (u - u_eq(r)): t_y = (dy/dr) t_r + (dy/du) t_u, the partials dhts_macro_state_from_ru_bwd applies, in float32 */
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u,
                                  float *t_y, void *stream);
