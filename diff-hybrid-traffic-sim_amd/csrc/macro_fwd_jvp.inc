@@ -62,6 +62,20 @@ __device__ __forceinline__ void ring_rec_copies_direct(CellRec *CR, int N, bool 
     if (vc && ic == (unsigned)(N - 1)) { CR[0].st = st; CR[0].sh = make_double2(cp.s, cp.h); CR[0].q0 = make_double2(cp.q0, 0.); }
     if (vc && ic == 0u) { CR[N + 1].st = st; CR[N + 1].sh = make_double2(cp.s, cp.h); CR[N + 1].q0 = make_double2(cp.q0, 0.); }
 }
+// kRamp (the kernel's last template argument; dhts_macro_rollout_fwd_jvp_ramp / _ring_ramp, DESIGN 4n): DESIGN 4m's source in chosen cells and
+// its tangent.  A ramp cell finds its column of ramps[] + 1 in the second half of its record's q0 (ramp_col_set / ramp_col_get,
+// macro_ckpt.inc: declared here, defined there), which the ramp forms leave as it is.
+__device__ __forceinline__ void ramp_col_set(CellRec *CR, unsigned cell, int col1);
+__device__ __forceinline__ int ramp_col_get(const CellRec *CR, unsigned cell);
+// the loads that fill ts have all been issued and have arrived behind this line: none of them is moved down to its use, where each
+// would wait for its own round trip in turn
+template <int kK>
+__device__ __forceinline__ void ramp_arrived(float (&ts)[kK]) {
+    static_assert(kK == 1 || kK == 2 || kK == 4, "one operand per direction");
+    if constexpr (kK == 1) asm volatile("" : "+v"(ts[0]));
+    else if constexpr (kK == 2) asm volatile("" : "+v"(ts[0]), "+v"(ts[1]));
+    else asm volatile("" : "+v"(ts[0]), "+v"(ts[1]), "+v"(ts[2]), "+v"(ts[3]));
+}
 __host__ __device__ inline size_t fwd_jvp_rec_bytes(int N) {       // = fwd2_lds_bytes(N) rounded up to 16
     return (sizeof(CellRec) * (size_t)(N + 2) + 16 * (size_t)(N + 1) + sizeof(int) * (size_t)(N + 2) + 16 + 15) & ~(size_t)15;
 }
@@ -78,7 +92,19 @@ __host__ __device__ inline size_t fwd_jvp_lds_bytes(int N, int kK) {
 // spill under the 128 of a 1024-thread block.
 // err: DHTS_FAULT_CFL (step, lane, interface), as the lane kernel raises it.  err_jvp: DHTS_FAULT_NAN with the lane's EARLIEST
 // (step, cell) of a non-finite tangent (jvp_raise_first).
-template <int kK, int kP, MacroBoundary kBound, bool kTaps>
+// kRamp: ramps [n_ramp] cell indices shared by all lanes, inflow [T][L][n_ramp], t_inflow [kK][T][L][n_ramp] or NULL (zero tangents).  Behind
+// the Godunov update of step s the owner of cell ramps[j] forms r' = (float)((double)r + dt (double)inflow[s][l][j]) and, behind jvp_cell,
+// nr' = (float)((double)nr + dt (double)t_inflow[d][s][l][j]) for d < n_act; y and ny stay.  Both additions are in front of everything that
+// reads the state or the tangents after step s: the record, the kept rd_own, the copy the next step reads, the ring's seam copies, the
+// finiteness test, the outputs and the readings.  With kP = 1 or 2 the owner holds its 1 + kK entries of the row its next update adds
+// in registers, asked for a whole step ahead (ramp_src / ramp_tan below): no global load is on any wavefront's dependent chain.  With a
+// run-time number of passes it loads them in the step, all at once (ramp_arrived); a wavefront without a ramp cell branches round the
+// loads (its threads find column 0 in their records), so none of them is on its chain.
+// Thread q writes column q + 1 into the record of cell ramps[q] once, behind the prologue's barrier; the first reader is behind one more
+// barrier of the prologue (kP = 1, 2) resp. the update of step 0, two barriers later.  An entry of ramps outside [0, N) is compared as
+// an unsigned value and forms no address.  No barrier is added to the step loop, no atomic and no LDS anywhere; with kRamp false the
+// kernel is the one it was.
+template <int kK, int kP, MacroBoundary kBound, bool kTaps, bool kRamp>
 __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     int L, int N, int T, int p_arg, double dt, double dx, double um,
     const float *__restrict__ r_in, const float *__restrict__ y_in, const float *__restrict__ u_in,
@@ -87,7 +113,8 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     float *__restrict__ r_out, float *__restrict__ y_out, float *__restrict__ u_out, float *__restrict__ q_out,
     float *__restrict__ t_r_out, float *__restrict__ t_y_out,
     const int32_t *__restrict__ det, int n_det, float *__restrict__ taps, float *__restrict__ t_taps,
-    dhts_error *err, dhts_error *err_jvp) {
+    dhts_error *err, dhts_error *err_jvp,
+    const int32_t *__restrict__ ramps, int n_ramp, const float *__restrict__ inflow, const float *__restrict__ t_inflow) {
     constexpr bool kSched = kBound == kBoundSched, kRing = kBound == kBoundRing;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = blockIdx.x;
@@ -128,6 +155,12 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     for (int i = tid; i < 2 * kK * P; i += blockDim.x) TN[i] = make_float2(0.f, 0.f);
     if (tid == 0) { Q[0] = N; CNT[0] = 1; CNT[1] = 1; }      // entry 0 of every step's queue: interface N
     __syncthreads();
+    if constexpr (kRamp) {
+        for (int q = tid; q < n_ramp; q += blockDim.x) {
+            const unsigned rc = (unsigned)ramps[q];
+            if (rc < (unsigned)N) ramp_col_set(CR, rc, q + 1);
+        }
+    }
     // the tangents of the initial state into copy 0
     for (int d = 0; d < n_act; ++d)
         for (int k = tid; k < N; k += blockDim.x) {
@@ -152,6 +185,32 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
     const int Nv = kRing && kTaps ? ring_len(N) : N; // (a ring with detectors, where no scalar register is to spare: see ring_rec_copies)
     constexpr bool kKeep = kP > 0;
     double rd_own[kP > 0 ? kP : 1], yd_own[kP > 0 ? kP : 1];
+    // kRamp with a literal number of passes (kPre): the entries of inflow and t_inflow that the thread's next update adds wait in
+    // registers, one row per pass, asked for a whole step ahead as the checkpointed forward does -- no global load on the step's
+    // dependent chain at all.  A run-time number of passes (kP = 0, DHTS_OPT_MACRO_FWD_WAVES alone) would index them at run time, which is
+    // scratch: there the owner loads in the step.  ramp_load: the 1 + n_act entries of row `row` for column rc (t_inflow NULL or a slot
+    // d >= n_act: 0, nothing is read).
+    constexpr bool kPre = kRamp && kP > 0;
+    const size_t dir_inflow = kRamp ? (size_t)T * L * n_ramp : 0;
+    float ramp_src[kP > 0 ? kP : 1], ramp_tan[kP > 0 ? kP : 1][kK];
+    auto ramp_load = [&](const int row, const int rc, float &s, float (&ts)[kK]) {
+        const size_t e = ((size_t)row * L + lane) * n_ramp + (rc - 1);
+        s = inflow[e];
+#pragma unroll
+        for (int d = 0; d < kK; ++d) ts[d] = t_inflow && d < n_act ? t_inflow[d * dir_inflow + e] : 0.f;
+    };
+    if constexpr (kPre) {
+        __syncthreads();                             // the columns are in the records (once per launch: the step loop takes no barrier more)
+#pragma unroll
+        for (int j = 0; j < kP; ++j) {
+            const int i = lo + (j << 6) + t;
+            const int rc = i < N ? ramp_col_get(CR, (unsigned)i) : 0;
+            ramp_src[j] = 0.f;
+#pragma unroll
+            for (int d = 0; d < kK; ++d) ramp_tan[j][d] = 0.f;
+            if (rc) ramp_load(0, rc, ramp_src[j], ramp_tan[j]);
+        }
+    }
 
     float4 sched_st = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 *sched_p = nullptr;
@@ -233,6 +292,8 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
                 // the tangents of step n - 1 (dmacro_lane.py:126-129 applied untransposed): the products of the cell's two interfaces,
                 // read where the fluxes are read
                 const float4 aL = PA[ic], bL = PB[ic], aR = PA[ic + 1], bR = PB[ic + 1];
+                int rc = 0;                                  // kRamp: the cell's column of ramps[] + 1, read beside the products
+                if constexpr (kRamp) rc = vc ? ramp_col_get(CR, ic) : 0;
                 JvpBlocks b;
                 cell_blocks(aL, bL, aR, bR, cf, ncf, b.d0, b.d1, b.d2);
                 bool fin = true;
@@ -242,6 +303,9 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
                     const float2 tl = tq[d * P + ic], tc = tq[d * P + ic + 1], tr = tq[d * P + ic + 2];
                     float nr, ny;
                     jvp_cell(b, tl.x, tl.y, tc.x, tc.y, tr.x, tr.y, nr, ny);
+                    if constexpr (kPre) {                    // the tangent of the on-ramp's source of step n - 1 (a slot d >= n_act holds 0)
+                        if (rc && t_inflow) nr = (float)((double)nr + dt * (double)ramp_tan[kP > 0 ? j : 0][d]);
+                    }
                     if (vc) tw[d * P + ic + 1] = make_float2(nr, ny);
                     if constexpr (kRing) {                   // the copy step n reads: slot 0 is cell N - 1, slot N + 1 is cell 0
                         if (seam) {
@@ -252,17 +316,54 @@ __global__ __launch_bounds__(768) void macro_rollout_fwd_jvp_kernel(
                     fin = fin && isfinite(nr) && isfinite(ny);
                     if (!solve && vc && d < n_act) { t_r_out[d * dir_state + base + i] = nr; t_y_out[d * dir_state + base + i] = ny; }
                 }
+                float src = 0.f;
+                if constexpr (kPre) {
+                    // the source of step n - 1 is in the register; row n leaves for it, a whole step ahead of the update that adds it
+                    src = ramp_src[kP > 0 ? j : 0];
+                    if (rc && solve) ramp_load(n, rc, ramp_src[kP > 0 ? j : 0], ramp_tan[kP > 0 ? j : 0]);
+                }
+                if constexpr (kRamp && !kPre) {
+                    // a run-time number of passes holds no row in registers: the owner asks for its 1 + n_act entries of row n - 1 here, all
+                    // of them before it waits for the first, and adds the tangents to what it has just stored, in front of every reader
+                    if (rc) {
+                        float ts[kK];
+                        ramp_load(n - 1, rc, src, ts);
+                        ramp_arrived(ts);
+                        if (t_inflow) {
+#pragma unroll
+                            for (int d = 0; d < kK; ++d) {
+                                if (d < n_act) {
+                                    float2 *own_t = tw + d * P + ic + 1;
+                                    float2 v = *own_t;
+                                    v.x = (float)((double)v.x + dt * (double)ts[d]);
+                                    *own_t = v;
+                                    if constexpr (kRing) {
+                                        if (seam) { own_t[ring_lo(Nv, ic)] = v; own_t[ring_hi(Nv, ic)] = v; }
+                                    }
+                                    fin = fin && isfinite(v.x);
+                                    if (!solve) t_r_out[d * dir_state + base + i] = v.x;
+                                }
+                            }
+                        }
+                    }
+                }
                 if (vc && bad_step < 0 && !fin) { bad_step = n - 1; bad_cell = i; }
                 const double r_old = kKeep ? rd_own[kP > 0 ? j : 0] : (double)st.x;
                 const double y_old = kKeep ? yd_own[kP > 0 ? j : 0] : (double)st.y;
                 st.x = (float)(r_old + (Fl.x - Fr.x) * c);
                 st.y = (float)(y_old + (Fl.y - Fr.y) * c);
+                if constexpr (kRamp) {
+                    if (rc) st.x = (float)((double)st.x + dt * (double)src);
+                }
                 if (kKeep) { rd_own[kP > 0 ? j : 0] = (double)st.x; yd_own[kP > 0 ? j : 0] = (double)st.y; }
                 CellPre cp;
                 cell_glue_pre(st.x, st.y, umf, kc, st.z, st.w, cp);     // set_next_state_vector_y, :282-299
-                if (vc && solve) { own->st = st; own->sh = make_double2(cp.s, cp.h); own->q0 = make_double2(cp.q0, 0.); }
+                if (vc && solve) {
+                    own->st = st; own->sh = make_double2(cp.s, cp.h);
+                    if constexpr (kRamp) own->q0.x = cp.q0; else own->q0 = make_double2(cp.q0, 0.);
+                }
                 else if (kTaps && vc) own->st = st;          // the final step's state, for the taps below
-                if constexpr (kRing && solve) ring_rec_copies(CR, Nv, vc, ic, st, cp);
+                if constexpr (kRing && solve) ring_rec_copies<kRamp>(CR, Nv, vc, ic, st, cp);
             }
             if (!solve) {
                 if (vc) { r_out[base + i] = st.x; y_out[base + i] = st.y; u_out[base + i] = st.z; q_out[base + i] = st.w; }

@@ -1655,8 +1655,8 @@ struct MacroForm {
     double *sse;
     const double *g_sse;
     const float *fin_r, *fin_y, *fin_u;
-    // on-ramps of the checkpointed pair: cells ramps [n_ramp] shared by all lanes, the density rates inflow [T][L][n_ramp] and, reverse,
-    // their cotangent g_inflow [T][L][n_ramp]; `ramps` NULL: not a ramp form
+    // on-ramps of the checkpointed pair and of the fused forward + tangent kernel: cells ramps [n_ramp] shared by all lanes, the density
+    // rates inflow [T][L][n_ramp] and, reverse, their cotangent g_inflow [T][L][n_ramp]; `ramps` NULL: not a ramp form
     const int32_t *ramps;
     int n_ramp;
     const float *inflow;
@@ -1849,16 +1849,18 @@ static JvpPlan macro_jvp_plan(const dhts_macro_desc *d, int T, int n_dir) {
 
 // The per-direction arrays of the two tangent entry points, [K] outermost: the tangents of (r, y) in and out, t_ghost [K][L][2][2] or
 // beside a schedule [K][T][L][2][2] (NULL: zero), the tangent readings [K][T][L][2][n_det] (with detectors).  ..._at: those of one
-// launch, which starts at direction k0.
+// launch, which starts at direction k0.  inflow: the fused kernel's ramp forms alone -- the tangents of f.inflow, [K][T][L][n_ramp] (NULL: zero).
 struct MacroTangents {
     const float *r, *y, *ghost;
     float *r_out, *y_out, *taps;
+    const float *inflow;
 };
 static MacroTangents macro_tangents_at(const MacroTangents &t, int k0, const dhts_macro_desc *d, int T, const MacroForm &f) {
     const size_t dir_state = (size_t)d->n_lanes * d->n_cells, dir_ghost = (f.sched() ? (size_t)T : 1) * d->n_lanes * 4,
-                 dir_taps = (size_t)T * d->n_lanes * 2 * f.n_det;
+                 dir_taps = (size_t)T * d->n_lanes * 2 * f.n_det, dir_inflow = (size_t)T * d->n_lanes * f.n_ramp;
     return {t.r + k0 * dir_state, t.y + k0 * dir_state, t.ghost ? t.ghost + k0 * dir_ghost : nullptr,
-            t.r_out + k0 * dir_state, t.y_out + k0 * dir_state, f.det ? t.taps + k0 * dir_taps : nullptr};
+            t.r_out + k0 * dir_state, t.y_out + k0 * dir_state, f.det ? t.taps + k0 * dir_taps : nullptr,
+            f.ramps && t.inflow ? t.inflow + k0 * dir_inflow : nullptr};
 }
 // how the kernels read t_ghost: 0 none, 1 the same in front of every step, 2 a schedule
 static int macro_ghost_mode(const MacroTangents &t, const MacroForm &f) { return !t.ghost ? 0 : (f.sched() ? 2 : 1); }
@@ -1937,12 +1939,15 @@ static int macro_fwd_jvp_launch(const dhts_macro_desc *d, int T, int n_dir, cons
         pick<0, 1, 2>(pl.p <= 2 ? pl.p : 0, [&](auto pv) {
             pick<kBoundConst, kBoundSched, kBoundRing>(f.bound, [&](auto bc) {
                 pick<0, 1>(f.det != nullptr, [&](auto tap) {
-                    constexpr int kK = decltype(kv)::value, kP = decltype(pv)::value;
-                    constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
-                    constexpr bool kT = decltype(tap)::value != 0;
-                    ok = launch_lds(macro_rollout_fwd_jvp_kernel<kK, kP, kS, kT>, L, 64 * pl.W, fwd_jvp_lds_bytes(N, kK), kLdsDefault, stream, L,
-                                    N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, a.r, a.y, a.ghost, ghost_mode, n_act, r_out, y_out,
-                                    u_out, ueq_out, a.r_out, a.y_out, f.det, f.n_det, o_taps, a.taps, o_err, err_jvp);
+                    pick<0, 1>(f.ramps != nullptr, [&](auto ramp) {
+                        constexpr int kK = decltype(kv)::value, kP = decltype(pv)::value;
+                        constexpr MacroBoundary kS = (MacroBoundary) decltype(bc)::value;
+                        constexpr bool kT = decltype(tap)::value != 0, kR = decltype(ramp)::value != 0;
+                        ok = launch_lds(macro_rollout_fwd_jvp_kernel<kK, kP, kS, kT, kR>, L, 64 * pl.W, fwd_jvp_lds_bytes(N, kK), kLdsDefault,
+                                        stream, L, N, T, pl.p, d->dt, d->dx, d->u_max, r, y, u, ueq, ghost, a.r, a.y, a.ghost, ghost_mode, n_act,
+                                        r_out, y_out, u_out, ueq_out, a.r_out, a.y_out, f.det, f.n_det, o_taps, a.taps, o_err, err_jvp, f.ramps,
+                                        f.n_ramp, f.inflow, a.inflow);
+                    });
                 });
             });
         });
@@ -2242,19 +2247,23 @@ static int macro_rollout_fwd_jvp_entry(const dhts_macro_desc *d, int T, int n_di
                                const float *t_r, const float *t_y, const float *t_ghost,
                                float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
                                const int32_t *det, int n_det, float *taps, float *t_taps,
-                               dhts_error *err, dhts_error *err_jvp, void *stream) {
+                               dhts_error *err, dhts_error *err_jvp, void *stream,
+                               const int32_t *ramps = nullptr, int n_ramp = 0, const float *inflow = nullptr, const float *t_inflow = nullptr) {
     if (!macro_fwd_args_ok(d, T, r, y, u, ueq, ring_or(bound, r, ghost), r_out, y_out, u_out, ueq_out) || n_dir < 1 || !t_r || !t_y ||
         !t_r_out || !t_y_out)
         return DHTS_E_INVALID;
     if (!macro_det_pair_ok(d, det, n_det, taps) || !macro_det_pair_ok(d, det, n_det, t_taps)) return DHTS_E_INVALID;
+    // the ramp entry points: no ramp is the sibling's call; the arrays only where a step reads them (t_inflow NULL: zero tangents)
+    if (n_ramp < 0 || (n_ramp > 0 && T > 0 && (!ramps || !inflow))) return DHTS_E_INVALID;
     if (macro_fwd_jvp_plan(d, T, n_dir).kmax < 1) return DHTS_E_INVALID;       // the lane does not fit: the taped pair covers it
-    const MacroTangents t = {t_r, t_y, t_ghost, t_r_out, t_y_out, t_taps};
+    MacroTangents t = {t_r, t_y, t_ghost, t_r_out, t_y_out, t_taps, nullptr};
     if (T == 0) {                                                // no step: state and tangents come back as they went in, no row is addressed
         if (!macro_tangents_copy(d, n_dir, t, stream)) return DHTS_E_LAUNCH;
         return macro_state_copy(d, r, y, u, ueq, r_out, y_out, u_out, ueq_out, stream);
     }
     MacroForm f = macro_bound_form(bound, det, n_det);
     f.taps = taps;
+    if (n_ramp > 0) { f.ramps = ramps; f.n_ramp = n_ramp; f.inflow = inflow; t.inflow = t_inflow; }
     return macro_fwd_jvp_launch(d, T, n_dir, r, y, u, ueq, ghost, t, r_out, y_out, u_out, ueq_out, f, err, err_jvp, stream);
 }
 int dhts_macro_rollout_fwd_jvp(const dhts_macro_desc *d, int T, int n_dir,
@@ -2512,6 +2521,27 @@ int dhts_macro_rollout_bwd_ckpt_target_ramp(const dhts_macro_desc *d, int T, int
     return macro_rollout_bwd_ckpt_target_entry(d, T, segment, ckpt, r, y, u, ueq, ghost, bound, g_r, g_y, target, g_sse, r_fin, y_fin, u_fin,
                                                g_r_out, g_y_out, ring ? nullptr : g_ghost, err, stream,
                                                MacroRamps{true, ramps, n_ramp, inflow, g_inflow});
+}
+// ---- on-ramp inflow and its tangent on the fused forward + tangent kernel -------------------------------------------
+int dhts_macro_rollout_fwd_jvp_ramp(const dhts_macro_desc *d, int T, int n_dir,
+                                    const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                    const float *t_r, const float *t_y, const float *t_ghost,
+                                    float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                                    const int32_t *det, int n_det, float *taps, float *t_taps,
+                                    dhts_error *err, dhts_error *err_jvp, void *stream,
+                                    const int32_t *ramps, int n_ramp, const float *inflow, const float *t_inflow) {
+    return macro_rollout_fwd_jvp_entry(d, T, n_dir, r, y, u, ueq, ghost, ghost_is_sched ? kBoundSched : kBoundConst, t_r, t_y, t_ghost, r_out,
+                                       y_out, u_out, ueq_out, t_r_out, t_y_out, det, n_det, taps, t_taps, err, err_jvp, stream, ramps, n_ramp,
+                                       inflow, t_inflow);
+}
+int dhts_macro_rollout_fwd_jvp_ring_ramp(const dhts_macro_desc *d, int T, int n_dir,
+                                         const float *r, const float *y, const float *u, const float *ueq, const float *t_r, const float *t_y,
+                                         float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                                         const int32_t *det, int n_det, float *taps, float *t_taps,
+                                         dhts_error *err, dhts_error *err_jvp, void *stream,
+                                         const int32_t *ramps, int n_ramp, const float *inflow, const float *t_inflow) {
+    return macro_rollout_fwd_jvp_entry(d, T, n_dir, r, y, u, ueq, nullptr, kBoundRing, t_r, t_y, nullptr, r_out, y_out, u_out, ueq_out,
+                                       t_r_out, t_y_out, det, n_det, taps, t_taps, err, err_jvp, stream, ramps, n_ramp, inflow, t_inflow);
 }
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u, float *t_y,
                                  void *stream) {

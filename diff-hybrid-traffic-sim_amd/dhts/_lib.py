@@ -176,6 +176,11 @@ SIGNATURES = {
                                                 [C.c_int, _P, C.c_int] + [_P] * 2),
     "dhts_macro_rollout_bwd_ckpt_target_ramp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 6 + [C.c_int] + [_P] * 11 +
                                                 [C.c_int, _P, _P, C.c_int] + [_P] * 2),
+    # the siblings' arguments, then ramps, n_ramp, inflow, t_inflow
+    "dhts_macro_rollout_fwd_jvp_ramp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 5 + [C.c_int] + [_P] * 10 + [C.c_int] +
+                                        [_P] * 5 + [_P, C.c_int, _P, _P]),
+    "dhts_macro_rollout_fwd_jvp_ring_ramp": (C.c_int, [C.POINTER(MacroDesc), C.c_int, C.c_int] + [_P] * 13 + [C.c_int] + [_P] * 5 +
+                                             [_P, C.c_int, _P, _P]),
     "dhts_micro_step_fwd": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),
     "dhts_micro_step_fwd_tensor_head": (C.c_int, [C.POINTER(MicroDesc)] + [_P] * 10),

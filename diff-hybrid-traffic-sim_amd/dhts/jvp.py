@@ -7,11 +7,13 @@ import torch
 from . import ops
 
 
-def _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u):
-    """Shape checks of dhts.macro_rollout_jvp's tangents (ValueError, before anything touches a device).  Returns K."""
-    given = [(n, t) for n, t in (("t_r0", t_r0), ("t_u0", t_u0), ("t_ghost_r", t_ghost_r), ("t_ghost_u", t_ghost_u)) if t is not None]
+def _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u, t_inflow=None, n_ramp=0):
+    """Shape checks of dhts.macro_rollout_jvp's tangents (ValueError, before anything touches a device).  Returns K.  t_inflow: the
+    tangent of `inflow` [T][L][n_ramp], one more leaf."""
+    given = [(n, t) for n, t in (("t_r0", t_r0), ("t_u0", t_u0), ("t_ghost_r", t_ghost_r), ("t_ghost_u", t_ghost_u), ("t_inflow", t_inflow))
+             if t is not None]
     if not given:
-        raise ValueError("macro_rollout_jvp needs at least one of t_r0, t_u0, t_ghost_r, t_ghost_u")
+        raise ValueError("macro_rollout_jvp needs at least one of t_r0, t_u0, t_ghost_r, t_ghost_u, t_inflow")
     if r0.dim() != 2:
         raise ValueError("r0 must be [L][N]")
     L, N = r0.shape
@@ -21,15 +23,17 @@ def _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u):
     K = int(given[0][1].shape[0])
     want_g = (K, int(T), L, 2) if ghost_r is not None and ghost_r.dim() == 3 else (K, L, 2)
     for n, t in given:
-        want = (K, L, N) if n in ("t_r0", "t_u0") else want_g
+        want = (K, L, N) if n in ("t_r0", "t_u0") else ((K, int(T), L, n_ramp) if n == "t_inflow" else want_g)
         if tuple(t.shape) != want:
             raise ValueError("%s must have shape %s (got %s): all tangents share K = %d, boundary tangents follow the form of ghost_r"
                              % (n, want, tuple(t.shape), K))
+    if t_inflow is not None and (t_inflow.dtype != torch.float32 or t_inflow.device != r0.device):
+        raise ValueError("t_inflow must be a float32 tensor on r0's device (%s) (got %s on %s)" % (r0.device, t_inflow.dtype, t_inflow.device))
     return K
 
 
 def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, t_u0=None, t_ghost_r=None, t_ghost_u=None,
-                      detectors=None, check_faults=True, fused=False, ring=False):
+                      detectors=None, check_faults=True, fused=False, ring=False, ramps=None, inflow=None, t_inflow=None):
     """dhts.macro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((rT, yT, uT, qT[, readings]), (t_rT, t_yT, t_uT[, t_readings])).  The primal outputs are those of
@@ -51,12 +55,28 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
     Lanes of more than 1410 cells do not fit it (ValueError before anything is launched; fused=False covers them).
 
     ring=True (with fused=True only; ghost_r, ghost_u, t_ghost_r and t_ghost_u None): the lane is closed as in dhts.macro_rollout(ring=True)
-    (dhts_macro_rollout_fwd_jvp_ring); the tangents of the two end cells are each other's boundary tangents."""
+    (dhts_macro_rollout_fwd_jvp_ring); the tangents of the two end cells are each other's boundary tangents.
+
+    ramps / inflow / t_inflow (with fused=True only): dhts.macro_rollout's on-ramps -- `ramps` the cells, `inflow` float32 [T][L][R] the
+    density rate cell ramps[j] of lane l gets in step t -- and t_inflow float32 [K][T][L][R], the tangent of `inflow`: one more leaf
+    tangent, which counts as "at least one given" and shares K; None is zero, so ramps and inflow alone give the other leaves' tangents
+    through a rollout with a source.  The primal outputs are dhts.macro_rollout(..., checkpoint=True, ramps=, inflow=)'s bit for bit, and
+    with detectors the readings and t_readings are those after the source (dhts_macro_rollout_fwd_jvp_ramp / _ring_ramp).
+    ramps without inflow (or the reverse), t_inflow without ramps, any of the three with fused=False, a wrong shape, dtype or device:
+    ValueError before anything touches a device."""
     ops._macro_ring_checks(ring, ghost_r, ghost_u, t_ghost_r, t_ghost_u, fused=fused, r0=r0, u0=u0)
     if not ring and (ghost_r.dim() != ghost_u.dim() or ghost_r.dim() not in (2, 3)):
         raise ValueError("ghost_r and ghost_u must both be [L][2] or both [T][L][2]")
     T = int(T)
-    K = _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u)
+    if (ramps is None) != (inflow is None):
+        raise ValueError("ramps and inflow go together: the cells, and inflow [T][L][R] with the rate each of them gets in every step")
+    if t_inflow is not None and ramps is None:
+        raise ValueError("t_inflow needs ramps and inflow: it is the tangent of inflow")
+    if ramps is not None and not fused:
+        raise ValueError("ramps, inflow and t_inflow live on the fused forward + tangent kernel only: pass fused=True")
+    cells = ops._macro_ramp_checks(r0, T, ramps, inflow, False, True)
+    n_ramp = 0 if cells is None else (cells.numel() if isinstance(cells, torch.Tensor) else len(cells))
+    K = _jvp_tangents(r0, ghost_r, T, t_r0, t_u0, t_ghost_r, t_ghost_u, t_inflow, n_ramp)
     L, N = r0.shape
     sched = not ring and ghost_r.dim() == 3
     want = (T, L, 2) if sched else (L, 2)
@@ -102,8 +122,14 @@ def macro_rollout_jvp(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, *, t_r0=None, 
             t_ghost = torch.stack([tgr, tgy], dim=-1).contiguous()          # [K][L][2][2], or [K][T][L][2][2]
         if fused:                            # one kernel, no tape
             err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
+            ramp = {}
+            if cells is not None:
+                ramp = dict(ramps=cells if isinstance(cells, torch.Tensor) else torch.tensor(cells, dtype=torch.int32, device=dev),
+                            inflow=ops._f32c(inflow.detach(), "inflow"),
+                            t_inflow=None if t_inflow is None else ops._f32c(t_inflow.detach(), "t_inflow"))
             (rT, yT, uT, qT, readings), (t_rT, t_yT, t_taps) = ops.macro_rollout_fwd_jvp(desc, T, r0c, y0, u0c, q0, ghost, tr0, ty0,
-                                                                                         t_ghost=t_ghost, det=det, err=err, err_jvp=err_jvp)
+                                                                                         t_ghost=t_ghost, det=det, err=err, err_jvp=err_jvp,
+                                                                                         **ramp)
             if check_faults:                 # the pair's order: the forward's record first, then the tangents'
                 ops.raise_on_fault(err)
                 ops.raise_on_fault(err_jvp)

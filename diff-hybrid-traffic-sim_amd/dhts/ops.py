@@ -947,17 +947,23 @@ _MACRO_FWD_JVP_PLAN_KEYS = ("waves", "passes", "dirs_per_launch", "launches", "l
 
 
 def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, det=None, err=None, err_jvp=None, out=None, taps=None,
-                          t_taps=None):
+                          t_taps=None, ramps=None, inflow=None, t_inflow=None):
     """The rollout and K tangent directions of it in one kernel, no tape (dhts_macro_rollout_fwd_jvp, include/dhts.h): what
     macro_rollout_fwd / _fwd_sched / _fwd_taps followed by macro_rollout_jvp returns, bit for bit.  r, y, u, ueq [L][N]; ghost [L][2][4]
     or a schedule [T][L][2][4]; t_r, t_y [K][L][N]; t_ghost None (zero), [K][L][2][2], or [K][T][L][2][2] beside a schedule; det int32
     CUDA [D] or None.  err: the forward's fault record (CFL), err_jvp: the tangent sweep's (the earliest non-finite tangent); each may be
     None.  out: (r_out, y_out, u_out, ueq_out, t_r_out, t_y_out) buffers to fill; taps [T][L][3][D] and t_taps [K][T][L][2][D] are
     allocated with det unless handed in.  A lane the plan cannot take is a ValueError before anything is launched.
+    ramps int32 CUDA [R] with inflow float32 [T][L][R]: DESIGN 4m's source behind every step (dhts_macro_rollout_fwd_jvp_ramp /
+    _ring_ramp), and t_inflow None (zero) or float32 [K][T][L][R] its tangent per direction.
     Returns ((rT, yT, uT, qT, taps), (t_rT, t_yT, t_taps)), the readings None without det."""
     L, N, T = desc.n_lanes, desc.n_cells, int(T)
     if T < 0:
         raise ValueError("T must be >= 0")
+    if (ramps is None) != (inflow is None):
+        raise ValueError("ramps and inflow go together")
+    if t_inflow is not None and ramps is None:
+        raise ValueError("t_inflow without ramps")
     for name, t in (("r", r), ("y", y), ("u", u), ("ueq", ueq)):
         if tuple(t.shape) != (L, N):
             raise ValueError("%s must have shape (%d, %d)" % (name, L, N))
@@ -985,6 +991,23 @@ def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, 
         if len(out) != 6:
             raise ValueError("out must be (r_out, y_out, u_out, ueq_out, t_r_out, t_y_out)")
     out = _state_out(("r_out", "y_out", "u_out", "ueq_out", "t_r_out", "t_y_out"), out, (r, y, u, ueq, t_r, t_y))
+    if ramps is not None:
+        ramps, R, inflow = _macro_ramp_args(desc, T, ramps, inflow)
+        if t_inflow is not None:
+            if not isinstance(t_inflow, torch.Tensor) or tuple(t_inflow.shape) != (K, T, L, R):
+                raise ValueError("t_inflow must have shape (%d, %d, %d, %d): the directions of t_r, then the shape of inflow" % (K, T, L, R))
+            t_inflow = _f32c(t_inflow, "t_inflow")
+        tail = (_ptr(det), D, _with_det(taps, det), _with_det(t_taps, det), _ptr(err), _ptr(err_jvp), _stream(), _ptr(ramps), R,
+                _data(inflow), _data(t_inflow))
+        if ring:
+            check(_lib.lib().dhts_macro_rollout_fwd_jvp_ring_ramp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(t_r),
+                                                                  _ptr(t_y), *(_ptr(o) for o in out), *tail),
+                  "dhts_macro_rollout_fwd_jvp_ring_ramp")
+        else:
+            check(_lib.lib().dhts_macro_rollout_fwd_jvp_ramp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
+                                                             _ptr(t_r), _ptr(t_y), _ptr(t_ghost), *(_ptr(o) for o in out), *tail),
+                  "dhts_macro_rollout_fwd_jvp_ramp")
+        return (out[0], out[1], out[2], out[3], taps), (out[4], out[5], t_taps)
     if ring:
         check(_lib.lib().dhts_macro_rollout_fwd_jvp_ring(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(t_r), _ptr(t_y),
                                                          *(_ptr(o) for o in out), _ptr(det), D, _with_det(taps, det), _with_det(t_taps, det),
@@ -1334,10 +1357,11 @@ def macro_rollout_bwd_ckpt_ramp(desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, ra
                            g_taps, target, g_sse, final, g_ghost, ramps, inflow, g_inflow)
 
 
-def macro_rollout_fwd_jvp_ring(desc, T, r, y, u, ueq, t_r, t_y, det=None, err=None, err_jvp=None, out=None, taps=None, t_taps=None):
-    """macro_rollout_fwd_jvp of a ring (dhts_macro_rollout_fwd_jvp_ring): no ghost and no t_ghost; the tangents of the two end cells are
-    each other's boundary tangents.  Returns ((rT, yT, uT, qT, taps), (t_rT, t_yT, t_taps))."""
-    return macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, None, t_r, t_y, None, det, err, err_jvp, out, taps, t_taps)
+def macro_rollout_fwd_jvp_ring(desc, T, r, y, u, ueq, t_r, t_y, det=None, err=None, err_jvp=None, out=None, taps=None, t_taps=None,
+                               ramps=None, inflow=None, t_inflow=None):
+    """macro_rollout_fwd_jvp of a ring (dhts_macro_rollout_fwd_jvp_ring; with ramps: dhts_macro_rollout_fwd_jvp_ring_ramp): no ghost and no
+    t_ghost; the tangents of the two end cells are each other's boundary tangents.  Returns ((rT, yT, uT, qT, taps), (t_rT, t_yT, t_taps))."""
+    return macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, None, t_r, t_y, None, det, err, err_jvp, out, taps, t_taps, ramps, inflow, t_inflow)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -524,6 +524,39 @@ int dhts_macro_rollout_bwd_ckpt_target_ramp(const dhts_macro_desc *d, int T, int
                                             const float *r_fin, const float *y_fin, const float *u_fin, float *g_r_out, float *g_y_out,
                                             double *g_ghost, const int32_t *ramps, int n_ramp, const float *inflow, float *g_inflow, int ring,
                                             dhts_error *err, void *stream);
+/* ---- on-ramp inflow and its tangent on the fused forward + tangent kernel ----
+ * The source above in forward mode, without a tape: the T calls of dMacroForwardLayer.forward (road/lane/_macro_lane.py:83-146, the
+ * blocks of road/lane/dmacro_lane.py:96-132 applied untransposed, :126-129) with the source of the _ckpt_ramp entry points behind every
+ * step and its tangent behind the step's tangent.  ramps [n_ramp], inflow [T][n_lanes][n_ramp] as there; t_inflow
+ * [n_dir][T][n_lanes][n_ramp] float32 the tangent of inflow per direction, or NULL: zero (nothing is read).  Behind the Godunov
+ * update of step t the owner of cell ramps[j] forms r' = (float)((double)r + dt * (double)inflow[t][l][j]), y' = y, as the
+ * checkpointed forward does -- the primal outputs and readings are dhts_macro_rollout_fwd_ckpt_ramp's bits -- and behind the cell's
+ * tangent step, for every direction d,
+ *     t_r' = (float)((double)t_r + dt * (double)t_inflow[d][t][l][j]),   t_y' = t_y.
+ * Everything that reads the state or the tangents after step t -- the next step, a ring's copies of its end cells, the finiteness
+ * test of err_jvp, the readings and their tangents, the outputs -- sees the primed values.
+ *   dhts_macro_rollout_fwd_jvp_ramp        as dhts_macro_rollout_fwd_jvp (constant or scheduled boundary cells, ghost_is_sched)
+ *   dhts_macro_rollout_fwd_jvp_ring_ramp   as dhts_macro_rollout_fwd_jvp_ring
+ * with the siblings' arguments in the siblings' order, then ramps, n_ramp, inflow, t_inflow; the siblings' arithmetic, fault
+ * records, DHTS_E_INVALID rules and plan (dhts_macro_fwd_jvp_plan and the cell limits 997 / 1239 / 1410 hold as they stand: no LDS,
+ * no barrier and no atomic is added).  Every launch of a call recomputes the primal with the source; launches after the first read the
+ * same inflow and their own directions of t_inflow.  n_ramp = 0: the sibling's call, the three arrays are not read.
+ * DHTS_E_INVALID besides, nothing dereferenced and nothing launched: n_ramp < 0; n_ramp > 0 with T > 0 and a NULL ramps or inflow.
+ * T = 0: state and tangents come back as they went in, no row is addressed.  An index of ramps outside [0, n_cells) names no cell:
+ * nothing is added for it and no address is formed from it.  PRECONDITION as above: the entries inside [0, n_cells) are distinct. */
+int dhts_macro_rollout_fwd_jvp_ramp(const dhts_macro_desc *d, int T, int n_dir,
+                                    const float *r, const float *y, const float *u, const float *ueq, const float *ghost, int ghost_is_sched,
+                                    const float *t_r, const float *t_y, const float *t_ghost,
+                                    float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                                    const int32_t *det, int n_det, float *taps, float *t_taps,
+                                    dhts_error *err, dhts_error *err_jvp, void *stream,
+                                    const int32_t *ramps, int n_ramp, const float *inflow, const float *t_inflow);
+int dhts_macro_rollout_fwd_jvp_ring_ramp(const dhts_macro_desc *d, int T, int n_dir,
+                                         const float *r, const float *y, const float *u, const float *ueq, const float *t_r, const float *t_y,
+                                         float *r_out, float *y_out, float *u_out, float *ueq_out, float *t_r_out, float *t_y_out,
+                                         const int32_t *det, int n_det, float *taps, float *t_taps,
+                                         dhts_error *err, dhts_error *err_jvp, void *stream,
+                                         const int32_t *ramps, int n_ramp, const float *inflow, const float *t_inflow);
 /* tangent of y = r (u - u_eq(r)): t_y = (dy/dr) t_r + (dy/du) t_u, the partials dhts_macro_state_from_ru_bwd applies, in float32 */
 int dhts_macro_state_from_ru_jvp(int64_t n, double u_max, const float *r, const float *u, const float *t_r, const float *t_u,
                                  float *t_y, void *stream);
