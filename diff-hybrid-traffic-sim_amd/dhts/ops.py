@@ -8,6 +8,7 @@ Mirrors the reference operators
     dMicroForwardLayer  road/lane/dmicro_lane.py:228-298
 batched over lanes and fused over time steps.
 """
+import collections
 import ctypes as C
 import operator
 import warnings
@@ -343,15 +344,16 @@ class MacroRollout(torch.autograd.Function):
 
     (r0, u0 [L][N], ghost_r, ghost_u [L][2]) -> (rT, yT, uT, qT [L][N]) (+ hist [T][L][3][N] when asked).
     ghost_r, ghost_u [T][L][2] instead: a boundary schedule, row t set in front of step t; their gradients come back per step.
-    det (int32 CUDA [D], the last argument): detector readings [T][L][3][D] as the fifth output instead of a history,
-    readings[t][l][:][j] = (r, y, u) of cell det[j] after step t; nothing of size [T][L][N] is written, saved or read back then.
+    det (int32 CUDA [D]): detector readings [T][L][3][D] as the fifth output instead of a history, readings[t][l][:][j] = (r, y, u) of
+    cell det[j] after step t; nothing of size [T][L][N] is written, saved or read back then.
     What example/inverse/macro.py does with one dMacroLane in a RoadNetwork (macro.py:34-68,
     _inverse.py:91-99), for L lanes at once: state set by set_state_vector_u, ghosts by
     set_leftmost_cell / set_rightmost_cell, T x RoadNetwork.forward, state read by get_state_vector (at chosen cells: the readings).
-    checkpoint (the last argument; None / False: the taped path; True: the plan's segment length; a positive int: that one): keep (r, y)
-    every so many steps instead of the tape, and let the reverse sweep replay one segment at a time with its interface products in LDS
-    (macro_ckpt_plan) -- the same outputs and gradients bit for bit, and the only buffer that grows with T besides the readings is 8 B
-    per cell per segment.  Not with want_hist, and not for lanes the reverse kernel's LDS cannot hold (ValueError).
+    checkpoint (None / False: the taped path; True: the plan's segment length; a positive int: that one): keep (r, y) every so many steps
+    instead of the tape, and let the reverse sweep replay one segment at a time with its interface products in LDS (macro_ckpt_plan) --
+    the same outputs and gradients bit for bit, and the only buffer that grows with T besides the readings is 8 B per cell per segment.
+    Not with want_hist, and not for lanes the reverse kernel's LDS cannot hold (ValueError).  A checkpointed call that requires grad is
+    the "MacroRollout" row of _MACRO_CKPT_FORMS: the pair every checkpointed form shares runs it; the taped path is all here.
     """
 
     @staticmethod
@@ -360,25 +362,20 @@ class MacroRollout(torch.autograd.Function):
         sched = _macro_boundary_form(L, ghost_r, ghost_u, T)
         desc = macro_desc(L, N, dt, dx, u_max)
         segment = _macro_checkpoint_segment(checkpoint, desc, T, want_hist, 0 if det is None else int(det.numel()))
-        r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
         need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
-        ctx.segment = segment if need_grad else None
+        if segment is not None and need_grad:
+            return _macro_ckpt_forward(ctx, "MacroRollout", r0, u0, ghost_r, ghost_u, None, T, dt, dx, u_max, check_faults, det, checkpoint,
+                                       None, None, segment=segment)
+        r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
+        ctx.segment = None
         err = new_error_record(r0.device)
-        tape = None
-        if ctx.segment is not None:
-            # the checkpointed pair: the checkpoint buffer, the readings if asked for and the fault record; no tape.  The replay reads the
-            # forward's inputs again: (y0, q0, ghost) stay alive beside what the taped path saves
-            ctx.ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=r0.device)
-            ctx.replay = (y0, q0, ghost)
-            (rT, yT, uT, qT), steps = macro_rollout_fwd_ckpt(desc, T, r0c, y0, u0c, q0, ghost, ctx.ckpt, segment=segment, det=det, err=err)
+        tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
+        if det is not None:
+            (rT, yT, uT, qT), steps = macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
         else:
-            tape = torch.empty(macro_tape_numel(desc, T), dtype=torch.float32, device=r0.device) if need_grad else None
-            if det is not None:
-                (rT, yT, uT, qT), steps = macro_rollout_fwd_taps(desc, T, r0c, y0, u0c, q0, ghost, det, tape=tape, err=err)
-            else:
-                steps = torch.empty(T, L, 3, N, dtype=torch.float32, device=r0.device) if want_hist else None
-                fwd = macro_rollout_fwd_sched if sched else macro_rollout_fwd
-                rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=steps, err=err)
+            steps = torch.empty(T, L, 3, N, dtype=torch.float32, device=r0.device) if want_hist else None
+            fwd = macro_rollout_fwd_sched if sched else macro_rollout_fwd
+            rT, yT, uT, qT = fwd(desc, T, r0c, y0, u0c, q0, ghost, tape=tape, hist=steps, err=err)
         if check_faults:
             raise_on_fault(err)
         ctx.sched = sched
@@ -389,28 +386,109 @@ class MacroRollout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_steps=None):
+        if ctx.segment is not None:
+            return _macro_ckpt_backward(ctx, g_rT, g_yT, g_uT, g_steps)
         r0, u0, gr, gu, gq, rT, yT, steps, det = ctx.saved_tensors
         desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        L = desc.n_lanes
         g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
         gs = None
-        ckpt = ctx.segment is not None       # (its glue goes over the T-sized cotangents a part at a time: _glue_rows)
         if steps is not None and g_steps is not None and g_steps.numel():      # (T = 0: no row, and an empty tensor has no address)
-            # [T][L][2][N], with detectors [T][L][2][D]
-            gs = _per_step_cotangent(steps, g_steps, um, rows=_glue_rows(T, L * steps.shape[3]) if ckpt else None)
+            gs = _per_step_cotangent(steps, g_steps, um)                         # [T][L][2][N], with detectors [T][L][2][D]
         err = new_error_record(r0.device)
-        if ckpt:
-            y0, q0, ghost = ctx.replay
-            taps = gs is not None and det is not None            # (no readings to look at: the plain sweep)
-            g_r0, g_y0, g_ghost = macro_rollout_bwd_ckpt(desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, segment=ctx.segment,
-                                                         det=det if taps else None, g_taps=gs if taps else None, err=err)
-            del gs                           # (the sweep is enqueued on this stream: the allocator may hand the block to the glue below)
-        elif gs is not None and det is not None:
+        if gs is not None and det is not None:
             g_r0, g_y0, g_ghost = macro_rollout_bwd_taps(desc, T, ctx.tape, g_r, g_y, det, gs, sched=ctx.sched, err=err)
         else:                            # (no readings to look at: the plain sweep over the same tape)
             bwd = macro_rollout_bwd_sched if ctx.sched else macro_rollout_bwd
             g_r0, g_y0, g_ghost = bwd(desc, T, ctx.tape, g_r, g_y, g_hist=gs, err=err)      # [L][2][2], or [T][L][2][2] per step
-        return _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * L) if ckpt else None) + (None,) * 8
+        return _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, None) + (None,) * 8
+
+
+# ---- the checkpointed forms: one row per autograd Function, one forward / backward pair for all of them -------------------
+# What the Functions differ in is this table and nothing else.  boundary: "open" (ghost_r, ghost_u [L][2] or a schedule [T][L][2]),
+# "ring" (no boundary arguments) or "either" (the call's: ghost_r None is a ring).  raw: the raw layer's form and with it the plan that
+# gives the segment -- "plain" (detectors or nothing; macro_ckpt_plan), "target" (the dense fit; macro_ckpt_target_plan) or None (the
+# call's: a target is the fit).  sweep_buffers: the reverse sweep's outputs (g_r0, g_y0, g_ghost) are made in forward.  idle_ckpt: the
+# checkpoint buffer is allocated even when no leaf requires grad.  release: backward drops the checkpoint buffer and the replay inputs
+# (a second backward over a retained graph then fails).  keep_uT: uT is saved for backward also without a fit, which alone reads it.
+# nones: the backward's trailing Nones, one per argument of forward behind the leaves.
+_MacroForm = collections.namedtuple("_MacroForm", "boundary raw ramps sweep_buffers idle_ckpt release keep_uT nones")
+_MACRO_CKPT_FORMS = {
+    "MacroRollout":           _MacroForm("open",   "plain",  False, False, False, False, False, 8),
+    "MacroRolloutTarget":     _MacroForm("open",   "target", False, True,  False, True,  False, 7),
+    "MacroRolloutRing":       _MacroForm("ring",   "plain",  False, False, True,  True,  False, 7),
+    "MacroRolloutRingTarget": _MacroForm("ring",   "target", False, False, False, True,  False, 7),
+    "MacroRolloutRamp":       _MacroForm("either", None,     True,  False, True,  True,  True,  9),
+}
+
+
+def _macro_ckpt_forward(ctx, name, r0, u0, ghost_r, ghost_u, inflow, T, dt, dx, u_max, check_faults, det, checkpoint, target, ramps,
+                        segment=None):
+    """The forward of every checkpointed form (name: its row of _MACRO_CKPT_FORMS): the leaves as the kernels read them, the checkpoint
+    buffer, the one raw call, the fault check and what backward needs -> (rT, yT, uT, qT[, readings [T][L][3][D] | sse [L][2]]).
+    segment: resolved already (MacroRollout, which needs it to choose its path)."""
+    form = _MACRO_CKPT_FORMS[name]
+    L, N = r0.shape
+    ring, raw = ghost_r is None, form.raw or ("plain" if target is None else "target")
+    sched = False if ring else _macro_boundary_form(L, ghost_r, ghost_u, T)
+    desc = macro_desc(L, N, dt, dx, u_max)
+    if segment is None:
+        segment = _macro_segment(checkpoint, desc, T, raw, 0 if det is None else int(det.numel()))
+    dev = r0.device
+    gr = gu = gq = ghost = inf = None
+    if ring:
+        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
+        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
+    else:
+        r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
+    if form.ramps:
+        inf = _f32c(inflow.detach(), "inflow")
+    need_grad = any(t is not None and t.requires_grad for t in (r0, u0, ghost_r, ghost_u, inflow))
+    ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad or form.idle_ckpt else None
+    err = new_error_record(dev)
+    (rT, yT, uT, qT), extra = _macro_ckpt_fwd(raw, desc, T, r0c, y0, u0c, q0, ghost, ckpt, segment, err, None, det, None, target, None,
+                                              ramps, inf)
+    fit = raw == "target"
+    if check_faults:
+        raise_on_fault(err)
+    if need_grad:
+        # the replay reads the forward's inputs again: (y0, q0, ghost) stay alive beside the checkpoints; no tape exists
+        ctx.form, ctx.raw, ctx.ckpt, ctx.replay, ctx.target = form, raw, ckpt, (y0, q0, ghost), target
+        ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
+        ctx.out_bwd = ctx.g_ghost = None
+        if form.sweep_buffers:
+            ctx.out_bwd = (torch.empty(L, N, dtype=torch.float32, device=dev), torch.empty(L, N, dtype=torch.float32, device=dev))
+            if not ring:
+                ctx.g_ghost = torch.empty((max(int(T), 1), L, 2, 2) if sched else (L, 2, 2), dtype=torch.float64, device=dev)
+        ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, uT if fit or form.keep_uT else None, None if fit else extra, det, ramps, inf)
+    ctx.mark_non_differentiable(qT)
+    return (rT, yT, uT, qT) if extra is None else (rT, yT, uT, qT, extra)
+
+
+def _macro_ckpt_backward(ctx, g_rT, g_yT, g_uT, g_extra):
+    """The backward of every checkpointed form: the seeds, the cotangent of the readings (its glue goes over the T-sized arrays a part at
+    a time: _glue_rows) or of sse, the one raw call, the glue back to the leaves -> a gradient per argument of the form's forward."""
+    form = ctx.form
+    r0, u0, gr, gu, gq, rT, yT, uT, steps, det, ramps, inf = ctx.saved_tensors
+    desc, T, um = ctx.desc, ctx.T, ctx.u_max
+    L, fit = desc.n_lanes, ctx.raw == "target"
+    g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
+    gs = g_sse = None
+    if fit:
+        g_sse = g_extra.contiguous() if g_extra is not None else None
+    elif steps is not None and g_extra is not None and g_extra.numel():      # (T = 0: no row, and an empty tensor has no address)
+        gs = _per_step_cotangent(steps, g_extra, um, rows=_glue_rows(T, L * steps.shape[3]))
+    err = new_error_record(r0.device)
+    y0, q0, ghost = ctx.replay
+    g_r0, g_y0, g_ghost, *g_inflow = _macro_ckpt_bwd(
+        ctx.raw, desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, ctx.segment, err, ctx.out_bwd,
+        det if gs is not None else None, gs, ctx.target, g_sse, (rT, yT, uT) if fit else None, ctx.g_ghost, ramps, inf)
+    del gs, y0, q0, ghost                # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
+    if form.release:
+        ctx.replay = ctx.ckpt = None
+    grads = _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * L))
+    if form.boundary == "either" and g_ghost is None:        # (a ring through a forward that has boundary arguments)
+        grads += (None, None)
+    return grads + tuple(g_inflow) + (None,) * form.nones
 
 
 class MacroRolloutTarget(torch.autograd.Function):
@@ -422,41 +500,12 @@ class MacroRolloutTarget(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, check_faults, checkpoint, target):
-        L, N = r0.shape
-        sched = _macro_boundary_form(L, ghost_r, ghost_u, T)
-        desc = macro_desc(L, N, dt, dx, u_max)
-        segment = _macro_target_segment(checkpoint, desc, T)
-        dev = r0.device
-        r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
-        need_grad = any(t.requires_grad for t in (r0, u0, ghost_r, ghost_u))
-        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
-        err = new_error_record(dev)
-        (rT, yT, uT, qT), sse = macro_rollout_fwd_ckpt_target(desc, T, r0c, y0, u0c, q0, ghost, ckpt, target, segment=segment, err=err)
-        if check_faults:
-            raise_on_fault(err)
-        if need_grad:
-            # ... and here also the reverse sweep's outputs
-            ctx.out_bwd = (torch.empty(L, N, dtype=torch.float32, device=dev), torch.empty(L, N, dtype=torch.float32, device=dev))
-            ctx.g_ghost = torch.empty((max(int(T), 1), L, 2, 2) if sched else (L, 2, 2), dtype=torch.float64, device=dev)
-            ctx.ckpt, ctx.replay, ctx.target = ckpt, (y0, q0, ghost), target
-            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
-            ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, uT)
-        ctx.mark_non_differentiable(qT)
-        return rT, yT, uT, qT, sse
+        return _macro_ckpt_forward(ctx, "MacroRolloutTarget", r0, u0, ghost_r, ghost_u, None, T, dt, dx, u_max, check_faults, None,
+                                   checkpoint, target, None)
 
     @staticmethod
     def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_sse):
-        r0, u0, gr, gu, gq, rT, yT, uT = ctx.saved_tensors
-        desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
-        err = new_error_record(r0.device)
-        y0, q0, ghost = ctx.replay
-        g_r0, g_y0, g_ghost = macro_rollout_bwd_ckpt_target(desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, ctx.target,
-                                                            g_sse=g_sse.contiguous() if g_sse is not None else None, final=(rT, yT, uT),
-                                                            segment=ctx.segment, err=err, out=ctx.out_bwd, g_ghost=ctx.g_ghost)
-        del y0, q0, ghost                # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
-        ctx.replay = ctx.ckpt = None
-        return _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * desc.n_lanes)) + (None,) * 7
+        return _macro_ckpt_backward(ctx, g_rT, g_yT, g_uT, g_sse)
 
 
 class MacroRolloutRing(torch.autograd.Function):
@@ -467,39 +516,12 @@ class MacroRolloutRing(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, r0, u0, T, dt, dx, u_max, check_faults, det, checkpoint):
-        L, N = r0.shape
-        desc = macro_desc(L, N, dt, dx, u_max)
-        segment = _macro_checkpoint_segment(checkpoint, desc, T, False, 0 if det is None else int(det.numel()))
-        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
-        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
-        need_grad = r0.requires_grad or u0.requires_grad
-        err = new_error_record(r0.device)
-        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=r0.device)
-        (rT, yT, uT, qT), steps = macro_rollout_fwd_ckpt_ring(desc, T, r0c, y0, u0c, q0, ckpt, segment=segment, det=det, err=err)
-        if check_faults:
-            raise_on_fault(err)
-        if need_grad:
-            ctx.ckpt, ctx.replay = ckpt, (y0, q0)
-            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
-            ctx.save_for_backward(r0c, u0c, rT, yT, steps, det)
-        ctx.mark_non_differentiable(qT)
-        return (rT, yT, uT, qT) if steps is None else (rT, yT, uT, qT, steps)
+        return _macro_ckpt_forward(ctx, "MacroRolloutRing", r0, u0, None, None, None, T, dt, dx, u_max, check_faults, det, checkpoint,
+                                   None, None)
 
     @staticmethod
     def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_steps=None):
-        r0, u0, rT, yT, steps, det = ctx.saved_tensors
-        desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
-        gs = None
-        if steps is not None and g_steps is not None and g_steps.numel():      # (T = 0: no row, and an empty tensor has no address)
-            gs = _per_step_cotangent(steps, g_steps, um, rows=_glue_rows(T, desc.n_lanes * steps.shape[3]))
-        err = new_error_record(r0.device)
-        y0, q0 = ctx.replay
-        g_r0, g_y0 = macro_rollout_bwd_ckpt_ring(desc, T, ctx.ckpt, r0, y0, u0, q0, g_r, g_y, segment=ctx.segment,
-                                                 det=det if gs is not None else None, g_taps=gs, err=err)
-        del gs, y0, q0                   # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
-        ctx.replay = ctx.ckpt = None
-        return _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0) + (None,) * 7
+        return _macro_ckpt_backward(ctx, g_rT, g_yT, g_uT, g_steps)
 
 
 class MacroRolloutRingTarget(torch.autograd.Function):
@@ -508,37 +530,12 @@ class MacroRolloutRingTarget(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, r0, u0, T, dt, dx, u_max, check_faults, checkpoint, target):
-        L, N = r0.shape
-        desc = macro_desc(L, N, dt, dx, u_max)
-        segment = _macro_target_segment(checkpoint, desc, T)
-        r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
-        y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
-        need_grad = r0.requires_grad or u0.requires_grad
-        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=r0.device) if need_grad else None
-        err = new_error_record(r0.device)
-        (rT, yT, uT, qT), sse = macro_rollout_fwd_ckpt_target_ring(desc, T, r0c, y0, u0c, q0, ckpt, target, segment=segment, err=err)
-        if check_faults:
-            raise_on_fault(err)
-        if need_grad:
-            ctx.ckpt, ctx.replay, ctx.target = ckpt, (y0, q0), target
-            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
-            ctx.save_for_backward(r0c, u0c, rT, yT, uT)
-        ctx.mark_non_differentiable(qT)
-        return rT, yT, uT, qT, sse
+        return _macro_ckpt_forward(ctx, "MacroRolloutRingTarget", r0, u0, None, None, None, T, dt, dx, u_max, check_faults, None, checkpoint,
+                                   target, None)
 
     @staticmethod
     def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_sse):
-        r0, u0, rT, yT, uT = ctx.saved_tensors
-        desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
-        err = new_error_record(r0.device)
-        y0, q0 = ctx.replay
-        g_r0, g_y0 = macro_rollout_bwd_ckpt_target_ring(desc, T, ctx.ckpt, r0, y0, u0, q0, g_r, g_y, ctx.target,
-                                                        g_sse=g_sse.contiguous() if g_sse is not None else None, final=(rT, yT, uT),
-                                                        segment=ctx.segment, err=err)
-        del y0, q0
-        ctx.replay = ctx.ckpt = None
-        return _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0) + (None,) * 7
+        return _macro_ckpt_backward(ctx, g_rT, g_yT, g_uT, g_sse)
 
 
 class MacroRolloutRamp(torch.autograd.Function):
@@ -548,59 +545,12 @@ class MacroRolloutRamp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, r0, u0, ghost_r, ghost_u, inflow, T, dt, dx, u_max, check_faults, det, checkpoint, target, ramps):
-        L, N = r0.shape
-        ring, fit = ghost_r is None, target is not None
-        desc = macro_desc(L, N, dt, dx, u_max)
-        if fit:
-            segment = _macro_target_segment(checkpoint, desc, T)
-        else:
-            segment = _macro_checkpoint_segment(checkpoint, desc, T, False, 0 if det is None else int(det.numel()))
-        gr = gu = gq = ghost = None
-        if ring:
-            r0c, u0c = _f32c(r0.detach(), "r0"), _f32c(u0.detach(), "u0")
-            y0, q0 = macro_state_from_ru(r0c, u0c, u_max)
-        else:
-            _macro_boundary_form(L, ghost_r, ghost_u, T)
-            r0c, u0c, gr, gu, gq, y0, q0, ghost = _macro_leaves(r0, u0, ghost_r, ghost_u, u_max)
-        inf = _f32c(inflow.detach(), "inflow")
-        need_grad = any(t is not None and t.requires_grad for t in (r0, u0, ghost_r, ghost_u, inflow))
-        dev = r0.device
-        ckpt = torch.empty(macro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev)
-        err = new_error_record(dev)
-        (rT, yT, uT, qT), extra = macro_rollout_fwd_ckpt_ramp(desc, T, r0c, y0, u0c, q0, ghost, ckpt, ramps, inf, segment=segment, det=det,
-                                                              target=target, err=err)
-        if check_faults:
-            raise_on_fault(err)
-        if need_grad:
-            ctx.ckpt, ctx.replay, ctx.target, ctx.ring = ckpt, (y0, q0, ghost), target, ring
-            ctx.desc, ctx.T, ctx.u_max, ctx.segment, ctx.check_faults = desc, T, u_max, segment, check_faults
-            ctx.save_for_backward(r0c, u0c, gr, gu, gq, rT, yT, uT, None if fit else extra, det, ramps, inf)
-        ctx.mark_non_differentiable(qT)
-        return (rT, yT, uT, qT) if extra is None else (rT, yT, uT, qT, extra)
+        return _macro_ckpt_forward(ctx, "MacroRolloutRamp", r0, u0, ghost_r, ghost_u, inflow, T, dt, dx, u_max, check_faults, det, checkpoint,
+                                   target, ramps)
 
     @staticmethod
     def backward(ctx, g_rT, g_yT, g_uT, _g_qT, g_extra=None):
-        r0, u0, gr, gu, gq, rT, yT, uT, steps, det, ramps, inf = ctx.saved_tensors
-        desc, T, um = ctx.desc, ctx.T, ctx.u_max
-        fit = ctx.target is not None
-        g_r, g_y = _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um)
-        gs = g_sse = None
-        if fit:
-            g_sse = g_extra.contiguous() if g_extra is not None else None
-        elif steps is not None and g_extra is not None and g_extra.numel():      # (T = 0: no row, and an empty tensor has no address)
-            gs = _per_step_cotangent(steps, g_extra, um, rows=_glue_rows(T, desc.n_lanes * steps.shape[3]))
-        err = new_error_record(r0.device)
-        y0, q0, ghost = ctx.replay
-        g_r0, g_y0, g_ghost, g_inflow = macro_rollout_bwd_ckpt_ramp(
-            desc, T, ctx.ckpt, r0, y0, u0, q0, ghost, g_r, g_y, ramps, inf, segment=ctx.segment, det=det if gs is not None else None,
-            g_taps=gs, target=ctx.target, g_sse=g_sse, final=(rT, yT, uT) if fit else None, err=err)
-        del gs, y0, q0, ghost            # (the sweep is enqueued on this stream: the allocator may hand the blocks to the glue below)
-        ctx.replay = ctx.ckpt = None
-        if ctx.ring:
-            grads = _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0) + (None, None)
-        else:
-            grads = _macro_bwd_done(ctx, err, (r0, u0, gr, gu, gq), g_r0, g_y0, g_ghost, _glue_rows(T, 2 * desc.n_lanes))
-        return grads + (g_inflow,) + (None,) * 9
+        return _macro_ckpt_backward(ctx, g_rT, g_yT, g_uT, g_extra)
 
 
 def _macro_ramp_checks(r0, T, ramps, inflow, want_hist, checkpoint):
@@ -631,13 +581,6 @@ def _macro_ramp_checks(r0, T, ramps, inflow, want_hist, checkpoint):
     return cells
 
 
-def _macro_ring_bwd_done(ctx, err, r0, u0, g_r0, g_y0):
-    """_macro_bwd_done without boundary cells -> (g_r0, g_u0)."""
-    if ctx.check_faults:
-        raise_on_fault(err)
-    return g_r0, macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, ctx.u_max)
-
-
 def _macro_ring_checks(ring, ghost_r, ghost_u, t_ghost_r=None, t_ghost_u=None, want_hist=False, checkpoint=None, fused=None, r0=None,
                        u0=None):
     """Every ValueError of `ring=True` of dhts.macro_rollout (fused None) and dhts.macro_rollout_jvp (checkpoint None), raised before
@@ -661,7 +604,7 @@ def _macro_ring_checks(ring, ghost_r, ghost_u, t_ghost_r=None, t_ghost_u=None, w
         raise ValueError("r0 must be [L][N] and u0 must have its shape (got %s and %s)" % (tuple(r0.shape), tuple(u0.shape)))
 
 
-# ---- what the two macro autograd Functions (and dhts.jvp.macro_rollout_jvp) share: the leaves, the backward's seeds and tail, the segment ----
+# ---- what the macro autograd Functions (and dhts.jvp.macro_rollout_jvp) share: the leaves, the backward's seeds and tail, the segment ----
 def _macro_boundary_form(L, ghost_r, ghost_u, T):
     """-> whether (ghost_r, ghost_u) are a schedule [T][L][2] (else [L][2]); ValueError for anything else."""
     sched = ghost_r.dim() == 3
@@ -693,11 +636,14 @@ def _macro_bwd_seeds(rT, yT, g_rT, g_yT, g_uT, um):
 
 
 def _macro_bwd_done(ctx, err, leaves, g_r0, g_y0, g_ghost, rows):
-    """The fault check and the glue back to the leaves -> (g_r0, g_u0, g_ghost_r, g_ghost_u); rows: _ghost_ry_to_ru's."""
+    """The fault check and the glue back to the leaves -> (g_r0, g_u0, g_ghost_r, g_ghost_u), or with g_ghost None (a ring: no boundary
+    cells) (g_r0, g_u0); rows: _ghost_ry_to_ru's."""
     r0, u0, gr, gu, gq = leaves
     if ctx.check_faults:             # reading the record back synchronises: off inside HIP-graph capture
         raise_on_fault(err)
     g_u0 = macro_state_from_ru_bwd(r0, u0, g_y0, g_r0, ctx.u_max)
+    if g_ghost is None:
+        return g_r0, g_u0
     return (g_r0, g_u0) + _ghost_ry_to_ru(g_ghost, gr, gu, gq, ctx.u_max, rows=rows)
 
 
@@ -713,11 +659,6 @@ def _macro_segment(checkpoint, desc, T, form, n_det=0):
         raise ValueError("lanes of %d cells do not fit the checkpointed reverse sweep (its LDS holds up to %d cells): "
                          "use the taped path, checkpoint=None" % (desc.n_cells, MACRO_CKPT_MAX_CELLS))
     return _checkpoint_segment(checkpoint, plan)
-
-
-def _macro_target_segment(checkpoint, desc, T):
-    """dhts.macro_rollout's `checkpoint` beside `target` -> the segment length of the target forms' own plan; ValueError otherwise."""
-    return _macro_segment(checkpoint, desc, T, "target")
 
 
 def _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint):
@@ -739,7 +680,7 @@ def _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, che
         raise ValueError("target must be contiguous: a copy of it is as large as the history it replaces")
     if target.requires_grad:
         raise ValueError("target is data and not differentiable: pass it detached")
-    _macro_target_segment(checkpoint, macro_desc(L, N, float(dt), float(dx), float(u_max)), int(T))
+    _macro_segment(checkpoint, macro_desc(L, N, float(dt), float(dx), float(u_max)), int(T), "target")
 
 
 def _macro_checkpoint_segment(checkpoint, desc, T, want_hist, n_det):
@@ -811,48 +752,40 @@ def macro_rollout(r0, u0, ghost_r, ghost_u, T, dt, dx, u_max, want_hist=False, c
     (normalised density per second) cell ramps[j] of lane l gets in step t, added behind the step's own float32 store as
     (float)((double)r + dt (double)inflow) with y unchanged; a negative entry is an off-ramp, nothing is clamped.  The
     return tuple is the form's own; inflow is a differentiable leaf and inflow.grad is float32 [T][L][R] (MacroRolloutRamp)."""
+    # every form's checks, each ValueError where it has always stood and all of them before anything touches a device ...
     _macro_ring_checks(ring, ghost_r, ghost_u, want_hist=want_hist, checkpoint=checkpoint, r0=r0, u0=u0)
     cells = _macro_ramp_checks(r0, T, ramps, inflow, want_hist, checkpoint)
-    if cells is not None:
-        det = None
+    desc = det = None
+    if cells is not None:                # (the on-ramp forms look at the lane's size first)
         desc = macro_desc(int(r0.shape[0]), int(r0.shape[1]), float(dt), float(dx), float(u_max))
-        if target is not None:
-            _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
-        else:
-            det = None if detectors is None else _detector_cells(detectors, int(r0.shape[-1]))
-            _macro_checkpoint_segment(checkpoint, desc, int(T), False, 0 if det is None else len(det))
-        if not ring:
-            _macro_boundary_form(int(r0.shape[0]), ghost_r, ghost_u, int(T))
-        if isinstance(det, list):
-            det = torch.tensor(det, dtype=torch.int32, device=r0.device)
-        if isinstance(cells, list):
-            cells = torch.tensor(cells, dtype=torch.int32, device=r0.device)
-        return MacroRolloutRamp.apply(r0, u0, ghost_r, ghost_u, inflow, int(T), float(dt), float(dx), float(u_max), check_faults, det,
-                                      checkpoint, target, cells)
-    if ring:
-        if target is not None:
-            _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
-            return MacroRolloutRingTarget.apply(r0, u0, int(T), float(dt), float(dx), float(u_max), check_faults, checkpoint, target)
-        det = None if detectors is None else _detector_cells(detectors, int(r0.shape[-1]))
-        _macro_checkpoint_segment(checkpoint, macro_desc(int(r0.shape[0]), int(r0.shape[1]), float(dt), float(dx), float(u_max)), int(T),
-                                  False, 0 if det is None else len(det))
-        if isinstance(det, list):
-            det = torch.tensor(det, dtype=torch.int32, device=r0.device)
-        return MacroRolloutRing.apply(r0, u0, int(T), float(dt), float(dx), float(u_max), check_faults, det, checkpoint)
-    if target is not None:
+    if target is not None:               # (... which end with the segment of the target forms' plan)
         _macro_target_checks(r0, T, dt, dx, u_max, target, want_hist, detectors, checkpoint)
-        return MacroRolloutTarget.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), check_faults, checkpoint, target)
-    det = None
-    if detectors is not None:
-        if want_hist:
-            raise ValueError("want_hist and detectors exclude each other: the history holds every cell")
-        det = _detector_cells(detectors, int(r0.shape[-1]))
-    if checkpoint is not None and checkpoint is not False and r0.dim() == 2:      # (ValueError before the detectors are uploaded)
-        _macro_checkpoint_segment(checkpoint, macro_desc(int(r0.shape[0]), int(r0.shape[1]), float(dt), float(dx), float(u_max)), int(T),
-                                  want_hist, 0 if det is None else len(det))
+    else:
+        if detectors is not None:
+            if want_hist:
+                raise ValueError("want_hist and detectors exclude each other: the history holds every cell")
+            det = _detector_cells(detectors, int(r0.shape[-1]))
+        if checkpoint is not None and checkpoint is not False and r0.dim() == 2:      # (ValueError before the detectors are uploaded)
+            if desc is None:
+                desc = macro_desc(int(r0.shape[0]), int(r0.shape[1]), float(dt), float(dx), float(u_max))
+            _macro_checkpoint_segment(checkpoint, desc, int(T), want_hist, 0 if det is None else len(det))
+    if cells is not None and not ring:
+        _macro_boundary_form(int(r0.shape[0]), ghost_r, ghost_u, int(T))
+    # ... the uploads, and the form's Function
     if isinstance(det, list):
         det = torch.tensor(det, dtype=torch.int32, device=r0.device)
-    return MacroRollout.apply(r0, u0, ghost_r, ghost_u, int(T), float(dt), float(dx), float(u_max), want_hist, check_faults, det, checkpoint)
+    if isinstance(cells, list):
+        cells = torch.tensor(cells, dtype=torch.int32, device=r0.device)
+    size = (int(T), float(dt), float(dx), float(u_max))
+    if cells is not None:
+        return MacroRolloutRamp.apply(r0, u0, ghost_r, ghost_u, inflow, *size, check_faults, det, checkpoint, target, cells)
+    if ring and target is not None:
+        return MacroRolloutRingTarget.apply(r0, u0, *size, check_faults, checkpoint, target)
+    if ring:
+        return MacroRolloutRing.apply(r0, u0, *size, check_faults, det, checkpoint)
+    if target is not None:
+        return MacroRolloutTarget.apply(r0, u0, ghost_r, ghost_u, *size, check_faults, checkpoint, target)
+    return MacroRollout.apply(r0, u0, ghost_r, ghost_u, *size, want_hist, check_faults, det, checkpoint)
 
 
 # ---- forward mode: Jacobian-vector products over the rollout tape ---------------------------------------------------------------------
@@ -2088,32 +2021,12 @@ def micro_step_bwd(desc, tape, g_p, g_v, count=None):
     return out[0], out[1], g_virtual
 
 
-# ---- what the micro autograd Functions share: the forward set-up of a checkpointed call, the fault check, the backward's seeds ----------
+# ---- what the micro autograd Functions share: the segment, the backward's seeds and its fault record ------------------------------------
 def _micro_segment(p0, params, T, dt, checkpoint, plan):
     """-> (desc, the segment `checkpoint` asks for or None): a ValueError before a device is touched."""
     L, V = p0.shape
     desc = micro_desc(L, V, dt)
     return desc, _checkpoint_segment(checkpoint, lambda sg: plan(desc, T, params.requires_grad, sg))
-
-
-def _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad):
-    """Everything every checkpointed pair needs is made here (no allocation inside backward but for a cotangent autograd does not hand
-    over): the checkpoint buffer -- none when nothing requires grad --, g_params and, with _micro_fwd_done behind the forward call, the
-    two fault records; neither tape exists.  -> (p0c, v0c, the forward's record)."""
-    p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
-    dev = p0c.device
-    ctx.desc, ctx.T, ctx.segment = desc, T, segment
-    ctx.params = params.detach().contiguous()
-    ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
-    ctx.g_params = torch.empty(6, desc.n_lanes, desc.capacity, dtype=torch.float64, device=dev) if params.requires_grad else None
-    return p0c, v0c, new_error_record(dev)
-
-
-def _micro_fwd_done(ctx, err, count, check_faults, need_grad):
-    if check_faults:                     # a collision is printed like the reference does, and tolerated
-        raise_on_fault(err)
-    ctx.count, ctx.check_faults = count, check_faults
-    ctx.err_bwd = new_error_record(err.device) if need_grad else None
 
 
 def _micro_bwd_seeds(ctx, g_pT, g_vT):
@@ -2133,6 +2046,86 @@ def _micro_bwd_done(ctx):
         MicroRollout.last_bwd_record = ctx.err_bwd           # (dhts.ops.micro_bwd_fault() reads it on demand)
 
 
+# ---- the checkpointed forms: one row per autograd Function, one forward / backward pair for all of them -------------------
+# boundary: what the head vehicle follows and which gradient the backward returns for it -- "head" (g_head), "lead" (g_lead), "head or
+# lead" (exactly one is a tensor; a slot for each) or "ring" (data: none).  raw: the raw layer's form; observe: what the third output
+# is -- "hist" (when asked), "samples" (unless observe is False) or "fit" (sse).  plan: which plan gives the segment.  sweep_buffers:
+# the reverse sweep's outputs that are made in forward (the checkpoint buffer, g_params and both fault records always are).  nones: the
+# backward's trailing Nones, one per argument of forward behind the leaves.  No form keeps a checkpoint without a leaf that requires
+# grad and none releases its context after backward, so neither is a column here.
+_MicroForm = collections.namedtuple("_MicroForm", "boundary raw observe plan sweep_buffers nones")
+_MICRO_CKPT_FORMS = {
+    "MicroRollout":           _MicroForm("head",         "hist",    "hist",    micro_ckpt_plan,        (),                          6),
+    "MicroRolloutSamples":    _MicroForm("head",         "samples", "samples", micro_ckpt_plan,        (),                          7),
+    "MicroRolloutLead":       _MicroForm("lead",         "lead",    "samples", micro_ckpt_plan,        ("g_lead",),                 9),
+    "MicroRolloutTarget":     _MicroForm("head or lead", "target",  "fit",     micro_ckpt_target_plan, ("g_lead", "g_head", "out"), 7),
+    "MicroRolloutRing":       _MicroForm("ring",         "ring",    "samples", micro_ckpt_plan,        (),                          9),
+    "MicroRolloutRingTarget": _MicroForm("ring",         "target",  "fit",     micro_ckpt_target_plan, ("out",),                    7),
+}
+
+
+def _micro_ckpt_forward(ctx, name, p0, v0, params, count, T, dt, check_faults, checkpoint, head=None, lead=None, lead_length=None, ring=None,
+                        want_hist=False, probes=None, every=1, observe=True, target=None, resolved=None):
+    """The forward of every checkpointed form (name: its row of _MICRO_CKPT_FORMS): the segment, the boundary as the kernels read it,
+    the one raw call and the fault check -> (pT, vT[, hist | samples | sse]).  Everything the pair needs is made here (no allocation
+    inside backward but for a cotangent autograd does not hand over, i.e. none inside a graph capture of it): the checkpoint buffer --
+    none when nothing requires grad --, g_params, the form's sweep_buffers and the two fault records; neither tape exists.
+    resolved: (desc, segment) where they exist already (MicroRollout, which needs them to choose its path)."""
+    form = _MICRO_CKPT_FORMS[name]
+    desc, segment = resolved or _micro_segment(p0, params, T, dt, checkpoint, form.plan)
+    leaf = head if lead is None else lead
+    need_grad = p0.requires_grad or v0.requires_grad or params.requires_grad or (leaf is not None and leaf.requires_grad)
+    p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
+    L, V, dev = desc.n_lanes, desc.capacity, p0c.device
+    ctx.form, ctx.want_hist, ctx.probes, ctx.every, ctx.observe = form, want_hist, probes, every, observe
+    ctx.desc, ctx.T, ctx.segment, ctx.count, ctx.check_faults = desc, T, segment, count, check_faults
+    ctx.params = params.detach().contiguous()
+    ctx.ckpt = torch.empty(micro_ckpt_numel(desc, T, segment), dtype=torch.float32, device=dev) if need_grad else None
+    ctx.g_params = torch.empty(6, L, V, dtype=torch.float64, device=dev) if params.requires_grad else None
+    err, ctx.err_bwd = new_error_record(dev), new_error_record(dev) if need_grad else None
+    ctx.head = None if head is None else head.detach().contiguous()
+    ctx.lead = None if lead is None else _f32c(lead.detach(), "lead")
+    ctx.lead_length = None if lead_length is None else lead_length.detach().to(device=dev, dtype=torch.float64).contiguous()
+    ctx.ring = None if ring is None else ring.detach().to(device=dev).contiguous()
+    ctx.target = None if target is None else _f32c(target, "target")
+    made = form.sweep_buffers if need_grad else ()
+    ctx.g_lead = torch.empty(T, L, 2, dtype=torch.float32, device=dev) if "g_lead" in made and lead is not None else None
+    ctx.g_head = torch.zeros(L, 2, dtype=torch.float64, device=dev) if "g_head" in made and lead is None else None
+    ctx.out_bwd = (torch.empty_like(p0c), torch.empty_like(v0c)) if "out" in made else None
+    hist = torch.empty(T, L, 2, V, dtype=torch.float32, device=dev) if want_hist else None
+    out, third = _micro_ckpt_fwd(form.raw, desc, T, p0c, v0c, ctx.params, ctx.ckpt, count, segment, err, None, head=ctx.head, hist=hist,
+                                 probes=probes, every=every, observe=observe, lead=ctx.lead, lead_length=ctx.lead_length, target=ctx.target,
+                                 ring=ctx.ring)
+    if check_faults:                     # a collision is printed like the reference does, and tolerated
+        raise_on_fault(err)
+    third = hist if form.observe == "hist" else third
+    return out if third is None else out + (third,)
+
+
+def _micro_ckpt_backward(ctx, g_pT, g_vT, g_third=None):
+    """The backward of every checkpointed form: the seeds, the cotangent of the third output as the form's sweep takes it, the one raw
+    call -> a gradient per argument of the form's forward."""
+    form, desc, T = ctx.form, ctx.desc, ctx.T
+    g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
+    observed = g_third is not None and {"hist": ctx.want_hist, "samples": ctx.observe, "fit": True}[form.observe]
+    g = {form.observe: g_third.contiguous() if observed else None}        # (None: nothing enters there; the fit's kernel takes zero)
+    if form.raw == "samples" and not observed:                               # (its sweep alone wants the array)
+        P = desc.capacity if ctx.probes is None else int(ctx.probes.numel())
+        g["samples"] = torch.zeros(T // ctx.every, desc.n_lanes, 2, P, device=err.device)
+    if ctx.g_head is not None:
+        ctx.g_head.zero_()
+    g_p0, g_v0, g_b = _micro_ckpt_bwd(form.raw, desc, T, ctx.ckpt, ctx.params, g_p, g_v, ctx.count, ctx.segment, err, ctx.out_bwd,
+                                      ctx.g_params, head=ctx.head, g_head=ctx.g_head, g_hist=g.get("hist"), probes=ctx.probes,
+                                      every=ctx.every, g_samples=g.get("samples"), lead=ctx.lead, lead_length=ctx.lead_length,
+                                      g_lead=ctx.g_lead, target=ctx.target, g_sse=g.get("fit"), ring=ctx.ring)
+    _micro_bwd_done(ctx)
+    if form.boundary == "head or lead":
+        g_b = (g_b, None) if ctx.lead is None else (None, g_b)
+    else:
+        g_b = () if form.boundary == "ring" else (g_b,)
+    return (g_p0, g_v0, ctx.g_params) + g_b + (None,) * form.nones
+
+
 class MicroRollout(torch.autograd.Function):
     """T fused differentiable IDM steps of L independent lanes with a fixed head gap.
 
@@ -2145,7 +2138,8 @@ class MicroRollout(torch.autograd.Function):
     _micro_lane.py:131-214 over _idm.py:30-49); outputs and the other gradients are bit for bit those of a call without it.
     checkpoint (None / False: the taped path; True: the plan's segment length; a positive int: that one): keep the state every so many
     steps instead of the tapes, and let the reverse sweep rebuild one segment of tape at a time in LDS (micro_ckpt_plan) -- the same
-    outputs and gradients bit for bit, and the only buffer that grows with T is 8 B per vehicle per segment.
+    outputs and gradients bit for bit, and the only buffer that grows with T is 8 B per vehicle per segment.  A checkpointed call that
+    requires grad is the "MicroRollout" row of _MICRO_CKPT_FORMS: the pair every checkpointed form shares runs it.
     """
 
     @staticmethod
@@ -2155,7 +2149,8 @@ class MicroRollout(torch.autograd.Function):
         want_params = params.requires_grad
         need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or want_params
         if segment is not None and need_grad:
-            return MicroRollout._forward_ckpt(ctx, p0, v0, params, head, count, desc, T, want_hist, check_faults, segment)
+            return _micro_ckpt_forward(ctx, "MicroRollout", p0, v0, params, count, T, dt, check_faults, checkpoint, head=head,
+                                       want_hist=want_hist, resolved=(desc, segment))
         p0c, v0c = _f32c(p0.detach(), "p0"), _f32c(v0.detach(), "v0")
         ctx.segment = None
         tape = torch.empty(micro_tape_numel(desc, T), dtype=torch.float32, device=p0.device) if need_grad else None
@@ -2179,27 +2174,13 @@ class MicroRollout(torch.autograd.Function):
         return pT, vT
 
     @staticmethod
-    def _forward_ckpt(ctx, p0, v0, params, head, count, desc, T, want_hist, check_faults, segment):
-        """The forward of a checkpointed call (one that requires grad): _micro_ckpt_setup's buffers and hist."""
-        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, True)
-        ctx.tape = ctx.ptape = None
-        ctx.head, ctx.want_hist = head.detach().contiguous(), want_hist
-        hist = torch.empty(T, desc.n_lanes, 2, desc.capacity, dtype=torch.float32, device=p0c.device) if want_hist else None
-        pT, vT = micro_rollout_fwd_ckpt(desc, T, p0c, v0c, ctx.params, ctx.head, ctx.ckpt, count=count, segment=segment, hist=hist, err=err)
-        _micro_fwd_done(ctx, err, count, check_faults, True)
-        return (pT, vT, hist) if want_hist else (pT, vT)
-
-    @staticmethod
     def backward(ctx, g_pT, g_vT, g_hist=None):
-        desc, T = ctx.desc, ctx.T
+        if ctx.segment is not None:
+            return _micro_ckpt_backward(ctx, g_pT, g_vT, g_hist)
         g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
         gh = g_hist.contiguous() if (ctx.want_hist and g_hist is not None) else None
-        if ctx.segment is not None:
-            g_p0, g_v0, g_head = micro_rollout_bwd_ckpt(desc, T, ctx.ckpt, ctx.params, ctx.head, g_p, g_v, count=ctx.count,
-                                                        segment=ctx.segment, g_hist=gh, err=err, g_params=ctx.g_params)
-        else:
-            g_p0, g_v0, g_head = micro_rollout_bwd(desc, T, ctx.tape, g_p, g_v, count=ctx.count, g_hist=gh, err=err,
-                                                   ptape=ctx.ptape, params=ctx.params, g_params=ctx.g_params)
+        g_p0, g_v0, g_head = micro_rollout_bwd(ctx.desc, ctx.T, ctx.tape, g_p, g_v, count=ctx.count, g_hist=gh, err=err,
+                                               ptape=ctx.ptape, params=ctx.params, g_params=ctx.g_params)
         _micro_bwd_done(ctx)
         return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None, None
 
@@ -2227,25 +2208,12 @@ class MicroRolloutSamples(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, head, count, T, dt, check_faults, checkpoint, probes, every):
-        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_plan)
-        need_grad = p0.requires_grad or v0.requires_grad or head.requires_grad or params.requires_grad
-        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
-        ctx.head, ctx.probes, ctx.every = head.detach().contiguous(), probes, every
-        pT, vT, samples = micro_rollout_fwd_ckpt_samples(desc, T, p0c, v0c, ctx.params, ctx.head, ctx.ckpt, probes, every, count=count,
-                                                         segment=segment, err=err)
-        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
-        return pT, vT, samples
+        return _micro_ckpt_forward(ctx, "MicroRolloutSamples", p0, v0, params, count, T, dt, check_faults, checkpoint, head=head,
+                                   probes=probes, every=every)
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_samples):
-        desc, T = ctx.desc, ctx.T
-        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
-        P = desc.capacity if ctx.probes is None else int(ctx.probes.numel())
-        gs = g_samples.contiguous() if g_samples is not None else torch.zeros(T // ctx.every, desc.n_lanes, 2, P, device=err.device)
-        g_p0, g_v0, g_head = micro_rollout_bwd_ckpt_samples(desc, T, ctx.ckpt, ctx.params, ctx.head, g_p, g_v, ctx.probes, ctx.every, gs,
-                                                            count=ctx.count, segment=ctx.segment, err=err, g_params=ctx.g_params)
-        _micro_bwd_done(ctx)
-        return g_p0, g_v0, ctx.g_params, g_head, None, None, None, None, None, None, None
+        return _micro_ckpt_backward(ctx, g_pT, g_vT, g_samples)
 
 
 class MicroRolloutLead(torch.autograd.Function):
@@ -2255,27 +2223,12 @@ class MicroRolloutLead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, lead, lead_length, count, T, dt, check_faults, checkpoint, probes, every, observe):
-        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_plan)
-        need_grad = p0.requires_grad or v0.requires_grad or lead.requires_grad or params.requires_grad
-        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
-        dev = p0c.device
-        ctx.lead, ctx.probes, ctx.every, ctx.observe = _f32c(lead.detach(), "lead"), probes, every, observe
-        ctx.lead_length = None if lead_length is None else lead_length.detach().to(device=dev, dtype=torch.float64).contiguous()
-        ctx.g_lead = torch.empty(T, desc.n_lanes, 2, dtype=torch.float32, device=dev) if need_grad else None
-        pT, vT, samples = micro_rollout_fwd_ckpt_lead(desc, T, p0c, v0c, ctx.params, ctx.lead, ctx.ckpt, probes, every,
-                                                      lead_length=ctx.lead_length, count=count, segment=segment, observe=observe, err=err)
-        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
-        return (pT, vT, samples) if observe else (pT, vT)
+        return _micro_ckpt_forward(ctx, "MicroRolloutLead", p0, v0, params, count, T, dt, check_faults, checkpoint, lead=lead,
+                                   lead_length=lead_length, probes=probes, every=every, observe=observe)
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_samples=None):
-        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
-        gs = g_samples.contiguous() if (ctx.observe and g_samples is not None) else None      # (None: nothing enters at the samples)
-        g_p0, g_v0, g_lead = micro_rollout_bwd_ckpt_lead(ctx.desc, ctx.T, ctx.ckpt, ctx.params, ctx.lead, g_p, g_v, ctx.probes, ctx.every,
-                                                         gs, lead_length=ctx.lead_length, count=ctx.count, segment=ctx.segment, err=err,
-                                                         g_lead=ctx.g_lead, g_params=ctx.g_params)
-        _micro_bwd_done(ctx)
-        return (g_p0, g_v0, ctx.g_params, g_lead) + (None,) * 9
+        return _micro_ckpt_backward(ctx, g_pT, g_vT, g_samples)
 
 
 class MicroRolloutTarget(torch.autograd.Function):
@@ -2286,37 +2239,12 @@ class MicroRolloutTarget(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, head, lead, lead_length, count, T, dt, check_faults, checkpoint, target):
-        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_target_plan)
-        boundary = head if lead is None else lead
-        need_grad = p0.requires_grad or v0.requires_grad or boundary.requires_grad or params.requires_grad
-        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
-        L, dev = desc.n_lanes, p0c.device
-        ctx.head = None if head is None else head.detach().contiguous()
-        ctx.lead = None if lead is None else _f32c(lead.detach(), "lead")
-        ctx.lead_length = None if lead_length is None else lead_length.detach().to(device=dev, dtype=torch.float64).contiguous()
-        ctx.target = _f32c(target, "target")
-        # ... and here also the reverse sweep's outputs
-        ctx.g_lead = torch.empty(T, L, 2, dtype=torch.float32, device=dev) if (need_grad and lead is not None) else None
-        ctx.g_head = torch.zeros(L, 2, dtype=torch.float64, device=dev) if (need_grad and lead is None) else None
-        ctx.out_bwd = (torch.empty_like(p0c), torch.empty_like(v0c)) if need_grad else None
-        pT, vT, sse = micro_rollout_fwd_ckpt_target(desc, T, p0c, v0c, ctx.params, ctx.ckpt, ctx.target, head=ctx.head, lead=ctx.lead,
-                                                    lead_length=ctx.lead_length, count=count, segment=segment, err=err)
-        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
-        return pT, vT, sse
+        return _micro_ckpt_forward(ctx, "MicroRolloutTarget", p0, v0, params, count, T, dt, check_faults, checkpoint, head=head, lead=lead,
+                                   lead_length=lead_length, target=target)
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_sse):
-        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
-        gs = g_sse.contiguous() if g_sse is not None else None          # (None: the kernel takes zero)
-        if ctx.g_head is not None:
-            ctx.g_head.zero_()
-        g_p0, g_v0, g_b = micro_rollout_bwd_ckpt_target(ctx.desc, ctx.T, ctx.ckpt, ctx.params, g_p, g_v, ctx.target, g_sse=gs, head=ctx.head,
-                                                        lead=ctx.lead, lead_length=ctx.lead_length, count=ctx.count, segment=ctx.segment,
-                                                        err=err, out=ctx.out_bwd, g_head=ctx.g_head, g_lead=ctx.g_lead,
-                                                        g_params=ctx.g_params)
-        _micro_bwd_done(ctx)
-        g_head, g_lead = (g_b, None) if ctx.lead is None else (None, g_b)
-        return (g_p0, g_v0, ctx.g_params, g_head, g_lead) + (None,) * 7
+        return _micro_ckpt_backward(ctx, g_pT, g_vT, g_sse)
 
 
 class MicroRolloutRing(torch.autograd.Function):
@@ -2327,23 +2255,12 @@ class MicroRolloutRing(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, ring, count, T, dt, check_faults, checkpoint, probes, every, observe):
-        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_plan)
-        need_grad = p0.requires_grad or v0.requires_grad or params.requires_grad
-        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
-        ctx.ring, ctx.probes, ctx.every, ctx.observe = ring.detach().to(device=p0c.device).contiguous(), probes, every, observe
-        pT, vT, samples = micro_rollout_fwd_ckpt_ring(desc, T, p0c, v0c, ctx.params, ctx.ring, ctx.ckpt, probes, every, count=count,
-                                                      segment=segment, observe=observe, err=err)
-        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
-        return (pT, vT, samples) if observe else (pT, vT)
+        return _micro_ckpt_forward(ctx, "MicroRolloutRing", p0, v0, params, count, T, dt, check_faults, checkpoint, ring=ring,
+                                   probes=probes, every=every, observe=observe)
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_samples=None):
-        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
-        gs = g_samples.contiguous() if (ctx.observe and g_samples is not None) else None      # (None: nothing enters at the samples)
-        g_p0, g_v0 = micro_rollout_bwd_ckpt_ring(ctx.desc, ctx.T, ctx.ckpt, ctx.params, ctx.ring, g_p, g_v, ctx.probes, ctx.every, gs,
-                                                 count=ctx.count, segment=ctx.segment, err=err, g_params=ctx.g_params)
-        _micro_bwd_done(ctx)
-        return (g_p0, g_v0, ctx.g_params) + (None,) * 9
+        return _micro_ckpt_backward(ctx, g_pT, g_vT, g_samples)
 
 
 class MicroRolloutRingTarget(torch.autograd.Function):
@@ -2352,25 +2269,12 @@ class MicroRolloutRingTarget(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, v0, params, ring, count, T, dt, check_faults, checkpoint, target):
-        desc, segment = _micro_segment(p0, params, T, dt, checkpoint, micro_ckpt_target_plan)
-        need_grad = p0.requires_grad or v0.requires_grad or params.requires_grad
-        p0c, v0c, err = _micro_ckpt_setup(ctx, desc, T, segment, p0, v0, params, need_grad)
-        ctx.ring, ctx.target = ring.detach().to(device=p0c.device).contiguous(), _f32c(target, "target")
-        ctx.out_bwd = (torch.empty_like(p0c), torch.empty_like(v0c)) if need_grad else None
-        pT, vT, sse = micro_rollout_fwd_ckpt_target_ring(desc, T, p0c, v0c, ctx.params, ctx.ring, ctx.ckpt, ctx.target, count=count,
-                                                         segment=segment, err=err)
-        _micro_fwd_done(ctx, err, count, check_faults, need_grad)
-        return pT, vT, sse
+        return _micro_ckpt_forward(ctx, "MicroRolloutRingTarget", p0, v0, params, count, T, dt, check_faults, checkpoint, ring=ring,
+                                   target=target)
 
     @staticmethod
     def backward(ctx, g_pT, g_vT, g_sse):
-        g_p, g_v, err = _micro_bwd_seeds(ctx, g_pT, g_vT)
-        gs = g_sse.contiguous() if g_sse is not None else None          # (None: the kernel takes zero)
-        g_p0, g_v0 = micro_rollout_bwd_ckpt_target_ring(ctx.desc, ctx.T, ctx.ckpt, ctx.params, ctx.ring, g_p, g_v, ctx.target, g_sse=gs,
-                                                        count=ctx.count, segment=ctx.segment, err=err, out=ctx.out_bwd,
-                                                        g_params=ctx.g_params)
-        _micro_bwd_done(ctx)
-        return (g_p0, g_v0, ctx.g_params) + (None,) * 7
+        return _micro_ckpt_backward(ctx, g_pT, g_vT, g_sse)
 
 
 def _micro_ring_checks(p0, head, T, ring, lead, lead_length, want_hist, checkpoint):
@@ -2479,48 +2383,40 @@ def micro_rollout(p0, v0, params, head, T, dt, count=None, want_hist=False, chec
     its cotangent exists; the kernels read target once per direction (MicroRolloutTarget).  checkpoint=True or a segment is required
     (the segment plan is micro_ckpt_target_plan's: its reverse ring is wider), want_hist / probes / every are not accepted (ValueError),
     lead / lead_length and ring combine with it.  Without a leaf that requires grad no checkpoint is kept: a loss evaluation."""
+    # every form's checks, each ValueError where it has always stood and all of them before anything touches a device ...
+    fit, led = target is not None, lead is not None or lead_length is not None
     if ring is not None:
         _micro_ring_checks(p0, head, T, ring, lead, lead_length, want_hist, checkpoint)
-        if target is not None:
-            _micro_target_checks(p0, T, target, want_hist, checkpoint, probes, every)
-            _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_target_plan)
-            return MicroRolloutRingTarget.apply(p0, v0, params, ring, count, int(T), float(dt), bool(check_faults), checkpoint, target)
-        sampling = micro_sampling(probes, every, int(p0.shape[-1]), False)
-        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_plan)
-        slots, ev = sampling if sampling is not None else (None, 1)
-        return MicroRolloutRing.apply(p0, v0, params, ring, count, int(T), float(dt), bool(check_faults), checkpoint,
-                                      _device_slots(slots, p0.device), ev, sampling is not None)
-    if target is not None:
+    if fit:
         _micro_target_checks(p0, T, target, want_hist, checkpoint, probes, every)
-        if lead is not None or lead_length is not None:
-            if lead is None:
-                raise ValueError("lead_length needs lead")
-            _micro_lead_checks(p0, head, T, lead, lead_length, False, checkpoint)
-        elif head is None:
-            raise ValueError("head must be given (float64 [L][2]) unless lead is")
-        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_target_plan)
-        return MicroRolloutTarget.apply(p0, v0, params, head, lead, lead_length, count, int(T), float(dt), bool(check_faults), checkpoint,
-                                        target)
-    if lead is not None or lead_length is not None:
+    if led and ring is None:
         if lead is None:
             raise ValueError("lead_length needs lead")
         _micro_lead_checks(p0, head, T, lead, lead_length, want_hist, checkpoint)
-        sampling = micro_sampling(probes, every, int(p0.shape[-1]), False)
-        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_plan)
-        slots, ev = sampling if sampling is not None else (None, 1)
-        return MicroRolloutLead.apply(p0, v0, params, lead, lead_length, count, int(T), float(dt), bool(check_faults), checkpoint,
-                                      _device_slots(slots, p0.device), ev, sampling is not None)
-    sampling = micro_sampling(probes, every, int(p0.shape[-1]), want_hist)
+    elif fit and ring is None and head is None:
+        raise ValueError("head must be given (float64 [L][2]) unless lead is")
+    sampling = None if fit else micro_sampling(probes, every, int(p0.shape[-1]), want_hist)
+    checkpointed = checkpoint is not None and checkpoint is not False
+    if (ring is not None or led or fit or (sampling is not None and checkpointed)) and p0.dim() == 2:
+        # (a bad `checkpoint` is a ValueError before the probes are uploaded; the plain form's is raised by MicroRollout itself)
+        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_target_plan if fit else micro_ckpt_plan)
+    # ... the upload, and the form's Function
+    slots, ev = sampling if sampling is not None else (None, 1)
+    run = (count, int(T), float(dt), bool(check_faults), checkpoint)
+    if ring is not None and fit:
+        return MicroRolloutRingTarget.apply(p0, v0, params, ring, *run, target)
+    if ring is not None:
+        return MicroRolloutRing.apply(p0, v0, params, ring, *run, _device_slots(slots, p0.device), ev, sampling is not None)
+    if fit:
+        return MicroRolloutTarget.apply(p0, v0, params, head, lead, lead_length, *run, target)
+    if led:
+        return MicroRolloutLead.apply(p0, v0, params, lead, lead_length, *run, _device_slots(slots, p0.device), ev, sampling is not None)
     if sampling is None:
         return MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), want_hist, bool(check_faults), checkpoint)
-    slots, every = sampling
-    if checkpoint is None or checkpoint is False:
+    if not checkpointed:                 # the taped path has no sampled kernel form: the samples are cut out of a dense history
         pT, vT, hist = MicroRollout.apply(p0, v0, params, head, count, int(T), float(dt), True, bool(check_faults), None)
-        return pT, vT, cut_samples(hist, slots, every, count)
-    if p0.dim() == 2:                    # (a bad `checkpoint` is a ValueError before the probes are uploaded)
-        _micro_segment(p0, params, int(T), float(dt), checkpoint, micro_ckpt_plan)
-    return MicroRolloutSamples.apply(p0, v0, params, head, count, int(T), float(dt), bool(check_faults), checkpoint,
-                                     _device_slots(slots, p0.device), every)
+        return pT, vT, cut_samples(hist, slots, ev, count)
+    return MicroRolloutSamples.apply(p0, v0, params, head, *run, _device_slots(slots, p0.device), ev)
 
 
 # ---------------------------------------------------------------------------------------------------------
