@@ -38,10 +38,40 @@
 // -(t_len[tail] + t_len[head]) / 2, the followers' expression with the tail as its leader.  kB = kBoundHead / kBoundLead are the code
 // the form was before (profiles/micro_ring_resources*.txt).
 
+//
+// A third pass, DHTS_MICRO_SAMPLES 3, gives the GAUSS-NEWTON form (kGN; dhts_micro_rollout_fwd_jvp_gn),
+// micro_rollout_fwd_jvp_gn_kernel<kK, kParams, kB, kBlock>: the normal equations of a trajectory fit instead of samples / t_samples.  At a
+// sampled step the thread of a live probe slot forms r = x - target in float32 (NaN = not observed, as the checkpointed target forms)
+// and adds the exact double products t_a t_b (a <= b), t_a r and r r of both planes to its own accumulators; after the step loop the
+// workgroup sums them over the slots by the target forms' fixed-order pairwise tree in the LDS the loop is done with, and thread 0
+// stores sse [L][2], jtr [L][K] and jtj [L][K][K] (both triangles).  No atomics: the same bits every run.  A launch carries the
+// directions MicroGn::dir names among the call's K -- every per-direction pointer is the CALL's, not the launch's -- and writes their
+// rows of jtr and their pairs of jtj; p_out, v_out, sse NULL: another launch of the call writes them.  Rows of target [T / every][L][2][n]
+// travel up to two rows ahead in registers (a row is asked for two sampled steps before its use and copied one before) and are loaded at
+// sampled steps only; there is no global store in the step loop.  kBlock is the
+// block bound: the accumulators (10 + 4 + 2 doubles at kK = 4) need the registers a block of 1024 does not leave.  Passes 0 and 1 are
+// the code they were before (profiles/micro_gn_resources*.txt).
+
+// the direction slot d of a launch carries: its own place among the pointers the launch is handed, or (kGN) gn.dir[d] among the call's
+#undef DHTS_GN_DIR
+#if DHTS_MICRO_SAMPLES == 3
+#define DHTS_GN_DIR(d) gn.dir[d]
+#else
+#define DHTS_GN_DIR(d) d
+#endif
 #if !DHTS_MICRO_SAMPLES
 __host__ __device__ inline size_t micro_fwd_jvp_lds_bytes(int V, int kK) {
     return sizeof(float2) * (size_t)(2 + 2 * kK) * (size_t)(V + 1) + 2 * sizeof(double) * (size_t)kK;
 }
+// kGN: what the fit is against, where its sums go and which of the call's n_dir directions this launch carries in its slots
+struct MicroGn {
+    const float *target;     // [T / every][L][2][n] float32, the layout of samples; NaN = not observed
+    double *sse;             // [L][2], or NULL (every launch of a call but the first)
+    double *jtr;             // [L][n_dir]
+    double *jtj;             // [L][n_dir][n_dir]
+    int n_dir;               // K of the call
+    int dir[4];              // slot d of the launch carries direction dir[d], d < n_act
+};
 #endif
 
 // grid = L workgroups (one traffic lane each) of blockDim.x >= V threads (V rounded up to 64): one vehicle per thread, its float32
@@ -66,10 +96,23 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_kernel(
     const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
     float *__restrict__ hist, float *__restrict__ t_hist, dhts_error *err, dhts_error *err_jvp) {
-    constexpr bool kSamp = false, kLead = false, kRing = false, kHeadGap = true;
+    constexpr bool kSamp = false, kLead = false, kRing = false, kHeadGap = true, kGN = false;
+    constexpr int kBlockBound = 1024;
     const MicroProbes pr = {};
     float *const samples = nullptr, *const t_samples = nullptr;
     const MicroLead ld = {};
+#elif DHTS_MICRO_SAMPLES == 3
+template <int kK, bool kParams, MicroBoundary kB, int kBlock>
+__global__ __launch_bounds__(kBlock) void micro_rollout_fwd_jvp_gn_kernel(
+    int L, int V, int T, double dt, const float *__restrict__ p_in, const float *__restrict__ v_in, const int32_t *__restrict__ count,
+    const double *__restrict__ params, const double *__restrict__ head, const float *__restrict__ t_p_in,
+    const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
+    float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
+    MicroProbes pr, MicroGn gn, dhts_error *err, dhts_error *err_jvp, MicroLead ld) {
+    constexpr bool kSamp = true, kGN = true, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead;
+    constexpr int kBlockBound = kBlock;
+    float *const hist = nullptr, *const t_hist = nullptr, *const samples = nullptr, *const t_samples = nullptr;
+    static_assert(kK <= 4, "MicroGn::dir has four slots");
 #else
 template <int kK, bool kParams, MicroBoundary kB>
 __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
@@ -78,8 +121,16 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
     const float *__restrict__ t_v_in, const double *__restrict__ t_head, const double *__restrict__ t_params, int n_act,
     float *__restrict__ p_out, float *__restrict__ v_out, float *__restrict__ t_p_out, float *__restrict__ t_v_out,
     MicroProbes pr, float *__restrict__ samples, float *__restrict__ t_samples, dhts_error *err, dhts_error *err_jvp, MicroLead ld) {
-    constexpr bool kSamp = true, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead;
+    constexpr bool kSamp = true, kLead = kB == kBoundLead, kRing = kB == kBoundRing, kHeadGap = kB == kBoundHead, kGN = false;
+    constexpr int kBlockBound = 1024;
     float *const hist = nullptr, *const t_hist = nullptr;
+#endif
+#if DHTS_MICRO_SAMPLES == 3
+    // kGN: this vehicle's sums -- sse p, sse v | jtr [kK] | the upper triangle of jtj, row by row
+    constexpr int kAcc = 2 + kK + kK * (kK + 1) / 2;
+    double acc[kAcc];
+#pragma unroll
+    for (int i = 0; i < kAcc; ++i) acc[i] = 0.;
 #endif
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = blockIdx.x;
@@ -100,6 +151,32 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
     const double inv_dt = 1.0 / dt;
     const size_t h_dir = (size_t)T * L * 2 * V;          // one direction of t_hist
 
+#if DHTS_MICRO_SAMPLES == 3
+    if constexpr (kGN) {
+        if (V > B) {                                     // every output of the lane NaN, the three sums among them
+            const float nanf_ = __builtin_nanf("");
+            const double nand_ = (double)nanf_;
+            if (p_out) for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
+#pragma unroll
+            for (int d = 0; d < kK; ++d)
+                if (d < n_act)
+                    for (int i = k; i < V; i += B) { t_p_out[DHTS_GN_DIR(d) * plane + base + i] = nanf_; t_v_out[DHTS_GN_DIR(d) * plane + base + i] = nanf_; }
+            if (k == 0) {
+                if (gn.sse) { gn.sse[(size_t)lane * 2] = nand_; gn.sse[(size_t)lane * 2 + 1] = nand_; }
+#pragma unroll
+                for (int a = 0; a < kK; ++a) {
+                    if (a >= n_act) continue;
+                    gn.jtr[(size_t)lane * gn.n_dir + DHTS_GN_DIR(a)] = nand_;
+#pragma unroll
+                    for (int b = 0; b < kK; ++b)
+                        if (b < n_act) gn.jtj[((size_t)lane * gn.n_dir + DHTS_GN_DIR(a)) * gn.n_dir + DHTS_GN_DIR(b)] = nand_;
+                }
+                raise_fault(err, DHTS_FAULT_CAPACITY, 0, lane, -3); raise_fault(err_jvp, DHTS_FAULT_CAPACITY, 0, lane, -3);
+            }
+            return;
+        }
+    } else
+#endif
     if (V > B) {
         const float nanf_ = __builtin_nanf("");
         for (int i = k; i < V; i += B) { p_out[base + i] = nanf_; v_out[base + i] = nanf_; }
@@ -127,8 +204,8 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
 #pragma unroll
     for (int d = 0; d < kK; ++d) {
         const bool act = vk && d < n_act;
-        tp[d] = act ? t_p_in[d * plane + base + k] : 0.f;
-        tv[d] = act ? t_v_in[d * plane + base + k] : 0.f;
+        tp[d] = act ? t_p_in[DHTS_GN_DIR(d) * plane + base + k] : 0.f;
+        tv[d] = act ? t_v_in[DHTS_GN_DIR(d) * plane + base + k] : 0.f;
     }
     IdmDerived prm = {};
     IdmParamDerived pm = {};
@@ -155,7 +232,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
 #pragma unroll
             for (int d = 0; d < kK; ++d) {
                 if (d < n_act) {
-                    const double *tq = t_params + (size_t)d * 6 * plane + base;
+                    const double *tq = t_params + (size_t)DHTS_GN_DIR(d) * 6 * plane + base;
 #pragma unroll
                     for (int q = 0; q < 5; ++q) tth[d][q] = tq[q * plane + k];
                     tth[d][5] = -(tq[5 * plane + kl] + tq[5 * plane + k]) * 0.5;
@@ -170,6 +247,16 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
 
     for (int i = k; i < (2 + 2 * kK) * P; i += B) S[i] = make_float2(0.f, 0.f);
     if constexpr (!kHeadGap) { if (k < 2 * kK) TH[k] = 0.; }
+#if DHTS_MICRO_SAMPLES == 3
+    else if constexpr (kGN) {
+        if (k < 2 * kK) {
+            int g = gn.dir[0];
+#pragma unroll
+            for (int d = 1; d < kK; ++d) g = (k >> 1) == d ? gn.dir[d] : g;
+            TH[k] = ((k >> 1) < n_act && t_head) ? t_head[((size_t)g * L + lane) * 2 + (k & 1)] : 0.;
+        }
+    }
+#endif
     else if (k < 2 * kK) TH[k] = ((k >> 1) < n_act && t_head) ? t_head[((size_t)(k >> 1) * L + lane) * 2 + (k & 1)] : 0.;
     __syncthreads();
 
@@ -179,7 +266,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         // flight in (lx, ly) and (ltx, lty); a direction of t_lead is T L 2 floats, NULL = zero.  The widest form with the parameter
         // term has no register left for eight more floats (128 VGPRs at 1024 threads): there the tangent rows are loaded in the
         // step that hands them over (kTanAhead false), the state row still travels ahead.
-        constexpr bool kTanAhead = !(kParams && kK >= 4);
+        constexpr bool kTanAhead = !(kParams && kK >= 4) || (kGN && kBlockBound < 1024);
         const float *lrow = nullptr, *ltrow = nullptr;
         float lx = 0.f, ly = 0.f, ltx[kLead && kTanAhead ? kK : 1], lty[kLead && kTanAhead ? kK : 1];
         const size_t lt_dir = (size_t)T * L * 2;
@@ -200,7 +287,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                     S[n] = make_float2(lrow[0], lrow[1]);
 #pragma unroll
                     for (int d = 0; d < kK; ++d)
-                        TN[d * P + n] = (ltrow && d < n_act) ? make_float2(ltrow[d * lt_dir], ltrow[d * lt_dir + 1]) : make_float2(0.f, 0.f);
+                        TN[d * P + n] = (ltrow && d < n_act) ? make_float2(ltrow[DHTS_GN_DIR(d) * lt_dir], ltrow[DHTS_GN_DIR(d) * lt_dir + 1]) : make_float2(0.f, 0.f);
                     lrow += (size_t)L * 2;
                     if (ltrow) ltrow += (size_t)L * 2;
                     const bool more = T > 1;
@@ -209,7 +296,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
 #pragma unroll
                         for (int d = 0; d < kK; ++d) {
                             const bool on = more && ltrow && d < n_act;
-                            ltx[d] = on ? ltrow[d * lt_dir] : 0.f; lty[d] = on ? ltrow[d * lt_dir + 1] : 0.f;
+                            ltx[d] = on ? ltrow[DHTS_GN_DIR(d) * lt_dir] : 0.f; lty[d] = on ? ltrow[DHTS_GN_DIR(d) * lt_dir + 1] : 0.f;
                         }
                     }
                 }
@@ -221,11 +308,44 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         int col = -1, cd = 0;
         size_t so = 0, s_dir = 0;
         if constexpr (kSamp) {
+#if DHTS_MICRO_SAMPLES == 3
+            if constexpr (kGN) col = micro_probe_column(pr, k, V);
+            else
+#endif
             col = (!kHeadGap && t_samples == nullptr) ? -1 : micro_probe_column(pr, k, V);      // kLead, kRing, no sample arrays: no column
             cd = pr.every;
             s_dir = (size_t)(T / pr.every) * L * 2 * pr.n;
             so = (size_t)lane * 2 * pr.n + (col < 0 ? 0 : col);
         }
+#if DHTS_MICRO_SAMPLES == 3
+        // kGN: this slot's column of the target row to load next (a row is L 2 n floats); the next two sampled rows are in (g1p, g1v) and
+        // (g2p, g2v), `rj` rows are behind (the copy g1 = g2 one sampled step after g2's load is where that load is waited for at the
+        // latest: one sampled step of cover is certain, two where the compiler renames).  Everything loaded so far arrives here, before the first row is asked for: left pending
+        // across the loop's entry, those loads would make every step wait for every load issued since (one counter, in order).
+        const float *tg = nullptr;
+        float g1p = 0.f, g1v = 0.f, g2p = 0.f, g2v = 0.f;
+        int rj = 0;
+        const int g_rows = T / pr.every;
+        const size_t g_row = (size_t)L * 2 * pr.n;
+        const bool g_on = vk && col >= 0;
+        if constexpr (kGN) {
+            asm volatile("" : "+v"(p), "+v"(v));
+#pragma unroll
+            for (int d = 0; d < kK; ++d) asm volatile("" : "+v"(tp[d]), "+v"(tv[d]));
+            if constexpr (kParams) {
+#pragma unroll
+                for (int d = 0; d < kK; ++d)
+#pragma unroll
+                    for (int qq = 0; qq < 6; ++qq) asm volatile("" : "+v"(tth[d][qq]));
+            }
+            if (g_on && g_rows > 0) {
+                tg = gn.target + so;
+                g1p = tg[0]; g1v = tg[pr.n];
+                tg += g_row;
+                if (g_rows > 1) { g2p = tg[0]; g2v = tg[pr.n]; }
+            }
+        }
+#endif
         for (int step = 0; step < T; ++step) {
             const int q = step & 1;
             bool due = false;
@@ -285,7 +405,7 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
 #pragma unroll
                         for (int d = 0; d < kK; ++d) {
                             if constexpr (kTanAhead) TN[((q ^ 1) * kK + d) * P + n] = make_float2(ltx[d], lty[d]);
-                            else TN[((q ^ 1) * kK + d) * P + n] = (ltrow && d < n_act) ? make_float2(ltrow[d * lt_dir], ltrow[d * lt_dir + 1])
+                            else TN[((q ^ 1) * kK + d) * P + n] = (ltrow && d < n_act) ? make_float2(ltrow[DHTS_GN_DIR(d) * lt_dir], ltrow[DHTS_GN_DIR(d) * lt_dir + 1])
                                                                                        : make_float2(0.f, 0.f);
                         }
                         lrow += (size_t)L * 2;
@@ -295,15 +415,47 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
                             if constexpr (kTanAhead) {
 #pragma unroll
                                 for (int d = 0; d < kK; ++d)
-                                    if (ltrow && d < n_act) { ltx[d] = ltrow[d * lt_dir]; lty[d] = ltrow[d * lt_dir + 1]; }
+                                    if (ltrow && d < n_act) { ltx[d] = ltrow[DHTS_GN_DIR(d) * lt_dir]; lty[d] = ltrow[DHTS_GN_DIR(d) * lt_dir + 1]; }
                             }
                         }
                     }
                 }
+#if DHTS_MICRO_SAMPLES == 3
+                if constexpr (kGN) {
+                    if (due && g_on) {
+                        // one observed entry per plane: x - target in float32, every product exact in double; p's terms, then v's
+                        const float rp = p - g1p, rv = v - g1v;
+                        if (g1p == g1p) {
+                            acc[0] += (double)rp * (double)rp;
+                            int i = 2 + kK;
+#pragma unroll
+                            for (int a = 0; a < kK; ++a) {
+                                acc[2 + a] += (double)tp[a] * (double)rp;
+#pragma unroll
+                                for (int b = a; b < kK; ++b) acc[i++] += (double)tp[a] * (double)tp[b];
+                            }
+                        }
+                        if (g1v == g1v) {
+                            acc[1] += (double)rv * (double)rv;
+                            int i = 2 + kK;
+#pragma unroll
+                            for (int a = 0; a < kK; ++a) {
+                                acc[2 + a] += (double)tv[a] * (double)rv;
+#pragma unroll
+                                for (int b = a; b < kK; ++b) acc[i++] += (double)tv[a] * (double)tv[b];
+                            }
+                        }
+                        g1p = g2p; g1v = g2v;
+                        ++rj;
+                        tg += g_row;
+                        if (rj + 1 < g_rows) { g2p = tg[0]; g2v = tg[pr.n]; }
+                    }
+                } else
+#endif
                 if constexpr (kSamp) { if (due && col >= 0 && samples) { samples[so] = p; samples[so + pr.n] = v; } }
                 else if (hist) { float *hp = hist + ((size_t)step * L + lane) * 2 * V + k; hp[0] = p; hp[V] = v; }
             }
-            if constexpr (kSamp) {
+            if constexpr (kSamp && !kGN) {
                 if (due) {
                     if (col >= 0) {                      // (col >= 0 is a slot below V) slots at or beyond count: 0, as in t_hist
                         float *hp = t_samples + so;
@@ -323,12 +475,64 @@ __global__ __launch_bounds__(1024) void micro_rollout_fwd_jvp_samples_kernel(
         }
     }
     if (k < V) {
-        p_out[base + k] = p; v_out[base + k] = v;
+        if (!kGN || p_out != nullptr) { p_out[base + k] = p; v_out[base + k] = v; }
 #pragma unroll
         for (int d = 0; d < kK; ++d)
-            if (d < n_act) { t_p_out[d * plane + base + k] = tp[d]; t_v_out[d * plane + base + k] = tv[d]; }
+            if (d < n_act) { t_p_out[DHTS_GN_DIR(d) * plane + base + k] = tp[d]; t_v_out[DHTS_GN_DIR(d) * plane + base + k] = tv[d]; }
     }
     if (fault_step >= 0) raise_fault(err, DHTS_FAULT_COLLISION, fault_step, lane, k);
+#if DHTS_MICRO_SAMPLES == 3
+    if constexpr (kGN) {
+        // The lane's sums: per accumulator the target forms' pairwise tree over the slots in a fixed order (no atomics: the same bits
+        // every run), kChunk accumulators a round, one plane of V doubles each -- every access of the step loop lies before a barrier
+        // all threads have passed, and kChunk V doubles fit the (2 + 2 kK) (V + 1) float2 it used.  Thread 0 stores each total where
+        // it belongs: sse, this launch's rows of jtr, its pairs of jtj and their mirror images.
+        constexpr int kChunk = 2 + 2 * kK;
+        double *A = reinterpret_cast<double *>(lds);
+        int w0 = 512;
+        while (w0 >= V) w0 >>= 1;                        // the largest power of two below V (0 for V = 1)
+        const size_t row = (size_t)lane * gn.n_dir;
+#pragma unroll
+        for (int c0 = 0; c0 < kAcc; c0 += kChunk) {
+            __syncthreads();
+            if (k < V) {
+#pragma unroll
+                for (int c = 0; c < kChunk; ++c)
+                    if (c0 + c < kAcc) A[(size_t)c * V + k] = acc[c0 + c];      // (a slot at or beyond count, or no probe: 0)
+            }
+            __syncthreads();
+            for (int w = w0; w > 0; w >>= 1) {
+                if (k < w && k + w < V) {
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c)
+                        if (c0 + c < kAcc) A[(size_t)c * V + k] += A[(size_t)c * V + k + w];
+                }
+                __syncthreads();
+            }
+            if (k == 0) {
+#pragma unroll
+                for (int c = 0; c < kChunk; ++c) {
+                    const int i = c0 + c;
+                    if (i >= kAcc) continue;
+                    const double x = A[(size_t)c * V];
+                    if (i < 2) { if (gn.sse) gn.sse[(size_t)lane * 2 + i] = x; }
+                    else if (i < 2 + kK) { if (i - 2 < n_act) gn.jtr[row + DHTS_GN_DIR(i - 2)] = x; }
+                    else {
+                        int j = 2 + kK;
+#pragma unroll
+                        for (int a = 0; a < kK; ++a)
+#pragma unroll
+                            for (int b = a; b < kK; ++b, ++j)
+                                if (j == i && b < n_act) {
+                                    gn.jtj[(row + DHTS_GN_DIR(a)) * gn.n_dir + DHTS_GN_DIR(b)] = x;
+                                    gn.jtj[(row + DHTS_GN_DIR(b)) * gn.n_dir + DHTS_GN_DIR(a)] = x;
+                                }
+                    }
+                }
+            }
+        }
+    }
+#endif
     // the lane's EARLIEST non-finite tangent, as micro_rollout_jvp_kernel records it: the minimum of (step, vehicle) through one LDS word
     if (err_jvp != nullptr) {
         unsigned *word = reinterpret_cast<unsigned *>(lds);

@@ -565,6 +565,10 @@ __device__ inline void micro_lead_fill(float *g_lead, int T, int L, int lane, in
 #define DHTS_MICRO_SAMPLES 2
 #include "micro_ckpt.inc"
 #undef DHTS_MICRO_SAMPLES
+// ---- the Gauss-Newton normal equations inside the fused kernel (dhts_micro_rollout_fwd_jvp_gn): the text of micro_fwd_jvp.inc once more ----
+#define DHTS_MICRO_SAMPLES 3
+#include "micro_fwd_jvp.inc"
+#undef DHTS_MICRO_SAMPLES
 
 }  // namespace dhts
 
@@ -773,6 +777,38 @@ static int micro_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, const fl
     (const void *)micro_rollout_fwd_jvp_samples_kernel<2, false, kBoundRing>,
     (const void *)micro_rollout_fwd_jvp_samples_kernel<4, true, kBoundRing>,
     (const void *)micro_rollout_fwd_jvp_samples_kernel<4, false, kBoundRing>};
+// ---- the Gauss-Newton form of the fused kernel: which instantiations exist, what a launch carries, which launches a call takes -------
+// The block bound a launch of kK directions is compiled for.  Four directions with the parameter term need 169 .. 186 VGPRs (16 double
+// accumulators beside 24 parameter tangents), which a block of 1024 does not leave: that instantiation exists for 512 threads only and
+// carries lanes of up to 512 slots.  Every other one fits the 128 VGPRs of 1024 threads and exists for that bound alone (a smaller
+// bound compiles to the same registers).
+constexpr int micro_gn_bound(int kK, bool params) { return kK >= 4 && params ? 512 : 1024; }
+// The widest micro_rollout_fwd_jvp_gn_kernel a lane of V slots can be handed: every instantiation held shows no scratch and no spill
+// for all three boundaries (profiles/micro_gn_resources.txt); a wider one is not instantiated, the plan narrows the launch instead.
+constexpr int micro_gn_kmax(int V, bool params) { return params && V > micro_gn_bound(4, true) ? 2 : 4; }
+// K directions under launch width w.  K <= w: one launch.  Otherwise the directions are cut into blocks of w / 2 and every PAIR of
+// blocks gets a launch (cross products need both directions in one launch): f(first, n_act, dir) per launch, until one returns false.
+// w < 2 carries K = 1 only.  Returns the number of launches, 0 where the width cannot carry K, -1 where f stopped.
+template <class F>
+inline int micro_gn_each_launch(int K, int w, F &&f) {
+    int dir[4] = {0, 0, 0, 0};
+    if (K < 1 || w < 1 || (K > w && w < 2)) return 0;
+    if (K <= w) {
+        for (int d = 0; d < K; ++d) dir[d] = d;
+        return f(true, K, dir) ? 1 : -1;
+    }
+    const int h = w / 2, nb = (K + h - 1) / h;
+    int launches = 0;
+    for (int i = 0; i < nb; ++i)
+        for (int j = i + 1; j < nb; ++j) {
+            int n = 0;
+            for (int d = i * h; d < (i + 1) * h && d < K; ++d) dir[n++] = d;
+            for (int d = j * h; d < (j + 1) * h && d < K; ++d) dir[n++] = d;
+            if (!f(launches == 0, n, dir)) return -1;
+            ++launches;
+        }
+    return launches;
+}
 // ---- the tape-free paths: the fused forward + tangent kernel and the checkpointed pair, every form through three launches ----------
 // The form a call runs in, host only (unpacked into the kernels' parameter lists at the launch): what it observes -- the dense
 // history, probe samples or the fit to a target -- with the arrays of that kind, and the recorded leader where the head follows one.
@@ -858,6 +894,39 @@ static int micro_fwd_jvp_launch(const dhts_micro_desc *d, int T, int n_dir, cons
         return ok;
     });
     return lds_ok ? launch_status() : DHTS_E_LAUNCH;
+}
+// The Gauss-Newton form: the launches of micro_gn_each_launch, each handed the CALL's per-direction arrays and its own direction map; the
+// first alone writes p_out, v_out, sse and the forward's fault record.  An entry of jtj or jtr that several launches write receives
+// the same bits from each (the same sum in the same order), so nothing is assembled afterwards and nothing races on one stream.
+static int micro_fwd_jvp_gn_launch(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                   const double *params, const double *head, const float *t_p, const float *t_v, const double *t_head,
+                                   const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                   const MicroProbes &pr, const MicroLead *lead, const float *target, double *sse, double *jtr, double *jtj,
+                                   dhts_error *err, dhts_error *err_jvp, void *stream) {
+    const int L = d->n_lanes, V = d->capacity;
+    const int width = micro_gn_kmax(V, t_params != nullptr);
+    const int boundary = !lead ? kBoundHead : (lead->ring ? kBoundRing : kBoundLead);
+    const MicroLead ld = lead ? *lead : MicroLead{};
+    const int launches = micro_gn_each_launch(n_dir, width, [&](bool first, int n_act, const int *dir) {
+        MicroGn gn = {target, first ? sse : nullptr, jtr, jtj, n_dir, {dir[0], dir[1], dir[2], dir[3]}};
+        bool ok = false;
+        pick<4, 2, 1>(n_act >= 3 ? 4 : n_act, [&](auto kv) {
+            pick<0, 1>(t_params != nullptr, [&](auto pv) {
+                pick<0, 1, 2>(boundary, [&](auto bv) {
+                    constexpr int kK = decltype(kv)::value;
+                    constexpr bool kParams = decltype(pv)::value != 0;
+                    if (padded64(V) <= micro_gn_bound(kK, kParams))      // (the plan's width never asks otherwise)
+                        ok = launch_lds(micro_rollout_fwd_jvp_gn_kernel<kK, kParams, (MicroBoundary) decltype(bv)::value, micro_gn_bound(kK, kParams)>,
+                                        L, padded64(V), micro_fwd_jvp_lds_bytes(V, kK), kLdsDefault, stream, L, V, T, d->dt, p, v, count,
+                                        params, head, t_p, t_v, t_head, t_params, n_act, first ? p_out : nullptr,
+                                        first ? v_out : nullptr, t_p_out, t_v_out, pr, gn, first ? err : nullptr, err_jvp, ld);
+                });
+            });
+        });
+        return ok;
+    });
+    if (launches == 0) return DHTS_E_INVALID;
+    return launches > 0 ? launch_status() : DHTS_E_LAUNCH;
 }
 // The checkpointed pair: both read block and segment (the form's ring) off the plan; the reverse kernel asks for its LDS above 64 KB.
 static int micro_ckpt_fwd_launch(const dhts_micro_desc *d, int T, int segment, const float *p, const float *v, const int32_t *count,
@@ -1029,6 +1098,39 @@ int dhts_micro_fwd_jvp_plan(const dhts_micro_desc *d, int T, int n_dir, int want
     plan[1] = g.widest;
     plan[2] = g.launches;
     plan[3] = (int32_t)micro_fwd_jvp_lds_bytes(d->capacity, g.widest);
+    return DHTS_OK;
+}
+// ---- the Gauss-Newton normal equations of a trajectory fit inside the fused kernel ---------------------------------------------------
+int dhts_micro_rollout_fwd_jvp_gn(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                  const double *params, const double *head, const float *lead, const double *lead_length,
+                                  const double *ring, const float *t_p, const float *t_v, const double *t_head, const float *t_lead,
+                                  const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                  const int32_t *probes, int n_probes, int every, const float *target, double *sse, double *jtr,
+                                  double *jtj, dhts_error *err, dhts_error *err_jvp, void *stream) {
+    MicroProbes pr;
+    // the head follows exactly one of head, lead, ring (T = 0 reads no row of lead: a NULL lead is then the lead form's, as its siblings')
+    const int bounds = (head != nullptr) + (lead != nullptr) + (ring != nullptr);
+    if (!micro_fwd_args_ok(d, T, p, v, params, p_out, v_out) || !micro_tangent_args_ok(n_dir, t_p, t_v, t_p_out, t_v_out) ||
+        bounds > 1 || (bounds == 0 && T > 0) || (t_head && !head) || ((t_lead || lead_length) && (head || ring || (!lead && T > 0))) ||
+        !micro_probes_ok(d, probes, n_probes, every, &pr) || (T / every > 0 && !target) || !sse || !jtr || !jtj)
+        return DHTS_E_INVALID;
+    if (micro_gn_each_launch(n_dir, micro_gn_kmax(d->capacity, t_params != nullptr), [](bool, int, const int *) { return true; }) == 0)
+        return DHTS_E_INVALID;
+    const MicroLead ld = {lead, lead_length, nullptr, t_lead, ring};
+    return micro_fwd_jvp_gn_launch(d, T, n_dir, p, v, count, params, head, t_p, t_v, t_head, t_params, p_out, v_out, t_p_out, t_v_out, pr,
+                                   head ? nullptr : &ld, target, sse, jtr, jtj, err, err_jvp, stream);
+}
+int dhts_micro_fwd_jvp_gn_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]) {
+    if (!micro_desc_ok(d) || T < 0 || n_dir < 1 || !plan) return DHTS_E_INVALID;
+    const int width = micro_gn_kmax(d->capacity, want_params != 0);
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = padded64(d->capacity);
+    plan[1] = width;
+    plan[2] = micro_gn_each_launch(n_dir, width, [](bool, int, const int *) { return true; });
+    const int widest = n_dir >= 3 && width >= 4 ? 4 : (n_dir >= 2 && width >= 2 ? 2 : 1);
+    plan[3] = (int32_t)micro_fwd_jvp_lds_bytes(d->capacity, widest);
+    plan[4] = n_dir <= width ? n_dir : width / 2;
+    plan[5] = micro_gn_bound(widest, want_params != 0);
     return DHTS_OK;
 }
 // ---- reverse mode from checkpoints, the segment tape in LDS ----------------------------------------------------------------------

@@ -165,6 +165,10 @@ SIGNATURES = {
     "dhts_micro_rollout_fwd_ckpt_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 9 + [C.c_int, C.c_int] + [_P] * 3),
     "dhts_micro_rollout_bwd_ckpt_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 7 + [C.c_int, C.c_int] + [_P] * 6),
     "dhts_micro_rollout_fwd_jvp_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 13 + [C.c_int, C.c_int] + [_P] * 5),
+    # desc T n_dir | p v count params | head lead lead_length ring | t_p t_v t_head t_lead t_params | the four outputs | probes n_probes
+    # every | target sse jtr jtj | err err_jvp stream
+    "dhts_micro_rollout_fwd_jvp_gn": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 18 + [C.c_int, C.c_int] + [_P] * 7),
+    "dhts_micro_fwd_jvp_gn_plan": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 8)]),
     "dhts_micro_rollout_fwd_ckpt_target_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 12),
     "dhts_micro_rollout_bwd_ckpt_target_ring": (C.c_int, [C.POINTER(MicroDesc), C.c_int, C.c_int] + [_P] * 13),
     # the siblings' arguments, then ramps, n_ramp, inflow (reverse: and g_inflow), ring, err, stream

@@ -173,8 +173,39 @@ def _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head, t_lead=None, T=0):
     return K
 
 
+def _micro_gn_checks(target, fused, want_hist):
+    """What target= rules out whatever the shapes are (ValueError, before anything touches a device)."""
+    if not fused:
+        raise ValueError("target lives in the fused kernel only: pass fused=True")
+    if want_hist:
+        raise ValueError("target and want_hist exclude each other: the fit is formed in the kernel so that no history exists")
+    if not isinstance(target, torch.Tensor):
+        raise ValueError("target must be a float32 tensor")
+
+
+def _micro_gn_target(p0, T, dt, K, t_params, sampling, target):
+    """target against the shape of the samples it takes the place of, and K against the plan of the Gauss-Newton form (ValueError, before
+    anything touches a device)."""
+    L, V = p0.shape
+    slots, every = sampling if sampling is not None else (None, 1)
+    n = V if slots is None else (int(slots.numel()) if isinstance(slots, torch.Tensor) else len(slots))
+    shape = (T // every, L, 2, n)
+    if target.dtype != torch.float32:
+        raise ValueError("target must be float32 (got %s)" % target.dtype)
+    if tuple(target.shape) != shape:
+        raise ValueError("target must have shape %s (got %s): [T // every][L][2][P], the shape of samples" % (shape, tuple(target.shape)))
+    if target.device != p0.device:
+        raise ValueError("target must be on p0's device %s (got %s)" % (p0.device, target.device))
+    if not target.is_contiguous():
+        raise ValueError("target must be contiguous")
+    if target.requires_grad:
+        raise ValueError("target must not require grad: it is data (a gradient of sse is dhts.micro_rollout(checkpoint=True, target=)'s)")
+    ops._gn_plan_carries(ops.micro_desc(L, V, dt), T, K, t_params is not None)
+
+
 def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_params=None, t_head=None, count=None, want_hist=False,
-                      check_faults=True, fused=False, probes=None, every=1, lead=None, lead_length=None, t_lead=None, ring=None):
+                      check_faults=True, fused=False, probes=None, every=1, lead=None, lead_length=None, t_lead=None, ring=None,
+                      target=None):
     """dhts.micro_rollout and K Jacobian-vector products of it in one pass over its tape (forward mode).
 
     Returns ((pT, vT[, hist]), (t_pT, t_vT[, t_hist])).  The primal outputs are those of dhts.micro_rollout(p0, v0, params, head, T, dt,
@@ -200,18 +231,31 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
 
     ring: as dhts.micro_rollout's `ring` (float64 [L]; the head vehicle follows the image of the tail one circumference ahead, whose
     tangents are the tail's; the tail's length tangent is in the head's gap).  It lives on the fused path only: fused=True is required,
-    want_hist is not accepted, and head, t_head, lead (with lead_length) and t_lead must be None.  probes / every combine with it."""
+    want_hist is not accepted, and head, t_head, lead (with lead_length) and t_lead must be None.  probes / every combine with it.
+
+    target: the Gauss-Newton normal equations of a trajectory fit, formed inside the fused kernel (dhts_micro_rollout_fwd_jvp_gn; fused=True
+    is required, want_hist is not accepted; every boundary and probes / every combine with it).  target is what was observed: float32,
+    contiguous, on p0's device, not requiring grad, of the shape samples would have -- [T][L][2][V] without sampling,
+    [T // every][L][2][P] with it; a NaN entry is not observed, a slot at or beyond count is never read.  The call returns
+    ((pT, vT, sse), (t_pT, t_vT, jtr, jtj)) and allocates neither history nor samples: with r = x - target in float32 and t_a the
+    float32 tangent of x in direction a, sse float64 [L][2] is dhts.micro_rollout(checkpoint=True, target=)'s (sum of r r per plane),
+    jtr float64 [L][K] the sum of t_a r and jtj float64 [L][K][K] the sum of t_a t_b over the observed entries of both planes of a lane
+    -- exact double products, summed in a fixed order (two runs give the same bits; jtj is bit-symmetric).  The loss is sse.sum(), its
+    gradient along the directions 2 jtr.sum(0), the Gauss-Newton matrix 2 jtj.sum(0).  K directions beyond what a launch carries are
+    run as one launch per pair of direction blocks (ops.micro_gn_launches); a K the lane's plan cannot carry is a ValueError."""
     T = int(T)
+    if target is not None:
+        _micro_gn_checks(target, fused, want_hist)
     if ring is not None:
         if lead is not None or lead_length is not None or t_lead is not None:
             raise ValueError("lead, lead_length and t_lead must be None when ring is given: the head vehicle follows the tail")
         return _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t_head, count, want_hist, check_faults, fused,
-                                       probes, every, None, None, None, ring)
+                                       probes, every, None, None, None, ring, target)
     if lead is None and (t_lead is not None or lead_length is not None):
         raise ValueError("t_lead and lead_length need lead")
     if lead is not None:
         return _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t_head, count, want_hist, check_faults, fused,
-                                       probes, every, lead, lead_length, t_lead)
+                                       probes, every, lead, lead_length, t_lead, None, target)
     K = _micro_jvp_tangents(p0, t_p0, t_v0, t_params, t_head)
     L, V = p0.shape
     sampling = ops.micro_sampling(probes, every, V, want_hist)
@@ -225,6 +269,8 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
         raise ValueError("count must be int32 [L]")
     if T < 0:
         raise ValueError("T must be >= 0")
+    if target is not None:
+        _micro_gn_target(p0, T, dt, K, t_params, sampling, target)
     desc = ops.micro_desc(L, V, dt)
     with torch.no_grad():
         p0c, v0c = ops._f32c(p0.detach(), "p0"), ops._f32c(v0.detach(), "v0")
@@ -241,6 +287,15 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
         tq = None if t_params is None else tan(t_params, (K, 6, L, V), torch.float64)
         if fused:                            # one kernel, no tape
             err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
+            if target is not None:           # the Gauss-Newton form: no history and no samples, the fit's sums instead
+                slots, ev = sampling if sampling is not None else (None, 1)
+                prim, tang = ops.micro_rollout_fwd_jvp_gn(desc, T, p0c, v0c, par, tp, tv, target, head=head.detach(),
+                                                          probes=ops._device_slots(slots, dev), every=ev, count=count, t_head=th,
+                                                          t_params=tq, err=err, err_jvp=err_jvp)
+                if check_faults:
+                    ops.raise_on_fault(err)
+                    ops.raise_on_fault(err_jvp)
+                return prim, tang
             if sampling is not None:         # the sampled kernel form: no history of either kind
                 slots = ops._device_slots(sampling[0], dev)
                 prim, tang = ops.micro_rollout_fwd_jvp_samples(desc, T, p0c, v0c, par, head.detach(), tp, tv, slots, sampling[1], count=count,
@@ -277,7 +332,7 @@ def micro_rollout_jvp(p0, v0, params, head, T, dt, *, t_p0=None, t_v0=None, t_pa
 
 
 def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t_head, count, want_hist, check_faults, fused, probes, every,
-                            lead, lead_length, t_lead, ring=None):
+                            lead, lead_length, t_lead, ring=None, target=None):
     """dhts.micro_rollout_jvp with a recorded leader, or (ring given, lead None) on a ring road: every ValueError first, then the lead
     or the ring form of the fused kernel."""
     what, follows = ("lead", "`lead`") if ring is None else ("ring", "the tail")
@@ -303,6 +358,8 @@ def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t
     if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (L,)):
         raise ValueError("count must be int32 [L]")
     sampling = ops.micro_sampling(probes, every, V, False)
+    if target is not None:
+        _micro_gn_target(p0, T, dt, K, t_params, sampling, target)
     desc = ops.micro_desc(L, V, dt)
     with torch.no_grad():
         p0c, v0c = ops._f32c(p0.detach(), "p0"), ops._f32c(v0.detach(), "v0")
@@ -320,7 +377,13 @@ def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t
         slots, ev = sampling if sampling is not None else (None, 1)
         slots = ops._device_slots(slots, dev)
         err, err_jvp = ops.new_error_record(dev), ops.new_error_record(dev)
-        if ring is not None:
+        if target is not None:
+            prim, tang = ops.micro_rollout_fwd_jvp_gn(desc, T, p0c, v0c, params.detach(), tp, tv, target,
+                                                      lead=None if ring is not None else ops._f32c(lead.detach(), "lead"), lead_length=ll,
+                                                      ring=None if ring is None else ring.detach().to(device=dev).contiguous(),
+                                                      probes=slots, every=ev, count=count, t_lead=tl, t_params=tq, err=err,
+                                                      err_jvp=err_jvp)
+        elif ring is not None:
             prim, tang = ops.micro_rollout_fwd_jvp_ring(desc, T, p0c, v0c, params.detach(), ring.detach().to(device=dev).contiguous(), tp,
                                                         tv, slots, ev, count=count, t_params=tq, observe=sampling is not None, err=err,
                                                         err_jvp=err_jvp)
@@ -331,6 +394,8 @@ def _micro_rollout_jvp_lead(p0, v0, params, head, T, dt, t_p0, t_v0, t_params, t
         if check_faults:                 # the forward's record first (a collision is printed and tolerated), then the tangents'
             ops.raise_on_fault(err)
             ops.raise_on_fault(err_jvp)
+    if target is not None:
+        return prim, tang
     if sampling is None:
         return prim[:2], tang[:2]
     return prim, tang

@@ -1471,6 +1471,51 @@ def micro_rollout_fwd_jvp(desc, T, p, v, params, head, t_p, t_v, count=None, t_h
     return _micro_fwd_jvp("hist", desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, head=head, t_head=t_head, want_hist=want_hist)
 
 
+def micro_fwd_jvp_gn_plan(desc, T, n_dir, want_params=False):
+    """What dhts_micro_rollout_fwd_jvp_gn launches for this shape (include/dhts.h): the keys of micro_jvp_plan -- dirs_per_launch the
+    widest kernel held for the lane (no scratch, no spill), launches 0 where that width cannot carry n_dir -- then pair_block, the
+    directions per block of the pair-of-blocks scheme, and block_bound, the block size the widest launch's kernel is compiled for."""
+    plan = (C.c_int32 * 8)()
+    check(_lib.lib().dhts_micro_fwd_jvp_gn_plan(C.byref(desc), int(T), int(n_dir), int(bool(want_params)), C.byref(plan)),
+          "dhts_micro_fwd_jvp_gn_plan")
+    return dict(zip(_MICRO_JVP_PLAN_KEYS + ("pair_block", "block_bound"), list(plan)))
+
+
+def micro_gn_launches(n_dir, width):
+    """The launches dhts_micro_rollout_fwd_jvp_gn takes for n_dir directions under launch width `width`, each a tuple of the directions it
+    carries (the library's schedule restated: its count is micro_fwd_jvp_gn_plan's `launches`).  n_dir <= width: one launch.  Otherwise
+    blocks of width // 2 directions and one launch per PAIR of blocks, so that every pair of directions meets in some launch; a width
+    below 2 carries one direction only (an empty list: it cannot carry n_dir)."""
+    n_dir, width = int(n_dir), int(width)
+    if n_dir < 1 or width < 1 or (n_dir > width and width < 2):
+        return []
+    if n_dir <= width:
+        return [tuple(range(n_dir))]
+    h = width // 2
+    blocks = [tuple(range(b, min(b + h, n_dir))) for b in range(0, n_dir, h)]
+    return [blocks[i] + blocks[j] for i in range(len(blocks)) for j in range(i + 1, len(blocks))]
+
+
+def micro_rollout_fwd_jvp_gn(desc, T, p, v, params, t_p, t_v, target, head=None, lead=None, lead_length=None, ring=None, probes=None, every=1,
+                             count=None, t_head=None, t_lead=None, t_params=None, err=None, err_jvp=None, out=None):
+    """The fused rollout + tangent call with the Gauss-Newton normal equations of a trajectory fit formed in the kernel
+    (dhts_micro_rollout_fwd_jvp_gn, include/dhts.h), through the launch path of the sampled forms: exactly one of head, lead, ring names
+    the boundary; target is a contiguous float32 [T // every][L][2][P] on p's device (the shape of samples; probes=None, every=1: [T][L][2][V]),
+    NaN = not observed.  Neither samples nor t_samples exists.  Returns ((pT, vT, sse), (t_pT, t_vT, jtr, jtj)): sse float64 [L][2], jtr
+    float64 [L][K], jtj float64 [L][K][K].  ValueError: a K the plan cannot carry (micro_fwd_jvp_gn_plan)."""
+    if (head is not None) + (lead is not None) + (ring is not None) != 1:
+        raise ValueError("exactly one of head, lead and ring must be given")
+    if t_head is not None and head is None:
+        raise ValueError("t_head needs head")
+    if (t_lead is not None or lead_length is not None) and lead is None:
+        raise ValueError("t_lead and lead_length need lead")
+    if target is None:
+        raise ValueError("target must be given")
+    form = "samples" if head is not None else ("lead" if lead is not None else "ring")
+    return _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, head=head, t_head=t_head, probes=probes,
+                          every=every, lead=lead, lead_length=lead_length, t_lead=t_lead, ring=ring, target=target)
+
+
 def micro_fwd_jvp_plan(desc, T, n_dir, want_params=False):
     """What dhts_micro_rollout_fwd_jvp launches for this shape: the keys of micro_jvp_plan."""
     plan = (C.c_int32 * 8)()
@@ -1747,14 +1792,38 @@ def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, 
     return out[0], out[1], (None if ring is not None else g_head if lead is None else g_lead)
 
 
+def _gn_target_arg(target, shape, device):
+    """The Gauss-Newton form's check of target: a contiguous float32 tensor of the shape of samples on the state's device, no grad."""
+    if (not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != tuple(shape)
+            or target.device != device or not target.is_contiguous() or target.requires_grad):
+        raise ValueError("target must be a contiguous float32 tensor of shape %s on %s that does not require grad" % (tuple(shape), device))
+
+
+def _gn_plan_carries(desc, T, K, want_params):
+    """The Gauss-Newton form's plan, or the ValueError for a K it cannot carry."""
+    plan = micro_fwd_jvp_gn_plan(desc, T, K, want_params)
+    if plan["launches"] == 0:
+        raise ValueError("V = %d%s: a launch of the Gauss-Newton form carries %d direction%s (block %d, compiled for %d threads), which "
+                         "cannot form the cross products of K = %d" % (desc.capacity, " with t_params" if want_params else "",
+                                                                        plan["dirs_per_launch"], "" if plan["dirs_per_launch"] == 1 else "s",
+                                                                        plan["block"], plan["block_bound"], K))
+    return plan
+
+
 def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, err_jvp, out, head=None, t_head=None, want_hist=False,
-                   probes=None, every=1, observe=True, lead=None, lead_length=None, t_lead=None, ring=None):
+                   probes=None, every=1, observe=True, lead=None, lead_length=None, t_lead=None, ring=None, target=None):
     """The fused rollout + tangent call of the "hist", "samples", "lead" and "ring" forms -> ((pT, vT, observed), (t_pT, t_vT, t_observed)),
-    observed = the histories (None unless asked for or handed in) or the sample arrays (None with observe False)."""
+    observed = the histories (None unless asked for or handed in) or the sample arrays (None with observe False).  target (the three
+    sampled forms): the Gauss-Newton form, dhts_micro_rollout_fwd_jvp_gn -> ((pT, vT, sse), (t_pT, t_vT, jtr, jtj)); out holds the four
+    state buffers only."""
     L, V, T = desc.n_lanes, desc.capacity, int(T)
     sampled = form != "hist"
     if sampled:
         rows, n, n_probes = _samples_shape(desc, T, probes, every)
+    if target is not None:
+        if not sampled:
+            raise ValueError("target takes the place of the sample arrays: the dense fit is the sampled form with probes=None, every=1")
+        _gn_target_arg(target, (rows, L, 2, n), p.device)
     if form == "lead":
         _lead_args(desc, T, lead, lead_length)
     if form == "ring":
@@ -1770,6 +1839,21 @@ def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, 
     _dir_arg("t_head", t_head, torch.float64, (K, L, 2))
     _dir_arg("t_params", t_params, torch.float64, (K, 6, L, V))
     out = tuple(out) if out is not None else ()
+    if target is not None:
+        _gn_plan_carries(desc, T, K, t_params is not None)
+        if len(out) not in (0, 4):
+            raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out)")
+        state = _state_out(("p_out", "v_out", "t_p_out", "t_v_out"), out, (p, v, t_p, t_v))
+        sse = torch.zeros(L, 2, dtype=torch.float64, device=p.device)
+        jtr, jtj = torch.zeros(L, K, dtype=torch.float64, device=p.device), torch.zeros(L, K, K, dtype=torch.float64, device=p.device)
+        # include/dhts.h: desc T n_dir p v count params | head lead lead_length ring | t_p t_v t_head t_lead t_params | the four outputs |
+        # probes n_probes every | target sse jtr jtj | err err_jvp stream
+        check(_lib.lib().dhts_micro_rollout_fwd_jvp_gn(
+            C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head), _data(lead), _ptr(lead_length), _ptr(ring),
+            _ptr(t_p), _ptr(t_v), _ptr(t_head), _data(t_lead), _ptr(t_params), _ptr(state[0]), _ptr(state[1]), _ptr(state[2]),
+            _ptr(state[3]), _ptr(probes), n_probes, every, _data(target), _ptr(sse), _ptr(jtr), _ptr(jtj), _ptr(err), _ptr(err_jvp),
+            _stream()), "dhts_micro_rollout_fwd_jvp_gn")
+        return (state[0], state[1], sse), (state[2], state[3], jtr, jtj)
     names = ("samples", "t_samples") if sampled else ("hist", "t_hist")
     if len(out) not in (0, 4, 6) or (len(out) == 6 and not observe):
         raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, %s, %s])" % names)

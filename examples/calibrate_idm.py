@@ -24,6 +24,11 @@ recorded leader lives on the tape-free paths: with --checkpoint (Adam) or --meth
 (dhts.micro_rollout(target=observed)) and return the squared error per lane, loss = sse.sum() / observed.numel(); neither the history
 nor its cotangent is allocated, so the fit holds `observed` and the checkpoints and nothing else of size T x V.  The same log up to
 the summation order of the loss (float64 in the kernels, float32 in torch.mean).
+--method lm --fused --fused-loss: the normal equations inside the fused kernel (dhts.micro_rollout_jvp(fused=True, target=observed)) --
+the call returns sse [L][2], J^T r [L][5] and J^T J [L][5][5] in float64, summed over the lanes here, instead of hist and five
+directions of t_hist; the trial step's loss is dhts.micro_rollout(checkpoint=True, target=observed)'s sse without grad (with --observe
+the sse of the same fused call with one direction: the checkpointed target form is dense).  The fit then holds `observed` and nothing else of size T x V, with
+and without --observe, --leader and --ring.  The same first loss up to the summation order; the later lines pass through the solve.
 --ring C: the closed experiment of car-following research -- n_vehicle drivers on a ring road of circumference C metres, the head
 following the tail one circumference ahead (dhts.micro_rollout(ring=) / micro_rollout_jvp(ring=)).  The truth is a ring rollout of a
 perturbed platoon (even spacing C / n_vehicle with a jitter, random speeds: what grows into stop-and-go waves), and the fit runs on the
@@ -65,7 +70,8 @@ def main():
     ap.add_argument("--leader", action="store_true",
                     help="fit the followers of a recorded leader: the truth has n_vehicle + 1 vehicles, its head's trajectory is given")
     ap.add_argument("--fused-loss", action="store_true",
-                    help="Adam with --checkpoint: the squared error and its gradient inside the rollout kernels (target=), no history")
+                    help="Adam with --checkpoint: the squared error and its gradient inside the rollout kernels (target=), no history; "
+                         "--method lm --fused: the normal equations J^T J, J^T r and the loss inside the fused kernel")
     ap.add_argument("--ring", type=float, default=None, metavar="C",
                     help="a ring road of circumference C metres: the head vehicle follows the tail (needs --checkpoint or --method lm --fused)")
     ap.add_argument("--seed", type=int, default=0)
@@ -83,7 +89,9 @@ def main():
         ap.error("--ring and --leader exclude each other: on a ring the head vehicle follows the tail")
     if args.ring is not None and args.ring < 2.0 * args.vehicle_length * args.n_vehicle:
         ap.error("--ring C is too short for n_vehicle vehicles: give each at least two vehicle lengths")
-    if args.fused_loss and (args.checkpoint is None or args.observe is not None):
+    if args.fused_loss and args.method == "lm" and not args.fused:
+        ap.error("--fused-loss with --method lm forms the normal equations in the fused kernel: add --fused")
+    if args.fused_loss and args.method == "adam" and (args.checkpoint is None or args.observe is not None):
         ap.error("--fused-loss is the dense fit on the checkpointed path: add --checkpoint, drop --observe")
     sampled = {}                                  # the arguments of a sampled call; none: the dense history
     if args.observe is not None:
@@ -152,8 +160,35 @@ def main():
             unit = th.zeros(5, 6, L, V, dtype=th.float64, device=dev)      # direction i: d params / d theta_i, the same on every vehicle
             for i in range(5):
                 unit[i, i] = 1.0
+            def normal_equations(theta, directions=unit):
+                """--fused-loss: (loss, J^T J, J^T r) from the fused kernel; neither hist nor t_hist is written."""
+                params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+                (_, _, sse), (_, _, jtr, jtj) = dhts.micro_rollout_jvp(p0, v0, params, None if follow else head, T, dt, t_params=directions,
+                                                                        fused=True, target=observed, **follow, **sampled)
+                return sse.sum() / observed.numel(), jtj.sum(0), jtr.sum(0)
+
+            def trial_loss(theta):
+                """--fused-loss: the loss alone, no grad -- the checkpointed target form, or (sampled: that form is dense) the fused call's sse."""
+                if sampled:          # one direction is one launch of the narrowest kernel: the same sse
+                    return normal_equations(theta, unit[:1])[0]
+                params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+                with th.no_grad():
+                    sse = dhts.micro_rollout(p0, v0, params, None if follow else head, T, dt, checkpoint=True, target=observed, **follow)[2]
+                return sse.sum() / observed.numel()
+
             for ep in range(args.n_episode):
                 params = th.cat([theta, length])[:, None, None].expand(6, L, V)
+                if args.fused_loss:
+                    loss, jtj, jtr = normal_equations(theta)
+                    err = ((theta - truth[:5]) / truth[:5]).abs().max()
+                    lines.append("{} {}\n".format(err.item(), loss.item()))
+                    step = -th.linalg.solve(jtj + th.diag(lam * th.diagonal(jtj).clamp_min(1e-30)), jtr)
+                    trial_theta = th.max(th.min(theta + step, hi), lo)
+                    if trial_loss(trial_theta).item() < loss.item():
+                        theta, lam = trial_theta, max(lam / 3.0, 1e-9)
+                    else:
+                        lam = min(lam * 3.0, 1e9)
+                    continue
                 if follow:
                     (_, _, hist), (_, _, t_hist) = dhts.micro_rollout_jvp(p0, v0, params, None, T, dt, t_params=unit, fused=True, **follow,
                                                                           **observe)

@@ -960,6 +960,48 @@ int dhts_micro_rollout_bwd_ckpt_target_ring(const dhts_micro_desc *d, int T, int
                                             const float *target, const double *g_sse, float *g_p_out, float *g_v_out, double *g_params,
                                             dhts_error *err, void *stream);
 
+/*
+ * The GAUSS-NEWTON NORMAL EQUATIONS of a trajectory fit inside the fused forward + tangent kernel: forward mode's counterpart of the
+ * _ckpt_target pair.  dhts_micro_rollout_fwd_jvp_gn runs the rollout and its n_dir tangent directions as dhts_micro_rollout_fwd_jvp_samples
+ * / _lead / _ring do -- the same arguments, arithmetic, fault records and bits of (p_out, v_out, t_p_out, t_v_out) -- and, instead of
+ * writing samples / t_samples, sums over them against
+ *   target   [T / every][L][2][n] float32, the layout of samples (n = n_probes, or V with probes NULL; probes NULL and every 1 is
+ *            hist's indexing [T][L][2][V]): the observed (p, v) of probe slot i after step (j + 1) every - 1.  A NaN entry is NOT
+ *            OBSERVED and adds exactly 0 to all three sums; a column whose slot is at or beyond count[l] is never read.
+ * With x the float32 sample, r = x - target in float32, and t_a the float32 tangent of x in direction a (what t_samples would hold):
+ *   sse      [L][2] double      sse[l][c] = sum of (double)r (double)r over the observed entries of plane c: dhts_micro_rollout_fwd_ckpt_target's
+ *                               definition and, with probes NULL and every 1, its bits
+ *   jtr      [L][n_dir] double          jtr[l][a]    = sum over the observed entries of lane l, BOTH planes, of (double)t_a (double)r
+ *   jtj      [L][n_dir][n_dir] double   jtj[l][a][b] = the same sum of (double)t_a (double)t_b; both triangles are written, bit-symmetric
+ * Every product is exact in double.  A thread sums its own vehicle's terms in step order (p's, then v's), the workgroup combines the
+ * slots by the target forms' fixed-order pairwise tree: no atomics, two runs give the same bits.  T / every = 0 and an empty lane give
+ * zeros.  No weights but the NaN mask; no gradient of the sums (reverse mode has the _ckpt_target pair).
+ *   head, or lead (lead_length), or ring    exactly one is non-NULL and names the form (T = 0: all three may be NULL); t_head only with
+ *            head, t_lead only with lead, each [n_dir][...] as in the sibling, NULL: zero.
+ * Launches: a launch carries up to plan[1] directions.  n_dir <= plan[1]: one launch.  Otherwise the directions are cut into blocks of
+ * plan[1] / 2 and every PAIR of blocks gets a launch (a cross product needs both directions in one launch): with plan[1] = 4, n_dir 5, 6:
+ * 3 launches, 7, 8: 6.  Each recomputes the primal and writes its directions' rows of jtr and pairs of jtj in place; an entry written by
+ * several launches receives the same bits from each.  The first alone writes p_out, v_out, sse and is handed err.
+ * dhts_micro_fwd_jvp_gn_plan: plan[0] block size (the lane rounded up to 64: one vehicle per thread)
+ *                             plan[1] direction slots of the widest kernel held for this lane and want_params: the widest whose
+ *                                     compiler listing has no scratch and no register spill (the accumulators are 2 + K + K (K + 1) / 2
+ *                                     doubles per thread): 4, but 2 with want_params for a lane of more than 512 slots
+ *                             plan[2] launches for n_dir, 0: plan[1] cannot carry n_dir (plan[1] = 1 carries n_dir = 1 only)
+ *                             plan[3] dynamic LDS bytes of the widest launch (the siblings': the sums are combined in the same bytes)
+ *                             plan[4] directions per block of the pair scheme (n_dir where one launch takes them all)
+ *                             plan[5] the block bound the widest launch's kernel is compiled for (512 or 1024)
+ * DHTS_E_INVALID, nothing dereferenced and nothing launched: whatever the siblings reject; more or fewer than one of head, lead, ring
+ * (T > 0); t_head without head, t_lead or lead_length beside head or ring, or without lead where T > 0; a NULL target with T / every > 0; a NULL sse, jtr or jtj; an n_dir
+ * with plan[2] = 0.  A block smaller than the lane: DHTS_FAULT_CAPACITY, the lane's sse, jtr and jtj NaN.
+ */
+int dhts_micro_rollout_fwd_jvp_gn(const dhts_micro_desc *d, int T, int n_dir, const float *p, const float *v, const int32_t *count,
+                                  const double *params, const double *head, const float *lead, const double *lead_length,
+                                  const double *ring, const float *t_p, const float *t_v, const double *t_head, const float *t_lead,
+                                  const double *t_params, float *p_out, float *v_out, float *t_p_out, float *t_v_out,
+                                  const int32_t *probes, int n_probes, int every, const float *target, double *sse, double *jtr,
+                                  double *jtj, dhts_error *err, dhts_error *err_jvp, void *stream);
+int dhts_micro_fwd_jvp_gn_plan(const dhts_micro_desc *d, int T, int n_dir, int want_params, int32_t plan[8]);
+
 int dhts_micro_step_fwd(const dhts_micro_desc *d,
                         const float *p, const float *v, const int32_t *count, const double *params, const double *head,
                         float *p_out, float *v_out, float *tape, dhts_error *err, void *stream);
