@@ -92,21 +92,21 @@ class _NetStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, r, y, own, action, u, q, net, step, hard):
-        lib, st = _lib.lib(), ops._stream()
+        st = ops._stream()
         r, y, own, action, u, q = (x.contiguous() for x in (r, y, own, action, u, q))
         L = net.L
         ghost = torch.empty(L, 2, 4, dtype=torch.float32, device=r.device)
         own_out = own.clone()           # (side-0 rows are not written)
-        _lib.check(lib.dhts_net_ghosts_fwd(C.byref(net.desc), C.byref(net.dtab.c), int(step), int(hard), _addr(action), _addr(r), _addr(u),
-                                           _addr(own), _addr(own_out), _addr(ghost), st), "dhts_net_ghosts_fwd")
+        _lib.call("dhts_net_ghosts_fwd", d=C.byref(net.desc), t=C.byref(net.dtab.c), step=int(step), hard=int(hard), action=_addr(action),
+                  r=_addr(r), u=_addr(u), own_in=_addr(own), own_out=_addr(own_out), ghost=_addr(ghost), stream=st)
         nr, ny, nu, nq = (torch.empty_like(r) for _ in range(4))
-        tapes = []
+        tapes, step_fwd = [], _lib.bind("dhts_macro_step_fwd")
         for g in net.groups:
             tape = None if hard else torch.empty(g["tape_numel"], dtype=torch.float32, device=r.device)
             co, lo = g["cell_off"], g["lane_off"]
-            _lib.check(lib.dhts_macro_step_fwd(C.byref(g["desc"]), _addr(r, co), _addr(y, co), _addr(u, co), _addr(q, co), _addr(ghost, 8 * lo),
-                                               _addr(nr, co), _addr(ny, co), _addr(nu, co), _addr(nq, co),
-                                               _addr(tape) if tape is not None else None, _addr(net.err), st), "dhts_macro_step_fwd")
+            step_fwd(d=C.byref(g["desc"]), r=_addr(r, co), y=_addr(y, co), u=_addr(u, co), ueq=_addr(q, co), ghost=_addr(ghost, 8 * lo),
+                     r_out=_addr(nr, co), y_out=_addr(ny, co), u_out=_addr(nu, co), ueq_out=_addr(nq, co),
+                     tape=_addr(tape) if tape is not None else None, err=_addr(net.err), stream=st)
             tapes.append(tape)
         # what backward reads is snapshotted here: rollout() rebuilds the descriptors and the fault record on every call, and
         # update() overwrites the per-step tables in place (a pending backward across an update() is refused below)
@@ -123,22 +123,23 @@ class _NetStep(torch.autograd.Function):
             raise RuntimeError("BatchedMacroNetwork: an evaluation episode (differentiable=False) keeps no tape to back-propagate through")
         if net._version != ctx.version:
             raise RuntimeError("BatchedMacroNetwork.update() overwrote the per-step tables this episode ran on: call backward() before update()")
-        lib, st = _lib.lib(), ops._stream()
+        st = ops._stream()
         r, y, u, own, action = ctx.saved_tensors
         g_nr, g_ny, g_own = g_nr.contiguous(), g_ny.contiguous(), g_own.contiguous()
         g_r, g_y = torch.empty_like(r), torch.empty_like(r)
         g_ghost = torch.zeros(net.L, 2, 2, dtype=torch.float64, device=r.device)
+        step_bwd = _lib.bind("dhts_macro_step_bwd")
         for g, gdesc, tape in zip(net.groups, ctx.gdescs, ctx.tapes):
             co, lo = g["cell_off"], g["lane_off"]
-            _lib.check(lib.dhts_macro_step_bwd(C.byref(gdesc), _addr(tape), _addr(g_nr, co), _addr(g_ny, co), _addr(g_r, co), _addr(g_y, co),
-                                               C.c_void_p(g_ghost.data_ptr() + 8 * 4 * lo), _addr(ctx.err), st), "dhts_macro_step_bwd")
+            step_bwd(d=C.byref(gdesc), tape=_addr(tape), g_r=_addr(g_nr, co), g_y=_addr(g_ny, co), g_r_out=_addr(g_r, co),
+                     g_y_out=_addr(g_y, co), g_ghost=C.c_void_p(g_ghost.data_ptr() + 8 * 4 * lo), err=_addr(ctx.err), stream=st)
         g_own_out = torch.empty_like(own)
         g_action = torch.zeros_like(action)
         scratch = torch.empty(net.L, 2, 4, dtype=torch.float32, device=r.device)
-        _lib.check(lib.dhts_net_ghosts_bwd(C.byref(ctx.desc), C.byref(net.dtab.c), _addr(ctx.inter[0]), _addr(ctx.inter[1]), ctx.step,
-                                           _addr(action), _addr(r), _addr(y), _addr(u), _addr(own), C.c_void_p(g_ghost.data_ptr()),
-                                           _addr(g_own), _addr(g_own_out), _addr(g_r), _addr(g_y), _addr(g_action), _addr(scratch), st),
-                   "dhts_net_ghosts_bwd")
+        _lib.call("dhts_net_ghosts_bwd", d=C.byref(ctx.desc), t=C.byref(net.dtab.c), inter_ptr=_addr(ctx.inter[0]), inter_idx=_addr(ctx.inter[1]),
+                  step=ctx.step, action=_addr(action), r=_addr(r), y=_addr(y), u=_addr(u), own_in=_addr(own),
+                  g_ghost=C.c_void_p(g_ghost.data_ptr()), g_own_in=_addr(g_own), g_own_out=_addr(g_own_out), g_r=_addr(g_r), g_y=_addr(g_y),
+                  g_action=_addr(g_action), scratch=_addr(scratch), stream=st)
         return g_r, g_y, g_own_out, g_action, None, None, None, None, None
 
 

@@ -16,7 +16,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import MacroDesc, MicroDesc, check
+from ._lib import MacroDesc, MicroDesc, call, check, raw
 from .tables import UploadedTables
 
 EPS = 1e-5  # model/macro/_arz.py:2
@@ -106,21 +106,20 @@ def macro_desc(L, N, dt, dx, u_max):
 
 def macro_tape_numel(desc, T):
     """float32 elements of the rollout tape (include/dhts.h: left-cell states + the compacted products of the exceptions)."""
-    return _lib.lib().dhts_macro_tape_bytes(C.byref(desc), int(T)) // 4
+    return raw("dhts_macro_tape_bytes", d=C.byref(desc), T=int(T)) // 4
 
 
 def macro_step_tape_numel(desc):
     """float32 elements of the single-step operator's tape (the reference's per-cell blocks)."""
-    return _lib.lib().dhts_macro_step_tape_bytes(C.byref(desc)) // 4
+    return raw("dhts_macro_step_tape_bytes", d=C.byref(desc)) // 4
 
 
 def macro_step_fwd(desc, r, y, u, ueq, ghost, tape=None, err=None):
     """One step of L lanes through the operator entry point (dqs-layout tape)."""
     r, y, u, ueq, ghost = (_f32c(t, n) for t, n in ((r, "r"), (y, "y"), (u, "u"), (ueq, "ueq"), (ghost, "ghost")))
     out = tuple(torch.empty_like(r) for _ in range(4))
-    check(_lib.lib().dhts_macro_step_fwd(C.byref(desc), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost),
-                                         _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(tape), _ptr(err), _stream()),
-          "dhts_macro_step_fwd")
+    call("dhts_macro_step_fwd", d=C.byref(desc), r=_ptr(r), y=_ptr(y), u=_ptr(u), ueq=_ptr(ueq), ghost=_ptr(ghost), r_out=_ptr(out[0]),
+         y_out=_ptr(out[1]), u_out=_ptr(out[2]), ueq_out=_ptr(out[3]), tape=_ptr(tape), err=_ptr(err), stream=_stream())
     return out
 
 
@@ -128,31 +127,30 @@ def macro_step_bwd(desc, tape, g_r, g_y, err=None):
     g_r, g_y = _f32c(g_r, "g_r"), _f32c(g_y, "g_y")
     out = (torch.empty_like(g_r), torch.empty_like(g_y))
     g_ghost = torch.zeros(desc.n_lanes, 2, 2, dtype=torch.float64, device=g_r.device)
-    check(_lib.lib().dhts_macro_step_bwd(C.byref(desc), _ptr(tape), _ptr(g_r), _ptr(g_y), _ptr(out[0]), _ptr(out[1]),
-                                         _ptr(g_ghost), _ptr(err), _stream()), "dhts_macro_step_bwd")
+    call("dhts_macro_step_bwd", d=C.byref(desc), tape=_ptr(tape), g_r=_ptr(g_r), g_y=_ptr(g_y), g_r_out=_ptr(out[0]), g_y_out=_ptr(out[1]),
+         g_ghost=_ptr(g_ghost), err=_ptr(err), stream=_stream())
     return out[0], out[1], g_ghost
 
 
 def macro_state_from_ru(r, u, u_max):
     r, u = _f32c(r, "r"), _f32c(u, "u")
     y, q = torch.empty_like(r), torch.empty_like(r)
-    check(_lib.lib().dhts_macro_state_from_ru(r.numel(), float(u_max), _ptr(r), _ptr(u), _ptr(y), _ptr(q), _stream()),
-          "dhts_macro_state_from_ru")
+    call("dhts_macro_state_from_ru", n=r.numel(), u_max=float(u_max), r=_ptr(r), u=_ptr(u), y=_ptr(y), ueq=_ptr(q), stream=_stream())
     return y, q
 
 
 def macro_state_from_ru_bwd(r, u, g_y, g_r, u_max):
     """g_r is updated in place; returns g_u."""
     g_u = torch.empty_like(r)
-    check(_lib.lib().dhts_macro_state_from_ru_bwd(r.numel(), float(u_max), _ptr(r), _ptr(u), _ptr(g_y), _ptr(g_r),
-                                                  _ptr(g_u), _stream()), "dhts_macro_state_from_ru_bwd")
+    call("dhts_macro_state_from_ru_bwd", n=r.numel(), u_max=float(u_max), r=_ptr(r), u=_ptr(u), g_y=_ptr(g_y), g_r=_ptr(g_r),
+         g_u=_ptr(g_u), stream=_stream())
     return g_u
 
 
 def macro_u_tap_bwd(r, y, g_u, g_r, g_y, u_max):
     """g_r, g_y updated in place."""
-    check(_lib.lib().dhts_macro_u_tap_bwd(r.numel(), float(u_max), _ptr(r), _ptr(y), _ptr(g_u), _ptr(g_r), _ptr(g_y),
-                                          _stream()), "dhts_macro_u_tap_bwd")
+    call("dhts_macro_u_tap_bwd", n=r.numel(), u_max=float(u_max), r=_ptr(r), y=_ptr(y), g_u=_ptr(g_u), g_r=_ptr(g_r), g_y=_ptr(g_y),
+         stream=_stream())
 
 
 def _det_i32(det, N):
@@ -194,14 +192,14 @@ def _macro_rollout_fwd(desc, T, r, y, u, ueq, ghost, ghost_name, sched, tape, er
         taps = _obs_buffer("taps", taps, (T, L, 3, D), r.device, new=_empty_rows)
     if out is None:
         out = tuple(torch.empty_like(r) for _ in range(4))
-    state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost))
-    outs = tuple(_ptr(o) for o in out)
+    args = dict(d=C.byref(desc), T=T, r=_ptr(r), y=_ptr(y), u=_ptr(u), ueq=_ptr(ueq), r_out=_ptr(out[0]), y_out=_ptr(out[1]),
+                u_out=_ptr(out[2]), ueq_out=_ptr(out[3]), tape=_ptr(tape), err=_ptr(err), stream=_stream())
+    args["ghost_sched" if sched and det is None else "ghost"] = _ptr(ghost)
     if det is not None:
-        check(_lib.lib().dhts_macro_rollout_fwd_taps(C.byref(desc), T, *state, int(sched), *outs, _ptr(tape), _ptr(det), D,
-                                                     _with_det(taps, det), _ptr(err), _stream()), "dhts_macro_rollout_fwd_taps")
+        args.update(ghost_is_sched=int(sched), det=_ptr(det), n_det=D, taps=_with_det(taps, det))
     else:
-        entry = "dhts_macro_rollout_fwd_sched" if sched else "dhts_macro_rollout_fwd"
-        check(getattr(_lib.lib(), entry)(C.byref(desc), T, *state, *outs, _ptr(tape), _ptr(hist), _ptr(err), _stream()), entry)
+        args["hist"] = _ptr(hist)
+    call("dhts_macro_rollout_fwd" + ("_taps" if det is not None else "_sched" if sched else ""), args)
     return out, taps
 
 
@@ -225,15 +223,14 @@ def _macro_rollout_bwd(desc, T, tape, g_r, g_y, sched, err, out, g_hist=None, de
         g_ghost = torch.empty(max(T, 1), L, 2, 2, dtype=torch.float64, device=g_r.device)      # every row is written
     elif g_ghost is None:
         g_ghost = torch.zeros(L, 2, 2, dtype=torch.float64, device=g_r.device)
-    grads = (_ptr(tape), _ptr(g_r), _ptr(g_y))
+    args = dict(d=C.byref(desc), T=T, tape=_ptr(tape), g_r=_ptr(g_r), g_y=_ptr(g_y), g_r_out=_ptr(out[0]), g_y_out=_ptr(out[1]),
+                err=_ptr(err), stream=_stream())
+    args["g_ghost_sched" if sched and det is None else "g_ghost"] = _ptr(g_ghost)
     if det is not None:
-        check(_lib.lib().dhts_macro_rollout_bwd_taps(C.byref(desc), T, *grads, _ptr(det), D, _with_det(g_taps, det),
-                                                     _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), int(bool(sched)), _ptr(err), _stream()),
-              "dhts_macro_rollout_bwd_taps")
+        args.update(ghost_is_sched=int(bool(sched)), det=_ptr(det), n_det=D, g_taps=_with_det(g_taps, det))
     else:
-        entry = "dhts_macro_rollout_bwd_sched" if sched else "dhts_macro_rollout_bwd"
-        check(getattr(_lib.lib(), entry)(C.byref(desc), T, *grads, _ptr(g_hist), _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err),
-                                         _stream()), entry)
+        args["g_hist"] = _ptr(g_hist)
+    call("dhts_macro_rollout_bwd" + ("_taps" if det is not None else "_sched" if sched else ""), args)
     return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
 
 
@@ -281,22 +278,22 @@ def macro_rollout_plan(desc, T, want_hist=False):
     """Which kernel instantiations dhts_macro_rollout_fwd / _bwd launch for this shape (include/dhts.h).
     fwd_kernel: 0 = two-phase lane kernel, 1 = one-phase, 2 = two-phase pair kernel."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_macro_rollout_plan(C.byref(desc), int(T), int(bool(want_hist)), C.byref(plan)), "dhts_macro_rollout_plan")
+    call("dhts_macro_rollout_plan", d=C.byref(desc), T=int(T), want_hist=int(bool(want_hist)), plan=C.byref(plan))
     return dict(zip(_MACRO_PLAN_KEYS, list(plan)))
 
 
 def macro_taps_plan(desc, T, n_det):
     """Which kernel instantiations dhts_macro_rollout_fwd_taps / _bwd_taps launch for this shape: the fields of macro_rollout_plan."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_macro_taps_plan(C.byref(desc), int(T), int(n_det), C.byref(plan)), "dhts_macro_taps_plan")
+    call("dhts_macro_taps_plan", d=C.byref(desc), T=int(T), n_det=int(n_det), plan=C.byref(plan))
     return dict(zip(_MACRO_PLAN_KEYS, list(plan)))
 
 
 def macro_tape_expand(desc, T, tape):
     """The reference's blocks dqs (dmacro_lane.py:56) of all T steps from a rollout tape: float32 [T][L][3][Np][4]."""
-    Np = _lib.lib().dhts_padded(desc.n_cells)
+    Np = raw("dhts_padded", n=desc.n_cells)
     dqs = torch.empty(int(T), desc.n_lanes, 3, Np, 4, dtype=torch.float32, device=tape.device)
-    check(_lib.lib().dhts_macro_tape_expand(C.byref(desc), int(T), _ptr(tape), _ptr(dqs), _stream()), "dhts_macro_tape_expand")
+    call("dhts_macro_tape_expand", d=C.byref(desc), T=int(T), tape=_ptr(tape), dqs_out=_ptr(dqs), stream=_stream())
     return dqs
 
 
@@ -795,8 +792,8 @@ def macro_state_from_ru_jvp(r, u, t_r, t_u, u_max):
     if not (r.shape == u.shape == t_r.shape == t_u.shape):
         raise ValueError("r, u, t_r and t_u must have one shape")
     t_y = torch.empty_like(r)
-    check(_lib.lib().dhts_macro_state_from_ru_jvp(r.numel(), float(u_max), _ptr(r), _ptr(u), _ptr(t_r), _ptr(t_u), _ptr(t_y), _stream()),
-          "dhts_macro_state_from_ru_jvp")
+    call("dhts_macro_state_from_ru_jvp", n=r.numel(), u_max=float(u_max), r=_ptr(r), u=_ptr(u), t_r=_ptr(t_r), t_u=_ptr(t_u), t_y=_ptr(t_y),
+         stream=_stream())
     return t_y
 
 
@@ -806,8 +803,8 @@ def macro_u_tap_jvp(r, y, t_r, t_y, u_max):
     if not (r.shape == y.shape == t_r.shape == t_y.shape):
         raise ValueError("r, y, t_r and t_y must have one shape")
     t_u = torch.empty_like(r)
-    check(_lib.lib().dhts_macro_u_tap_jvp(r.numel(), float(u_max), _ptr(r), _ptr(y), _ptr(t_r), _ptr(t_y), _ptr(t_u), _stream()),
-          "dhts_macro_u_tap_jvp")
+    call("dhts_macro_u_tap_jvp", n=r.numel(), u_max=float(u_max), r=_ptr(r), y=_ptr(y), t_r=_ptr(t_r), t_y=_ptr(t_y), t_u=_ptr(t_u),
+         stream=_stream())
     return t_u
 
 
@@ -859,9 +856,9 @@ def macro_rollout_jvp(desc, T, tape, t_r, t_y, t_ghost=None, det=None, err=None,
         raise ValueError("a sweep of T > 0 steps needs the rollout's tape")
     if out is None:
         out = (torch.empty_like(t_r), torch.empty_like(t_y))
-    check(_lib.lib().dhts_macro_rollout_jvp(C.byref(desc), T, _ptr(tape), K, _ptr(t_r), _ptr(t_y), _ptr(t_ghost), int(sched),
-                                            _ptr(out[0]), _ptr(out[1]), _ptr(det), D, _with_det(t_taps, det), _ptr(err), _stream()),
-          "dhts_macro_rollout_jvp")
+    call("dhts_macro_rollout_jvp", d=C.byref(desc), T=T, tape=_ptr(tape), n_dir=K, t_r=_ptr(t_r), t_y=_ptr(t_y), t_ghost=_ptr(t_ghost),
+         ghost_is_sched=int(sched), t_r_out=_ptr(out[0]), t_y_out=_ptr(out[1]), det=_ptr(det), n_det=D, t_taps=_with_det(t_taps, det),
+         err=_ptr(err), stream=_stream())
     return out[0], out[1], t_taps
 
 
@@ -872,7 +869,7 @@ def macro_jvp_plan(desc, T, n_dir, n_det=0):
     """What dhts_macro_rollout_jvp launches for this shape: kernel 0 = general, 1 = fast; its block; the directions of the widest launch;
     the number of launches (0 for T = 0)."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_macro_jvp_plan(C.byref(desc), int(T), int(n_dir), int(n_det), C.byref(plan)), "dhts_macro_jvp_plan")
+    call("dhts_macro_jvp_plan", d=C.byref(desc), T=int(T), n_dir=int(n_dir), n_det=int(n_det), plan=C.byref(plan))
     return dict(zip(_MACRO_JVP_PLAN_KEYS, list(plan)))
 
 
@@ -930,26 +927,15 @@ def macro_rollout_fwd_jvp(desc, T, r, y, u, ueq, ghost, t_r, t_y, t_ghost=None, 
             if not isinstance(t_inflow, torch.Tensor) or tuple(t_inflow.shape) != (K, T, L, R):
                 raise ValueError("t_inflow must have shape (%d, %d, %d, %d): the directions of t_r, then the shape of inflow" % (K, T, L, R))
             t_inflow = _f32c(t_inflow, "t_inflow")
-        tail = (_ptr(det), D, _with_det(taps, det), _with_det(t_taps, det), _ptr(err), _ptr(err_jvp), _stream(), _ptr(ramps), R,
-                _data(inflow), _data(t_inflow))
-        if ring:
-            check(_lib.lib().dhts_macro_rollout_fwd_jvp_ring_ramp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(t_r),
-                                                                  _ptr(t_y), *(_ptr(o) for o in out), *tail),
-                  "dhts_macro_rollout_fwd_jvp_ring_ramp")
-        else:
-            check(_lib.lib().dhts_macro_rollout_fwd_jvp_ramp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                             _ptr(t_r), _ptr(t_y), _ptr(t_ghost), *(_ptr(o) for o in out), *tail),
-                  "dhts_macro_rollout_fwd_jvp_ramp")
-        return (out[0], out[1], out[2], out[3], taps), (out[4], out[5], t_taps)
-    if ring:
-        check(_lib.lib().dhts_macro_rollout_fwd_jvp_ring(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(t_r), _ptr(t_y),
-                                                         *(_ptr(o) for o in out), _ptr(det), D, _with_det(taps, det), _with_det(t_taps, det),
-                                                         _ptr(err), _ptr(err_jvp), _stream()), "dhts_macro_rollout_fwd_jvp_ring")
-        return (out[0], out[1], out[2], out[3], taps), (out[4], out[5], t_taps)
-    check(_lib.lib().dhts_macro_rollout_fwd_jvp(C.byref(desc), T, K, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                _ptr(t_r), _ptr(t_y), _ptr(t_ghost), *(_ptr(o) for o in out), _ptr(det), D,
-                                                _with_det(taps, det), _with_det(t_taps, det), _ptr(err), _ptr(err_jvp), _stream()),
-          "dhts_macro_rollout_fwd_jvp")
+    args = dict(d=C.byref(desc), T=T, n_dir=K, r=_ptr(r), y=_ptr(y), u=_ptr(u), ueq=_ptr(ueq), t_r=_ptr(t_r), t_y=_ptr(t_y),
+                r_out=_ptr(out[0]), y_out=_ptr(out[1]), u_out=_ptr(out[2]), ueq_out=_ptr(out[3]), t_r_out=_ptr(out[4]), t_y_out=_ptr(out[5]),
+                det=_ptr(det), n_det=D, taps=_with_det(taps, det), t_taps=_with_det(t_taps, det), err=_ptr(err), err_jvp=_ptr(err_jvp),
+                stream=_stream())
+    if not ring:
+        args.update(ghost=_ptr(ghost), ghost_is_sched=int(sched), t_ghost=_ptr(t_ghost))
+    if ramps is not None:
+        args.update(ramps=_ptr(ramps), n_ramp=R, inflow=_data(inflow), t_inflow=_data(t_inflow))
+    call("dhts_macro_rollout_fwd_jvp" + ("_ring" if ring else "") + ("_ramp" if ramps is not None else ""), args)
     return (out[0], out[1], out[2], out[3], taps), (out[4], out[5], t_taps)
 
 
@@ -958,7 +944,7 @@ def macro_fwd_jvp_plan(desc, T, n_dir, n_det=0):
     direction slots of the widest launch (0: the lane does not fit), the number of launches (0 for T = 0 or when nothing fits) and the
     widest launch's dynamic LDS bytes.  Needs no device."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_macro_fwd_jvp_plan(C.byref(desc), int(T), int(n_dir), int(n_det), C.byref(plan)), "dhts_macro_fwd_jvp_plan")
+    call("dhts_macro_fwd_jvp_plan", d=C.byref(desc), T=int(T), n_dir=int(n_dir), n_det=int(n_det), plan=C.byref(plan))
     return dict(zip(_MACRO_FWD_JVP_PLAN_KEYS, list(plan)))
 
 
@@ -980,9 +966,9 @@ def _macro_ckpt_plan(entry, forms, desc, shape, segment):
     plan = (C.c_int32 * 8)()
     if not 0 <= int(segment) <= 0x7fffffff:
         raise ValueError("segment must be 0 (the plan's choice) or a positive int")
-    ask, shape = getattr(_lib.lib(), entry), tuple(int(v) for v in shape)
-    status = ask(C.byref(desc), *shape, int(segment), C.byref(plan))
-    if status == _lib.E_INVALID and int(segment) and ask(C.byref(desc), *shape, 0, C.byref(plan)) == 0:
+    args = dict(zip(("T", "n_det"), (int(v) for v in shape)), d=C.byref(desc), plan=C.byref(plan))
+    status = raw(entry, dict(args, segment=int(segment)))
+    if status == _lib.E_INVALID and int(segment) and raw(entry, dict(args, segment=0)) == 0:
         # the plan's own segment is accepted, so the descriptor, T and n_det are good and it is the segment that is not
         raise ValueError("segment must be 0 (the plan's choice) or 1 .. %s (%d) for lanes of %d cells" % (forms, plan[3], desc.n_cells))
     check(status, entry)
@@ -991,7 +977,7 @@ def _macro_ckpt_plan(entry, forms, desc, shape, segment):
 
 def macro_ckpt_numel(desc, T, segment=0):
     """float32 elements of the checkpoint buffer (opaque: the float32 (r, y) of every cell every `segment` steps, include/dhts.h)."""
-    return _lib.lib().dhts_macro_ckpt_bytes(C.byref(desc), int(T), int(segment)) // 4
+    return raw("dhts_macro_ckpt_bytes", d=C.byref(desc), T=int(T), segment=int(segment)) // 4
 
 
 def _macro_ckpt_args(desc, T, segment, ckpt, r, y, u, ueq, ghost):
@@ -1066,36 +1052,22 @@ def _macro_ckpt_fwd(form, desc, T, r, y, u, ueq, ghost, ckpt, segment, err, out,
         raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = tuple(torch.empty_like(r) for _ in range(4))
+    ring = ghost is None
     if ramps is not None:
         ramps, R, inflow = _macro_ramp_args(desc, T, ramps, inflow)
-        head = (C.byref(desc), T, int(segment), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched), _ptr(out[0]), _ptr(out[1]),
-                _ptr(out[2]), _ptr(out[3]))
-        tail = (_ptr(ramps), R, _data(inflow), int(ghost is None), _ptr(err), _stream())
-        if fit:
-            check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target_ramp(*head, _data(ckpt), _data(target), _ptr(sse), *tail),
-                  "dhts_macro_rollout_fwd_ckpt_target_ramp")
-            return out, sse
-        check(_lib.lib().dhts_macro_rollout_fwd_ckpt_ramp(*head, _ptr(det), D, _with_det(taps, det), _data(ckpt), *tail),
-              "dhts_macro_rollout_fwd_ckpt_ramp")
-        return out, taps
-    if ghost is None:
-        state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]))
-        if fit:
-            check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target_ring(C.byref(desc), T, segment, *state, _data(ckpt), _data(target), _ptr(sse),
-                                                                     _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt_target_ring")
-            return out, sse
-        check(_lib.lib().dhts_macro_rollout_fwd_ckpt_ring(C.byref(desc), T, int(segment), *state, _ptr(det), D, _with_det(taps, det), _data(ckpt),
-                                                          _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt_ring")
-        return out, taps
+    # the family's arguments by name, each group where a sibling takes it: the boundary cells, the fit or the detectors, the ramps
+    args = dict(d=C.byref(desc), T=T, segment=int(segment), r=_ptr(r), y=_ptr(y), u=_ptr(u), ueq=_ptr(ueq), r_out=_ptr(out[0]),
+                y_out=_ptr(out[1]), u_out=_ptr(out[2]), ueq_out=_ptr(out[3]), ckpt=_data(ckpt), err=_ptr(err), stream=_stream())
+    if not ring or ramps is not None:
+        args.update(ghost=_ptr(ghost), ghost_is_sched=int(sched))
     if fit:
-        check(_lib.lib().dhts_macro_rollout_fwd_ckpt_target(C.byref(desc), T, segment, _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _data(ckpt), _data(target),
-                                                            _ptr(sse), _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt_target")
-        return out, sse
-    check(_lib.lib().dhts_macro_rollout_fwd_ckpt(C.byref(desc), T, int(segment), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched),
-                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(det), D, _with_det(taps, det),
-                                                 _data(ckpt), _ptr(err), _stream()), "dhts_macro_rollout_fwd_ckpt")
-    return out, taps
+        args.update(target=_data(target), sse=_ptr(sse))
+    else:
+        args.update(det=_ptr(det), n_det=D, taps=_with_det(taps, det))
+    if ramps is not None:
+        args.update(ramps=_ptr(ramps), n_ramp=R, inflow=_data(inflow), ring=int(ring))
+    call("dhts_macro_rollout_fwd_ckpt" + ("_target" if fit else "") + ("_ramp" if ramps is not None else "_ring" if ring else ""), args)
+    return out, (sse if fit else taps)
 
 
 def _macro_ckpt_bwd(form, desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment, err, out, det=None, g_taps=None, target=None, g_sse=None,
@@ -1135,59 +1107,33 @@ def _macro_ckpt_bwd(form, desc, T, ckpt, r, y, u, ueq, ghost, g_r, g_y, segment,
         raise TypeError("target is not a CUDA tensor")
     if out is None:
         out = (torch.empty_like(g_r), torch.empty_like(g_y))
+    ring = ghost is None
     if ramps is not None:
         ramps, R, inflow, g_inflow = _macro_ramp_args(desc, T, ramps, inflow, g_inflow, True)
-        if ghost is None and g_ghost is not None:
-            raise ValueError("a ring has no boundary cells and no g_ghost")
-        if ghost is not None:
-            want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
-            if g_ghost is None:
-                g_ghost = (torch.empty if sched else torch.zeros)(want, dtype=torch.float64, device=g_r.device)
-            elif tuple(g_ghost.shape) != want or g_ghost.dtype != torch.float64 or not g_ghost.is_contiguous():
-                raise ValueError("g_ghost must be a contiguous float64 tensor of shape %s" % (want,))
-            elif not sched:
-                g_ghost.zero_()
-        head = (C.byref(desc), T, int(segment), _data(ckpt), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost), int(sched), _ptr(g_r),
-                _ptr(g_y))
-        tail = (_ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(ramps), R, _data(inflow), _data(g_inflow), int(ghost is None), _ptr(err),
-                _stream())
-        if fit:
-            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target_ramp(*head, _data(target), _ptr(g_sse), _ptr(final[0]), _ptr(final[1]),
-                                                                     _ptr(final[2]), *tail), "dhts_macro_rollout_bwd_ckpt_target_ramp")
-        else:
-            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_ramp(*head, _ptr(det), D, _with_det(g_taps, det), *tail),
-                  "dhts_macro_rollout_bwd_ckpt_ramp")
-        return out[0], out[1], (None if ghost is None else (g_ghost[:T] if sched else g_ghost)), g_inflow
-    if ghost is None:
+    if ring:
         if g_ghost is not None:
             raise ValueError("a ring has no boundary cells and no g_ghost")
-        state = (_ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(g_r), _ptr(g_y))
-        if fit:
-            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target_ring(C.byref(desc), T, segment, _data(ckpt), *state, _data(target), _ptr(g_sse),
-                                                                     _ptr(final[0]), _ptr(final[1]), _ptr(final[2]), _ptr(out[0]), _ptr(out[1]),
-                                                                     _ptr(err), _stream()), "dhts_macro_rollout_bwd_ckpt_target_ring")
-        else:
-            check(_lib.lib().dhts_macro_rollout_bwd_ckpt_ring(C.byref(desc), T, int(segment), _data(ckpt), *state, _ptr(det), D,
-                                                              _with_det(g_taps, det), _ptr(out[0]), _ptr(out[1]), _ptr(err), _stream()),
-                  "dhts_macro_rollout_bwd_ckpt_ring")
-        return out[0], out[1], None
-    want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
-    if g_ghost is None:              # (a schedule's: every row is written; the sums are added to)
-        g_ghost = (torch.empty if sched else torch.zeros)(want, dtype=torch.float64, device=g_r.device)
-    elif tuple(g_ghost.shape) != want or g_ghost.dtype != torch.float64 or not g_ghost.is_contiguous():
-        raise ValueError("g_ghost must be a contiguous float64 tensor of shape %s" % (want,))
-    elif not sched:
-        g_ghost.zero_()
-    if fit:
-        check(_lib.lib().dhts_macro_rollout_bwd_ckpt_target(C.byref(desc), T, segment, _data(ckpt), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost),
-                                                            int(sched), _ptr(g_r), _ptr(g_y), _data(target), _ptr(g_sse), _ptr(final[0]),
-                                                            _ptr(final[1]), _ptr(final[2]), _ptr(out[0]), _ptr(out[1]), _ptr(g_ghost), _ptr(err),
-                                                            _stream()), "dhts_macro_rollout_bwd_ckpt_target")
     else:
-        check(_lib.lib().dhts_macro_rollout_bwd_ckpt(C.byref(desc), T, int(segment), _data(ckpt), _ptr(r), _ptr(y), _ptr(u), _ptr(ueq), _ptr(ghost),
-                                                     int(sched), _ptr(g_r), _ptr(g_y), _ptr(det), D, _with_det(g_taps, det), _ptr(out[0]),
-                                                     _ptr(out[1]), _ptr(g_ghost), _ptr(err), _stream()), "dhts_macro_rollout_bwd_ckpt")
-    return out[0], out[1], (g_ghost[:T] if sched else g_ghost)
+        want = (max(T, 1), L, 2, 2) if sched else (L, 2, 2)
+        if g_ghost is None:              # (a schedule's: every row is written; the sums are added to)
+            g_ghost = (torch.empty if sched else torch.zeros)(want, dtype=torch.float64, device=g_r.device)
+        elif tuple(g_ghost.shape) != want or g_ghost.dtype != torch.float64 or not g_ghost.is_contiguous():
+            raise ValueError("g_ghost must be a contiguous float64 tensor of shape %s" % (want,))
+        elif not sched:
+            g_ghost.zero_()
+    args = dict(d=C.byref(desc), T=T, segment=int(segment), ckpt=_data(ckpt), r=_ptr(r), y=_ptr(y), u=_ptr(u), ueq=_ptr(ueq), g_r=_ptr(g_r),
+                g_y=_ptr(g_y), g_r_out=_ptr(out[0]), g_y_out=_ptr(out[1]), err=_ptr(err), stream=_stream())
+    if not ring or ramps is not None:
+        args.update(ghost=_ptr(ghost), ghost_is_sched=int(sched), g_ghost=_ptr(g_ghost))
+    if fit:
+        args.update(target=_data(target), g_sse=_ptr(g_sse), r_fin=_ptr(final[0]), y_fin=_ptr(final[1]), u_fin=_ptr(final[2]))
+    else:
+        args.update(det=_ptr(det), n_det=D, g_taps=_with_det(g_taps, det))
+    if ramps is not None:
+        args.update(ramps=_ptr(ramps), n_ramp=R, inflow=_data(inflow), g_inflow=_data(g_inflow), ring=int(ring))
+    call("dhts_macro_rollout_bwd_ckpt" + ("_target" if fit else "") + ("_ramp" if ramps is not None else "_ring" if ring else ""), args)
+    g_ghost = None if ring else g_ghost[:T] if sched else g_ghost
+    return (out[0], out[1], g_ghost) + ((g_inflow,) if ramps is not None else ())
 
 
 def macro_rollout_fwd_ckpt(desc, T, r, y, u, ueq, ghost, ckpt, segment=0, det=None, err=None, out=None, taps=None):
@@ -1308,18 +1254,18 @@ def micro_desc(L, V, dt):
 
 def micro_tape_numel(desc, T):
     """float32 elements of the rollout tape (second rows of dEgo / dLeading)."""
-    return _lib.lib().dhts_micro_tape_bytes(C.byref(desc), int(T)) // 4
+    return raw("dhts_micro_tape_bytes", d=C.byref(desc), T=int(T)) // 4
 
 
 def micro_param_tape_numel(desc, T):
     """float32 elements of the parameter tape of a rollout that is differentiated w.r.t. the driver parameters (opaque: a header, the
     head gaps and 8 bytes per vehicle-step, include/dhts.h)."""
-    return _lib.lib().dhts_micro_param_tape_bytes(C.byref(desc), int(T)) // 4
+    return raw("dhts_micro_param_tape_bytes", d=C.byref(desc), T=int(T)) // 4
 
 
 def micro_step_tape_numel(desc):
     """float32 elements of the single-step operator's tape (the reference's dqs)."""
-    return _lib.lib().dhts_micro_step_tape_bytes(C.byref(desc)) // 4
+    return raw("dhts_micro_step_tape_bytes", d=C.byref(desc)) // 4
 
 
 def micro_step_fwd(desc, p, v, params, head, count=None, tape=None, err=None, tensor_ladder=False, head_tensor=False):
@@ -1328,10 +1274,9 @@ def micro_step_fwd(desc, p, v, params, head, count=None, tape=None, err=None, te
     lanes' head gaps are float32 tensors there (dMicroLane under a tensor gap: dhts_micro_step_fwd_tensor_head)."""
     p, v = _f32c(p, "p"), _f32c(v, "v")
     out = (torch.empty_like(p), torch.empty_like(v))
-    lib = _lib.lib()
-    fn = lib.dhts_micro_step_fwd_tensor if tensor_ladder else (lib.dhts_micro_step_fwd_tensor_head if head_tensor else lib.dhts_micro_step_fwd)
-    check(fn(C.byref(desc), _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
-             _ptr(out[0]), _ptr(out[1]), _ptr(tape), _ptr(err), _stream()), "dhts_micro_step_fwd")
+    entry = "dhts_micro_step_fwd" + ("_tensor" if tensor_ladder else "_tensor_head" if head_tensor else "")
+    check(raw(entry, d=C.byref(desc), p=_ptr(p), v=_ptr(v), count=_ptr(count), params=_ptr(params), head=_ptr(head), p_out=_ptr(out[0]),
+              v_out=_ptr(out[1]), tape=_ptr(tape), err=_ptr(err), stream=_stream()), "dhts_micro_step_fwd")
     return out
 
 
@@ -1351,16 +1296,11 @@ def micro_rollout_fwd(desc, T, p, v, params, head, count=None, tape=None, hist=N
     params, head = params.contiguous(), head.contiguous()
     if out is None:
         out = (torch.empty_like(p), torch.empty_like(v))
-    if ptape is not None:
-        if ptape.dtype != torch.float32 or ptape.numel() != micro_param_tape_numel(desc, T):
-            raise ValueError("ptape must be float32 [micro_param_tape_numel(desc, T)]")
-        check(_lib.lib().dhts_micro_rollout_fwd_params(C.byref(desc), int(T), _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
-                                                       _ptr(out[0]), _ptr(out[1]), _ptr(tape), _ptr(ptape), _ptr(hist), _ptr(err),
-                                                       _stream()), "dhts_micro_rollout_fwd_params")
-        return out
-    check(_lib.lib().dhts_micro_rollout_fwd(C.byref(desc), int(T), _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head),
-                                            _ptr(out[0]), _ptr(out[1]), _ptr(tape), _ptr(hist), _ptr(err), _stream()),
-          "dhts_micro_rollout_fwd")
+    if ptape is not None and (ptape.dtype != torch.float32 or ptape.numel() != micro_param_tape_numel(desc, T)):
+        raise ValueError("ptape must be float32 [micro_param_tape_numel(desc, T)]")
+    call("dhts_micro_rollout_fwd" + ("_params" if ptape is not None else ""),
+         dict(d=C.byref(desc), T=int(T), p=_ptr(p), v=_ptr(v), count=_ptr(count), params=_ptr(params), head=_ptr(head), p_out=_ptr(out[0]),
+              v_out=_ptr(out[1]), tape=_ptr(tape), ptape=_ptr(ptape), hist=_ptr(hist), err=_ptr(err), stream=_stream()))
     return out
 
 
@@ -1373,7 +1313,8 @@ def micro_rollout_bwd(desc, T, tape, g_p, g_v, count=None, g_hist=None, err=None
         out = (torch.empty_like(g_p), torch.empty_like(g_v))
     if g_head is None:
         g_head = torch.zeros(desc.n_lanes, 2, dtype=torch.float64, device=g_p.device)
-    if ptape is not None or params is not None or g_params is not None:
+    with_params = ptape is not None or params is not None or g_params is not None
+    if with_params:
         L, V = desc.n_lanes, desc.capacity
         if ptape is None or params is None or g_params is None:
             raise ValueError("ptape, params and g_params go together")
@@ -1382,20 +1323,17 @@ def micro_rollout_bwd(desc, T, tape, g_p, g_v, count=None, g_hist=None, err=None
         for name, t in (("params", params), ("g_params", g_params)):
             if t.dtype != torch.float64 or tuple(t.shape) != (6, L, V) or not t.is_contiguous():
                 raise ValueError("%s must be a contiguous float64 [6][L][V]" % name)
-        check(_lib.lib().dhts_micro_rollout_bwd_params(C.byref(desc), int(T), _ptr(tape), _ptr(ptape), _ptr(count), _ptr(params),
-                                                       _ptr(g_p), _ptr(g_v), _ptr(g_hist), _ptr(out[0]), _ptr(out[1]), _ptr(g_head),
-                                                       _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_params")
-        return out[0], out[1], g_head
-    check(_lib.lib().dhts_micro_rollout_bwd(C.byref(desc), int(T), _ptr(tape), _ptr(count), _ptr(g_p), _ptr(g_v),
-                                            _ptr(g_hist), _ptr(out[0]), _ptr(out[1]), _ptr(g_head), _ptr(err), _stream()),
-          "dhts_micro_rollout_bwd")
+    call("dhts_micro_rollout_bwd" + ("_params" if with_params else ""),
+         dict(d=C.byref(desc), T=int(T), tape=_ptr(tape), ptape=_ptr(ptape), count=_ptr(count), params=_ptr(params), g_p=_ptr(g_p),
+              g_v=_ptr(g_v), g_hist=_ptr(g_hist), g_p_out=_ptr(out[0]), g_v_out=_ptr(out[1]), g_head=_ptr(g_head), g_params=_ptr(g_params),
+              err=_ptr(err), stream=_stream()))
     return out[0], out[1], g_head
 
 
 def micro_rollout_plan(desc, T, has_count=False):
     """Which kernel instantiations dhts_micro_rollout_fwd / _bwd launch for this shape (include/dhts.h)."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_micro_rollout_plan(C.byref(desc), int(T), int(bool(has_count)), C.byref(plan)), "dhts_micro_rollout_plan")
+    call("dhts_micro_rollout_plan", d=C.byref(desc), T=int(T), has_count=int(bool(has_count)), plan=C.byref(plan))
     keys = ("fwd_waves", "fwd_passes", "fwd_full_lane", "bwd_one_vehicle_per_thread", "bwd_block")
     return dict(zip(keys, list(plan)[:5]))
 
@@ -1404,7 +1342,7 @@ def micro_param_plan(desc, T, has_count=False):
     """The same plan's entries for the rollout that is differentiated w.r.t. the driver parameters: bytes per vehicle-step of its
     parameter tape (8 = the pre-step state; the reverse sweep recomputes the partials) and the block size of its reverse sweep."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_micro_rollout_plan(C.byref(desc), int(T), int(bool(has_count)), C.byref(plan)), "dhts_micro_rollout_plan")
+    call("dhts_micro_rollout_plan", d=C.byref(desc), T=int(T), has_count=int(bool(has_count)), plan=C.byref(plan))
     return dict(param_tape_bytes=plan[5], param_bwd_block=plan[6])
 
 
@@ -1443,9 +1381,9 @@ def micro_rollout_jvp(desc, T, tape, t_p, t_v, count=None, t_head=None, ptape=No
     if out is None:
         out = (torch.empty_like(t_p), torch.empty_like(t_v))
     hist_ptr = None if t_hist is None or not t_hist.numel() else _ptr(t_hist)      # (T = 0: no row, and an empty tensor has no address)
-    check(_lib.lib().dhts_micro_rollout_jvp(C.byref(desc), T, K, _ptr(tape) if T > 0 else None, _ptr(ptape), _ptr(count), _ptr(params),
-                                            _ptr(t_p), _ptr(t_v), _ptr(t_head), _ptr(t_params), _ptr(out[0]), _ptr(out[1]), hist_ptr,
-                                            _ptr(err), _stream()), "dhts_micro_rollout_jvp")
+    call("dhts_micro_rollout_jvp", d=C.byref(desc), T=T, n_dir=K, tape=_ptr(tape) if T > 0 else None, ptape=_ptr(ptape), count=_ptr(count),
+         params=_ptr(params), t_p=_ptr(t_p), t_v=_ptr(t_v), t_head=_ptr(t_head), t_params=_ptr(t_params), t_p_out=_ptr(out[0]),
+         t_v_out=_ptr(out[1]), t_hist=hist_ptr, err=_ptr(err), stream=_stream())
     return out[0], out[1], t_hist
 
 
@@ -1456,7 +1394,7 @@ def micro_jvp_plan(desc, T, n_dir, want_params=False):
     """What dhts_micro_rollout_jvp launches for this shape: its block (one vehicle per thread), the direction slots of the widest launch,
     the number of launches and the widest launch's dynamic LDS bytes."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_micro_jvp_plan(C.byref(desc), int(T), int(n_dir), int(bool(want_params)), C.byref(plan)), "dhts_micro_jvp_plan")
+    call("dhts_micro_jvp_plan", d=C.byref(desc), T=int(T), n_dir=int(n_dir), want_params=int(bool(want_params)), plan=C.byref(plan))
     return dict(zip(_MICRO_JVP_PLAN_KEYS, list(plan)))
 
 
@@ -1476,8 +1414,7 @@ def micro_fwd_jvp_gn_plan(desc, T, n_dir, want_params=False):
     widest kernel held for the lane (no scratch, no spill), launches 0 where that width cannot carry n_dir -- then pair_block, the
     directions per block of the pair-of-blocks scheme, and block_bound, the block size the widest launch's kernel is compiled for."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_micro_fwd_jvp_gn_plan(C.byref(desc), int(T), int(n_dir), int(bool(want_params)), C.byref(plan)),
-          "dhts_micro_fwd_jvp_gn_plan")
+    call("dhts_micro_fwd_jvp_gn_plan", d=C.byref(desc), T=int(T), n_dir=int(n_dir), want_params=int(bool(want_params)), plan=C.byref(plan))
     return dict(zip(_MICRO_JVP_PLAN_KEYS + ("pair_block", "block_bound"), list(plan)))
 
 
@@ -1519,8 +1456,7 @@ def micro_rollout_fwd_jvp_gn(desc, T, p, v, params, t_p, t_v, target, head=None,
 def micro_fwd_jvp_plan(desc, T, n_dir, want_params=False):
     """What dhts_micro_rollout_fwd_jvp launches for this shape: the keys of micro_jvp_plan."""
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_micro_fwd_jvp_plan(C.byref(desc), int(T), int(n_dir), int(bool(want_params)), C.byref(plan)),
-          "dhts_micro_fwd_jvp_plan")
+    call("dhts_micro_fwd_jvp_plan", d=C.byref(desc), T=int(T), n_dir=int(n_dir), want_params=int(bool(want_params)), plan=C.byref(plan))
     return dict(zip(_MICRO_JVP_PLAN_KEYS, list(plan)))
 
 
@@ -1538,7 +1474,7 @@ def micro_ckpt_plan(desc, T, want_params=False, segment=0):
 
 def micro_ckpt_numel(desc, T, segment=0):
     """float32 elements of the checkpoint buffer (opaque: the float32 (p, v) of every slot every `segment` steps, include/dhts.h)."""
-    return _lib.lib().dhts_micro_ckpt_bytes(C.byref(desc), int(T), int(segment)) // 4
+    return raw("dhts_micro_ckpt_bytes", d=C.byref(desc), T=int(T), segment=int(segment)) // 4
 
 
 # ---- the tape-free paths' raw layer: every check once, then _micro_ckpt_fwd / _micro_ckpt_bwd / _micro_fwd_jvp for every form -----------
@@ -1552,7 +1488,7 @@ def _micro_ckpt_plan(entry, forms, desc, T, want_params, segment):
     plan = (C.c_int32 * 8)()
     if not 0 <= int(segment) <= 0x7fffffff:
         raise ValueError("segment must be 0 (the plan's choice) or a positive int")
-    status = getattr(_lib.lib(), entry)(C.byref(desc), int(T), int(bool(want_params)), int(segment), C.byref(plan))
+    status = raw(entry, d=C.byref(desc), T=int(T), want_params=int(bool(want_params)), segment=int(segment), plan=C.byref(plan))
     if status == _lib.E_INVALID and int(T) >= 0:
         raise ValueError("segment must be 0 (the plan's choice) or 1 .. max_segment%s for %d vehicle slots%s" %
                          (forms, desc.capacity, " with the parameter gradient" if want_params else ""))
@@ -1692,32 +1628,25 @@ def _micro_ckpt_fwd(form, desc, T, p, v, params, ckpt, count, segment, err, out,
             raise ValueError("sse must be a contiguous float64 tensor of shape (%d, 2)" % L)
     if out is None:
         out = (torch.empty_like(p), torch.empty_like(v))
-    # include/dhts.h: desc T segment p v count params | head, or lead lead_length, or all three, or ring | p_out v_out ckpt | observed |
-    # err stream
-    lib, a, z = _lib.lib(), (C.byref(desc), int(T), S, _ptr(p), _ptr(v), _ptr(count), _ptr(params)), (_ptr(out[0]), _ptr(out[1]), _data(ckpt))
-    if form == "hist":
-        check(lib.dhts_micro_rollout_fwd_ckpt(*a, _ptr(head), *z, _data(hist), _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt")
-        return out, None
-    if form == "samples":
-        check(lib.dhts_micro_rollout_fwd_ckpt_samples(*a, _ptr(head), *z, _ptr(probes), n_probes, every, _data(samples), _ptr(err), _stream()),
-              "dhts_micro_rollout_fwd_ckpt_samples")
-        return out, samples
-    if form == "lead":
-        check(lib.dhts_micro_rollout_fwd_ckpt_lead(*a, _data(lead), _ptr(lead_length), *z, _ptr(probes), n_probes, every, _data(samples),
-                                                   _ptr(err), _stream()), "dhts_micro_rollout_fwd_ckpt_lead")
-        return out, samples
-    if form == "ring":
-        check(lib.dhts_micro_rollout_fwd_ckpt_ring(*a, _ptr(ring), *z, _ptr(probes), n_probes, every, _data(samples), _ptr(err), _stream()),
-              "dhts_micro_rollout_fwd_ckpt_ring")
-        return out, samples
-    if ring is not None:
-        check(lib.dhts_micro_rollout_fwd_ckpt_target_ring(*a, _ptr(ring), *z, _data(target), _ptr(sse), _ptr(err), _stream()),
-              "dhts_micro_rollout_fwd_ckpt_target_ring")
-        return out, sse
-    # (a T = 0 call with lead: no row exists; the library takes the lead form from the NULL head)
-    check(lib.dhts_micro_rollout_fwd_ckpt_target(*a, _ptr(head), _data(lead), _ptr(lead_length), *z, _data(target), _ptr(sse), _ptr(err),
-                                                 _stream()), "dhts_micro_rollout_fwd_ckpt_target")
-    return out, sse
+    # (a T = 0 call of the target form with lead: no row exists; the library takes the lead form from the NULL head)
+    # the family's arguments by name, each group where a sibling takes it: what the head vehicle follows, what is observed
+    on_ring = form == "ring" or (form == "target" and ring is not None)
+    args = dict(d=C.byref(desc), T=int(T), segment=S, p=_ptr(p), v=_ptr(v), count=_ptr(count), params=_ptr(params), p_out=_ptr(out[0]),
+                v_out=_ptr(out[1]), ckpt=_data(ckpt), err=_ptr(err), stream=_stream())
+    if on_ring:
+        args["ring"] = _ptr(ring)
+    if not on_ring and form != "lead":
+        args["head"] = _ptr(head)
+    if form == "lead" or (form == "target" and not on_ring):
+        args.update(lead=_data(lead), lead_length=_ptr(lead_length))
+    if sampled:
+        args.update(probes=_ptr(probes), n_probes=n_probes, every=every, samples=_data(samples))
+    elif form == "target":
+        args.update(target=_data(target), sse=_ptr(sse))
+    else:
+        args["hist"] = _data(hist)
+    call("dhts_micro_rollout_fwd_ckpt" + ("" if form == "hist" else "_target_ring" if form == "target" and on_ring else "_" + form), args)
+    return out, (sse if form == "target" else samples if sampled else None)
 
 
 def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, out, g_params, head=None, g_head=None, g_hist=None,
@@ -1766,29 +1695,22 @@ def _micro_ckpt_bwd(form, desc, T, ckpt, params, g_p, g_v, count, segment, err, 
             g_lead = torch.empty(int(T), L, 2, dtype=torch.float32, device=g_p.device)
         elif g_lead.dtype != torch.float32 or tuple(g_lead.shape) != (int(T), L, 2) or not g_lead.is_contiguous():
             raise ValueError("g_lead must be a contiguous float32 tensor of shape (%d, %d, 2)" % (int(T), L))
-    # include/dhts.h: desc T segment ckpt count params | head, or lead lead_length, or all three, or ring | g_p g_v | observed |
-    # g_p_out g_v_out | g_head, or g_lead, or both, or neither | g_params err stream
-    lib, a = _lib.lib(), (C.byref(desc), int(T), S, _data(ckpt), _ptr(count), _ptr(params))
-    g, z = (_ptr(g_p), _ptr(g_v)), (_ptr(out[0]), _ptr(out[1]))
-    if form == "hist":
-        check(lib.dhts_micro_rollout_bwd_ckpt(*a, _ptr(head), *g, _ptr(g_hist), *z, _ptr(g_head), _ptr(g_params), _ptr(err), _stream()),
-              "dhts_micro_rollout_bwd_ckpt")
-    elif form == "samples":
-        check(lib.dhts_micro_rollout_bwd_ckpt_samples(*a, _ptr(head), *g, _ptr(probes), n_probes, every, _data(g_samples), *z, _ptr(g_head),
-                                                      _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_samples")
-    elif form == "lead":
-        check(lib.dhts_micro_rollout_bwd_ckpt_lead(*a, _data(lead), _ptr(lead_length), *g, _ptr(probes), n_probes, every, _data(g_samples), *z,
-                                                   _data(g_lead), _ptr(g_params), _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_lead")
-    elif form == "ring":
-        check(lib.dhts_micro_rollout_bwd_ckpt_ring(*a, _ptr(ring), *g, _ptr(probes), n_probes, every, _data(g_samples), *z, _ptr(g_params),
-                                                   _ptr(err), _stream()), "dhts_micro_rollout_bwd_ckpt_ring")
-    elif ring is not None:
-        check(lib.dhts_micro_rollout_bwd_ckpt_target_ring(*a, _ptr(ring), *g, _data(target), _ptr(g_sse), *z, _ptr(g_params), _ptr(err),
-                                                          _stream()), "dhts_micro_rollout_bwd_ckpt_target_ring")
+    on_ring = form == "ring" or (form == "target" and ring is not None)
+    args = dict(d=C.byref(desc), T=int(T), segment=S, ckpt=_data(ckpt), count=_ptr(count), params=_ptr(params), g_p=_ptr(g_p), g_v=_ptr(g_v),
+                g_p_out=_ptr(out[0]), g_v_out=_ptr(out[1]), g_params=_ptr(g_params), err=_ptr(err), stream=_stream())
+    if on_ring:
+        args["ring"] = _ptr(ring)
+    if not on_ring and form != "lead":
+        args.update(head=_ptr(head), g_head=_ptr(g_head))
+    if form == "lead" or (form == "target" and not on_ring):
+        args.update(lead=_data(lead), lead_length=_ptr(lead_length), g_lead=_data(g_lead))
+    if sampled:
+        args.update(probes=_ptr(probes), n_probes=n_probes, every=every, g_samples=_data(g_samples))
+    elif form == "target":
+        args.update(target=_data(target), g_sse=_ptr(g_sse))
     else:
-        check(lib.dhts_micro_rollout_bwd_ckpt_target(*a, _ptr(head), _data(lead), _ptr(lead_length), *g, _data(target), _ptr(g_sse), *z,
-                                                     _ptr(g_head), _data(g_lead), _ptr(g_params), _ptr(err), _stream()),
-              "dhts_micro_rollout_bwd_ckpt_target")
+        args["g_hist"] = _ptr(g_hist)
+    call("dhts_micro_rollout_bwd_ckpt" + ("" if form == "hist" else "_target_ring" if form == "target" and on_ring else "_" + form), args)
     return out[0], out[1], (None if ring is not None else g_head if lead is None else g_lead)
 
 
@@ -1846,38 +1768,32 @@ def _micro_fwd_jvp(form, desc, T, p, v, params, t_p, t_v, count, t_params, err, 
         state = _state_out(("p_out", "v_out", "t_p_out", "t_v_out"), out, (p, v, t_p, t_v))
         sse = torch.zeros(L, 2, dtype=torch.float64, device=p.device)
         jtr, jtj = torch.zeros(L, K, dtype=torch.float64, device=p.device), torch.zeros(L, K, K, dtype=torch.float64, device=p.device)
-        # include/dhts.h: desc T n_dir p v count params | head lead lead_length ring | t_p t_v t_head t_lead t_params | the four outputs |
-        # probes n_probes every | target sse jtr jtj | err err_jvp stream
-        check(_lib.lib().dhts_micro_rollout_fwd_jvp_gn(
-            C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params), _ptr(head), _data(lead), _ptr(lead_length), _ptr(ring),
-            _ptr(t_p), _ptr(t_v), _ptr(t_head), _data(t_lead), _ptr(t_params), _ptr(state[0]), _ptr(state[1]), _ptr(state[2]),
-            _ptr(state[3]), _ptr(probes), n_probes, every, _data(target), _ptr(sse), _ptr(jtr), _ptr(jtj), _ptr(err), _ptr(err_jvp),
-            _stream()), "dhts_micro_rollout_fwd_jvp_gn")
-        return (state[0], state[1], sse), (state[2], state[3], jtr, jtj)
-    names = ("samples", "t_samples") if sampled else ("hist", "t_hist")
-    if len(out) not in (0, 4, 6) or (len(out) == 6 and not observe):
-        raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, %s, %s])" % names)
-    shape = (rows, L, 2, n) if sampled else (T, L, 2, V)
-    new = (torch.zeros if observe else None) if sampled else (torch.empty if want_hist else None)
-    obs = [_obs_buffer(name, t, shp, p.device, new) for name, t, shp in zip(names, out[4:6] or (None, None), (shape, (K,) + shape))]
-    state = _state_out(("p_out", "v_out", "t_p_out", "t_v_out"), out, (p, v, t_p, t_v))
-    # include/dhts.h: desc T n_dir p v count params | head, or lead lead_length, or ring | t_p t_v | t_head, or t_lead, or neither |
-    # t_params | the four outputs |
-    # probes n_probes every (sampled) | the two observed arrays | err err_jvp stream
-    lib, a, t = _lib.lib(), (C.byref(desc), T, K, _ptr(p), _ptr(v), _ptr(count), _ptr(params)), (_ptr(t_p), _ptr(t_v))
-    z = (_ptr(state[0]), _ptr(state[1]), _ptr(state[2]), _ptr(state[3]))
-    e = (_data(obs[0]), _data(obs[1]), _ptr(err), _ptr(err_jvp), _stream())
-    if form == "hist":
-        check(lib.dhts_micro_rollout_fwd_jvp(*a, _ptr(head), *t, _ptr(t_head), _ptr(t_params), *z, *e), "dhts_micro_rollout_fwd_jvp")
-    elif form == "samples":
-        check(lib.dhts_micro_rollout_fwd_jvp_samples(*a, _ptr(head), *t, _ptr(t_head), _ptr(t_params), *z, _ptr(probes), n_probes, every, *e),
-              "dhts_micro_rollout_fwd_jvp_samples")
-    elif form == "ring":
-        check(lib.dhts_micro_rollout_fwd_jvp_ring(*a, _ptr(ring), *t, _ptr(t_params), *z, _ptr(probes), n_probes, every, *e),
-              "dhts_micro_rollout_fwd_jvp_ring")
+        observed = dict(target=_data(target), sse=_ptr(sse), jtr=_ptr(jtr), jtj=_ptr(jtj))
     else:
-        check(lib.dhts_micro_rollout_fwd_jvp_lead(*a, _data(lead), _ptr(lead_length), *t, _data(t_lead), _ptr(t_params), *z, _ptr(probes),
-                                                  n_probes, every, *e), "dhts_micro_rollout_fwd_jvp_lead")
+        names = ("samples", "t_samples") if sampled else ("hist", "t_hist")
+        if len(out) not in (0, 4, 6) or (len(out) == 6 and not observe):
+            raise ValueError("out must be (p_out, v_out, t_p_out, t_v_out[, %s, %s])" % names)
+        shape = (rows, L, 2, n) if sampled else (T, L, 2, V)
+        new = (torch.zeros if observe else None) if sampled else (torch.empty if want_hist else None)
+        obs = [_obs_buffer(name, t, shp, p.device, new) for name, t, shp in zip(names, out[4:6] or (None, None), (shape, (K,) + shape))]
+        state = _state_out(("p_out", "v_out", "t_p_out", "t_v_out"), out, (p, v, t_p, t_v))
+        observed = {names[0]: _data(obs[0]), names[1]: _data(obs[1])}
+    # the family's arguments by name, each group where a sibling takes it (the Gauss-Newton entry takes every boundary group)
+    gn = target is not None
+    args = dict(observed, d=C.byref(desc), T=T, n_dir=K, p=_ptr(p), v=_ptr(v), count=_ptr(count), params=_ptr(params), t_p=_ptr(t_p),
+                t_v=_ptr(t_v), t_params=_ptr(t_params), p_out=_ptr(state[0]), v_out=_ptr(state[1]), t_p_out=_ptr(state[2]),
+                t_v_out=_ptr(state[3]), err=_ptr(err), err_jvp=_ptr(err_jvp), stream=_stream())
+    if gn or form in ("hist", "samples"):
+        args.update(head=_ptr(head), t_head=_ptr(t_head))
+    if gn or form == "lead":
+        args.update(lead=_data(lead), lead_length=_ptr(lead_length), t_lead=_data(t_lead))
+    if gn or form == "ring":
+        args["ring"] = _ptr(ring)
+    if sampled:
+        args.update(probes=_ptr(probes), n_probes=n_probes, every=every)
+    call("dhts_micro_rollout_fwd_jvp" + ("_gn" if gn else "" if form == "hist" else "_" + form), args)
+    if gn:
+        return (state[0], state[1], sse), (state[2], state[3], jtr, jtj)
     return (state[0], state[1], obs[0]), (state[2], state[3], obs[1])
 
 
@@ -2100,8 +2016,8 @@ def micro_step_bwd(desc, tape, g_p, g_v, count=None):
     g_p, g_v = _f32c(g_p, "g_p"), _f32c(g_v, "g_v")
     out = (torch.empty_like(g_p), torch.empty_like(g_v))
     g_virtual = torch.zeros(desc.n_lanes, 2, dtype=torch.float64, device=g_p.device)
-    check(_lib.lib().dhts_micro_step_bwd(C.byref(desc), _ptr(tape), _ptr(count), _ptr(g_p), _ptr(g_v), _ptr(out[0]), _ptr(out[1]),
-                                         _ptr(g_virtual), None, _stream()), "dhts_micro_step_bwd")
+    call("dhts_micro_step_bwd", d=C.byref(desc), tape=_ptr(tape), count=_ptr(count), g_p=_ptr(g_p), g_v=_ptr(g_v), g_p_out=_ptr(out[0]),
+         g_v_out=_ptr(out[1]), g_head=_ptr(g_virtual), err=None, stream=_stream())
     return out[0], out[1], g_virtual
 
 
@@ -2520,8 +2436,9 @@ def arz_interface_batch(inp, dt=0.01, dx=5.0, variant=0):
     f32 = [torch.empty(4, n, dtype=torch.float32, device=dev) for _ in range(5)]
     bad = torch.empty(n, dtype=torch.int32, device=dev)
     speed = torch.empty(2, n, dtype=torch.float64, device=dev)
-    check(_lib.lib().dhts_arz_interface_batch(n, int(variant), _ptr(soa), float(dt), float(dx), _ptr(case), _ptr(q0), _ptr(flux),
-                                              *[_ptr(t) for t in f32], _ptr(bad), _ptr(speed), _stream()), "dhts_arz_interface_batch")
+    call("dhts_arz_interface_batch", n=n, variant=int(variant), dt=float(dt), dx=float(dx), case_ind=_ptr(case), q0=_ptr(q0), flux=_ptr(flux),
+         dL=_ptr(f32[0]), dR=_ptr(f32[1]), fp=_ptr(f32[2]), A=_ptr(f32[3]), B=_ptr(f32[4]), cfl_bad=_ptr(bad), speed=_ptr(speed),
+         stream=_stream(), **{"in": _ptr(soa)})
     m = [t.t().reshape(n, 2, 2) for t in f32]
     return dict(case=case, q0=q0.t().contiguous(), flux=flux.t().contiguous(), dL=m[0], dR=m[1], fp=m[2], A=m[3], B=m[4],
                 cfl_bad=bad.bool(), speed=speed.t().contiguous())
@@ -2540,8 +2457,8 @@ def idm_batch(inp, variant=0):
     col = torch.empty(n, dtype=torch.int32, device=dev)
     acs = torch.empty(2, n, dtype=torch.float64, device=dev)
     clips = torch.empty(2, n, dtype=torch.int32, device=dev)
-    check(_lib.lib().dhts_idm_batch(n, int(variant), _ptr(soa), _ptr(nxt), _ptr(dE), _ptr(dLd), _ptr(col), _ptr(acs), _ptr(clips), _stream()),
-          "dhts_idm_batch")
+    call("dhts_idm_batch", n=n, variant=int(variant), next_pv=_ptr(nxt), dEgo=_ptr(dE), dLeading=_ptr(dLd), collided=_ptr(col),
+         acc_sstar=_ptr(acs), clips=_ptr(clips), stream=_stream(), **{"in": _ptr(soa)})
     return dict(next_p=nxt[0], next_v=nxt[1], dEgo=dE.t().reshape(n, 2, 2), dLeading=dLd.t().reshape(n, 2, 2),
                 collided=col.bool(), acc=acs[0], sstar=acs[1], clipped_acc=clips[0].bool(), clipped_spacing=clips[1].bool())
 
@@ -2556,7 +2473,7 @@ def idm_jac_batch(inp):
     soa = inp.t().contiguous()
     dE = torch.empty(4, n, dtype=torch.float32, device=dev)
     dLd = torch.empty(4, n, dtype=torch.float32, device=dev)
-    check(_lib.lib().dhts_idm_jac_batch(n, _ptr(soa), _ptr(dE), _ptr(dLd), _stream()), "dhts_idm_jac_batch")
+    call("dhts_idm_jac_batch", n=n, dEgo=_ptr(dE), dLeading=_ptr(dLd), stream=_stream(), **{"in": _ptr(soa)})
     return dE.t().reshape(n, 2, 2), dLd.t().reshape(n, 2, 2)
 
 
@@ -2570,7 +2487,7 @@ def idm_param_jac_batch(inp):
     soa = inp.t().contiguous()
     dacc = torch.empty(6, n, dtype=torch.float64, device=dev)
     clips = torch.empty(2, n, dtype=torch.int32, device=dev)
-    check(_lib.lib().dhts_idm_param_jac_batch(n, _ptr(soa), _ptr(dacc), _ptr(clips), _stream()), "dhts_idm_param_jac_batch")
+    call("dhts_idm_param_jac_batch", n=n, dacc=_ptr(dacc), clips=_ptr(clips), stream=_stream(), **{"in": _ptr(soa)})
     return dacc.t().contiguous(), clips[0].bool(), clips[1].bool()
 
 
@@ -2634,8 +2551,7 @@ class NetMacroRollout(torch.autograd.Function):
                 err=None):
         a, d = _net_desc(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length)
         R = d.n_replicas
-        lib = _lib.lib()
-        hist_n, tape_n = lib.dhts_net_macro_hist_bytes(C.byref(d)) // 4, lib.dhts_net_macro_tape_bytes(C.byref(d)) // 4
+        hist_n, tape_n = raw("dhts_net_macro_hist_bytes", d=C.byref(d)) // 4, raw("dhts_net_macro_tape_bytes", d=C.byref(d)) // 4
         if hist_n == 0:
             raise ValueError("unsupported network size (need cells + lanes <= 1024 and lanes <= cells)")
         dev = a.device
@@ -2646,9 +2562,8 @@ class NetMacroRollout(torch.autograd.Function):
         reward = torch.empty(R, dtype=torch.float32, device=dev)
         ws = torch.zeros(R * dev_tables.T * 2 * dev_tables.n_lanes, dtype=torch.float32, device=dev)
         rec = _FaultRecord(dev, check_faults, err)
-        check(lib.dhts_net_macro_rollout_fwd(C.byref(d), C.byref(dev_tables.c), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc),
-                                             _ptr(queue), _ptr(reward), _ptr(ws), _ptr(rec.fwd), _stream()),
-              "dhts_net_macro_rollout_fwd")
+        call("dhts_net_macro_rollout_fwd", d=C.byref(d), t=C.byref(dev_tables.c), action=_ptr(a), hist=_ptr(hist), tape=_ptr(tape), kc=_ptr(kc),
+             queue=_ptr(queue), reward=_ptr(reward), workspace=_ptr(ws), err=_ptr(rec.fwd), stream=_stream())
         rec.after_forward()
         ctx.d, ctx.tables, ctx.rec = d, dev_tables, rec
         ctx.save_for_backward(a, hist, tape, kc, queue, ws)
@@ -2662,9 +2577,8 @@ class NetMacroRollout(torch.autograd.Function):
         g_action = torch.empty_like(a)
         err = ctx.rec.for_reverse(a.device)
         g = g_reward.contiguous().float()          # a named local: the (possibly fresh) tensor must outlive the launch
-        check(_lib.lib().dhts_net_macro_rollout_bwd(C.byref(d), C.byref(ctx.tables.c), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc),
-                                                    _ptr(queue), _ptr(g), _ptr(g_action), _ptr(ws), _ptr(err),
-                                                    _stream()), "dhts_net_macro_rollout_bwd")
+        call("dhts_net_macro_rollout_bwd", d=C.byref(d), t=C.byref(ctx.tables.c), action=_ptr(a), hist=_ptr(hist), tape=_ptr(tape),
+             kc=_ptr(kc), queue=_ptr(queue), g_reward=_ptr(g), g_action=_ptr(g_action), workspace=_ptr(ws), err=_ptr(err), stream=_stream())
         ctx.rec.after_reverse(err)
         return g_action, None, None, None, None, None, None, None, None, None
 
@@ -2686,8 +2600,8 @@ def net_macro_eval(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max, 
     queue = torch.empty(R, dev_tables.T, dev_tables.n_lanes, dtype=torch.float32, device=a.device)
     reward = torch.empty(R, dtype=torch.float32, device=a.device)
     rec = _FaultRecord(a.device, err=err)
-    check(_lib.lib().dhts_net_macro_rollout_eval(C.byref(d), C.byref(dev_tables.c), _ptr(a), _ptr(queue), _ptr(reward), _ptr(rec.fwd),
-                                                 _stream()), "dhts_net_macro_rollout_eval")
+    call("dhts_net_macro_rollout_eval", d=C.byref(d), t=C.byref(dev_tables.c), action=_ptr(a), queue=_ptr(queue), reward=_ptr(reward),
+         err=_ptr(rec.fwd), stream=_stream())
     rec.after_forward()
     return reward, queue
 
@@ -2701,7 +2615,7 @@ def net_macro_plan(n_action, dev_tables, n_inter_sq=1, frames_per_phase=1, dt=1.
     with n_lanes, n_cells, T and n_replica_tables (DeviceNetTables) -- nothing is launched."""
     _, d = _net_desc((1, n_action), dev_tables, n_inter_sq, frames_per_phase, dt, u_max, 0.2, 5.0)
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_net_macro_plan(C.byref(d), C.byref(plan)), "dhts_net_macro_plan")
+    call("dhts_net_macro_plan", d=C.byref(d), plan=C.byref(plan))
     out = dict(zip(_NET_MACRO_PLAN_KEYS, [int(x) for x in plan]))
     out["loss_waves"] = bool(out["loss_waves"])
     return out
@@ -2756,13 +2670,13 @@ class DeviceHybridTables:
 
 def _hybrid_buffers(d, tc, dev):
     """What a fused hybrid rollout writes: (hist, tape, kc, queue [R][T][L], reward [R], counts [R][4], workspace)."""
-    lib, R, T = _lib.lib(), d.n_replicas, d.n_steps
-    ws_n = lib.dhts_net_hybrid_workspace_bytes(C.byref(d), C.byref(tc))
+    R, T = d.n_replicas, d.n_steps
+    ws_n = raw("dhts_net_hybrid_workspace_bytes", d=C.byref(d), t=C.byref(tc))
     if ws_n == 0:
         raise ValueError("unsupported hybrid network size")
     f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
     # (an all-micro network has no cells: the kernels' unconditional prefetches still want something to read)
-    return (f32(max(R * (T + 1) * 4 * d.n_cells, 64)), f32(max(lib.dhts_net_hybrid_tape_bytes(C.byref(d)) // 4, 64)),
+    return (f32(max(R * (T + 1) * 4 * d.n_cells, 64)), f32(max(raw("dhts_net_hybrid_tape_bytes", d=C.byref(d)) // 4, 64)),
             f32(max(R * T * d.n_cells, 64)), f32(R, T, d.n_lanes), f32(R), torch.zeros(R, 4, dtype=torch.int32, device=dev),
             torch.empty(ws_n, dtype=torch.uint8, device=dev))
 
@@ -2779,14 +2693,13 @@ class NetHybridRollout(torch.autograd.Function):
         a, d = _net_desc(action, t, n_inter_sq, frames_per_phase, dt, u_max, static_speed, vehicle_length)
         R = d.n_replicas
         tc = t.c(loss_steps)
-        lib, dev = _lib.lib(), a.device
+        dev = a.device
         hist, tape, kc, queue, reward, counts, ws = _hybrid_buffers(d, tc, dev)
         rec = _FaultRecord(dev, check_faults, err, err_bwd)
 
         def launch(tc):
-            check(lib.dhts_net_hybrid_rollout_fwd(C.byref(d), C.byref(tc), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc), _ptr(queue),
-                                                  _ptr(reward), _ptr(counts), _ptr(ws), _ptr(rec.fwd), _stream()),
-                  "dhts_net_hybrid_rollout_fwd")
+            call("dhts_net_hybrid_rollout_fwd", d=C.byref(d), t=C.byref(tc), action=_ptr(a), hist=_ptr(hist), tape=_ptr(tape), kc=_ptr(kc),
+                 queue=_ptr(queue), reward=_ptr(reward), counts=_ptr(counts), workspace=_ptr(ws), err=_ptr(rec.fwd), stream=_stream())
             rec.after_forward()
         try:
             launch(tc)
@@ -2794,7 +2707,7 @@ class NetHybridRollout(torch.autograd.Function):
             # two replicas per compute unit (more replicas than units) halve the record staging area: the same batch once more
             # with one replica per unit before the caller hears of it (the reverse sweep follows the tables it is given)
             plan = (C.c_int32 * 8)()
-            check(lib.dhts_net_hybrid_plan(C.byref(d), C.byref(tc), plan), "dhts_net_hybrid_plan")
+            call("dhts_net_hybrid_plan", d=C.byref(d), t=C.byref(tc), plan=plan)
             if not plan[0]:
                 raise
             import copy
@@ -2823,9 +2736,8 @@ class NetHybridRollout(torch.autograd.Function):
         g_action = torch.empty_like(a)
         err = ctx.rec.for_reverse(a.device)
         g = g_cut.contiguous().float()             # a named local: the (possibly fresh) tensor must outlive the launch
-        check(_lib.lib().dhts_net_hybrid_rollout_bwd(C.byref(d), C.byref(tc), _ptr(a), _ptr(hist), _ptr(tape), _ptr(kc), _ptr(queue),
-                                                     _ptr(g), _ptr(g_action), _ptr(ws), _ptr(err), _stream()),
-              "dhts_net_hybrid_rollout_bwd")
+        call("dhts_net_hybrid_rollout_bwd", d=C.byref(d), t=C.byref(tc), action=_ptr(a), hist=_ptr(hist), tape=_ptr(tape), kc=_ptr(kc),
+             queue=_ptr(queue), g_reward=_ptr(g), g_action=_ptr(g_action), workspace=_ptr(ws), err=_ptr(err), stream=_stream())
         ctx.rec.after_reverse(err)
         return g_action, None, None, None, None, None, None, None, None, None, None, None
 
@@ -2855,16 +2767,15 @@ class NetHybridStateRollout(torch.autograd.Function):
         if g0 is not None and tuple(g0.shape) != (R, t.n_lanes, 4):
             raise ValueError("ghost0 must be [R][%d lanes][4]" % t.n_lanes)
         tc = t.c(0)
-        lib = _lib.lib()
         hist, tape, kc, queue, reward, counts, ws = _hybrid_buffers(d, tc, dev)
         veh = torch.zeros(R, 128, 4, dtype=torch.float32, device=dev)
         veh[:, :, 0] = -1.0
         events = torch.full((R, 256, 2), -1, dtype=torch.int32, device=dev)
         err = new_error_record(dev)
         io = _lib.HybridStateIO(plain=1 if plain else 0, state0=_ptr(state0), ghost0=_ptr(g0), veh_out=_ptr(veh), events=_ptr(events))
-        check(lib.dhts_net_hybrid_state_rollout_fwd(C.byref(d), C.byref(tc), C.byref(io), _ptr(action), _ptr(hist), _ptr(tape), _ptr(kc),
-                                                    _ptr(queue), _ptr(reward), _ptr(counts), _ptr(ws), _ptr(err), _stream()),
-              "dhts_net_hybrid_state_rollout_fwd")
+        call("dhts_net_hybrid_state_rollout_fwd", d=C.byref(d), t=C.byref(tc), io=C.byref(io), action=_ptr(action), hist=_ptr(hist),
+             tape=_ptr(tape), kc=_ptr(kc), queue=_ptr(queue), reward=_ptr(reward), counts=_ptr(counts), workspace=_ptr(ws), err=_ptr(err),
+             stream=_stream())
         if check_faults:
             raise_on_fault(err)
         fin = hist[:R * (t.T + 1) * 4 * t.n_cells].view(R, t.T + 1, 4, t.n_cells)[:, t.T]
@@ -2892,10 +2803,9 @@ class NetHybridStateRollout(torch.autograd.Function):
         g_state0 = torch.empty(R, 3, Cc, dtype=torch.float32, device=dev)
         err = new_error_record(dev)
         tc = t.c(0)
-        check(_lib.lib().dhts_net_hybrid_state_rollout_bwd(C.byref(d), C.byref(tc), 1 if ctx.plain else 0, _ptr(action), _ptr(hist), _ptr(tape),
-                                                           _ptr(kc), _ptr(queue), _ptr(g_reward), _ptr(g_stateT), _ptr(gv), _ptr(g_action),
-                                                           _ptr(g_state0), _ptr(ws), _ptr(err), _stream()),
-              "dhts_net_hybrid_state_rollout_bwd")
+        call("dhts_net_hybrid_state_rollout_bwd", d=C.byref(d), t=C.byref(tc), plain=1 if ctx.plain else 0, action=_ptr(action),
+             hist=_ptr(hist), tape=_ptr(tape), kc=_ptr(kc), queue=_ptr(queue), g_reward=_ptr(g_reward), g_stateT=_ptr(g_stateT), g_veh=_ptr(gv),
+             g_action=_ptr(g_action), g_state0=_ptr(g_state0), workspace=_ptr(ws), err=_ptr(err), stream=_stream())
         if ctx.check_faults:
             raise_on_fault(err)
         # initial (r, y, u) -> (r0, u0): y0 = r0 (u0 - u_eq(r0)) (FullQ.from_r_u), u0 itself where step 0 read the given speed
@@ -2920,7 +2830,7 @@ def net_hybrid_plan(n_replicas, n_action, dev_tables, n_inter_sq=1, frames_per_p
     _, d = _net_desc((n_replicas, n_action), t, n_inter_sq, frames_per_phase, dt, u_max, 0.2, 5.0)
     tc = t.c(0)
     plan = (C.c_int32 * 8)()
-    check(_lib.lib().dhts_net_hybrid_plan(C.byref(d), C.byref(tc), plan), "dhts_net_hybrid_plan")
+    call("dhts_net_hybrid_plan", d=C.byref(d), t=C.byref(tc), plan=plan)
     keys = ("packed", "block", "stage_h", "lds_fwd", "lds_bwd", "loc_lanes", "max_step_records", "cus")
     out = dict(zip(keys, [int(x) for x in plan]))
     out["packed"] = bool(out["packed"])
@@ -2938,8 +2848,8 @@ def net_hybrid_eval(action, dev_tables, n_inter_sq, frames_per_phase, dt, u_max,
     reward = torch.empty(R, dtype=torch.float32, device=a.device)
     counts = torch.zeros(R, 4, dtype=torch.int32, device=a.device)
     rec = _FaultRecord(a.device, err=err)
-    check(_lib.lib().dhts_net_hybrid_rollout_eval(C.byref(d), C.byref(tc), _ptr(a), _ptr(queue), _ptr(reward), _ptr(counts),
-                                                  _ptr(rec.fwd), _stream()), "dhts_net_hybrid_rollout_eval")
+    call("dhts_net_hybrid_rollout_eval", d=C.byref(d), t=C.byref(tc), action=_ptr(a), queue=_ptr(queue), reward=_ptr(reward),
+         counts=_ptr(counts), err=_ptr(rec.fwd), stream=_stream())
     rec.after_forward()
     return reward, queue, counts
 

@@ -216,9 +216,8 @@ class _NetstepRollout(torch.autograd.Function):
         Rn = max(R, 1)
         a, d = ops._net_desc(action.reshape(Rn, -1), net, sq, F, dt, um, s0, vlen)
         dev = a.device
-        lib = _lib.lib()
         tc = net._c(sq, loss_steps)
-        ws_n = lib.dhts_netstep_workspace_bytes(C.byref(d), C.byref(tc))
+        ws_n = _lib.raw("dhts_netstep_workspace_bytes", d=C.byref(d), t=C.byref(tc))
         if ws_n == 0:
             raise ValueError("dhts_netstep: unsupported network / sizes")
         # the workspace holds what the reverse sweep reads (records, tape, histories): a differentiable rollout owns its own, so that
@@ -235,9 +234,9 @@ class _NetstepRollout(torch.autograd.Function):
         counts = torch.zeros(Rn, 4, dtype=torch.int32, device=dev)
         rec = ops._FaultRecord(dev, check_faults, own=net.err)      # the network's record, zeroed per episode, read in both directions
         net.err.zero_()
-        _lib.check(lib.dhts_netstep_rollout_fwd(C.byref(d), C.byref(tc), 0 if differentiable else 1, ops._ptr(a), ops._ptr(hist), ops._ptr(queue),
-                                                ops._ptr(reward), ops._ptr(counts), ops._ptr(ws), ops._ptr(rec.fwd), ops._stream()),
-                   "dhts_netstep_rollout_fwd")
+        _lib.call("dhts_netstep_rollout_fwd", d=C.byref(d), t=C.byref(tc), hard=0 if differentiable else 1, action=ops._ptr(a),
+                  hist=ops._ptr(hist), queue=ops._ptr(queue), reward=ops._ptr(reward), counts=ops._ptr(counts), workspace=ops._ptr(ws),
+                  err=ops._ptr(rec.fwd), stream=ops._stream())
         rec.after_forward()
         net.last_hist = hist if R else hist[0]
         ctx.d, ctx.tc, ctx.differentiable, ctx.rec = d, tc, differentiable, rec
@@ -259,8 +258,7 @@ class _NetstepRollout(torch.autograd.Function):
         err = ctx.rec.for_reverse(a.device)
         g = g_cut.reshape(-1).contiguous().float()
         g_action = torch.empty_like(a)
-        _lib.check(_lib.lib().dhts_netstep_rollout_bwd(C.byref(ctx.d), C.byref(ctx.tc), ops._ptr(a), ops._ptr(hist), ops._ptr(queue), ops._ptr(g),
-                                                       ops._ptr(g_action), ops._ptr(ws), ops._ptr(err), ops._stream()),
-                   "dhts_netstep_rollout_bwd")
+        _lib.call("dhts_netstep_rollout_bwd", d=C.byref(ctx.d), t=C.byref(ctx.tc), action=ops._ptr(a), hist=ops._ptr(hist), queue=ops._ptr(queue),
+                  g_reward=ops._ptr(g), g_action=ops._ptr(g_action), workspace=ops._ptr(ws), err=ops._ptr(err), stream=ops._stream())
         ctx.rec.after_reverse(err)
         return (g_action.reshape(ctx.shape),) + (None,) * 10
