@@ -612,9 +612,14 @@ __device__ __forceinline__ void arz_interface_fast_pre(double rL, double yL, dou
 //     trivial -- the interfaces a queue always holds -- are overwritten at the end, in a block a wavefront without such a lane skips);
 //   * the cells' float32 state is taken as stored (no float64 copies of values only compared in float32).
 // ls / rs = (r, y, u, u_eq) of the left / right cell, (sL, hL, q0L) = the left cell's CellPre, hR = 0.5 / sqrt(max(r_R, eps)).
-__device__ __forceinline__ void arz_interface_queued(const float4 ls, double sL, double hL, double q0L, const float4 rs, double hR,
-                                                     const IfaceConst &k, Iface &o) {
+// Returns the lane mask of the interfaces that fail the CFL test (o.cfl_bad as a mask: 0 unless the exact tests ran), so that the caller
+// branches on a scalar it already holds.  o.cfl_bad is still filled, as every solver fills an Iface; the pair kernel reads the mask only.  The wavefront may be partly active (the tail of a queue): `act` is its EXEC mask, and the
+// three wave-uniform branches below test combinations of masks that sit in scalar registers -- no boolean is materialised as 0 / 1 in a
+// vector register and compared again.
+__device__ __forceinline__ unsigned long long arz_interface_queued(const float4 ls, double sL, double hL, double q0L, const float4 rs, double hR,
+                                                                   const IfaceConst &k, Iface &o) {
     typedef unsigned long long M;
+    const M act = __builtin_amdgcn_ballot_w64(true);
     const double um = k.um;
     const double rL = (double)ls.x, yL = (double)ls.y, uL = (double)ls.z, qL = (double)ls.w;
     const double yR = (double)rs.y, uR = (double)rs.z;
@@ -645,9 +650,10 @@ __device__ __forceinline__ void arz_interface_queued(const float4 ls, double sL,
     const bool c1 = __builtin_amdgcn_inverse_ballot_w64(midM);
     // ---- CFL (arz_classify_fast): the exact tests only where the cheap bound does not settle it ----
     const double bound = __builtin_fma(0.5, fabs(qL), fabs(uL) + fabs(uR)) + __builtin_fma(0.5 * um, sL, 0.5 * um);
-    const bool sure = (bound < k.cfl_lim) & k.lim_ok;
+    const M sureM = __builtin_amdgcn_ballot_w64(bound < k.cfl_lim) & (k.lim_ok ? ~(M)0 : (M)0);
     o.cfl_bad = false;
-    if (__builtin_amdgcn_ballot_w64(!sure)) {
+    M badM = 0;
+    if (act & ~sureM) {
         asm volatile("" ::: "memory");
         const bool vL = __builtin_amdgcn_inverse_ballot_w64(vacL), vR = __builtin_amdgcn_inverse_ballot_w64(vacR);
         const bool is4 = __builtin_amdgcn_inverse_ballot_w64(b4), is5 = __builtin_amdgcn_inverse_ballot_w64(b5);
@@ -661,6 +667,7 @@ __device__ __forceinline__ void arz_interface_queued(const float4 ls, double sL,
         const bool ok_uL = fabs(uL) < k.cfl_lim, ok_uR = fabs(uR) < k.cfl_lim;
         const bool ok1 = (vL & ok_uL) | (!vL & ((vR & ok_avg) | (!vR & ok_uR)));
         o.cfl_bad = !(ok0 & ok1 & k.lim_ok);
+        badM = __builtin_amdgcn_ballot_w64(o.cfl_bad);
     }
     // ---- Q_M (c1) / Q_C, their Jacobians, the flux and its Jacobian, the products: every lane (arz_mid_state ... arz_mid_products) ----
     MidState m;
@@ -674,7 +681,7 @@ __device__ __forceinline__ void arz_interface_queued(const float4 ls, double sL,
     arz_mid_products_right(fp, dR, B);
     o.B[0] = c1 ? B[0] : 0.f; o.B[1] = c1 ? B[1] : 0.f; o.B[2] = c1 ? B[2] : 0.f; o.B[3] = c1 ? B[3] : 0.f;
     // ---- Q_0 = Q_L where the interface is trivial after all ----
-    if (__builtin_amdgcn_ballot_w64(triv)) {
+    if (trivM & act) {
         asm volatile("" ::: "memory");
         if (triv) {
             const double qc = __builtin_amdgcn_inverse_ballot_w64(vacL) ? k.ueq_2eps : q0L;
@@ -685,6 +692,7 @@ __device__ __forceinline__ void arz_interface_queued(const float4 ls, double sL,
             o.B[0] = o.B[1] = o.B[2] = o.B[3] = 0.f;
         }
     }
+    return badM;
 }
 
 __device__ __forceinline__ void arz_interface(double rL, double yL, double uL, double qL,

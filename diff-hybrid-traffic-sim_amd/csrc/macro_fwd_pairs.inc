@@ -91,22 +91,26 @@ __device__ __forceinline__ bool own_calm(float u, float q, float s32, float half
 }
 // The trivial solve of the interface right of an own cell (arz_is_trivial_fast_v + arz_trivial_fast, operation for operation,
 // with the left cell's quantities taken from OwnPre): is Q_0 = Q_L, its flux, its flux Jacobian.
-// kDense: neither cell of the interface is (nearly) empty: vacL = vacR = false as literals.
+// kDense: neither cell of the interface is (nearly) empty: vacL = vacR = 0 as literals.
+// The case logic runs on LANE MASKS, as phase 2's does (arz_interface_queued): every compare feeds its own ballot and the booleans are
+// combined as 64-bit scalars -- held as bools the compiler materialises them as 0 / 1 in vector registers and compares them again
+// (five vector instructions per interface).  Called by whole wavefronts only (EXEC = all ones: ~mask needs no masking).
+typedef unsigned long long LaneMask;
 template <bool kDense>
-__device__ __forceinline__ bool own_iface(double rd, double yd, float u32, double ud, const OwnPre &o, bool vacL_, bool vacR_, float uR32,
-                                          double uRd, const IfaceConst &k, double &Fr, double &Fy, TapeFp &fp) {
-    const bool vacL = kDense ? false : vacL_, vacR = kDense ? false : vacR_;
+__device__ __forceinline__ LaneMask own_iface(double rd, double yd, float u32, double ud, const OwnPre &o, LaneMask vacL_, LaneMask vacR_,
+                                              float uR32, double uRd, const IfaceConst &k, double &Fr, double &Fy, TapeFp &fp) {
+    const LaneMask vacL = kDense ? 0 : vacL_, vacR = kDense ? 0 : vacR_;
     const double ueqp = -k.um * o.h;
     const double dU = ud - uRd;
-    const bool same = fabs(dU) < kEps;
-    const bool b4 = !(vacL | vacR | same) & (u32 > uR32);
+    const LaneMask same = __builtin_amdgcn_ballot_w64(fabs(dU) < kEps);
+    const LaneMask b4 = ~(vacL | vacR | same) & __builtin_amdgcn_ballot_w64(u32 > uR32);
     const double bm = __builtin_fma(dU, k.inv_um, o.s);
     const double rm = bm * bm;
     const double l0l = __builtin_fma(rd, ueqp, ud);
     const double diff = __builtin_fma(rm, uRd, -(rd * ud));
-    const bool zero0 = vacL | (same & !vacR);
-    const bool triv = zero0 | (b4 & (diff >= 0.0)) | (!b4 & (l0l >= 0.0));
-    const double qc = vacL ? k.ueq_2eps : o.q0;
+    const LaneMask zero0 = vacL | (same & ~vacR);
+    const LaneMask triv = zero0 | (b4 & __builtin_amdgcn_ballot_w64(diff >= 0.0)) | (~b4 & __builtin_amdgcn_ballot_w64(l0l >= 0.0));
+    const double qc = (!kDense && __builtin_amdgcn_inverse_ballot_w64(vacL)) ? k.ueq_2eps : o.q0;
     const double u0 = __builtin_fma(yd, o.inv, qc);
     Fr = rd * u0;
     Fy = yd * u0;
@@ -134,7 +138,7 @@ __device__ long long dhts_fwd_clock[2][16][2];      // [kernel: 0 = lane-group, 
 struct PairOut {
     double Fr1, Fy1, Fr2, Fy2;
     TapeFp fp1, fp2;
-    bool easy1, triv2;
+    LaneMask easy1, triv2;      // lane masks: interface 2m + 1 / 2m + 2 is trivial and inside the cheap CFL bound
 };
 template <bool kDense, bool kUpd, bool kSolve>
 __device__ __forceinline__ void pair_phase1(float ra, float ya, float rb, float yb, double rda, double yda, double rdb, double ydb,
@@ -152,10 +156,11 @@ __device__ __forceinline__ void pair_phase1(float ra, float ya, float rb, float 
         // of the cell right of this thread's second cell (the next thread's first): its speed by a DPP wave shift, its flags as the
         // wavefront's lane masks moved down by one (lane 63 gets nothing useful: that interface is queued)
         const float un = take_right(ua, ua);
-        const bool vac_a = ra <= kEpsF, vac_b = rb <= kEpsF;     // r < 1e-5 (double) for a float32 r
-        const bool calm_a = own_calm(ua, qa, A.s32, half_um, calm_thr), calm_b = own_calm(ub, qb, B.s32, half_um, calm_thr);
-        const bool vac_n = kDense ? false : __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(vac_a) >> 1);
-        const bool calm_n = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(calm_a) >> 1);
+        const LaneMask vac_a = kDense ? 0 : __builtin_amdgcn_ballot_w64(ra <= kEpsF);     // r < 1e-5 (double) for a float32 r
+        const LaneMask vac_b = kDense ? 0 : __builtin_amdgcn_ballot_w64(rb <= kEpsF);
+        const LaneMask calm_a = __builtin_amdgcn_ballot_w64(own_calm(ua, qa, A.s32, half_um, calm_thr));
+        const LaneMask calm_b = __builtin_amdgcn_ballot_w64(own_calm(ub, qb, B.s32, half_um, calm_thr));
+        const LaneMask vac_n = vac_a >> 1, calm_n = calm_a >> 1;
         const double uad = (double)ua, ubd = (double)ub, und = (double)un;
         o.easy1 = own_iface<kDense>(rda, yda, ua, uad, A, vac_a, vac_b, ub, ubd, kc, o.Fr1, o.Fy1, o.fp1) & calm_a & calm_b;
         o.triv2 = own_iface<kDense>(rdb, ydb, ub, ubd, B, vac_b, vac_n, un, und, kc, o.Fr2, o.Fy2, o.fp2) & calm_b & calm_n;
@@ -247,10 +252,10 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
     const double c = dt / dx;
     int fault_step = -1, fault_index = 0, fault_lane = 0;
     const float half_um = 0.5f * umf, calm_thr = own_calm_thr(kc);
-    const bool last_t = t == 63;                     // this thread's second interface is one of the queue's standing entries
     const bool young = rotate != 0 && blockIdx.x >= (gridDim.x >> 1);      // (DHTS_OPT_MACRO_FWD_ROTATE: the rotation is for speed only)
     float4 *tp_pair = kTape ? tape + (size_t)(kG * blockIdx.x) * geo.row_f4 : nullptr;     // the group's first row of the step
     const size_t tp_stride = (size_t)L * geo.row_f4;
+    const int row_span = (int)(16 * (size_t)kG * geo.row_f4);      // bytes of the group's rows of a step: what the step's buffer descriptor covers
     // the thread's two S slots as byte offsets from the group's first row (interface N has none: that thread's second entry
     // goes onto its first slot and is overwritten)
     const unsigned ts_off1 = (unsigned)(16 * (size_t)sub * geo.row_f4) + 12u * (unsigned)(2 * m + 1);
@@ -260,8 +265,10 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
     const int s2 = tid & (kG - 1), k2 = tid / kG;
     int *q2 = region_q(s2);
     const int *cnt2p = region_cnt(s2);
-    const CellRec *CR2 = region_cr(s2);
-    double2 *FX2 = region_fxe(s2);
+    typedef __attribute__((address_space(3))) char LdsByte;      // (32-bit pointers: the offsets below stay 32-bit arithmetic)
+    const LdsByte *cr2_lds = (const LdsByte *)region_cr(s2);
+    LdsByte *fx2_lds = (LdsByte *)region_fxe(s2);
+    const unsigned rec_even = (unsigned)sizeof(CellRec) * (unsigned)(H + 1);      // bytes from slot kk to slot H + 1 + kk
     const unsigned offH2 = (unsigned)(16 * ((size_t)s2 * geo.row_f4 + geo.s_f4));
 
 #ifdef DHTS_FWD3_STAMPS
@@ -356,48 +363,62 @@ __global__ __launch_bounds__(1024) void macro_rollout_fwd3_kernel(
             }
             return;
         }
-        const bool easy1 = po.easy1, easy2 = po.triv2 & !last_t;
-        const bool app2 = !(po.triv2 | last_t);             // (lane 63's second interface is a standing entry: never appended)
-        if (easy1) FXo[0] = make_double2(po.Fr1, po.Fy1);
-        if (easy2) FXe[1] = make_double2(po.Fr2, po.Fy2);
+        // (lane masks from here to the barrier: who stores a flux, who appends one entry or two -- scalar logic, the vector side sees
+        // EXEC masks and one select for the atomic's operand.  Lane 63's second interface is a standing entry: never appended.)
+        const LaneMask last_m = 1ull << 63;
+        const LaneMask app1_m = ~po.easy1, app2_m = ~(po.triv2 | last_m);
+        const bool app1 = __builtin_amdgcn_inverse_ballot_w64(app1_m), app2 = __builtin_amdgcn_inverse_ballot_w64(app2_m);
+        if (__builtin_amdgcn_inverse_ballot_w64(po.easy1)) FXo[0] = make_double2(po.Fr1, po.Fy1);
+        if (__builtin_amdgcn_inverse_ballot_w64(po.triv2 & ~last_m)) FXe[1] = make_double2(po.Fr2, po.Fy2);
         // the queue: one LDS atomic per thread that has something to append
-        const int nq = (easy1 ? 0 : 1) + (app2 ? 1 : 0);
+        const int nq = __builtin_amdgcn_inverse_ballot_w64(app1_m & app2_m) ? 2 : 1;      // (where the thread appends at all)
         int kq = 0;
-        if (nq) kq = atomicAdd(cnt, nq);
+        if (__builtin_amdgcn_inverse_ballot_w64(app1_m | app2_m)) kq = atomicAdd(cnt, nq);
+        // The tape row as a buffer: the group's first row of the step is the descriptor's base (scalar), a thread's place in it a 32-bit
+        // offset -- no 64-bit vector add per store; a store past the group's rows would be dropped, not written.
+        const __amdgpu_buffer_rsrc_t trow = __builtin_amdgcn_make_buffer_rsrc(row0, 0, kTape ? row_span : 0, 0x00020000);
         if (kTape) {
-            *reinterpret_cast<TapeFp *>(row0 + ts_off2) = po.fp2;
-            *reinterpret_cast<TapeFp *>(row0 + ts_off1) = po.fp1;
+            __builtin_amdgcn_raw_buffer_store_b96(fp_tape_bits(po.fp2), trow, ts_off2, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b96(fp_tape_bits(po.fp1), trow, ts_off1, 0, 0);
         }
-        if (!easy1) Q[kq] = 2 * m + 1;
-        if (app2) Q[kq + (easy1 ? 0 : 1)] = 2 * m + 2;
+        if (app1) Q[kq] = 2 * m + 1;
+        if (app2) Q[kq + nq - 1] = 2 * m + 2;                  // the thread's last slot: behind its first entry if it appended one
         FWD3_STAMP(0)
         lds_only_barrier();
         FWD3_STAMP(1)
         // ---- phase 2 ----
-        const int qn2 = cnt2p[n & 1];
+        int qn2 = cnt2p[n & 1];
         bool held = false;
         for (int k = k2; ; k += blockDim.x / kG) {
-            const unsigned i = (unsigned)q2[k < N + 2 ? k : 0];       // read beside the count, not behind it
+            unsigned i = (unsigned)q2[k < N + 2 ? k : 0];             // read beside the count, not behind it:
+            asm volatile("" : "+v"(i), "+v"(qn2));                    // (both loads issued, ONE wait; unpinned, the entry's load sinks behind the branch on the count)
             if (!(k < qn2)) break;
             if (!held) { held = true; __builtin_amdgcn_s_setprio(3); }      // the workgroup's critical path
-            const unsigned kk = i >> 1;
-            const bool odd = i & 1u;
-            const CellRec *lf = CR2 + kk + (odd ? 0 : H + 1), *rt = CR2 + kk + (odd ? H + 2 : 0);
+            // The records of interface i = 2 kk + odd: left cell in slot kk (odd) or H + 1 + kk (even), right cell in slot H + 2 + kk (odd)
+            // or kk (even); its flux in slot kk + odd (H + 1).  Formed as 32-bit LDS byte offsets with 24-bit multiply-adds: indexing the
+            // generic pointers costs three 64-bit multiply-adds and a select chain in front of the reads.  __umul24 needs both factors
+            // below 2^24: they are kk <= H, odd <= 1, 48 and 48 (H + 2) -- and H <= 1024, because a lane has N / 128 <= 16 wavefronts under
+            // __launch_bounds__(1024) and its region must fit the 160 KB of LDS (dhts_macro_rollout_plan refuses the kernel otherwise).
+            const unsigned kk = i >> 1, odd = i & 1u;
+            const unsigned rec_kk = __umul24(kk, (unsigned)sizeof(CellRec));
+            const unsigned left_off = rec_kk + rec_even - __umul24(odd, rec_even), right_off = rec_kk + __umul24(odd, rec_even + (unsigned)sizeof(CellRec));
+            const CellRec *lf = (const CellRec *)(cr2_lds + left_off), *rt = (const CellRec *)(cr2_lds + right_off);
             const float4 ls = lf->st, rs = rt->st;
             const double2 lsh = lf->sh;
             Iface f;
-            arz_interface_queued(ls, lsh.x, lsh.y, lf->q0.x, rs, rt->sh.y, kc, f);
-            FX2[kk + (odd ? H + 1 : 0)] = make_double2(f.Fr, f.Fy);
+            const LaneMask bad_m = arz_interface_queued(ls, lsh.x, lsh.y, lf->q0.x, rs, rt->sh.y, kc, f);
+            *(double2 *)(fx2_lds + (16u * kk + __umul24(odd, 16u * (unsigned)(H + 1)))) = make_double2(f.Fr, f.Fy);
             if (kTape) {
-                if (k == 0) *reinterpret_cast<uint2 *>(row0 + offH2) = make_uint2((unsigned)qn2, 0u);
-                *reinterpret_cast<unsigned short *>(row0 + (offH2 + 8u + 2u * (unsigned)k)) = (unsigned short)i;
+                typedef unsigned v2u __attribute__((ext_vector_type(2)));
+                if (k == 0) __builtin_amdgcn_raw_buffer_store_b64(v2u{(unsigned)qn2, 0u}, trow, offH2, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)i, trow, offH2 + 8u + 2u * (unsigned)k, 0, 0);
                 const unsigned offE = offH2 + 16u * (unsigned)geo.h_f4 + 32u * (unsigned)k;
-                *reinterpret_cast<float4 *>(row0 + offE) = make_float4(f.A[0], f.A[1], f.A[2], f.A[3]);
-                *reinterpret_cast<float4 *>(row0 + offE + 16) = make_float4(f.B[0], f.B[1], f.B[2], f.B[3]);
+                __builtin_amdgcn_raw_buffer_store_b128(bits_f4(f.A[0], f.A[1], f.A[2], f.A[3]), trow, offE, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(bits_f4(f.B[0], f.B[1], f.B[2], f.B[3]), trow, offE + 16u, 0, 0);
             }
-            if (__builtin_amdgcn_ballot_w64(f.cfl_bad)) {
+            if (bad_m) {
                 asm volatile("" ::: "memory");
-                if (f.cfl_bad && fault_step < 0) { fault_step = n; fault_index = (int)i; fault_lane = kG * blockIdx.x + s2; }
+                if (__builtin_amdgcn_inverse_ballot_w64(bad_m) && fault_step < 0) { fault_step = n; fault_index = (int)i; fault_lane = kG * blockIdx.x + s2; }
             }
         }
         __builtin_amdgcn_s_setprio(0);

@@ -75,8 +75,12 @@ __device__ __forceinline__ unsigned short *tape_idx(unsigned *hdr, const TapeGeo
 __device__ __forceinline__ const unsigned short *tape_idx(const unsigned *hdr, const TapeGeom &g) { return reinterpret_cast<const unsigned short *>(hdr + 2); }
 struct __attribute__((packed, aligned(4))) TapeFp { float f0, f2, f3; };
 static_assert(sizeof(TapeFp) == 12, "TapeFp layout");
-// (stored member by member -- three dword stores: measured faster in the forward kernel than one global_store_dwordx3 and
-// than three planes, 4.32 against 4.41 and 4.44 ms)
+// (the lane kernels write it member by member through a plain pointer -- measured in round 2 against three planes, 4.32 against
+// 4.44 ms; the pair kernel stores it as ONE 12-byte buffer store through the step's row descriptor: fp_tape_bits below)
+typedef unsigned bits3 __attribute__((ext_vector_type(3)));      // what the 12- and 16-byte buffer loads and stores carry
+typedef unsigned bits4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bits3 fp_tape_bits(const TapeFp &f) { return bits3{__float_as_uint(f.f0), __float_as_uint(f.f2), __float_as_uint(f.f3)}; }
+__device__ __forceinline__ bits4 bits_f4(float a, float b, float c, float d) { return bits4{__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)}; }
 __device__ __forceinline__ float4 tape_trivial_A(const TapeFp &s) { return make_float4(s.f0, 1.f, s.f2, s.f3); }
 
 // ---- detector taps (dhts_macro_rollout_fwd_taps) -------------------------------------------------------------------
@@ -693,8 +697,6 @@ __device__ __forceinline__ void tape_fill_slots(const float4 *row, const TapeGeo
 // stay zero: the edge cells add 0) | float4 XA[2][N + 1], XB[2][N + 1] | u32 STAMP[2][N + 2] | without per-step cotangents:
 // SEntry SB[2][kB / 64 + 1].
 typedef float v2f __attribute__((ext_vector_type(2)));
-typedef unsigned bits3 __attribute__((ext_vector_type(3)));
-typedef unsigned bits4 __attribute__((ext_vector_type(4)));
 struct alignas(16) SEntry { unsigned x, y, z; };      // an S entry in LDS: one 12-byte access at a 16-byte stride
 __device__ __forceinline__ TapeFp tape_fp_bits(bits3 b) { TapeFp f; f.f0 = __uint_as_float(b.x); f.f2 = __uint_as_float(b.y); f.f3 = __uint_as_float(b.z); return f; }
 __device__ __forceinline__ float4 f4_bits(bits4 b) { return make_float4(__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)); }
